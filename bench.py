@@ -6,7 +6,11 @@
   python bench.py --gpus N --steps K --warmup W          (N > 1: starts its own N rank processes — `self_launch` — before anything touches the GPU)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (the same ranks started by the caller; z-slab decomposition)
 
-Prints ONE JSON line on rank 0.  `roofline` is the dominant kernel of the step — the momentum-RHS stencil with the
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`); everything else it can measure or check runs only with `--full`.  `--dump-outputs DIR` writes what the
+timed path returned after its last step (`dump_outputs`; N = 1 only).
+
+With `--full`: `roofline` is the dominant kernel of the step — the momentum-RHS stencil with the
 RK stage combination fused behind it (K1+K6) — timed live with HIP events recorded on the step's own
 stream inside the timed region; its algorithmic bytes per launch are the compulsory reads/writes of each RK stage
 (RK44: 72/104/104/152 B per cell — stages >= 2 read p as well and apply the previous projection in registers).  `roofline_k1` is the plain momentum-RHS stencil (48 B/cell) timed
@@ -166,110 +170,12 @@ def strong_single_gpu(ins, dev, n=512, steps=10, warmup=2):
             "speedup_vs_n1_hint": {"n1_ms_per_step": ms, "speedup": 1.0, "source": "this run (N = 1)"}}
 
 
-def self_launch(args):
-    """`python bench.py --gpus N` without a launcher around it: start the N ranks as CHILD processes (torch.distributed.run, rendezvous on 127.0.0.1, a free
-    port) — this parent never imports torch and never touches the GPU, so nothing is exec'ed from a GPU-initialised process —, relay rank 0's single JSON line and
-    exit non-zero if any rank failed, no line came back or the run exceeded INS_BENCH_LAUNCH_TIMEOUT seconds (default 1500; the whole process group is killed)."""
-    import signal
-    import socket
-    import subprocess
-
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.abspath(__file__),
-           # spelled out (not sys.argv): torch.distributed.run's parser claims abbreviations such as `--n` even behind the script name
-           "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--cells", str(args.n)]
-    if args.no_cpu_baseline:
-        cmd.append("--no-cpu-baseline")
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC only on this pool (RCCL across processes)
-    env["INS_BENCH_SELF_LAUNCHED"] = "1"
-    limit = float(os.environ.get("INS_BENCH_LAUNCH_TIMEOUT", "1500"))
-    proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True, start_new_session=True)
-    try:
-        stdout, _ = proc.communicate(timeout=limit)
-    except subprocess.TimeoutExpired:
-        try:
-            os.killpg(proc.pid, signal.SIGKILL)
-        except ProcessLookupError:
-            pass
-        proc.wait()
-        print(f"bench.py: the {args.gpus} ranks did not finish within {limit:.0f} s; killed", file=sys.stderr)
-        sys.exit(124)
-    line = None
-    for ln in stdout.splitlines():
-        if ln.startswith("{"):
-            try:
-                if "metric" in json.loads(ln):
-                    line = ln
-            except ValueError:
-                pass
-    if proc.returncode != 0 or line is None:
-        sys.stderr.write(stdout)
-        print(f"bench.py: rank launcher exited with {proc.returncode}" + ("" if line else "; no result line from rank 0"), file=sys.stderr)
-        sys.exit(proc.returncode or 1)
-    print(line)
-    sys.exit(0)
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--n", "--cells", dest="n", type=int, default=256, help="cells per direction on one GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    args = ap.parse_args()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        return self_launch(args)  # before torch / the library are imported: the parent stays off the GPU
+def full_measurements(args, ins, dev, n, setup, method, cache, stepper, dt, chained, ms_per_step):
+    """`--full` on one GPU, after the timed region: the stage kernel's roofline from the HIP events recorded inside it, the same K steps as K
+    `timestep_` calls, K1 alone on the final state and at 512^3, and the check that the state is still a valid flow."""
+    import ctypes as C
 
     import torch
-
-    import ins_amd as ins
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if args.gpus != world:
-        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: one rank per GPU")
-    if world > 1:
-        from bench_dist import run_distributed  # z-slab path
-
-        return run_distributed(args, ins)
-    torch.cuda.set_device(local_rank)
-    dev = torch.device("cuda", local_rank)
-
-    n = args.n
-    x = (np.linspace(0.0, 1.0, n + 1),) * 3
-    setup = ins.Setup(x=x, Re=1000.0, device=dev)
-    ps = ins.psolver_spectral(setup)
-    u = ins.velocityfield(setup, tgv3d, 0.0, psolver=ps)
-    method = ins.RKMethods.RK44()
-    cache = ins.ode_method_cache(method, setup, ps)
-    stepper = ins.create_stepper(method, setup=setup, psolver=ps, u=u, t=0.0)
-    dt = 1e-3 if n <= 256 else 2.5e-4  # (--n 512: the strong-scaling box of BASELINE configs[3] as the headline workload, for profiling)
-    # The timed region is the fixed-Δt loop of solve_unsteady (solver.jl:74-83, no processors) = `timesteps_`: K steps in one native call,
-    # u valid before and after; INS_BENCH_SINGLE_STEPS=1 times K calls of `timestep_` instead (u materialised after every step).
-    chained = not os.environ.get("INS_BENCH_SINGLE_STEPS")
-
-    def advance(st, k):
-        if chained:
-            return ins.timesteps_(method, st, dt, k, cache=cache)
-        for _ in range(k):
-            st = ins.timestep_(method, st, dt, cache=cache)
-        return st
-
-    if args.warmup:
-        stepper = advance(stepper, args.warmup)
-    ins._lib.call("ins_rk_profile_enable", cache.handle, 1)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    stepper = advance(stepper, args.steps)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    import ctypes as C
 
     k1_ms, k1_n = C.c_double(), C.c_int64()
     ins._lib.call("ins_rk_profile_read", cache.handle, C.byref(k1_ms), C.byref(k1_n))
@@ -284,9 +190,7 @@ def main():
         torch.cuda.synchronize()
         single_ms = (time.perf_counter() - ts0) * 1e3 / args.steps
 
-    ms_per_step = (t1 - t0) * 1e3 / args.steps
     cells = float(n) ** 3
-    value = cells / (ms_per_step * 1e-3) / 1e6
     k1_avg_ms = k1_ms.value / max(k1_n.value, 1)
     stage_bytes, k4_bytes = stage_bytes_per_cell(method, args.steps, chained)
     fused_bytes_per_cell = float(np.mean(stage_bytes))
@@ -329,23 +233,8 @@ def main():
     energy = ins.total_kinetic_energy(stepper.u, setup)
     assert np.isfinite(energy) and div / n < 1e-10, f"bench state is not a valid flow: div={div}, E={energy}"
 
-    out = {
-        "metric": "M lattice-cell updates/sec (RK4 step incl. Poisson), 3D TGV fp64",
-        "value": value,
-        "unit": "M cell-updates/s",
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
+    return {
         "ms_per_step_single_calls": single_ms,
-        "higher_is_better": True,
-        "scaling": "single",  # one GPU: the N = 1 point of both curves (weak: 256^3 per GPU = this line's value; strong: `strong_512`)
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": f"TaylorGreenVortex3D {n}^3 periodic fp64, RK44 + spectral Poisson, dt={dt:g}, Re=1e3",
-                   "grid": [n, n, n], "decomposition": "single GPU",
-                   "loop": "timesteps_ (K steps, one native call)" if chained else "timestep_ x K"},
         "roofline": {
             "kernel": "k_flux64 FUSE[/CORR] (K1+K6: momentum-RHS stencil + RK stage combination; stages >= 2 also apply "
                       "the previous projection's gradient-subtract in registers)",
@@ -376,12 +265,171 @@ def main():
                            "note": "per cell and step: 4 Poisson solves x (32 + 16 + 16 + 16 + 16) B + the final K4 (64 B, once per call when chained) + the stage kernels"},
         "check": {"max_abs_div_times_dx": div / n, "kinetic_energy": energy},
     }
-    del stepper, cache, u, ps, setup
-    torch.cuda.empty_cache()
-    if not os.environ.get("INS_BENCH_SKIP_STRONG_512"):
-        out["strong_512"] = strong_single_gpu(ins, dev)
-    if not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(n)
+
+
+DUMP_VALUES = 1 << 21  # at most this many values of u go to --dump-outputs (16 MB of float64)
+
+
+def dump_outputs(path, ins, stepper):
+    """What the timed path hands its caller after the last timed step: the stepper's velocity field u (ghost layers included) as `u.npy`
+    (float64, flattened in the field's column-major order) and its time t as `t.npy`.  A field of more than DUMP_VALUES values is written as a
+    fixed sample: the sorted distinct positions among DUMP_VALUES draws of numpy's generator seeded with 0, the same for every run on the same grid."""
+    import torch
+
+    u = stepper.u
+    if u.numel() <= DUMP_VALUES:
+        vals = ins.to_numpy(u).ravel(order="F")
+    else:
+        flat = np.unique(np.random.default_rng(0).integers(0, u.numel(), DUMP_VALUES))
+        idx = tuple(torch.from_numpy(np.ascontiguousarray(i)).to(u.device) for i in np.unravel_index(flat, tuple(u.shape), order="F"))
+        vals = u[idx].cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "u.npy"), np.ascontiguousarray(vals, dtype=np.float64))
+    np.save(os.path.join(path, "t.npy"), np.array([stepper.t], dtype=np.float64))
+
+
+def self_launch(args):
+    """`python bench.py --gpus N` without a launcher around it: start the N ranks as CHILD processes (torch.distributed.run, rendezvous on 127.0.0.1, a free
+    port) — this parent never imports torch and never touches the GPU, so nothing is exec'ed from a GPU-initialised process —, relay rank 0's single JSON line and
+    exit non-zero if any rank failed, no line came back or the run exceeded INS_BENCH_LAUNCH_TIMEOUT seconds (default 1500; the whole process group is killed)."""
+    import signal
+    import socket
+    import subprocess
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.abspath(__file__),
+           # spelled out (not sys.argv): torch.distributed.run's parser claims abbreviations such as `--n` even behind the script name
+           "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--cells", str(args.n)]
+    if args.no_cpu_baseline:
+        cmd.append("--no-cpu-baseline")
+    if args.full:
+        cmd.append("--full")
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC only on this pool (RCCL across processes)
+    env["INS_BENCH_SELF_LAUNCHED"] = "1"
+    limit = float(os.environ.get("INS_BENCH_LAUNCH_TIMEOUT", "1500"))
+    proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True, start_new_session=True)
+    try:
+        stdout, _ = proc.communicate(timeout=limit)
+    except subprocess.TimeoutExpired:
+        try:
+            os.killpg(proc.pid, signal.SIGKILL)
+        except ProcessLookupError:
+            pass
+        proc.wait()
+        print(f"bench.py: the {args.gpus} ranks did not finish within {limit:.0f} s; killed", file=sys.stderr)
+        sys.exit(124)
+    line = None
+    for ln in stdout.splitlines():
+        if ln.startswith("{"):
+            try:
+                if "metric" in json.loads(ln):
+                    line = ln
+            except ValueError:
+                pass
+    if proc.returncode != 0 or line is None:
+        sys.stderr.write(stdout)
+        print(f"bench.py: rank launcher exited with {proc.returncode}" + ("" if line else "; no result line from rank 0"), file=sys.stderr)
+        sys.exit(proc.returncode or 1)
+    print(line)
+    sys.exit(0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--n", "--cells", dest="n", type=int, default=256, help="cells per direction on one GPU")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the roofline figures, single-call timing, K1 at 512^3, the 512^3 strong-scaling leg, the CPU baseline and the state check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed path's result after its last step as DIR/<name>.npy (one GPU only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        return self_launch(args)  # before torch / the library are imported: the parent stays off the GPU
+
+    import torch
+
+    import ins_amd as ins
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.gpus != world:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: one rank per GPU")
+    if world > 1:
+        from bench_dist import run_distributed  # z-slab path
+
+        return run_distributed(args, ins)
+    torch.cuda.set_device(local_rank)
+    dev = torch.device("cuda", local_rank)
+
+    n = args.n
+    x = (np.linspace(0.0, 1.0, n + 1),) * 3
+    setup = ins.Setup(x=x, Re=1000.0, device=dev)
+    ps = ins.psolver_spectral(setup)
+    u = ins.velocityfield(setup, tgv3d, 0.0, psolver=ps)
+    method = ins.RKMethods.RK44()
+    cache = ins.ode_method_cache(method, setup, ps)
+    stepper = ins.create_stepper(method, setup=setup, psolver=ps, u=u, t=0.0)
+    dt = 1e-3 if n <= 256 else 2.5e-4  # (--n 512: the strong-scaling box of BASELINE configs[3] as the headline workload, for profiling)
+    # The timed region is the fixed-Δt loop of solve_unsteady (solver.jl:74-83, no processors) = `timesteps_`: K steps in one native call,
+    # u valid before and after; INS_BENCH_SINGLE_STEPS=1 times K calls of `timestep_` instead (u materialised after every step).
+    chained = not os.environ.get("INS_BENCH_SINGLE_STEPS")
+
+    def advance(st, k):
+        if chained:
+            return ins.timesteps_(method, st, dt, k, cache=cache)
+        for _ in range(k):
+            st = ins.timestep_(method, st, dt, cache=cache)
+        return st
+
+    if args.warmup:
+        stepper = advance(stepper, args.warmup)
+    if args.full:
+        ins._lib.call("ins_rk_profile_enable", cache.handle, 1)  # HIP events around the stage-kernel launches of the timed region (`roofline`)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    stepper = advance(stepper, args.steps)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    ms_per_step = (t1 - t0) * 1e3 / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ins, stepper)
+
+    out = {
+        "metric": "M lattice-cell updates/sec (RK4 step incl. Poisson), 3D TGV fp64",
+        "value": float(n) ** 3 / (ms_per_step * 1e-3) / 1e6,
+        "unit": "M cell-updates/s",
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "single",  # one GPU: the N = 1 point of both curves (weak: 256^3 per GPU = this line's value; strong: `strong_512`)
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"TaylorGreenVortex3D {n}^3 periodic fp64, RK44 + spectral Poisson, dt={dt:g}, Re=1e3",
+                   "grid": [n, n, n], "decomposition": "single GPU",
+                   "loop": "timesteps_ (K steps, one native call)" if chained else "timestep_ x K"},
+    }
+    if args.full:
+        out.update(full_measurements(args, ins, dev, n, setup, method, cache, stepper, dt, chained, ms_per_step))
+        del stepper, cache, u, ps, setup
+        torch.cuda.empty_cache()
+        if not os.environ.get("INS_BENCH_SKIP_STRONG_512"):
+            out["strong_512"] = strong_single_gpu(ins, dev)
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(n)
     print(json.dumps(out))
 
 

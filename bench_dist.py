@@ -52,9 +52,10 @@ def _sync(dev):
         torch.cuda.synchronize()
 
 
-def run_slab(ins, n, dt, steps, warmup, dev, backend, profile=True):
+def run_slab(ins, n, dt, steps, warmup, dev, backend, profile=True, check=True):
     """Warm-up + timed `steps` chained RK44 steps of the TGV on the global box `n`, this rank's z-slab.  Returns (max-over-ranks seconds,
-    diagnostics).  Barrier + device synchronisation on both sides of the timed region."""
+    diagnostics).  Barrier + device synchronisation on both sides of the timed region.  `profile`: the stage-kernel roofline after it;
+    `check`: divergence and finiteness of the final state."""
     world, rank = dist.get_world_size(), dist.get_rank()
     lay = ins.SlabLayout(n, world, rank)
     reh = _rehearsal_kernels()
@@ -103,8 +104,9 @@ def run_slab(ins, n, dt, steps, warmup, dev, backend, profile=True):
         info["nstage"] = sum(1 for _, _, b in prof if b)
         info["cells_rank"] = float(n[0]) * n[1] * lay.nzl
         info["stage_bytes"] = sum(b for _, _, b in prof) * info["cells_rank"]
-    info["div"] = st.max_abs_divergence(u)
-    info["finite"] = bool(torch.isfinite(u).all())
+    if check:
+        info["div"] = st.max_abs_divergence(u)
+        info["finite"] = bool(torch.isfinite(u).all())
     del st, K, u
     if dev.type == "cuda":
         torch.cuda.empty_cache()
@@ -140,12 +142,11 @@ def run_distributed(args, ins):
         n = (args.n, args.n, args.n * world)
     elif args.n != 256:  # --n: cells per direction and GPU (default 256); the weak-scaling boxes keep their aspect
         n = tuple(v * args.n // 256 for v in n)
-    el, info = run_slab(ins, n, 1e-3, args.steps, args.warmup, dev, backend)
-    stage_ms, nstage, cells_rank, stage_bytes, div, finite = (info[k] for k in ("stage_ms", "nstage", "cells_rank", "stage_bytes", "div", "finite"))
-    # strong-scaling leg (north star / BASELINE configs[3]): the SAME 512^3 box on every N, z-slabs of 512/N planes
+    el, info = run_slab(ins, n, 1e-3, args.steps, args.warmup, dev, backend, profile=args.full, check=args.full)
+    # strong-scaling leg (north star / BASELINE configs[3], --full): the SAME 512^3 box on every N, z-slabs of 512/N planes
     strong = None
     n5 = STRONG_GRID if not os.environ.get("INS_BENCH_STRONG_GRID") else tuple(int(v) for v in os.environ["INS_BENCH_STRONG_GRID"].split("x"))
-    if not os.environ.get("INS_BENCH_SKIP_STRONG_512") and n5[2] % world == 0 and n5[1] % world == 0 and n5[2] // world >= 2:
+    if args.full and not os.environ.get("INS_BENCH_SKIP_STRONG_512") and n5[2] % world == 0 and n5[1] % world == 0 and n5[2] // world >= 2:
         ssteps, swarm = max(2, min(args.steps, 10)), min(args.warmup, 2)
         el5, info5 = run_slab(ins, n5, 2.5e-4, ssteps, swarm, dev, backend, profile=False)
         ms5 = el5 * 1e3 / ssteps
@@ -183,16 +184,18 @@ def run_distributed(args, ins):
                        "grid": list(n), "decomposition": f"z-slabs x{world} ({args.n}^3 cells per GPU), RCCL halo planes + "
                                         + ("one all-gather of interface values per solve (distributed tridiagonal z solve)" if info["zsolve"] == "tridiag"
                                            else "all-to-all transposes around the z-FFT")},
-            "roofline": {"kernel": "k_flux64 CORR (slab): momentum-RHS stencil + RK stage combination + in-register pressure correction, per rank (rank 0)",
-                         "bound": "hbm", "achieved": stage_bytes / (stage_ms * 1e-3) / 1e9 if stage_ms > 0 else None, "peak": 8000.0, "unit": "GB/s",
-                         "frac": stage_bytes / (stage_ms * 1e-3) / 1e9 / 8000.0 if stage_ms > 0 else None, "traffic": None,
-                         "bytes_per_cell": stage_bytes / cells_rank / max(nstage, 1), "avg_launch_ms": stage_ms / max(nstage, 1), "launches": nstage,
-                         "note": "algorithmic bytes of the stages measured (2 chained RK44 steps after the timed region) / HIP-event time of their launches "
-                                 "(interior + boundary plane ranges summed per stage); N = 1 has the PMC traffic figure"},
-            "strong_512": strong,
             "rccl_ranks": rccl_ranks,
             "rehearsal": ("CPU stand-in kernels injected by a test (INS_BENCH_REHEARSAL_KERNELS): launch-path check only, the numbers mean nothing" if rehearsal else None),
-            "check": {"max_abs_div_times_dx": div * (1.0 / n[0]), "finite": finite, "backend": backend, "zsolve": info["zsolve"], "kx_chunks": info["kx_chunks"]},
         }
+        if args.full:
+            stage_ms, nstage, cells_rank, stage_bytes, div, finite = (info[k] for k in ("stage_ms", "nstage", "cells_rank", "stage_bytes", "div", "finite"))
+            out["roofline"] = {"kernel": "k_flux64 CORR (slab): momentum-RHS stencil + RK stage combination + in-register pressure correction, per rank (rank 0)",
+                               "bound": "hbm", "achieved": stage_bytes / (stage_ms * 1e-3) / 1e9 if stage_ms > 0 else None, "peak": 8000.0, "unit": "GB/s",
+                               "frac": stage_bytes / (stage_ms * 1e-3) / 1e9 / 8000.0 if stage_ms > 0 else None, "traffic": None,
+                               "bytes_per_cell": stage_bytes / cells_rank / max(nstage, 1), "avg_launch_ms": stage_ms / max(nstage, 1), "launches": nstage,
+                               "note": "algorithmic bytes of the stages measured (2 chained RK44 steps after the timed region) / HIP-event time of their launches "
+                                       "(interior + boundary plane ranges summed per stage); N = 1 has the PMC traffic figure"}
+            out["strong_512"] = strong
+            out["check"] = {"max_abs_div_times_dx": div * (1.0 / n[0]), "finite": finite, "backend": backend, "zsolve": info["zsolve"], "kx_chunks": info["kx_chunks"]}
         print(json.dumps(out))
     dist.destroy_process_group()

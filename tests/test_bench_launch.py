@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -21,7 +23,7 @@ def _env(**kw):
 
 
 def test_bench_gpus2_self_launch_prints_one_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n", "8", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n", "8", "--no-cpu-baseline", "--full"],
                        cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -34,6 +36,26 @@ def test_bench_gpus2_self_launch_prints_one_line():
     assert s["scaling"] == "strong" and s["n_gpus"] == 2 and s["grid"] == [16, 8, 8] and s["planes_per_rank"] == 4
     assert s["ms_per_step"] > 0 and s["value"] > 0 and s["finite"] and "speedup_vs_n1_hint" in s
     assert s["max_abs_div_times_dx"] < 1e-10 and out["check"]["max_abs_div_times_dx"] < 1e-10
+
+
+def test_bench_gpus2_plain_run_prints_only_the_headline():
+    """Without --full the ranks time the steps and nothing else: no stage-kernel roofline, no strong-scaling leg, no state check."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--n", "8"],
+                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["higher_is_better"] is True and out["dtype"] == "f64" and out["unit"] == "M cell-updates/s"
+    assert not {"roofline", "strong_512", "check", "cpu_baseline"} & set(out)
+
+
+@pytest.mark.parametrize("argv,msg", [(["--steps", "0"], "--steps"), (["--gpus", "2", "--dump-outputs", "out"], "--dump-outputs")])
+def test_bench_rejects_bad_arguments(argv, msg):
+    """Refused while parsing, before torch or the library are imported."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and msg in r.stderr
 
 
 def test_bench_self_launch_reports_rank_failure():
@@ -54,7 +76,7 @@ def test_bench_refuses_mismatched_world():
 def test_bench_gpus8_self_launch_runs_eight_ranks():
     """The N = 8 shape of the driver's scaling run (BASELINE configs[3]: 512^3 over 8 z-slabs) on the same launch path with eight gloo ranks and tiny grids:
     the weak box of GLOBAL_GRIDS[8] scaled by --n, the strong leg with two planes per rank."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--n", "8", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--n", "8", "--no-cpu-baseline", "--full"],
                        cwd=ROOT, env=_env(INS_BENCH_STRONG_GRID="16x16x16"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -3,6 +3,6 @@
 cd "$(dirname "$0")/.."
 B='import sys,json; d=json.loads(sys.stdin.readline()); print(d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["roofline_k1"]["avg_launch_ms"])'
 for i in 1 2 3; do
-  echo -n "prev: "; INS_HIP_LIB=$PWD/$1 INS_BENCH_SKIP_K1_512=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline | python -c "$B"
-  echo -n "new : "; INS_BENCH_SKIP_K1_512=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline | python -c "$B"
+  echo -n "prev: "; INS_HIP_LIB=$PWD/$1 INS_BENCH_SKIP_K1_512=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --full | python -c "$B"
+  echo -n "new : "; INS_BENCH_SKIP_K1_512=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --full | python -c "$B"
 done

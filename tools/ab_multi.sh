@@ -5,7 +5,7 @@ B='import sys,json; d=json.loads(sys.stdin.readline()); print(d["ms_per_step"], 
 for i in 1 2 3; do
   for lib in "$@"; do
     echo -n "$lib: "
-    if [ "$lib" = "-" ]; then INS_BENCH_SKIP_K1_512=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline | python -c "$B"
-    else INS_HIP_LIB=$PWD/$lib INS_BENCH_SKIP_K1_512=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline | python -c "$B"; fi
+    if [ "$lib" = "-" ]; then INS_BENCH_SKIP_K1_512=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --full | python -c "$B"
+    else INS_HIP_LIB=$PWD/$lib INS_BENCH_SKIP_K1_512=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --full | python -c "$B"; fi
   done
 done

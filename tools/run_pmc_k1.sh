@@ -9,4 +9,4 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmc_w -o w --output-form
 ls gpurun_out/pmc_f gpurun_out/pmc_w
 python3 tools/k1_lab.py parse 512 gpurun_out/pmc_f/f_counter_collection.csv gpurun_out/pmc_w/w_counter_collection.csv $V > gpurun_out/k1_traffic_512.txt 2>&1
 cat gpurun_out/k1_traffic_512.txt
-python bench.py > gpurun_out/bench2.json 2> gpurun_out/bench2.err; cat gpurun_out/bench2.json
+python bench.py --full

@@ -17,4 +17,4 @@ python3 tools/pmc_traffic.py $O/f256/f_counter_collection.csv $O/w256/w_counter_
 cat $O/pmc_table_512.txt $O/pmc_table_256.txt
 find $O -name "*kernel_stats.csv" | head
 unset INS_BENCH_SKIP_K1_512 INS_BENCH_SKIP_STRONG_512
-python3 bench.py > $O/bench.json 2> $O/bench.err; tail -c 3000 $O/bench.json
+python3 bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 3000 $O/bench.json
