@@ -176,6 +176,30 @@ int ins_poisson_last_info(const ins_poisson_t* ps, int64_t* iterations, double* 
  * leaves it.  Spectral solver: fused divergence*Ω -> FFT -> symbol -> iFFT -> gradient-subtract path. */
 int ins_project_f64(const ins_grid_t* grid, ins_poisson_t* ps, double* u, double* p, void* stream);
 
+/* ---------------------------------------------------------------------------------- pullbacks (reverse mode) */
+/* Each entry is the exact transpose of this library's forward operator on the whole padded array, ghost volumes included
+ * (DESIGN.md "Differentiability"); cotangents use the field layout of the forward.  Gather kernels, no atomics, fp64. */
+/* divergence_adjoint!(ubar, φ, setup)      operators.jl:127-145 (ubar += Dᵀφ over the whole padded array) */
+int ins_divergence_adjoint_f64(const ins_grid_t* grid, const double* phi, double* ubar, void* stream);
+/* pressuregradient_adjoint!(pbar, φ, setup) operators.jl:180-199 (pbar += Gᵀφ).  applypressure!'s pullback in p is −1 times this. */
+int ins_pressuregradient_adjoint_f64(const ins_grid_t* grid, const double* phi, double* pbar, void* stream);
+/* convection_adjoint!(ubar, φbar, u, setup) operators.jl:417-519 (ubar += J(u)ᵀφbar, J the Jacobian of convection! at the ghost-filled u) */
+int ins_convection_adjoint_f64(const ins_grid_t* grid, const double* u, const double* phibar, double* ubar, void* stream);
+/* diffusion_adjoint!(ubar, φbar, setup)    operators.jl:575-616 (ubar += Dfᵀφbar; visc = 1/Re, or 1 for use_viscosity = false) */
+int ins_diffusion_adjoint_f64(const ins_grid_t* grid, double visc, const double* phibar, double* ubar, void* stream);
+/* Pullback of momentum! (fill + convection + diffusion, operators.jl:967-976) at the ghost-filled u: one pass that overwrites
+ * ubar = J(u)ᵀφbar over the whole padded array (accumulate = 0) or adds to it (accumulate != 0).  A body force drops out. */
+int ins_momentum_pullback_f64(const ins_grid_t* grid, double visc, const double* u, const double* phibar, double* ubar, int accumulate, void* stream);
+/* apply_bc_u_pullback!(φbar, t, setup)     boundary_conditions.jl:169-206, 290-516, in place: the transpose of the linear part of
+ * apply_bc_u! (the same for dudt = true and for time-dependent Dirichlet data, which only change the constants).  Directions and sides are
+ * walked in the reverse order of the forward fill. */
+int ins_apply_bc_u_pullback_f64(const ins_grid_t* grid, double* phibar, void* stream);
+/* apply_bc_p_pullback!(φbar, t, setup)     boundary_conditions.jl:208-230, 320-516, in place (reverse order of apply_bc_p!) */
+int ins_apply_bc_p_pullback_f64(const ins_grid_t* grid, double* phibar, void* stream);
+/* Pullback of project (pressure.jl:52-82), in place: φbar ← φbar − Dᵀ·Ω·poisson·bc_pᵀ·Gᵀ·φbar, the Poisson solve being its own
+ * transpose (pressure.jl:15-19).  `pwork`: a scalar field of scratch.  Stream-ordered, like the solve (CG: blocking). */
+int ins_project_pullback_f64(const ins_grid_t* grid, ins_poisson_t* ps, double* phibar, double* pwork, void* stream);
+
 /* ---------------------------------------------------------------------------------- explicit Runge-Kutta */
 /* ode_method_cache(method, setup) + create_stepper     time_stepper_caches.jl:34-49, step_explicit_runge_kutta.jl:1-2.
  * `A` is the SHIFTED nstage x nstage tableau of methods.jl:231-236, row-major; `c` the shifted nodes. */

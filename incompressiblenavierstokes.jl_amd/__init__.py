@@ -19,6 +19,13 @@ from .operators import (
     Qfield_,
     apply_bc_p,
     apply_bc_p_,
+    apply_bc_p_pullback_,
+    apply_bc_u_pullback_,
+    convection_adjoint_,
+    diffusion_adjoint_,
+    divergence_adjoint_,
+    momentum_pullback_,
+    pressuregradient_adjoint_,
     apply_bc_temp,
     apply_bc_temp_,
     applybodyforce,
@@ -77,6 +84,7 @@ from .pressure import (
     pressure,
     project,
     project_,
+    project_pullback_,
     psolver_cg,
     psolver_direct,
     psolver_spectral,
@@ -97,5 +105,6 @@ from .time_steppers import (
     timestep_,
     timesteps_,
 )
+from . import autodiff as ad  # noqa: E402  (torch.autograd Functions over the pullback kernels: ins_amd.ad)
 
 _lib.load()  # fail loudly at import time if libinship.so is absent

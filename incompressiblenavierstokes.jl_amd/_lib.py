@@ -94,6 +94,14 @@ SIGNATURES = {
     "ins_poisson_solve_f64": (C.c_int, [vp, vp, vp]),
     "ins_poisson_last_info": (C.c_int, [vp, C.POINTER(C.c_int64), c_double_p]),
     "ins_project_f64": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ins_divergence_adjoint_f64": (C.c_int, [vp, vp, vp, vp]),
+    "ins_pressuregradient_adjoint_f64": (C.c_int, [vp, vp, vp, vp]),
+    "ins_convection_adjoint_f64": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ins_diffusion_adjoint_f64": (C.c_int, [vp, C.c_double, vp, vp, vp]),
+    "ins_momentum_pullback_f64": (C.c_int, [vp, C.c_double, vp, vp, vp, C.c_int, vp]),
+    "ins_apply_bc_u_pullback_f64": (C.c_int, [vp, vp, vp]),
+    "ins_apply_bc_p_pullback_f64": (C.c_int, [vp, vp, vp]),
+    "ins_project_pullback_f64": (C.c_int, [vp, vp, vp, vp, vp]),
     "ins_rk_create": (C.c_int, [vp, vp, C.c_int, c_double_p, c_double_p, C.POINTER(vp)]),
     "ins_rk_destroy": (C.c_int, [vp]),
     "ins_rk_step_f64": (C.c_int, [vp, C.c_double, vp, C.c_double, C.c_double, C.POINTER(vp), vp]),

@@ -1,0 +1,323 @@
+"""Reverse-mode differentiability (the reference's ChainRules rrules, operators.jl:100-616, boundary_conditions.jl:114-230, pressure.jl:15-19,
+sciml.jl:49-113) as `torch.autograd.Function`s, exported as `ins_amd.ad`.
+
+Every function here has the signature of its allocating twin in `ins_amd` and the same forward result; its backward runs the pullback kernels of
+csrc/ins_adjoint.hip, each the exact transpose of the forward operator on the whole padded array (DESIGN.md "Differentiability").
+`ad.timestep` is the non-mutating Runge-Kutta step of step_explicit_runge_kutta.jl:61-120 built from them, so
+
+    u = ad.timestep(method, stepper, Δt).u
+    loss = (u * u).sum(); loss.backward()          # stepper.u.grad = ∂loss/∂u0
+
+A closure model given as a torch function `m(u, θ)` is added as F + m(u, θ), and its parameters get gradients from torch.
+"""
+import torch
+
+from . import operators as O
+from .pressure import project_, project_pullback_
+from .setup import _fortran_strides, scalarfield, vectorfield
+from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
+
+__all__ = ["apply_bc_u", "apply_bc_p", "scalewithvolume", "divergence", "pressuregradient", "applypressure", "poisson", "convection", "diffusion",
+           "momentum", "project", "right_hand_side", "create_right_hand_side", "timestep"]
+
+
+def _field(setup, x, vector):
+    """`x` itself when it already has the library's field layout, else a copy in that layout (cotangents from torch are often expanded
+    views with zero strides, or permuted the other way)."""
+    g = setup.grid
+    shape = tuple(g.N) + ((g.dimension,) if vector else ())
+    if (x.dtype == torch.float64 and x.device == setup.device and tuple(x.shape) == shape and tuple(x.stride()) == _fortran_strides(shape)):
+        return x
+    return _copy(setup, x, vector)
+
+
+def _saved_field(ctx, setup, u):
+    """The velocity a stencil reads, kept for backward: the input itself goes through save_for_backward, so an in-place change of it
+    before backward() raises instead of giving a wrong gradient; a layout copy is private to the Function."""
+    uf = _field(setup, u, True)
+    if uf is u:
+        ctx.save_for_backward(u)
+        ctx.ucopy = None
+    else:
+        ctx.save_for_backward()
+        ctx.ucopy = uf
+    return uf
+
+
+def _saved(ctx):
+    return ctx.saved_tensors[0] if ctx.ucopy is None else ctx.ucopy
+
+
+def _copy(setup, x, vector):
+    """A fresh field (library layout) holding `x`: the pullbacks work in place on it."""
+    f = vectorfield(setup) if vector else scalarfield(setup)
+    f.copy_(x.detach())
+    return f
+
+
+# ------------------------------------------------------------------------------------ ghost fill
+class _ApplyBCU(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, t, setup, dudt):
+        ctx.setup = setup
+        return O.apply_bc_u_(_copy(setup, u, True), t, setup, dudt=dudt)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return O.apply_bc_u_pullback_(_copy(s, g, True), 0.0, s), None, None, None
+
+
+class _ApplyBCP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, t, setup):
+        ctx.setup = setup
+        return O.apply_bc_p_(_copy(setup, p, False), t, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return O.apply_bc_p_pullback_(_copy(s, g, False), 0.0, s), None, None
+
+
+def apply_bc_u(u, t, setup, dudt=False):
+    """boundary_conditions.jl:114-167 (rrule: apply_bc_u_pullback!)"""
+    return _ApplyBCU.apply(u, t, setup, bool(dudt))
+
+
+def apply_bc_p(p, t, setup):
+    """boundary_conditions.jl:114-206 (rrule: apply_bc_p_pullback!)"""
+    return _ApplyBCP.apply(p, t, setup)
+
+
+# ------------------------------------------------------------------------------------ linear operators
+class _ScaleWithVolume(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, setup):
+        ctx.setup = setup
+        return O.scalewithvolume_(_copy(setup, p, False), setup)
+
+    @staticmethod
+    def backward(ctx, g):  # diagonal over the whole padded array
+        s = ctx.setup
+        return O.scalewithvolume_(_copy(s, g, False), s), None
+
+
+class _Divergence(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup):
+        ctx.setup = setup
+        return O.divergence(_field(setup, u, True), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return O.divergence_adjoint_(vectorfield(s), _field(s, g, False), s), None
+
+
+class _PressureGradient(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, setup):
+        ctx.setup = setup
+        return O.pressuregradient(_field(setup, p, False), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return O.pressuregradient_adjoint_(scalarfield(s), _field(s, g, True), s), None
+
+
+class _ApplyPressure(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, p, setup):
+        ctx.setup = setup
+        return O.applypressure_(_copy(setup, u, True), _field(setup, p, False), setup)
+
+    @staticmethod
+    def backward(ctx, g):  # u − G p: (φ, −Gᵀφ)
+        s = ctx.setup
+        gf = _field(s, g, True)
+        pbar = O.pressuregradient_adjoint_(scalarfield(s), gf, s).neg_()
+        return g, pbar, None
+
+
+class _Poisson(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f, psolver):
+        ctx.psolver = psolver
+        return psolver(_copy(psolver.setup, f, False))
+
+    @staticmethod
+    def backward(ctx, g):  # the solve is symmetric on the padded arrays (pressure.jl:15-19)
+        ps = ctx.psolver
+        return ps(_copy(ps.setup, g, False)), None
+
+
+def scalewithvolume(p, setup):
+    """operators.jl:81-95"""
+    return _ScaleWithVolume.apply(p, setup)
+
+
+def divergence(u, setup):
+    """operators.jl:97-125 (rrule: divergence_adjoint!)"""
+    return _Divergence.apply(u, setup)
+
+
+def pressuregradient(p, setup):
+    """operators.jl:149-178 (rrule: pressuregradient_adjoint!)"""
+    return _PressureGradient.apply(p, setup)
+
+
+def applypressure(u, p, setup):
+    """operators.jl:203-233.  The pullbacks are φ for u and −Gᵀφ for p (not the reference's rrule, which drops the first and flips
+    the sign of the second)."""
+    return _ApplyPressure.apply(u, p, setup)
+
+
+def poisson(psolver, f):
+    """pressure.jl:15-19: the solve is its own pullback."""
+    return _Poisson.apply(f, psolver)
+
+
+# ------------------------------------------------------------------------------------ momentum
+class _Convection(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup):
+        ctx.setup = setup
+        uf = _saved_field(ctx, setup, u)
+        return O.convection(uf, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return O.convection_adjoint_(vectorfield(s), _field(s, g, True), _saved(ctx), s), None
+
+
+class _Diffusion(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup, use_viscosity):
+        ctx.setup, ctx.use_viscosity = setup, use_viscosity
+        return O.diffusion(_field(setup, u, True), setup, use_viscosity)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return O.diffusion_adjoint_(vectorfield(s), _field(s, g, True), s, ctx.use_viscosity), None, None
+
+
+class _Momentum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, t, setup):
+        ctx.setup = setup
+        uf = _saved_field(ctx, setup, u)
+        return O.momentum(uf, None, t, setup)
+
+    @staticmethod
+    def backward(ctx, g):  # the body force is additive: it drops out
+        s = ctx.setup
+        return O.momentum_pullback_(vectorfield(s), _field(s, g, True), _saved(ctx), s), None, None
+
+
+def convection(u, setup):
+    """operators.jl:366-415 (rrule: convection_adjoint!)"""
+    return _Convection.apply(u, setup)
+
+
+def diffusion(u, setup, use_viscosity=True):
+    """operators.jl:521-573 (rrule: diffusion_adjoint!)"""
+    return _Diffusion.apply(u, setup, bool(use_viscosity))
+
+
+def momentum(u, temp, t, setup):
+    """operators.jl:940-976 (convection + diffusion + body force; the pullback is one fused kernel)."""
+    if temp is not None:
+        raise NotImplementedError("the temperature pullbacks are not implemented (the reference marks them @test_broken)")
+    return _Momentum.apply(u, t, setup)
+
+
+# ------------------------------------------------------------------------------------ projection and right-hand side
+class _Project(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup, psolver):
+        ctx.setup, ctx.psolver = setup, psolver
+        return project_(_copy(setup, u, True), setup, psolver, scalarfield(setup))
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return project_pullback_(_copy(s, g, True), s, ctx.psolver, scalarfield(s)), None, None
+
+
+class _RightHandSide(torch.autograd.Function):
+    """project(bc_dudt(momentum(bc(u)))) forward and backward, each as one sequence of native calls on the setup's stream."""
+
+    @staticmethod
+    def forward(ctx, u, t, setup, psolver):
+        ctx.setup, ctx.psolver = setup, psolver
+        tmp = O.apply_bc_u_(_copy(setup, u, True), t, setup)
+        dudt = O.momentum_(vectorfield(setup), tmp, None, t, setup)
+        O.apply_bc_u_(dudt, t, setup, dudt=True)
+        project_(dudt, setup, psolver, scalarfield(setup))
+        ctx.u = tmp
+        return dudt
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        φ = project_pullback_(_copy(s, g, True), s, ctx.psolver, scalarfield(s))
+        O.apply_bc_u_pullback_(φ, 0.0, s, dudt=True)
+        ubar = O.momentum_pullback_(vectorfield(s), φ, ctx.u, s)
+        return O.apply_bc_u_pullback_(ubar, 0.0, s), None, None, None
+
+
+def project(u, setup, psolver):
+    """pressure.jl:52-82: u − G bc_p(poisson(Ω D u)); pullback φ − Dᵀ Ω poisson bc_pᵀ Gᵀ φ in one native sequence."""
+    return _Project.apply(u, setup, psolver)
+
+
+def right_hand_side(u, params, t):
+    """sciml.jl:49-113: du/dt = project(bc(momentum(bc(u)))), `params = (setup, psolver)`."""
+    setup, psolver = params[0], params[1]
+    return _RightHandSide.apply(u, float(t), setup, psolver)
+
+
+def create_right_hand_side(setup, psolver):
+    """sciml.jl:13-19: `right_hand_side(u, param, t)`, differentiable in u."""
+
+    def rhs(u, param, t):
+        return right_hand_side(u, (setup, psolver), t)
+
+    return rhs
+
+
+# ------------------------------------------------------------------------------------ time stepping
+def timestep(method, stepper, Δt, θ=None):
+    """step_explicit_runge_kutta.jl:61-120: one explicit Runge-Kutta step without mutation, differentiable in `stepper.u` and (through a torch
+    closure model `m(u, θ)`) in θ.  The stage combinations are torch arithmetic."""
+    setup, psolver, u, temp, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.temp, stepper.t, stepper.n
+    if temp is not None:
+        raise NotImplementedError("ad.timestep: the temperature equation has no pullback (the reference marks it @test_broken)")
+    m = setup.closure_model
+    if m is not None and getattr(m, "_ins_closure", None) == "smagorinsky" and torch.is_grad_enabled():
+        raise NotImplementedError("ad.timestep: the Smagorinsky closure has no pullback; give the closure as a torch function m(u, θ)")
+    if isinstance(method, LMWray3) and (setup.needs_bc_planes or (setup.bodyforce is not None and not setup.issteadybodyforce)):
+        # the native step runs the low-storage loop then (step_lmwray3.jl), whose ghost fills happen at other times than the ERK form's
+        raise NotImplementedError("ad.timestep: LMWray3 with time-dependent boundary data or body force; use an ExplicitRungeKuttaMethod")
+    erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
+    A, c = erk.A, erk.c
+    tstart, ustart, ku = t, u, []
+    for i in range(len(erk.b)):
+        u = apply_bc_u(u, t, setup)
+        F = momentum(u, None, t, setup)
+        if m is not None:
+            F = F + m(u, θ)
+        ku.append(F)
+        t = tstart + c[i] * Δt
+        u = ustart
+        for j in range(i + 1):
+            if A[i, j] != 0:
+                u = u + (Δt * A[i, j]) * ku[j]
+        u = apply_bc_u(u, t, setup)
+        u = project(u, setup, psolver)
+    u = apply_bc_u(u, t, setup)
+    return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=None, t=t, n=n + 1)

@@ -1,0 +1,562 @@
+// Reverse-mode pullbacks of the step operators (operators.jl:100-616, boundary_conditions.jl:114-230, 290-516,
+// pressure.jl:15-19): each is the exact transpose of THIS library's forward operator on the whole padded array,
+// ghost volumes included (DESIGN.md "Differentiability").
+//
+// Gather form everywhere: one work-item per output volume reads the cotangent stencil around it, so no atomics
+// and every output is written once.  fp64, 2-D and 3-D, any BC mix, uniform and stretched grids; the metric
+// tables and reciprocal conventions are those of the generic forward twins in ins_operators.hip.
+#include "ins_internal.h"
+#include "ins_wave64.h"
+
+namespace {
+
+// x along the 64-lane wavefront (unit-stride rows), 4 rows per block, one z-plane per grid layer: as box_launch in ins_operators.hip.
+inline void box(const GridDev& g, dim3& grid, dim3& block) {
+  block = dim3(64, 4, 1);
+  grid = dim3(cdiv(g.N[0], 64), cdiv(g.N[1], 4), (unsigned)(g.D == 3 ? g.N[2] : 1));
+}
+
+// Volume I holds a degree of freedom of component al in the forward stencils (k_convdiff / k_pressuregradient):
+// inside the 1..N-2 box in every direction and inside Iu[al].  Safe for any I, out-of-array indices included.
+template <int D>
+__device__ __forceinline__ bool dof(const GridDev& g, int al, int i0, int i1, int i2) {
+  const int I[3] = {i0, i1, i2};
+  bool ok = true;
+#pragma unroll
+  for (int b = 0; b < D; ++b) ok = ok && I[b] >= 1 && I[b] <= g.N[b] - 2 && I[b] >= g.iu_lo[al][b] && I[b] < g.iu_hi[al][b];
+  return ok;
+}
+
+template <int D>
+__device__ __forceinline__ bool in_ip(const GridDev& g, int i0, int i1, int i2) {
+  const int I[3] = {i0, i1, i2};
+  bool ok = true;
+#pragma unroll
+  for (int b = 0; b < D; ++b) ok = ok && I[b] >= g.ip_lo[b] && I[b] < g.ip_hi[b];
+  return ok;
+}
+
+// Coordinates of I shifted by s in direction b.
+#define INS_SH(I, b, s) ((I)[0] + ((b) == 0) * (s)), ((I)[1] + ((b) == 1) * (s)), ((I)[2] + ((b) == 2) * (s))
+
+// --------------------------------------------------------------------------------------------
+// divergence_adjoint                                                     operators.jl:127-145
+//   ubar[α][I] += alpha · (φ[I]/Δα[Iα] [I ∈ Ip] − φ[I+eα]/Δα[Iα+1] [I+eα ∈ Ip])   over the whole padded array
+// --------------------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(256) void k_divergence_adjoint(GridDev g, const double* __restrict__ phi, double* __restrict__ ubar, double alpha) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const int j = blockIdx.y * 4 + threadIdx.y;
+  const int k = D == 3 ? (int)blockIdx.z : 0;
+  if (i >= g.N[0] || j >= g.N[1]) return;
+  const int I[3] = {i, j, k};
+  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  const bool here = in_ip<D>(g, i, j, k);
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    double v = 0.0;
+    if (here) v += phi[c] * g.rdx[a][I[a]];
+    if (in_ip<D>(g, INS_SH(I, a, 1))) v -= phi[c + g.sx[a]] * g.rdx[a][I[a] + 1];
+    ubar[a * g.sc + c] += alpha * v;
+  }
+}
+
+// --------------------------------------------------------------------------------------------
+// pressuregradient_adjoint                                               operators.jl:180-199
+//   pbar[I] += Σα (φα[I−eα]/Δuα[Iα−1] [I−eα dof of α] − φα[I]/Δuα[Iα] [I dof of α])
+// --------------------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(256) void k_pressuregradient_adjoint(GridDev g, const double* __restrict__ phi, double* __restrict__ pbar) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const int j = blockIdx.y * 4 + threadIdx.y;
+  const int k = D == 3 ? (int)blockIdx.z : 0;
+  if (i >= g.N[0] || j >= g.N[1]) return;
+  const int I[3] = {i, j, k};
+  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  double v = 0.0;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    const double* pa = phi + a * g.sc;
+    if (dof<D>(g, a, i, j, k)) v -= pa[c] * g.rdxu[a][I[a]];
+    if (dof<D>(g, a, INS_SH(I, a, -1))) v += pa[c - g.sx[a]] * g.rdxu[a][I[a] - 1];
+  }
+  pbar[c] += v;
+}
+
+// --------------------------------------------------------------------------------------------
+// convection / diffusion pullback                               operators.jl:417-519, 575-616
+//   The forward (k_convdiff) adds to a DOF volume c of component α, per direction β,
+//     r(c)·[ ν(mb(c)(u[c+eβ]−u[c]) − ma(c)(u[c]−u[c−eβ])) − (Φ(c) − Φ(c−eβ)) ],
+//     Φ(f) = ½(uα[f]+uα[f+eβ]) · (A₂βα[fα] uβ[f] + A₁βα[fα+1] uβ[f+eα])        (the flux through the upper β-face of f)
+//   with r = 1/Δuβ (α == β) or 1/Δβ.  So ⟨φ, F⟩ = Σ_f ψ(f) Φ(f) + diffusion terms with
+//     ψαβ(f) = −r(f) φα[f] [f dof] + r(f+eβ) φα[f+eβ] [f+eβ dof],
+//   and ubar = J(u)ᵀφ gathers, per output volume x and component γ:
+//     (a) α = γ:  ψγβ(f) · ½(A₂ uβ[f] + A₁ uβ[f+eγ])         for f = x and f = x − eβ
+//     (b) β = γ:  ψαγ(x) · ½(uα[x]+uα[x+eγ]) · A₂γα[xα]    and  ψαγ(x−eα) · ½(uα[x−eα]+uα[x−eα+eγ]) · A₁γα[xα]
+//   (both when α = β = γ: the product rule).  A flux is evaluated only where ψ has a DOF term, i.e. exactly where the
+//   forward evaluated it, so every read stays inside the padded array.
+//   MODE bit0 = convection, bit1 = diffusion.  ACC: ubar += J^T φ, else ubar = J^T φ.
+// --------------------------------------------------------------------------------------------
+template <int D>
+__device__ __forceinline__ double rr(const GridDev& g, int al, int be, int ib) {
+  return (al == be ? g.rdxu[be] : g.rdx[be])[ib];
+}
+
+// ψαβ(f) at f = (f0, f1, f2) (linear index cf); `live` = it has a DOF term
+template <int D>
+__device__ __forceinline__ double psi(const GridDev& g, int al, int be, const int (&F)[3], long long cf, const double* __restrict__ phia,
+                                      bool& live) {
+  const bool d0 = dof<D>(g, al, F[0], F[1], F[2]);
+  const bool d1 = dof<D>(g, al, INS_SH(F, be, 1));
+  live = d0 || d1;
+  double v = 0.0;
+  if (d0) v -= rr<D>(g, al, be, F[be]) * phia[cf];
+  if (d1) v += rr<D>(g, al, be, F[be] + 1) * phia[cf + g.sx[be]];
+  return v;
+}
+
+template <int D, int MODE, bool ACC>
+__global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, double visc, const double* __restrict__ u, const double* __restrict__ phi,
+                                                          double* __restrict__ ubar) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const int j = blockIdx.y * 4 + threadIdx.y;
+  const int k = D == 3 ? (int)blockIdx.z : 0;
+  if (i >= g.N[0] || j >= g.N[1]) return;
+  const int X[3] = {i, j, k};
+  const long long c = i + j * g.sx[1] + k * g.sx[2];
+
+#pragma unroll
+  for (int ga = 0; ga < D; ++ga) {
+    const double* pg = phi + ga * g.sc;
+    double v = 0.0;
+    if (MODE & 2) {
+      const bool dx = dof<D>(g, ga, i, j, k);
+#pragma unroll
+      for (int be = 0; be < D; ++be) {
+        const int ib = X[be];
+        const long long sb = g.sx[be];
+        // ma(i) = mdx[i] | mdxu[i-1],  mb(i) = mdx[i+1] | mdxu[i]   (k_convdiff)
+        if (dx) {
+          const double ma = ga == be ? g.mdx[be][ib] : g.mdxu[be][ib - 1];
+          const double mb = ga == be ? g.mdx[be][ib + 1] : g.mdxu[be][ib];
+          v -= visc * pg[c] * rr<D>(g, ga, be, ib) * (ma + mb);
+        }
+        if (dof<D>(g, ga, INS_SH(X, be, -1))) {
+          const double mb = ga == be ? g.mdx[be][ib] : g.mdxu[be][ib - 1];
+          v += visc * pg[c - sb] * rr<D>(g, ga, be, ib - 1) * mb;
+        }
+        if (dof<D>(g, ga, INS_SH(X, be, 1))) {
+          const double ma = ga == be ? g.mdx[be][ib + 1] : g.mdxu[be][ib];
+          v += visc * pg[c + sb] * rr<D>(g, ga, be, ib + 1) * ma;
+        }
+      }
+    }
+    if (MODE & 1) {
+      const long long sg = g.sx[ga];
+      // (a) α = γ: ∂Φγβ(f)/∂uγ = ½ (A₂βγ[fγ] uβ[f] + A₁βγ[fγ+1] uβ[f+eγ])
+#pragma unroll
+      for (int be = 0; be < D; ++be) {
+        const long long sb = g.sx[be];
+        const double* ub = u + be * g.sc;
+        const double* A1 = g.A1[be][ga];
+        const double* A2 = g.A2[be][ga];
+#pragma unroll
+        for (int sh = 0; sh < 2; ++sh) {  // f = x, x − eβ
+          const int F[3] = {INS_SH(X, be, -sh)};
+          const long long cf = c - sh * sb;
+          bool live;
+          const double w = psi<D>(g, ga, be, F, cf, pg, live);
+          if (live) v += w * 0.5 * (A2[F[ga]] * ub[cf] + A1[F[ga] + 1] * ub[cf + sg]);
+        }
+      }
+      // (b) β = γ: ∂Φαγ(f)/∂uγ[f] = ½(uα[f]+uα[f+eγ]) A₂γα[fα];  ∂Φαγ(f)/∂uγ[f+eα] = ½(uα[f]+uα[f+eγ]) A₁γα[fα+1]
+#pragma unroll
+      for (int al = 0; al < D; ++al) {
+        const long long sa = g.sx[al];
+        const double* ua = u + al * g.sc;
+        const double* pa = phi + al * g.sc;
+        const double* A1 = g.A1[ga][al];
+        const double* A2 = g.A2[ga][al];
+        {
+          bool live;
+          const double w = psi<D>(g, al, ga, X, c, pa, live);
+          if (live) v += w * 0.5 * (ua[c] + ua[c + sg]) * A2[X[al]];
+        }
+        {
+          const int F[3] = {INS_SH(X, al, -1)};
+          const long long cf = c - sa;
+          bool live;
+          const double w = psi<D>(g, al, ga, F, cf, pa, live);
+          if (live) v += w * 0.5 * (ua[cf] + ua[cf + sg]) * A1[X[al]];
+        }
+      }
+    }
+    double* ob = ubar + ga * g.sc + c;
+    *ob = ACC ? *ob + v : v;
+  }
+}
+
+// --------------------------------------------------------------------------------------------
+// apply_bc_u_pullback / apply_bc_p_pullback           boundary_conditions.jl:169-230, 290-516
+//   The exact transpose of k_bc_u / k_bc_p (ins_bc.hip): the forward sweeps β = 0..D-1 and, per line, left side then
+//   right side, each fill a copy (x[i] = x[j]) or a constant; the transpose walks β = D-1..0 and the sides right then
+//   left, turning x[i] = x[j] into (x̄[j] += x̄[i]; x̄[i] = 0) and x[i] = const into x̄[i] = 0.  Time-dependent Dirichlet
+//   planes only change the constant, so the pullback does not read them.
+// --------------------------------------------------------------------------------------------
+__device__ __forceinline__ void move_to(double* __restrict__ x, long long from, long long to) {
+  const double t = x[from];
+  x[from] = 0.0;
+  x[to] += t;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_bc_u_pullback(GridDev g, double* __restrict__ u, int be) {
+  const int o0 = be == 0 ? 1 : 0;
+  const int o1 = be == 2 ? 1 : 2;
+  const int q0 = blockIdx.x * 256 + threadIdx.x;
+  const int q1 = D == 3 ? (int)blockIdx.y : 0;
+  const int al = blockIdx.z;
+  if (q0 >= g.N[o0]) return;
+  const long long base = q0 * g.sx[o0] + (D == 3 ? q1 * g.sx[o1] : 0);
+  const long long sb = g.sx[be];
+  double* ua = u + al * g.sc + base;
+  const int bcl = g.bc[be][0], bcr = g.bc[be][1];
+  if (bcl == INS_BC_PERIODIC) {  // forward: x[ia] = x[ib-1]; x[ib] = x[ia+1]
+    const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
+    move_to(ua, ib * sb, (ia + 1) * sb);
+    move_to(ua, ia * sb, (ib - 1) * sb);
+    return;
+  }
+#pragma unroll
+  for (int side = 1; side >= 0; --side) {
+    const int bc = side ? bcr : bcl;
+    if (bc == INS_BC_HALO) continue;
+    const int i = side ? g.iu_hi[al][be] : g.iu_lo[al][be] - 1;
+    const int jn = side ? i - 1 : i + 1;
+    if (bc == INS_BC_DIRICHLET || (bc == INS_BC_SYMMETRIC && al == be))
+      ua[i * sb] = 0.0;
+    else if (bc == INS_BC_SYMMETRIC || bc == INS_BC_PRESSURE)
+      move_to(ua, i * sb, jn * sb);
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_bc_p_pullback(GridDev g, double* __restrict__ p, int be) {
+  const int o0 = be == 0 ? 1 : 0;
+  const int o1 = be == 2 ? 1 : 2;
+  const int q0 = blockIdx.x * 256 + threadIdx.x;
+  const int q1 = D == 3 ? (int)blockIdx.y : 0;
+  if (q0 >= g.N[o0]) return;
+  double* pl = p + q0 * g.sx[o0] + (D == 3 ? q1 * g.sx[o1] : 0);
+  const long long sb = g.sx[be];
+  const int bcl = g.bc[be][0], bcr = g.bc[be][1];
+  const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
+  if (bcl == INS_BC_PERIODIC) {
+    move_to(pl, ib * sb, (ia + 1) * sb);
+    move_to(pl, ia * sb, (ib - 1) * sb);
+    return;
+  }
+#pragma unroll
+  for (int side = 1; side >= 0; --side) {
+    const int bc = side ? bcr : bcl;
+    const int i = side ? ib : ia;
+    const int jn = side ? i - 1 : i + 1;
+    if (bc == INS_BC_SYMMETRIC)
+      move_to(pl, i * sb, jn * sb);
+    else if (bc == INS_BC_PRESSURE)
+      pl[i * sb] = 0.0;
+  }
+}
+
+#undef INS_SH
+
+// --------------------------------------------------------------------------------------------
+// Tiled fused momentum pullback: uniform, all-periodic 3-D boxes (the k_flux64 idioms)
+//   x along the 64-lane wavefront, 62 output columns per wavefront (lanes 0 and 63 carry the x halos; x neighbours by DPP shifts), one
+//   padded row per wavefront, and a register march in z: each lane holds u and φ for rows y-1..y+1 on planes z-1..z+1 and loads one new
+//   plane per step.  Workgroups are ordered so the 8 XCDs each take a contiguous band of rows (as k_flux64).
+//   On such a box every interior volume is a DOF of every component, so with φ masked to the interior and everything outside the
+//   padded array read as 0, the terms of k_convdiff_adjoint become branch-free: ψαβ(f) = rαβ (φmα[f+eβ] − φmα[f]), and a flux whose
+//   ψ vanishes contributes 0 whatever u it reads.  Same sums as the generic kernel with the metric tables taken as constants
+//   (G->uniform_exact: constant to 4·N·eps), so the two agree to rounding.
+// --------------------------------------------------------------------------------------------
+struct AdjTiledArgs {
+  int N0, N1, N2;
+  int ntx, nty, nzc, zc;
+  long long sy, sz, sc;
+  double r[3][3];     // r[α][β]: 1/Δuβ (α == β) or 1/Δβ
+  double dco[3][3];   // ν · r[γ][β] · (mdx | mdxu)β: diffusion coefficient
+  double a1[3][3], a2[3][3];  // [β][α]: A₁βα, A₂βα
+  const double* u;
+  const double* phi;
+  double* ubar;
+};
+
+constexpr int ADJ_NW = 4;   // wavefronts (rows) per workgroup
+constexpr int ADJ_ZC = 32;  // planes per workgroup
+
+// Component q at this lane's volume + (dx, dy, dz), |d| <= 1: y / z from the register window, x by a DPP shift (all lanes active).
+// Called with indices that are constants after unrolling, so the window stays in registers.
+__device__ __forceinline__ double at(const double (&W)[3][3][3], int q, int dx, int dy, int dz) {
+  const double v = W[q][dy + 1][dz + 1];
+  return dx == 1 ? next_h(v, 0.0) : dx == -1 ? prev_h(v, 0.0) : v;
+}
+
+template <bool ACC>
+__global__ __launch_bounds__(64 * ADJ_NW) void k_momentum_pullback_tiled(AdjTiledArgs a) {
+  const int nty_local = (a.nty + 7) >> 3;
+  int seq = (int)(blockIdx.x >> 3);
+  if (seq >= a.ntx * nty_local * a.nzc) return;
+  const int txi = seq % a.ntx;
+  seq /= a.ntx;
+  const int tyi = (int)(blockIdx.x & 7) * nty_local + seq % nty_local;
+  const int tzi = seq / nty_local;
+  if (tyi >= a.nty) return;
+  const int lane = threadIdx.x;
+  const int y = tyi * ADJ_NW + __builtin_amdgcn_readfirstlane(threadIdx.y);
+  if (y >= a.N1) return;  // whole wavefront
+  const int P = txi * 62 + lane - 1;  // padded column of this lane
+  const bool colin = P >= 0 && P < a.N0;
+  const bool colint = P >= 1 && P <= a.N0 - 2;
+  const int k0 = tzi * a.zc, k1 = min(k0 + a.zc, a.N2);
+
+  double U[3][3][3], F[3][3][3];  // [component][dy + 1][dz + 1] at this lane's column
+  auto load_plane = [&](int slot, int kz) {
+    const bool zin = kz >= 0 && kz < a.N2, zint = kz >= 1 && kz <= a.N2 - 2;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+      const int yy = y + dy - 1;
+      const bool ok = colin && zin && yy >= 0 && yy < a.N1;
+      const bool okp = colint && zint && yy >= 1 && yy <= a.N1 - 2;
+      const long long c = P + yy * a.sy + kz * a.sz;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        U[q][dy][slot] = ok ? a.u[q * a.sc + c] : 0.0;
+        F[q][dy][slot] = okp ? a.phi[q * a.sc + c] : 0.0;
+      }
+    }
+  };
+  load_plane(0, k0 - 1);
+  load_plane(1, k0);
+  for (int k = k0; k < k1; ++k) {
+    load_plane(2, k + 1);
+    double out[3];
+#pragma unroll
+    for (int ga = 0; ga < 3; ++ga) {
+      const int g0 = ga == 0, g1 = ga == 1, g2 = ga == 2;  // e_γ
+      double v = 0.0;
+#pragma unroll
+      for (int be = 0; be < 3; ++be) {
+        const int b0 = be == 0, b1 = be == 1, b2 = be == 2;  // e_β
+        const double f0 = at(F, ga, 0, 0, 0);
+        // diffusion
+        v += a.dco[ga][be] * (at(F, ga, b0, b1, b2) + at(F, ga, -b0, -b1, -b2) - 2.0 * f0);
+        // (a) α = γ, direction β
+        const double rg = a.r[ga][be];
+        const double p0 = rg * (at(F, ga, b0, b1, b2) - f0);
+        const double p1 = rg * (f0 - at(F, ga, -b0, -b1, -b2));
+        v += 0.5 * (p0 * (a.a2[be][ga] * at(U, be, 0, 0, 0) + a.a1[be][ga] * at(U, be, g0, g1, g2)) +
+                    p1 * (a.a2[be][ga] * at(U, be, -b0, -b1, -b2) + a.a1[be][ga] * at(U, be, g0 - b0, g1 - b1, g2 - b2)));
+        // (b) β = γ, component α = be
+        const int al = be;
+        const double fa = at(F, al, 0, 0, 0);
+        const double ra = a.r[al][ga];
+        const double q0 = ra * (at(F, al, g0, g1, g2) - fa);
+        const double q1 = ra * (at(F, al, g0 - b0, g1 - b1, g2 - b2) - at(F, al, -b0, -b1, -b2));
+        v += 0.5 * (q0 * (at(U, al, 0, 0, 0) + at(U, al, g0, g1, g2)) * a.a2[ga][al] +
+                    q1 * (at(U, al, -b0, -b1, -b2) + at(U, al, g0 - b0, g1 - b1, g2 - b2)) * a.a1[ga][al]);
+      }
+      out[ga] = v;
+    }
+    if (lane >= 1 && lane <= 62 && colin) {
+      const long long c = P + y * a.sy + k * a.sz;
+#pragma unroll
+      for (int ga = 0; ga < 3; ++ga) {
+        double* o = a.ubar + ga * a.sc + c;
+        *o = ACC ? *o + out[ga] : out[ga];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy) {
+        U[q][dy][0] = U[q][dy][1];
+        U[q][dy][1] = U[q][dy][2];
+        F[q][dy][0] = F[q][dy][1];
+        F[q][dy][1] = F[q][dy][2];
+      }
+  }
+}
+
+
+template <int MODE, bool ACC>
+int launch_convdiff_adjoint(const ins_grid* G, double visc, const double* u, const double* phi, double* ubar, hipStream_t s) {
+  const GridDev& g = G->g;
+  dim3 grid, block;
+  box(g, grid, block);
+  if (g.D == 2)
+    hipLaunchKernelGGL((k_convdiff_adjoint<2, MODE, ACC>), grid, block, 0, s, g, visc, u, phi, ubar);
+  else
+    hipLaunchKernelGGL((k_convdiff_adjoint<3, MODE, ACC>), grid, block, 0, s, g, visc, u, phi, ubar);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+
+
+bool adj_tiled_supported(const ins_grid* G) {
+  return G->g.D == 3 && G->all_periodic && G->all_dof && G->uniform_exact && !ins_opt(OPT_INS_DISABLE_ADJ_TILED);
+}
+
+int launch_momentum_pullback_tiled(const ins_grid* G, double visc, const double* u, const double* phi, double* ubar, bool acc, hipStream_t s) {
+  const GridDev& g = G->g;
+  const ins_grid_desc_t& d = G->desc;  // host copy of the tables
+  AdjTiledArgs a;
+  a.N0 = g.N[0];
+  a.N1 = g.N[1];
+  a.N2 = g.N[2];
+  a.sy = g.sx[1];
+  a.sz = g.sx[2];
+  a.sc = g.sc;
+  for (int al = 0; al < 3; ++al)
+    for (int be = 0; be < 3; ++be) {
+      const double dxb = d.dx[be][1], dxub = d.dxu[be][1];
+      a.r[al][be] = al == be ? 1.0 / dxub : 1.0 / dxb;
+      const double m = al == be ? (dxb > 2 * INS_EPS ? 1.0 / dxb : 0.0) : (dxub > 2 * INS_EPS ? 1.0 / dxub : 0.0);
+      a.dco[al][be] = visc * a.r[al][be] * m;
+      a.a1[be][al] = d.A1[be][al][2];
+      a.a2[be][al] = d.A2[be][al][1];
+    }
+  a.u = u;
+  a.phi = phi;
+  a.ubar = ubar;
+  a.ntx = (int)cdiv(a.N0, 62);
+  a.nty = (int)cdiv(a.N1, ADJ_NW);
+  a.zc = ADJ_ZC;
+  a.nzc = (int)cdiv(a.N2, ADJ_ZC);
+  const unsigned nb = (unsigned)(8LL * a.ntx * ((a.nty + 7) / 8) * a.nzc);
+  if (acc)
+    hipLaunchKernelGGL(k_momentum_pullback_tiled<true>, dim3(nb), dim3(64, ADJ_NW), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_momentum_pullback_tiled<false>, dim3(nb), dim3(64, ADJ_NW), 0, s, a);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// internal launchers
+// ------------------------------------------------------------------------------------------------
+int ins_k_divergence_adjoint(const ins_grid* G, const double* phi, double* ubar, double alpha, hipStream_t s) {
+  const GridDev& g = G->g;
+  dim3 grid, block;
+  box(g, grid, block);
+  if (g.D == 2)
+    hipLaunchKernelGGL(k_divergence_adjoint<2>, grid, block, 0, s, g, phi, ubar, alpha);
+  else
+    hipLaunchKernelGGL(k_divergence_adjoint<3>, grid, block, 0, s, g, phi, ubar, alpha);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+
+int ins_k_pressuregradient_adjoint(const ins_grid* G, const double* phi, double* pbar, hipStream_t s) {
+  const GridDev& g = G->g;
+  dim3 grid, block;
+  box(g, grid, block);
+  if (g.D == 2)
+    hipLaunchKernelGGL(k_pressuregradient_adjoint<2>, grid, block, 0, s, g, phi, pbar);
+  else
+    hipLaunchKernelGGL(k_pressuregradient_adjoint<3>, grid, block, 0, s, g, phi, pbar);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+
+int ins_k_apply_bc_u_pullback(const ins_grid* G, double* u, hipStream_t s) {
+  const GridDev& g = G->g;
+  for (int be = g.D - 1; be >= 0; --be) {  // reverse of ins_k_apply_bc_u
+    if (g.bc[be][0] == INS_BC_HALO && g.bc[be][1] == INS_BC_HALO) continue;
+    const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
+    dim3 grid(cdiv(g.N[o0], 256), g.D == 3 ? g.N[o1] : 1, g.D);
+    if (g.D == 2)
+      hipLaunchKernelGGL(k_bc_u_pullback<2>, grid, dim3(256), 0, s, g, u, be);
+    else
+      hipLaunchKernelGGL(k_bc_u_pullback<3>, grid, dim3(256), 0, s, g, u, be);
+    INS_LAUNCH_CHECK();
+  }
+  return INS_OK;
+}
+
+int ins_k_apply_bc_p_pullback(const ins_grid* G, double* p, hipStream_t s) {
+  const GridDev& g = G->g;
+  for (int be = g.D - 1; be >= 0; --be) {  // reverse of ins_k_apply_bc_p_fields
+    const int l = g.bc[be][0], r = g.bc[be][1];
+    if ((l == INS_BC_DIRICHLET || l == INS_BC_HALO) && (r == INS_BC_DIRICHLET || r == INS_BC_HALO)) continue;
+    const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
+    dim3 grid(cdiv(g.N[o0], 256), g.D == 3 ? g.N[o1] : 1, 1);
+    if (g.D == 2)
+      hipLaunchKernelGGL(k_bc_p_pullback<2>, grid, dim3(256), 0, s, g, p, be);
+    else
+      hipLaunchKernelGGL(k_bc_p_pullback<3>, grid, dim3(256), 0, s, g, p, be);
+    INS_LAUNCH_CHECK();
+  }
+  return INS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// C ABI
+// ------------------------------------------------------------------------------------------------
+extern "C" int ins_divergence_adjoint_f64(const ins_grid_t* G, const double* phi, double* ubar, void* stream) {
+  INS_REQUIRE(G && phi && ubar, "null argument");
+  return ins_k_divergence_adjoint(G, phi, ubar, 1.0, as_stream(stream));
+}
+
+extern "C" int ins_pressuregradient_adjoint_f64(const ins_grid_t* G, const double* phi, double* pbar, void* stream) {
+  INS_REQUIRE(G && phi && pbar, "null argument");
+  return ins_k_pressuregradient_adjoint(G, phi, pbar, as_stream(stream));
+}
+
+extern "C" int ins_convection_adjoint_f64(const ins_grid_t* G, const double* u, const double* phibar, double* ubar, void* stream) {
+  INS_REQUIRE(G && u && phibar && ubar, "null argument");
+  INS_REQUIRE(ubar != u && ubar != phibar, "convection_adjoint! cannot run in place");
+  return launch_convdiff_adjoint<1, true>(G, 0.0, u, phibar, ubar, as_stream(stream));
+}
+
+extern "C" int ins_diffusion_adjoint_f64(const ins_grid_t* G, double visc, const double* phibar, double* ubar, void* stream) {
+  INS_REQUIRE(G && phibar && ubar, "null argument");
+  INS_REQUIRE(ubar != phibar, "diffusion_adjoint! cannot run in place");
+  return launch_convdiff_adjoint<2, true>(G, visc, nullptr, phibar, ubar, as_stream(stream));
+}
+
+extern "C" int ins_momentum_pullback_f64(const ins_grid_t* G, double visc, const double* u, const double* phibar, double* ubar, int accumulate,
+                                         void* stream) {
+  INS_REQUIRE(G && u && phibar && ubar, "null argument");
+  INS_REQUIRE(ubar != u && ubar != phibar, "momentum pullback cannot run in place");
+  if (adj_tiled_supported(G)) return launch_momentum_pullback_tiled(G, visc, u, phibar, ubar, accumulate != 0, as_stream(stream));
+  if (accumulate) return launch_convdiff_adjoint<3, true>(G, visc, u, phibar, ubar, as_stream(stream));
+  return launch_convdiff_adjoint<3, false>(G, visc, u, phibar, ubar, as_stream(stream));
+}
+
+extern "C" int ins_apply_bc_u_pullback_f64(const ins_grid_t* G, double* phibar, void* stream) {
+  INS_REQUIRE(G && phibar, "null argument");
+  return ins_k_apply_bc_u_pullback(G, phibar, as_stream(stream));
+}
+
+extern "C" int ins_apply_bc_p_pullback_f64(const ins_grid_t* G, double* phibar, void* stream) {
+  INS_REQUIRE(G && phibar, "null argument");
+  return ins_k_apply_bc_p_pullback(G, phibar, as_stream(stream));
+}
+
+// project(u) = u − G·bc_p(poisson(Ω·(D·u)))  =>  φ ← φ − Dᵀ·Ω·poisson·bc_pᵀ·Gᵀ·φ   (the solve is symmetric on the padded arrays).
+// All launches on one stream; `pwork` is a scalar field of scratch.
+extern "C" int ins_project_pullback_f64(const ins_grid_t* G, ins_poisson_t* ps, double* phibar, double* pwork, void* stream) {
+  INS_REQUIRE(G && ps && phibar && pwork, "null argument");
+  INS_REQUIRE(ps->grid == G, "psolver was created for a different grid");
+  INS_REQUIRE(phibar != pwork, "pwork must be its own array");
+  hipStream_t s = as_stream(stream);
+  int rc;
+  INS_HIP_TRY(hipMemsetAsync(pwork, 0, G->ncell * sizeof(double), s));
+  if ((rc = ins_k_pressuregradient_adjoint(G, phibar, pwork, s))) return rc;
+  if ((rc = ins_k_apply_bc_p_pullback(G, pwork, s))) return rc;
+  if ((rc = ins_k_poisson_solve(ps, pwork, s))) return rc;
+  if ((rc = ins_k_scalewithvolume(G, pwork, s))) return rc;
+  return ins_k_divergence_adjoint(G, pwork, phibar, -1.0, s);
+}

@@ -185,6 +185,53 @@ def max_abs_divergence(u, setup):
     return out.value
 
 
+# ------------------------------------------------------------------------------------ pullbacks (reverse mode)
+# Exact transposes of the operators above on the whole padded array (DESIGN.md "Differentiability"); `ad` builds torch.autograd on them.
+def divergence_adjoint_(ubar, φ, setup):
+    """operators.jl:127-145 (adds Dᵀφ to ubar)"""
+    _lib.call("ins_divergence_adjoint_f64", setup.handle, setup.ptr(φ, False), setup.ptr(ubar, True), setup.stream)
+    return ubar
+
+
+def pressuregradient_adjoint_(pbar, φ, setup):
+    """operators.jl:180-199 (adds Gᵀφ to pbar)"""
+    _lib.call("ins_pressuregradient_adjoint_f64", setup.handle, setup.ptr(φ, True), setup.ptr(pbar, False), setup.stream)
+    return pbar
+
+
+def convection_adjoint_(ubar, φbar, u, setup):
+    """operators.jl:417-519 (adds J(u)ᵀφbar to ubar; `u` is the ghost-filled field convection! read)"""
+    _lib.call("ins_convection_adjoint_f64", setup.handle, setup.ptr(u, True), setup.ptr(φbar, True), setup.ptr(ubar, True), setup.stream)
+    return ubar
+
+
+def diffusion_adjoint_(ubar, φbar, setup, use_viscosity=True):
+    """operators.jl:575-616 (adds the transpose of diffusion! applied to φbar to ubar)"""
+    visc = 1.0 / setup.Re if use_viscosity else 1.0
+    _lib.call("ins_diffusion_adjoint_f64", setup.handle, visc, setup.ptr(φbar, True), setup.ptr(ubar, True), setup.stream)
+    return ubar
+
+
+def momentum_pullback_(ubar, φbar, u, setup, accumulate=False):
+    """Pullback of momentum! at the ghost-filled `u` (convection + diffusion in one pass; a body force drops out): ubar = J(u)ᵀφbar,
+    or ubar += J(u)ᵀφbar with `accumulate`."""
+    _lib.call("ins_momentum_pullback_f64", setup.handle, 1.0 / setup.Re, setup.ptr(u, True), setup.ptr(φbar, True), setup.ptr(ubar, True),
+              int(bool(accumulate)), setup.stream)
+    return ubar
+
+
+def apply_bc_u_pullback_(φbar, t, setup, dudt=False):
+    """boundary_conditions.jl:169-206, in place.  Neither `t` nor `dudt` changes the transpose (they only move the constants)."""
+    _lib.call("ins_apply_bc_u_pullback_f64", setup.handle, setup.ptr(φbar, True), setup.stream)
+    return φbar
+
+
+def apply_bc_p_pullback_(φbar, t, setup):
+    """boundary_conditions.jl:208-230, in place."""
+    _lib.call("ins_apply_bc_p_pullback_f64", setup.handle, setup.ptr(φbar, False), setup.stream)
+    return φbar
+
+
 # ------------------------------------------------------------------------------------ body force
 def applybodyforce_(F, u, t, setup):
     """operators.jl:873-897 (adds to F): the stored field when steady, else `bodyforce.(α, xu[α]..., t)` evaluated on the host."""

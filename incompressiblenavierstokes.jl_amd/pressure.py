@@ -214,6 +214,12 @@ def project_(u, setup, psolver, p):
     return u
 
 
+def project_pullback_(φbar, setup, psolver, pwork):
+    """Pullback of project, in place: φbar ← φbar − Dᵀ Ω poisson bc_pᵀ Gᵀ φbar (pressure.jl:15-19, 52-82).  `pwork`: scalar-field scratch."""
+    _lib.call("ins_project_pullback_f64", setup.handle, psolver.handle, setup.ptr(φbar, True), setup.ptr(pwork, False), setup.stream)
+    return φbar
+
+
 def project(u, setup, psolver):
     """pressure.jl:52-66 (allocating twin, operator by operator as the reference)."""
     div = scalewithvolume(divergence(u, setup), setup)

@@ -27,7 +27,8 @@ import IncompressibleNavierStokes:
     timestep!, ode_method_cache, get_cfl_timestep!, kinetic_energy!, total_kinetic_energy,
     ExplicitRungeKuttaMethod, PeriodicBC, DirichletBC, SymmetricBC, PressureBC,
     vorticity!, interpolate_u_p!, interpolate_ω_p!, Qfield!, Dfield!, eig2field!, dissipation_from_strain!,
-    convection_diffusion_temp!, dissipation!, gravity!, smagorinsky_closure
+    convection_diffusion_temp!, dissipation!, gravity!, smagorinsky_closure,
+    divergence_adjoint!, pressuregradient_adjoint!, convection_adjoint!, diffusion_adjoint!, apply_bc_u_pullback!, apply_bc_p_pullback!
 
 const lib = get(ENV, "INSHIP_LIB", "libinship.so")
 const RA = ROCArray{Float64}
@@ -319,6 +320,49 @@ function project!(u::RA, setup; psolver::HipPSolver, p::RA)
     check(ccall((:ins_project_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
                 handle(setup), psolver.h, pointer(u), pointer(p), stream()))
     u
+end
+
+# ---- pullbacks (reverse mode): the exact transposes on the padded arrays that the reference's rrules call (DESIGN.md "Differentiability").
+# Each `*_adjoint!` accumulates into its first argument as the reference's kernels do (operators.jl:127-145, 180-199, 417-519, 575-616).
+function divergence_adjoint!(u::RA, φ::RA, setup)
+    check(ccall((:ins_divergence_adjoint_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), pointer(φ), pointer(u), stream()))
+    u
+end
+function pressuregradient_adjoint!(pbar::RA, φ::RA, setup)
+    check(ccall((:ins_pressuregradient_adjoint_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), pointer(φ), pointer(pbar), stream()))
+    pbar
+end
+function convection_adjoint!(ubar::RA, φbar::RA, u::RA, setup)
+    check(ccall((:ins_convection_adjoint_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), pointer(u), pointer(φbar), pointer(ubar), stream()))
+    ubar
+end
+function diffusion_adjoint!(u::RA, φ::RA, setup; use_viscosity = true)
+    check(ccall((:ins_diffusion_adjoint_f64, lib), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), use_viscosity ? 1 / setup.Re : 1.0, pointer(φ), pointer(u), stream()))
+    u
+end
+# convection + diffusion pullback in one pass (overwrites ubar; accumulate = true adds)
+function momentum_pullback!(ubar::RA, φbar::RA, u::RA, setup; accumulate = false)
+    check(ccall((:ins_momentum_pullback_f64, lib), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Cvoid}),
+                handle(setup), 1 / setup.Re, pointer(u), pointer(φbar), pointer(ubar), Cint(accumulate), stream()))
+    ubar
+end
+function apply_bc_u_pullback!(φbar::RA, t, setup; kwargs...)   # boundary_conditions.jl:169-206 (in place)
+    check(ccall((:ins_apply_bc_u_pullback_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}), handle(setup), pointer(φbar), stream()))
+    φbar
+end
+function apply_bc_p_pullback!(φbar::RA, t, setup; kwargs...)   # boundary_conditions.jl:208-230 (in place)
+    check(ccall((:ins_apply_bc_p_pullback_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}), handle(setup), pointer(φbar), stream()))
+    φbar
+end
+# φbar ← φbar − Dᵀ Ω poisson bc_pᵀ Gᵀ φbar, in place; `p` is scratch
+function project_pullback!(φbar::RA, setup; psolver::HipPSolver, p::RA)
+    check(ccall((:ins_project_pullback_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), psolver.h, pointer(φbar), pointer(p), stream()))
+    φbar
 end
 
 # ---- step-adjacent operators (SURVEY §8f rows 2 and 4): with these methods the reference's own host-driven `timestep!`
