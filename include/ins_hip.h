@@ -200,6 +200,23 @@ int ins_apply_bc_p_pullback_f64(const ins_grid_t* grid, double* phibar, void* st
  * transpose (pressure.jl:15-19).  `pwork`: a scalar field of scratch.  Stream-ordered, like the solve (CG: blocking). */
 int ins_project_pullback_f64(const ins_grid_t* grid, ins_poisson_t* ps, double* phibar, double* pwork, void* stream);
 
+/* ---------------------------------------------------------------------------------- DNS-to-LES filters  (lib/NeuralClosure/src/filter.jl) */
+/* `les` and `dns` are two grids with the same boundary conditions, n_dns = comp·n_les interior volumes in every direction and nested faces
+ * (x_les[i] == x_dns[comp·i]); anything else: INS_ERR_INVALID.  comp >= 1, even or odd.  Fields are the padded arrays of their own grid.
+ * (Φ::FaceAverage)(v, u, setup_les, comp)  filter.jl:26-46: v[I, α], I ∈ Iu[α] of the coarse grid, = unweighted mean of the comp^(D−1) fine
+ * α-faces that tile coarse face I (also on stretched grids, like the reference).  Any BC mix.  Writes Iu[α] only. */
+int ins_filter_face_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, const double* u, double* v, void* stream);
+/* (Φ::VolumeAverage)(v, u, setup_les, comp) filter.jl:82-116: mean over the coarse volume centred on the coarse face (comp + 1 planes along α
+ * for even comp, comp for odd), fine indices wrapped over the fine interior.  All-periodic grids, else INS_ERR_UNSUPPORTED.  Writes Iu[α] only. */
+int ins_filter_volume_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, const double* u, double* v, void* stream);
+/* reconstruct!(u, v, setup_dns, setup_les, comp)  filter.jl:48-80: piecewise linear along α, piecewise constant across.  All-periodic grids,
+ * else INS_ERR_UNSUPPORTED.  The left neighbour is wrapped over the coarse interior; writes the fine interior only. */
+int ins_reconstruct_f64(const ins_grid_t* dns, const ins_grid_t* les, int comp, const double* v, double* u, void* stream);
+/* Exact transposes of the two filters (no reference counterpart): ubar = Φᵀ w over the whole padded fine array (zero where Φ reads nothing),
+ * w read on Iu[α] only.  Gather kernels, no atomics. */
+int ins_filter_face_pullback_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, const double* w, double* ubar, void* stream);
+int ins_filter_volume_pullback_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, const double* w, double* ubar, void* stream);
+
 /* ---------------------------------------------------------------------------------- explicit Runge-Kutta */
 /* ode_method_cache(method, setup) + create_stepper     time_stepper_caches.jl:34-49, step_explicit_runge_kutta.jl:1-2.
  * `A` is the SHIFTED nstage x nstage tableau of methods.jl:231-236, row-major; `c` the shifted nodes. */

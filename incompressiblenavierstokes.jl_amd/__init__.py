@@ -107,4 +107,9 @@ from .time_steppers import (
 )
 from . import autodiff as ad  # noqa: E402  (torch.autograd Functions over the pullback kernels: ins_amd.ad)
 
+from . import neuralclosure  # noqa: E402  (lib/NeuralClosure: filters, filtered-DNS data generation, closures, losses, training)
+from .neuralclosure import (FaceAverage, VolumeAverage, cnn, collocate, create_dataloader_post, create_dataloader_prior,  # noqa: E402
+                            create_io_arrays, create_les_data, create_loss_post, create_loss_prior, create_relerr_post, create_relerr_prior,
+                            decollocate, filtersaver, lesdatagen, reconstruct, reconstruct_, train, wrappedclosure)
+
 _lib.load()  # fail loudly at import time if libinship.so is absent

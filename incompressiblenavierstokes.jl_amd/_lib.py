@@ -102,6 +102,11 @@ SIGNATURES = {
     "ins_apply_bc_u_pullback_f64": (C.c_int, [vp, vp, vp]),
     "ins_apply_bc_p_pullback_f64": (C.c_int, [vp, vp, vp]),
     "ins_project_pullback_f64": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ins_filter_face_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "ins_filter_volume_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "ins_reconstruct_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "ins_filter_face_pullback_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "ins_filter_volume_pullback_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "ins_rk_create": (C.c_int, [vp, vp, C.c_int, c_double_p, c_double_p, C.POINTER(vp)]),
     "ins_rk_destroy": (C.c_int, [vp]),
     "ins_rk_step_f64": (C.c_int, [vp, C.c_double, vp, C.c_double, C.c_double, C.POINTER(vp), vp]),

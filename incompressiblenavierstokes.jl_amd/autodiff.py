@@ -18,7 +18,7 @@ from .setup import _fortran_strides, scalarfield, vectorfield
 from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
 
 __all__ = ["apply_bc_u", "apply_bc_p", "scalewithvolume", "divergence", "pressuregradient", "applypressure", "poisson", "convection", "diffusion",
-           "momentum", "project", "right_hand_side", "create_right_hand_side", "timestep"]
+           "momentum", "project", "right_hand_side", "create_right_hand_side", "timestep", "FaceAverage", "VolumeAverage"]
 
 
 def _field(setup, x, vector):
@@ -288,6 +288,45 @@ def create_right_hand_side(setup, psolver):
         return right_hand_side(u, (setup, psolver), t)
 
     return rhs
+
+
+# ------------------------------------------------------------------------------------ DNS-to-LES filters
+class _Filter(torch.autograd.Function):
+    """`v = Φ(u, setup_les, comp)` (lib/NeuralClosure filter.jl) with the exact transpose as backward (csrc/ins_filter.hip): a loss on
+    filtered quantities of a differentiable DNS step.  `Filter.apply(u, setup_les, comp, setup_dns=None)`."""
+
+    _kind = None
+
+    @classmethod
+    def _filter(cls):
+        from . import neuralclosure as nc
+
+        return nc.FaceAverage() if cls._kind == "face" else nc.VolumeAverage()
+
+    @classmethod
+    def forward(cls, ctx, u, setup_les, comp, setup_dns=None):
+        from .neuralclosure import dns_setup_of
+
+        dns = setup_dns or dns_setup_of(setup_les, int(comp))
+        ctx.les, ctx.dns, ctx.comp = setup_les, dns, int(comp)
+        return cls._filter()(_field(dns, u, True), setup_les, int(comp), setup_dns=dns)
+
+    @classmethod
+    def backward(cls, ctx, g):
+        ubar = cls._filter().pullback_(vectorfield(ctx.dns), _field(ctx.les, g, True), ctx.les, ctx.comp, ctx.dns)
+        return ubar, None, None, None
+
+
+class FaceAverage(_Filter):
+    """filter.jl:26-46"""
+
+    _kind = "face"
+
+
+class VolumeAverage(_Filter):
+    """filter.jl:82-116"""
+
+    _kind = "volume"
 
 
 # ------------------------------------------------------------------------------------ time stepping

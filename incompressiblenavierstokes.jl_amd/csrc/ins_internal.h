@@ -141,7 +141,8 @@ void ins_set_error(const char* fmt, ...);
   X(INS_F32_HIPFFT_PROJECT)      \
   X(INS_F32_SPLIT_GRADIENT)      \
   X(INS_FFT_ALLOW_RESET)         \
-  X(INS_DISABLE_ADJ_TILED)
+  X(INS_DISABLE_ADJ_TILED)     \
+  X(INS_DISABLE_FILTER_TILED)
 #define INS_OPT_ENUM(id) OPT_##id,
 enum InsOptId { INS_OPT_LIST(INS_OPT_ENUM) INS_OPT_COUNT };
 #undef INS_OPT_ENUM

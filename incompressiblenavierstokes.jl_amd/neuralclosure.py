@@ -1,0 +1,447 @@
+"""lib/NeuralClosure of the reference on this library: DNS-to-LES filters (filter.jl), filtered-DNS data generation (data_generation.jl),
+closure wrappers and the CNN (closure.jl, cnn.jl), data loaders, a-priori / a-posteriori losses and the training loop (training.jl).
+Exported as `ins_amd.neuralclosure`; the main names also from `ins_amd`.
+
+The filters run in csrc/ins_filter.hip.  The network is torch (float64): a closure is a callable `m(u, θ)`; for a
+`torch.nn.Module` built by `cnn`, θ is `None` (the module's own parameters, which a `torch.optim` optimiser updates in place) or a
+dict name -> tensor as `torch.func.functional_call` takes it.
+
+Array layouts.  Fields are the library's padded tensors `N + (D,)`.  Training arrays (`create_io_arrays`, `collocate`, `decollocate`, the
+CNN) are `(n_1, …, n_D, D, nsample)`: interior volumes only, component, then sample — the reference's layout; the CNN permutes to torch's
+`(nsample, channel, n_1, …, n_D)` internally.  Trajectories (`filtersaver`) are padded: `N + (D, nt)`.
+
+Out of scope: FNO and group-equivariant layers, the symmetry errors (`rot2stag`), `gaussian_force`, JLD2 files (`filenames` writes `.npz`).
+"""
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import autodiff as ad
+from .initializers import random_field
+from .operators import apply_bc_u_, momentum_
+from .pressure import default_psolver, project_
+from .processors import Observable, processor
+from .setup import Setup, scalarfield, to_numpy, vectorfield
+from .solver import solve_unsteady
+from .time_steppers import RKMethods, create_stepper, ode_method_cache, timestep_
+
+__all__ = ["AbstractFilter", "FaceAverage", "VolumeAverage", "reconstruct", "reconstruct_", "lesdatagen", "filtersaver", "create_les_data",
+           "create_io_arrays", "wrappedclosure", "collocate", "decollocate", "cnn", "create_dataloader_prior", "create_dataloader_post",
+           "create_loss_prior", "create_relerr_prior", "create_loss_post", "create_relerr_post", "train"]
+
+
+# ------------------------------------------------------------------------------------------------ filters (filter.jl)
+def _interior_faces(setup, b):
+    """Face coordinates of direction b without the ghost volumes."""
+    x = np.asarray(setup.grid.x[b])
+    left = 2 if setup.boundary_conditions[b][0].code == _lib.INS_BC_PRESSURE else 1
+    return x[left:-1]
+
+
+def dns_setup_of(setup_les, comp):
+    """The fine grid a filter call refers to when the caller gives none (the reference's filters take `setup_les` only and read sizes off the
+    arrays): every coarse volume split into `comp` equal parts, same boundary conditions.  Cached on `setup_les`."""
+    cache = setup_les.__dict__.setdefault("_dns_setups", {})
+    if comp not in cache:
+        xs = []
+        for b in range(setup_les.grid.dimension):
+            x = _interior_faces(setup_les, b)
+            fine = [x[:-1] + (x[1:] - x[:-1]) * (q / comp) for q in range(comp)]
+            xs.append(np.append(np.stack(fine, axis=1).reshape(-1), x[-1]))
+        cache[comp] = Setup(x=tuple(xs), boundary_conditions=setup_les.boundary_conditions, Re=setup_les.Re, device=setup_les.device)
+    return cache[comp]
+
+
+class AbstractFilter:
+    """Discrete DNS filter (filter.jl:1-15): `Φ(v, u, setup_les, comp)` filters the DNS field `u` into the LES field `v` (only `Iu[α]` is
+    written: ghosts are the caller's `apply_bc_u_`); `Φ(u, setup_les, comp)` allocates `v`.  `setup_dns` names the fine grid; without it
+    the fine grid is `setup_les` subdivided (`dns_setup_of`)."""
+
+    _entry = None
+
+    def __call__(self, *args, setup_dns=None):
+        if len(args) == 3:
+            u, setup_les, comp = args
+            v = vectorfield(setup_les)
+        elif len(args) == 4:
+            v, u, setup_les, comp = args
+        else:
+            raise TypeError("Φ(u, setup_les, comp) or Φ(v, u, setup_les, comp)")
+        dns = setup_dns or dns_setup_of(setup_les, int(comp))
+        _lib.call(f"ins_filter_{self._entry}_f64", setup_les.handle, dns.handle, int(comp), dns.ptr(u, True), setup_les.ptr(v, True), setup_les.stream)
+        return v
+
+    def pullback_(self, ubar, w, setup_les, comp, setup_dns=None):
+        """ubar = Φᵀ w over the whole padded fine array."""
+        dns = setup_dns or dns_setup_of(setup_les, int(comp))
+        _lib.call(f"ins_filter_{self._entry}_pullback_f64", setup_les.handle, dns.handle, int(comp), setup_les.ptr(w, True), dns.ptr(ubar, True),
+                  setup_les.stream)
+        return ubar
+
+    def __repr__(self):
+        return f"{type(self).__name__}()"
+
+
+class FaceAverage(AbstractFilter):
+    """Average fine grid velocity field over coarse volume face (filter.jl:17-46)."""
+
+    _entry = "face"
+
+
+class VolumeAverage(AbstractFilter):
+    """Average fine grid velocity field over coarse volume (filter.jl:20-21, 82-116).  All-periodic grids."""
+
+    _entry = "volume"
+
+
+def reconstruct_(u, v, setup_dns, setup_les, comp):
+    """Reconstruct DNS velocity `u` from LES velocity `v` (filter.jl:48-76): writes the fine interior."""
+    _lib.call("ins_reconstruct_f64", setup_dns.handle, setup_les.handle, int(comp), setup_les.ptr(v, True), setup_dns.ptr(u, True), setup_les.stream)
+    return u
+
+
+def reconstruct(v, setup_dns, setup_les, comp):
+    """filter.jl:78-80"""
+    return reconstruct_(vectorfield(setup_dns), v, setup_dns, setup_les, comp)
+
+
+# ------------------------------------------------------------------------------------------------ data generation (data_generation.jl)
+def lesdatagen(dnsobs, Φ, les, compression, psolver, dns=None):
+    """data_generation.jl:37-60: on every DNS observation `(u, F, t)` store `ū = bc(Φu)` and the commutator error
+    `c = ΦF − project(bc(momentum(ū)))` on the host."""
+    p = scalarfield(les)
+    Φu, FΦ, ΦF = vectorfield(les), vectorfield(les), vectorfield(les)
+    results = dict(u=[], c=[])
+
+    def step(obs):
+        u, F, t = obs["u"], obs["F"], obs["t"]
+        Φ(Φu, u, les, compression, setup_dns=dns)
+        apply_bc_u_(Φu, t, les)
+        Φ(ΦF, F, les, compression, setup_dns=dns)
+        momentum_(FΦ, Φu, None, t, les)
+        apply_bc_u_(FΦ, t, les, dudt=True)
+        project_(FΦ, les, psolver, p)
+        results["u"].append(to_numpy(Φu))
+        results["c"].append(to_numpy(ΦF - FΦ))
+
+    dnsobs.on(step)
+    return results
+
+
+def filtersaver(dns, les, filters, compression, psolver_dns, psolver_les, *, nupdate=1, filenames=None, F=None, p=None):
+    """Save filtered DNS data (data_generation.jl:62-120): a processor that every `nupdate` steps (and for the initial state) forms
+    `F = project(bc(momentum(u)))` on the DNS grid and hands `(u, F, t)` to one `lesdatagen` per (LES grid, filter), LES grid fastest.
+    `finalize` returns one dict `(u, c, t, comptime)` per pair, `u` and `c` stacked along a last axis; `filenames` (one per pair) are written
+    with `np.savez`.  `F` and `p` are scratch on the DNS grid, allocated here unless given; the processor never writes into the state."""
+    les, filters, compression, psolver_les = list(les), list(filters), list(compression), list(psolver_les)
+    if filenames is not None and len(filenames) != len(les) * len(filters):
+        raise ValueError("one file name per (LES grid, filter) pair")
+    F = vectorfield(dns) if F is None else F
+    p = scalarfield(dns) if p is None else p
+
+    def initialize(state):
+        s0 = state.value
+        dnsobs = Observable(dict(u=s0["u"], F=F, t=s0["t"]))
+        data = [lesdatagen(dnsobs, Φ, les[i], compression[i], psolver_les[i], dns) for Φ in filters for i in range(len(les))]
+        results = dict(data=data, t=[], comptime=time.time())
+
+        def step(s):
+            if s["n"] % nupdate != 0:
+                return
+            u, t = s["u"], s["t"]
+            momentum_(F, u, None, t, dns)
+            apply_bc_u_(F, t, dns, dudt=True)
+            project_(F, dns, psolver_dns, p)
+            results["t"].append(t)
+            dnsobs.value = dict(u=u, F=F, t=t)
+
+        state.on(step)
+        step(s0)  # save initial conditions
+        return results
+
+    def finalize(results, state):
+        comptime = time.time() - results["comptime"]
+        out = []
+        for i, d in enumerate(results["data"]):
+            r = dict(u=np.stack(d["u"], axis=-1), c=np.stack(d["c"], axis=-1), t=np.array(results["t"]), comptime=comptime)
+            if filenames is not None:
+                np.savez(filenames[i], **r)
+            out.append(r)
+        return out
+
+    return processor(initialize, finalize, nupdate=nupdate)
+
+
+def create_les_data(*, D, Re, lims, nles, ndns, filters, tburn, tsim, savefreq, Δt=None, method=None, create_psolver=default_psolver, icfunc=None,
+                    processors=None, rng=None, filenames=None, device=None, **kwargs):
+    """Create filtered DNS data (data_generation.jl:125-223): burn-in DNS from `icfunc(setup, psolver, rng)`, then a DNS of length `tsim` whose
+    state is filtered every `savefreq` steps onto every grid of `nles` by every filter.  Returns `filtersaver`'s list."""
+    method = method or RKMethods.RK44()
+    rng = rng if rng is not None else np.random.default_rng()
+    nles = list(nles)
+    compression = [ndns // n for n in nles]
+    if any(c * n != ndns for c, n in zip(compression, nles)):
+        raise ValueError("every nles must divide ndns")
+    dns = Setup(x=tuple(np.linspace(lims[0], lims[1], ndns + 1) for _ in range(D)), Re=Re, device=device, **kwargs)
+    les = [Setup(x=tuple(np.linspace(lims[0], lims[1], n + 1) for _ in range(D)), Re=Re, device=device, **kwargs) for n in nles]
+    psolver = create_psolver(dns)
+    psolver_les = [create_psolver(s) for s in les]
+    if icfunc is None:
+        def icfunc(setup, psolver, rng):
+            return random_field(setup, 0.0, psolver=psolver, seed=int(rng.integers(2**31 - 1)))
+    u = icfunc(dns, psolver, rng)
+    if bool(torch.isnan(u).any()):
+        print("Warning: initial conditions contain NaNs")
+    processors = dict(processors or {})
+    cache = ode_method_cache(method, dns, psolver)
+    if tburn > 0:  # the initial spectrum is artificial: a short simulation makes it realistic
+        (u, _, _), _ = solve_unsteady(setup=dns, ustart=u, docopy=False, tlims=(0.0, tburn), Δt=Δt, method=method, psolver=psolver, cache=cache,
+                                      processors=processors)
+    saver = filtersaver(dns, les, filters, compression, psolver, psolver_les, nupdate=savefreq, filenames=filenames)
+    _, outputs = solve_unsteady(setup=dns, ustart=u, docopy=False, tlims=(0.0, tsim), Δt=Δt, method=method, psolver=psolver, cache=cache,
+                                processors={**processors, "f": saver})
+    return outputs["f"]
+
+
+def create_io_arrays(data, setup):
+    """Create (ū, c) pairs for a-priori training (data_generation.jl:228-252): `data` is a list of trajectories `dict(u, c, t)` on the grid of
+    `setup`; returns `dict(u, c)` of numpy arrays `(n…, D, nsample)` holding `Iu[α]` of every component, trajectories joined along the
+    sample axis."""
+    g = setup.grid
+    D = g.dimension
+    out = {}
+    for key in ("u", "c"):
+        parts = []
+        for traj in data:
+            nt = len(traj["t"])
+            a = np.zeros(tuple(n - 2 for n in g.N) + (D, nt))
+            for α in range(D):
+                sl = tuple(slice(lo, hi) for lo, hi in g.Iu[α])
+                a[..., α, :] = np.asarray(traj[key])[sl + (α, slice(None))]
+            parts.append(a)
+        out[key] = np.concatenate(parts, axis=-1)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ closure.jl, cnn.jl
+def _inside(setup):
+    Iu = setup.grid.Iu
+    if any(I != Iu[0] for I in Iu):
+        raise ValueError("Only periodic grids are supported")
+    return tuple(slice(lo, hi) for lo, hi in Iu[0])
+
+
+def wrappedclosure(m, setup):
+    """Wrap closure model `m(x, θ)` on `(n…, D, nsample)` arrays so that it can be used in the solver (closure.jl:4-17): the interior of the
+    padded field goes in as one sample, the result is padded periodically (ghosts = the opposite interior layer).  Differentiable."""
+    inside = _inside(setup)
+    D = setup.grid.dimension
+
+    def neuralclosure(u, θ):
+        mu = m(u[inside].unsqueeze(-1), θ).squeeze(-1)
+        for d in range(D):
+            mu = torch.cat([mu.narrow(d, mu.shape[d] - 1, 1), mu, mu.narrow(d, 0, 1)], dim=d)
+        return mu
+
+    return neuralclosure
+
+
+def collocate(u):
+    """Interpolate velocity components to volume centers (closure.jl:37-72): `(n…, D, nsample)`, out[i] = (u_α[i] + u_α[i − e_α]) / 2,
+    periodic."""
+    D = u.shape[-2]
+    return torch.stack([(u[..., a, :] + torch.roll(u[..., a, :], 1, dims=a)) / 2 for a in range(D)], dim=-2)
+
+
+def decollocate(u):
+    """Interpolate closure force from volume centers to volume faces (closure.jl:74-108): out[i] = (u_α[i] + u_α[i + e_α]) / 2, periodic."""
+    D = u.shape[-2]
+    return torch.stack([(u[..., a, :] + torch.roll(u[..., a, :], -1, dims=a)) / 2 for a in range(D)], dim=-2)
+
+
+class CNN(torch.nn.Module):
+    """collocate → circular padding by Σ radii → convolutions (kernel 2r+1, no further padding) → decollocate, float64 (cnn.jl)."""
+
+    def __init__(self, D, radii, channels, activations, use_bias, generator=None):
+        super().__init__()
+        if channels[-1] != D:
+            raise ValueError("the last layer must have D channels (one force field per direction)")
+        self.D, self.pad, self.activations = D, int(sum(radii)), list(activations)
+        c = [D] + list(channels)
+        Conv = torch.nn.Conv2d if D == 2 else torch.nn.Conv3d
+        self.convs = torch.nn.ModuleList(Conv(c[i], c[i + 1], 2 * radii[i] + 1, bias=bool(use_bias[i]), dtype=torch.float64) for i in range(len(radii)))
+        for conv in self.convs:  # glorot_uniform weights, zero bias, as Lux's Conv with init_weight = glorot_uniform
+            torch.nn.init.xavier_uniform_(conv.weight, generator=generator)
+            if conv.bias is not None:
+                torch.nn.init.zeros_(conv.bias)
+
+    def forward(self, u, θ=None):
+        if θ is not None:
+            return torch.func.functional_call(self, θ, (u,))
+        D = self.D
+        x = collocate(u)
+        x = x.permute(D + 1, D, *range(D))  # (nsample, D, n…)
+        x = torch.nn.functional.pad(x, (self.pad,) * (2 * D), mode="circular")
+        for conv, σ in zip(self.convs, self.activations):
+            x = conv(x)
+            if σ is not None:
+                x = σ(x)
+        x = x.permute(*range(2, D + 2), 1, 0)
+        return decollocate(x)
+
+
+def cnn(*, setup, radii, channels, activations, use_bias, rng=None):
+    """Create CNN closure model (cnn.jl): a `torch.nn.Module` on the device of `setup`, callable as `m(x, θ)`.  `activations[i]` is a
+    callable or None (identity); `rng`: a `torch.Generator` (CPU) or an integer seed for the weights."""
+    gen = rng
+    if rng is not None and not isinstance(rng, torch.Generator):
+        gen = torch.Generator().manual_seed(int(rng))
+    return CNN(setup.grid.dimension, list(radii), list(channels), activations, use_bias, gen).to(setup.device)
+
+
+# ------------------------------------------------------------------------------------------------ training.jl
+def _as_tensor(a, device):
+    return torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a, dtype=torch.float64, device=device)
+
+
+def create_dataloader_prior(data, *, batchsize=50, device=None):
+    """training.jl:1-23: `dataloader(rng) -> ((x, y), rng)`, a batch of `batchsize` random samples (sorted indices) on `device`.
+    `rng` is a `numpy.random.Generator`."""
+    x, y = data
+    nsample = x.shape[-1]
+
+    def dataloader(rng):
+        i = np.sort(rng.permutation(nsample)[:batchsize])
+        return (_as_tensor(x[..., i], device), _as_tensor(y[..., i], device)), rng
+
+    return dataloader
+
+
+def create_dataloader_post(trajectories, *, ntrajectory, nunroll, device=None):
+    """Create trajectory dataloader (training.jl:25-41): `ntrajectory` random trajectories, of each `nunroll + 1` consecutive states from a
+    random start."""
+
+    def dataloader(rng):
+        data = []
+        for k in rng.permutation(len(trajectories))[:ntrajectory]:
+            u, t = trajectories[k]["u"], np.asarray(trajectories[k]["t"])
+            nt = len(t)
+            if nt < nunroll + 1:
+                raise ValueError(f"Trajectory too short for nunroll = {nunroll}")
+            istart = int(rng.integers(0, nt - nunroll))
+            it = slice(istart, istart + nunroll + 1)
+            data.append(dict(u=_as_tensor(u[..., it], device), t=t[it]))
+        return data, rng
+
+    return dataloader
+
+
+def train(*, dataloader, loss, trainstate, niter, callback=None, callbackstate=None, λ=None):
+    """training.jl:43-63: `niter` times: batch, gradient of `loss(batch, θ)`, optional weight decay `g += λθ`, optimiser step, callback.
+    `trainstate = dict(opt=<torch.optim optimiser over the parameters>, θ=<what the loss takes>, rng=<numpy Generator>)`."""
+    opt, θ, rng = trainstate["opt"], trainstate["θ"], trainstate["rng"]
+    for _ in range(niter):
+        batch, rng = dataloader(rng)
+        opt.zero_grad(set_to_none=True)
+        loss(batch, θ).backward()
+        if λ is not None:
+            for group in opt.param_groups:
+                for q in group["params"]:
+                    if q.grad is not None:
+                        q.grad.add_(q.detach(), alpha=λ)
+        opt.step()
+        trainstate = dict(opt=opt, θ=θ, rng=rng)
+        if callback is not None:
+            callbackstate = callback(callbackstate, trainstate)
+    return dict(trainstate=trainstate, callbackstate=callbackstate)
+
+
+def create_loss_prior(f, normalize=None):
+    """Return mean squared error loss for the predictor `f` (training.jl:110-113): Σ(f(x, θ) − y)² / normalize(y), default Σy²."""
+    normalize = normalize or (lambda y: (y * y).sum())
+
+    def loss_prior(batch, θ):
+        x, y = batch
+        d = f(x, θ) - y
+        return (d * d).sum() / normalize(y)
+
+    return loss_prior
+
+
+def create_relerr_prior(f, x, y):
+    """Create a-priori error (training.jl:115-118): θ -> ‖f(x, θ) − y‖ / ‖y‖."""
+
+    def relerr_prior(θ):
+        with torch.no_grad():
+            return float(torch.linalg.vector_norm(f(x, θ) - y) / torch.linalg.vector_norm(y))
+
+    return relerr_prior
+
+
+class _SetupView(Setup):
+    """`(; setup..., closure_model)`: the same grid handle and device, another closure model.  Keeps its parent alive; owns nothing."""
+
+    def __init__(self, parent, closure_model):
+        self.__dict__.update(parent.__dict__)
+        self._parent, self.closure_model = parent, closure_model
+
+    def __del__(self):
+        pass
+
+
+def _field_of(setup, a):
+    f = vectorfield(setup)
+    f.copy_(a)
+    return f
+
+
+def create_loss_post(*, setup, method, psolver, closure_model, nsubstep=1):
+    """Create a-posteriori loss function (training.jl:120-146): unroll `ad.timestep` from the first state of every trajectory in the batch and
+    average Σ|u − u_ref|² / Σ|u_ref|² (on `Iu`) over the following states.  Differentiable in θ."""
+    setup = _SetupView(setup, closure_model)
+    inside = _inside(setup)
+
+    def loss_post(data, θ):
+        total = 0.0
+        for traj in data:
+            u, t = traj["u"], traj["t"]
+            stepper = create_stepper(method, setup=setup, psolver=psolver, u=_field_of(setup, u[..., 0]), temp=None, t=float(t[0]))
+            loss = 0.0
+            for it in range(1, len(t)):
+                Δt = float(t[it] - t[it - 1]) / nsubstep
+                for _ in range(nsubstep):
+                    stepper = ad.timestep(method, stepper, Δt, θ)
+                uref = u[..., it][inside]
+                d = stepper.u[inside] - uref
+                loss = loss + (d * d).sum() / (uref * uref).sum()
+            total = total + loss / (len(t) - 1)
+        return total / len(data)
+
+    return loss_post
+
+
+def create_relerr_post(*, data, setup, method, psolver, closure_model, nsubstep=1):
+    """Create a-posteriori relative error (training.jl:148-180): θ -> mean over the trajectory of ‖u − u_ref‖ / ‖u_ref‖ (on `Iu`), the LES run
+    with the native mutating `timestep_`."""
+    setup = _SetupView(setup, closure_model)
+    inside = _inside(setup)
+    u, t = _as_tensor(data["u"], setup.device), np.asarray(data["t"])
+    v = vectorfield(setup)
+    cache = ode_method_cache(method, setup, psolver)
+
+    def relerr_post(θ):
+        with torch.no_grad():
+            v.copy_(u[..., 0])
+            stepper = create_stepper(method, setup=setup, psolver=psolver, u=v, temp=None, t=float(t[0]))
+            e = 0.0
+            for it in range(1, len(t)):
+                Δt = float(t[it] - t[it - 1]) / nsubstep
+                for _ in range(nsubstep):
+                    stepper = timestep_(method, stepper, Δt, θ=θ, cache=cache)
+                uref = u[..., it][inside]
+                e += float(torch.linalg.vector_norm(stepper.u[inside] - uref) / torch.linalg.vector_norm(uref))
+            return e / (len(t) - 1)
+
+    return relerr_post

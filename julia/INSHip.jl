@@ -365,6 +365,38 @@ function project_pullback!(φbar::RA, setup; psolver::HipPSolver, p::RA)
     φbar
 end
 
+# ---- DNS-to-LES filters (lib/NeuralClosure/src/filter.jl).  NeuralClosure is a package of its own, so the filter types are mirrored here;
+# `NeuralClosure.FaceAverage` users forward with `(Φ::NeuralClosure.FaceAverage)(v::ROCArray, u, les, comp) = INSHip.FaceAverage()(v, u, les, comp; setup_dns)`.
+# The C entries need both grids: `setup_dns` is the fine setup (n_dns = comp·n_les, nested faces).
+struct FaceAverage end
+struct VolumeAverage end
+function (::FaceAverage)(v::RA, u::RA, setup_les, comp; setup_dns)        # filter.jl:26-46 (writes Iu[α] of v)
+    check(ccall((:ins_filter_face_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup_les), handle(setup_dns), Cint(comp), pointer(u), pointer(v), stream()))
+    v
+end
+function (::VolumeAverage)(v::RA, u::RA, setup_les, comp; setup_dns)      # filter.jl:82-116 (all-periodic grids)
+    check(ccall((:ins_filter_volume_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup_les), handle(setup_dns), Cint(comp), pointer(u), pointer(v), stream()))
+    v
+end
+function reconstruct!(u::RA, v::RA, setup_dns, setup_les, comp)           # filter.jl:48-76 (all-periodic grids; writes the fine interior)
+    check(ccall((:ins_reconstruct_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup_dns), handle(setup_les), Cint(comp), pointer(v), pointer(u), stream()))
+    u
+end
+# ubar = Φᵀ w over the whole padded fine array (the reference has no filter rrule)
+function filter_pullback!(::FaceAverage, ubar::RA, w::RA, setup_les, comp; setup_dns)
+    check(ccall((:ins_filter_face_pullback_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup_les), handle(setup_dns), Cint(comp), pointer(w), pointer(ubar), stream()))
+    ubar
+end
+function filter_pullback!(::VolumeAverage, ubar::RA, w::RA, setup_les, comp; setup_dns)
+    check(ccall((:ins_filter_volume_pullback_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup_les), handle(setup_dns), Cint(comp), pointer(w), pointer(ubar), stream()))
+    ubar
+end
+
 # ---- step-adjacent operators (SURVEY §8f rows 2 and 4): with these methods the reference's own host-driven `timestep!`
 # (closure model / temperature / body force present) runs entirely on libinship's kernels --------------------------------
 vorticity!(ω::RA, u::RA, setup) =
