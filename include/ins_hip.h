@@ -299,6 +299,30 @@ int ins_smagorinsky_force_needs_sigma(const ins_grid_t* grid);
 /* tensorbasis!(B, V, u, setup)            tensorbasis.jl:16-72 (writes Ip): nb, nv = 3, 2 (2-D) or 11, 5 (3-D).  B is nb·D·D scalar fields,
  * element (a, b) of basis tensor ib at field index ib·D·D + a + D·b (the SMatrix' column-major order); V is nv scalar fields. */
 int ins_tensorbasis_f64(const ins_grid_t* grid, const double* u, double* B, double* V, void* stream);
+
+/* ---------------------------------------------------------------------------------- differentiable tensor-basis closure */
+/* Symmetric tensors are D(D+1)/2 scalar fields [xx, yy, (zz), xy, (xz, yz)] as in ins_smagtensor_f64; nb, nv = 3, 2 (2-D) or 11, 5 (3-D).
+ * The cotangent of such a tensor has the same D(D+1)/2 fields: <taubar, tau> = Σ_{a<=b} taubar_ab tau_ab, i.e. as a full D×D matrix its
+ * off-diagonal entries are halved on both sides of the diagonal.  The pullbacks are exact transposes on the whole padded array masked to
+ * Ip, gather kernels in two passes through a ∇ubar scratch (D·D fields) that the grid handle owns and allocates on first use. */
+/* tensorbasis_adjoint!(ubar, Bbar, Vbar, u, setup)   tensorbasis.jl:30-95 (the reference's 3-D kernel is an empty TODO; here 2-D and 3-D):
+ * transpose of the Jacobian of ins_tensorbasis_f64 at u.  Bbar: nb·D·D fields in the layout of B, Vbar: nv fields; either may be NULL
+ * (= zero), not both.  ubar is overwritten over the whole padded array (accumulate = 0) or added to (accumulate != 0). */
+int ins_tensorbasis_pullback_f64(const ins_grid_t* grid, const double* u, const double* Bbar, const double* Vbar, double* ubar, int accumulate,
+                                 void* stream);
+/* divoftensor_adjoint!(σbar, sbar, setup)   operators.jl:1186-1287: transpose of ins_divoftensor_f64 on the D(D+1)/2 symmetric fields (an
+ * off-diagonal field receives the terms of (α, β) and of (β, α)); σbar += ... over the whole padded array, sbar read on Iu[α] only. */
+int ins_divoftensor_adjoint_f64(const ins_grid_t* grid, const double* sbar, double* sigmabar, void* stream);
+/* The invariants V of tensorbasis! alone   tensorbasis.jl:49-50, 70-74: overwrites V (nv fields) on Ip, no B is formed. */
+int ins_tensorinvariants_f64(const ins_grid_t* grid, const double* u, double* V, void* stream);
+/* tau = Σ_i a_i B_i(u)   tensorbasis.jl:59-69 contracted as lastdimcontract does (:137-146), in registers: `a` is nb scalar fields read on
+ * Ip, tau D(D+1)/2 fields, overwrites tau on Ip; ghost-fill each field with ins_apply_bc_p_f64 before ins_divoftensor_f64. */
+int ins_tensorclosure_stress_f64(const ins_grid_t* grid, const double* u, const double* a, double* tau, void* stream);
+/* One backward for the two entries above   tensorbasis.jl:30-95, 148-157: abar_i = <taubar, B_i> overwrites abar over the whole padded
+ * array (0 outside Ip); ubar = J_tau(u)ᵀ taubar + J_V(u)ᵀ Vbar overwrites (accumulate = 0) or is added to (accumulate != 0).  Vbar may be
+ * NULL; a, taubar and abar may be NULL together (invariants only). */
+int ins_tensorclosure_pullback_f64(const ins_grid_t* grid, const double* u, const double* a, const double* taubar, const double* Vbar, double* abar,
+                                   double* ubar, int accumulate, void* stream);
 /* ins_combine_f64 for scalar fields (tempstart + Σ Δt A[i,j] ktemp[j], step_explicit_runge_kutta.jl:39-44) */
 int ins_combine_scalar_f64(const ins_grid_t* grid, const double* base, double* out, int nterms, const double* coefs,
                            const double* const* ks, void* stream);

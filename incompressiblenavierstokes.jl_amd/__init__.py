@@ -37,6 +37,7 @@ from .operators import (
     dissipation_from_strain,
     dissipation_from_strain_,
     divoftensor_,
+    divoftensor_adjoint_,
     eig2field,
     eig2field_,
     gravity,
@@ -50,6 +51,10 @@ from .operators import (
     tensorbasis,
     tensorbasis_,
     tensorbasis_matrices,
+    tensorbasis_pullback_,
+    tensorclosure_pullback_,
+    tensorclosure_stress_,
+    tensorinvariants_,
     tensorfield,
     vorticity,
     vorticity_,
@@ -110,6 +115,6 @@ from . import autodiff as ad  # noqa: E402  (torch.autograd Functions over the p
 from . import neuralclosure  # noqa: E402  (lib/NeuralClosure: filters, filtered-DNS data generation, closures, losses, training)
 from .neuralclosure import (FaceAverage, VolumeAverage, cnn, collocate, create_dataloader_post, create_dataloader_prior,  # noqa: E402
                             create_io_arrays, create_les_data, create_loss_post, create_loss_prior, create_relerr_post, create_relerr_prior,
-                            decollocate, filtersaver, lesdatagen, reconstruct, reconstruct_, train, wrappedclosure)
+                            decollocate, filtersaver, lesdatagen, reconstruct, reconstruct_, tensorclosure, train, wrappedclosure)
 
 _lib.load()  # fail loudly at import time if libinship.so is absent

@@ -102,6 +102,11 @@ SIGNATURES = {
     "ins_apply_bc_u_pullback_f64": (C.c_int, [vp, vp, vp]),
     "ins_apply_bc_p_pullback_f64": (C.c_int, [vp, vp, vp]),
     "ins_project_pullback_f64": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ins_tensorbasis_pullback_f64": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp]),
+    "ins_divoftensor_adjoint_f64": (C.c_int, [vp, vp, vp, vp]),
+    "ins_tensorinvariants_f64": (C.c_int, [vp, vp, vp, vp]),
+    "ins_tensorclosure_stress_f64": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ins_tensorclosure_pullback_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "ins_filter_face_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "ins_filter_volume_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "ins_reconstruct_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),

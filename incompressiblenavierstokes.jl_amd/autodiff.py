@@ -10,6 +10,7 @@ csrc/ins_adjoint.hip, each the exact transpose of the forward operator on the wh
 
 A closure model given as a torch function `m(u, θ)` is added as F + m(u, θ), and its parameters get gradients from torch.
 """
+import numpy as np
 import torch
 
 from . import operators as O
@@ -18,7 +19,8 @@ from .setup import _fortran_strides, scalarfield, vectorfield
 from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
 
 __all__ = ["apply_bc_u", "apply_bc_p", "scalewithvolume", "divergence", "pressuregradient", "applypressure", "poisson", "convection", "diffusion",
-           "momentum", "project", "right_hand_side", "create_right_hand_side", "timestep", "FaceAverage", "VolumeAverage"]
+           "momentum", "project", "right_hand_side", "create_right_hand_side", "timestep", "FaceAverage", "VolumeAverage", "tensorbasis", "divoftensor",
+           "lastdimcontract", "tensorinvariants", "tensorclosure_stress", "apply_bc_p_fields", "smagorinsky_closure"]
 
 
 def _field(setup, x, vector):
@@ -327,6 +329,172 @@ class VolumeAverage(_Filter):
     """filter.jl:82-116"""
 
     _kind = "volume"
+
+
+# ------------------------------------------------------------------------------------ tensor-basis closure
+def _nfield(setup, x, ncomp, fresh=False):
+    """`x` as an N + (ncomp,) field in the library's layout (a copy when it has another one, or when `fresh`)."""
+    from .setup import _alloc
+
+    shape = tuple(setup.grid.N) + (ncomp,)
+    if (not fresh and x.dtype == torch.float64 and x.device == setup.device and tuple(x.shape) == shape
+            and tuple(x.stride()) == _fortran_strides(shape)):
+        return x.detach()
+    if tuple(x.shape) != shape:
+        raise ValueError(f"expected a field of shape {shape}, got {tuple(x.shape)}")
+    f = _alloc(setup, shape)
+    f.copy_(x.detach())
+    return f
+
+
+def _check_f64(setup, *xs):
+    for x in xs:
+        if x.dtype != torch.float64:
+            raise TypeError("fields must be float64 torch tensors")
+        if x.device != setup.device:
+            raise ValueError(f"field lives on {x.device}, setup on {setup.device}")
+
+
+class _TensorBasis(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup):
+        ctx.setup = setup
+        ctx.set_materialize_grads(False)
+        _check_f64(setup, u)
+        return O.tensorbasis(_saved_field(ctx, setup, u), setup)
+
+    @staticmethod
+    def backward(ctx, gB, gV):
+        s = ctx.setup
+        if gB is None and gV is None:
+            return None, None
+        D = s.grid.dimension
+        nb, nv, _ = O._tb_sizes(s)
+        Bbar = None if gB is None else _nfield(s, gB, nb * D * D)
+        Vbar = None if gV is None else _nfield(s, gV, nv)
+        return O.tensorbasis_pullback_(vectorfield(s), Bbar, Vbar, _saved(ctx), s), None
+
+
+class _DivOfTensor(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, σ, setup):
+        ctx.setup = setup
+        _check_f64(setup, σ)
+        return O.divoftensor_(vectorfield(setup), _nfield(setup, σ, O._tb_sizes(setup)[2]), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return O.divoftensor_adjoint_(O.tensorfield(s), _field(s, g, True), s), None
+
+
+class _TensorInvariants(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup):
+        from .setup import _alloc
+
+        ctx.setup = setup
+        _check_f64(setup, u)
+        V = _alloc(setup, tuple(setup.grid.N) + (O._tb_sizes(setup)[1],))
+        return O.tensorinvariants_(V, _saved_field(ctx, setup, u), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        Vbar = _nfield(s, g, O._tb_sizes(s)[1])
+        return O.tensorclosure_pullback_(vectorfield(s), None, None, Vbar, _saved(ctx), None, s), None
+
+
+class _TensorClosureStress(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, a, setup):
+        ctx.setup = setup
+        _check_f64(setup, u, a)
+        uf = _field(setup, u, True)
+        af = _nfield(setup, a, O._tb_sizes(setup)[0])
+        # both inputs go through save_for_backward when they already are library fields: an in-place change before backward() raises
+        ctx.ucopy = None if uf is u else uf
+        ctx.acopy = None if af.data_ptr() == a.data_ptr() else af
+        ctx.save_for_backward(*([u] if ctx.ucopy is None else []), *([a] if ctx.acopy is None else []))
+        return O.tensorclosure_stress_(O.tensorfield(setup), uf, af, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        from .setup import _alloc
+
+        s = ctx.setup
+        saved = list(ctx.saved_tensors)
+        u = saved.pop(0) if ctx.ucopy is None else ctx.ucopy
+        a = saved.pop(0).detach() if ctx.acopy is None else ctx.acopy
+        nb, _, ns = O._tb_sizes(s)
+        abar = _alloc(s, tuple(s.grid.N) + (nb,))
+        ubar = O.tensorclosure_pullback_(vectorfield(s), abar, _nfield(s, g, ns), None, u, a, s)
+        return ubar, abar, None
+
+
+def tensorbasis(u, setup):
+    """tensorbasis.jl:1-15 (rrule: tensorbasis_adjoint!, here in 2-D and 3-D): `(B, V)` as `ins_amd.tensorbasis`."""
+    return _TensorBasis.apply(u, setup)
+
+
+def divoftensor(σ, setup):
+    """operators.jl:1155-1184 (rrule: divoftensor_adjoint!) on a symmetric `tensorfield` N + (D(D+1)/2,)."""
+    return _DivOfTensor.apply(σ, setup)
+
+
+def lastdimcontract(a, b):
+    """tensorbasis.jl:97-157: c[I] = Σ_i a[I, i] b[I, i, ...] — plain torch (its pullback is torch's)."""
+    return (a.reshape(a.shape + (1,) * (b.dim() - a.dim())) * b).sum(dim=a.dim() - 1)
+
+
+def tensorinvariants(u, setup):
+    """The invariants V of `tensorbasis` alone (N + (nv,), written on Ip), without forming B."""
+    return _TensorInvariants.apply(u, setup)
+
+
+def tensorclosure_stress(u, a, setup):
+    """τ = Σ_i a_i B_i(u) as a symmetric `tensorfield` (written on Ip): `lastdimcontract(a, tensorbasis(u)[0])` in one kernel that keeps the
+    basis in registers; the backward gives ubar and abar_i = <τbar, B_i>.  `a` is N + (nb,)."""
+    return _TensorClosureStress.apply(u, a, setup)
+
+
+def apply_bc_p_fields(σ, t, setup):
+    """`apply_bc_p` on every channel of an N + (n,) field (the stress tensor's ghost fill, operators.jl:1296)."""
+    return torch.stack([apply_bc_p(σ[..., q], t, setup) for q in range(σ.shape[-1])], dim=-1)
+
+
+def _gridsize2(setup):
+    """gridsize² = Σ_α Δ_α[I_α]² over the padded array (operators.jl:1137)."""
+    g = setup.grid
+    D = g.dimension
+    d2 = torch.zeros(tuple(g.N), dtype=torch.float64, device=setup.device)
+    for α in range(D):
+        shape = [1] * D
+        shape[α] = g.N[α]
+        d2 = d2 + torch.as_tensor(np.asarray(g.Δ[α], dtype=np.float64) ** 2, device=setup.device).reshape(shape)
+    return d2
+
+
+def smagorinsky_closure(setup):
+    """Differentiable Smagorinsky closure `m(u, θ)` (operators.jl:1284-1300), θ a 0-dim tensor: the member a_2 = 2 θ² d² sqrt(2 V_1), every
+    other a_i = 0, of the tensor-basis family, so ∂/∂u runs in the fused kernels and ∂/∂θ is torch's: a learnable Smagorinsky constant."""
+    g = setup.grid
+    D = g.dimension
+    nb = O._tb_sizes(setup)[0]
+    ip = tuple(slice(lo, hi) for lo, hi in g.Ip)
+    pads = [q for α in reversed(range(D)) for q in (g.Ip[α][0], g.N[α] - g.Ip[α][1])]
+    d2 = _gridsize2(setup)[ip]
+
+    def closure(u, θ):
+        θ = torch.as_tensor(θ, dtype=torch.float64, device=setup.device)
+        V = tensorinvariants(u, setup)
+        a2 = torch.nn.functional.pad(2 * θ * θ * d2 * torch.sqrt(2 * V[ip + (0,)]), pads)  # Ip only: sqrt has no derivative at the zeros outside
+        z = torch.zeros_like(a2)
+        a = torch.stack([z, a2] + [z] * (nb - 2), dim=-1)
+        τ = apply_bc_p_fields(tensorclosure_stress(u, a, setup), 0.0, setup)
+        return divoftensor(τ, setup)
+
+    return closure
 
 
 # ------------------------------------------------------------------------------------ time stepping

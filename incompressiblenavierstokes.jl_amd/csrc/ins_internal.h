@@ -194,6 +194,9 @@ struct ins_grid {
   // scratch for blocking reductions
   double* red_dev = nullptr;
   double* red_host = nullptr;  // pinned
+  // ∇ubar of the tensor-basis pullbacks (ins_tensorclosure.hip): D·D scalar fields, allocated on first use
+  double* gradbar_dev = nullptr;
+  size_t gradbar_count = 0;
 };
 
 enum PoissonKind { POISSON_SPECTRAL = 0, POISSON_CG = 1, POISSON_FDM = 2 };

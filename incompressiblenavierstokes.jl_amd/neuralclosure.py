@@ -10,6 +10,8 @@ Array layouts.  Fields are the library's padded tensors `N + (D,)`.  Training ar
 CNN) are `(n_1, …, n_D, D, nsample)`: interior volumes only, component, then sample — the reference's layout; the CNN permutes to torch's
 `(nsample, channel, n_1, …, n_D)` internally.  Trajectories (`filtersaver`) are padded: `N + (D, nt)`.
 
+`tensorclosure` is the symmetry tensor-basis model (tensorbasis.jl) on the fused kernels of csrc/ins_tensorclosure.hip.
+
 Out of scope: FNO and group-equivariant layers, the symmetry errors (`rot2stag`), `gaussian_force`, JLD2 files (`filenames` writes `.npz`).
 """
 import time
@@ -28,7 +30,7 @@ from .solver import solve_unsteady
 from .time_steppers import RKMethods, create_stepper, ode_method_cache, timestep_
 
 __all__ = ["AbstractFilter", "FaceAverage", "VolumeAverage", "reconstruct", "reconstruct_", "lesdatagen", "filtersaver", "create_les_data",
-           "create_io_arrays", "wrappedclosure", "collocate", "decollocate", "cnn", "create_dataloader_prior", "create_dataloader_post",
+           "create_io_arrays", "wrappedclosure", "collocate", "decollocate", "cnn", "tensorclosure", "create_dataloader_prior", "create_dataloader_post",
            "create_loss_prior", "create_relerr_prior", "create_loss_post", "create_relerr_post", "train"]
 
 
@@ -299,6 +301,53 @@ def cnn(*, setup, radii, channels, activations, use_bias, rng=None):
     if rng is not None and not isinstance(rng, torch.Generator):
         gen = torch.Generator().manual_seed(int(rng))
     return CNN(setup.grid.dimension, list(radii), list(channels), activations, use_bias, gen).to(setup.device)
+
+
+class TensorClosure(torch.nn.Module):
+    """Tensor-basis closure of Silvis et al. (tensorbasis.jl): c = divoftensor(bc_p(Σ_i a_i(V) B_i)) with the coefficients a pointwise network of
+    the invariants — linear layers over the channel axis, float64.  Frame-invariant by construction, and defined on every grid the kernels of
+    csrc/ins_tensorclosure.hip accept.  Called on the padded field: `m(u, θ)`."""
+
+    def __init__(self, setup, hidden, activation, generator=None):
+        super().__init__()
+        from .operators import _tb_sizes
+
+        self.setup, self.activation = setup, activation
+        nb, nv, _ = _tb_sizes(setup)
+        c = [nv] + list(hidden) + [nb]
+        self.layers = torch.nn.ModuleList(torch.nn.Linear(c[i], c[i + 1], dtype=torch.float64) for i in range(len(c) - 1))
+        for layer in self.layers:  # glorot_uniform weights, zero bias, as `cnn`
+            torch.nn.init.xavier_uniform_(layer.weight, generator=generator)
+            torch.nn.init.zeros_(layer.bias)
+
+    def coefficients(self, V):
+        """a = MLP(V) per cell: N + (nv,) -> N + (nb,)."""
+        x = V
+        for i, layer in enumerate(self.layers):
+            x = layer(x)
+            if i + 1 < len(self.layers) and self.activation is not None:
+                x = self.activation(x)
+        return x
+
+    def forward(self, u, θ=None):
+        if θ is not None:
+            return torch.func.functional_call(self, θ, (u,))
+        s = self.setup
+        a = self.coefficients(ad.tensorinvariants(u, s))
+        τ = ad.apply_bc_p_fields(ad.tensorclosure_stress(u, a, s), 0.0, s)
+        return ad.divoftensor(τ, s)
+
+
+def tensorclosure(*, setup, hidden, activation, rng=None):
+    """Create tensor-basis closure model: a float64 `torch.nn.Module` on the device of `setup`, callable as `m(u, θ)` on the padded field, so it
+    is a `closure_model` for `create_loss_post`, `create_relerr_post` and `ad.timestep` as it stands.  `hidden`: widths of the hidden layers of
+    the coefficient network V -> a; `activation`: a callable or None; `rng`: a `torch.Generator` (CPU) or an integer seed for the weights;
+    θ = None uses the module's own parameters, a dict goes through `torch.func.functional_call`.  The invariants enter as they are: scale them
+    in `activation` / the first layer if the flow needs it."""
+    gen = rng
+    if rng is not None and not isinstance(rng, torch.Generator):
+        gen = torch.Generator().manual_seed(int(rng))
+    return TensorClosure(setup, list(hidden), activation, gen).to(setup.device)
 
 
 # ------------------------------------------------------------------------------------------------ training.jl

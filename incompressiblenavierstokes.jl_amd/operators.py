@@ -472,3 +472,54 @@ def tensorbasis_matrices(B, setup):
     """View of `B` as N + (nb, D, D) with [..., ib, a, b] = element (a, b)."""
     D = setup.grid.dimension
     return B.reshape(tuple(setup.grid.N) + (-1, D, D)).transpose(-1, -2)
+
+
+# ------------------------------------------------------------------------------------ differentiable tensor-basis closure
+# csrc/ins_tensorclosure.hip: τ = Σ_i a_i B_i(u) and the invariants formed in registers (no B field), and the pullbacks of both routes.
+def _tb_sizes(setup):
+    """(nb, nv, ns): basis tensors, invariants, stored entries of a symmetric tensor."""
+    D = setup.grid.dimension
+    return ((3, 2) if D == 2 else (11, 5)) + (D * (D + 1) // 2,)
+
+
+def _ptr_or_null(setup, f, ncomp):
+    return None if f is None else setup.ptr(f, ncomp)
+
+
+def tensorbasis_pullback_(ubar, Bbar, Vbar, u, setup, accumulate=False):
+    """tensorbasis.jl:30-95 (2-D and 3-D): ubar = J(u)ᵀ(Bbar, Vbar) over the whole padded array, or ubar += with `accumulate`.
+    `Bbar` / `Vbar` in the layout of `tensorbasis_`; either may be None (zero)."""
+    D = setup.grid.dimension
+    nb, nv, _ = _tb_sizes(setup)
+    _lib.call("ins_tensorbasis_pullback_f64", setup.handle, setup.ptr(u, True), _ptr_or_null(setup, Bbar, nb * D * D), _ptr_or_null(setup, Vbar, nv),
+              setup.ptr(ubar, True), int(bool(accumulate)), setup.stream)
+    return ubar
+
+
+def divoftensor_adjoint_(σbar, sbar, setup):
+    """operators.jl:1186-1287 (adds the transpose of divoftensor_ applied to sbar to the D(D+1)/2 symmetric fields σbar)"""
+    ns = _tb_sizes(setup)[2]
+    _lib.call("ins_divoftensor_adjoint_f64", setup.handle, setup.ptr(sbar, True), setup.ptr(σbar, ns), setup.stream)
+    return σbar
+
+
+def tensorinvariants_(V, u, setup):
+    """The invariants of tensorbasis_ alone (tensorbasis.jl:49-50, 70-74): writes `V`, N + (nv,), on Ip."""
+    _lib.call("ins_tensorinvariants_f64", setup.handle, setup.ptr(u, True), setup.ptr(V, _tb_sizes(setup)[1]), setup.stream)
+    return V
+
+
+def tensorclosure_stress_(τ, u, a, setup):
+    """τ = Σ_i a_i B_i(u) on Ip (tensorbasis.jl:59-69, 137-146) without storing B: `a` is N + (nb,), `τ` a `tensorfield`."""
+    nb, _, ns = _tb_sizes(setup)
+    _lib.call("ins_tensorclosure_stress_f64", setup.handle, setup.ptr(u, True), setup.ptr(a, nb), setup.ptr(τ, ns), setup.stream)
+    return τ
+
+
+def tensorclosure_pullback_(ubar, abar, τbar, Vbar, u, a, setup, accumulate=False):
+    """One backward for `tensorclosure_stress_` and `tensorinvariants_`: abar_i = <τbar, B_i> (overwritten), ubar = J_τ(u)ᵀτbar + J_V(u)ᵀVbar
+    (overwritten, or added to with `accumulate`).  `Vbar` may be None; `abar`, `τbar` and `a` may be None together."""
+    nb, nv, ns = _tb_sizes(setup)
+    _lib.call("ins_tensorclosure_pullback_f64", setup.handle, setup.ptr(u, True), _ptr_or_null(setup, a, nb), _ptr_or_null(setup, τbar, ns),
+              _ptr_or_null(setup, Vbar, nv), _ptr_or_null(setup, abar, nb), setup.ptr(ubar, True), int(bool(accumulate)), setup.stream)
+    return ubar

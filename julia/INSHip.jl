@@ -365,6 +365,38 @@ function project_pullback!(φbar::RA, setup; psolver::HipPSolver, p::RA)
     φbar
 end
 
+# ---- differentiable tensor-basis closure (tensorbasis.jl, operators.jl:1155-1287).  Symmetric tensors are D(D+1)/2 scalar fields
+# [xx, yy, (zz), xy, (xz, yz)] (N..., D(D+1)/2), B is (N..., nb·D·D) as ins_tensorbasis_f64 writes it, V and a are (N..., nv) and (N..., nb).
+nullable(x) = x === nothing ? Ptr{Float64}(C_NULL) : pointer(x)
+# tensorbasis.jl:30-95 in 2-D and 3-D: ubar = J(u)ᵀ(Bbar, Vbar) (or += with accumulate); Bbar or Vbar may be `nothing`
+function tensorbasis_pullback!(ubar::RA, Bbar, Vbar, u::RA, setup; accumulate = false)
+    check(ccall((:ins_tensorbasis_pullback_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Cvoid}),
+                handle(setup), pointer(u), nullable(Bbar), nullable(Vbar), pointer(ubar), Cint(accumulate), stream()))
+    ubar
+end
+function divoftensor_adjoint!(σbar::RA, sbar::RA, setup)   # operators.jl:1186-1287 (σbar += ...)
+    check(ccall((:ins_divoftensor_adjoint_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), pointer(sbar), pointer(σbar), stream()))
+    σbar
+end
+function tensorinvariants!(V::RA, u::RA, setup)            # tensorbasis.jl:49-50, 70-74 (writes Ip)
+    check(ccall((:ins_tensorinvariants_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), pointer(u), pointer(V), stream()))
+    V
+end
+function tensorclosure_stress!(τ::RA, u::RA, a::RA, setup)  # τ = Σ_i a_i B_i(u) on Ip, no B stored
+    check(ccall((:ins_tensorclosure_stress_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), pointer(u), pointer(a), pointer(τ), stream()))
+    τ
+end
+# abar_i = <τbar, B_i> (overwritten), ubar = J_τ(u)ᵀτbar + J_V(u)ᵀVbar (or += with accumulate); Vbar, or (a, τbar, abar) together, may be `nothing`
+function tensorclosure_pullback!(ubar::RA, abar, τbar, Vbar, u::RA, a, setup; accumulate = false)
+    check(ccall((:ins_tensorclosure_pullback_f64, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Cvoid}),
+                handle(setup), pointer(u), nullable(a), nullable(τbar), nullable(Vbar), nullable(abar), pointer(ubar), Cint(accumulate), stream()))
+    ubar, abar
+end
+
 # ---- DNS-to-LES filters (lib/NeuralClosure/src/filter.jl).  NeuralClosure is a package of its own, so the filter types are mirrored here;
 # `NeuralClosure.FaceAverage` users forward with `(Φ::NeuralClosure.FaceAverage)(v::ROCArray, u, les, comp) = INSHip.FaceAverage()(v, u, les, comp; setup_dns)`.
 # The C entries need both grids: `setup_dns` is the fine setup (n_dns = comp·n_les, nested faces).
