@@ -348,6 +348,35 @@ int ins_rk_set_closure(ins_rk_t* rk, int32_t kind, double theta);
 /* One step; `temp` (scalar field, nullable exactly when no temperature equation is set) is advanced with u.  Asynchronous. */
 int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double* temp, double t, double dt, void* stream);
 
+/* ---------------------------------------------------------------------------------- pullbacks of the temperature equation
+ * Exact transposes of the temperature operators above on the whole padded arrays (csrc/ins_temp_adjoint.hip; DESIGN.md "Differentiability",
+ * "Temperature equation").  Gather kernels, no atomics, bitwise reproducible, fp64, 2-D and 3-D, any BC mix.  The reference's own rules for
+ * convection_diffusion_temp and dissipation do not work (operators.jl:699-704, test/chainrules.jl:119-131).  Slab grids: INS_ERR_UNSUPPORTED. */
+/* apply_bc_temp_pullback!(tempbar, t, setup)   boundary_conditions.jl:142-157, 248-270, 341-342, 407-412, 469-470, 515-516, in place: the
+ * transpose of the linear part of apply_bc_temp!, directions and sides in the reverse order of the forward fill.  Periodic: the ghost
+ * cotangent is added to its image volume, then zeroed; Dirichlet (constant or callable): zeroed; Symmetric / Pressure: added to the mirrored
+ * interior volume, then zeroed.  bc[2β+side] as in ins_apply_bc_temp_f64; neither t nor the Dirichlet values enter. */
+int ins_apply_bc_temp_pullback_f64(const ins_grid_t* grid, const int32_t* bc, double* tempbar, void* stream);
+/* gravity_adjoint!(tempbar, φbar, setup)       operators.jl:892-908: tempbar += (α2·avg)ᵀ φbar[:, gdir], φbar read on Iu[gdir] only, with the
+ * Δ weights of this library's avg (operators.jl:59-62).  φbar is a vector field; gdir 0-based. */
+int ins_gravity_adjoint_f64(const ins_grid_t* grid, int gdir, double a2, const double* phibar, double* tempbar, void* stream);
+/* convection_diffusion_temp_adjoint!(ubar, tempbar, cbar, u, temp, setup)   operators.jl:712-737 (the rrule at :699-704 is broken): c is
+ * bilinear in (u, temp) plus the temp-only diffusion part, cbar is read on Ip only.  ubar[J, β] += avg(temp, J, β)·(cbar[J+eβ]/Δβ[Jβ+1] −
+ * cbar[J]/Δβ[Jβ]); tempbar += the transposed convective averages and three-point diffusion stencil.  ubar or tempbar may be NULL to skip
+ * that half (not both). */
+int ins_convection_diffusion_temp_adjoint_f64(const ins_grid_t* grid, double a4, const double* u, const double* temp, const double* cbar,
+                                              double* ubar, double* tempbar, void* stream);
+/* dissipation_adjoint!(ubar, cbar, u, setup)   operators.jl:791-814 (no working reference rule): ubar += wbar ⊙ d + diffusionᵀ(wbar ⊙ u), with
+ * d = diffusion(u) on the degrees of freedom and wbar[J, β] = coef/2·(cbar[J]·[J ∈ Ip] + cbar[J+eβ]·[J+eβ ∈ Ip]); d and wbar ⊙ u are
+ * recomputed from their stencils, no scratch field.  visc = 1/Re, coef = Re·α1/γ as in ins_dissipation_f64. */
+int ins_dissipation_adjoint_f64(const ins_grid_t* grid, double visc, double coef, const double* u, const double* cbar, double* ubar, void* stream);
+/* One Runge-Kutta stage's temperature-coupled pullback in one launch (step_explicit_runge_kutta.jl:79-83; operators.jl:712-737, 791-814,
+ * 914-931), at the ghost-filled (u, temp): tempbar = gravityᵀ Fbar + (∂c/∂temp)ᵀ cbar overwrites tempbar over the whole padded array;
+ * ubar += (∂c/∂u)ᵀ cbar + [desc->dodissipation] dissipationᵀ cbar accumulates on top of what ins_momentum_pullback_f64 wrote.  The same
+ * sums as the four operator-level entries above.  Only a2, a4, diss_coef, gdir and dodissipation of `desc` are read. */
+int ins_temperature_pullback_f64(const ins_grid_t* grid, const ins_temperature_desc_t* desc, double visc, const double* u, const double* temp,
+                                 const double* Fbar, const double* cbar, double* ubar, double* tempbar, void* stream);
+
 /* observespectrum(state; setup, npoint, a)   processors.jl:303-332.  The index sets of spectral_stuff (utils.jl:49-108) are built
  * on the host: bin i sums the modes inds[offsets[i] .. offsets[i+1]), each a 0-based column-major position in the K = Np .÷ 2
  * array of retained non-negative wavenumbers.  ins_spectrum_f64 writes ehat[0 .. nbin) (DEVICE): per component one ghost strip,

@@ -28,6 +28,11 @@ from .operators import (
     pressuregradient_adjoint_,
     apply_bc_temp,
     apply_bc_temp_,
+    apply_bc_temp_pullback_,
+    convection_diffusion_temp_adjoint_,
+    dissipation_adjoint_,
+    gravity_adjoint_,
+    temperature_pullback_,
     applybodyforce,
     applybodyforce_,
     convection_diffusion_temp,

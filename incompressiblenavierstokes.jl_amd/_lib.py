@@ -107,6 +107,11 @@ SIGNATURES = {
     "ins_tensorinvariants_f64": (C.c_int, [vp, vp, vp, vp]),
     "ins_tensorclosure_stress_f64": (C.c_int, [vp, vp, vp, vp, vp]),
     "ins_tensorclosure_pullback_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "ins_apply_bc_temp_pullback_f64": (C.c_int, [vp, C.POINTER(C.c_int32), vp, vp]),
+    "ins_gravity_adjoint_f64": (C.c_int, [vp, C.c_int, C.c_double, vp, vp, vp]),
+    "ins_convection_diffusion_temp_adjoint_f64": (C.c_int, [vp, C.c_double, vp, vp, vp, vp, vp, vp]),
+    "ins_dissipation_adjoint_f64": (C.c_int, [vp, C.c_double, C.c_double, vp, vp, vp, vp]),
+    "ins_temperature_pullback_f64": (C.c_int, [vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
     "ins_filter_face_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "ins_filter_volume_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "ins_reconstruct_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),

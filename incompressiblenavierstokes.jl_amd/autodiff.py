@@ -2,7 +2,7 @@
 sciml.jl:49-113) as `torch.autograd.Function`s, exported as `ins_amd.ad`.
 
 Every function here has the signature of its allocating twin in `ins_amd` and the same forward result; its backward runs the pullback kernels of
-csrc/ins_adjoint.hip, each the exact transpose of the forward operator on the whole padded array (DESIGN.md "Differentiability").
+csrc/ins_adjoint.hip and csrc/ins_temp_adjoint.hip (the temperature equation, which the reference's rules do not cover), each the exact transpose of the forward operator on the whole padded array (DESIGN.md "Differentiability").
 `ad.timestep` is the non-mutating Runge-Kutta step of step_explicit_runge_kutta.jl:61-120 built from them, so
 
     u = ad.timestep(method, stepper, Δt).u
@@ -14,11 +14,12 @@ import numpy as np
 import torch
 
 from . import operators as O
+from .boundary_conditions import DirichletBC
 from .pressure import project_, project_pullback_
 from .setup import _fortran_strides, scalarfield, vectorfield
 from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
 
-__all__ = ["apply_bc_u", "apply_bc_p", "scalewithvolume", "divergence", "pressuregradient", "applypressure", "poisson", "convection", "diffusion",
+__all__ = ["apply_bc_u", "apply_bc_p", "apply_bc_temp", "gravity", "convection_diffusion_temp", "dissipation", "scalewithvolume", "divergence", "pressuregradient", "applypressure", "poisson", "convection", "diffusion",
            "momentum", "project", "right_hand_side", "create_right_hand_side", "timestep", "FaceAverage", "VolumeAverage", "tensorbasis", "divoftensor",
            "lastdimcontract", "tensorinvariants", "tensorclosure_stress", "apply_bc_p_fields", "smagorinsky_closure"]
 
@@ -231,10 +232,149 @@ def diffusion(u, setup, use_viscosity=True):
 
 
 def momentum(u, temp, t, setup):
-    """operators.jl:940-976 (convection + diffusion + body force; the pullback is one fused kernel)."""
-    if temp is not None:
-        raise NotImplementedError("the temperature pullbacks are not implemented (the reference marks them @test_broken)")
-    return _Momentum.apply(u, t, setup)
+    """operators.jl:940-976 (convection + diffusion + body force; the pullback is one fused kernel).  With a temperature field the gravity term
+    is added (operators.jl:974), differentiable in `u` and in `temp`."""
+    if temp is None:
+        return _Momentum.apply(u, t, setup)
+    if setup.temperature is None:
+        raise NotImplementedError("ad.momentum: a temperature field needs setup.temperature (temperature_equation)")
+    return _Momentum.apply(u, t, setup) + gravity(temp, setup)
+
+
+# ------------------------------------------------------------------------------------ temperature equation
+def _save_inputs(ctx, setup, items):
+    """The fields a backward reads, `items` = (tensor, vector) pairs: an input that already is a library field goes through
+    save_for_backward, so an in-place change of it before backward() raises; a layout copy is private to the Function."""
+    fields, saved, copies = [], [], []
+    for x, vector in items:
+        f = _field(setup, x, vector)
+        fields.append(f)
+        if f is x:
+            saved.append(x)
+            copies.append(None)
+        else:
+            copies.append(f)
+    ctx.save_for_backward(*saved)
+    ctx.copies = copies
+    return fields
+
+
+def _saved_inputs(ctx):
+    saved = list(ctx.saved_tensors)
+    return [saved.pop(0) if c is None else c for c in ctx.copies]
+
+
+class _ApplyBCTemp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, temp, t, setup):
+        ctx.setup = setup
+        return O.apply_bc_temp_(_copy(setup, temp, False), t, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return O.apply_bc_temp_pullback_(_copy(s, g, False), 0.0, s), None, None
+
+
+class _Gravity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, temp, setup):
+        ctx.setup = setup
+        return O.gravity(_field(setup, temp, False), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return O.gravity_adjoint_(scalarfield(s), _field(s, g, True), s), None
+
+
+class _ConvectionDiffusionTemp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, temp, setup):
+        ctx.setup = setup
+        uf, tf = _save_inputs(ctx, setup, [(u, True), (temp, False)])
+        return O.convection_diffusion_temp(uf, tf, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        u, temp = _saved_inputs(ctx)
+        ubar = vectorfield(s) if ctx.needs_input_grad[0] else None
+        tempbar = scalarfield(s) if ctx.needs_input_grad[1] else None
+        if ubar is not None or tempbar is not None:
+            O.convection_diffusion_temp_adjoint_(ubar, tempbar, _field(s, g, False), u, temp, s)
+        return ubar, tempbar, None
+
+
+class _Dissipation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup):
+        ctx.setup = setup
+        (uf,) = _save_inputs(ctx, setup, [(u, True)])
+        return O.dissipation(uf, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        (u,) = _saved_inputs(ctx)
+        return O.dissipation_adjoint_(vectorfield(s), _field(s, g, False), u, s), None
+
+
+class _StageRightHandSide(torch.autograd.Function):
+    """(u, temp) -> (F, Ftemp) of one Runge-Kutta stage (step_explicit_runge_kutta.jl:79-83): F = momentum(u, temp), Ftemp =
+    convection_diffusion_temp(u, temp) + dissipation(u).  The backward is two launches: momentum_pullback_, then temperature_pullback_."""
+
+    @staticmethod
+    def forward(ctx, u, temp, t, setup):
+        ctx.setup = setup
+        ctx.set_materialize_grads(False)
+        uf, tf = _save_inputs(ctx, setup, [(u, True), (temp, False)])
+        F = O.momentum_(vectorfield(setup), uf, tf, t, setup)
+        Ftemp = O.convection_diffusion_temp_(scalarfield(setup), uf, tf, setup)
+        if setup.temperature.dodissipation:
+            O.dissipation_(Ftemp, vectorfield(setup), uf, setup)
+        return F, Ftemp
+
+    @staticmethod
+    def backward(ctx, gF, gT):
+        s = ctx.setup
+        if gF is None and gT is None:
+            return None, None, None, None
+        u, temp = _saved_inputs(ctx)
+        Fbar = vectorfield(s) if gF is None else _field(s, gF, True)
+        cbar = scalarfield(s) if gT is None else _field(s, gT, False)
+        ubar = O.momentum_pullback_(vectorfield(s), Fbar, u, s)
+        ubar, tempbar = O.temperature_pullback_(ubar, scalarfield(s), Fbar, cbar, u, temp, s)
+        return ubar, tempbar, None, None
+
+
+def _need_temperature(setup, what):
+    if setup.temperature is None:
+        raise ValueError(f"ad.{what} needs setup.temperature (temperature_equation)")
+
+
+def apply_bc_temp(temp, t, setup):
+    """boundary_conditions.jl:236-246 (rrule: apply_bc_temp_pullback!)"""
+    _need_temperature(setup, "apply_bc_temp")
+    return _ApplyBCTemp.apply(temp, t, setup)
+
+
+def gravity(temp, setup):
+    """operators.jl:884-931 (rrule: gravity_adjoint!)"""
+    _need_temperature(setup, "gravity")
+    return _Gravity.apply(temp, setup)
+
+
+def convection_diffusion_temp(u, temp, setup):
+    """operators.jl:692-737, differentiable in `u` and in `temp` (the reference's rrule, :699-704, returns undefined names)."""
+    _need_temperature(setup, "convection_diffusion_temp")
+    return _ConvectionDiffusionTemp.apply(u, temp, setup)
+
+
+def dissipation(u, setup):
+    """operators.jl:770-814 (the reference's rrule is @test_broken); the pullback recomputes diffusion(u) in the kernel."""
+    _need_temperature(setup, "dissipation")
+    return _Dissipation.apply(u, setup)
 
 
 # ------------------------------------------------------------------------------------ projection and right-hand side
@@ -499,23 +639,30 @@ def smagorinsky_closure(setup):
 
 # ------------------------------------------------------------------------------------ time stepping
 def timestep(method, stepper, Δt, θ=None):
-    """step_explicit_runge_kutta.jl:61-120: one explicit Runge-Kutta step without mutation, differentiable in `stepper.u` and (through a torch
-    closure model `m(u, θ)`) in θ.  The stage combinations are torch arithmetic."""
+    """step_explicit_runge_kutta.jl:61-120: one explicit Runge-Kutta step without mutation, differentiable in `stepper.u`, in `stepper.temp`
+    (with the temperature equation) and (through a torch closure model `m(u, θ)`) in θ.  The stage combinations are torch arithmetic; with a
+    temperature field the right-hand side of a stage, (u, temp) -> (F, Ftemp), is one Function whose backward is two launches."""
     setup, psolver, u, temp, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.temp, stepper.t, stepper.n
-    if temp is not None:
-        raise NotImplementedError("ad.timestep: the temperature equation has no pullback (the reference marks it @test_broken)")
+    if temp is not None and setup.temperature is None:
+        raise ValueError("a temperature field needs setup.temperature (temperature_equation)")
     m = setup.closure_model
     if m is not None and getattr(m, "_ins_closure", None) == "smagorinsky" and torch.is_grad_enabled():
         raise NotImplementedError("ad.timestep: the Smagorinsky closure has no pullback; give the closure as a torch function m(u, θ)")
-    if isinstance(method, LMWray3) and (setup.needs_bc_planes or (setup.bodyforce is not None and not setup.issteadybodyforce)):
+    tempplanes = temp is not None and any(isinstance(bc, DirichletBC) and callable(bc.u) for side in setup.temperature.boundary_conditions for bc in side)
+    if isinstance(method, LMWray3) and (setup.needs_bc_planes or tempplanes or (setup.bodyforce is not None and not setup.issteadybodyforce)):
         # the native step runs the low-storage loop then (step_lmwray3.jl), whose ghost fills happen at other times than the ERK form's
         raise NotImplementedError("ad.timestep: LMWray3 with time-dependent boundary data or body force; use an ExplicitRungeKuttaMethod")
     erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
     A, c = erk.A, erk.c
-    tstart, ustart, ku = t, u, []
+    tstart, ustart, tempstart, ku, ktemp = t, u, temp, [], []
     for i in range(len(erk.b)):
         u = apply_bc_u(u, t, setup)
-        F = momentum(u, None, t, setup)
+        if temp is None:
+            F = momentum(u, None, t, setup)
+        else:
+            temp = apply_bc_temp(temp, t, setup)
+            F, Ftemp = _StageRightHandSide.apply(u, temp, t, setup)
+            ktemp.append(Ftemp)
         if m is not None:
             F = F + m(u, θ)
         ku.append(F)
@@ -524,7 +671,14 @@ def timestep(method, stepper, Δt, θ=None):
         for j in range(i + 1):
             if A[i, j] != 0:
                 u = u + (Δt * A[i, j]) * ku[j]
+        if temp is not None:
+            temp = tempstart
+            for j in range(i + 1):
+                if A[i, j] != 0:
+                    temp = temp + (Δt * A[i, j]) * ktemp[j]
         u = apply_bc_u(u, t, setup)
         u = project(u, setup, psolver)
     u = apply_bc_u(u, t, setup)
-    return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=None, t=t, n=n + 1)
+    if temp is not None:
+        temp = apply_bc_temp(temp, t, setup)
+    return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=t, n=n + 1)

@@ -338,6 +338,55 @@ def gravity(temp, setup):
     return gravity_(vectorfield(setup), temp, setup)
 
 
+# ------------------------------------------------------------------------------------ temperature pullbacks (reverse mode)
+# csrc/ins_temp_adjoint.hip: exact transposes of the four operators above on the whole padded arrays (DESIGN.md "Temperature equation").
+def apply_bc_temp_pullback_(tempbar, t, setup):
+    """boundary_conditions.jl:248-270, in place.  Neither `t` nor the Dirichlet values change the transpose (they only move the constants)."""
+    bcs = setup.temperature.boundary_conditions
+    codes = (C.c_int32 * 6)()
+    for be in range(setup.grid.dimension):
+        for side in range(2):
+            codes[2 * be + side] = bcs[be][side].code
+    _lib.call("ins_apply_bc_temp_pullback_f64", setup.handle, codes, setup.ptr(tempbar, False), setup.stream)
+    return tempbar
+
+
+def gravity_adjoint_(tempbar, φbar, setup):
+    """operators.jl:892-908 (adds (α2 avg)ᵀ φbar[..., gdir] to tempbar)"""
+    T = setup.temperature
+    _lib.call("ins_gravity_adjoint_f64", setup.handle, int(T.gdir), T.α2, setup.ptr(φbar, True), setup.ptr(tempbar, False), setup.stream)
+    return tempbar
+
+
+def convection_diffusion_temp_adjoint_(ubar, tempbar, cbar, u, temp, setup):
+    """operators.jl:712-737 at the ghost-filled (u, temp): adds (∂c/∂u)ᵀ cbar to `ubar` and (∂c/∂temp)ᵀ cbar to `tempbar`; either may be
+    None to skip that half.  Returns (ubar, tempbar)."""
+    _lib.call("ins_convection_diffusion_temp_adjoint_f64", setup.handle, setup.temperature.α4, setup.ptr(u, True), setup.ptr(temp, False),
+              setup.ptr(cbar, False), _ptr_or_null(setup, ubar, True), _ptr_or_null(setup, tempbar, False), setup.stream)
+    return ubar, tempbar
+
+
+def dissipation_adjoint_(ubar, cbar, u, setup):
+    """operators.jl:791-814 at the ghost-filled `u` (adds J(u)ᵀ cbar to ubar; diffusion(u) is recomputed in the kernel, no scratch field)"""
+    T = setup.temperature
+    _lib.call("ins_dissipation_adjoint_f64", setup.handle, 1.0 / setup.Re, setup.Re * T.α1 / T.γ, setup.ptr(u, True), setup.ptr(cbar, False),
+              setup.ptr(ubar, True), setup.stream)
+    return ubar
+
+
+def temperature_pullback_(ubar, tempbar, Fbar, cbar, u, temp, setup):
+    """One Runge-Kutta stage's temperature-coupled pullback in one launch: tempbar = gravityᵀ Fbar + (∂c/∂temp)ᵀ cbar (overwritten),
+    ubar += (∂c/∂u)ᵀ cbar + dissipationᵀ cbar (the latter with `dodissipation`), on top of what `momentum_pullback_` wrote.
+    Returns (ubar, tempbar)."""
+    from .time_steppers import _TempDesc
+
+    T = setup.temperature
+    desc = _TempDesc(a2=T.α2, a4=T.α4, diss_coef=setup.Re * T.α1 / T.γ, gdir=int(T.gdir), dodissipation=int(T.dodissipation))
+    _lib.call("ins_temperature_pullback_f64", setup.handle, C.byref(desc), 1.0 / setup.Re, setup.ptr(u, True), setup.ptr(temp, False),
+              setup.ptr(Fbar, True), setup.ptr(cbar, False), setup.ptr(ubar, True), setup.ptr(tempbar, False), setup.stream)
+    return ubar, tempbar
+
+
 # ------------------------------------------------------------------------------------ field diagnostics
 def _vort_field(setup):
     return scalarfield(setup) if setup.grid.dimension == 2 else vectorfield(setup)

@@ -28,7 +28,8 @@ import IncompressibleNavierStokes:
     ExplicitRungeKuttaMethod, PeriodicBC, DirichletBC, SymmetricBC, PressureBC,
     vorticity!, interpolate_u_p!, interpolate_ω_p!, Qfield!, Dfield!, eig2field!, dissipation_from_strain!,
     convection_diffusion_temp!, dissipation!, gravity!, smagorinsky_closure,
-    divergence_adjoint!, pressuregradient_adjoint!, convection_adjoint!, diffusion_adjoint!, apply_bc_u_pullback!, apply_bc_p_pullback!
+    divergence_adjoint!, pressuregradient_adjoint!, convection_adjoint!, diffusion_adjoint!, apply_bc_u_pullback!, apply_bc_p_pullback!,
+    apply_bc_temp_pullback!
 
 const lib = get(ENV, "INSHIP_LIB", "libinship.so")
 const RA = ROCArray{Float64}
@@ -479,6 +480,46 @@ function apply_bc_temp!(temp::RA, t, setup; kwargs...)
                                   handle(setup), codes, vals, planes, pointer(temp), stream()))
     isempty(keep) || AMDGPU.synchronize()
     temp
+end
+# ---- pullbacks of the temperature equation (csrc/ins_temp_adjoint.hip): exact transposes of the four operators above on the padded arrays.
+# The reference has a working rule only for gravity (operators.jl:884-910) and apply_bc_temp (boundary_conditions.jl:248-270); its rrule of
+# convection_diffusion_temp returns undefined names (operators.jl:699-704) and dissipation's is @test_broken, so the last three are new names.
+function apply_bc_temp_pullback!(φbar::RA, t, setup; kwargs...)   # boundary_conditions.jl:248-270 (in place; neither t nor the values enter)
+    bcs = setup.temperature.boundary_conditions
+    codes = zeros(Int32, 6)
+    for β = 1:length(bcs), (side, bc) in enumerate(bcs[β])
+        codes[2(β - 1) + side] = bccode(bc)
+    end
+    check(ccall((:ins_apply_bc_temp_pullback_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), codes, pointer(φbar), stream()))
+    φbar
+end
+function gravity_adjoint!(tempbar::RA, φbar::RA, setup)           # operators.jl:892-908 (tempbar += (α2 avg)ᵀ φbar[:, gdir])
+    check(ccall((:ins_gravity_adjoint_f64, lib), Cint, (Ptr{Cvoid}, Cint, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), setup.temperature.gdir - 1, setup.temperature.α2, pointer(φbar), pointer(tempbar), stream()))
+    tempbar
+end
+# operators.jl:712-737: ubar += (∂c/∂u)ᵀ cbar, tempbar += (∂c/∂temp)ᵀ cbar at the ghost-filled (u, temp); ubar or tempbar may be `nothing`
+function convection_diffusion_temp_adjoint!(ubar, tempbar, cbar::RA, u::RA, temp::RA, setup)
+    check(ccall((:ins_convection_diffusion_temp_adjoint_f64, lib), Cint,
+                (Ptr{Cvoid}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), setup.temperature.α4, pointer(u), pointer(temp), pointer(cbar), nullable(ubar), nullable(tempbar), stream()))
+    ubar, tempbar
+end
+function dissipation_adjoint!(ubar::RA, cbar::RA, u::RA, setup)   # operators.jl:791-814 (ubar += J(u)ᵀ cbar; diffusion(u) is recomputed, no scratch)
+    check(ccall((:ins_dissipation_adjoint_f64, lib), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                handle(setup), 1 / setup.Re, setup.Re * setup.temperature.α1 / setup.temperature.γ, pointer(u), pointer(cbar), pointer(ubar), stream()))
+    ubar
+end
+# one stage's temperature-coupled pullback in one launch: tempbar = gravityᵀ Fbar + (∂c/∂temp)ᵀ cbar (overwritten),
+# ubar += (∂c/∂u)ᵀ cbar + dissipationᵀ cbar on top of momentum_pullback!
+function temperature_pullback!(ubar::RA, tempbar::RA, Fbar::RA, cbar::RA, u::RA, temp::RA, setup)
+    desc = Ref(tempdesc(setup))
+    GC.@preserve desc check(ccall((:ins_temperature_pullback_f64, lib), Cint,
+                                  (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                                  handle(setup), Base.unsafe_convert(Ptr{Cvoid}, desc), 1 / setup.Re, pointer(u), pointer(temp), pointer(Fbar), pointer(cbar),
+                                  pointer(ubar), pointer(tempbar), stream()))
+    ubar, tempbar
 end
 # smagorinsky_closure(setup): σ as D(D+1)/2 scalar fields [xx, yy, (zz), xy, (xz, yz)].  A callable struct, so that `timestep!` can tell this
 # closure from a user function and carry it inside the native stage loop (ins_rk_set_closure).
