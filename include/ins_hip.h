@@ -160,7 +160,10 @@ int ins_poisson_fdm_create(const ins_grid_t* grid, const double* const* V, const
 int ins_poisson_destroy(ins_poisson_t* ps);
 /* Which transform engine a spectral solver was planned on: *engine = 1 when all of its passes are this library's own kernels
  * (power-of-two sides and 192 / 384 = 3 * 2^m, csrc/ins_fft.hip), 2 when rocFFT 2-D plans feed the own fused z pass, 0 when every transform
- * is a rocFFT plan (pressure.jl:316 leaves the choice to the FFT library).  Other solver kinds: *engine = -1. */
+ * is a rocFFT plan (pressure.jl:316 leaves the choice to the FFT library).  Other solver kinds: *engine = -1.
+ * The launch sequence of a solver is chosen once, when it is created, from the box and the values the route-selecting switches have then
+ * (INS_DISABLE_OWNFFT, INS_OWNFFT_POW2_ONLY, INS_DISABLE_ZSOLVE, INS_DISABLE_LINE3, INS_DISABLE_XYFUSED, INS_YZ_FUSED, INS_YZ_PARTITIONS,
+ * INS_DISABLE_YZ_FUSED): ins_set_option afterwards changes what later solvers get, never a solver that exists. */
 int ins_poisson_fft_engine(const ins_poisson_t* ps, int32_t* engine);
 /* *partitions > 0: the solver runs FOUR passes per solve — the z direction of pressure.jl:326-341 as periodic tridiagonal systems (the circulant with the
  * eigenvalues âz) solved by the partition method inside the two y passes, `*partitions` z-partitions (csrc/ins_fft.hip k_yz_*) — instead of five with a

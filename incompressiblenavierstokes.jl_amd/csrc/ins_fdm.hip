@@ -506,7 +506,7 @@ int ins_fdm_solve(ins_fdm* F, hipStream_t s, const ins_grid* G, const double* u,
     const int m2 = 2 * F->kxs;
     const long long m2n1 = (long long)m2 * n1;
     const double alpha = 1.0 / std::sqrt(F->hx * (double)n0);
-    int rc = ins_k_ownfft_xfwd(u ? G : nullptr, u ? u : x, u ? 4 : 0, y, n0, n1, n2, F->xtw, s, F->kxs, 0);
+    int rc = ins_k_ownfft_xfwd(u ? G : nullptr, u ? u : x, u ? XSRC_DIV_WALLS : XSRC_PI, y, n0, n1, n2, F->xtw, s, F->kxs, 0);
     if (rc) return rc;
     INS_BLAS_TRY(rocblas_dgemm_strided_batched(F->h, rocblas_operation_none, rocblas_operation_none, m2, n1, n1, &alpha, y, m2, m2n1, F->V[1], n1, 0,
                                                &zero, x, m2, m2n1, n2));
@@ -528,7 +528,7 @@ int ins_fdm_solve(ins_fdm* F, hipStream_t s, const ins_grid* G, const double* u,
     const long long rows = (long long)m2 * n1, tot2 = rows * n2;
     const double alpha = 1.0 / (std::sqrt(F->hx * (double)n0) * std::sqrt(F->hy * (double)n1));
     const int nblk2 = (int)std::min<long long>((tot2 + 255) / 256, 4096);
-    int rc = ins_k_ownfft_xfwd(u ? G : nullptr, u ? u : x, u ? 4 : 0, y, n0, n1, n2, F->xtw, s, F->kxs, 0);
+    int rc = ins_k_ownfft_xfwd(u ? G : nullptr, u ? u : x, u ? XSRC_DIV_WALLS : XSRC_PI, y, n0, n1, n2, F->xtw, s, F->kxs, 0);
     if (rc) return rc;
     if ((rc = ins_k_ownfft_y(y, kxn, n1, n2, F->ytw, false, s, F->kxs))) return rc;
     INS_BLAS_TRY(rocblas_dgemm(F->h, rocblas_operation_none, rocblas_operation_none, (int)rows, n2, n2, &alpha, y, (int)rows, F->V[2], n2, &zero, x, (int)rows));

@@ -379,12 +379,12 @@ __global__ __launch_bounds__(256) void k_xfwd(GridDev g, const double* __restric
       const int idx = t + 256 * q;
       const int row = idx / N, i = idx - row * N;
       const int j = min(j0 + row, n1 - 1);
-      if (SRC == 0) {
+      if (SRC == XSRC_PI) {
         v[q] = reinterpret_cast<const T*>(src)[i + (long long)N * (j + (long long)n1 * kz)];
-      } else if (SRC == 6) {
+      } else if (SRC == XSRC_FIELD) {
         // one padded scalar array (a velocity component): its interior volumes, ghosts stripped on the fly (observespectrum, ins_spectrum.hip)
         v[q] = (T)src[(g.ip_lo[0] + i) + (g.ip_lo[1] + j) * g.sx[1] + (g.ip_lo[2] + kz) * g.sx[2]];
-      } else if (SRC == 5) {
+      } else if (SRC == XSRC_DIV_U32) {
         // as SRC 1, from a FLOAT velocity field (the `_f32` family solves its pressure equation with these fp64 passes, ins_f32.hip):
         // differences and metrics in double from the float values
         const float* sf = reinterpret_cast<const float*>(src);
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(256) void k_xfwd(GridDev g, const double* __restric
         d += ((double)sf[g.sc + c] - (double)sf[g.sc + cy]) * g.rdx[1][I1];
         d += ((double)sf[2 * g.sc + c] - (double)sf[2 * g.sc + cz]) * g.rdx[2][I2];
         v[q] = (T)(d * (g.dx[0][I0] * g.dx[1][I1] * g.dx[2][I2]));
-      } else if (SRC == 4) {
+      } else if (SRC == XSRC_DIV_WALLS) {
         // Ω · div(u) at the pressure point (i, j, kz) of a grid with walls: the ghost volumes of u are valid (k_div_to_pI<3, false>)
         const int I0 = g.ip_lo[0] + i, I1 = g.ip_lo[1] + j, I2 = g.ip_lo[2] + kz;
         const long long c = I0 + I1 * g.sx[1] + I2 * g.sx[2];
@@ -405,7 +405,7 @@ __global__ __launch_bounds__(256) void k_xfwd(GridDev g, const double* __restric
         d += (src[g.sc + c] - src[g.sc + c - g.sx[1]]) * g.rdx[1][I1];
         d += (src[2 * g.sc + c] - src[2 * g.sc + c - g.sx[2]]) * g.rdx[2][I2];
         v[q] = (T)(d * (g.dx[0][I0] * g.dx[1][I1] * g.dx[2][I2]));
-      } else if (SRC == 3) {
+      } else if (SRC == XSRC_DIV_2D) {
         // 2-D: Ω · div(u*) at interior cell (i, j) with periodic wrap (k_div_to_pI<2, true>)
         const int I0 = i + 1, I1 = j + 1;
         const long long c = I0 + I1 * g.sx[1];
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(256) void k_xfwd(GridDev g, const double* __restric
         const long long c = I0 + I1 * g.sx[1] + I2 * g.sx[2];
         const long long cx = I0 == 1 ? c + (long long)(g.N[0] - 3) : c - 1;
         const long long cy = I1 == 1 ? c + (long long)(g.N[1] - 3) * g.sx[1] : c - g.sx[1];
-        const long long cz = (SRC == 1 && I2 == 1) ? c + (long long)(g.N[2] - 3) * g.sx[2] : c - g.sx[2];  // SRC 2: slab ghost plane
+        const long long cz = (SRC == XSRC_DIV && I2 == 1) ? c + (long long)(g.N[2] - 3) * g.sx[2] : c - g.sx[2];  // SRC 2: slab ghost plane
         double d = 0.0;
         d += (src[c] - src[cx]) * g.rdx[0][I0];
         d += (src[g.sc + c] - src[g.sc + cy]) * g.rdx[1][I1];
@@ -699,20 +699,20 @@ int launch_xfwd(const GridDev& g, const double* src, int from_u, double2* out, i
   constexpr int NP = fft_r3(LOGN) == 5 ? 640 / N : (fft_r3(LOGN) == 3 ? 768 / N : (N >= 1024 ? 2 : (1024 / N > 16 ? 16 : 1024 / N)));  // 2 NP N a multiple of 256
   constexpr size_t lds = ((size_t)NP * N + N) * sizeof(double2);
   dim3 grid((n1 + 2 * NP - 1) / (2 * NP), n2);
-  if (from_u == 6)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, 6>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
-  else if (from_u == 5)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, 5>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
-  else if (from_u == 4)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, 4>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
-  else if (from_u == 3)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, 3>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
-  else if (from_u == 2)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, 2>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+  if (from_u == XSRC_FIELD)
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_FIELD>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+  else if (from_u == XSRC_DIV_U32)
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_U32>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+  else if (from_u == XSRC_DIV_WALLS)
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_WALLS>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+  else if (from_u == XSRC_DIV_2D)
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_2D>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+  else if (from_u == XSRC_DIV_SLAB)
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_SLAB>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
   else if (from_u)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, 1>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
   else
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, 0>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_PI>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
@@ -725,9 +725,9 @@ int launch_xfwd32(const GridDev& g, const float* src, int from_u, float2* out, i
   dim3 grid((n1 + 2 * NP - 1) / (2 * NP), n2);
   const double* srcd = reinterpret_cast<const double*>(src);  // the kernel reads float data behind this pointer (C = float2)
   if (from_u)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, 5, float2>), grid, dim3(256), lds, s, g, srcd, out, n1, tw, kxs, 0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_U32, float2>), grid, dim3(256), lds, s, g, srcd, out, n1, tw, kxs, 0, (int)ins_opt(OPT_INS_X_SKEL));
   else
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, 0, float2>), grid, dim3(256), lds, s, g, srcd, out, n1, tw, kxs, 0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_PI, float2>), grid, dim3(256), lds, s, g, srcd, out, n1, tw, kxs, 0, (int)ins_opt(OPT_INS_X_SKEL));
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
@@ -1230,7 +1230,7 @@ __global__ __launch_bounds__(NT) void k_xyfwd(GridDev g, const double* __restric
   for (int idx = t; idx < N1 * N0; idx += NT) {
     const int j = idx / N0, i = idx - j * N0;
     double v;
-    if (SRC == 0) {
+    if (SRC == XSRC_PI) {
       v = src[i + (long long)N0 * (j + (long long)N1 * kz)];
     } else {
       const int I0 = i + 1, I1 = j + 1, I2 = kz + 1;
@@ -1323,7 +1323,7 @@ __global__ __launch_bounds__(NT) void k_xysolve2d(GridDev g, const double* __res
   for (int idx = t; idx < N1 * N0; idx += NT) {
     const int j = idx / N0, i = idx - j * N0;
     double v;
-    if (SRC == 0) {
+    if (SRC == XSRC_PI) {
       v = src[i + (long long)N0 * j];
     } else {
       const int I0 = i + 1, I1 = j + 1;
@@ -1383,11 +1383,11 @@ int launch_xysolve2d(const GridDev& g, const double* src, int from_u, double* pI
   const double inv_n = 1.0 / ((double)N0 * N1);
   int rc;
   if (from_u) {
-    if ((rc = set_lds(&k_xysolve2d<LX, LY, 3, NT>, lds))) return rc;
-    hipLaunchKernelGGL((k_xysolve2d<LX, LY, 3, NT>), dim3(1), dim3(NT), lds, s, g, src, pI, twx, twy, ax, ay, inv_n);
+    if ((rc = set_lds(&k_xysolve2d<LX, LY, XSRC_DIV_2D, NT>, lds))) return rc;
+    hipLaunchKernelGGL((k_xysolve2d<LX, LY, XSRC_DIV_2D, NT>), dim3(1), dim3(NT), lds, s, g, src, pI, twx, twy, ax, ay, inv_n);
   } else {
-    if ((rc = set_lds(&k_xysolve2d<LX, LY, 0, NT>, lds))) return rc;
-    hipLaunchKernelGGL((k_xysolve2d<LX, LY, 0, NT>), dim3(1), dim3(NT), lds, s, g, src, pI, twx, twy, ax, ay, inv_n);
+    if ((rc = set_lds(&k_xysolve2d<LX, LY, XSRC_PI, NT>, lds))) return rc;
+    hipLaunchKernelGGL((k_xysolve2d<LX, LY, XSRC_PI, NT>), dim3(1), dim3(NT), lds, s, g, src, pI, twx, twy, ax, ay, inv_n);
   }
   INS_LAUNCH_CHECK();
   return INS_OK;
@@ -1404,11 +1404,11 @@ int launch_xy(const GridDev& g, const double* src, int from_u, double2* spec, do
     if ((rc = set_lds(&k_xyinv<LX, LY, NT>, lds))) return rc;
     hipLaunchKernelGGL((k_xyinv<LX, LY, NT>), dim3(n2), dim3(NT), lds, s, spec, pI, twx, twy, kxs);
   } else if (from_u) {
-    if ((rc = set_lds(&k_xyfwd<LX, LY, 1, NT>, lds))) return rc;
-    hipLaunchKernelGGL((k_xyfwd<LX, LY, 1, NT>), dim3(n2), dim3(NT), lds, s, g, src, spec, twx, twy, kxs);
+    if ((rc = set_lds(&k_xyfwd<LX, LY, XSRC_DIV, NT>, lds))) return rc;
+    hipLaunchKernelGGL((k_xyfwd<LX, LY, XSRC_DIV, NT>), dim3(n2), dim3(NT), lds, s, g, src, spec, twx, twy, kxs);
   } else {
-    if ((rc = set_lds(&k_xyfwd<LX, LY, 0, NT>, lds))) return rc;
-    hipLaunchKernelGGL((k_xyfwd<LX, LY, 0, NT>), dim3(n2), dim3(NT), lds, s, g, src, spec, twx, twy, kxs);
+    if ((rc = set_lds(&k_xyfwd<LX, LY, XSRC_PI, NT>, lds))) return rc;
+    hipLaunchKernelGGL((k_xyfwd<LX, LY, XSRC_PI, NT>), dim3(n2), dim3(NT), lds, s, g, src, spec, twx, twy, kxs);
   }
   INS_LAUNCH_CHECK();
   return INS_OK;
@@ -1438,28 +1438,22 @@ int launch_xy(const GridDev& g, const double* src, int from_u, double2* spec, do
 bool ins_ownfft_supported(const int np[3]) {  // power-of-two boxes (slab and 2-D paths)
   if (ins_opt(OPT_INS_DISABLE_OWNFFT)) return false;
   for (int a = 0; a < 3; ++a)
-    if (np[a] < 16 || np[a] > 1024 || (np[a] & (np[a] - 1))) return false;
+    if (!ins_pow2_len(np[a])) return false;
   return ins_zsolve_supported(np[2]);
 }
 // z-slab path: own x / y passes for power-of-two and 3 * 2^m sides (the z direction is either the distributed tridiagonal solve — any plane count — or the
 // transposes around the fused z kernel / a rocFFT z plan)
 bool ins_ownfft_supported_slab(const int np[3]) {
   if (ins_opt(OPT_INS_DISABLE_OWNFFT)) return false;
-  for (int a = 0; a < 2; ++a) {
-    const bool pow2 = np[a] >= 16 && np[a] <= 1024 && !(np[a] & (np[a] - 1));
-    const bool r3 = (np[a] == 96 || np[a] == 192 || np[a] == 384 || np[a] == 160 || np[a] == 320 || np[a] == 640) && !ins_opt(OPT_INS_OWNFFT_POW2_ONLY);
-    if (!pow2 && !r3) return false;
-  }
+  for (int a = 0; a < 2; ++a)
+    if (!ins_pow2_len(np[a]) && !ins_mixed_len(np[a])) return false;
   return np[2] >= 2;
 }
 // single-GPU 3-D solver: sides of 3 * 2^m (192, 384) run on the own passes too (a radix-3 stage in front; INS_OWNFFT_POW2_ONLY keeps rocFFT for them)
 bool ins_ownfft_supported_mixed(const int np[3]) {
   if (ins_opt(OPT_INS_DISABLE_OWNFFT)) return false;
-  for (int a = 0; a < 3; ++a) {
-    const bool pow2 = np[a] >= 16 && np[a] <= 1024 && !(np[a] & (np[a] - 1));
-    const bool r3 = (np[a] == 96 || np[a] == 192 || np[a] == 384 || np[a] == 160 || np[a] == 320 || np[a] == 640) && !ins_opt(OPT_INS_OWNFFT_POW2_ONLY);  // 3 * 2^m, 5 * 2^m
-    if (!pow2 && !r3) return false;
-  }
+  for (int a = 0; a < 3; ++a)
+    if (!ins_pow2_len(np[a]) && !ins_mixed_len(np[a])) return false;
   return ins_zsolve_supported(np[2]);
 }
 

@@ -215,12 +215,27 @@ bool ins_fdm_takes_u(const ins_fdm* F);
 double* ins_fdm_buffer(ins_fdm* F);
 const double* ins_fdm_mean(ins_fdm* F);  // device scalar the consumer subtracts (singular systems), or nullptr
 
+// Launch sequence of a spectral solver: chosen once, when the solver is created (ins_spectral_choose, ins_poisson.hip), and dispatched on everywhere.
+enum SpectralRoute {
+  ROUTE_ROCFFT = 0,     // rocFFT plans over all D directions + k_symbol
+  ROUTE_ROCFFT_ZFUSED,  // 3-D: batched rocFFT (x,y) plans + the fused z kernel (ins_zsolve.hip)
+  ROUTE_OWN2D,          // 2-D: own x forward, the fused solve kernel along y, own x inverse
+  ROUTE_OWN2D_ONE,      // 2-D, up to 64 x 64 volumes: the whole solve as one launch (k_xysolve2d)
+  ROUTE_OWN_LDS,        // 3-D: own x, LDS y (k_yfft), fused z, y, x
+  ROUTE_OWN_LINE3,      // 3-D: the same with the y passes on the register passes (k_line3, ins_zsolve.hip)
+  ROUTE_OWN_XY,         // 3-D, planes of 16 .. 64 on both sides: xy forward, fused z, xy inverse (k_xy*)
+  ROUTE_OWN_YZ,         // 3-D, opt-in: own x, the z direction riding on the two LDS y passes (k_yz_*), own x: four passes
+};
+// Storage order in which a route's y pass leaves ky; ahat[1] is uploaded in that order, and nowhere else does the order enter.
+enum KyOrder { KY_NATURAL = 0, KY_DIGITREV, KY_LINE3 };  // rocFFT and the 2-D kernels / the LDS passes and k_xy / k_line3
+
 struct ins_poisson {
   PoissonKind kind;
   const ins_grid* grid;
   // spectral
   hipfftHandle plan_fwd = 0, plan_inv = 0;
-  bool plans = false;
+  SpectralRoute route = ROUTE_ROCFFT;
+  KyOrder ky_order = KY_NATURAL;
   double* pI = nullptr;            // real n^D
   hipfftDoubleComplex* phat = nullptr;  // (n/2+1) n [n]
   double* ahat[3] = {nullptr, nullptr, nullptr};
@@ -229,14 +244,11 @@ struct ins_poisson {
   void* work = nullptr;
   size_t work_bytes = 0;
   hipStream_t plan_stream = nullptr;
-  bool zfused = false;      // 3-D: batched 2-D (x,y) plans + the fused z kernel (ins_zsolve.hip)
-  bool ownfft = false;      // 3-D power-of-two box: all five passes are own LDS kernels (ins_fft.hip), no rocFFT
-  bool y3 = false;          // ownfft, 3-D: the y passes run on the register passes (k_line3, ins_zsolve.hip); ahat[1] is in THEIR storage order
-  int kxs = 0;              // ownfft: row stride of phat (kmax[0] rounded up to 8 complex = 128 B)
+  int kxs = 0;              // own routes: row stride of phat (kmax[0] rounded up to 8 complex = 128 B)
   double* tw = nullptr;     // z twiddles
-  double* tw_x = nullptr;   // x / y twiddles (ownfft)
+  double* tw_x = nullptr;   // x / y twiddles (own routes)
   double* tw_y = nullptr;
-  int yz_P = 0;             // > 0: the z direction rides on the y passes (ins_fft.hip k_yz_*: four passes per solve), yz_P partitions
+  int yz_P = 0;             // ROUTE_OWN_YZ: partition count of the k_yz_* passes; 0 on every other route
   double* yz_scratch = nullptr;
   // cg
   double abstol = 0, reltol = 0;
@@ -357,6 +369,22 @@ int ins_k_reduce(const ins_grid* grid, int op, const double* a, const double* b,
 int ins_validate_real_plans(hipfftHandle fwd, hipfftHandle inv, int rank, const int* n, int batch);
 int ins_fft_make_real_plans(hipfftHandle* fwd, hipfftHandle* inv, int rank, int* n, int batch);
 void ins_fft_solver_released();
+// side lengths the own passes take: a power of two in 16 .. 1024, or 3 * 2^m / 5 * 2^m (a radix-3 / radix-5 stage in front; INS_OWNFFT_POW2_ONLY
+// leaves these to rocFFT)
+static inline bool ins_pow2_len(int n) { return n >= 16 && n <= 1024 && !(n & (n - 1)); }
+static inline bool ins_mixed_len(int n) {
+  return (n == 96 || n == 192 || n == 384 || n == 160 || n == 320 || n == 640) && !ins_opt(OPT_INS_OWNFFT_POW2_ONLY);
+}
+// Where the x-forward pass (k_xfwd, ins_fft.hip) takes its rows from; the launchers carry it as `int from_u`, the kernels as template argument SRC.
+enum XfwdSrc {
+  XSRC_PI = 0,         // rows of the unpadded right-hand side pI
+  XSRC_DIV = 1,        // Ω·div(u) formed on the fly, 3-D, periodic wrap in all directions
+  XSRC_DIV_SLAB = 2,   // the same on a z-slab: the z neighbour comes from the ghost plane
+  XSRC_DIV_2D = 3,     // Ω·div(u), 2-D, periodic wrap
+  XSRC_DIV_WALLS = 4,  // Ω·div(u) on a grid with walls: the ghost volumes of u are valid
+  XSRC_DIV_U32 = 5,    // as XSRC_DIV from a FLOAT velocity field, differences and metrics in double
+  XSRC_FIELD = 6,      // one padded scalar array, ghosts stripped on the fly (observespectrum)
+};
 bool ins_zsolve_supported(int nz);
 bool ins_ownfft_supported(const int np[3]);
 bool ins_ownfft_supported_slab(const int np[3]);

@@ -4,6 +4,7 @@
 //   cg      : Jacobi-preconditioned CG with fused vector-update + reduction kernels.
 //   project : for the spectral solver the ghost strip / re-pad copies, scalewithvolume! and the periodic
 //             apply_bc_p! are folded into the divergence and gradient kernels.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
@@ -781,11 +782,59 @@ inline BoxLaunch full_box(const GridDev& g) {
   return l;
 }
 
+// K<2> or K<3> by the dimension of `g`, on stream `s` (both from the enclosing scope), then the launch check
+#define LAUNCH_D(K, grid, block, ...)                                           \
+  do {                                                                          \
+    if (g.D == 2)                                                               \
+      hipLaunchKernelGGL(K<2>, grid, block, 0, s, __VA_ARGS__);                 \
+    else                                                                        \
+      hipLaunchKernelGGL(K<3>, grid, block, 0, s, __VA_ARGS__);                 \
+    INS_LAUNCH_CHECK();                                                         \
+  } while (0)
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
 // spectral
 // ------------------------------------------------------------------------------------------------
+static inline bool own_route(SpectralRoute r) { return r >= ROUTE_OWN2D; }  // every pass is one of the library's own kernels: no rocFFT plan
+
+// Which launch sequence a box gets: a function of the box and of the option values at the time of the call, with no HIP call.  ins_poisson_spectral_create
+// calls it once, and the route-selecting switches (INS_DISABLE_OWNFFT, INS_OWNFFT_POW2_ONLY, INS_DISABLE_ZSOLVE, INS_DISABLE_LINE3, INS_DISABLE_XYFUSED,
+// INS_YZ_FUSED, INS_YZ_PARTITIONS, INS_DISABLE_YZ_FUSED) are read nowhere else: ins_set_option does not move a solver that exists to another route.
+static SpectralRoute ins_spectral_choose(int D, const int np[3], int* yz_P) {
+  *yz_P = 0;
+  if (D == 2) {  // power-of-two boxes run on own passes
+    const int np2[3] = {np[0], 16, np[1]};
+    if (!ins_ownfft_supported(np2)) return ROUTE_ROCFFT;
+    return ins_ownfft_xy_supported(np[0], np[1]) ? ROUTE_OWN2D_ONE : ROUTE_OWN2D;
+  }
+  if (!ins_ownfft_supported_mixed(np)) return ins_zsolve_supported(np[2]) ? ROUTE_ROCFFT_ZFUSED : ROUTE_ROCFFT;
+  // the four-pass route (opt-in) rides on the LDS y passes; otherwise the y passes run on the register passes wherever they exist
+  if ((*yz_P = ins_ownfft_yz_partitions(np[0] / 2 + 1, np[1], np[2]))) return ROUTE_OWN_YZ;
+  if (ins_line3_supported(np[1])) return ROUTE_OWN_LINE3;
+  return ins_ownfft_xy_supported(np[0], np[1]) ? ROUTE_OWN_XY : ROUTE_OWN_LDS;
+}
+
+static KyOrder ins_spectral_ky_order(SpectralRoute r) {
+  switch (r) {
+    case ROUTE_OWN_LDS:
+    case ROUTE_OWN_XY:
+    case ROUTE_OWN_YZ: return KY_DIGITREV;  // k_yfft, k_xyfwd and k_yz_fwd share one storage order (ins_fft.hip)
+    case ROUTE_OWN_LINE3: return KY_LINE3;
+    default: return KY_NATURAL;  // rocFFT; the 2-D kernels index the symbol by frequency
+  }
+}
+
+// out[position] = ay[frequency held there] for a y pass that leaves ky in `order`
+static void permute_ky(KyOrder order, int n, const double* ay, double* out) {
+  switch (order) {
+    case KY_DIGITREV: return ins_ownfft_permute_symbol(n, ay, out);
+    case KY_LINE3: return ins_line3_permute_symbol(n, ay, out);
+    case KY_NATURAL: std::copy(ay, ay + n, out);
+  }
+}
+
 extern "C" int ins_poisson_spectral_create(const ins_grid_t* G, ins_poisson_t** out) {
   INS_REQUIRE(G && out, "null argument");
   // assert_uniform_periodic (utils.jl:1-13)
@@ -811,13 +860,10 @@ extern "C" int ins_poisson_spectral_create(const ins_grid_t* G, ins_poisson_t** 
     ins_poisson_destroy(ps);
     return code;
   };
-  ps->ownfft = D == 3 && ins_ownfft_supported_mixed(ps->np);
-  // 2-D power-of-two boxes: own x passes around the fused solve kernel run along y (FFT · symbol · inverse FFT in one pass):
-  // three kernels instead of rocFFT's eight plus its three staging copies per solve
-  const int np2[3] = {ps->np[0], 16, ps->np[1]};
-  const bool own2d = D == 2 && ins_ownfft_supported(np2);
-  if (own2d) ps->ownfft = true;
-  if (ps->ownfft) {  // rows of phat padded to whole 128-B lines: the y / z tiles then never straddle a line (profiles/r01f_pmc_traffic.json)
+  ps->route = ins_spectral_choose(D, ps->np, &ps->yz_P);
+  ps->ky_order = ins_spectral_ky_order(ps->route);
+  const bool own = own_route(ps->route), own2d = ps->route == ROUTE_OWN2D || ps->route == ROUTE_OWN2D_ONE;
+  if (own) {  // rows of phat padded to whole 128-B lines: the y / z tiles then never straddle a line (profiles/r01f_pmc_traffic.json)
     ps->kxs = ins_opt(OPT_INS_PHAT_DENSE) ? ps->kmax[0] : ((ps->kmax[0] + 7) & ~7);
     ncplx = (long long)ps->kxs * ps->kmax[1] * ps->kmax[2];
   }
@@ -833,14 +879,9 @@ extern "C" int ins_poisson_spectral_create(const ins_grid_t* G, ins_poisson_t** 
       const double sn = std::sin(M_PI * ((double)k / ps->np[a]));
       ah[k] = 4 * om * sn * sn / (G->h[a] * G->h[a]);
     }
-    if (ps->ownfft && D == 3 && a == 1) {  // the own y pass leaves ky in its storage order: digit-reversed (ins_fft.hip) or that of the register passes (k_line3)
-      // the four-pass route (opt-in) rides on the LDS y passes; otherwise the y passes run on the register passes wherever they exist
-      ps->y3 = ins_line3_supported(ps->np[1]) && ins_ownfft_yz_partitions(ps->kmax[0], ps->np[1], ps->np[2]) == 0;
+    if (a == 1) {  // the route's y pass leaves ky in its storage order
       std::vector<double> perm(ah.size());
-      if (ps->y3)
-        ins_line3_permute_symbol(ps->np[1], ah.data(), perm.data());
-      else
-        ins_ownfft_permute_symbol(ps->np[1], ah.data(), perm.data());
+      permute_ky(ps->ky_order, ps->np[1], ah.data(), perm.data());
       ah.swap(perm);
     }
     if (hipMalloc(&ps->ahat[a], ah.size() * sizeof(double)) != hipSuccess ||
@@ -849,23 +890,17 @@ extern "C" int ins_poisson_spectral_create(const ins_grid_t* G, ins_poisson_t** 
       return fail(INS_ERR_HIP);
     }
   }
-  // plan_rfft(pI): all D dims, real -> half-complex along x (pressure.jl:316).  hipFFT takes lengths slowest first.
-  // plan_rfft(pI): all D dims, real -> half-complex along x (pressure.jl:316); hipFFT takes lengths slowest first.
-  // 3-D with a power-of-two nz: batched 2-D (x,y) plans + ONE fused z kernel (FFT · symbol · inverse FFT) = 5 passes.
-  if (own2d) {
+  if (own2d) {  // own x passes around the fused solve kernel run along y (FFT · symbol · inverse FFT in one pass): three kernels instead of rocFFT's
+                // eight plus its three staging copies per solve
     if ((rc = ins_zsolve_twiddles(ps->np[0], &ps->tw_x))) return fail(rc);
     if ((rc = ins_zsolve_twiddles(ps->np[1], &ps->tw))) return fail(rc);
     // the solve kernel adds ay[line / kxs] to the symbol: one "row" of lines here, contributing nothing
     if (hipMalloc(&ps->ahat[2], sizeof(double)) != hipSuccess || hipMemset(ps->ahat[2], 0, sizeof(double)) != hipSuccess) return fail(INS_ERR_HIP);
-    ps->zfused = true;
-  } else if (ps->ownfft) {  // no rocFFT plans at all
+  } else if (own) {  // no rocFFT plans at all
     if ((rc = ins_zsolve_twiddles(ps->np[0], &ps->tw_x))) return fail(rc);
     if ((rc = ins_zsolve_twiddles(ps->np[1], &ps->tw_y))) return fail(rc);
     if ((rc = ins_zsolve_twiddles(ps->np[2], &ps->tw))) return fail(rc);
-    ps->zfused = true;
-    // four passes instead of five where the box allows it: the z direction as tridiagonal systems carried by the two y passes (ins_fft.hip, k_yz_*)
-    ps->yz_P = ins_ownfft_yz_partitions(ps->kmax[0], ps->np[1], ps->np[2]);
-    if (ps->yz_P) {
+    if (ps->route == ROUTE_OWN_YZ) {  // four passes instead of five: the z direction as tridiagonal systems carried by the two y passes (ins_fft.hip, k_yz_*)
       const long long nc = ins_ownfft_yz_scratch(ps->kmax[0], ps->np[1], ps->np[2], ps->yz_P);
       if (hipMalloc(&ps->yz_scratch, nc * 2 * sizeof(double)) != hipSuccess) {
         ins_set_error("hipMalloc(yz scratch) failed");
@@ -873,94 +908,107 @@ extern "C" int ins_poisson_spectral_create(const ins_grid_t* G, ins_poisson_t** 
       }
     }
   } else {
+    // plan_rfft(pI): all D dims, real -> half-complex along x (pressure.jl:316); hipFFT takes lengths slowest first.
+    // ROUTE_ROCFFT_ZFUSED: batched 2-D (x,y) plans + ONE fused z kernel (FFT · symbol · inverse FFT) = 5 passes.
     int nfull[3] = {ps->np[2], ps->np[1], ps->np[0]};
-    ps->zfused = D == 3 && ins_zsolve_supported(ps->np[2]);
-    rc = ps->zfused ? ins_fft_make_real_plans(&ps->plan_fwd, &ps->plan_inv, 2, nfull + 1, ps->np[2])
-                    : ins_fft_make_real_plans(&ps->plan_fwd, &ps->plan_inv, D, nfull + (3 - D), 1);
-    if (rc) return fail(rc);
-    ps->plans = true;
-    if (ps->zfused && (rc = ins_zsolve_twiddles(ps->np[2], &ps->tw))) return fail(rc);
+    const bool zfused = ps->route == ROUTE_ROCFFT_ZFUSED;
+    rc = zfused ? ins_fft_make_real_plans(&ps->plan_fwd, &ps->plan_inv, 2, nfull + 1, ps->np[2])
+                : ins_fft_make_real_plans(&ps->plan_fwd, &ps->plan_inv, D, nfull + (3 - D), 1);
+    if (rc) {
+      ps->plan_fwd = ps->plan_inv = 0;  // nothing for ins_poisson_destroy to release
+      return fail(rc);
+    }
+    if (zfused && (rc = ins_zsolve_twiddles(ps->np[2], &ps->tw))) return fail(rc);
   }
   *out = ps;
   return INS_OK;
 }
 
-// pI -> pI through the five own passes; from_u != nullptr: the right-hand side Ω·div(u) is formed inside pass 1
-static int ownfft_transform(ins_poisson* ps, const double* from_u, hipStream_t s, int src_code = 1) {
-  const int n0 = ps->np[0], n1 = ps->np[1], n2 = ps->np[2], kxn = ps->kmax[0], kxs = ps->kxs;
-  double* ph = reinterpret_cast<double*>(ps->phat);
-  int rc;
-  if (ps->grid->g.D == 2) {  // x forward, fused solve along y (lines = kx, "planes" = ky), x inverse
-    if (ins_ownfft_xy_supported(n0, n1))  // up to 64 x 64 volumes: the whole solve as one launch
-      return ins_k_ownfft_xysolve2d(ps->grid, ps->pI, 0, ps->pI, n0, n1, ps->tw_x, ps->tw, ps->ahat[0], ps->ahat[1], s);
-    if ((rc = ins_k_ownfft_xfwd(ps->grid, ps->pI, false, ph, n0, n1, 1, ps->tw_x, s, kxs))) return rc;
-    if ((rc = ins_k_zsolve(ph, n1, (long long)kxs, ps->ahat[0], kxn, ps->ahat[2], ps->ahat[1], ps->tw, 1.0 / ((double)n0 * n1), true, s, kxs))) return rc;
-    return ins_k_ownfft_xinv(ph, ps->pI, n0, n1, 1, ps->tw_x, s, kxs);
-  }
-  // small planes (16 .. 64 on both sides): the x and the y pass of a plane as one kernel each way — four launches per solve... three: xy forward, z, xy inverse
-  if (!ps->y3 && !ps->yz_P && (src_code == 1 || !from_u) && ins_ownfft_xy_supported(n0, n1)) {
-    if ((rc = ins_k_ownfft_xy(ps->grid, from_u ? from_u : ps->pI, from_u ? 1 : 0, ph, nullptr, n0, n1, n2, ps->tw_x, ps->tw_y, false, s, kxs))) return rc;
-    const double inv_n = 1.0 / ((double)n0 * n1 * n2);
-    if ((rc = ins_k_zsolve(ph, n2, (long long)kxs * n1, ps->ahat[0], kxn, ps->ahat[1], ps->ahat[2], ps->tw, inv_n, true, s, kxs))) return rc;
-    return ins_k_ownfft_xy(nullptr, nullptr, 0, ph, ps->pI, n0, n1, n2, ps->tw_x, ps->tw_y, true, s, kxs);
-  }
-  if ((rc = ins_k_ownfft_xfwd(ps->grid, from_u ? from_u : ps->pI, from_u ? src_code : 0, ph, n0, n1, n2, ps->tw_x, s, kxs))) return rc;
-  if (ps->yz_P && !ins_opt(OPT_INS_DISABLE_YZ_FUSED)) {
-    const ins_grid* G = ps->grid;
-    const double c = G->h[0] * G->h[1] / G->h[2];  // Ω/Δz²
-    if ((rc = ins_k_ownfft_yz_solve(ph, kxn, n1, n2, kxs, ps->yz_P, ps->ahat[0], ps->ahat[1], c, -1.0 / ((double)n0 * n1), ps->tw_y, ps->yz_scratch, s))) return rc;
-    return ins_k_ownfft_xinv(ph, ps->pI, n0, n1, n2, ps->tw_x, s, kxs);
-  }
-  if ((rc = ps->y3 ? ins_k_line3_y(ph, kxn, n1, n2, ps->tw_y, false, s, kxs) : ins_k_ownfft_y(ph, kxn, n1, n2, ps->tw_y, false, s, kxs))) return rc;
-  const double inv_n = 1.0 / ((double)n0 * n1 * n2);
-  if ((rc = ins_k_zsolve(ph, n2, (long long)kxs * n1, ps->ahat[0], kxn, ps->ahat[1], ps->ahat[2], ps->tw, inv_n, true, s, kxs))) return rc;
-  if ((rc = ps->y3 ? ins_k_line3_y(ph, kxn, n1, n2, ps->tw_y, true, s, kxs) : ins_k_ownfft_y(ph, kxn, n1, n2, ps->tw_y, true, s, kxs))) return rc;
-  return ins_k_ownfft_xinv(ph, ps->pI, n0, n1, n2, ps->tw_x, s, kxs);
+// The route a solve with right-hand-side source `src` takes on this solver: its own, with one exception.  The forward kernel of ROUTE_OWN_XY forms only
+// XSRC_PI and XSRC_DIV; any other source (the float family's XSRC_DIV_U32) runs the sequence of ROUTE_OWN_LDS, whose y pass leaves ky in the same order.
+static SpectralRoute route_for_source(const ins_poisson* ps, int src) {
+  return (ps->route == ROUTE_OWN_XY && src != XSRC_PI && src != XSRC_DIV) ? ROUTE_OWN_LDS : ps->route;
 }
 
-static int spectral_transform(ins_poisson* ps, hipStream_t s) {
+// pI <- solution of L p = f through the solver's route.  u == nullptr: f is in pI.  Own routes only: f = Ω·div(u) is formed from u inside the first
+// pass, as source `src` (3-D: XSRC_DIV, XSRC_DIV_U32; 2-D: XSRC_DIV_2D).
+static int spectral_transform(ins_poisson* ps, hipStream_t s, const double* u = nullptr, int src = XSRC_DIV) {
   const GridDev& g = ps->grid->g;
-  if (ps->ownfft) return ownfft_transform(ps, nullptr, s);
-  INS_FFT_TRY(hipfftSetStream(ps->plan_fwd, s));
-  INS_FFT_TRY(hipfftSetStream(ps->plan_inv, s));
-  INS_FFT_TRY(hipfftExecD2Z(ps->plan_fwd, ps->pI, ps->phat));
-  double inv_n = 1.0;
-  for (int a = 0; a < g.D; ++a) inv_n /= ps->np[a];
-  if (ps->zfused) {
-    int rc = ins_k_zsolve(reinterpret_cast<double*>(ps->phat), ps->np[2], (long long)ps->kmax[0] * ps->kmax[1], ps->ahat[0], ps->kmax[0],
-                          ps->ahat[1], ps->ahat[2], ps->tw, inv_n, true, s);
-    if (rc) return rc;
-    INS_FFT_TRY(hipfftExecZ2D(ps->plan_inv, ps->phat, ps->pI));
-    return INS_OK;
+  const int n0 = ps->np[0], n1 = ps->np[1], n2 = ps->np[2], kxn = ps->kmax[0], kxs = ps->kxs;
+  double* ph = reinterpret_cast<double*>(ps->phat);
+  const double* f = u ? u : ps->pI;
+  if (!u) src = XSRC_PI;
+  const SpectralRoute route = route_for_source(ps, src);
+  INS_REQUIRE(ins_spectral_ky_order(route) == ps->ky_order, "spectral solve: the route for this source leaves ky in another order than the solver's symbol");
+  const double inv_n = 1.0 / ((double)n0 * n1 * n2);  // own routes (n2 == 1 in 2-D)
+  auto zpass = [&]() { return ins_k_zsolve(ph, n2, (long long)kxs * n1, ps->ahat[0], kxn, ps->ahat[1], ps->ahat[2], ps->tw, inv_n, true, s, kxs); };
+  int rc;
+  switch (route) {
+    case ROUTE_ROCFFT:
+    case ROUTE_ROCFFT_ZFUSED: {
+      INS_REQUIRE(!u, "spectral solve: the rocFFT routes take their right-hand side from pI");
+      INS_FFT_TRY(hipfftSetStream(ps->plan_fwd, s));
+      INS_FFT_TRY(hipfftSetStream(ps->plan_inv, s));
+      INS_FFT_TRY(hipfftExecD2Z(ps->plan_fwd, ps->pI, ps->phat));
+      double inv_np = 1.0;  // (divided direction by direction here: the last bit differs from inv_n on sides that are no power of two)
+      for (int a = 0; a < g.D; ++a) inv_np /= ps->np[a];
+      if (route == ROUTE_ROCFFT_ZFUSED) {
+        if ((rc = ins_k_zsolve(ph, n2, (long long)kxn * ps->kmax[1], ps->ahat[0], kxn, ps->ahat[1], ps->ahat[2], ps->tw, inv_np, true, s))) return rc;
+      } else {
+        dim3 block(64, 4, 1), grid(cdiv(kxn, 64), cdiv(ps->kmax[1], 4), g.D == 3 ? ps->kmax[2] : 1);
+        LAUNCH_D(k_symbol, grid, block, ps->phat, ps->ahat[0], ps->ahat[1], ps->ahat[2], kxn, ps->kmax[1], inv_np);  // (2-D: ahat[2] == nullptr)
+      }
+      INS_FFT_TRY(hipfftExecZ2D(ps->plan_inv, ps->phat, ps->pI));
+      return INS_OK;
+    }
+    case ROUTE_OWN2D_ONE:  // the whole solve as one launch (the launcher takes the source as a flag: its divergence is the 2-D one)
+      return ins_k_ownfft_xysolve2d(ps->grid, f, u ? XSRC_DIV : XSRC_PI, ps->pI, n0, n1, ps->tw_x, ps->tw, ps->ahat[0], ps->ahat[1], s);
+    case ROUTE_OWN2D:  // x forward, fused solve along y (lines = kx, "planes" = ky), x inverse
+      if ((rc = ins_k_ownfft_xfwd(ps->grid, f, src, ph, n0, n1, 1, ps->tw_x, s, kxs))) return rc;
+      if ((rc = ins_k_zsolve(ph, n1, (long long)kxs, ps->ahat[0], kxn, ps->ahat[2], ps->ahat[1], ps->tw, inv_n, true, s, kxs))) return rc;
+      return ins_k_ownfft_xinv(ph, ps->pI, n0, n1, 1, ps->tw_x, s, kxs);
+    case ROUTE_OWN_XY:  // the x and the y pass of a plane as one kernel each way: xy forward, z, xy inverse
+      if ((rc = ins_k_ownfft_xy(ps->grid, f, src, ph, nullptr, n0, n1, n2, ps->tw_x, ps->tw_y, false, s, kxs))) return rc;
+      if ((rc = zpass())) return rc;
+      return ins_k_ownfft_xy(nullptr, nullptr, XSRC_PI, ph, ps->pI, n0, n1, n2, ps->tw_x, ps->tw_y, true, s, kxs);
+    case ROUTE_OWN_YZ: {
+      if ((rc = ins_k_ownfft_xfwd(ps->grid, f, src, ph, n0, n1, n2, ps->tw_x, s, kxs))) return rc;
+      const ins_grid* G = ps->grid;
+      const double c = G->h[0] * G->h[1] / G->h[2];  // Ω/Δz²
+      if ((rc = ins_k_ownfft_yz_solve(ph, kxn, n1, n2, kxs, ps->yz_P, ps->ahat[0], ps->ahat[1], c, -1.0 / ((double)n0 * n1), ps->tw_y, ps->yz_scratch, s))) return rc;
+      return ins_k_ownfft_xinv(ph, ps->pI, n0, n1, n2, ps->tw_x, s, kxs);
+    }
+    case ROUTE_OWN_LDS:
+    case ROUTE_OWN_LINE3: {
+      const auto ypass = route == ROUTE_OWN_LINE3 ? ins_k_line3_y : ins_k_ownfft_y;
+      if ((rc = ins_k_ownfft_xfwd(ps->grid, f, src, ph, n0, n1, n2, ps->tw_x, s, kxs))) return rc;
+      if ((rc = ypass(ph, kxn, n1, n2, ps->tw_y, false, s, kxs))) return rc;
+      if ((rc = zpass())) return rc;
+      if ((rc = ypass(ph, kxn, n1, n2, ps->tw_y, true, s, kxs))) return rc;
+      return ins_k_ownfft_xinv(ph, ps->pI, n0, n1, n2, ps->tw_x, s, kxs);
+    }
   }
-  dim3 block(64, 4, 1), grid(cdiv(ps->kmax[0], 64), cdiv(ps->kmax[1], 4), g.D == 3 ? ps->kmax[2] : 1);
+  ins_set_error("spectral solve: unknown route %d", (int)route);
+  return INS_ERR_INVALID;
+}
+
+// copyto!(buf, view(p, Ip)) (PACK)  /  copyto!(view(p, Ip), buf) - *shift           pressure.jl:320, 347
+template <bool PACK>
+static int pack_box(const ins_poisson* ps, double* p, double* buf, hipStream_t s, const double* shift = nullptr) {
+  const GridDev& g = ps->grid->g;
+  dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), g.D == 3 ? ps->np[2] : 1);
   if (g.D == 2)
-    hipLaunchKernelGGL(k_symbol<2>, grid, block, 0, s, ps->phat, ps->ahat[0], ps->ahat[1], (const double*)nullptr, ps->kmax[0],
-                       ps->kmax[1], inv_n);
+    hipLaunchKernelGGL((k_pack<2, PACK>), grid, block, 0, s, g, p, buf, ps->np[0], ps->np[1], shift);
   else
-    hipLaunchKernelGGL(k_symbol<3>, grid, block, 0, s, ps->phat, ps->ahat[0], ps->ahat[1], ps->ahat[2], ps->kmax[0], ps->kmax[1],
-                       inv_n);
+    hipLaunchKernelGGL((k_pack<3, PACK>), grid, block, 0, s, g, p, buf, ps->np[0], ps->np[1], shift);
   INS_LAUNCH_CHECK();
-  INS_FFT_TRY(hipfftExecZ2D(ps->plan_inv, ps->phat, ps->pI));
   return INS_OK;
 }
 
 static int spectral_solve(ins_poisson* ps, double* p, hipStream_t s) {
-  const GridDev& g = ps->grid->g;
-  dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), g.D == 3 ? ps->np[2] : 1);
-  if (g.D == 2)
-    hipLaunchKernelGGL((k_pack<2, true>), grid, block, 0, s, g, p, ps->pI, ps->np[0], ps->np[1]);
-  else
-    hipLaunchKernelGGL((k_pack<3, true>), grid, block, 0, s, g, p, ps->pI, ps->np[0], ps->np[1]);
-  INS_LAUNCH_CHECK();
-  int rc = spectral_transform(ps, s);
-  if (rc) return rc;
-  if (g.D == 2)
-    hipLaunchKernelGGL((k_pack<2, false>), grid, block, 0, s, g, p, ps->pI, ps->np[0], ps->np[1]);
-  else
-    hipLaunchKernelGGL((k_pack<3, false>), grid, block, 0, s, g, p, ps->pI, ps->np[0], ps->np[1]);
-  INS_LAUNCH_CHECK();
-  return INS_OK;
+  int rc;
+  if ((rc = pack_box<true>(ps, p, ps->pI, s)) || (rc = spectral_transform(ps, s))) return rc;
+  return pack_box<false>(ps, p, ps->pI, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1015,6 +1063,18 @@ static int finish_sum(const ins_grid* G, double* partial_dev, int nblk, hipStrea
 }
 
 
+// p[Ip] -= mean(p[Ip]) (bordered mode, before and after the iteration).  Blocking.
+static int cg_remove_mean(ins_poisson* ps, double* p, hipStream_t s) {
+  const ins_grid* G = ps->grid;
+  const GridDev& g = G->g;
+  const BoxLaunch l = full_box(g);
+  double sum;
+  int rc = ins_k_reduce(G, 3, p, nullptr, g.ip_lo, g.ip_hi, &sum, s);
+  if (rc) return rc;
+  LAUNCH_D(k_shift, l.grid, l.block, g, p, sum / (double)ps->ndof);
+  return INS_OK;
+}
+
 // Device-resident scalars (default); INS_CG_HOSTSYNC=1 keeps the reference's three host reads per iteration (cg_solve_hostsync below).
 static int cg_solve_device(ins_poisson* ps, double* p, hipStream_t s) {
   const ins_grid* G = ps->grid;
@@ -1042,12 +1102,7 @@ static int cg_solve_device(ins_poisson* ps, double* p, hipStream_t s) {
   const bool bordered = ps->bordered && ps->singular;
   if (bordered) {
     INS_REQUIRE(!ps->comm, "bordered CG on slabs is not implemented");
-    double sum;
-    if ((rc = ins_k_reduce(G, 3, p, nullptr, g.ip_lo, g.ip_hi, &sum, s))) return rc;
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_shift<2>, full_box(g).grid, full_box(g).block, 0, s, g, p, sum / (double)ps->ndof);
-    else
-      hipLaunchKernelGGL(k_shift<3>, full_box(g).grid, full_box(g).block, 0, s, g, p, sum / (double)ps->ndof);
+    if ((rc = cg_remove_mean(ps, p, s))) return rc;
   }
   hipLaunchKernelGGL(k_cgd_init, dim3(nb), dim3(256), 0, s, g, n, p, ps->r, ps->q, ps->L, partial);
   if ((rc = fold(0))) return rc;
@@ -1070,15 +1125,7 @@ static int cg_solve_device(ins_poisson* ps, double* p, hipStream_t s) {
       if ((rc = fold(3))) return rc;
     }
   }
-  if (bordered) {
-    double sum;
-    if ((rc = ins_k_reduce(G, 3, p, nullptr, g.ip_lo, g.ip_hi, &sum, s))) return rc;
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_shift<2>, full_box(g).grid, full_box(g).block, 0, s, g, p, sum / (double)ps->ndof);
-    else
-      hipLaunchKernelGGL(k_shift<3>, full_box(g).grid, full_box(g).block, 0, s, g, p, sum / (double)ps->ndof);
-    INS_LAUNCH_CHECK();
-  }
+  if (bordered && (rc = cg_remove_mean(ps, p, s))) return rc;
   ps->last_iter = (long long)ps->cg_host[CG_ITERS];
   ps->last_res = ps->cg_host[CG_RES];
   return INS_OK;
@@ -1098,22 +1145,9 @@ static int cg_solve(ins_poisson* ps, double* p, hipStream_t s) {
   } guard{partial};
   int rc;
   double ss;
-#define LAUNCH_D(K, ...)                                                        \
-  do {                                                                          \
-    if (g.D == 2)                                                               \
-      hipLaunchKernelGGL(K<2>, l.grid, l.block, 0, s, __VA_ARGS__);             \
-    else                                                                        \
-      hipLaunchKernelGGL(K<3>, l.grid, l.block, 0, s, __VA_ARGS__);             \
-    INS_LAUNCH_CHECK();                                                         \
-  } while (0)
-
   const bool bordered = ps->bordered && ps->singular;
-  if (bordered) {
-    double sum;
-    if ((rc = ins_k_reduce(G, 3, p, nullptr, g.ip_lo, g.ip_hi, &sum, s))) return rc;
-    LAUNCH_D(k_shift, g, p, sum / (double)ps->ndof);
-  }
-  LAUNCH_D(k_cg_init, g, p, ps->r, ps->q, ps->L, partial);
+  if (bordered && (rc = cg_remove_mean(ps, p, s))) return rc;
+  LAUNCH_D(k_cg_init, l.grid, l.block, g, p, ps->r, ps->q, ps->L, partial);
   if ((rc = finish_sum(G, partial, l.nblk, s, &ss))) return rc;
   double residual = std::sqrt(ss);
   const double tolerance = std::fmax(ps->reltol * residual, ps->abstol);
@@ -1121,28 +1155,23 @@ static int cg_solve(ins_poisson* ps, double* p, hipStream_t s) {
   long long it = 0;
   while (it < ps->maxiter && residual > tolerance) {
     double rho, qL;
-    LAUNCH_D(k_cg_precond, g, ps->r, ps->dinv, ps->L, partial);
+    LAUNCH_D(k_cg_precond, l.grid, l.block, g, ps->r, ps->dinv, ps->L, partial);
     if ((rc = finish_sum(G, partial, l.nblk, s, &rho))) return rc;
     const double beta = rho / rho_prev;
     hipLaunchKernelGGL(k_cg_dir, dim3(std::min<long long>((G->ncell + 255) / 256, 4096)), dim3(256), 0, s, G->ncell, beta, ps->L, ps->q);
     INS_LAUNCH_CHECK();
     if ((rc = ins_k_apply_bc_p(G, ps->q, s))) return rc;
     if ((rc = ins_k_laplacian(G, ps->q, ps->L, s))) return rc;
-    LAUNCH_D(k_cg_dot, g, ps->q, ps->L, partial);
+    LAUNCH_D(k_cg_dot, l.grid, l.block, g, ps->q, ps->L, partial);
     if ((rc = finish_sum(G, partial, l.nblk, s, &qL))) return rc;
     const double alpha = rho / qL;
-    LAUNCH_D(k_cg_update, g, alpha, p, ps->r, ps->q, ps->L, partial);
+    LAUNCH_D(k_cg_update, l.grid, l.block, g, alpha, p, ps->r, ps->q, ps->L, partial);
     if ((rc = finish_sum(G, partial, l.nblk, s, &ss))) return rc;
     rho_prev = rho;
     residual = std::sqrt(ss);
     ++it;
   }
-  if (bordered) {
-    double sum;
-    if ((rc = ins_k_reduce(G, 3, p, nullptr, g.ip_lo, g.ip_hi, &sum, s))) return rc;
-    LAUNCH_D(k_shift, g, p, sum / (double)ps->ndof);
-  }
-#undef LAUNCH_D
+  if (bordered && (rc = cg_remove_mean(ps, p, s))) return rc;
   ps->last_iter = it;
   ps->last_res = residual;
   return INS_OK;
@@ -1171,7 +1200,7 @@ extern "C" int ins_poisson_fft_engine(const ins_poisson_t* ps, int32_t* engine) 
     ins_set_error("ins_poisson_fft_engine: null argument");
     return INS_ERR_INVALID;
   }
-  *engine = ps->kind != POISSON_SPECTRAL ? -1 : (ps->ownfft ? 1 : (ps->zfused ? 2 : 0));
+  *engine = ps->kind != POISSON_SPECTRAL ? -1 : (own_route(ps->route) ? 1 : (ps->route == ROUTE_ROCFFT_ZFUSED ? 2 : 0));
   return INS_OK;
 }
 
@@ -1186,7 +1215,7 @@ extern "C" int ins_poisson_yz_partitions(const ins_poisson_t* ps, int32_t* parti
 
 extern "C" int ins_poisson_destroy(ins_poisson_t* ps) {
   if (!ps) return INS_OK;
-  if (ps->plans) {
+  if (ps->plan_fwd) {  // the rocFFT routes
     (void)hipfftDestroy(ps->plan_fwd);
     (void)hipfftDestroy(ps->plan_inv);
     ins_fft_solver_released();
@@ -1212,23 +1241,10 @@ extern "C" int ins_poisson_destroy(ins_poisson_t* ps) {
 
 // psolver_direct: pack Ip -> FDM solve (ins_fdm.hip) -> unpack                     pressure.jl:101-154
 static int fdm_solve(ins_poisson* ps, double* p, hipStream_t s) {
-  const GridDev& g = ps->grid->g;
   double* buf = ins_fdm_buffer(ps->fdm);
-  dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), g.D == 3 ? ps->np[2] : 1);
-  if (g.D == 2)
-    hipLaunchKernelGGL((k_pack<2, true>), grid, block, 0, s, g, p, buf, ps->np[0], ps->np[1]);
-  else
-    hipLaunchKernelGGL((k_pack<3, true>), grid, block, 0, s, g, p, buf, ps->np[0], ps->np[1]);
-  INS_LAUNCH_CHECK();
-  int rc = ins_fdm_solve(ps->fdm, s);
-  if (rc) return rc;
-  const double* shift = ins_fdm_mean(ps->fdm);  // e'p = 0 of the bordered system, applied while unpacking
-  if (g.D == 2)
-    hipLaunchKernelGGL((k_pack<2, false>), grid, block, 0, s, g, p, buf, ps->np[0], ps->np[1], shift);
-  else
-    hipLaunchKernelGGL((k_pack<3, false>), grid, block, 0, s, g, p, buf, ps->np[0], ps->np[1], shift);
-  INS_LAUNCH_CHECK();
-  return INS_OK;
+  int rc;
+  if ((rc = pack_box<true>(ps, p, buf, s)) || (rc = ins_fdm_solve(ps->fdm, s))) return rc;
+  return pack_box<false>(ps, p, buf, s, ins_fdm_mean(ps->fdm));  // e'p = 0 of the bordered system, applied while unpacking
 }
 
 extern "C" int ins_poisson_fdm_create(const ins_grid_t* G, const double* const* V, const double* const* lam, ins_poisson_t** out) {
@@ -1255,53 +1271,32 @@ extern "C" int ins_poisson_fdm_create(const ins_grid_t* G, const double* const* 
     delete ps;
     return rc;
   }
-  if (g.D == 3 && g.bc[2][0] == INS_BC_PERIODIC && g.bc[2][1] == INS_BC_PERIODIC) {  // periodic z: Fourier modes if the spacing is constant
-    const ins_grid_desc_t& d = G->desc;
+  const ins_grid_desc_t& d = G->desc;
+  // constant spacing along direction a, to 4·N·eps·h.  periodic: every Δ and every Δu but the last (Δ/2 by construction, grid.jl:196);
+  // else (between walls): Δ of the volumes 1 .. N-2 only
+  auto uniform = [&](int a, bool periodic) {
+    const double h = d.dx[a][1], tol = 4.0 * d.N[a] * INS_EPS * h;
     bool uni = true;
-    const double hz = d.dx[2][1];
-    const double ztol = 4.0 * d.N[2] * 2.220446049250313e-16 * hz;
-    for (int k = 0; k < d.N[2]; ++k) uni = uni && std::fabs(d.dx[2][k] - hz) <= ztol && (k == d.N[2] - 1 || std::fabs(d.dxu[2][k] - hz) <= ztol);  // (the last Δu is Δ/2 by construction, grid.jl:196)
-    if (uni && (rc = ins_fdm_enable_zfft(ps->fdm, hz, lam[2]))) {
-      ins_poisson_destroy(ps);
-      return rc;
-    }
-    if (uni && g.bc[0][0] == INS_BC_PERIODIC && g.bc[0][1] == INS_BC_PERIODIC) {  // periodic x too (channel flows)
-      const double hx = d.dx[0][1];
-      const double xtol = 4.0 * d.N[0] * 2.220446049250313e-16 * hx;
-      bool unix_ = true;
-      for (int k = 0; k < d.N[0]; ++k) unix_ = unix_ && std::fabs(d.dx[0][k] - hx) <= xtol && (k == d.N[0] - 1 || std::fabs(d.dxu[0][k] - hx) <= xtol);
-      if (unix_ && (rc = ins_fdm_enable_xfft(ps->fdm, hx, lam[0]))) {
-        ins_poisson_destroy(ps);
-        return rc;
-      }
-    }
+    if (periodic)
+      for (int k = 0; k < d.N[a]; ++k) uni = uni && std::fabs(d.dx[a][k] - h) <= tol && (k == d.N[a] - 1 || std::fabs(d.dxu[a][k] - h) <= tol);
+    else
+      for (int k = 1; k < d.N[a] - 1; ++k) uni = uni && std::fabs(d.dx[a][k] - h) <= tol;
+    return uni;
+  };
+  auto periodic = [&](int a) { return g.bc[a][0] == INS_BC_PERIODIC && g.bc[a][1] == INS_BC_PERIODIC; };
+  auto fail = [&](int code) {
+    ins_poisson_destroy(ps);
+    return code;
+  };
+  if (g.D == 3 && periodic(2) && uniform(2, true)) {  // periodic z: Fourier modes if the spacing is constant
+    if ((rc = ins_fdm_enable_zfft(ps->fdm, d.dx[2][1], lam[2]))) return fail(rc);
+    if (periodic(0) && uniform(0, true) && (rc = ins_fdm_enable_xfft(ps->fdm, d.dx[0][1], lam[0]))) return fail(rc);  // periodic x too (channel flows)
   }
-  if (g.D == 3 && g.bc[0][0] == INS_BC_PERIODIC && g.bc[0][1] == INS_BC_PERIODIC && g.bc[1][0] == INS_BC_PERIODIC && g.bc[1][1] == INS_BC_PERIODIC &&
-      !(g.bc[2][0] == INS_BC_PERIODIC && g.bc[2][1] == INS_BC_PERIODIC)) {  // periodic x and y, walls / open sides in z
-    const ins_grid_desc_t& d = G->desc;
-    bool uni = true;
-    double hh[2];
-    for (int a = 0; a < 2; ++a) {
-      hh[a] = d.dx[a][1];
-      const double tol = 4.0 * d.N[a] * 2.220446049250313e-16 * hh[a];
-      for (int k = 0; k < d.N[a]; ++k) uni = uni && std::fabs(d.dx[a][k] - hh[a]) <= tol && (k == d.N[a] - 1 || std::fabs(d.dxu[a][k] - hh[a]) <= tol);
-    }
-    if (uni && (rc = ins_fdm_enable_xyfft(ps->fdm, hh[0], hh[1], lam[0], lam[1]))) {
-      ins_poisson_destroy(ps);
-      return rc;
-    }
+  if (g.D == 3 && periodic(0) && periodic(1) && !periodic(2) && uniform(0, true) && uniform(1, true)) {  // periodic x and y, walls / open sides in z
+    if ((rc = ins_fdm_enable_xyfft(ps->fdm, d.dx[0][1], d.dx[1][1], lam[0], lam[1]))) return fail(rc);
   }
-  if (g.D == 3 && g.bc[2][0] != INS_BC_PERIODIC) {  // uniform z between walls: cosine modes (the enable call checks the eigenvalues it was given)
-    const ins_grid_desc_t& d = G->desc;
-    const double hz = d.dx[2][1];
-    const double ztol = 4.0 * d.N[2] * 2.220446049250313e-16 * hz;
-    bool uni = true;
-    for (int k = 1; k < d.N[2] - 1; ++k) uni = uni && std::fabs(d.dx[2][k] - hz) <= ztol;
-    if (uni && (rc = ins_fdm_enable_zdct(ps->fdm, hz, lam[2]))) {
-      ins_poisson_destroy(ps);
-      return rc;
-    }
-  }
+  // uniform z between walls: cosine modes (the enable call checks the eigenvalues it was given)
+  if (g.D == 3 && g.bc[2][0] != INS_BC_PERIODIC && uniform(2, false) && (rc = ins_fdm_enable_zdct(ps->fdm, d.dx[2][1], lam[2]))) return fail(rc);
   *out = ps;
   return INS_OK;
 }
@@ -1323,6 +1318,23 @@ extern "C" int ins_poisson_solve_f64(ins_poisson_t* ps, double* p, void* stream)
 int ins_fdm_modes(const ins_fdm* F);
 // test hook: which directions of the direct solver run in trigonometric modes (1 Fourier z, 2 Fourier x, 4 Fourier x and y, 8 cosine z)
 extern "C" int ins_dbg_fdm_modes(const ins_poisson_t* ps) { return (ps && ps->kind == POISSON_FDM) ? ins_fdm_modes(ps->fdm) : -1; }
+// test hooks: a live spectral solver's route and ky order (SpectralRoute / KyOrder values; -1: not a spectral solver); the choice for a box under the
+// current option values, without touching the device; the symbol permutation of a ky order and the inverse map of the k_line3 one
+extern "C" int ins_dbg_spectral_route(const ins_poisson_t* ps, int32_t* ky_order) {
+  const bool spectral = ps && ps->kind == POISSON_SPECTRAL;
+  if (ky_order) *ky_order = spectral ? (int32_t)ps->ky_order : -1;
+  return spectral ? (int)ps->route : -1;
+}
+extern "C" int ins_dbg_spectral_choose(int D, int n0, int n1, int n2, int32_t* ky_order, int32_t* partitions) {
+  const int np[3] = {n0, n1, D == 3 ? n2 : 1};
+  int P = 0;
+  const SpectralRoute r = ins_spectral_choose(D, np, &P);
+  if (ky_order) *ky_order = (int32_t)ins_spectral_ky_order(r);
+  if (partitions) *partitions = P;
+  return (int)r;
+}
+extern "C" void ins_dbg_permute_ky(int ky_order, int n, const double* ay, double* out) { permute_ky((KyOrder)ky_order, n, ay, out); }
+extern "C" int ins_dbg_line3_pos_of_freq(int n, int k) { return ins_line3_pos_of_freq(n, k); }
 extern "C" int ins_dbg_fdm_fold_mask(const ins_poisson_t* ps) { return (ps && ps->kind == POISSON_FDM) ? ins_fdm_fold_mask(ps->fdm) : -1; }
 
 extern "C" int ins_poisson_last_info(const ins_poisson_t* ps, int64_t* iterations, double* residual) {
@@ -1365,10 +1377,7 @@ static int fdm_rhs(const ins_grid* G, ins_poisson* ps, const double* u, double* 
 #undef INS_DIVFOLD
   } else {
     const dim3 grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), g.D == 3 ? ps->np[2] : 1);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_div_to_pI<2>, grid, block, 0, s, g, u, buf, ps->np[0], ps->np[1]);
-    else
-      hipLaunchKernelGGL(k_div_to_pI<3>, grid, block, 0, s, g, u, buf, ps->np[0], ps->np[1]);
+    LAUNCH_D(k_div_to_pI, grid, block, g, u, buf, ps->np[0], ps->np[1]);
   }
   INS_LAUNCH_CHECK();
   return INS_OK;
@@ -1406,56 +1415,50 @@ static int fdm_unpack(const ins_grid* G, ins_poisson* ps, double* u, double* p, 
   return INS_OK;
 }
 
-int ins_k_project_fdm_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, double* p, hipStream_t s) {
+// direct solver: Ω·div(u) straight into the solver's buffer, and copy-back - mean + apply_bc_p! in one pass; ucorr != nullptr (u itself): applypressure!
+// on it in that pass too, else the gradient-subtract is left to the caller
+static int fdm_project(const ins_grid* G, ins_poisson* ps, const double* u, double* ucorr, double* p, hipStream_t s) {
   int rc, fm = 0;
   double* buf = ins_fdm_buffer(ps->fdm);
-  if (ins_fdm_takes_u(ps->fdm)) {
+  if (ins_fdm_takes_u(ps->fdm)) {  // periodic x: the divergence is formed inside the solver's x pass
     if ((rc = ins_fdm_solve(ps->fdm, s, G, u))) return rc;
   } else {
     fm = ins_opt(OPT_INS_DISABLE_FDM_FOLDFUSE) ? 0 : ins_fdm_fold_mask(ps->fdm);
     if ((rc = fdm_rhs(G, ps, u, buf, fm, s))) return rc;
     if ((rc = ins_fdm_solve(ps->fdm, s, nullptr, nullptr, fm != 0))) return rc;
   }
-  return fdm_unpack(G, ps, nullptr, p, buf, fm, s);
+  return fdm_unpack(G, ps, ucorr, p, buf, fm, s);
 }
+int ins_k_project_fdm_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, double* p, hipStream_t s) { return fdm_project(G, ps, u, nullptr, p, s); }
 
 int ins_k_project(const ins_grid* G, ins_poisson* ps, double* u, double* p, hipStream_t s) {
   const GridDev& g = G->g;
   int rc;
   if (ps->kind == POISSON_SPECTRAL) {
     dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), g.D == 3 ? ps->np[2] : 1);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_div_to_pI<2>, grid, block, 0, s, g, u, ps->pI, ps->np[0], ps->np[1]);
-    else
-      hipLaunchKernelGGL(k_div_to_pI<3>, grid, block, 0, s, g, u, ps->pI, ps->np[0], ps->np[1]);
-    INS_LAUNCH_CHECK();
+    LAUNCH_D(k_div_to_pI, grid, block, g, u, ps->pI, ps->np[0], ps->np[1]);
     if ((rc = spectral_transform(ps, s))) return rc;
     dim3 gridp(cdiv(g.N[0], 64), cdiv(g.N[1], 4), (unsigned)g.N[2]);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_grad_from_pI<2>, gridp, block, 0, s, g, u, p, ps->pI, ps->np[0], ps->np[1], 1);
-    else
-      hipLaunchKernelGGL(k_grad_from_pI<3>, gridp, block, 0, s, g, u, p, ps->pI, ps->np[0], ps->np[1], ps->np[2]);
-    INS_LAUNCH_CHECK();
+    LAUNCH_D(k_grad_from_pI, gridp, block, g, u, p, ps->pI, ps->np[0], ps->np[1], ps->np[2]);  // (2-D: np[2] == 1)
     return INS_OK;
   }
-  if (ps->kind == POISSON_FDM && !ins_opt(OPT_INS_DISABLE_FDM_FUSED)) {
-    // direct solver: Ω·div(u) straight into the solver's buffer, and copy-back - mean + apply_bc_p! + applypressure! in one pass
-    double* buf = ins_fdm_buffer(ps->fdm);
-    int fm = 0;
-    if (ins_fdm_takes_u(ps->fdm)) {  // periodic x: the divergence is formed inside the solver's x pass
-      if ((rc = ins_fdm_solve(ps->fdm, s, G, u))) return rc;
-    } else {
-      fm = ins_opt(OPT_INS_DISABLE_FDM_FOLDFUSE) ? 0 : ins_fdm_fold_mask(ps->fdm);
-      if ((rc = fdm_rhs(G, ps, u, buf, fm, s))) return rc;
-      if ((rc = ins_fdm_solve(ps->fdm, s, nullptr, nullptr, fm != 0))) return rc;
-    }
-    return fdm_unpack(G, ps, u, p, buf, fm, s);
-  }
+  if (ins_k_project_fdm_fused(ps)) return fdm_project(G, ps, u, u, p, s);
   if ((rc = ins_k_divergence(G, u, p, s))) return rc;
   if ((rc = ins_k_scalewithvolume(G, p, s))) return rc;
   if ((rc = ins_k_poisson_solve(ps, p, s))) return rc;
   if ((rc = ins_k_apply_bc_p(G, p, s))) return rc;
   return ins_k_applypressure(G, u, p, s);
+}
+
+// First half of the fused periodic projection only: pI <- solution of L p = Ω div(u) (u: interior volumes valid).
+// The gradient-subtract is left to the next stage's stencil kernel (k_momentum_flux<..., CORR>).
+int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s) {
+  const GridDev& g = G->g;
+  if (own_route(ps->route)) return spectral_transform(ps, s, u);  // K2 lives inside the first pass
+  dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), ps->np[2]);
+  hipLaunchKernelGGL((k_div_to_pI<3, true>), grid, block, 0, s, g, u, ps->pI, ps->np[0], ps->np[1]);
+  INS_LAUNCH_CHECK();
+  return spectral_transform(ps, s);
 }
 
 // project! for the fused periodic RK stage: u holds valid INTERIOR values only; on return its interior is
@@ -1464,15 +1467,8 @@ int ins_k_project(const ins_grid* G, ins_poisson* ps, double* u, double* p, hipS
 int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout) {
   const GridDev& g = G->g;
   dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), ps->np[2]);
-  int rc;
   double* dst = uout ? uout : u;
-  if (ps->ownfft) {  // K2 lives inside the x-forward pass
-    rc = ownfft_transform(ps, u, s);
-  } else {
-    hipLaunchKernelGGL((k_div_to_pI<3, true>), grid, block, 0, s, g, u, ps->pI, ps->np[0], ps->np[1]);
-    INS_LAUNCH_CHECK();
-    rc = spectral_transform(ps, s);
-  }
+  int rc = ins_k_project_periodic_solve_only(G, ps, u, s);
   if (rc) return rc;
   if (keep_p)
     hipLaunchKernelGGL(k_grad_ghost3<true>, grid, block, 0, s, g, dst, p, ps->pI, ps->np[0], ps->np[1], ps->np[2], (const double*)u);
@@ -1482,20 +1478,17 @@ int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, 
   return INS_OK;
 }
 
-// The same for 2-D (own x passes + the fused solve kernel along y): x forward with the divergence formed inside, solve, x inverse,
-// gradient-subtract with the periodic ghost images.  Four launches per projection.
+// The same for 2-D (ROUTE_OWN2D, ROUTE_OWN2D_ONE): the solve with the divergence formed inside its first pass; the next stage kernel corrects in registers ...
+bool ins_poisson_own2d(const ins_poisson* ps) { return ps->kind == POISSON_SPECTRAL && (ps->route == ROUTE_OWN2D || ps->route == ROUTE_OWN2D_ONE); }
+int ins_k_project_periodic_solve_only_2d(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s) {
+  return spectral_transform(ps, s, u, XSRC_DIV_2D);
+}
+// ... or this pass subtracts the gradient and writes the periodic ghost images
 int ins_k_project_periodic_fused_2d(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s) {
   const GridDev& g = G->g;
-  const int n0 = ps->np[0], n1 = ps->np[1], kxn = ps->kmax[0], kxs = ps->kxs;
-  double* ph = reinterpret_cast<double*>(ps->phat);
-  int rc;
-  if (ins_ownfft_xy_supported(n0, n1)) {
-    if ((rc = ins_k_ownfft_xysolve2d(G, u, 1, ps->pI, n0, n1, ps->tw_x, ps->tw, ps->ahat[0], ps->ahat[1], s))) return rc;
-  } else {
-    if ((rc = ins_k_ownfft_xfwd(G, u, 3, ph, n0, n1, 1, ps->tw_x, s, kxs))) return rc;
-    if ((rc = ins_k_zsolve(ph, n1, (long long)kxs, ps->ahat[0], kxn, ps->ahat[2], ps->ahat[1], ps->tw, 1.0 / ((double)n0 * n1), true, s, kxs))) return rc;
-    if ((rc = ins_k_ownfft_xinv(ph, ps->pI, n0, n1, 1, ps->tw_x, s, kxs))) return rc;
-  }
+  const int n0 = ps->np[0], n1 = ps->np[1];
+  int rc = ins_k_project_periodic_solve_only_2d(G, ps, u, s);
+  if (rc) return rc;
   dim3 block(64, 4, 1), grid(cdiv(n0, 64), cdiv(n1, 4), 1);
   if (keep_p)
     hipLaunchKernelGGL((k_grad_ghost<2, true>), grid, block, 0, s, g, u, p, ps->pI, n0, n1, 1);
@@ -1505,41 +1498,18 @@ int ins_k_project_periodic_fused_2d(const ins_grid* G, ins_poisson* ps, double* 
   return INS_OK;
 }
 
-// first half of the 2-D fused projection only: pI <- solution of L p = Ω div(u) (u: interior volumes valid); the next stage kernel corrects in registers
-int ins_k_project_periodic_solve_only_2d(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s) {
-  const int n0 = ps->np[0], n1 = ps->np[1], kxn = ps->kmax[0], kxs = ps->kxs;
-  double* ph = reinterpret_cast<double*>(ps->phat);
-  int rc;
-  if (ins_ownfft_xy_supported(n0, n1)) return ins_k_ownfft_xysolve2d(G, u, 1, ps->pI, n0, n1, ps->tw_x, ps->tw, ps->ahat[0], ps->ahat[1], s);
-  if ((rc = ins_k_ownfft_xfwd(G, u, 3, ph, n0, n1, 1, ps->tw_x, s, kxs))) return rc;
-  if ((rc = ins_k_zsolve(ph, n1, (long long)kxs, ps->ahat[0], kxn, ps->ahat[2], ps->ahat[1], ps->tw, 1.0 / ((double)n0 * n1), true, s, kxs))) return rc;
-  return ins_k_ownfft_xinv(ph, ps->pI, n0, n1, 1, ps->tw_x, s, kxs);
-}
-
-bool ins_poisson_own2d(const ins_poisson* ps) { return ps->kind == POISSON_SPECTRAL && ps->ownfft && ps->grid->g.D == 2; }
-
-// First half of the fused periodic projection only: pI <- solution of L p = Ω div(u) (u: interior volumes valid).
-// The gradient-subtract is left to the next stage's stencil kernel (k_momentum_flux<..., CORR>).
-int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s) {
-  const GridDev& g = G->g;
-  if (ps->ownfft) return ownfft_transform(ps, u, s);
-  dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), ps->np[2]);
-  hipLaunchKernelGGL((k_div_to_pI<3, true>), grid, block, 0, s, g, u, ps->pI, ps->np[0], ps->np[1]);
-  INS_LAUNCH_CHECK();
-  return spectral_transform(ps, s);
-}
-
-// The `_f32` family's pressure equation on power-of-two boxes: right-hand side Ω·div(u) from the FLOAT field u32 (periodic images), the five fp64
+// The `_f32` family's pressure equation on boxes with own passes: right-hand side Ω·div(u) from the FLOAT field u32 (periodic images), the fp64
 // passes, solution in ps->pI (double, unpadded).  false: this solver has no own passes (the caller keeps hipFFT).
-bool ins_k_spectral_own3d(const ins_poisson* ps) { return ps->kind == POISSON_SPECTRAL && ps->ownfft && ps->grid->g.D == 3; }
+bool ins_k_spectral_own3d(const ins_poisson* ps) { return ps->kind == POISSON_SPECTRAL && own_route(ps->route) && ps->grid->g.D == 3; }
 int ins_k_spectral_solve_from_u32(ins_poisson* ps, const float* u32, hipStream_t s) {
-  return ownfft_transform(ps, reinterpret_cast<const double*>(u32), s, 5);
+  return spectral_transform(ps, s, reinterpret_cast<const double*>(u32), XSRC_DIV_U32);
 }
 const double* ins_k_spectral_pI(const ins_poisson* ps) { return ps->pI; }
 
-// The same five passes on float2 spectra (the `_f32` family, ins_f32.hip): `ps` supplies the symbol vectors (double, ây in the digit-reversed order of
-// the y pass) and the grid; the float work arrays and float2 twiddles belong to the caller.  u32 != nullptr: right-hand side Ω·div(u) from the
-// float velocity field inside the x pass (periodic images); else the right-hand side is in pI32.  Solution in pI32 (unpadded).
+// The same five passes on float2 spectra (the `_f32` family, ins_f32.hip): `ps` supplies the symbol vectors (double, ây in the solver's ky order: the y
+// pass here is the float twin of the one that leaves that order) and the grid; the float work arrays and float2 twiddles belong to the caller.
+// u32 != nullptr: right-hand side Ω·div(u) from the float velocity field inside the x pass (periodic images); else the right-hand side is in pI32.
+// Solution in pI32 (unpadded).
 bool ins_zsolve_f32_supported(int nz);
 int ins_k_zsolve_f32(float* data, int nz, long long nl, const double* ax, int kxn, const double* ay, const double* az, const float* tw, double inv_n,
                      bool zero_mean, hipStream_t s, int kxs);
@@ -1550,12 +1520,14 @@ bool ins_k_spectral_own3d_f32(const ins_poisson* ps) { return ins_k_spectral_own
 int ins_k_spectral_solve_f32(ins_poisson* ps, const float* u32, float* pI32, float* phat32, int kxs32, const float* twx, const float* twy,
                              const float* twz, hipStream_t s) {
   const int n0 = ps->np[0], n1 = ps->np[1], n2 = ps->np[2], kxn = ps->kmax[0];
+  INS_REQUIRE(ps->ky_order != KY_NATURAL, "float2 spectral solve: the solver has no own y pass");
+  const auto ypass = ps->ky_order == KY_LINE3 ? ins_k_line3_y_f32 : ins_k_ownfft_y_f32;
   int rc;
-  if ((rc = ins_k_ownfft_xfwd_f32(ps->grid, u32 ? u32 : pI32, u32 ? 1 : 0, phat32, n0, n1, n2, twx, s, kxs32))) return rc;
-  if ((rc = ps->y3 ? ins_k_line3_y_f32(phat32, kxn, n1, n2, twy, false, s, kxs32) : ins_k_ownfft_y_f32(phat32, kxn, n1, n2, twy, false, s, kxs32))) return rc;
+  if ((rc = ins_k_ownfft_xfwd_f32(ps->grid, u32 ? u32 : pI32, u32 ? XSRC_DIV : XSRC_PI, phat32, n0, n1, n2, twx, s, kxs32))) return rc;
+  if ((rc = ypass(phat32, kxn, n1, n2, twy, false, s, kxs32))) return rc;
   const double inv_n = 1.0 / ((double)n0 * n1 * n2);
   if ((rc = ins_k_zsolve_f32(phat32, n2, (long long)kxs32 * n1, ps->ahat[0], kxn, ps->ahat[1], ps->ahat[2], twz, inv_n, true, s, kxs32))) return rc;
-  if ((rc = ps->y3 ? ins_k_line3_y_f32(phat32, kxn, n1, n2, twy, true, s, kxs32) : ins_k_ownfft_y_f32(phat32, kxn, n1, n2, twy, true, s, kxs32))) return rc;
+  if ((rc = ypass(phat32, kxn, n1, n2, twy, true, s, kxs32))) return rc;
   return ins_k_ownfft_xinv_f32(phat32, pI32, n0, n1, n2, twx, s, kxs32);
 }
 

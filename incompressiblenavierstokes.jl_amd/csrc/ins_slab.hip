@@ -262,7 +262,7 @@ extern "C" int ins_slab_fft_sizes(const ins_slab_fft_t* S, int64_t* real_elems, 
 
 static int slab_xy_forward(ins_slab_fft* S, double* pI, double* work, hipStream_t s) {
   if (S->ownfft) {
-    int rc = ins_k_ownfft_xfwd(nullptr, pI, 0, work, S->np[0], S->np[1], S->nzl, S->tw_x, s);
+    int rc = ins_k_ownfft_xfwd(nullptr, pI, XSRC_PI, work, S->np[0], S->np[1], S->nzl, S->tw_x, s);
     if (!rc) rc = ins_k_ownfft_y(work, S->kxn, S->np[1], S->nzl, S->tw_y, false, s);
     return rc;
   }
@@ -360,7 +360,7 @@ extern "C" int ins_slab_fft_forward_packed(ins_slab_fft_t* S, const ins_grid_t* 
     INS_REQUIRE(G && G->g.D == 3 && G->g.N[0] == S->np[0] + 2 && G->g.N[1] == S->np[1] + 2 && G->g.N[2] == S->nzl + 2, "grid does not match the slab");
   }
   hipStream_t s = as_stream(stream);
-  int rc = ins_k_ownfft_xfwd(from_u ? G : nullptr, src, from_u ? 2 : 0, work, S->np[0], S->np[1], S->nzl, S->tw_x, s);
+  int rc = ins_k_ownfft_xfwd(from_u ? G : nullptr, src, from_u ? XSRC_DIV_SLAB : XSRC_PI, work, S->np[0], S->np[1], S->nzl, S->tw_x, s);
   if (rc) return rc;
   return ins_k_ownfft_y_packed(work, sendbuf, S->kxn, S->np[1], S->nzl, S->nyl, cw, S->tw_y, false, s);
 }
@@ -423,11 +423,11 @@ extern "C" int ins_slab_ztri_transform(ins_slab_fft_t* S, const ins_grid_t* G, c
   if (from_u) {
     INS_REQUIRE(S->ownfft, "forming the right-hand side inside the x pass needs x and y sides of 2^m or 3 * 2^m");
     INS_REQUIRE(G && G->g.D == 3 && G->g.N[0] == S->np[0] + 2 && G->g.N[1] == S->np[1] + 2 && G->g.N[2] == S->nzl + 2, "grid does not match the slab");
-    if ((rc = ins_k_ownfft_xfwd(G, src, 2, work, S->np[0], S->np[1], S->nzl, S->tw_x, s, S->kxs))) return rc;
+    if ((rc = ins_k_ownfft_xfwd(G, src, XSRC_DIV_SLAB, work, S->np[0], S->np[1], S->nzl, S->tw_x, s, S->kxs))) return rc;
     return slab_y(S, work, false, s);
   }
   if (S->ownfft) {
-    if ((rc = ins_k_ownfft_xfwd(nullptr, src, 0, work, S->np[0], S->np[1], S->nzl, S->tw_x, s, S->kxs))) return rc;
+    if ((rc = ins_k_ownfft_xfwd(nullptr, src, XSRC_PI, work, S->np[0], S->np[1], S->nzl, S->tw_x, s, S->kxs))) return rc;
     return slab_y(S, work, false, s);
   }
   return slab_xy_forward(S, const_cast<double*>(src), work, s);
@@ -483,7 +483,7 @@ extern "C" int ins_slab_xfwd_planes(ins_slab_fft_t* S, const ins_grid_t* G, cons
   INS_REQUIRE(G->g.D == 3 && G->g.N[0] == S->np[0] + 2 && G->g.N[1] == S->np[1] + 2 && G->g.N[2] == S->nzl + 2, "grid does not match the slab");
   INS_REQUIRE(kz0 >= 0 && nkz >= 0 && kz0 + nkz <= S->nzl, "bad plane range");
   if (nkz == 0) return INS_OK;
-  return ins_k_ownfft_xfwd(G, u, 2, work, S->np[0], S->np[1], nkz, S->tw_x, as_stream(stream), S->kxs, kz0);
+  return ins_k_ownfft_xfwd(G, u, XSRC_DIV_SLAB, work, S->np[0], S->np[1], nkz, S->tw_x, as_stream(stream), S->kxs, kz0);
 }
 
 /* 1 when kx chunks are supported (power-of-two nz -> fused z kernel). */

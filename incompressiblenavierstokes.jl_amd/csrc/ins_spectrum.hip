@@ -206,7 +206,7 @@ extern "C" int ins_spectrum_f64(ins_spectrum_t* S, const double* u, double* ehat
       double* ph = reinterpret_cast<double*>(S->hat);
       const int kxn = S->np[0] / 2 + 1;
       int rc;
-      if ((rc = ins_k_ownfft_xfwd(S->grid, u + a * g.sc, 6, ph, S->np[0], S->np[1], S->np[2], S->tw[0], s, S->kxs))) return rc;  // ghosts stripped inside the x pass
+      if ((rc = ins_k_ownfft_xfwd(S->grid, u + a * g.sc, XSRC_FIELD, ph, S->np[0], S->np[1], S->np[2], S->tw[0], s, S->kxs))) return rc;  // ghosts stripped inside the x pass
       if ((rc = ins_k_line3_y(ph, kxn, S->np[1], S->np[2], S->tw[1], false, s, S->kxs))) return rc;
       if ((rc = ins_k_line3_z(ph, kxn, S->np[1], S->np[2], S->tw[2], s, S->kxs))) return rc;
     } else {

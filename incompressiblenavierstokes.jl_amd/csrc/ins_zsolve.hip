@@ -722,16 +722,14 @@ int launch_zsolve(double2* data, long long nl, const double* ax, int kxn, const 
 
 bool ins_zsolve_supported(int nz) {
   if (ins_opt(OPT_INS_DISABLE_ZSOLVE)) return false;
-  // 3 x 8 x 8, 6 x 8 x 8, 5 x 8 x 8 and 10 x 8 x 8 in the three-pass kernel
-  if ((nz == 96 || nz == 192 || nz == 384 || nz == 160 || nz == 320 || nz == 640) && !ins_opt(OPT_INS_OWNFFT_POW2_ONLY)) return true;
-  return nz >= 16 && nz <= 1024 && (nz & (nz - 1)) == 0;
+  return ins_pow2_len(nz) || ins_mixed_len(nz);  // the latter as 3 x 8 x 8, 6 x 8 x 8, 5 x 8 x 8 and 10 x 8 x 8 in the three-pass kernel
 }
 
 // The y passes of the single-GPU spectral solve on the register passes (k_line3): lengths the three-pass kernel has, plus 128 = 2 x 8 x 8.
 bool ins_line3_supported(int n) {
   if (ins_opt(OPT_INS_DISABLE_LINE3)) return false;
   if (n == 128 || n == 256 || n == 512) return true;
-  return (n == 96 || n == 192 || n == 384 || n == 160 || n == 320 || n == 640) && !ins_opt(OPT_INS_OWNFFT_POW2_ONLY);
+  return ins_mixed_len(n);
 }
 // out[p] = ay[k(p)]: the frequency held at storage position p after the forward pass of k_line3
 void ins_line3_permute_symbol(int n, const double* ay, double* out) {

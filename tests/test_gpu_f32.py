@@ -55,7 +55,8 @@ def test_momentum_f32_matches_oracle(ins, oracle, n):
 
 
 @pytest.mark.parametrize("n", [(128, 16, 12), (32, 16, 64), (24, 18), (66, 12, 10),  # last: rocFFT non-power-of-two sizes
-                               (32, 16, 512), (64, 16, 256), (32, 32, 192), (32, 16, 384)])  # the float2 z pass (three-pass kernel: every length it has)
+                               (32, 16, 512), (64, 16, 256), (32, 32, 192), (32, 16, 384),  # the float2 z pass (three-pass kernel: every length it has)
+                               (16, 16, 192), (16, 128, 192)])  # the float2 y pass in both ky orders: digit-reversed (LDS pass) and that of k_line3
 def test_project_and_poisson_f32_match_oracle(ins, oracle, n):
     o = oracle
     f32 = ins.f32
