@@ -5,39 +5,10 @@
 // Gather form everywhere: one work-item per output volume reads the cotangent stencil around it, so no atomics
 // and every output is written once.  fp64, 2-D and 3-D, any BC mix, uniform and stretched grids; the metric
 // tables and reciprocal conventions are those of the generic forward twins in ins_operators.hip.
-#include "ins_internal.h"
+#include "ins_stencil.h"
 #include "ins_wave64.h"
 
 namespace {
-
-// x along the 64-lane wavefront (unit-stride rows), 4 rows per block, one z-plane per grid layer: as box_launch in ins_operators.hip.
-inline void box(const GridDev& g, dim3& grid, dim3& block) {
-  block = dim3(64, 4, 1);
-  grid = dim3(cdiv(g.N[0], 64), cdiv(g.N[1], 4), (unsigned)(g.D == 3 ? g.N[2] : 1));
-}
-
-// Volume I holds a degree of freedom of component al in the forward stencils (k_convdiff / k_pressuregradient):
-// inside the 1..N-2 box in every direction and inside Iu[al].  Safe for any I, out-of-array indices included.
-template <int D>
-__device__ __forceinline__ bool dof(const GridDev& g, int al, int i0, int i1, int i2) {
-  const int I[3] = {i0, i1, i2};
-  bool ok = true;
-#pragma unroll
-  for (int b = 0; b < D; ++b) ok = ok && I[b] >= 1 && I[b] <= g.N[b] - 2 && I[b] >= g.iu_lo[al][b] && I[b] < g.iu_hi[al][b];
-  return ok;
-}
-
-template <int D>
-__device__ __forceinline__ bool in_ip(const GridDev& g, int i0, int i1, int i2) {
-  const int I[3] = {i0, i1, i2};
-  bool ok = true;
-#pragma unroll
-  for (int b = 0; b < D; ++b) ok = ok && I[b] >= g.ip_lo[b] && I[b] < g.ip_hi[b];
-  return ok;
-}
-
-// Coordinates of I shifted by s in direction b.
-#define INS_SH(I, b, s) ((I)[0] + ((b) == 0) * (s)), ((I)[1] + ((b) == 1) * (s)), ((I)[2] + ((b) == 2) * (s))
 
 // --------------------------------------------------------------------------------------------
 // divergence_adjoint                                                     operators.jl:127-145
@@ -45,12 +16,7 @@ __device__ __forceinline__ bool in_ip(const GridDev& g, int i0, int i1, int i2) 
 // --------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void k_divergence_adjoint(GridDev g, const double* __restrict__ phi, double* __restrict__ ubar, double alpha) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= g.N[0] || j >= g.N[1]) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
   const bool here = in_ip<D>(g, i, j, k);
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -67,12 +33,7 @@ __global__ __launch_bounds__(256) void k_divergence_adjoint(GridDev g, const dou
 // --------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void k_pressuregradient_adjoint(GridDev g, const double* __restrict__ phi, double* __restrict__ pbar) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= g.N[0] || j >= g.N[1]) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
   double v = 0.0;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -118,12 +79,7 @@ __device__ __forceinline__ double psi(const GridDev& g, int al, int be, const in
 template <int D, int MODE, bool ACC>
 __global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, double visc, const double* __restrict__ u, const double* __restrict__ phi,
                                                           double* __restrict__ ubar) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= g.N[0] || j >= g.N[1]) return;
-  const int X[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
 
 #pragma unroll
   for (int ga = 0; ga < D; ++ga) {
@@ -133,7 +89,7 @@ __global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, double visc
       const bool dx = dof<D>(g, ga, i, j, k);
 #pragma unroll
       for (int be = 0; be < D; ++be) {
-        const int ib = X[be];
+        const int ib = I[be];
         const long long sb = g.sx[be];
         // ma(i) = mdx[i] | mdxu[i-1],  mb(i) = mdx[i+1] | mdxu[i]   (k_convdiff)
         if (dx) {
@@ -141,11 +97,11 @@ __global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, double visc
           const double mb = ga == be ? g.mdx[be][ib + 1] : g.mdxu[be][ib];
           v -= visc * pg[c] * rr<D>(g, ga, be, ib) * (ma + mb);
         }
-        if (dof<D>(g, ga, INS_SH(X, be, -1))) {
+        if (dof<D>(g, ga, INS_SH(I, be, -1))) {
           const double mb = ga == be ? g.mdx[be][ib] : g.mdxu[be][ib - 1];
           v += visc * pg[c - sb] * rr<D>(g, ga, be, ib - 1) * mb;
         }
-        if (dof<D>(g, ga, INS_SH(X, be, 1))) {
+        if (dof<D>(g, ga, INS_SH(I, be, 1))) {
           const double ma = ga == be ? g.mdx[be][ib + 1] : g.mdxu[be][ib];
           v += visc * pg[c + sb] * rr<D>(g, ga, be, ib + 1) * ma;
         }
@@ -162,7 +118,7 @@ __global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, double visc
         const double* A2 = g.A2[be][ga];
 #pragma unroll
         for (int sh = 0; sh < 2; ++sh) {  // f = x, x − eβ
-          const int F[3] = {INS_SH(X, be, -sh)};
+          const int F[3] = {INS_SH(I, be, -sh)};
           const long long cf = c - sh * sb;
           bool live;
           const double w = psi<D>(g, ga, be, F, cf, pg, live);
@@ -179,15 +135,15 @@ __global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, double visc
         const double* A2 = g.A2[ga][al];
         {
           bool live;
-          const double w = psi<D>(g, al, ga, X, c, pa, live);
-          if (live) v += w * 0.5 * (ua[c] + ua[c + sg]) * A2[X[al]];
+          const double w = psi<D>(g, al, ga, I, c, pa, live);
+          if (live) v += w * 0.5 * (ua[c] + ua[c + sg]) * A2[I[al]];
         }
         {
-          const int F[3] = {INS_SH(X, al, -1)};
+          const int F[3] = {INS_SH(I, al, -1)};
           const long long cf = c - sa;
           bool live;
           const double w = psi<D>(g, al, ga, F, cf, pa, live);
-          if (live) v += w * 0.5 * (ua[cf] + ua[cf + sg]) * A1[X[al]];
+          if (live) v += w * 0.5 * (ua[cf] + ua[cf + sg]) * A1[I[al]];
         }
       }
     }
@@ -203,21 +159,10 @@ __global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, double visc
 //   left, turning x[i] = x[j] into (x̄[j] += x̄[i]; x̄[i] = 0) and x[i] = const into x̄[i] = 0.  Time-dependent Dirichlet
 //   planes only change the constant, so the pullback does not read them.
 // --------------------------------------------------------------------------------------------
-__device__ __forceinline__ void move_to(double* __restrict__ x, long long from, long long to) {
-  const double t = x[from];
-  x[from] = 0.0;
-  x[to] += t;
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void k_bc_u_pullback(GridDev g, double* __restrict__ u, int be) {
-  const int o0 = be == 0 ? 1 : 0;
-  const int o1 = be == 2 ? 1 : 2;
-  const int q0 = blockIdx.x * 256 + threadIdx.x;
-  const int q1 = D == 3 ? (int)blockIdx.y : 0;
+  INS_LINE_INDEX(be);
   const int al = blockIdx.z;
-  if (q0 >= g.N[o0]) return;
-  const long long base = q0 * g.sx[o0] + (D == 3 ? q1 * g.sx[o1] : 0);
   const long long sb = g.sx[be];
   double* ua = u + al * g.sc + base;
   const int bcl = g.bc[be][0], bcr = g.bc[be][1];
@@ -242,12 +187,8 @@ __global__ __launch_bounds__(256) void k_bc_u_pullback(GridDev g, double* __rest
 
 template <int D>
 __global__ __launch_bounds__(256) void k_bc_p_pullback(GridDev g, double* __restrict__ p, int be) {
-  const int o0 = be == 0 ? 1 : 0;
-  const int o1 = be == 2 ? 1 : 2;
-  const int q0 = blockIdx.x * 256 + threadIdx.x;
-  const int q1 = D == 3 ? (int)blockIdx.y : 0;
-  if (q0 >= g.N[o0]) return;
-  double* pl = p + q0 * g.sx[o0] + (D == 3 ? q1 * g.sx[o1] : 0);
+  INS_LINE_INDEX(be);
+  double* pl = p + base;
   const long long sb = g.sx[be];
   const int bcl = g.bc[be][0], bcr = g.bc[be][1];
   const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
@@ -267,8 +208,6 @@ __global__ __launch_bounds__(256) void k_bc_p_pullback(GridDev g, double* __rest
       pl[i * sb] = 0.0;
   }
 }
-
-#undef INS_SH
 
 // --------------------------------------------------------------------------------------------
 // Tiled fused momentum pullback: uniform, all-periodic 3-D boxes (the k_flux64 idioms)
@@ -392,13 +331,8 @@ __global__ __launch_bounds__(64 * ADJ_NW) void k_momentum_pullback_tiled(AdjTile
 template <int MODE, bool ACC>
 int launch_convdiff_adjoint(const ins_grid* G, double visc, const double* u, const double* phi, double* ubar, hipStream_t s) {
   const GridDev& g = G->g;
-  dim3 grid, block;
-  box(g, grid, block);
-  if (g.D == 2)
-    hipLaunchKernelGGL((k_convdiff_adjoint<2, MODE, ACC>), grid, block, 0, s, g, visc, u, phi, ubar);
-  else
-    hipLaunchKernelGGL((k_convdiff_adjoint<3, MODE, ACC>), grid, block, 0, s, g, visc, u, phi, ubar);
-  INS_LAUNCH_CHECK();
+  const Launch3 l = box_launch(g.D, g.N);
+  INS_LAUNCH_D((k_convdiff_adjoint<D, MODE, ACC>), l, s, g, visc, u, phi, ubar);
   return INS_OK;
 }
 
@@ -448,25 +382,15 @@ int launch_momentum_pullback_tiled(const ins_grid* G, double visc, const double*
 // ------------------------------------------------------------------------------------------------
 int ins_k_divergence_adjoint(const ins_grid* G, const double* phi, double* ubar, double alpha, hipStream_t s) {
   const GridDev& g = G->g;
-  dim3 grid, block;
-  box(g, grid, block);
-  if (g.D == 2)
-    hipLaunchKernelGGL(k_divergence_adjoint<2>, grid, block, 0, s, g, phi, ubar, alpha);
-  else
-    hipLaunchKernelGGL(k_divergence_adjoint<3>, grid, block, 0, s, g, phi, ubar, alpha);
-  INS_LAUNCH_CHECK();
+  const Launch3 l = box_launch(g.D, g.N);
+  INS_LAUNCH_D((k_divergence_adjoint<D>), l, s, g, phi, ubar, alpha);
   return INS_OK;
 }
 
 int ins_k_pressuregradient_adjoint(const ins_grid* G, const double* phi, double* pbar, hipStream_t s) {
   const GridDev& g = G->g;
-  dim3 grid, block;
-  box(g, grid, block);
-  if (g.D == 2)
-    hipLaunchKernelGGL(k_pressuregradient_adjoint<2>, grid, block, 0, s, g, phi, pbar);
-  else
-    hipLaunchKernelGGL(k_pressuregradient_adjoint<3>, grid, block, 0, s, g, phi, pbar);
-  INS_LAUNCH_CHECK();
+  const Launch3 l = box_launch(g.D, g.N);
+  INS_LAUNCH_D((k_pressuregradient_adjoint<D>), l, s, g, phi, pbar);
   return INS_OK;
 }
 
@@ -474,13 +398,7 @@ int ins_k_apply_bc_u_pullback(const ins_grid* G, double* u, hipStream_t s) {
   const GridDev& g = G->g;
   for (int be = g.D - 1; be >= 0; --be) {  // reverse of ins_k_apply_bc_u
     if (g.bc[be][0] == INS_BC_HALO && g.bc[be][1] == INS_BC_HALO) continue;
-    const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
-    dim3 grid(cdiv(g.N[o0], 256), g.D == 3 ? g.N[o1] : 1, g.D);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_bc_u_pullback<2>, grid, dim3(256), 0, s, g, u, be);
-    else
-      hipLaunchKernelGGL(k_bc_u_pullback<3>, grid, dim3(256), 0, s, g, u, be);
-    INS_LAUNCH_CHECK();
+    INS_LAUNCH_D((k_bc_u_pullback<D>), line_launch(g, be, g.D), s, g, u, be);
   }
   return INS_OK;
 }
@@ -490,13 +408,7 @@ int ins_k_apply_bc_p_pullback(const ins_grid* G, double* p, hipStream_t s) {
   for (int be = g.D - 1; be >= 0; --be) {  // reverse of ins_k_apply_bc_p_fields
     const int l = g.bc[be][0], r = g.bc[be][1];
     if ((l == INS_BC_DIRICHLET || l == INS_BC_HALO) && (r == INS_BC_DIRICHLET || r == INS_BC_HALO)) continue;
-    const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
-    dim3 grid(cdiv(g.N[o0], 256), g.D == 3 ? g.N[o1] : 1, 1);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_bc_p_pullback<2>, grid, dim3(256), 0, s, g, p, be);
-    else
-      hipLaunchKernelGGL(k_bc_p_pullback<3>, grid, dim3(256), 0, s, g, p, be);
-    INS_LAUNCH_CHECK();
+    INS_LAUNCH_D((k_bc_p_pullback<D>), line_launch(g, be, 1), s, g, p, be);
   }
   return INS_OK;
 }

@@ -1,6 +1,6 @@
 // Ghost-volume fill (boundary_conditions.jl:159-206, 276-318, 344-388, 414-502) and the blocking
 // box reductions used by diagnostics and the CG solver.
-#include "ins_internal.h"
+#include "ins_stencil.h"
 
 namespace {
 
@@ -11,13 +11,8 @@ namespace {
 // Plane coordinates (q0, q1) enumerate the two directions != β in memory order.
 template <int D>
 __global__ __launch_bounds__(256) void k_bc_u(GridDev g, double* __restrict__ u, int be, int dudt, const double* const* planes) {
-  const int o0 = be == 0 ? 1 : 0;             // fastest direction != be
-  const int o1 = be == 2 ? 1 : 2;             // slowest direction != be (3-D only)
-  const int q0 = blockIdx.x * 256 + threadIdx.x;
-  const int q1 = D == 3 ? (int)blockIdx.y : 0;
+  INS_LINE_INDEX(be);
   const int al = blockIdx.z;
-  if (q0 >= g.N[o0]) return;
-  const long long base = q0 * g.sx[o0] + (D == 3 ? q1 * g.sx[o1] : 0);
   const long long sb = g.sx[be];
   double* ua = u + al * g.sc;
   const int bcl = g.bc[be][0], bcr = g.bc[be][1];
@@ -54,12 +49,7 @@ __global__ __launch_bounds__(256) void k_bc_u(GridDev g, double* __restrict__ u,
 template <int D>
 __global__ __launch_bounds__(256) void k_bc_p(GridDev g, double* __restrict__ p, int be, long long fstride = 0) {
   p += (long long)blockIdx.z * fstride;  // several scalar fields in one launch (the stress components of the closure, ins_k_apply_bc_p_fields)
-  const int o0 = be == 0 ? 1 : 0;
-  const int o1 = be == 2 ? 1 : 2;
-  const int q0 = blockIdx.x * 256 + threadIdx.x;
-  const int q1 = D == 3 ? (int)blockIdx.y : 0;
-  if (q0 >= g.N[o0]) return;
-  const long long base = q0 * g.sx[o0] + (D == 3 ? q1 * g.sx[o1] : 0);
+  INS_LINE_INDEX(be);
   const long long sb = g.sx[be];
   const int bcl = g.bc[be][0], bcr = g.bc[be][1];
   const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
@@ -133,13 +123,7 @@ int ins_k_apply_bc_u(const ins_grid* G, double* u, int dudt, const double* const
   const GridDev& g = G->g;
   for (int be = 0; be < g.D; ++be) {
     if (g.bc[be][0] == INS_BC_HALO && g.bc[be][1] == INS_BC_HALO) continue;
-    const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
-    dim3 grid(cdiv(g.N[o0], 256), g.D == 3 ? g.N[o1] : 1, g.D);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_bc_u<2>, grid, dim3(256), 0, s, g, u, be, dudt, planes);
-    else
-      hipLaunchKernelGGL(k_bc_u<3>, grid, dim3(256), 0, s, g, u, be, dudt, planes);
-    INS_LAUNCH_CHECK();
+    INS_LAUNCH_D((k_bc_u<D>), line_launch(g, be, g.D), s, g, u, be, dudt, planes);
   }
   return INS_OK;
 }
@@ -151,13 +135,7 @@ int ins_k_apply_bc_p_fields(const ins_grid* G, double* p, int nf, hipStream_t s)
     const int l = g.bc[be][0], r = g.bc[be][1];
     const bool noop = (l == INS_BC_DIRICHLET || l == INS_BC_HALO) && (r == INS_BC_DIRICHLET || r == INS_BC_HALO);
     if (noop) continue;
-    const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
-    dim3 grid(cdiv(g.N[o0], 256), g.D == 3 ? g.N[o1] : 1, nf);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_bc_p<2>, grid, dim3(256), 0, s, g, p, be, G->ncell);
-    else
-      hipLaunchKernelGGL(k_bc_p<3>, grid, dim3(256), 0, s, g, p, be, G->ncell);
-    INS_LAUNCH_CHECK();
+    INS_LAUNCH_D((k_bc_p<D>), line_launch(g, be, nf), s, g, p, be, G->ncell);
   }
   return INS_OK;
 }

@@ -11,27 +11,15 @@
 // Slab (HALO) sides are not taken: the multi-GPU path is fp64.
 #include <cmath>
 
-#include "ins_internal.h"
+#include "ins_stencil.h"
 
 namespace {
-
-template <int D>
-__device__ __forceinline__ bool in_range32(const int (&I)[3], const int* lo, const int* hi) {
-  bool ok = true;
-#pragma unroll
-  for (int b = 0; b < D; ++b) ok = ok && (I[b] >= lo[b]) && (I[b] < hi[b]);
-  return ok;
-}
 
 // apply_bc_u!                                   boundary_conditions.jl:159-206, 276-288, 344-375, 414-428, 472-482 (constant boundary data)
 template <int D>
 __global__ __launch_bounds__(256) void k32g_bc_u(GridDev g, float* __restrict__ u, int be) {
-  const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
-  const int q0 = blockIdx.x * 256 + threadIdx.x;
-  const int q1 = D == 3 ? (int)blockIdx.y : 0;
+  INS_LINE_INDEX(be);
   const int al = blockIdx.z;
-  if (q0 >= g.N[o0]) return;
-  const long long base = q0 * g.sx[o0] + (D == 3 ? q1 * g.sx[o1] : 0);
   const long long sb = g.sx[be];
   float* ua = u + al * g.sc;
   const int bcl = g.bc[be][0], bcr = g.bc[be][1];
@@ -59,11 +47,7 @@ __global__ __launch_bounds__(256) void k32g_bc_u(GridDev g, float* __restrict__ 
 // apply_bc_p!                                   boundary_conditions.jl:306-318, 388, 445-453, 497-502
 template <int D>
 __global__ __launch_bounds__(256) void k32g_bc_p(GridDev g, float* __restrict__ p, int be) {
-  const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
-  const int q0 = blockIdx.x * 256 + threadIdx.x;
-  const int q1 = D == 3 ? (int)blockIdx.y : 0;
-  if (q0 >= g.N[o0]) return;
-  const long long base = q0 * g.sx[o0] + (D == 3 ? q1 * g.sx[o1] : 0);
+  INS_LINE_INDEX(be);
   const long long sb = g.sx[be];
   const int bcl = g.bc[be][0], bcr = g.bc[be][1];
   const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
@@ -87,19 +71,14 @@ __global__ __launch_bounds__(256) void k32g_bc_p(GridDev g, float* __restrict__ 
 // momentum! = fill!(F, 0) + convectiondiffusion!                                         operators.jl:647-690, 971
 template <int D>
 __global__ __launch_bounds__(256) void k32g_momentum(GridDev g, float visc, const float* __restrict__ u, float* __restrict__ F) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= g.N[0] || j >= g.N[1]) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
   bool inside = true;
 #pragma unroll
   for (int a = 0; a < D; ++a) inside = inside && I[a] >= 1 && I[a] <= g.N[a] - 2;
 #pragma unroll
   for (int al = 0; al < D; ++al) {
     float* Fa = F + al * g.sc;
-    if (!(inside && in_range32<D>(I, g.iu_lo[al], g.iu_hi[al]))) {
+    if (!(inside && in_range<D>(I, g.iu_lo[al], g.iu_hi[al]))) {
       Fa[c] = 0.f;
       continue;
     }
@@ -131,12 +110,7 @@ __global__ __launch_bounds__(256) void k32g_momentum(GridDev g, float visc, cons
 // (the right-hand side of the fp64 solver); P = float: the diagnostic.
 template <int D, typename P, bool SCALE>
 __global__ __launch_bounds__(256) void k32g_div(GridDev g, const float* __restrict__ u, P* __restrict__ out) {
-  const int i = g.ip_lo[0] + blockIdx.x * 64 + threadIdx.x;
-  const int j = g.ip_lo[1] + blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? g.ip_lo[2] + (int)blockIdx.z : 0;
-  if (i >= g.ip_hi[0] || j >= g.ip_hi[1]) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], i >= g.ip_hi[0] || j >= g.ip_hi[1]);
   P d = 0;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -154,16 +128,11 @@ __global__ __launch_bounds__(256) void k32g_div(GridDev g, const float* __restri
 // applypressure!                                                                          operators.jl:225-233
 template <int D>
 __global__ __launch_bounds__(256) void k32g_applypressure(GridDev g, float* __restrict__ u, const float* __restrict__ p) {
-  const int i = 1 + blockIdx.x * 64 + threadIdx.x;
-  const int j = 1 + blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? 1 + (int)blockIdx.z : 0;
-  if (i > g.N[0] - 2 || j > g.N[1] - 2) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 1, 1, 1, i > g.N[0] - 2 || j > g.N[1] - 2);
   const float pc = p[c];
 #pragma unroll
   for (int a = 0; a < D; ++a)
-    if (in_range32<D>(I, g.iu_lo[a], g.iu_hi[a])) u[a * g.sc + c] -= (p[c + g.sx[a]] - pc) * (float)g.rdxu[a][I[a]];
+    if (in_range<D>(I, g.iu_lo[a], g.iu_hi[a])) u[a * g.sc + c] -= (p[c + g.sx[a]] - pc) * (float)g.rdxu[a][I[a]];
 }
 
 __global__ __launch_bounds__(256) void k32g_widen(long long n, const float* __restrict__ a, double* __restrict__ b) {
@@ -191,13 +160,7 @@ int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s) {
   int rc = no_halo(G, "apply_bc_u (f32)");
   if (rc) return rc;
   for (int be = 0; be < g.D; ++be) {  // direction after direction: edges and corners come out as in the reference (boundary_conditions.jl:162-165)
-    const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
-    dim3 grid(cdiv(g.N[o0], 256), g.D == 3 ? g.N[o1] : 1, g.D);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k32g_bc_u<2>, grid, dim3(256), 0, s, g, u, be);
-    else
-      hipLaunchKernelGGL(k32g_bc_u<3>, grid, dim3(256), 0, s, g, u, be);
-    INS_LAUNCH_CHECK();
+    INS_LAUNCH_D((k32g_bc_u<D>), line_launch(g, be, g.D), s, g, u, be);
   }
   return INS_OK;
 }
@@ -208,37 +171,21 @@ int ins_k32g_apply_bc_p(const ins_grid* G, float* p, hipStream_t s) {
   if (rc) return rc;
   for (int be = 0; be < g.D; ++be) {
     if (g.bc[be][0] == INS_BC_DIRICHLET && g.bc[be][1] == INS_BC_DIRICHLET) continue;  // no-op (boundary_conditions.jl:388)
-    const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
-    dim3 grid(cdiv(g.N[o0], 256), g.D == 3 ? g.N[o1] : 1, 1);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k32g_bc_p<2>, grid, dim3(256), 0, s, g, p, be);
-    else
-      hipLaunchKernelGGL(k32g_bc_p<3>, grid, dim3(256), 0, s, g, p, be);
-    INS_LAUNCH_CHECK();
+    INS_LAUNCH_D((k32g_bc_p<D>), line_launch(g, be, 1), s, g, p, be);
   }
   return INS_OK;
 }
 
 int ins_k32g_momentum(const ins_grid* G, float visc, const float* u, float* F, hipStream_t s) {
   const GridDev& g = G->g;
-  dim3 grid(cdiv(g.N[0], 64), cdiv(g.N[1], 4), g.D == 3 ? g.N[2] : 1);
-  if (g.D == 2)
-    hipLaunchKernelGGL(k32g_momentum<2>, grid, dim3(64, 4), 0, s, g, visc, u, F);
-  else
-    hipLaunchKernelGGL(k32g_momentum<3>, grid, dim3(64, 4), 0, s, g, visc, u, F);
-  INS_LAUNCH_CHECK();
+  INS_LAUNCH_D((k32g_momentum<D>), box_launch(g.D, g.N), s, g, visc, u, F);
   return INS_OK;
 }
 
 // div[Ip] = divergence(u) (padded float array; volumes outside Ip are left as they are)
 int ins_k32g_divergence(const ins_grid* G, const float* u, float* div, hipStream_t s) {
   const GridDev& g = G->g;
-  dim3 grid(cdiv(g.ip_hi[0] - g.ip_lo[0], 64), cdiv(g.ip_hi[1] - g.ip_lo[1], 4), g.D == 3 ? g.ip_hi[2] - g.ip_lo[2] : 1);
-  if (g.D == 2)
-    hipLaunchKernelGGL((k32g_div<2, float, false>), grid, dim3(64, 4), 0, s, g, u, div);
-  else
-    hipLaunchKernelGGL((k32g_div<3, float, false>), grid, dim3(64, 4), 0, s, g, u, div);
-  INS_LAUNCH_CHECK();
+  INS_LAUNCH_D((k32g_div<D, float, false>), box_launch(g.D, g.ip_lo, g.ip_hi), s, g, u, div);
   return INS_OK;
 }
 
@@ -259,21 +206,12 @@ int ins_k32g_project(const ins_grid* G, ins_poisson* ps64, double* p64, float* u
   const GridDev& g = G->g;
   int rc = no_halo(G, "project (f32)");
   if (rc) return rc;
-  dim3 gi(cdiv(g.ip_hi[0] - g.ip_lo[0], 64), cdiv(g.ip_hi[1] - g.ip_lo[1], 4), g.D == 3 ? g.ip_hi[2] - g.ip_lo[2] : 1);
-  if (g.D == 2)
-    hipLaunchKernelGGL((k32g_div<2, double, true>), gi, dim3(64, 4), 0, s, g, u, p64);
-  else
-    hipLaunchKernelGGL((k32g_div<3, double, true>), gi, dim3(64, 4), 0, s, g, u, p64);
-  INS_LAUNCH_CHECK();
+  INS_LAUNCH_D((k32g_div<D, double, true>), box_launch(g.D, g.ip_lo, g.ip_hi), s, g, u, p64);
   if ((rc = ins_k_poisson_solve(ps64, p64, s))) return rc;
   hipLaunchKernelGGL(k32g_round, flat_grid(G->ncell), dim3(256), 0, s, G->ncell, p64, p);
   INS_LAUNCH_CHECK();
   if ((rc = ins_k32g_apply_bc_p(G, p, s))) return rc;
-  dim3 gp(cdiv(g.N[0] - 2, 64), cdiv(g.N[1] - 2, 4), g.D == 3 ? g.N[2] - 2 : 1);
-  if (g.D == 2)
-    hipLaunchKernelGGL(k32g_applypressure<2>, gp, dim3(64, 4), 0, s, g, u, p);
-  else
-    hipLaunchKernelGGL(k32g_applypressure<3>, gp, dim3(64, 4), 0, s, g, u, p);
-  INS_LAUNCH_CHECK();
+  const int lo[3] = {1, 1, 1}, hi[3] = {g.N[0] - 1, g.N[1] - 1, g.N[2] - 1};
+  INS_LAUNCH_D((k32g_applypressure<D>), box_launch(g.D, lo, hi), s, g, u, p);
   return INS_OK;
 }

@@ -3,53 +3,16 @@
 // Same conventions as ins_operators.hip: one work-item per volume, x along the 64-lane wavefront (unit-stride row segments),
 // any boundary conditions, 2-D and 3-D, stretched grids.  All are single HBM passes; reciprocal metric tables replace the
 // reference's divisions (<= 1 ulp per term, inside the 1e-12 parity tolerance).
-#include "ins_internal.h"
+#include "ins_stencil.h"
 
 namespace {
-
-// Box of nx*ny*nz work-items as a 1-D grid of 64x4 workgroups with an XCD-aware order: workgroup ids are dealt round-robin to the
-// 8 XCDs, so id & 7 selects one of 8 y-ranges and, inside it, tiles run x fastest, then y, then z.  Every XCD then walks ITS slab of
-// rows plane after plane, and the k-1 / k+1 planes a stencil re-reads are still in that XCD's own 4 MB L2 (3 planes x 1/8 of the
-// rows x 3 components = 0.6 MB at 256^3) instead of coming from HBM three times.
-struct Launch3 {
-  dim3 grid, block;
-  int ntx, nty, nty_l;
-};
-inline Launch3 box_launch(int nx, int ny, int nz) {
-  Launch3 l;
-  l.block = dim3(64, 4, 1);
-  l.ntx = (int)cdiv(nx, 64);
-  l.nty = (int)cdiv(ny, 4);
-  l.nty_l = (l.nty + 7) / 8;
-  l.grid = dim3(8u * l.ntx * l.nty_l * (unsigned)nz, 1, 1);
-  return l;
-}
-
-// work-item -> volume of the box [lo, hi)
-#define INS_BOX_INDEX(lo0, lo1, lo2, hi0, hi1)                              \
-  int seq_ = (int)(blockIdx.x >> 3);                                         \
-  const int tx_ = seq_ % L.ntx;                                              \
-  seq_ /= L.ntx;                                                             \
-  const int ty_ = (int)(blockIdx.x & 7) * L.nty_l + seq_ % L.nty_l;          \
-  if (ty_ >= L.nty) return;                                                  \
-  const int i = (lo0) + tx_ * 64 + threadIdx.x;                              \
-  const int j = (lo1) + ty_ * 4 + threadIdx.y;                               \
-  const int k = D == 3 ? (lo2) + seq_ / L.nty_l : 0;                         \
-  if (i >= (hi0) || j >= (hi1)) return;                                      \
-  const int I[3] = {i, j, k};                                                \
-  const long long c = i + j * g.sx[1] + k * g.sx[2];                         \
-  (void)I
-
-struct BoxMap {
-  int ntx, nty, nty_l;
-};
 
 // --------------------------------------------------------------------------------------------
 // vorticity!                                             operators.jl:985-1020 (ndrange = N .- 1)
 // --------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void k_vorticity(GridDev g, BoxMap L, const double* __restrict__ u, double* __restrict__ w) {
-  INS_BOX_INDEX(0, 0, 0, g.N[0] - 1, g.N[1] - 1);
+  INS_BANDED_INDEX(0, 0, 0, g.N[0] - 1, g.N[1] - 1);
   if (D == 2) {
     const double* u0 = u;
     const double* u1 = u + g.sc;
@@ -68,7 +31,7 @@ __global__ __launch_bounds__(256) void k_vorticity(GridDev g, BoxMap L, const do
 // interpolate_u_p!                                                     operators.jl:1311-1326
 template <int D>
 __global__ __launch_bounds__(256) void k_interp_u_p(GridDev g, BoxMap L, const double* __restrict__ u, double* __restrict__ up) {
-  INS_BOX_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
+  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
 #pragma unroll
   for (int a = 0; a < D; ++a) {
     const double* ua = u + a * g.sc;
@@ -79,7 +42,7 @@ __global__ __launch_bounds__(256) void k_interp_u_p(GridDev g, BoxMap L, const d
 // interpolate_ω_p!                                                     operators.jl:1336-1370
 template <int D>
 __global__ __launch_bounds__(256) void k_interp_w_p(GridDev g, BoxMap L, const double* __restrict__ w, double* __restrict__ wp) {
-  INS_BOX_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
+  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
   if (D == 2) {
     wp[c] = (w[c - g.sx[0] - g.sx[1]] + w[c]) / 2;
   } else {
@@ -95,7 +58,7 @@ __global__ __launch_bounds__(256) void k_interp_w_p(GridDev g, BoxMap L, const d
 // Dfield! (after pressuregradient!)                                    operators.jl:1385-1422
 template <int D>
 __global__ __launch_bounds__(256) void k_Dfield(GridDev g, BoxMap L, const double* __restrict__ G, double* __restrict__ d, double eps) {
-  INS_BOX_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
+  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
   double gg = 0.0, lap = 0.0;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -111,7 +74,7 @@ __global__ __launch_bounds__(256) void k_Dfield(GridDev g, BoxMap L, const doubl
 // Qfield!                                                              operators.jl:1440-1460
 template <int D>
 __global__ __launch_bounds__(256) void k_Qfield(GridDev g, BoxMap L, const double* __restrict__ u, double* __restrict__ Q) {
-  INS_BOX_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
+  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
   double q = 0.0;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -245,7 +208,7 @@ __device__ __forceinline__ void gradient_result(const GridDev& g, const double (
 // one work-item per pressure point, every neighbour from global memory (2-D grids)
 template <int D, int OP>
 __global__ __launch_bounds__(256) void k_gradient_op(GridDev g, BoxMap L, double par, const double* __restrict__ u, double* __restrict__ out) {
-  INS_BOX_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
+  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
   double G[D][D];
   gradu<D>(g, u, c, I, G);
   gradient_result<D, OP>(g, G, I, c, par, out);
@@ -297,7 +260,7 @@ __device__ __forceinline__ void put(double* __restrict__ B, const GridDev& g, lo
 
 template <int D>
 __global__ __launch_bounds__(256) void k_tensorbasis(GridDev g, BoxMap L, const double* __restrict__ u, double* __restrict__ B, double* __restrict__ V) {
-  INS_BOX_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
+  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
   double G[D][D];
   gradu<D>(g, u, c, I, G);
   Mat<D> S, R, Id;
@@ -572,7 +535,7 @@ __device__ __forceinline__ double avg_at(const GridDev& g, const double* __restr
 template <int D>
 __global__ __launch_bounds__(256) void k_convdiff_temp(GridDev g, BoxMap L, double a4, const double* __restrict__ u, const double* __restrict__ temp,
                                                        double* __restrict__ out) {
-  INS_BOX_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
+  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
   const double tc = temp[c];
   double acc = 0.0;
 #pragma unroll
@@ -592,7 +555,7 @@ __global__ __launch_bounds__(256) void k_convdiff_temp(GridDev g, BoxMap L, doub
 template <int D>
 __global__ __launch_bounds__(256) void k_dissipation_interp(GridDev g, BoxMap L, double coef, const double* __restrict__ u, const double* __restrict__ diff,
                                                             double* __restrict__ diss) {
-  INS_BOX_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
+  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
   double d = 0.0;
 #pragma unroll
   for (int b = 0; b < D; ++b) {
@@ -624,7 +587,7 @@ template <int D>
 __global__ __launch_bounds__(256) void k_temp_stage(GridDev g, BoxMap L, double a4, double coef, const double* __restrict__ u, const double* __restrict__ temp,
                                                     const double* __restrict__ w, TempStage ts, const double* __restrict__ pI,
                                                     const double* __restrict__ diff) {
-  INS_BOX_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
+  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
   const double tc = temp[c];
   double acc = 0.0, d = 0.0;
   const int n[3] = {g.ip_hi[0] - g.ip_lo[0], g.ip_hi[1] - g.ip_lo[1], D == 3 ? g.ip_hi[2] - g.ip_lo[2] : 1};
@@ -674,7 +637,7 @@ __global__ __launch_bounds__(256) void k_temp_stage(GridDev g, BoxMap L, double 
 // gravity!  (F[:, gdir] += α2 avg(temp))   over the whole Iu[gdir]                     operators.jl:914-931
 template <int D>
 __global__ __launch_bounds__(256) void k_gravity(GridDev g, BoxMap L, int gdir, double a2, const double* __restrict__ temp, double* __restrict__ F) {
-  INS_BOX_INDEX(g.iu_lo[gdir][0], g.iu_lo[gdir][1], g.iu_lo[gdir][2], g.iu_hi[gdir][0], g.iu_hi[gdir][1]);
+  INS_BANDED_INDEX(g.iu_lo[gdir][0], g.iu_lo[gdir][1], g.iu_lo[gdir][2], g.iu_hi[gdir][0], g.iu_hi[gdir][1]);
   F[gdir * g.sc + c] += a2 * avg_at(g, temp, c, gdir == 0 ? i : (gdir == 1 ? j : k), gdir);
 }
 
@@ -687,12 +650,7 @@ struct TempBC {
 };
 template <int D>
 __global__ __launch_bounds__(256) void k_bc_temp(GridDev g, double* __restrict__ temp, int be, TempBC t) {
-  const int o0 = be == 0 ? 1 : 0;
-  const int o1 = be == 2 ? 1 : 2;
-  const int q0 = blockIdx.x * 256 + threadIdx.x;
-  const int q1 = D == 3 ? (int)blockIdx.y : 0;
-  if (q0 >= g.N[o0]) return;
-  const long long base = q0 * g.sx[o0] + (D == 3 ? q1 * g.sx[o1] : 0);
+  INS_LINE_INDEX(be);
   const long long sb = g.sx[be];
   const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
   if (t.bc[0] == INS_BC_PERIODIC) {
@@ -719,7 +677,7 @@ __global__ __launch_bounds__(256) void k_bc_temp(GridDev g, double* __restrict__
 // divoftensor!                                                                operators.jl:1203-1236
 template <int D>
 __global__ __launch_bounds__(256) void k_divoftensor(GridDev g, BoxMap L, const double* __restrict__ sig, double* __restrict__ s) {
-  INS_BOX_INDEX(0, 0, 0, g.N[0], g.N[1]);
+  INS_BANDED_INDEX(0, 0, 0, g.N[0], g.N[1]);
 #pragma unroll
   for (int a = 0; a < D; ++a) {
     bool dof = true;
@@ -862,18 +820,7 @@ __global__ __launch_bounds__(256) void k_divoftensor_rows(GridDev g, BoxMap L, i
   }
 }
 
-#define INS_LAUNCH_D(KERNEL, L, S, ...)                                                \
-  do {                                                                                  \
-    if (g.D == 2)                                                                       \
-      hipLaunchKernelGGL((KERNEL<2>), (L).grid, (L).block, 0, S, g, BoxMap{(L).ntx, (L).nty, (L).nty_l}, __VA_ARGS__);          \
-    else                                                                                \
-      hipLaunchKernelGGL((KERNEL<3>), (L).grid, (L).block, 0, S, g, BoxMap{(L).ntx, (L).nty, (L).nty_l}, __VA_ARGS__);          \
-    INS_LAUNCH_CHECK();                                                                 \
-  } while (0)
-
-inline Launch3 ip_launch(const GridDev& g) {
-  return box_launch(g.ip_hi[0] - g.ip_lo[0], g.ip_hi[1] - g.ip_lo[1], g.D == 3 ? g.ip_hi[2] - g.ip_lo[2] : 1);
-}
+inline Launch3 ip_launch(const GridDev& g) { return banded_launch(g.D, g.ip_lo, g.ip_hi); }
 
 template <int OP>
 int launch_gradient_op(const ins_grid* G, double par, const double* u, double* out, hipStream_t s, const double* pI = nullptr) {
@@ -883,13 +830,8 @@ int launch_gradient_op(const ins_grid* G, double par, const double* u, double* o
       constexpr int R = 2;
       const int nx = g.ip_hi[0] - g.ip_lo[0], ny = g.ip_hi[1] - g.ip_lo[1], nz = g.ip_hi[2] - g.ip_lo[2];
       const int zc = ins_opt(OPT_INS_FIELDS_ZC) > 0 ? (int)ins_opt(OPT_INS_FIELDS_ZC) : (nz >= 128 ? 32 : (nz >= 32 ? 16 : (nz >= 8 ? 8 : nz)));
-      Launch3 l;
-      l.block = dim3(64, 4, 1);
-      l.ntx = (int)cdiv(nx, GR_XO - 1);
-      l.nty = (int)cdiv(ny, 4 * R);
-      l.nty_l = (l.nty + 7) / 8;
-      l.grid = dim3(8u * l.ntx * l.nty_l * cdiv(nz, zc), 1, 1);
-      hipLaunchKernelGGL((k_gradient_rows<OP, R, true>), l.grid, l.block, 0, s, g, BoxMap{l.ntx, l.nty, l.nty_l}, zc, par, u, out, pI);
+      Launch3 l = banded_tiles((int)cdiv(nx, GR_XO - 1), (int)cdiv(ny, 4 * R), (int)cdiv(nz, zc));
+      hipLaunchKernelGGL((k_gradient_rows<OP, R, true>), l.grid, l.block, 0, s, g, l.map, zc, par, u, out, pI);
       INS_LAUNCH_CHECK();
       return INS_OK;
     }
@@ -900,7 +842,7 @@ int launch_gradient_op(const ins_grid* G, double par, const double* u, double* o
   if (g.D == 2) {
     if constexpr (OP != 1) {
       Launch3 l = ip_launch(g);
-      hipLaunchKernelGGL((k_gradient_op<2, OP>), l.grid, l.block, 0, s, g, BoxMap{l.ntx, l.nty, l.nty_l}, par, u, out);
+      hipLaunchKernelGGL((k_gradient_op<2, OP>), l.grid, l.block, 0, s, g, l.map, par, u, out);
     }
   } else if (ins_opt(OPT_INS_FIELDS_ROWS) >= 0 && g.ip_hi[0] - g.ip_lo[0] >= 32 && g.N[2] >= 4) {
     // register rows + DPP (INS_FIELDS_ROWS=-1: the older kernels).  256^3: strain dissipation 0.282 -> 0.207 ms, smagtensor 0.460 -> 0.449;
@@ -911,26 +853,21 @@ int launch_gradient_op(const ins_grid* G, double par, const double* u, double* o
     const int nx = g.ip_hi[0] - g.ip_lo[0], ny = g.ip_hi[1] - g.ip_lo[1], nz = g.ip_hi[2] - g.ip_lo[2];
     const int zca = ins_opt(OPT_INS_FIELDS_ZC) > 0 ? (int)ins_opt(OPT_INS_FIELDS_ZC) : (nz >= 128 ? 32 : (nz >= 32 ? 16 : (nz >= 8 ? 8 : nz)));
     const int zc = ins_opt(OPT_INS_FIELDS_NOBAR) ? -zca : zca;
-    Launch3 l;
-    l.block = dim3(64, 4, 1);
-    l.ntx = (int)cdiv(nx, GR_XO);
-    l.nty = (int)cdiv(ny, 4 * R);
-    l.nty_l = (l.nty + 7) / 8;
-    l.grid = dim3(8u * l.ntx * l.nty_l * cdiv(nz, zca), 1, 1);
+    Launch3 l = banded_tiles((int)cdiv(nx, GR_XO), (int)cdiv(ny, 4 * R), (int)cdiv(nz, zca));
     if (R == 2)
-      hipLaunchKernelGGL((k_gradient_rows<OP, 2>), l.grid, l.block, 0, s, g, BoxMap{l.ntx, l.nty, l.nty_l}, zc, par, u, out);
+      hipLaunchKernelGGL((k_gradient_rows<OP, 2>), l.grid, l.block, 0, s, g, l.map, zc, par, u, out);
     else if (R == 3)
-      hipLaunchKernelGGL((k_gradient_rows<OP, 3>), l.grid, l.block, 0, s, g, BoxMap{l.ntx, l.nty, l.nty_l}, zc, par, u, out);
+      hipLaunchKernelGGL((k_gradient_rows<OP, 3>), l.grid, l.block, 0, s, g, l.map, zc, par, u, out);
     else
-      hipLaunchKernelGGL((k_gradient_rows<OP, 4>), l.grid, l.block, 0, s, g, BoxMap{l.ntx, l.nty, l.nty_l}, zc, par, u, out);
+      hipLaunchKernelGGL((k_gradient_rows<OP, 4>), l.grid, l.block, 0, s, g, l.map, zc, par, u, out);
   } else if (!march || OP == 1) {  // eig2: its arithmetic dominates; the plain kernel measured faster (0.35 vs 0.43 ms at 256^3)
     Launch3 l = ip_launch(g);
-    hipLaunchKernelGGL((k_gradient_op<3, OP>), l.grid, l.block, 0, s, g, BoxMap{l.ntx, l.nty, l.nty_l}, par, u, out);
+    hipLaunchKernelGGL((k_gradient_op<3, OP>), l.grid, l.block, 0, s, g, l.map, par, u, out);
   } else {
     const int nz = g.ip_hi[2] - g.ip_lo[2];
     const int zc = nz >= 64 ? 32 : (nz >= 16 ? 8 : nz);  // planes per z-chunk: (zc + 2) / zc re-read at chunk ends
-    Launch3 l = box_launch(g.ip_hi[0] - g.ip_lo[0], g.ip_hi[1] - g.ip_lo[1], (int)cdiv(nz, zc));
-    hipLaunchKernelGGL((k_gradient_march<OP>), l.grid, l.block, 0, s, g, BoxMap{l.ntx, l.nty, l.nty_l}, zc, par, u, out);
+    Launch3 l = banded_tiles((int)cdiv(g.ip_hi[0] - g.ip_lo[0], 64), (int)cdiv(g.ip_hi[1] - g.ip_lo[1], 4), (int)cdiv(nz, zc));
+    hipLaunchKernelGGL((k_gradient_march<OP>), l.grid, l.block, 0, s, g, l.map, zc, par, u, out);
   }
   INS_LAUNCH_CHECK();
   return INS_OK;
@@ -941,8 +878,9 @@ int launch_gradient_op(const ins_grid* G, double par, const double* u, double* o
 extern "C" int ins_vorticity_f64(const ins_grid_t* G, const double* u, double* w, void* stream) {
   INS_REQUIRE(G && u && w, "null argument");
   const GridDev& g = G->g;
-  Launch3 l = box_launch(g.N[0] - 1, g.N[1] - 1, g.D == 3 ? g.N[2] - 1 : 1);
-  INS_LAUNCH_D(k_vorticity, l, as_stream(stream), u, w);
+  const int hi[3] = {g.N[0] - 1, g.N[1] - 1, g.N[2] - 1};
+  Launch3 l = banded_launch(g.D, hi);
+  INS_LAUNCH_D((k_vorticity<D>), l, as_stream(stream), g, l.map, u, w);
   return INS_OK;
 }
 
@@ -950,7 +888,7 @@ extern "C" int ins_interpolate_u_p_f64(const ins_grid_t* G, const double* u, dou
   INS_REQUIRE(G && u && up, "null argument");
   const GridDev& g = G->g;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D(k_interp_u_p, l, as_stream(stream), u, up);
+  INS_LAUNCH_D((k_interp_u_p<D>), l, as_stream(stream), g, l.map, u, up);
   return INS_OK;
 }
 
@@ -958,7 +896,7 @@ extern "C" int ins_interpolate_w_p_f64(const ins_grid_t* G, const double* w, dou
   INS_REQUIRE(G && w && wp, "null argument");
   const GridDev& g = G->g;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D(k_interp_w_p, l, as_stream(stream), w, wp);
+  INS_LAUNCH_D((k_interp_w_p<D>), l, as_stream(stream), g, l.map, w, wp);
   return INS_OK;
 }
 
@@ -968,7 +906,7 @@ extern "C" int ins_dfield_f64(const ins_grid_t* G, const double* p, double* Gp, 
   int rc = ins_pressuregradient_f64(G, p, Gp, stream);
   if (rc != INS_OK) return rc;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D(k_Dfield, l, as_stream(stream), (const double*)Gp, d, eps);
+  INS_LAUNCH_D((k_Dfield<D>), l, as_stream(stream), g, l.map, (const double*)Gp, d, eps);
   return INS_OK;
 }
 
@@ -976,7 +914,7 @@ extern "C" int ins_qfield_f64(const ins_grid_t* G, const double* u, double* Q, v
   INS_REQUIRE(G && u && Q, "null argument");
   const GridDev& g = G->g;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D(k_Qfield, l, as_stream(stream), u, Q);
+  INS_LAUNCH_D((k_Qfield<D>), l, as_stream(stream), g, l.map, u, Q);
   return INS_OK;
 }
 
@@ -1005,13 +943,7 @@ extern "C" int ins_apply_bc_temp_f64(const ins_grid_t* G, const int32_t* bc, con
                   "temperature boundary condition");
     }
     INS_REQUIRE((t.bc[0] == INS_BC_PERIODIC) == (t.bc[1] == INS_BC_PERIODIC), "periodic on both sides");
-    const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
-    dim3 grid(cdiv(g.N[o0], 256), g.D == 3 ? g.N[o1] : 1, 1);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_bc_temp<2>, grid, dim3(256), 0, as_stream(stream), g, temp, be, t);
-    else
-      hipLaunchKernelGGL(k_bc_temp<3>, grid, dim3(256), 0, as_stream(stream), g, temp, be, t);
-    INS_LAUNCH_CHECK();
+    INS_LAUNCH_D((k_bc_temp<D>), line_launch(g, be, 1), as_stream(stream), g, temp, be, t);
   }
   return INS_OK;
 }
@@ -1037,7 +969,7 @@ int ins_k_temp_stage(const ins_grid* G, double a4, double coef, const double* u,
   // (a register-row form of this kernel — 2 rows per work-item, 158 VGPRs — measured 1-2 % faster on the all-walls 256^3 temperature loop, with 4
   // rows and 227 VGPRs 6 % slower: not kept)
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D(k_temp_stage, l, s, a4, coef, u, temp, w, ts, pI, diff);
+  INS_LAUNCH_D((k_temp_stage<D>), l, s, g, l.map, a4, coef, u, temp, w, ts, pI, diff);
   return INS_OK;
 }
 
@@ -1045,7 +977,7 @@ extern "C" int ins_convection_diffusion_temp_f64(const ins_grid_t* G, double a4,
   INS_REQUIRE(G && u && temp && c, "null argument");
   const GridDev& g = G->g;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D(k_convdiff_temp, l, as_stream(stream), a4, u, temp, c);
+  INS_LAUNCH_D((k_convdiff_temp<D>), l, as_stream(stream), g, l.map, a4, u, temp, c);
   return INS_OK;
 }
 
@@ -1060,7 +992,7 @@ extern "C" int ins_dissipation_f64(const ins_grid_t* G, double visc, double coef
   if (rc == INS_ERR_UNSUPPORTED) rc = ins_k_diffusion_overwrite(G, visc, u, diff, as_stream(stream));
   if (rc != INS_OK) return rc;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D(k_dissipation_interp, l, as_stream(stream), coef, u, (const double*)diff, diss);
+  INS_LAUNCH_D((k_dissipation_interp<D>), l, as_stream(stream), g, l.map, coef, u, (const double*)diff, diss);
   return INS_OK;
 }
 
@@ -1068,9 +1000,8 @@ extern "C" int ins_gravity_f64(const ins_grid_t* G, int gdir, double a2, const d
   INS_REQUIRE(G && temp && F, "null argument");
   const GridDev& g = G->g;
   INS_REQUIRE(gdir >= 0 && gdir < g.D, "gravity direction");
-  Launch3 l = box_launch(g.iu_hi[gdir][0] - g.iu_lo[gdir][0], g.iu_hi[gdir][1] - g.iu_lo[gdir][1],
-                         g.D == 3 ? g.iu_hi[gdir][2] - g.iu_lo[gdir][2] : 1);
-  INS_LAUNCH_D(k_gravity, l, as_stream(stream), gdir, a2, temp, F);
+  Launch3 l = banded_launch(g.D, g.iu_lo[gdir], g.iu_hi[gdir]);
+  INS_LAUNCH_D((k_gravity<D>), l, as_stream(stream), g, l.map, gdir, a2, temp, F);
   return INS_OK;
 }
 
@@ -1094,18 +1025,13 @@ extern "C" int ins_divoftensor_f64(const ins_grid_t* G, const double* sig, doubl
     constexpr int R = 4;
     const int nx = g.N[0] - 2, ny = g.N[1] - 2, nz = g.N[2] - 2;
     const int zc = ins_opt(OPT_INS_FIELDS_ZC) > 0 ? (int)ins_opt(OPT_INS_FIELDS_ZC) : (nz >= 128 ? 32 : (nz >= 32 ? 16 : (nz >= 8 ? 8 : nz)));
-    Launch3 l;
-    l.block = dim3(64, 4, 1);
-    l.ntx = (int)cdiv(nx, GR_XO);
-    l.nty = (int)cdiv(ny, 4 * R);
-    l.nty_l = (l.nty + 7) / 8;
-    l.grid = dim3(8u * l.ntx * l.nty_l * cdiv(nz, zc), 1, 1);
-    hipLaunchKernelGGL((k_divoftensor_rows<R>), l.grid, l.block, 0, as_stream(stream), g, BoxMap{l.ntx, l.nty, l.nty_l}, ins_opt(OPT_INS_FIELDS_NOBAR) ? -zc : zc, sig, s);
+    Launch3 l = banded_tiles((int)cdiv(nx, GR_XO), (int)cdiv(ny, 4 * R), (int)cdiv(nz, zc));
+    hipLaunchKernelGGL((k_divoftensor_rows<R>), l.grid, l.block, 0, as_stream(stream), g, l.map, ins_opt(OPT_INS_FIELDS_NOBAR) ? -zc : zc, sig, s);
     INS_LAUNCH_CHECK();
     return INS_OK;
   }
-  Launch3 l = box_launch(g.N[0], g.N[1], g.D == 3 ? g.N[2] : 1);
-  INS_LAUNCH_D(k_divoftensor, l, as_stream(stream), sig, s);
+  Launch3 l = banded_launch(g.D, g.N);
+  INS_LAUNCH_D((k_divoftensor<D>), l, as_stream(stream), g, l.map, sig, s);
   return INS_OK;
 }
 
@@ -1113,6 +1039,6 @@ extern "C" int ins_tensorbasis_f64(const ins_grid_t* G, const double* u, double*
   INS_REQUIRE(G && u && B && V, "null argument");
   const GridDev& g = G->g;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D(k_tensorbasis, l, as_stream(stream), u, B, V);
+  INS_LAUNCH_D((k_tensorbasis<D>), l, as_stream(stream), g, l.map, u, B, V);
   return INS_OK;
 }

@@ -19,7 +19,7 @@
 // and reduces the x window over an LDS row.  INS_DISABLE_FILTER_TILED forces the generic kernel.
 #include <cmath>
 
-#include "ins_internal.h"
+#include "ins_stencil.h"
 
 namespace {
 
@@ -33,24 +33,14 @@ struct FilterArgs {
   double* v;
 };
 
-inline void box(const int N[3], int D, dim3& grid, dim3& block) {
-  block = dim3(64, 4, 1);
-  grid = dim3(cdiv(N[0], 64), cdiv(N[1], 4), (unsigned)(D == 3 ? N[2] : 1));
-}
-
 // --------------------------------------------------------------------------------------------
 // generic filters: one work-item per coarse volume, all components
 // --------------------------------------------------------------------------------------------
 template <int D, bool VOL>
 __global__ __launch_bounds__(256) void k_filter(FilterArgs a) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= a.Nc[0] || j >= a.Nc[1]) return;
-  const int I[3] = {i, j, k};
+  INS_VOL_INDEX(a.sxc, 0, 0, 0, i >= a.Nc[0] || j >= a.Nc[1]);
   const int C = a.comp;
   const int h = C / 2;
-  const long long cc = i + j * a.sxc[1] + k * a.sxc[2];
 #pragma unroll
   for (int al = 0; al < D; ++al) {
     bool in = true;
@@ -84,7 +74,7 @@ __global__ __launch_bounds__(256) void k_filter(FilterArgs a) {
         }
       }
     }
-    a.v[al * a.scc + cc] = sum / cnt;
+    a.v[al * a.scc + c] = sum / cnt;
   }
 }
 
@@ -161,32 +151,28 @@ __global__ __launch_bounds__(256) void k_filter_tiled(FilterArgs a) {
 // --------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void k_reconstruct(FilterArgs a, const double* __restrict__ v, double* __restrict__ u) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  const int F[3] = {i, j, k};
+  INS_VOL_INDEX(a.sxf, 0, 0, 0, false);
   bool in = true;
 #pragma unroll
-  for (int b = 0; b < D; ++b) in = in && F[b] >= 1 && F[b] <= a.nf[b];
+  for (int b = 0; b < D; ++b) in = in && I[b] >= 1 && I[b] <= a.nf[b];
   if (!in) return;
   const int C = a.comp;
-  int c[3] = {0, 0, 0}, off[3] = {0, 0, 0};
+  int ci[3] = {0, 0, 0}, off[3] = {0, 0, 0};
   long long cc = 0;
 #pragma unroll
   for (int b = 0; b < D; ++b) {
-    c[b] = (F[b] + C - 1) / C;
-    off[b] = C * c[b] - F[b];
-    cc += c[b] * a.sxc[b];
+    ci[b] = (I[b] + C - 1) / C;
+    off[b] = C * ci[b] - I[b];
+    cc += ci[b] * a.sxc[b];
   }
-  const long long fc = i + j * a.sxf[1] + k * a.sxf[2];
 #pragma unroll
   for (int al = 0; al < D; ++al) {
-    const int cl = c[al] == 1 ? a.nc[al] : c[al] - 1;
-    const long long cleft = cc + (long long)(cl - c[al]) * a.sxc[al];
+    const int cl = ci[al] == 1 ? a.nc[al] : ci[al] - 1;
+    const long long cleft = cc + (long long)(cl - ci[al]) * a.sxc[al];
     double s = 0.0;
     s += (double)(C - off[al]) * v[al * a.scc + cc];
     s += (double)off[al] * v[al * a.scc + cleft];
-    u[al * a.scf + fc] = s / (double)C;
+    u[al * a.scf + c] = s / (double)C;
   }
 }
 
@@ -195,13 +181,8 @@ __global__ __launch_bounds__(256) void k_reconstruct(FilterArgs a, const double*
 // --------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void k_filter_face_pullback(FilterArgs a, const double* __restrict__ w, double* __restrict__ ubar) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= a.Nf[0] || j >= a.Nf[1]) return;
-  const int F[3] = {i, j, k};
+  INS_VOL_INDEX(a.sxf, 0, 0, 0, i >= a.Nf[0] || j >= a.Nf[1]);
   const int C = a.comp;
-  const long long fc = i + j * a.sxf[1] + k * a.sxf[2];
   double cnt = 1.0;
   for (int b = 1; b < D; ++b) cnt *= (double)C;
 #pragma unroll
@@ -210,32 +191,27 @@ __global__ __launch_bounds__(256) void k_filter_face_pullback(FilterArgs a, cons
     long long cc = 0;
 #pragma unroll
     for (int b = 0; b < D; ++b) {
-      const int q = F[b] - a.lo[al][b] - (b == al ? C - 1 : 0);
+      const int q = I[b] - a.lo[al][b] - (b == al ? C - 1 : 0);
       hit = hit && q >= 0 && (b != al || q % C == 0);
-      const int I = a.lo[al][b] + (q >= 0 ? q / C : 0);
-      hit = hit && I < a.hi[al][b];
-      cc += I * a.sxc[b];
+      const int Ic = a.lo[al][b] + (q >= 0 ? q / C : 0);
+      hit = hit && Ic < a.hi[al][b];
+      cc += Ic * a.sxc[b];
     }
-    ubar[al * a.scf + fc] = hit ? w[al * a.scc + cc] / cnt : 0.0;
+    ubar[al * a.scf + c] = hit ? w[al * a.scc + cc] / cnt : 0.0;
   }
 }
 
 template <int D>
 __global__ __launch_bounds__(256) void k_filter_volume_pullback(FilterArgs a, const double* __restrict__ w, double* __restrict__ ubar) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= a.Nf[0] || j >= a.Nf[1]) return;
-  const int F[3] = {i, j, k};
+  INS_VOL_INDEX(a.sxf, 0, 0, 0, i >= a.Nf[0] || j >= a.Nf[1]);
   const int C = a.comp;
   const int h = C / 2;
-  const long long fc = i + j * a.sxf[1] + k * a.sxf[2];
   bool in = true;
   int ct[3] = {0, 0, 0};  // coarse volume whose tangential window holds F
 #pragma unroll
   for (int b = 0; b < D; ++b) {
-    in = in && F[b] >= 1 && F[b] <= a.nf[b];
-    ct[b] = (F[b] + C - 1) / C;
+    in = in && I[b] >= 1 && I[b] <= a.nf[b];
+    ct[b] = (I[b] + C - 1) / C;
   }
   double cnt = (double)(C % 2 == 0 ? C + 1 : C);
   for (int b = 1; b < D; ++b) cnt *= (double)C;
@@ -247,18 +223,18 @@ __global__ __launch_bounds__(256) void k_filter_volume_pullback(FilterArgs a, co
 #pragma unroll
       for (int b = 0; b < D; ++b)
         if (b != al) base += ct[b] * a.sxc[b];
-      // coarse faces comp·I within h of F[al] (periodic): at most two, and two only for even comp at the shared plane
-      const int q = F[al] / C, r = F[al] % C;
+      // coarse faces comp·Ic within h of I[al] (periodic): at most two, and two only for even comp at the shared plane
+      const int q = I[al] / C, r = I[al] % C;
       if (r <= h) {
-        const int I = q == 0 ? a.nc[al] : q;
-        s += w[al * a.scc + base + I * a.sxc[al]];
+        const int Ic = q == 0 ? a.nc[al] : q;
+        s += w[al * a.scc + base + Ic * a.sxc[al]];
       }
       if (C - r <= h) {
-        const int I = q + 1 > a.nc[al] ? 1 : q + 1;
-        s += w[al * a.scc + base + I * a.sxc[al]];
+        const int Ic = q + 1 > a.nc[al] ? 1 : q + 1;
+        s += w[al * a.scc + base + Ic * a.sxc[al]];
       }
     }
-    ubar[al * a.scf + fc] = s / cnt;
+    ubar[al * a.scf + c] = s / cnt;
   }
 }
 
@@ -328,7 +304,7 @@ int launch_filter(const ins_grid* les, const ins_grid* dns, int comp, const doub
   INS_REQUIRE(u != v, "the filter cannot run in place");
   a.u = u;
   a.v = v;
-  const int D = les->g.D;
+  const GridDev& g = les->g;
   if (tiled_supported(les, dns, comp, VOL)) {
     dim3 block(64, 4, 1), grid(cdiv(a.nf[0], 64), cdiv(a.nc[1], 4), (unsigned)a.nc[2]);
     if (comp == 2)
@@ -337,15 +313,10 @@ int launch_filter(const ins_grid* les, const ins_grid* dns, int comp, const doub
       hipLaunchKernelGGL((k_filter_tiled<4, VOL>), grid, block, 0, s, a);
     else
       hipLaunchKernelGGL((k_filter_tiled<8, VOL>), grid, block, 0, s, a);
+    INS_LAUNCH_CHECK();
   } else {
-    dim3 grid, block;
-    box(a.Nc, D, grid, block);
-    if (D == 2)
-      hipLaunchKernelGGL((k_filter<2, VOL>), grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL((k_filter<3, VOL>), grid, block, 0, s, a);
+    INS_LAUNCH_D((k_filter<D, VOL>), box_launch(g.D, a.Nc), s, a);
   }
-  INS_LAUNCH_CHECK();
   return INS_OK;
 }
 
@@ -364,13 +335,8 @@ extern "C" int ins_reconstruct_f64(const ins_grid_t* dns, const ins_grid_t* les,
   int rc = prepare(les, dns, comp, true, "reconstruct", a);
   if (rc) return rc;
   INS_REQUIRE(u && v && u != v, "null or aliased field");
-  dim3 grid, block;
-  box(a.Nf, les->g.D, grid, block);
-  if (les->g.D == 2)
-    hipLaunchKernelGGL((k_reconstruct<2>), grid, block, 0, as_stream(stream), a, v, u);
-  else
-    hipLaunchKernelGGL((k_reconstruct<3>), grid, block, 0, as_stream(stream), a, v, u);
-  INS_LAUNCH_CHECK();
+  const GridDev& g = les->g;
+  INS_LAUNCH_D((k_reconstruct<D>), box_launch(g.D, a.Nf), as_stream(stream), a, v, u);
   return INS_OK;
 }
 
@@ -379,13 +345,8 @@ extern "C" int ins_filter_face_pullback_f64(const ins_grid_t* les, const ins_gri
   int rc = prepare(les, dns, comp, false, "the face average", a);
   if (rc) return rc;
   INS_REQUIRE(w && ubar && w != ubar, "null or aliased field");
-  dim3 grid, block;
-  box(a.Nf, les->g.D, grid, block);
-  if (les->g.D == 2)
-    hipLaunchKernelGGL((k_filter_face_pullback<2>), grid, block, 0, as_stream(stream), a, w, ubar);
-  else
-    hipLaunchKernelGGL((k_filter_face_pullback<3>), grid, block, 0, as_stream(stream), a, w, ubar);
-  INS_LAUNCH_CHECK();
+  const GridDev& g = les->g;
+  INS_LAUNCH_D((k_filter_face_pullback<D>), box_launch(g.D, a.Nf), as_stream(stream), a, w, ubar);
   return INS_OK;
 }
 
@@ -394,12 +355,7 @@ extern "C" int ins_filter_volume_pullback_f64(const ins_grid_t* les, const ins_g
   int rc = prepare(les, dns, comp, true, "the volume average", a);
   if (rc) return rc;
   INS_REQUIRE(w && ubar && w != ubar, "null or aliased field");
-  dim3 grid, block;
-  box(a.Nf, les->g.D, grid, block);
-  if (les->g.D == 2)
-    hipLaunchKernelGGL((k_filter_volume_pullback<2>), grid, block, 0, as_stream(stream), a, w, ubar);
-  else
-    hipLaunchKernelGGL((k_filter_volume_pullback<3>), grid, block, 0, as_stream(stream), a, w, ubar);
-  INS_LAUNCH_CHECK();
+  const GridDev& g = les->g;
+  INS_LAUNCH_D((k_filter_volume_pullback<D>), box_launch(g.D, a.Nf), as_stream(stream), a, w, ubar);
   return INS_OK;
 }

@@ -2,29 +2,9 @@
 // x along the 64-lane wavefront so every global access is a unit-stride row segment.
 // These are the reference-faithful twins of operators.jl; the tiled 3-D fast paths live in
 // ins_fast3d.hip and are parity-tested against these and against the CPU oracle.
-#include "ins_internal.h"
+#include "ins_stencil.h"
 
 namespace {
-
-struct Launch3 {
-  dim3 grid, block;
-};
-
-// Box of nx*ny*nz work-items, x fastest; 64x4 threads so each wavefront owns one x-row segment.
-inline Launch3 box_launch(int nx, int ny, int nz) {
-  Launch3 l;
-  l.block = dim3(64, 4, 1);
-  l.grid = dim3(cdiv(nx, 64), cdiv(ny, 4), (unsigned)nz);
-  return l;
-}
-
-template <int D>
-__device__ __forceinline__ bool in_range(const int (&I)[3], const int* lo, const int* hi) {
-  bool ok = true;
-#pragma unroll
-  for (int b = 0; b < D; ++b) ok = ok && (I[b] >= lo[b]) && (I[b] < hi[b]);
-  return ok;
-}
 
 // --------------------------------------------------------------------------------------------
 // convection / diffusion / fused                       operators.jl:389-415, 549-573, 647-690
@@ -34,12 +14,7 @@ __device__ __forceinline__ bool in_range(const int (&I)[3], const int* lo, const
 template <int D, int MODE, bool OVERWRITE>
 __global__ __launch_bounds__(256) void k_convdiff(GridDev g, double visc, const double* __restrict__ u,
                                                   double* __restrict__ F) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= g.N[0] || j >= g.N[1]) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
   bool inside = true;
 #pragma unroll
   for (int a = 0; a < D; ++a) inside = inside && I[a] >= 1 && I[a] <= g.N[a] - 2;
@@ -93,12 +68,7 @@ __global__ __launch_bounds__(256) void k_convdiff(GridDev g, double visc, const 
 // One pass instead of three (kernel, k_combine, the ustart snapshot).  `epi.ustar` must not alias `u` (neighbours are read).
 template <int D>
 __global__ __launch_bounds__(256) void k_convdiff_rk(GridDev g, double visc, const double* __restrict__ u, double* __restrict__ F, RkEpi epi) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= g.N[0] || j >= g.N[1]) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
   bool inside = true;
 #pragma unroll
   for (int a = 0; a < D; ++a) inside = inside && I[a] >= 1 && I[a] <= g.N[a] - 2;
@@ -142,12 +112,8 @@ __global__ __launch_bounds__(256) void k_convdiff_rk(GridDev g, double visc, con
 template <int MODE, bool OVERWRITE>
 int launch_convdiff(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s) {
   const GridDev& g = G->g;
-  Launch3 l = box_launch(g.N[0], g.N[1], g.N[2]);
-  if (g.D == 2)
-    hipLaunchKernelGGL((k_convdiff<2, MODE, OVERWRITE>), l.grid, l.block, 0, s, g, visc, u, F);
-  else
-    hipLaunchKernelGGL((k_convdiff<3, MODE, OVERWRITE>), l.grid, l.block, 0, s, g, visc, u, F);
-  INS_LAUNCH_CHECK();
+  Launch3 l = box_launch(g.D, g.N);
+  INS_LAUNCH_D((k_convdiff<D, MODE, OVERWRITE>), l, s, g, visc, u, F);
   return INS_OK;
 }
 
@@ -156,12 +122,7 @@ int launch_convdiff(const ins_grid* G, double visc, const double* u, double* F, 
 // --------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void k_divergence(GridDev g, const double* __restrict__ u, double* __restrict__ div) {
-  const int i = g.ip_lo[0] + blockIdx.x * 64 + threadIdx.x;
-  const int j = g.ip_lo[1] + blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? g.ip_lo[2] + (int)blockIdx.z : 0;
-  if (i >= g.ip_hi[0] || j >= g.ip_hi[1]) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], i >= g.ip_hi[0] || j >= g.ip_hi[1]);
   double d = 0.0;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -174,11 +135,7 @@ __global__ __launch_bounds__(256) void k_divergence(GridDev g, const double* __r
 // scalewithvolume!                                                          operators.jl:81-95
 template <int D>
 __global__ __launch_bounds__(256) void k_scalewithvolume(GridDev g, double* __restrict__ p) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= g.N[0] || j >= g.N[1]) return;
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
   double om = g.dx[0][i] * g.dx[1][j];
   if (D == 3) om = om * g.dx[2][k];
   p[c] *= om;
@@ -187,12 +144,7 @@ __global__ __launch_bounds__(256) void k_scalewithvolume(GridDev g, double* __re
 // pressuregradient! / applypressure!                                 operators.jl:170-178, 225-233
 template <int D, bool APPLY>
 __global__ __launch_bounds__(256) void k_pressuregradient(GridDev g, const double* __restrict__ p, double* __restrict__ G) {
-  const int i = 1 + blockIdx.x * 64 + threadIdx.x;
-  const int j = 1 + blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? 1 + (int)blockIdx.z : 0;
-  if (i > g.N[0] - 2 || j > g.N[1] - 2) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 1, 1, 1, i > g.N[0] - 2 || j > g.N[1] - 2);
   const double pc = p[c];
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -210,12 +162,7 @@ __global__ __launch_bounds__(256) void k_pressuregradient(GridDev g, const doubl
 // laplacian!                                                           operators.jl:328-363
 template <int D>
 __global__ __launch_bounds__(256) void k_laplacian(GridDev g, const double* __restrict__ p, double* __restrict__ L) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= g.N[0] || j >= g.N[1]) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
   if (!in_range<D>(I, g.ip_lo, g.ip_hi)) {
     L[c] = 0.0;  // `L .= 0` (operators.jl:359)
     return;
@@ -250,11 +197,7 @@ __global__ __launch_bounds__(256) void k_laplacian(GridDev g, const double* __re
 template <int D>
 __global__ __launch_bounds__(256) void k_kinetic_energy(GridDev g, const double* __restrict__ u, double* __restrict__ ke,
                                                         int interpolate_first) {
-  const int i = g.ip_lo[0] + blockIdx.x * 64 + threadIdx.x;
-  const int j = g.ip_lo[1] + blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? g.ip_lo[2] + (int)blockIdx.z : 0;
-  if (i >= g.ip_hi[0] || j >= g.ip_hi[1]) return;
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], i >= g.ip_hi[0] || j >= g.ip_hi[1]);
   double e = 0.0;
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -267,12 +210,7 @@ __global__ __launch_bounds__(256) void k_kinetic_energy(GridDev g, const double*
 // buf = Δu[α] / |u[α]| on Iu[α]; elsewhere +inf                                solver.jl:115-118
 template <int D>
 __global__ __launch_bounds__(256) void k_cfl(GridDev g, const double* __restrict__ u, int al, double* __restrict__ buf) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  const int j = blockIdx.y * 4 + threadIdx.y;
-  const int k = D == 3 ? (int)blockIdx.z : 0;
-  if (i >= g.N[0] || j >= g.N[1]) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
   buf[c] = g.dxu[al][I[al]] / fabs(u[al * g.sc + c]);
 }
 
@@ -283,12 +221,8 @@ __global__ __launch_bounds__(256) void k_cfl(GridDev g, const double* __restrict
 // ------------------------------------------------------------------------------------------------
 int ins_k_momentum_rk_fused_generic(const ins_grid* G, double visc, const double* u, double* k_out, const RkEpi& epi, hipStream_t s) {
   const GridDev& g = G->g;
-  Launch3 l = box_launch(g.N[0], g.N[1], g.N[2]);
-  if (g.D == 2)
-    hipLaunchKernelGGL(k_convdiff_rk<2>, l.grid, l.block, 0, s, g, visc, u, k_out, epi);
-  else
-    hipLaunchKernelGGL(k_convdiff_rk<3>, l.grid, l.block, 0, s, g, visc, u, k_out, epi);
-  INS_LAUNCH_CHECK();
+  Launch3 l = box_launch(g.D, g.N);
+  INS_LAUNCH_D((k_convdiff_rk<D>), l, s, g, visc, u, k_out, epi);
   return INS_OK;
 }
 
@@ -302,35 +236,24 @@ int ins_k_diffusion_overwrite(const ins_grid* G, double visc, const double* u, d
 
 int ins_k_divergence(const ins_grid* G, const double* u, double* div, hipStream_t s) {
   const GridDev& g = G->g;
-  Launch3 l = box_launch(g.ip_hi[0] - g.ip_lo[0], g.ip_hi[1] - g.ip_lo[1], g.ip_hi[2] - g.ip_lo[2]);
-  if (g.D == 2)
-    hipLaunchKernelGGL(k_divergence<2>, l.grid, l.block, 0, s, g, u, div);
-  else
-    hipLaunchKernelGGL(k_divergence<3>, l.grid, l.block, 0, s, g, u, div);
-  INS_LAUNCH_CHECK();
+  Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
+  INS_LAUNCH_D((k_divergence<D>), l, s, g, u, div);
   return INS_OK;
 }
 
 int ins_k_scalewithvolume(const ins_grid* G, double* p, hipStream_t s) {
   const GridDev& g = G->g;
-  Launch3 l = box_launch(g.N[0], g.N[1], g.N[2]);
-  if (g.D == 2)
-    hipLaunchKernelGGL(k_scalewithvolume<2>, l.grid, l.block, 0, s, g, p);
-  else
-    hipLaunchKernelGGL(k_scalewithvolume<3>, l.grid, l.block, 0, s, g, p);
-  INS_LAUNCH_CHECK();
+  Launch3 l = box_launch(g.D, g.N);
+  INS_LAUNCH_D((k_scalewithvolume<D>), l, s, g, p);
   return INS_OK;
 }
 
 template <bool APPLY>
 static int launch_pg(const ins_grid* G, const double* p, double* Gf, hipStream_t s) {
   const GridDev& g = G->g;
-  Launch3 l = box_launch(g.N[0] - 2, g.N[1] - 2, g.D == 3 ? g.N[2] - 2 : 1);
-  if (g.D == 2)
-    hipLaunchKernelGGL((k_pressuregradient<2, APPLY>), l.grid, l.block, 0, s, g, p, Gf);
-  else
-    hipLaunchKernelGGL((k_pressuregradient<3, APPLY>), l.grid, l.block, 0, s, g, p, Gf);
-  INS_LAUNCH_CHECK();
+  const int lo[3] = {1, 1, 1}, hi[3] = {g.N[0] - 1, g.N[1] - 1, g.N[2] - 1};
+  Launch3 l = box_launch(g.D, lo, hi);
+  INS_LAUNCH_D((k_pressuregradient<D, APPLY>), l, s, g, p, Gf);
   return INS_OK;
 }
 
@@ -338,12 +261,8 @@ int ins_k_applypressure(const ins_grid* G, double* u, const double* p, hipStream
 
 int ins_k_laplacian(const ins_grid* G, const double* p, double* L, hipStream_t s) {
   const GridDev& g = G->g;
-  Launch3 l = box_launch(g.N[0], g.N[1], g.N[2]);
-  if (g.D == 2)
-    hipLaunchKernelGGL(k_laplacian<2>, l.grid, l.block, 0, s, g, p, L);
-  else
-    hipLaunchKernelGGL(k_laplacian<3>, l.grid, l.block, 0, s, g, p, L);
-  INS_LAUNCH_CHECK();
+  Launch3 l = box_launch(g.D, g.N);
+  INS_LAUNCH_D((k_laplacian<D>), l, s, g, p, L);
   return INS_OK;
 }
 
@@ -405,13 +324,9 @@ extern "C" int ins_momentum_f64(const ins_grid_t* G, double visc, const double* 
 extern "C" int ins_kinetic_energy_f64(const ins_grid_t* G, const double* u, double* ke, int interpolate_first, void* stream) {
   INS_ARGS2(G, u, ke);
   const GridDev& g = G->g;
-  Launch3 l = box_launch(g.ip_hi[0] - g.ip_lo[0], g.ip_hi[1] - g.ip_lo[1], g.ip_hi[2] - g.ip_lo[2]);
+  Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
   hipStream_t s = as_stream(stream);
-  if (g.D == 2)
-    hipLaunchKernelGGL(k_kinetic_energy<2>, l.grid, l.block, 0, s, g, u, ke, interpolate_first);
-  else
-    hipLaunchKernelGGL(k_kinetic_energy<3>, l.grid, l.block, 0, s, g, u, ke, interpolate_first);
-  INS_LAUNCH_CHECK();
+  INS_LAUNCH_D((k_kinetic_energy<D>), l, s, g, u, ke, interpolate_first);
   return INS_OK;
 }
 
@@ -447,12 +362,8 @@ extern "C" int ins_cfl_timestep_f64(const ins_grid_t* G, double Re, const double
     double damin = INFINITY;
     for (int i = g.iu_lo[a][a]; i < g.iu_hi[a][a]; ++i) damin = fmin(damin, G->desc.dxu[a][i]);
     const double dt_diff = Re * damin * damin / 2;
-    Launch3 l = box_launch(g.N[0], g.N[1], g.N[2]);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_cfl<2>, l.grid, l.block, 0, s, g, u, a, buf.p);
-    else
-      hipLaunchKernelGGL(k_cfl<3>, l.grid, l.block, 0, s, g, u, a, buf.p);
-    INS_LAUNCH_CHECK();
+    Launch3 l = box_launch(g.D, g.N);
+    INS_LAUNCH_D((k_cfl<D>), l, s, g, u, a, buf.p);
     double dt_conv;
     int rc = ins_k_reduce(G, 2, buf.p, nullptr, g.iu_lo[a], g.iu_hi[a], &dt_conv, s);
     if (rc) return rc;

@@ -8,7 +8,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "ins_internal.h"
+#include "ins_stencil.h"
 
 namespace {
 
@@ -782,16 +782,6 @@ inline BoxLaunch full_box(const GridDev& g) {
   return l;
 }
 
-// K<2> or K<3> by the dimension of `g`, on stream `s` (both from the enclosing scope), then the launch check
-#define LAUNCH_D(K, grid, block, ...)                                           \
-  do {                                                                          \
-    if (g.D == 2)                                                               \
-      hipLaunchKernelGGL(K<2>, grid, block, 0, s, __VA_ARGS__);                 \
-    else                                                                        \
-      hipLaunchKernelGGL(K<3>, grid, block, 0, s, __VA_ARGS__);                 \
-    INS_LAUNCH_CHECK();                                                         \
-  } while (0)
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -956,7 +946,7 @@ static int spectral_transform(ins_poisson* ps, hipStream_t s, const double* u = 
         if ((rc = ins_k_zsolve(ph, n2, (long long)kxn * ps->kmax[1], ps->ahat[0], kxn, ps->ahat[1], ps->ahat[2], ps->tw, inv_np, true, s))) return rc;
       } else {
         dim3 block(64, 4, 1), grid(cdiv(kxn, 64), cdiv(ps->kmax[1], 4), g.D == 3 ? ps->kmax[2] : 1);
-        LAUNCH_D(k_symbol, grid, block, ps->phat, ps->ahat[0], ps->ahat[1], ps->ahat[2], kxn, ps->kmax[1], inv_np);  // (2-D: ahat[2] == nullptr)
+        INS_LAUNCH_D((k_symbol<D>), (Launch3{grid, block}), s, ps->phat, ps->ahat[0], ps->ahat[1], ps->ahat[2], kxn, ps->kmax[1], inv_np);  // (2-D: ahat[2] == nullptr)
       }
       INS_FFT_TRY(hipfftExecZ2D(ps->plan_inv, ps->phat, ps->pI));
       return INS_OK;
@@ -997,11 +987,7 @@ template <bool PACK>
 static int pack_box(const ins_poisson* ps, double* p, double* buf, hipStream_t s, const double* shift = nullptr) {
   const GridDev& g = ps->grid->g;
   dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), g.D == 3 ? ps->np[2] : 1);
-  if (g.D == 2)
-    hipLaunchKernelGGL((k_pack<2, PACK>), grid, block, 0, s, g, p, buf, ps->np[0], ps->np[1], shift);
-  else
-    hipLaunchKernelGGL((k_pack<3, PACK>), grid, block, 0, s, g, p, buf, ps->np[0], ps->np[1], shift);
-  INS_LAUNCH_CHECK();
+  INS_LAUNCH_D((k_pack<D, PACK>), (Launch3{grid, block}), s, g, p, buf, ps->np[0], ps->np[1], shift);
   return INS_OK;
 }
 
@@ -1071,7 +1057,7 @@ static int cg_remove_mean(ins_poisson* ps, double* p, hipStream_t s) {
   double sum;
   int rc = ins_k_reduce(G, 3, p, nullptr, g.ip_lo, g.ip_hi, &sum, s);
   if (rc) return rc;
-  LAUNCH_D(k_shift, l.grid, l.block, g, p, sum / (double)ps->ndof);
+  INS_LAUNCH_D((k_shift<D>), l, s, g, p, sum / (double)ps->ndof);
   return INS_OK;
 }
 
@@ -1147,7 +1133,7 @@ static int cg_solve(ins_poisson* ps, double* p, hipStream_t s) {
   double ss;
   const bool bordered = ps->bordered && ps->singular;
   if (bordered && (rc = cg_remove_mean(ps, p, s))) return rc;
-  LAUNCH_D(k_cg_init, l.grid, l.block, g, p, ps->r, ps->q, ps->L, partial);
+  INS_LAUNCH_D((k_cg_init<D>), l, s, g, p, ps->r, ps->q, ps->L, partial);
   if ((rc = finish_sum(G, partial, l.nblk, s, &ss))) return rc;
   double residual = std::sqrt(ss);
   const double tolerance = std::fmax(ps->reltol * residual, ps->abstol);
@@ -1155,17 +1141,17 @@ static int cg_solve(ins_poisson* ps, double* p, hipStream_t s) {
   long long it = 0;
   while (it < ps->maxiter && residual > tolerance) {
     double rho, qL;
-    LAUNCH_D(k_cg_precond, l.grid, l.block, g, ps->r, ps->dinv, ps->L, partial);
+    INS_LAUNCH_D((k_cg_precond<D>), l, s, g, ps->r, ps->dinv, ps->L, partial);
     if ((rc = finish_sum(G, partial, l.nblk, s, &rho))) return rc;
     const double beta = rho / rho_prev;
     hipLaunchKernelGGL(k_cg_dir, dim3(std::min<long long>((G->ncell + 255) / 256, 4096)), dim3(256), 0, s, G->ncell, beta, ps->L, ps->q);
     INS_LAUNCH_CHECK();
     if ((rc = ins_k_apply_bc_p(G, ps->q, s))) return rc;
     if ((rc = ins_k_laplacian(G, ps->q, ps->L, s))) return rc;
-    LAUNCH_D(k_cg_dot, l.grid, l.block, g, ps->q, ps->L, partial);
+    INS_LAUNCH_D((k_cg_dot<D>), l, s, g, ps->q, ps->L, partial);
     if ((rc = finish_sum(G, partial, l.nblk, s, &qL))) return rc;
     const double alpha = rho / qL;
-    LAUNCH_D(k_cg_update, l.grid, l.block, g, alpha, p, ps->r, ps->q, ps->L, partial);
+    INS_LAUNCH_D((k_cg_update<D>), l, s, g, alpha, p, ps->r, ps->q, ps->L, partial);
     if ((rc = finish_sum(G, partial, l.nblk, s, &ss))) return rc;
     rho_prev = rho;
     residual = std::sqrt(ss);
@@ -1377,7 +1363,7 @@ static int fdm_rhs(const ins_grid* G, ins_poisson* ps, const double* u, double* 
 #undef INS_DIVFOLD
   } else {
     const dim3 grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), g.D == 3 ? ps->np[2] : 1);
-    LAUNCH_D(k_div_to_pI, grid, block, g, u, buf, ps->np[0], ps->np[1]);
+    INS_LAUNCH_D((k_div_to_pI<D>), (Launch3{grid, block}), s, g, u, buf, ps->np[0], ps->np[1]);
   }
   INS_LAUNCH_CHECK();
   return INS_OK;
@@ -1436,10 +1422,10 @@ int ins_k_project(const ins_grid* G, ins_poisson* ps, double* u, double* p, hipS
   int rc;
   if (ps->kind == POISSON_SPECTRAL) {
     dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), g.D == 3 ? ps->np[2] : 1);
-    LAUNCH_D(k_div_to_pI, grid, block, g, u, ps->pI, ps->np[0], ps->np[1]);
+    INS_LAUNCH_D((k_div_to_pI<D>), (Launch3{grid, block}), s, g, u, ps->pI, ps->np[0], ps->np[1]);
     if ((rc = spectral_transform(ps, s))) return rc;
     dim3 gridp(cdiv(g.N[0], 64), cdiv(g.N[1], 4), (unsigned)g.N[2]);
-    LAUNCH_D(k_grad_from_pI, gridp, block, g, u, p, ps->pI, ps->np[0], ps->np[1], ps->np[2]);  // (2-D: np[2] == 1)
+    INS_LAUNCH_D((k_grad_from_pI<D>), (Launch3{gridp, block}), s, g, u, p, ps->pI, ps->np[0], ps->np[1], ps->np[2]);  // (2-D: np[2] == 1)
     return INS_OK;
   }
   if (ins_k_project_fdm_fused(ps)) return fdm_project(G, ps, u, u, p, s);

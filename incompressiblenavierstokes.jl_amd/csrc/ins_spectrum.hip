@@ -7,7 +7,7 @@
 // volume instead of a rocFFT 3-D plan (round 2: 1.71 ms for the three components at 256^3, 0.09 of 8 TB/s); other boxes: a hipFFT D2Z plan.
 // Shell sums: the index list is cut into chunks of 4096 that do not cross shells, one workgroup per chunk, and the chunk sums of a shell are added in
 // order by one work-item — deterministic, and 2 000 workgroups instead of one wavefront per shell.
-#include "ins_internal.h"
+#include "ins_stencil.h"
 
 struct ins_spectrum {
   const ins_grid* grid;
@@ -196,11 +196,7 @@ extern "C" int ins_spectrum_f64(ins_spectrum_t* S, const double* u, double* ehat
   dim3 block(64, 4, 1), grid(cdiv(S->np[0], 64), cdiv(S->np[1], 4), (unsigned)S->np[2]);
   for (int a = 0; a < g.D; ++a) {
     if (!S->own) {
-      if (g.D == 2)
-        hipLaunchKernelGGL(k_strip<2>, grid, block, 0, s, g, u + a * g.sc, S->real, S->np[0], S->np[1]);
-      else
-        hipLaunchKernelGGL(k_strip<3>, grid, block, 0, s, g, u + a * g.sc, S->real, S->np[0], S->np[1]);
-      INS_LAUNCH_CHECK();
+      INS_LAUNCH_D((k_strip<D>), (Launch3{grid, block}), s, g, u + a * g.sc, S->real, S->np[0], S->np[1]);
     }
     if (S->own) {
       double* ph = reinterpret_cast<double*>(S->hat);

@@ -8,61 +8,9 @@
 // written once by one work-item, no atomics, so every result is bitwise reproducible.  fp64, 2-D and 3-D, any BC mix, uniform and stretched
 // grids.  One kernel template serves the four operator-level entries and the fused per-stage entry: PARTS selects the terms, so the fused
 // launch forms exactly the sums of the operator-level ones.
-#include "ins_internal.h"
+#include "ins_stencil.h"
 
 namespace {
-
-// Whole padded array as a 1-D grid of 64x4 workgroups in the XCD-aware order of ins_fields.hip: id & 7 selects one of 8 bands of rows, inside
-// it tiles run x fastest, then y, then z, so the k-1 / k+1 planes a stencil re-reads stay in the L2 of the XCD that read them.
-struct BoxMap {
-  int ntx, nty, nty_l;
-};
-struct Launch3 {
-  dim3 grid, block;
-  BoxMap map;
-};
-inline Launch3 padded_launch(const GridDev& g) {
-  Launch3 l;
-  l.block = dim3(64, 4, 1);
-  l.map.ntx = (int)cdiv(g.N[0], 64);
-  l.map.nty = (int)cdiv(g.N[1], 4);
-  l.map.nty_l = (l.map.nty + 7) / 8;
-  l.grid = dim3(8u * l.map.ntx * l.map.nty_l * (unsigned)(g.D == 3 ? g.N[2] : 1), 1, 1);
-  return l;
-}
-
-// Coordinates of I shifted by s in direction b.
-#define INS_SH(I, b, s) ((I)[0] + ((b) == 0) * (s)), ((I)[1] + ((b) == 1) * (s)), ((I)[2] + ((b) == 2) * (s))
-
-// Safe for any I, out-of-array indices included (ip_lo >= 1, ip_hi <= N-1; iu_lo >= 0, iu_hi <= N).
-template <int D>
-__device__ __forceinline__ bool in_ip(const GridDev& g, int i0, int i1, int i2) {
-  const int I[3] = {i0, i1, i2};
-  bool ok = true;
-#pragma unroll
-  for (int b = 0; b < D; ++b) ok = ok && I[b] >= g.ip_lo[b] && I[b] < g.ip_hi[b];
-  return ok;
-}
-
-// I ∈ Iu[al]: the range gravity! writes (k_gravity)
-template <int D>
-__device__ __forceinline__ bool in_iu(const GridDev& g, int al, int i0, int i1, int i2) {
-  const int I[3] = {i0, i1, i2};
-  bool ok = true;
-#pragma unroll
-  for (int b = 0; b < D; ++b) ok = ok && I[b] >= g.iu_lo[al][b] && I[b] < g.iu_hi[al][b];
-  return ok;
-}
-
-// I is a degree of freedom of component al in diffusion! (k_convdiff, and dof() of ins_adjoint.hip): inside 1..N-2 and inside Iu[al]
-template <int D>
-__device__ __forceinline__ bool dof(const GridDev& g, int al, int i0, int i1, int i2) {
-  const int I[3] = {i0, i1, i2};
-  bool ok = true;
-#pragma unroll
-  for (int b = 0; b < D; ++b) ok = ok && I[b] >= 1 && I[b] <= g.N[b] - 2 && I[b] >= g.iu_lo[al][b] && I[b] < g.iu_hi[al][b];
-  return ok;
-}
 
 // --------------------------------------------------------------------------------------------
 // gravity_adjoint                                                        operators.jl:892-908
@@ -230,17 +178,7 @@ struct TempAdjArgs {
 
 template <int D, int PARTS, bool TOVER>
 __global__ __launch_bounds__(256) void k_temp_adjoint(GridDev g, BoxMap L, TempAdjArgs a) {
-  int seq = (int)(blockIdx.x >> 3);
-  const int tx = seq % L.ntx;
-  seq /= L.ntx;
-  const int ty = (int)(blockIdx.x & 7) * L.nty_l + seq % L.nty_l;
-  if (ty >= L.nty) return;
-  const int i = tx * 64 + threadIdx.x;
-  const int j = ty * 4 + threadIdx.y;
-  const int k = D == 3 ? seq / L.nty_l : 0;
-  if (i >= g.N[0] || j >= g.N[1]) return;
-  const int I[3] = {i, j, k};
-  const long long c = i + j * g.sx[1] + k * g.sx[2];
+  INS_BANDED_INDEX(0, 0, 0, g.N[0], g.N[1]);
   if (PARTS & (P_GRAV | P_CDT_T)) {
     double v = 0.0;
     if (PARTS & P_GRAV) v += gravity_tempbar<D>(g, a.gdir, a.a2, a.Fbar + a.gdir * g.sc, I, c);
@@ -261,12 +199,8 @@ __global__ __launch_bounds__(256) void k_temp_adjoint(GridDev g, BoxMap L, TempA
 template <int PARTS, bool TOVER>
 int launch_temp_adjoint(const ins_grid* G, const TempAdjArgs& a, hipStream_t s) {
   const GridDev& g = G->g;
-  const Launch3 l = padded_launch(g);
-  if (g.D == 2)
-    hipLaunchKernelGGL((k_temp_adjoint<2, PARTS, TOVER>), l.grid, l.block, 0, s, g, l.map, a);
-  else
-    hipLaunchKernelGGL((k_temp_adjoint<3, PARTS, TOVER>), l.grid, l.block, 0, s, g, l.map, a);
-  INS_LAUNCH_CHECK();
+  const Launch3 l = banded_launch(g.D, g.N);
+  INS_LAUNCH_D((k_temp_adjoint<D, PARTS, TOVER>), l, s, g, l.map, a);
   return INS_OK;
 }
 
@@ -277,20 +211,10 @@ int launch_temp_adjoint(const ins_grid* G, const TempAdjArgs& a, hipStream_t s) 
 //   x[i] = x[j] into (x̄[j] += x̄[i]; x̄[i] = 0) and x[i] = value into x̄[i] = 0.  The Dirichlet values (constant or callable) only change the
 //   constant part, so neither they nor t enter.
 // --------------------------------------------------------------------------------------------
-__device__ __forceinline__ void move_to(double* __restrict__ x, long long from, long long to) {
-  const double t = x[from];
-  x[from] = 0.0;
-  x[to] += t;
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void k_bc_temp_pullback(GridDev g, double* __restrict__ tb, int be, int bcl, int bcr) {
-  const int o0 = be == 0 ? 1 : 0;
-  const int o1 = be == 2 ? 1 : 2;
-  const int q0 = blockIdx.x * 256 + threadIdx.x;
-  const int q1 = D == 3 ? (int)blockIdx.y : 0;
-  if (q0 >= g.N[o0]) return;
-  double* x = tb + q0 * g.sx[o0] + (D == 3 ? q1 * g.sx[o1] : 0);
+  INS_LINE_INDEX(be);
+  double* x = tb + base;
   const long long sb = g.sx[be];
   const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
   if (bcl == INS_BC_PERIODIC) {  // forward: x[ia] = x[ib-1]; x[ib] = x[ia+1]
@@ -309,8 +233,6 @@ __global__ __launch_bounds__(256) void k_bc_temp_pullback(GridDev g, double* __r
       move_to(x, i * sb, jn * sb);
   }
 }
-
-#undef INS_SH
 
 // z-slab grids (INS_BC_HALO sides): the ghost planes belong to another rank, whose cotangents this rank does not hold
 int refuse_slab(const ins_grid* G, const char* what) {
@@ -340,13 +262,7 @@ extern "C" int ins_apply_bc_temp_pullback_f64(const ins_grid_t* G, const int32_t
     INS_REQUIRE((bc[2 * be] == INS_BC_PERIODIC) == (bc[2 * be + 1] == INS_BC_PERIODIC), "periodic on both sides");
   }
   for (int be = g.D - 1; be >= 0; --be) {  // reverse of ins_apply_bc_temp_f64
-    const int o0 = be == 0 ? 1 : 0, o1 = be == 2 ? 1 : 2;
-    dim3 grid(cdiv(g.N[o0], 256), g.D == 3 ? g.N[o1] : 1, 1);
-    if (g.D == 2)
-      hipLaunchKernelGGL(k_bc_temp_pullback<2>, grid, dim3(256), 0, as_stream(stream), g, tempbar, be, (int)bc[2 * be], (int)bc[2 * be + 1]);
-    else
-      hipLaunchKernelGGL(k_bc_temp_pullback<3>, grid, dim3(256), 0, as_stream(stream), g, tempbar, be, (int)bc[2 * be], (int)bc[2 * be + 1]);
-    INS_LAUNCH_CHECK();
+    INS_LAUNCH_D((k_bc_temp_pullback<D>), line_launch(g, be, 1), as_stream(stream), g, tempbar, be, (int)bc[2 * be], (int)bc[2 * be + 1]);
   }
   return INS_OK;
 }

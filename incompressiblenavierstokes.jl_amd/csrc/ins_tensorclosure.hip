@@ -14,7 +14,7 @@
 // and for Z = X·Y with cotangent Zbar:  Xbar += Zbar·Yᵀ,  Ybar += Xᵀ·Zbar  (the two-factor case of
 // X_j bar += (X_1 … X_{j-1})ᵀ Mbar (X_{j+1} … X_k)ᵀ, applied along the product tree);  tr(X·Y) with cotangent v: Xbar += v Yᵀ, Ybar += v Xᵀ.
 // S and R are treated as independent full matrices; then ∇ubar = sym(Sbar) + skew(Rbar).
-#include "ins_internal.h"
+#include "ins_stencil.h"
 
 namespace {
 
@@ -121,23 +121,6 @@ __host__ __device__ constexpr int sym_index(int a, int b) {  // [xx, yy, (zz), x
   if (D == 2) return 2;
   const int lo = a < b ? a : b, hi = a < b ? b : a;
   return lo == 0 ? (hi == 1 ? 3 : 4) : 5;
-}
-
-template <int D>
-__device__ __forceinline__ bool in_ip(const GridDev& g, const int (&I)[3]) {
-  bool ok = true;
-#pragma unroll
-  for (int b = 0; b < D; ++b) ok = ok && I[b] >= g.ip_lo[b] && I[b] < g.ip_hi[b];
-  return ok;
-}
-
-// Iu[al] alone (the write set of k_divoftensor); false for any index outside the padded array
-template <int D>
-__device__ __forceinline__ bool in_iu(const GridDev& g, int al, const int (&I)[3]) {
-  bool ok = true;
-#pragma unroll
-  for (int b = 0; b < D; ++b) ok = ok && I[b] >= g.iu_lo[al][b] && I[b] < g.iu_hi[al][b] && I[b] >= 0 && I[b] < g.N[b];
-  return ok;
 }
 
 // ∇(u, I, Δ, Δu) and its symmetric / skew parts at the pressure point I (operators.jl:1023-1033): the expressions of gradu in ins_fields.hip
@@ -320,22 +303,12 @@ __device__ __forceinline__ Mat<D> full_cotangent(const GridDev& g, const double*
   return T;
 }
 
-// work-item -> volume of the box starting at (l0, l1, l2): x along the wavefront, 4 rows per block, one plane per grid layer
-#define INS_TC_INDEX(l0, l1, l2)                       \
-  const int i = (l0) + blockIdx.x * 64 + threadIdx.x;  \
-  const int j = (l1) + blockIdx.y * 4 + threadIdx.y;   \
-  const int k = D == 3 ? (l2) + (int)blockIdx.z : 0;   \
-  const int I[3] = {i, j, k};                          \
-  const long long c = i + j * g.sx[1] + k * g.sx[2];   \
-  (void)I
-
 // --------------------------------------------------------------------------------------------
 // forward: invariants and fused stress (write Ip)
 // --------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void k_tc_invariants(GridDev g, const double* __restrict__ u, double* __restrict__ V) {
-  INS_TC_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2]);
-  if (!in_ip<D>(g, I)) return;
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
   Mat<D> S, R;
   strain_rotation<D>(g, u, c, I, S, R);
   double v[5];
@@ -347,8 +320,7 @@ __global__ __launch_bounds__(256) void k_tc_invariants(GridDev g, const double* 
 
 template <int D>
 __global__ __launch_bounds__(256) void k_tc_stress(GridDev g, const double* __restrict__ u, const double* __restrict__ a, double* __restrict__ tau) {
-  INS_TC_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2]);
-  if (!in_ip<D>(g, I)) return;
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
   Mat<D> S, R;
   strain_rotation<D>(g, u, c, I, S, R);
   Mat<D> T = mzero<D>();
@@ -365,10 +337,9 @@ __global__ __launch_bounds__(256) void k_tc_stress(GridDev g, const double* __re
 // abar_i = <T, B_i> over the whole padded array (0 outside Ip, where the forward reads no a)
 template <int D>
 __global__ __launch_bounds__(256) void k_tc_abar(GridDev g, const double* __restrict__ u, const double* __restrict__ taubar, double* __restrict__ abar) {
-  INS_TC_INDEX(0, 0, 0);
-  if (i >= g.N[0] || j >= g.N[1]) return;
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
   constexpr int nb = D == 2 ? 3 : 11;
-  if (!in_ip<D>(g, I)) {
+  if (!in_ip<D>(g, i, j, k)) {
 #pragma unroll
     for (int ib = 0; ib < nb; ++ib) abar[ib * g.sc + c] = 0.0;
     return;
@@ -383,8 +354,7 @@ __global__ __launch_bounds__(256) void k_tc_abar(GridDev g, const double* __rest
 template <int D, bool HASA, bool HASV>
 __global__ __launch_bounds__(256) void k_tc_gradbar(GridDev g, const double* __restrict__ u, const double* __restrict__ a, const double* __restrict__ taubar,
                                                     const double* __restrict__ Vbar, double* __restrict__ gb) {
-  INS_TC_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2]);
-  if (!in_ip<D>(g, I)) return;
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
   Mat<D> S, R;
   strain_rotation<D>(g, u, c, I, S, R);
   double vb[5] = {0, 0, 0, 0, 0};
@@ -411,8 +381,7 @@ __global__ __launch_bounds__(256) void k_tc_gradbar(GridDev g, const double* __r
 template <int D, bool HASB, bool HASV>
 __global__ __launch_bounds__(256) void k_tb_gradbar(GridDev g, const double* __restrict__ u, const double* __restrict__ Bbar, const double* __restrict__ Vbar,
                                                     double* __restrict__ gb) {
-  INS_TC_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2]);
-  if (!in_ip<D>(g, I)) return;
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
   Mat<D> S, R;
   strain_rotation<D>(g, u, c, I, S, R);
   double vb[5] = {0, 0, 0, 0, 0};
@@ -440,8 +409,7 @@ __global__ __launch_bounds__(256) void k_tb_gradbar(GridDev g, const double* __r
 // --------------------------------------------------------------------------------------------
 template <int D, bool ACC>
 __global__ __launch_bounds__(256) void k_gradu_adjoint(GridDev g, const double* __restrict__ gb, double* __restrict__ ubar) {
-  INS_TC_INDEX(0, 0, 0);
-  if (i >= g.N[0] || j >= g.N[1]) return;
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
 #pragma unroll
   for (int a = 0; a < D; ++a) {
     const long long sa = g.sx[a];
@@ -451,10 +419,10 @@ __global__ __launch_bounds__(256) void k_gradu_adjoint(GridDev g, const double* 
       const long long sb = g.sx[b];
       const double* gab = gb + (long long)(a * D + b) * g.sc;
       if (a == b) {
-        if (in_ip<D>(g, I)) v += gab[c] * g.rdx[a][I[a]];
+        if (in_ip<D>(g, i, j, k)) v += gab[c] * g.rdx[a][I[a]];
         int J[3] = {I[0], I[1], I[2]};
         J[a] += 1;
-        if (in_ip<D>(g, J)) v -= gab[c + sa] * g.rdx[a][I[a] + 1];
+        if (in_ip<D>(g, J[0], J[1], J[2])) v -= gab[c + sa] * g.rdx[a][I[a] + 1];
       } else {
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
@@ -463,7 +431,7 @@ __global__ __launch_bounds__(256) void k_gradu_adjoint(GridDev g, const double* 
             int J[3] = {I[0], I[1], I[2]};
             J[a] += d;
             J[b] += s;
-            if (!in_ip<D>(g, J)) continue;  // J in Ip: 1 <= J_b <= N_b - 2, both table reads are inside
+            if (!in_ip<D>(g, J[0], J[1], J[2])) continue;  // J in Ip: 1 <= J_b <= N_b - 2, both table reads are inside
             const double r1 = g.rdxu[b][J[b]], r0 = g.rdxu[b][J[b] - 1];
             const double w = s < 0 ? r1 : (s == 0 ? r0 - r1 : -r0);
             v += gab[c + d * sa + s * sb] * w / 4;
@@ -487,15 +455,14 @@ __device__ __forceinline__ double dot_w(const GridDev& g, const double* __restri
   int J[3] = {I[0], I[1], I[2]};
   J[al] += dal;
   J[be] += dbe;
-  if (!in_iu<D>(g, al, J)) return 0.0;
+  if (!in_iu<D>(g, al, J[0], J[1], J[2])) return 0.0;
   const long long cj = J[0] + J[1] * g.sx[1] + (D == 3 ? J[2] * g.sx[2] : 0);
   return sbar[al * g.sc + cj] * g.rdx[be][J[be]] / 4;
 }
 
 template <int D>
 __global__ __launch_bounds__(256) void k_divoftensor_adjoint(GridDev g, const double* __restrict__ sbar, double* __restrict__ sigbar) {
-  INS_TC_INDEX(0, 0, 0);
-  if (i >= g.N[0] || j >= g.N[1]) return;
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
 #pragma unroll
   for (int a = 0; a < D; ++a)
 #pragma unroll
@@ -504,8 +471,8 @@ __global__ __launch_bounds__(256) void k_divoftensor_adjoint(GridDev g, const do
       if (a == b) {
         int J[3] = {I[0], I[1], I[2]};
         J[a] -= 1;
-        if (in_iu<D>(g, a, J)) v += sbar[a * g.sc + c - g.sx[a]] * g.rdxu[a][J[a]];
-        if (in_iu<D>(g, a, I)) v -= sbar[a * g.sc + c] * g.rdxu[a][I[a]];
+        if (in_iu<D>(g, a, J[0], J[1], J[2])) v += sbar[a * g.sc + c - g.sx[a]] * g.rdxu[a][J[a]];
+        if (in_iu<D>(g, a, i, j, k)) v -= sbar[a * g.sc + c] * g.rdxu[a][I[a]];
       } else {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -517,26 +484,6 @@ __global__ __launch_bounds__(256) void k_divoftensor_adjoint(GridDev g, const do
       sigbar[(long long)sym_index<D>(a, b) * g.sc + c] += v;
     }
 }
-
-#undef INS_TC_INDEX
-
-inline void whole_box(const GridDev& g, dim3& grid, dim3& block) {
-  block = dim3(64, 4, 1);
-  grid = dim3(cdiv(g.N[0], 64), cdiv(g.N[1], 4), (unsigned)(g.D == 3 ? g.N[2] : 1));
-}
-inline void ip_box(const GridDev& g, dim3& grid, dim3& block) {
-  block = dim3(64, 4, 1);
-  grid = dim3(cdiv(g.ip_hi[0] - g.ip_lo[0], 64), cdiv(g.ip_hi[1] - g.ip_lo[1], 4), (unsigned)(g.D == 3 ? g.ip_hi[2] - g.ip_lo[2] : 1));
-}
-
-#define INS_TC_LAUNCH(KERNEL2, KERNEL3, GRID, BLOCK, S, ...)                       \
-  do {                                                                             \
-    if (g.D == 2)                                                                  \
-      hipLaunchKernelGGL((KERNEL2), GRID, BLOCK, 0, S, g, __VA_ARGS__);            \
-    else                                                                           \
-      hipLaunchKernelGGL((KERNEL3), GRID, BLOCK, 0, S, g, __VA_ARGS__);            \
-    INS_LAUNCH_CHECK();                                                            \
-  } while (0)
 
 // the ∇ubar scratch of the grid handle: D·D scalar fields, allocated on first use (all pullbacks of one grid run on one stream at a time)
 int gradbar_scratch(const ins_grid* G, double** out) {
@@ -555,12 +502,11 @@ int gradbar_scratch(const ins_grid* G, double** out) {
 
 int launch_gradu_adjoint(const ins_grid* G, const double* gb, double* ubar, bool acc, hipStream_t s) {
   const GridDev& g = G->g;
-  dim3 grid, block;
-  whole_box(g, grid, block);
+  const Launch3 l = box_launch(g.D, g.N);
   if (acc)
-    INS_TC_LAUNCH((k_gradu_adjoint<2, true>), (k_gradu_adjoint<3, true>), grid, block, s, gb, ubar);
+    INS_LAUNCH_D((k_gradu_adjoint<D, true>), l, s, g, gb, ubar);
   else
-    INS_TC_LAUNCH((k_gradu_adjoint<2, false>), (k_gradu_adjoint<3, false>), grid, block, s, gb, ubar);
+    INS_LAUNCH_D((k_gradu_adjoint<D, false>), l, s, g, gb, ubar);
   return INS_OK;
 }
 
@@ -587,9 +533,8 @@ extern "C" int ins_tensorinvariants_f64(const ins_grid_t* G, const double* u, do
   INS_REQUIRE(G && u && V, "null argument");
   INS_TC_NO_SLAB(G);
   const GridDev& g = G->g;
-  dim3 grid, block;
-  ip_box(g, grid, block);
-  INS_TC_LAUNCH((k_tc_invariants<2>), (k_tc_invariants<3>), grid, block, as_stream(stream), u, V);
+  const Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
+  INS_LAUNCH_D((k_tc_invariants<D>), l, as_stream(stream), g, u, V);
   return INS_OK;
 }
 
@@ -598,9 +543,8 @@ extern "C" int ins_tensorclosure_stress_f64(const ins_grid_t* G, const double* u
   INS_TC_NO_SLAB(G);
   INS_REQUIRE(tau != u && tau != a, "tensorclosure stress cannot run in place");
   const GridDev& g = G->g;
-  dim3 grid, block;
-  ip_box(g, grid, block);
-  INS_TC_LAUNCH((k_tc_stress<2>), (k_tc_stress<3>), grid, block, as_stream(stream), u, a, tau);
+  const Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
+  INS_LAUNCH_D((k_tc_stress<D>), l, as_stream(stream), g, u, a, tau);
   return INS_OK;
 }
 
@@ -617,18 +561,14 @@ extern "C" int ins_tensorclosure_pullback_f64(const ins_grid_t* G, const double*
   double* gb = nullptr;
   int rc = gradbar_scratch(G, &gb);
   if (rc != INS_OK) return rc;
-  dim3 grid, block;
-  if (a) {
-    whole_box(g, grid, block);
-    INS_TC_LAUNCH((k_tc_abar<2>), (k_tc_abar<3>), grid, block, s, u, taubar, abar);
-  }
-  ip_box(g, grid, block);
+  if (a) INS_LAUNCH_D((k_tc_abar<D>), box_launch(g.D, g.N), s, g, u, taubar, abar);
+  const Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
   if (a && Vbar)
-    INS_TC_LAUNCH((k_tc_gradbar<2, true, true>), (k_tc_gradbar<3, true, true>), grid, block, s, u, a, taubar, Vbar, gb);
+    INS_LAUNCH_D((k_tc_gradbar<D, true, true>), l, s, g, u, a, taubar, Vbar, gb);
   else if (a)
-    INS_TC_LAUNCH((k_tc_gradbar<2, true, false>), (k_tc_gradbar<3, true, false>), grid, block, s, u, a, taubar, Vbar, gb);
+    INS_LAUNCH_D((k_tc_gradbar<D, true, false>), l, s, g, u, a, taubar, Vbar, gb);
   else
-    INS_TC_LAUNCH((k_tc_gradbar<2, false, true>), (k_tc_gradbar<3, false, true>), grid, block, s, u, a, taubar, Vbar, gb);
+    INS_LAUNCH_D((k_tc_gradbar<D, false, true>), l, s, g, u, a, taubar, Vbar, gb);
   return launch_gradu_adjoint(G, gb, ubar, accumulate != 0, s);
 }
 
@@ -643,14 +583,13 @@ extern "C" int ins_tensorbasis_pullback_f64(const ins_grid_t* G, const double* u
   double* gb = nullptr;
   int rc = gradbar_scratch(G, &gb);
   if (rc != INS_OK) return rc;
-  dim3 grid, block;
-  ip_box(g, grid, block);
+  const Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
   if (Bbar && Vbar)
-    INS_TC_LAUNCH((k_tb_gradbar<2, true, true>), (k_tb_gradbar<3, true, true>), grid, block, s, u, Bbar, Vbar, gb);
+    INS_LAUNCH_D((k_tb_gradbar<D, true, true>), l, s, g, u, Bbar, Vbar, gb);
   else if (Bbar)
-    INS_TC_LAUNCH((k_tb_gradbar<2, true, false>), (k_tb_gradbar<3, true, false>), grid, block, s, u, Bbar, Vbar, gb);
+    INS_LAUNCH_D((k_tb_gradbar<D, true, false>), l, s, g, u, Bbar, Vbar, gb);
   else
-    INS_TC_LAUNCH((k_tb_gradbar<2, false, true>), (k_tb_gradbar<3, false, true>), grid, block, s, u, Bbar, Vbar, gb);
+    INS_LAUNCH_D((k_tb_gradbar<D, false, true>), l, s, g, u, Bbar, Vbar, gb);
   return launch_gradu_adjoint(G, gb, ubar, accumulate != 0, s);
 }
 
@@ -659,8 +598,7 @@ extern "C" int ins_divoftensor_adjoint_f64(const ins_grid_t* G, const double* sb
   INS_TC_NO_SLAB(G);
   INS_REQUIRE(sbar != sigmabar, "divoftensor_adjoint! cannot run in place");
   const GridDev& g = G->g;
-  dim3 grid, block;
-  whole_box(g, grid, block);
-  INS_TC_LAUNCH((k_divoftensor_adjoint<2>), (k_divoftensor_adjoint<3>), grid, block, as_stream(stream), sbar, sigmabar);
+  const Launch3 l = box_launch(g.D, g.N);
+  INS_LAUNCH_D((k_divoftensor_adjoint<D>), l, as_stream(stream), g, sbar, sigmabar);
   return INS_OK;
 }
