@@ -546,6 +546,30 @@ int ins_rk_steps_f32(ins_rk32_t* rk, float visc, float* u, float dt, int nsteps,
 /* maximum(abs, divergence(u)) over Ip; blocking.  operators.jl:106-125 */
 int ins_max_abs_divergence_f32(const ins_grid_t* grid, ins_poisson32_t* ps, const float* u, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------- pullbacks of the `_f32` family (csrc/ins_adjoint32.hip)
+ * The Float32 twins of the `_f64` pullbacks above: each is the exact transpose of the `_f32` forward operator on the whole padded array, ghost
+ * volumes included.  Float fields, the fp64 grid handle (metric tables rounded to float where they enter the arithmetic), arithmetic in float,
+ * gather kernels without atomics, 2-D and 3-D, any mix of boundary conditions, uniform and stretched grids.  Slab (halo) grids: INS_ERR_UNSUPPORTED. */
+/* divergence_adjoint!(ubar, φ, setup)      operators.jl:127-145 (ubar += Dᵀφ over the whole padded array) */
+int ins_divergence_adjoint_f32(const ins_grid_t* grid, const float* phi, float* ubar, void* stream);
+/* pressuregradient_adjoint!(pbar, φ, setup) operators.jl:180-199 (pbar += Gᵀφ) */
+int ins_pressuregradient_adjoint_f32(const ins_grid_t* grid, const float* phi, float* pbar, void* stream);
+/* Pullback of momentum! (operators.jl:417-519, 575-616, 967-976) at the ghost-filled u, convection and diffusion in one launch: overwrites
+ * ubar = J(u)ᵀφbar over the whole padded array (accumulate = 0) or adds to it.  ubar must be another array than u and φbar. */
+int ins_momentum_pullback_f32(const ins_grid_t* grid, float visc, const float* u, const float* phibar, float* ubar, int accumulate, void* stream);
+/* apply_bc_u_pullback!(φbar, t, setup)     boundary_conditions.jl:169-206, 290-516, in place: the transpose of ins_apply_bc_u_f32 (constant
+ * boundary data), directions and sides walked in the reverse order of the fill. */
+int ins_apply_bc_u_pullback_f32(const ins_grid_t* grid, float* phibar, void* stream);
+/* apply_bc_p_pullback!(φbar, t, setup)     boundary_conditions.jl:208-230, 320-516, in place: the transpose of ins_apply_bc_p_f32 */
+int ins_apply_bc_p_pullback_f32(const ins_grid_t* grid, float* phibar, void* stream);
+/* Pullback of ins_project_f32 (pressure.jl:52-82, 15-19), in place, the transpose of what that entry does to the whole padded array.
+ *   wrapped solver (ins_poisson_wrap_f32): φbar ← φbar − Dᵀ·Ω·poisson·bc_pᵀ·Gᵀ·φbar with Gᵀφbar accumulated in double, the fp64 solve, and the
+ *     update rounded to float once — the mirror of the forward, which reads the left ghost column of u and leaves the ghosts alone;
+ *   spectral solver (ins_poisson_spectral_create_f32): the forward reads periodic images and refills the ghosts of u, u ↦ B·P·Z·u (Z drops the
+ *     ghosts, P projects the interior, B fills the ghosts); P is symmetric on a uniform periodic box, so φbar ← Z·P·Bᵀ·φbar.
+ * `pwork`: a float scalar field of scratch.  A wrapped spectral solver on an all-periodic box: INS_ERR_UNSUPPORTED. */
+int ins_project_pullback_f32(const ins_grid_t* grid, ins_poisson32_t* ps, float* phibar, float* pwork, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,7 @@ from .time_steppers import (
     timesteps_,
 )
 from . import autodiff as ad  # noqa: E402  (torch.autograd Functions over the pullback kernels: ins_amd.ad)
+from . import autodiff32 as ad32  # noqa: E402  (the same over float32 fields and the `_f32` pullbacks: ins_amd.ad32)
 
 from . import neuralclosure  # noqa: E402  (lib/NeuralClosure: filters, filtered-DNS data generation, closures, losses, training)
 from .neuralclosure import (FaceAverage, VolumeAverage, cnn, collocate, create_dataloader_post, create_dataloader_prior,  # noqa: E402

@@ -173,6 +173,12 @@ SIGNATURES = {
     "ins_rk_step_f32": (C.c_int, [vp, C.c_float, vp, C.c_float, vp]),
     "ins_rk_steps_f32": (C.c_int, [vp, C.c_float, vp, C.c_float, C.c_int, vp]),
     "ins_max_abs_divergence_f32": (C.c_int, [vp, vp, vp, C.POINTER(C.c_float), vp]),
+    "ins_divergence_adjoint_f32": (C.c_int, [vp, vp, vp, vp]),
+    "ins_pressuregradient_adjoint_f32": (C.c_int, [vp, vp, vp, vp]),
+    "ins_momentum_pullback_f32": (C.c_int, [vp, C.c_float, vp, vp, vp, C.c_int, vp]),
+    "ins_apply_bc_u_pullback_f32": (C.c_int, [vp, vp, vp]),
+    "ins_apply_bc_p_pullback_f32": (C.c_int, [vp, vp, vp]),
+    "ins_project_pullback_f32": (C.c_int, [vp, vp, vp, vp, vp]),
     "ins_comm_unique_id": (C.c_int, [vp]),
     "ins_comm_create": (C.c_int, [C.c_int, C.c_int, vp, C.POINTER(vp)]),
     "ins_comm_create_local": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]),

@@ -718,3 +718,11 @@ extern "C" int ins_max_abs_divergence_f32(const ins_grid_t* G, ins_poisson32_t* 
   *out = m / b.om;
   return INS_OK;
 }
+
+// What csrc/ins_adjoint32.hip needs of a Float32 solver handle: the wrapped fp64 solver (nullptr: a spectral Float32 solver) with its padded fp64 scratch,
+// and the grid the handle was made for.
+ins_poisson* ins_k32_wrapped(const ins_poisson32* ps, double** p64) {
+  *p64 = ps->p64;
+  return ps->wrap64;
+}
+const ins_grid* ins_k32_solver_grid(const ins_poisson32* ps) { return ps->grid; }

@@ -120,6 +120,47 @@ def project32_(u, setup, psolver, p):
     return u
 
 
+# ---- pullbacks (csrc/ins_adjoint32.hip): the exact transposes of the operators above on the whole padded float arrays
+def divergence_adjoint32_(ubar, φ, setup):
+    """operators.jl:127-145 (adds Dᵀφ to ubar)"""
+    _lib.call("ins_divergence_adjoint_f32", setup.handle, _ptr(setup, φ, 0), _ptr(setup, ubar, setup.grid.dimension), setup.stream)
+    return ubar
+
+
+def pressuregradient_adjoint32_(pbar, φ, setup):
+    """operators.jl:180-199 (adds Gᵀφ to pbar)"""
+    _lib.call("ins_pressuregradient_adjoint_f32", setup.handle, _ptr(setup, φ, setup.grid.dimension), _ptr(setup, pbar, 0), setup.stream)
+    return pbar
+
+
+def momentum_pullback32_(ubar, φbar, u, setup, accumulate=False):
+    """Pullback of momentum32_ at the ghost-filled `u` (convection + diffusion in one launch): ubar = J(u)ᵀφbar, or ubar += J(u)ᵀφbar with `accumulate`."""
+    D = setup.grid.dimension
+    _lib.call("ins_momentum_pullback_f32", setup.handle, float(1.0 / setup.Re), _ptr(setup, u, D), _ptr(setup, φbar, D), _ptr(setup, ubar, D),
+              int(bool(accumulate)), setup.stream)
+    return ubar
+
+
+def apply_bc_u_pullback32_(φbar, setup):
+    """boundary_conditions.jl:169-206, in place: the transpose of apply_bc_u32_ (constant boundary data)."""
+    _lib.call("ins_apply_bc_u_pullback_f32", setup.handle, _ptr(setup, φbar, setup.grid.dimension), setup.stream)
+    return φbar
+
+
+def apply_bc_p_pullback32_(φbar, setup):
+    """boundary_conditions.jl:208-230, in place: the transpose of apply_bc_p32_."""
+    _lib.call("ins_apply_bc_p_pullback_f32", setup.handle, _ptr(setup, φbar, 0), setup.stream)
+    return φbar
+
+
+def project_pullback32_(φbar, setup, psolver, pwork):
+    """Pullback of project32_ in place (pressure.jl:52-82, 15-19): the transpose of what project32_ does to the whole padded array with this
+    kind of solver (include/ins_hip.h); `pwork` is a float32 scalar field of scratch."""
+    D = setup.grid.dimension
+    _lib.call("ins_project_pullback_f32", setup.handle, psolver.handle, _ptr(setup, φbar, D), _ptr(setup, pwork, 0), setup.stream)
+    return φbar
+
+
 def max_abs_divergence32(u, setup, psolver):
     out = C.c_float()
     _lib.call("ins_max_abs_divergence_f32", setup.handle, psolver.handle, _ptr(setup, u, setup.grid.dimension), C.byref(out), setup.stream)
