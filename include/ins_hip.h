@@ -255,6 +255,15 @@ int ins_rk_profile_read(ins_rk_t* rk, double* momentum_ms, int64_t* momentum_lau
  * field the caller keeps alive, added to every stage force inside the stage kernels' combination (one more term: no extra pass).
  * NULL removes it.  With a force the steps of ins_rk_steps_f64 are not chained. */
 int ins_rk_set_bodyforce(ins_rk_t* rk, const double* force);
+
+/* Test hooks of the stage kernels that write the Poisson right-hand side themselves (fused periodic path, fp64, own-FFT solver, workgroups that
+ * span whole rows; INS_DISABLE_STAGE_RHS=1 switches the route off).  ins_dbg_stage_rhs_used: how many such stage kernels this integrator has
+ * enqueued.  ins_dbg_stage_rhs: one stage kernel through the production dispatch, u* = (1 - self_in) ustart + self_in u_in + coef_k kterm +
+ * coef_self F(u_in) into ustar (interior volumes) and its volume-scaled divergence into rhs (unpadded, device) when *used comes back 1;
+ * pI != NULL: u_in is an uncorrected stage velocity and pI its unpadded pressure. */
+int ins_dbg_stage_rhs_used(const ins_rk_t* rk, int64_t* launches);
+int ins_dbg_stage_rhs(ins_rk_t* rk, double visc, const double* u_in, const double* pI, const double* ustart, const double* kterm, double coef_k,
+                      double self_in, double coef_self, double* ustar, double* rhs, int32_t* used, void* stream);
 int ins_rk_pressure(const ins_rk_t* rk, double** p);
 /* The cache array ku[i] of ode_method_cache (time_steppers.jl).  It holds the stage force k_i only on the k-basis paths (INS_RK_KEEP_K=1
  * selects them everywhere); the fused stage loops work in the stage-velocity basis, where the periodic loop leaves the arrays untouched

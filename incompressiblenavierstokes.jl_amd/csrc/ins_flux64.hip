@@ -31,6 +31,8 @@ struct Plane {
   T v[3][R + 2];
   T h[3];  // packed halo columns: lane r = row r of column x0-1, lane 16+r = row r of column x0+64
   T raw[3][R];  // CORR: the output rows before the pressure correction (a term of the stage-velocity basis, ins_rk.hip)
+  T vm2;        // RHS: the y-component at row jb0-2 (the y-flux below the row whose v* the first output row's divergence needs)
+  T rawv0;      // RHS, CORR: the y-component at row jb0-1 before the pressure correction
 };
 
 // temperature rows of a register plane (EXTRA, a.tm): T rides along as a fourth component; vm1 = the y-component at the row BELOW the halo
@@ -47,8 +49,17 @@ struct TExt {
 // periodic image; 2 = z-slab: x, y periodic images, z through exchanged ghost planes, pI = [1 | nzl | 2] extended buffer.
 // EXTRA (extended stage loop, ins_rk_ext.hip): epi.extra is a vector field added to the stage force before it is used and stored
 // (k_i = F_i + closure(u_i) + gravity(temp_i), step_explicit_runge_kutta.jl:21-34).
-template <typename T, int R, int XW, bool FUSE, int CORR, bool SKEL = false, int NW = 4, bool EXTRA = false>
+// RHS (workgroups that span whole rows, 64 XW == n0; CORR 0 / 1): the kernel also stores the Poisson right-hand side Ω·div(u*) of the stage velocity
+// it writes, into a.epi.rhs_out (unpadded, the layout k_xfwd<XSRC_PI> reads), so the x-forward pass reads one scalar array instead of three components.
+// The three lower neighbours of a cell's divergence:
+//   x  u*(i-1): the wave shift; lane 0 takes lane 63 of the wavefront to the left (periodic inside the workgroup) through LDS.  The workgroup's one
+//      barrier per plane moves from the top of the plane to between the LDS write and the LDS read (two LDS slots, alternating by plane);
+//   y  v*(jb0-1), the row below the wavefront's first output row, belongs to another wavefront: it is computed here again, from the same expressions
+//      in the same order (so it is the value that wavefront stores): one more y-flux (row jb0-2 of v, of p), the v terms of the epilogue at row jb0-1;
+//   z  w*(k-1) is carried along the march; the march starts one plane early (k0-1, nothing stored) so the first plane of a chunk has it.
+template <typename T, int R, int XW, bool FUSE, int CORR, bool SKEL = false, int NW = 4, bool EXTRA = false, bool RHS = false>
 __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a) {
+  static_assert(!RHS || (FUSE && CORR <= 1 && !SKEL && !EXTRA), "right-hand side in the stage kernel: fused epilogue, periodic box, no extra terms");
   constexpr unsigned EB = (unsigned)sizeof(T);  // element bytes
   const T* const a_u = static_cast<const T*>(a.u);
   const T* const a_pI = static_cast<const T*>(a.pI);
@@ -65,6 +76,8 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
     tzi = seq / nty_local;
     if (tyi >= a.nty) return;
   }
+  __shared__ T rhs_lds_s[RHS ? 2 * NW * R : 1];  // RHS: u* of lane 63, [plane parity][wavefront][row]
+  T* const rhs_lds = rhs_lds_s;
   const int lane = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.y);
   const int wx = wave % XW, wy = wave / XW;
@@ -74,9 +87,10 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
   const int jb0 = (tyi * (NW / XW) + wy) * R;  // interior row of the first output row
   const int k0 = a.kB ? (tzi ? a.kB : a.k_lo) : a.k_lo + tzi * a.zc;  // padded plane index of the first output plane
   const int k1 = a.kB ? k0 + a.zc : min(k0 + a.zc, a.k_hi);
+  const int kw0 = RHS ? k0 - 1 : k0;  // first plane of the march
   if (x0 >= n0 || jb0 >= n1) {  // wavefront outside the box: it only keeps the workgroup's barrier count (one per plane)
-    if (a.bar)
-      for (int k = k0; k < k1; ++k) __builtin_amdgcn_s_barrier();
+    if (a.bar || RHS)
+      for (int k = kw0; k < k1; ++k) __builtin_amdgcn_s_barrier();
     return;
   }
   const long long sz = (long long)N0 * N1;
@@ -98,6 +112,9 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
     for (int rr = 0; rr < R + 3; ++rr) qrow[rr] = (unsigned)((prow_of(jb0 - 1 + rr) - 1) * n0) * EB;
   }
   const unsigned ubytes = (unsigned)sz * EB, qbytes = (unsigned)(n0 * n1) * EB;
+  // RHS: rows jb0-2 (stencil input, pressure) and jb0-1 (epilogue terms) through the periodic image
+  const unsigned urowm2 = (unsigned)((wrapi(jb0 - 2, n1) + 1) * N0) * EB, qrowm2 = (unsigned)(wrapi(jb0 - 2, n1) * n0) * EB;
+  const unsigned orowm1 = (unsigned)((wrapi(jb0 - 1, n1) + 1) * N0) * EB;
   const unsigned ucol = (unsigned)pcol_of(ci) * EB;            // main lanes: own column
   const unsigned qcol = CORR ? (unsigned)(pcol_of(ci) - 1) * EB : 0u;
   unsigned uhoff, qhoff = 0;  // packed halo loads: in-plane byte offset of this lane's (row, column)
@@ -114,7 +131,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
   }
 
   auto uplane = [&](int kk) {  // padded plane index -> plane actually read
-    return CORR == 1 ? wrapi(kk - 1, n2) + 1 : (CORR == 2 ? min(kk, N2 - 1) : kk);
+    return CORR == 1 ? wrapi(kk - 1, n2) + 1 : (CORR == 2 ? min(kk, N2 - 1) : ((RHS && kk < 0) ? kk + n2 : kk));
   };
   auto load_plane = [&](Plane<T, R>& P, int kk) {
     const T* base = a_u + (long long)uplane(kk) * sz;
@@ -124,6 +141,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
 #pragma unroll
       for (int rr = 0; rr < R + 2; ++rr) P.v[c][rr] = ldb<T>(rs, ucol, urow[rr]);
       P.h[c] = ldb<T>(rs, uhoff, 0);
+      if (RHS && c == 1) P.vm2 = ldb<T>(rs, ucol, urowm2);
     }
   };
   const unsigned urowm1 = (unsigned)(prow_of(jb0 - 2) * N0) * EB;
@@ -135,20 +153,24 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
     E.th = ldb<T>(rt, uhoff, 0);
     E.vm1 = ldb<T>(plane_rsrc(a_u + po + a.sc, ubytes), ucol, urowm1);
   };
-  auto load_p = [&](T (&P)[R + 3], T& PH, int kk) {
+  constexpr int NPR = R + 3 + (RHS ? 1 : 0);  // pressure rows jb0-1 .. jb0+R+1; RHS: row jb0-2 behind them
+  auto load_p = [&](T (&P)[NPR], T& PH, int kk) {
     const rsrc_t rs = plane_rsrc(a_pI + (long long)(CORR == 2 ? min(kk, N2) : wrapi(kk - 1, n2)) * n0 * n1, qbytes);
 #pragma unroll
     for (int rr = 0; rr < R + 3; ++rr) P[rr] = ldb<T>(rs, qcol, qrow[rr]);
     PH = ldb<T>(rs, qhoff, 0);
+    if constexpr (RHS) P[R + 3] = ldb<T>(rs, qcol, qrowm2);
   };
   // u = u* - ∇p (applypressure!, operators.jl:225-233) for one register plane and its packed halo columns
-  auto correct = [&](Plane<T, R>& P, const T (&Pc)[R + 3], T PHc, const T (&Pn)[R + 3], T PHn) {
+  auto correct = [&](Plane<T, R>& P, const T (&Pc)[NPR], T PHc, const T (&Pn)[NPR], T PHn) {
     if (a.epi.self_in != 0.0) {
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int rr = 0; rr < R; ++rr) P.raw[c][rr] = P.v[c][rr + 1];
+      if constexpr (RHS) P.rawv0 = P.v[1][0];
     }
+    if constexpr (RHS) P.vm2 -= (Pc[0] - Pc[R + 3]) * Y.gs;
 #pragma unroll
     for (int rr = 0; rr < R + 2; ++rr) {
       const T pc = Pc[rr];
@@ -162,7 +184,10 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
   };
 
   T zprev[3][R];
+  T zprevV0 = 0;    // RHS: the same for the y-component at row jb0-1
+  T wsprev[R] = {};  // RHS: w* of plane k-1 at the output rows
   auto zflux0 = [&](const Plane<T, R>& C, const Plane<T, R>& Nx) {  // upper-face z-fluxes of the plane below the chunk
+    if constexpr (RHS) zprevV0 = flux(C.v[1][0], Nx.v[1][0], C.v[2][0], C.v[2][1], Z.vo);
 #pragma unroll
     for (int rr = 1; rr <= R; ++rr) {
       const T Wc = C.v[2][rr];
@@ -184,8 +209,9 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
   T gacc[EXTRA ? R : 1];  // gravity!: α2 avg(temp) at the gdir-face (operators.jl:914-931; uniform grid: the plain mean)
   T Pz[3][EXTRA ? R : 1];  // the output rows of plane k-1 (for the Laplacian behind epi.wout)
   const T nux = X.vs * X.rs, nuy = Y.vs * Y.rs, nuz = Z.vs * Z.rs;  // ν/Δ² per direction (4ν/Δ · ¼/Δ: exact scalings)
+  T sV0 = 0;  // RHS: the y-component of s at row jb0-1
   auto epi_load = [&](const Plane<T, R>& C, int k, T (&sacc)[3][R]) {
-    const long long pk = (long long)k * sz;
+    const long long pk = (long long)((RHS && k < 1) ? k + n2 : k) * sz;  // (RHS: the plane below the first chunk through its periodic image)
     if constexpr (EXTRA) {
       if (a.epi.extra) {
         const T* b = static_cast<const T*>((const void*)a.epi.extra) + pk;
@@ -219,18 +245,21 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
         const rsrc_t rs = plane_rsrc(b + c * a.sc, ubytes);
 #pragma unroll
         for (int rr = 0; rr < R; ++rr) sacc[c][rr] = c0 * (ntl ? ldb_aux<2>(rs, ocol, orow[rr], (T)0) : ldb<T>(rs, ocol, orow[rr]));
+        if (RHS && c == 1) sV0 = c0 * ldb<T>(rs, ocol, orowm1);
       }
     } else {
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int rr = 0; rr < R; ++rr) sacc[c][rr] = C.v[c][rr + 1];
+      if constexpr (RHS) sV0 = C.v[1][0];
     }
     if (a.epi.self_in != 0.0) {  // the stencil input is itself a term: no second trip to memory for it
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int rr = 0; rr < R; ++rr) sacc[c][rr] += (T)a.epi.self_in * (CORR ? C.raw[c][rr] : C.v[c][rr + 1]);
+      if constexpr (RHS) sV0 += (T)a.epi.self_in * (CORR ? C.rawv0 : C.v[1][0]);
     }
     for (int q = 0; q < a.epi.n; ++q) {
       const T* kq = static_cast<const T*>((const void*)a.epi.k[q]) + pk;
@@ -243,6 +272,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
         for (int rr = 0; rr < R; ++rr) kv[rr] = ntl ? ldb_aux<2>(rs, ocol, orow[rr], (T)0) : ldb<T>(rs, ocol, orow[rr]);
 #pragma unroll
         for (int rr = 0; rr < R; ++rr) sacc[c][rr] += cq * kv[rr];
+        if (RHS && c == 1) sV0 += cq * ldb<T>(rs, ocol, orowm1);
       }
     }
   };
@@ -269,7 +299,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
       stb_aux<19>(r2, co, rowb, v2);
     }
   };
-  auto emit = [&](int rr, int k, T fu, T fv, T fw, T s0, T s1, T s2) {
+  auto emit = [&](int rr, int k, T fu, T fv, T fw, T s0, T s1, T s2, bool st) {
     const long long pk = (long long)k * sz;
     if constexpr (EXTRA) {
       fu += eacc[0][rr - 1];
@@ -283,7 +313,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
       }
     }
     const int j = jb0 + rr - 1;  // interior row
-    if (xout && j < n1) {
+    if (xout && j < n1 && st) {
       const unsigned rowb = orow[rr - 1], co = ocol;
       if (FUSE) {
         if (CORR && a.epi.ustart_out) {  // chained steps: s is the corrected stencil input = this step's ustart (no term was added to it)
@@ -308,7 +338,9 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
   T wwprev[TMK ? R : 1];  // w·diffusion(w) of plane k-1 at the output rows (zero below the first plane: operators.jl:793-807 reads a ghost of `diff`)
   T PzV0 = 0;               // v at the halo row of plane k-1
   T hU_prev = 0;            // packed halo columns of u, plane k-1
-  auto body = [&](Plane<T, R>& C, const Plane<T, R>& Nx, TExt<T, R>& CT, const TExt<T, R>& NT, int k, int kload) {
+  // st: store this plane's results (RHS: false for the plane below the chunk, which only sets up the carried w*)
+  auto body = [&](Plane<T, R>& C, const Plane<T, R>& Nx, TExt<T, R>& CT, const TExt<T, R>& NT, int k, int kload, bool st_) {
+    const bool st = RHS ? st_ : true;
     const T* nb = a_u + (long long)uplane(kload) * sz;
     const rsrc_t n0r = plane_rsrc(nb, ubytes), n1r = plane_rsrc(nb + a.sc, ubytes), n2r = plane_rsrc(nb + 2 * a.sc, ubytes);
     const T ch0 = C.h[0], ch1 = C.h[1], ch2 = C.h[2];
@@ -334,6 +366,10 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
     T fyu_o = 0, fyv_o = 0, fyw_o = 0;
     T Uo = 0, Vo = 0, Wo = 0;  // row rr - 1 of this plane (EXTRA: its registers already hold the next plane)
     T To = 0, wv_o = 0;        // T and v·diffusion(v) of row rr - 1
+    T us_u[RHS ? R : 1], dvs[RHS ? R : 1], dws[RHS ? R : 1];  // RHS: u* and the y / z differences of v* / w* at the output rows
+    T vs_o = 0;                                               // RHS: v* of row rr - 1
+    T cvm2 = 0;
+    if constexpr (RHS) cvm2 = C.vm2;
 #pragma unroll
     for (int rr = 0; rr <= R; ++rr) {
       const T Uc = C.v[0][rr], Vc = C.v[1][rr], Wc = C.v[2][rr];
@@ -342,7 +378,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
           const T fu = Uc + fyu_o + C.v[0][rr + 1] + Nx.v[0][rr] + zprev[0][rr - 1] + ch0;
           const T fv = Vc + fyv_o + C.v[1][rr + 1] + Nx.v[1][rr] + zprev[1][rr - 1] + ch1;
           const T fw = Wc + fyw_o + C.v[2][rr + 1] + Nx.v[2][rr] + zprev[2][rr - 1] + ch2;
-          emit(rr, k, fu, fv, fw, FUSE ? sacc[0][rr - 1] : (T)0, FUSE ? sacc[1][rr - 1] : (T)0, FUSE ? sacc[2][rr - 1] : (T)0);
+          emit(rr, k, fu, fv, fw, FUSE ? sacc[0][rr - 1] : (T)0, FUSE ? sacc[1][rr - 1] : (T)0, FUSE ? sacc[2][rr - 1] : (T)0, st);
         }
         fyu_o = Uc;
         fyv_o = Vc;
@@ -433,7 +469,29 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
           Pz[1][rr - 1] = Vc;
           Pz[2][rr - 1] = Wc;
         }
-        emit(rr, k, fu, fv, fw, FUSE ? sacc[0][rr - 1] : (T)0, FUSE ? sacc[1][rr - 1] : (T)0, FUSE ? sacc[2][rr - 1] : (T)0);
+        emit(rr, k, fu, fv, fw, FUSE ? sacc[0][rr - 1] : (T)0, FUSE ? sacc[1][rr - 1] : (T)0, FUSE ? sacc[2][rr - 1] : (T)0, st);
+        if constexpr (RHS) {  // the stored values (the expressions of emit)
+          const T su = sacc[0][rr - 1] + (T)a.epi.coef_self * fu, sv = sacc[1][rr - 1] + (T)a.epi.coef_self * fv, sw = sacc[2][rr - 1] + (T)a.epi.coef_self * fw;
+          us_u[rr - 1] = su;
+          dvs[rr - 1] = sv - vs_o;
+          dws[rr - 1] = sw - wsprev[rr - 1];
+          vs_o = sv;
+          wsprev[rr - 1] = sw;
+          if (lane == 63) rhs_lds[((k & 1) * NW + wave) * R + rr - 1] = su;
+        }
+      } else if constexpr (RHS) {
+        // v* at row jb0-1: the y-component of the rr >= 1 branch, term by term.  (A lambda shared by both rows was tried: it moved the register allocation of every
+        // existing instantiation, +4 VGPRs and one wave per SIMD less in the non-correcting 2-row kernels; the rhs test of tests/test_gpu_stage_rhs.py, which
+        // observes a bitwise-equal result today, pins the two copies together.)
+        const T fyv_m = flux(cvm2, Vc, cvm2, Vc, Y.vs);
+        const T fxv = flux(Vc, Vn, Uc, C.v[0][rr + 1], X.vo);
+        const T lxv = flux(rdlane(ch1, rr), Vc, rdlane(ch0, rr), rdlane(ch0, rr + 1), X.vo);
+        T fv = (fxv - prev_h(fxv, lxv)) * X.ro;
+        fv += (fyv - fyv_m) * Y.rs;
+        const T zv = flux(Vc, Nx.v[1][rr], Wc, C.v[2][rr + 1], Z.vo);
+        fv += (zv - zprevV0) * Z.ro;
+        zprevV0 = zv;
+        vs_o = sV0 + (T)a.epi.coef_self * fv;
       }
       fyu_o = fyu;
       fyv_o = fyv;
@@ -465,6 +523,27 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
     C.h[0] = ldb<T>(n0r, uhoff, 0);
     C.h[1] = ldb<T>(n1r, uhoff, 0);
     C.h[2] = ldb<T>(n2r, uhoff, 0);
+    if constexpr (RHS) {
+      C.vm2 = ldb<T>(n1r, ucol, urowm2);
+      // every wavefront's lane-63 u* of this plane is in LDS behind the barrier; the slot is written again two planes on, behind the next barrier, when every
+      // wavefront has read it.  Fences on LDS only: a fence on global memory would wait for the prefetch of plane k+2.
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+      const int lw = wy * XW + (wx + XW - 1) % XW;
+      T* ro = static_cast<T*>((void*)a.epi.rhs_out) + (long long)(k - 1) * n0 * n1;
+      const rsrc_t rr_ = plane_rsrc(ro, qbytes);
+      const T om = (T)a.om;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const T ul = rhs_lds[((k & 1) * NW + lw) * R + r];
+        T d = 0;  // Ω·div(u*): the expression of k_xfwd<XSRC_DIV> (ins_fft.hip)
+        d += (us_u[r] - prev_h(us_u[r], ul)) * (T)a.rdiv[0];
+        d += dvs[r] * (T)a.rdiv[1];
+        d += dws[r] * (T)a.rdiv[2];
+        if (st && xout && jb0 + r < n1) stb(rr_, (unsigned)min(ci, n0 - 1) * EB, (unsigned)(min(jb0 + r, n1 - 1) * n0) * EB, d * om);
+      }
+    }
     if constexpr (TMK) {
       if (tm) {
         hU_prev = ch0;
@@ -479,8 +558,8 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
   Plane<T, R> P0, P1;
   TExt<T, R> TE0, TE1;
   if (!CORR) {
-    load_plane(P0, k0 - 1);
-    load_plane(P1, k0);
+    load_plane(P0, kw0 - 1);
+    load_plane(P1, kw0);
     zflux0(P0, P1);
     if constexpr (EXTRA) {
 #pragma unroll
@@ -503,28 +582,28 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
         }
       }
     }
-    load_plane(P0, min(k0 + 1, k1));
+    load_plane(P0, min(kw0 + 1, k1));
     if constexpr (EXTRA) {
       if (a.tm) load_text(TE0, min(k0 + 1, k1));
     }
-    int k = k0;
+    int k = kw0;
     while (true) {
-      if (a.bar) __builtin_amdgcn_s_barrier();
-      body(P1, P0, TE1, TE0, k, min(k + 2, k1));
+      if (!RHS && a.bar) __builtin_amdgcn_s_barrier();
+      body(P1, P0, TE1, TE0, k, min(k + 2, k1), k >= k0);
       if (++k >= k1) break;
-      if (a.bar) __builtin_amdgcn_s_barrier();
-      body(P0, P1, TE0, TE1, k, min(k + 2, k1));
+      if (!RHS && a.bar) __builtin_amdgcn_s_barrier();
+      body(P0, P1, TE0, TE1, k, min(k + 2, k1), k >= k0);
       if (++k >= k1) break;
     }
   } else {
     // invariant at the top of iteration k: cur = corrected plane k, nxt = RAW plane k+1, Pa = p(k+1), Pb = p(k+2)
-    T Pa[R + 3], Pb[R + 3], Ha, Hb;
-    load_p(Pa, Ha, k0 - 1);
-    load_p(Pb, Hb, k0);
-    load_plane(P0, k0 - 1);
-    load_plane(P1, k0);
+    T Pa[NPR], Pb[NPR], Ha, Hb;
+    load_p(Pa, Ha, kw0 - 1);
+    load_p(Pb, Hb, kw0);
+    load_plane(P0, kw0 - 1);
+    load_plane(P1, kw0);
     correct(P0, Pa, Ha, Pb, Hb);
-    load_p(Pa, Ha, k0 + 1);
+    load_p(Pa, Ha, kw0 + 1);
     correct(P1, Pb, Hb, Pa, Ha);
     zflux0(P0, P1);
     if constexpr (EXTRA) {
@@ -533,19 +612,19 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
 #pragma unroll
         for (int rr = 0; rr < R; ++rr) Pz[c][rr] = P0.v[c][rr + 1];
     }
-    load_plane(P0, min(k0 + 1, k1));
-    load_p(Pb, Hb, min(k0 + 2, k1 + 1));
-    int k = k0;
+    load_plane(P0, min(kw0 + 1, k1));
+    load_p(Pb, Hb, min(kw0 + 2, k1 + 1));
+    int k = kw0;
     while (true) {
-      if (a.bar) __builtin_amdgcn_s_barrier();
+      if (!RHS && a.bar) __builtin_amdgcn_s_barrier();
       correct(P0, Pa, Ha, Pb, Hb);  // plane k+1 with p(k+1), p(k+2)
       load_p(Pa, Ha, min(k + 3, k1 + 1));
-      body(P1, P0, TE1, TE0, k, min(k + 2, k1));
+      body(P1, P0, TE1, TE0, k, min(k + 2, k1), k >= k0);
       if (++k >= k1) break;
-      if (a.bar) __builtin_amdgcn_s_barrier();
+      if (!RHS && a.bar) __builtin_amdgcn_s_barrier();
       correct(P1, Pb, Hb, Pa, Ha);
       load_p(Pb, Hb, min(k + 3, k1 + 1));
-      body(P0, P1, TE0, TE1, k, min(k + 2, k1));
+      body(P0, P1, TE0, TE1, k, min(k + 2, k1), k >= k0);
       if (++k >= k1) break;
     }
   }
@@ -634,6 +713,22 @@ int launch(const ins_grid* G, FluxArgs& a, int corr_mode, int part, hipStream_t 
   return launch_range<T, R, XW, FUSE, NW>(G, a, corr_mode, s);
 }
 
+// the instantiations that also write Ω·div(u*) (a.epi.rhs_out): fp64, whole rows per workgroup, every plane in one launch
+template <int R, int XW, int NW, int CORR>
+int launch_rhs(const ins_grid* G, FluxArgs& a, hipStream_t s) {
+  const GridDev& g = G->g;
+  a.ntx = 1;
+  a.nty = cdiv(g.N[1] - 2, (NW / XW) * R);
+  a.k_lo = 1;
+  a.k_hi = g.N[2] - 1;
+  a.kB = 0;
+  a.ntz = cdiv(a.k_hi - a.k_lo, a.zc);
+  const unsigned nb = (unsigned)(8LL * ((a.nty + 7) / 8) * a.ntz);
+  hipLaunchKernelGGL((k_flux64<double, R, XW, true, CORR, false, NW, false, true>), dim3(nb), dim3(64, NW, 1), 0, s, a);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+
 }  // namespace
 
 // Tuning knobs for experiments in one process on one allocation (not part of the public ABI); -1 keeps a value.
@@ -655,39 +750,27 @@ bool ins_flux64_supported(const ins_grid* G) {
   return !g_disable && g.D == 3 && G->all_dof && G->uniform_exact && g.N[0] - 2 >= 66 && g.N[1] - 2 >= 8 && g.N[2] - 2 >= 4;
 }
 
-// corr_mode 0: u has valid ghost volumes.  1 / 2: see k_flux64.  fuse: RK epilogue `epi`.
-template <typename T>
-static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, const RkEpi* epi, const T* pI, int corr_mode, hipStream_t s, int part) {
+// Workgroup shape of a launch: xw wavefronts side by side, nw per workgroup, `rows` output rows per lane, z-chunks of zc planes.  A function of the box and of
+// the tile-shape options; ext: the extended stage loop's instantiation; rhs: the caller wants the Poisson right-hand side from the kernel.
+struct TileShape {
+  int xw, rows, nw, zc;
+};
+static TileShape tile_shape(const ins_grid* G, int corr_mode, bool f32, bool ext, bool rhs) {
   const GridDev& g = G->g;
-  FluxArgs a;
-  memset(&a, 0, sizeof(a));
-  a.u = u;
-  a.pI = pI;
-  a.F = F;
-  a.sc = g.sc;
-  a.N0 = g.N[0];
-  a.N1 = g.N[1];
-  a.N2 = g.N[2];
   const int n2 = g.N[2] - 2;
-  a.X = make_dir(G, 0, visc);
-  a.Y = make_dir(G, 1, visc);
-  a.Z = make_dir(G, 2, visc);
-  if (epi) a.epi = *epi;
-  if (epi && epi->tstage) {
-    a.te = *epi->tstage;
-    a.tm = 1;
-    a.epi.tstage = nullptr;
-  }
   const int waves_x = cdiv(g.N[0] - 2, 64);
   // wavefronts side by side: 4 for 256-wide rows (2.85 vs 2.90 ms/step with 2), 2 for 512-wide ones (23.7 vs 24.3 ms/step)
   const int xwo = (corr_mode && ins_opt(OPT_INS_FLUX64_XW_CORR)) ? (int)ins_opt(OPT_INS_FLUX64_XW_CORR) : g_xw;
   int xw = xwo ? xwo : (waves_x >= 8 ? 2 : (waves_x >= 4 ? 4 : (waves_x >= 2 ? 2 : 1)));
   if (!xwo)  // rows of 3 or 6 wavefronts (192, 384 columns): side-by-side counts that leave no wavefront outside the box
     while (xw > 1 && cdiv(waves_x, xw) * xw > waves_x) xw >>= 1;
+  // a stage kernel that writes the Poisson right-hand side needs workgroups that span whole rows: 192 columns as three wavefronts side by side, two such rows
+  const bool three = rhs && corr_mode == 1 && !xwo && waves_x == 3 && !ins_opt(OPT_INS_FLUX64_NW);
+  if (three) xw = 3;
   int rows = corr_mode ? (g_rows_corr ? g_rows_corr : 2) : (g_rows ? g_rows : 4);
   rows = std::min(std::max(rows, 2), corr_mode ? 5 : 6);
-  constexpr bool F32 = sizeof(T) == 4;  // the fp32 family is built for the default shapes only (2 rows correcting, 4 otherwise)
-  if (F32) rows = corr_mode ? (ins_opt(OPT_INS_F32_CORR_ROWS) == 4 ? 4 : 2) : 4;
+  // the fp32 family is built for the default shapes only (2 rows correcting, 4 otherwise)
+  if (f32) rows = corr_mode ? (ins_opt(OPT_INS_F32_CORR_ROWS) == 4 ? 4 : 2) : 4;
   // Workgroup shape and z-chunk.  The wavefronts of a workgroup share halo rows / columns; a workgroup barrier per plane keeps them on
   // the same plane, so those shared lines are cache hits instead of HBM re-reads (512^3 plain K1, same box: 1.45 -> 1.37 ms with 4
   // wavefronts, 1.28 ms with 8 wavefronts = 128 x 16 cells per plane and workgroup: the flat-copy rate of that box, profiles/r02_k1_lab.txt;
@@ -701,7 +784,7 @@ static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, con
     return (long long)cdiv(g.N[0] - 2, 64 * xw) * cdiv(g.N[1] - 2, (nw_ / xw) * rows) * cdiv(n2, zc_);
   };
   const long long mintiles = ins_opt(OPT_INS_FLUX64_MINTILES) > 0 ? ins_opt(OPT_INS_FLUX64_MINTILES) : 256;  // one workgroup per CU
-  int nw = nwo == 16 ? 16 : (nwo == 8 ? 8 : (nwo == 4 ? 4 : 0));
+  int nw = three ? 6 : (nwo == 16 ? 16 : (nwo == 8 ? 8 : (nwo == 4 ? 4 : 0)));
   int zc = zco;
   if (!nw) {
     nw = 4;
@@ -725,11 +808,53 @@ static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, con
       while (zc > 4 && tiles(nw, zc) < 2 * mintiles) zc >>= 1;
   }
   if (rows != 2 && nw == 16) nw = 8;
-  if (epi && (epi->extra || epi->gtemp || epi->wout || epi->tstage)) {  // one instantiation serves the extended stage loop
+  if (ext) {  // one instantiation serves the extended stage loop
     rows = 2;
     nw = 4;
     if (!zco) zc = n2 >= 128 ? 32 : (n2 >= 64 ? 16 : (n2 >= 32 ? 8 : 4));
   }
+  return TileShape{xw, rows, nw, zc};
+}
+
+bool ins_flux128_supported(const ins_grid* G, const RkEpi* epi, int corr_mode, bool f32);
+// The one place that decides whether a stage kernel launch (fp64, fused epilogue, no extra terms, every plane) writes the Poisson right-hand side: the launch is
+// this file's kernel, its workgroups span whole rows (so u*(i-1) never belongs to another workgroup) and the tile shape is one the route is built for.
+bool ins_flux64_stage_rhs_supported(const ins_grid* G, int corr_mode) {
+  if (ins_opt(OPT_INS_DISABLE_STAGE_RHS) || corr_mode < 0 || corr_mode > 1 || !ins_flux64_supported(G) || g_skel || g_lds) return false;
+  if (ins_flux128_supported(G, nullptr, corr_mode, false)) return false;
+  const TileShape t = tile_shape(G, corr_mode, false, false, true);
+  if (64 * t.xw != G->g.N[0] - 2) return false;
+  if (corr_mode == 0) return t.rows == 4 && t.xw == 2 && t.nw == 4;
+  return t.rows == 2 && ((t.xw == 3 && t.nw == 6) || ((t.xw == 2 || t.xw == 4) && (t.nw == 4 || t.nw == 8)));
+}
+
+// corr_mode 0: u has valid ghost volumes.  1 / 2: see k_flux64.  fuse: RK epilogue `epi`.
+template <typename T>
+static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, const RkEpi* epi, const T* pI, int corr_mode, hipStream_t s, int part) {
+  const GridDev& g = G->g;
+  FluxArgs a;
+  memset(&a, 0, sizeof(a));
+  a.u = u;
+  a.pI = pI;
+  a.F = F;
+  a.sc = g.sc;
+  a.N0 = g.N[0];
+  a.N1 = g.N[1];
+  a.N2 = g.N[2];
+  a.X = make_dir(G, 0, visc);
+  a.Y = make_dir(G, 1, visc);
+  a.Z = make_dir(G, 2, visc);
+  if (epi) a.epi = *epi;
+  if (epi && epi->tstage) {
+    a.te = *epi->tstage;
+    a.tm = 1;
+    a.epi.tstage = nullptr;
+  }
+  const bool ext = epi && (epi->extra || epi->gtemp || epi->wout || epi->tstage);
+  const bool want_rhs = epi && epi->rhs_out;
+  const TileShape ts = tile_shape(G, corr_mode, sizeof(T) == 4, ext, want_rhs);
+  const int xw = ts.xw, rows = ts.rows, nw = ts.nw, zc = ts.zc;
+  constexpr bool F32 = sizeof(T) == 4;
   a.zc = zc;
   a.bar = ins_opt(OPT_INS_FLUX64_NOBAR) ? 0 : 1;
   // cache-policy bits of the stage kernel's once-only streams: bit 0 = nt on the result stores, bit 3 = nt on the loads of the epilogue terms (ustart, stage terms).
@@ -758,6 +883,26 @@ static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, con
       if (xw == 2) return launch<T, RR, 2, FUSE>(G, a, corr_mode, part, s);           \
       return launch<T, RR, 1, FUSE>(G, a, corr_mode, part, s);                        \
     }                                                                                 \
+  }
+  if (want_rhs) {
+    if (ins_stage_out_aliases_input(*epi, u)) {  // the right-hand side reads neighbouring cells of every input
+      ins_set_error("stage kernel asked for the Poisson right-hand side while u* overwrites one of its inputs");
+      return INS_ERR_INVALID;
+    }
+    if constexpr (!F32) {
+      if (part == 0 && ins_flux64_stage_rhs_supported(G, corr_mode)) {
+        a.rdiv[0] = 1.0 / G->desc.dx[0][1];
+        a.rdiv[1] = 1.0 / G->desc.dx[1][1];
+        a.rdiv[2] = 1.0 / G->desc.dx[2][1];
+        a.om = G->desc.dx[0][1] * G->desc.dx[1][1] * G->desc.dx[2][1];
+        if (corr_mode == 0) return launch_rhs<4, 2, 4, 0>(G, a, s);
+        if (xw == 3) return launch_rhs<2, 3, 6, 1>(G, a, s);
+        if (xw == 4) return nw == 8 ? launch_rhs<2, 4, 8, 1>(G, a, s) : launch_rhs<2, 4, 4, 1>(G, a, s);
+        return nw == 8 ? launch_rhs<2, 2, 8, 1>(G, a, s) : launch_rhs<2, 2, 4, 1>(G, a, s);
+      }
+    }
+    ins_set_error("stage kernel asked for the Poisson right-hand side on a box or tile shape it does not write it for");
+    return INS_ERR_UNSUPPORTED;
   }
   if (epi) {
     INS_F64_CASE(2, true)

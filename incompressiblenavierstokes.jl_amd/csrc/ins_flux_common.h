@@ -37,6 +37,7 @@ struct FluxArgs {  // field pointers are T* of the kernel instantiation (RkEpi's
   RkEpi epi;
   int tm;      // temperature stage inside the kernel (EXTRA instantiation, CORR = 0)
   TempEpi te;
+  double rdiv[3], om;  // epi.rhs_out: 1/Δ per direction and the cell volume Ω (the constants k_xfwd<XSRC_DIV> reads from the grid tables)
 };
 
 // 4 × face flux:  4ν(up - uc)/Δb - (uc + up)(ub0 + ub1)        [ν(up - uc)/Δb - ½(uc + up)·½(ub0 + ub1), times 4]

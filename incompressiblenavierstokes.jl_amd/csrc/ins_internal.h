@@ -113,6 +113,7 @@ void ins_set_error(const char* fmt, ...);
   X(INS_DISABLE_FDM_UNFOLD4)     \
   X(INS_DISABLE_FDM_FOLDFUSE)    \
   X(INS_DISABLE_INKERNEL_CORR)   \
+  X(INS_DISABLE_STAGE_RHS)       \
   X(INS_RK_KEEP_K)               \
   X(INS_DISABLE_EXT_FUSED)       \
   X(INS_EXT_TEMP_SPLIT)          \
@@ -237,6 +238,7 @@ struct ins_poisson {
   SpectralRoute route = ROUTE_ROCFFT;
   KyOrder ky_order = KY_NATURAL;
   double* pI = nullptr;            // real n^D
+  double* rhs = nullptr;           // real n^D, allocated on first use: Ω·div(u*) written by the stage kernel (ins_poisson_stage_rhs; pI is that kernel's pressure input)
   hipfftDoubleComplex* phat = nullptr;  // (n/2+1) n [n]
   double* ahat[3] = {nullptr, nullptr, nullptr};
   int np[3] = {1, 1, 1};
@@ -280,6 +282,7 @@ struct ins_rk {
   std::vector<double*> vb;        // all uncorrected stage velocities V_0..V_{s-2} (stage-velocity basis, ins_rk.hip)
   const double* force = nullptr;  // steady body force field (caller-owned), ins_rk_set_bodyforce
   ins_rk_ext* ext = nullptr;
+  long long stage_rhs_launches = 0;  // stage kernels enqueued that wrote the Poisson right-hand side themselves (ins_dbg_stage_rhs_used)
   bool profiling = false;
   std::vector<hipEvent_t> prof_events;  // (start, stop) pairs around momentum launches
   void* step_graph = nullptr;           // launch-bound boxes: one step of ins_rk_steps_f64 captured as a hipGraph (ins_rk.hip)
@@ -309,6 +312,7 @@ struct RkEpi {
   const double* ustart;     // nullptr: ustart is the stencil input itself (first stage)
   double* ustar;            // stage velocity out (interior volumes only)
   double* ustart_out;       // optional (first stage of a chained step, ustart == nullptr): the corrected stencil input is stored here
+  double* rhs_out;          // optional (ins_flux64_stage_rhs_supported): Ω·div(u*) of the stored stage velocity, unpadded n^3 (never the pressure input pI)
   const double* extra;      // optional vector field added to the stage force before it is used and stored (closure term: ins_rk_ext.hip)
   const double* gtemp;      // optional temperature field: gravity! is added to component gdir of the stage force (ga2 = α2)
   double ga2;
@@ -316,6 +320,14 @@ struct RkEpi {
   double* wout;             // optional: w_α = u_α · diffusion(u)_α of the stencil input is stored here (dissipation!, ins_rk_ext.hip)
   const struct TempEpi* tstage;  // optional (HOST pointer, read at launch): the temperature equation's stage inside the stage kernel
 };
+
+// The stage kernel stores u* over an array it also reads (its stencil input `in`, ustart or a stage term): safe cell by cell, but not for a kernel that reads
+// neighbouring cells of its epilogue inputs (epi.rhs_out), which another workgroup may already have overwritten.
+static inline bool ins_stage_out_aliases_input(const RkEpi& epi, const void* in) {
+  bool a = (const void*)epi.ustar == in || epi.ustar == epi.ustart;
+  for (int q = 0; q < epi.n; ++q) a = a || epi.ustar == epi.k[q];
+  return a;
+}
 
 // One stage of the temperature equation carried by the 64-wide stage kernel (ins_flux64.hip, EXTRA; step_explicit_runge_kutta.jl:23-27, 39-44):
 //   ktemp_i = convection_diffusion_temp(u, temp) + dissipation(u),   temp_out = tempstart + Σ_j coef_j k_j + c_self ktemp_i
@@ -360,7 +372,10 @@ bool ins_k_project_fdm_fused(const ins_poisson* ps);
 int ins_k_project_fdm_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, double* p, hipStream_t s);
 int ins_k_project_periodic_fused_2d(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s);
 bool ins_poisson_own2d(const ins_poisson* ps);
-int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s);
+// rhs != nullptr (own-FFT routes): the right-hand side Ω·div(u) is already in that buffer (the stage kernel wrote it) and the x pass reads it instead of u
+int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s, const double* rhs = nullptr);
+bool ins_flux64_stage_rhs_supported(const ins_grid* G, int corr_mode);  // the stage kernel of this box can write that right-hand side (ins_flux64.hip)
+double* ins_poisson_stage_rhs(ins_poisson* ps);                        // its buffer (nullptr: no own-FFT 3-D route, or out of memory)
 int ins_k_poisson_solve(ins_poisson* ps, double* p, hipStream_t s);
 // blocking reductions over an index box of a scalar field; op: 0 sum(a*b), 1 max|a|, 2 min(a)
 int ins_k_reduce(const ins_grid* grid, int op, const double* a, const double* b, const int lo[3], const int hi[3], double* out,

@@ -922,13 +922,16 @@ static SpectralRoute route_for_source(const ins_poisson* ps, int src) {
 
 // pI <- solution of L p = f through the solver's route.  u == nullptr: f is in pI.  Own routes only: f = Ω·div(u) is formed from u inside the first
 // pass, as source `src` (3-D: XSRC_DIV, XSRC_DIV_U32; 2-D: XSRC_DIV_2D).
-static int spectral_transform(ins_poisson* ps, hipStream_t s, const double* u = nullptr, int src = XSRC_DIV) {
+// rhs != nullptr (own 3-D routes): f is in that buffer instead of pI.
+static int spectral_transform(ins_poisson* ps, hipStream_t s, const double* u = nullptr, int src = XSRC_DIV, const double* rhs = nullptr) {
   const GridDev& g = ps->grid->g;
   const int n0 = ps->np[0], n1 = ps->np[1], n2 = ps->np[2], kxn = ps->kmax[0], kxs = ps->kxs;
   double* ph = reinterpret_cast<double*>(ps->phat);
-  const double* f = u ? u : ps->pI;
+  if (rhs) u = nullptr;
+  const double* f = u ? u : (rhs ? rhs : ps->pI);
   if (!u) src = XSRC_PI;
   const SpectralRoute route = route_for_source(ps, src);
+  INS_REQUIRE(!rhs || (own_route(route) && g.D == 3), "spectral solve: a right-hand side outside pI needs an own-FFT 3-D route");
   INS_REQUIRE(ins_spectral_ky_order(route) == ps->ky_order, "spectral solve: the route for this source leaves ky in another order than the solver's symbol");
   const double inv_n = 1.0 / ((double)n0 * n1 * n2);  // own routes (n2 == 1 in 2-D)
   auto zpass = [&]() { return ins_k_zsolve(ph, n2, (long long)kxs * n1, ps->ahat[0], kxn, ps->ahat[1], ps->ahat[2], ps->tw, inv_n, true, s, kxs); };
@@ -1211,6 +1214,7 @@ extern "C" int ins_poisson_destroy(ins_poisson_t* ps) {
   if (ps->tw_y) (void)hipFree(ps->tw_y);
   if (ps->yz_scratch) (void)hipFree(ps->yz_scratch);
   if (ps->pI) (void)hipFree(ps->pI);
+  if (ps->rhs) (void)hipFree(ps->rhs);
   if (ps->phat) (void)hipFree(ps->phat);
   for (int a = 0; a < 3; ++a)
     if (ps->ahat[a]) (void)hipFree(ps->ahat[a]);
@@ -1438,9 +1442,10 @@ int ins_k_project(const ins_grid* G, ins_poisson* ps, double* u, double* p, hipS
 
 // First half of the fused periodic projection only: pI <- solution of L p = Ω div(u) (u: interior volumes valid).
 // The gradient-subtract is left to the next stage's stencil kernel (k_momentum_flux<..., CORR>).
-int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s) {
+int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s, const double* rhs) {
   const GridDev& g = G->g;
-  if (own_route(ps->route)) return spectral_transform(ps, s, u);  // K2 lives inside the first pass
+  if (own_route(ps->route)) return spectral_transform(ps, s, u, XSRC_DIV, rhs);  // K2 lives inside the first pass, or the stage kernel has written it to rhs
+  INS_REQUIRE(!rhs, "a right-hand side written by the stage kernel needs an own-FFT route");
   dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), ps->np[2]);
   hipLaunchKernelGGL((k_div_to_pI<3, true>), grid, block, 0, s, g, u, ps->pI, ps->np[0], ps->np[1]);
   INS_LAUNCH_CHECK();
@@ -1450,11 +1455,11 @@ int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const 
 // project! for the fused periodic RK stage: u holds valid INTERIOR values only; on return its interior is
 // divergence-free and its ghost volumes are filled.  3-D, all-periodic, spectral solver.
 // uout != nullptr: u stays as it is (uncorrected) and the corrected field with its ghost volumes goes to uout.
-int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout) {
+int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout, const double* rhs) {
   const GridDev& g = G->g;
   dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), ps->np[2]);
   double* dst = uout ? uout : u;
-  int rc = ins_k_project_periodic_solve_only(G, ps, u, s);
+  int rc = ins_k_project_periodic_solve_only(G, ps, u, s, rhs);
   if (rc) return rc;
   if (keep_p)
     hipLaunchKernelGGL(k_grad_ghost3<true>, grid, block, 0, s, g, dst, p, ps->pI, ps->np[0], ps->np[1], ps->np[2], (const double*)u);
@@ -1487,6 +1492,14 @@ int ins_k_project_periodic_fused_2d(const ins_grid* G, ins_poisson* ps, double* 
 // The `_f32` family's pressure equation on boxes with own passes: right-hand side Ω·div(u) from the FLOAT field u32 (periodic images), the fp64
 // passes, solution in ps->pI (double, unpadded).  false: this solver has no own passes (the caller keeps hipFFT).
 bool ins_k_spectral_own3d(const ins_poisson* ps) { return ps->kind == POISSON_SPECTRAL && own_route(ps->route) && ps->grid->g.D == 3; }
+double* ins_poisson_stage_rhs(ins_poisson* ps) {
+  if (!ins_k_spectral_own3d(ps)) return nullptr;
+  if (!ps->rhs && hipMalloc(&ps->rhs, (size_t)ps->np[0] * ps->np[1] * ps->np[2] * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    ps->rhs = nullptr;
+  }
+  return ps->rhs;
+}
 int ins_k_spectral_solve_from_u32(ins_poisson* ps, const float* u32, hipStream_t s) {
   return spectral_transform(ps, s, reinterpret_cast<const double*>(u32), XSRC_DIV_U32);
 }

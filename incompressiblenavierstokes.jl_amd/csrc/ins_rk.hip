@@ -12,7 +12,8 @@ bool ins_fast3d_supported(const ins_grid* G);
 bool ins_flux64_supported(const ins_grid* G);
 
 int ins_k_momentum_rk_fused(const ins_grid* G, double visc, const double* u_in, double* k_out, const RkEpi& epi, hipStream_t s);
-int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout = nullptr);
+int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout = nullptr,
+                                 const double* rhs = nullptr);
 
 int ins_k_momentum(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s) {
   if (ins_fast3d_supported(G)) return ins_k_momentum_fast3d(G, visc, u, F, s);
@@ -157,6 +158,44 @@ extern "C" int ins_rk_pressure(const ins_rk_t* rk, double** p) {
   return INS_OK;
 }
 
+// How many stage kernels of this integrator have written the Poisson right-hand side themselves so far (a test asserts that the route ran).
+extern "C" int ins_dbg_stage_rhs_used(const ins_rk_t* rk, int64_t* launches) {
+  INS_REQUIRE(rk && launches, "null argument");
+  *launches = (int64_t)rk->stage_rhs_launches;
+  return INS_OK;
+}
+
+// Test hook: ONE stage kernel through the production dispatch, u* = (1 - self_in) ustart + self_in u_in + coef_k kterm + coef_self F(u_in), stored to ustar
+// (interior volumes), with Ω·div(u*) copied to rhs (unpadded n^3, device) where the stage kernel writes it; *used says whether it did.  pI == nullptr: u_in
+// has valid ghost volumes; else u_in is an uncorrected stage velocity and pI its unpadded pressure (the in-register correction).  ustart / kterm nullable.
+extern "C" int ins_dbg_stage_rhs(ins_rk_t* rk, double visc, const double* u_in, const double* pI, const double* ustart, const double* kterm, double coef_k,
+                                 double self_in, double coef_self, double* ustar, double* rhs, int32_t* used, void* stream) {
+  INS_REQUIRE(rk && u_in && ustar && rhs && used, "null argument");
+  const ins_grid* G = rk->grid;
+  hipStream_t s = as_stream(stream);
+  RkEpi epi;
+  memset(&epi, 0, sizeof(epi));
+  epi.ustart = ustart;
+  epi.ustar = ustar;
+  epi.coef_self = coef_self;
+  if (ustart) {
+    epi.self_in = self_in;
+    epi.c0m1 = -self_in;
+  }
+  if (kterm) {
+    epi.coef[0] = coef_k;
+    epi.k[0] = kterm;
+    epi.n = 1;
+  }
+  *used = 0;
+  INS_REQUIRE(!ins_stage_out_aliases_input(epi, u_in), "ustar must be an array of its own");
+  if (ins_flux64_stage_rhs_supported(G, pI ? 1 : 0) && (epi.rhs_out = ins_poisson_stage_rhs(rk->ps))) *used = 1;
+  int rc = pI ? ins_k_momentum_rk_fused_corr(G, visc, u_in, pI, rk->ku[0], epi, s) : ins_k_momentum_rk_fused(G, visc, u_in, rk->ku[0], epi, s);
+  if (rc) return rc;
+  if (*used) INS_HIP_TRY(hipMemcpyAsync(rhs, epi.rhs_out, (size_t)rk->ps->np[0] * rk->ps->np[1] * rk->ps->np[2] * sizeof(double), hipMemcpyDeviceToDevice, s));
+  return INS_OK;
+}
+
 extern "C" int ins_rk_set_bodyforce(ins_rk_t* rk, const double* force) {
   INS_REQUIRE(rk, "null argument");
   rk->force = force;
@@ -263,22 +302,29 @@ static int rk_step_fused_periodic(ins_rk* rk, double visc, double* u, double dt,
     epi.ustart = (i == 0) ? nullptr : (raw_in ? rk->ustart : u);  // raw_in: the corrected start field lives in the cache array
     epi.ustar = out;
     if (i == 0 && raw_in) epi.ustart_out = rk->ustart;
+    // Where the stage kernel spans whole rows it also writes Ω·div(u*), and the solver's x pass reads that one array instead of the three components
+    // of u* (INS_DISABLE_STAGE_RHS=1: the x pass forms it).  A buffer of its own: pI is the correcting kernel's pressure input.
+    // Not where u* overwrites one of the kernel's inputs (the last stage of an unchained step: ustart == out == the caller's u): that is safe cell by cell,
+    // but for the right-hand side a wavefront reads its neighbours' cells of the inputs (row jb0-1, plane k0-1), which another workgroup may have overwritten.
+    const bool corr = inkernel && (i > 0 || raw_in);
+    if (!ins_stage_out_aliases_input(epi, in) && ins_flux64_stage_rhs_supported(G, corr ? 1 : 0) && (epi.rhs_out = ins_poisson_stage_rhs(rk->ps)))
+      ++rk->stage_rhs_launches;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (rk->profiling) {
       INS_HIP_TRY(hipEventCreate(&e0));
       INS_HIP_TRY(hipEventCreate(&e1));
       INS_HIP_TRY(hipEventRecord(e0, s));
     }
-    rc = (inkernel && (i > 0 || raw_in)) ? ins_k_momentum_rk_fused_corr(G, visc, in, rk->ps->pI, rk->ku[i], epi, s)
-                             : ins_k_momentum_rk_fused(G, visc, in, rk->ku[i], epi, s);
+    rc = corr ? ins_k_momentum_rk_fused_corr(G, visc, in, rk->ps->pI, rk->ku[i], epi, s)
+              : ins_k_momentum_rk_fused(G, visc, in, rk->ku[i], epi, s);
     if (rc) return rc;
     if (rk->profiling) {
       INS_HIP_TRY(hipEventRecord(e1, s));
       rk->prof_events.push_back(e0);
       rk->prof_events.push_back(e1);
     }
-    rc = (inkernel && (i < ns - 1 || raw_out)) ? ins_k_project_periodic_solve_only(G, rk->ps, out, s)
-                                               : ins_k_project_periodic_fused(G, rk->ps, out, rk->p, i == ns - 1, s);
+    rc = (inkernel && (i < ns - 1 || raw_out)) ? ins_k_project_periodic_solve_only(G, rk->ps, out, s, epi.rhs_out)
+                                               : ins_k_project_periodic_fused(G, rk->ps, out, rk->p, i == ns - 1, s, nullptr, epi.rhs_out);
     if (rc) return rc;
     in = out;
   }
