@@ -579,6 +579,17 @@ int ins_apply_bc_p_pullback_f32(const ins_grid_t* grid, float* phibar, void* str
  * `pwork`: a float scalar field of scratch.  A wrapped spectral solver on an all-periodic box: INS_ERR_UNSUPPORTED. */
 int ins_project_pullback_f32(const ins_grid_t* grid, ins_poisson32_t* ps, float* phibar, float* pwork, void* stream);
 
+/* ---------------------------------------------------------------------------------- Float32 tensor-basis closure (csrc/ins_tensorclosure32.hip)
+ * The `_f32` twins of ins_tensorinvariants_f64, ins_tensorclosure_stress_f64, ins_tensorclosure_pullback_f64, ins_divoftensor_f64 and
+ * ins_divoftensor_adjoint_f64: the same argument lists, layouts, write sets, NULL rules and aliasing rules on float fields (the grid handle
+ * is the fp64 one; all arithmetic in float; pullbacks without atomic operations, bitwise reproducible).  Slab grids: INS_ERR_UNSUPPORTED. */
+int ins_tensorinvariants_f32(const ins_grid_t* grid, const float* u, float* V, void* stream);
+int ins_tensorclosure_stress_f32(const ins_grid_t* grid, const float* u, const float* a, float* tau, void* stream);
+int ins_tensorclosure_pullback_f32(const ins_grid_t* grid, const float* u, const float* a, const float* taubar, const float* Vbar, float* abar,
+                                   float* ubar, int accumulate, void* stream);
+int ins_divoftensor_f32(const ins_grid_t* grid, const float* sigma, float* s, void* stream);
+int ins_divoftensor_adjoint_f32(const ins_grid_t* grid, const float* sbar, float* sigmabar, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

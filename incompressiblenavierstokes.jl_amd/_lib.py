@@ -181,6 +181,11 @@ SIGNATURES = {
     "ins_apply_bc_u_pullback_f32": (C.c_int, [vp, vp, vp]),
     "ins_apply_bc_p_pullback_f32": (C.c_int, [vp, vp, vp]),
     "ins_project_pullback_f32": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ins_tensorinvariants_f32": (C.c_int, [vp, vp, vp, vp]),
+    "ins_tensorclosure_stress_f32": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ins_tensorclosure_pullback_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "ins_divoftensor_f32": (C.c_int, [vp, vp, vp, vp]),
+    "ins_divoftensor_adjoint_f32": (C.c_int, [vp, vp, vp, vp]),
     "ins_comm_unique_id": (C.c_int, [vp]),
     "ins_comm_create": (C.c_int, [C.c_int, C.c_int, vp, C.POINTER(vp)]),
     "ins_comm_create_local": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]),

@@ -7,9 +7,22 @@
     (u * u).sum().backward()                                                                              # u0.grad = ∂loss/∂u0
 
 A closure model given as a torch function `m(u, θ)` on float32 fields is added as F + m(u, θ); its parameters get gradients from torch.  What the `_f32`
-family does not run raises NotImplementedError: a temperature field, the library's fused Smagorinsky closure, callable boundary data, an unsteady
-body force, slab setups, and `psolver_wrap32` around `psolver_spectral` on an all-periodic box.
+family does not run raises NotImplementedError: a temperature field, the library's fused fp64 Smagorinsky closure `ins_amd.smagorinsky_closure`
+(its differentiable Float32 form is `ad32.smagorinsky_closure`, below), callable boundary data, an unsteady body force, slab setups, and `psolver_wrap32` around `psolver_spectral` on an all-periodic box.
+
+The tensor-basis closure runs in Float32 too (csrc/ins_tensorclosure32.hip), through module attributes with the semantics of their `ad` namesakes on
+float32 tensors (they are not in `__all__`):
+
+    apply_bc_p(p, t, setup), apply_bc_p_fields(σ, t, setup)      ghost fill of a scalar field / of every channel of an N + (n,) field
+    tensorinvariants(u, setup)                                    V, N + (nv,), written on Ip
+    tensorclosure_stress(u, a, setup)                             τ = Σ_i a_i B_i(u), a symmetric tensorfield32; backward gives ubar and abar
+    divoftensor(σ, setup), lastdimcontract(a, b)
+    smagorinsky_closure(setup)                                    m(u, θ) with a learnable constant: a_2 = 2 θ² d² sqrt(2 V_1)
+
+`neuralclosure.tensorclosure(..., dtype=torch.float32)` is built from them, and both are closure models for `ad32.timestep`.  A float64 tensor raises
+TypeError, a field of another shape ValueError, a slab setup NotImplementedError.
 """
+import numpy as np
 import torch
 
 from . import f32 as F32
@@ -20,16 +33,21 @@ from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
 __all__ = ["apply_bc_u", "momentum", "project", "timestep"]
 
 
-def _check_setup(setup, what):
+def _check_slab(setup, what):
     if any(isinstance(bc, HaloBC) for side in setup.boundary_conditions for bc in side):
         raise NotImplementedError(f"ad32.{what}: slab (halo) setups run in fp64 only")
+
+
+def _check_setup(setup, what):
+    _check_slab(setup, what)
     if setup.needs_bc_planes:
         raise NotImplementedError(f"ad32.{what}: the _f32 family takes constant boundary data (callable DirichletBC values: use ins_amd.ad)")
     if setup.bodyforce is not None and not setup.issteadybodyforce:
         raise NotImplementedError(f"ad32.{what}: an unsteady body force is evaluated in fp64 on the host (use ins_amd.ad)")
     m = setup.closure_model
     if m is not None and getattr(m, "_ins_closure", None) == "smagorinsky":
-        raise NotImplementedError(f"ad32.{what}: the fused Smagorinsky closure is fp64 and has no pullback; give the closure as a torch function m(u, θ)")
+        raise NotImplementedError(f"ad32.{what}: the fused Smagorinsky closure is fp64 and has no pullback; use ad32.smagorinsky_closure(setup), "
+                                  "or give the closure as a torch function m(u, θ)")
 
 
 def _check_psolver(setup, psolver, what):
@@ -136,6 +154,173 @@ def project(u, setup, psolver):
     _check_setup(setup, "project")
     _check_psolver(setup, psolver, "project")
     return _Project.apply(u, setup, psolver)
+
+
+# ------------------------------------------------------------------------------------ tensor-basis closure
+def _vec(setup, u):
+    """`u` as a float32 vector field in the library's layout; another dtype raises TypeError, another shape ValueError."""
+    shape = tuple(setup.grid.N) + (setup.grid.dimension,)
+    if u.dtype != torch.float32:
+        raise TypeError("ad32 takes float32 torch tensors")
+    if tuple(u.shape) != shape:
+        raise ValueError(f"expected a field of shape {shape}, got {tuple(u.shape)}")
+    return _field(setup, u, True)
+
+
+def _nfield(setup, x, ncomp):
+    """`x` as an N + (ncomp,) float32 field in the library's layout (a copy when it has another one)."""
+    shape = tuple(setup.grid.N) + (ncomp,)
+    if x.dtype != torch.float32:
+        raise TypeError("ad32 takes float32 torch tensors")
+    if tuple(x.shape) != shape:
+        raise ValueError(f"expected a field of shape {shape}, got {tuple(x.shape)}")
+    if x.device == setup.device and tuple(x.stride()) == _fortran_strides(shape):
+        return x.detach()
+    f = F32.nfield32(setup, ncomp)
+    f.copy_(x.detach())
+    return f
+
+
+def _saved_field(ctx, setup, u):
+    """The velocity a stencil reads, kept for backward: the input itself goes through save_for_backward (an in-place change before
+    backward() raises); a layout copy is private to the Function."""
+    uf = _vec(setup, u)
+    if uf is u:
+        ctx.save_for_backward(u)
+        ctx.ucopy = None
+    else:
+        ctx.save_for_backward()
+        ctx.ucopy = uf
+    return uf
+
+
+class _ApplyBCP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, setup):
+        ctx.setup = setup
+        return F32.apply_bc_p32_(_copy(setup, p, False), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return F32.apply_bc_p_pullback32_(_copy(s, g, False), s), None
+
+
+class _DivOfTensor(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, σ, setup):
+        ctx.setup = setup
+        return F32.divoftensor32_(F32.vectorfield32(setup), _nfield(setup, σ, F32._tb_sizes(setup)[2]), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return F32.divoftensor_adjoint32_(F32.tensorfield32(s), _field(s, g, True), s), None
+
+
+class _TensorInvariants(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup):
+        ctx.setup = setup
+        return F32.tensorinvariants32_(F32.nfield32(setup, F32._tb_sizes(setup)[1]), _saved_field(ctx, setup, u), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        u = ctx.saved_tensors[0] if ctx.ucopy is None else ctx.ucopy
+        Vbar = _nfield(s, g, F32._tb_sizes(s)[1])
+        return F32.tensorclosure_pullback32_(F32.vectorfield32(s), None, None, Vbar, u, None, s), None
+
+
+class _TensorClosureStress(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, a, setup):
+        ctx.setup = setup
+        uf = _vec(setup, u)
+        af = _nfield(setup, a, F32._tb_sizes(setup)[0])
+        # both inputs go through save_for_backward when they already are library fields: an in-place change before backward() raises
+        ctx.ucopy = None if uf is u else uf
+        ctx.acopy = None if af.data_ptr() == a.data_ptr() else af
+        ctx.save_for_backward(*([u] if ctx.ucopy is None else []), *([a] if ctx.acopy is None else []))
+        return F32.tensorclosure_stress32_(F32.tensorfield32(setup), uf, af, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        saved = list(ctx.saved_tensors)
+        u = saved.pop(0) if ctx.ucopy is None else ctx.ucopy
+        a = saved.pop(0).detach() if ctx.acopy is None else ctx.acopy
+        nb, _, ns = F32._tb_sizes(s)
+        abar = F32.nfield32(s, nb)
+        ubar = F32.tensorclosure_pullback32_(F32.vectorfield32(s), abar, _nfield(s, g, ns), None, u, a, s)
+        return ubar, abar, None
+
+
+def apply_bc_p(p, t, setup):
+    """boundary_conditions.jl:114-206 with T = Float32 (`t` does not enter); pullback: apply_bc_p_pullback32_."""
+    _check_slab(setup, "apply_bc_p")
+    if tuple(p.shape) != tuple(setup.grid.N):
+        raise ValueError(f"expected a field of shape {tuple(setup.grid.N)}, got {tuple(p.shape)}")
+    return _ApplyBCP.apply(p, setup)
+
+
+def apply_bc_p_fields(σ, t, setup):
+    """`apply_bc_p` on every channel of an N + (n,) field (the stress tensor's ghost fill, operators.jl:1296)."""
+    if σ.dim() != setup.grid.dimension + 1:
+        raise ValueError(f"expected a field of shape {tuple(setup.grid.N)} + (n,), got {tuple(σ.shape)}")
+    return torch.stack([apply_bc_p(σ[..., q], t, setup) for q in range(σ.shape[-1])], dim=-1)
+
+
+def tensorinvariants(u, setup):
+    """The invariants V of the tensor basis (N + (nv,), written on Ip) with T = Float32, without forming B."""
+    _check_slab(setup, "tensorinvariants")
+    return _TensorInvariants.apply(u, setup)
+
+
+def tensorclosure_stress(u, a, setup):
+    """τ = Σ_i a_i B_i(u) as a symmetric `tensorfield32` (written on Ip) in one kernel that keeps the basis in registers; the backward gives
+    ubar and abar_i = <τbar, B_i>.  `a` is N + (nb,)."""
+    _check_slab(setup, "tensorclosure_stress")
+    return _TensorClosureStress.apply(u, a, setup)
+
+
+def divoftensor(σ, setup):
+    """operators.jl:1155-1184 with T = Float32 (pullback: divoftensor_adjoint32_) on a symmetric `tensorfield32` N + (D(D+1)/2,)."""
+    _check_slab(setup, "divoftensor")
+    return _DivOfTensor.apply(σ, setup)
+
+
+def lastdimcontract(a, b):
+    """tensorbasis.jl:97-157: c[I] = Σ_i a[I, i] b[I, i, ...] — plain torch (its pullback is torch's)."""
+    return (a.reshape(a.shape + (1,) * (b.dim() - a.dim())) * b).sum(dim=a.dim() - 1)
+
+
+def smagorinsky_closure(setup):
+    """Differentiable Smagorinsky closure `m(u, θ)` with T = Float32 (operators.jl:1284-1300), θ a 0-dim tensor: the member
+    a_2 = 2 θ² d² sqrt(2 V_1), every other a_i = 0, of the tensor-basis family, as `ad.smagorinsky_closure`; gridsize² d² is held in float32."""
+    _check_slab(setup, "smagorinsky_closure")
+    g = setup.grid
+    D = g.dimension
+    nb = F32._tb_sizes(setup)[0]
+    ip = tuple(slice(lo, hi) for lo, hi in g.Ip)
+    pads = [q for α in reversed(range(D)) for q in (g.Ip[α][0], g.N[α] - g.Ip[α][1])]
+    d2 = torch.zeros(tuple(g.N), dtype=torch.float64, device=setup.device)
+    for α in range(D):
+        shape = [1] * D
+        shape[α] = g.N[α]
+        d2 = d2 + torch.as_tensor(np.asarray(g.Δ[α], dtype=np.float64) ** 2, device=setup.device).reshape(shape)
+    d2 = d2[ip].float()
+
+    def closure(u, θ):
+        θ = torch.as_tensor(θ, dtype=torch.float32, device=setup.device)
+        V = tensorinvariants(u, setup)
+        a2 = torch.nn.functional.pad(2 * θ * θ * d2 * torch.sqrt(2 * V[ip + (0,)]), pads)  # Ip only: sqrt has no derivative at the zeros outside
+        z = torch.zeros_like(a2)
+        a = torch.stack([z, a2] + [z] * (nb - 2), dim=-1)
+        τ = apply_bc_p_fields(tensorclosure_stress(u, a, setup), 0.0, setup)
+        return divoftensor(τ, setup)
+
+    return closure
 
 
 def timestep(method, stepper, Δt, θ=None):

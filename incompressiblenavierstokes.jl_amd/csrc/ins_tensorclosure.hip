@@ -9,299 +9,11 @@
 // work-item in a fixed order of additions, so results are bitwise reproducible run to run.  The ∇ubar scratch belongs to the grid
 // handle (grown on first use).
 //
-// Reverse rules (derived, not probed).  Every tensor is a sum of products of S and R, evaluated through the binary products
-//   SR = S·R, RS = R·S, SS = S·S, RR = R·R, P = SS·RR, Q = RR·SS, ...
-// and for Z = X·Y with cotangent Zbar:  Xbar += Zbar·Yᵀ,  Ybar += Xᵀ·Zbar  (the two-factor case of
-// X_j bar += (X_1 … X_{j-1})ᵀ Mbar (X_{j+1} … X_k)ᵀ, applied along the product tree);  tr(X·Y) with cotangent v: Xbar += v Yᵀ, Ybar += v Xᵀ.
-// S and R are treated as independent full matrices; then ∇ubar = sym(Sbar) + skew(Rbar).
-#include "ins_stencil.h"
+// The matrix helpers, strain_rotation, the basis tensors, the invariants and the reverse rules are in ins_tensorbasis.h, shared with the
+// Float32 kernels (ins_tensorclosure32.hip).
+#include "ins_tensorbasis.h"
 
 namespace {
-
-template <int D>
-struct Mat {
-  double m[D][D];
-};
-
-template <int D>
-__device__ __forceinline__ Mat<D> mzero() {
-  Mat<D> r;
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) r.m[a][b] = 0.0;
-  return r;
-}
-template <int D>
-__device__ __forceinline__ Mat<D> mm(const Mat<D>& x, const Mat<D>& y) {  // x·y, the summation order of mmul in ins_fields.hip
-  Mat<D> r;
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      double v = 0.0;
-#pragma unroll
-      for (int q = 0; q < D; ++q) v += x.m[a][q] * y.m[q][b];
-      r.m[a][b] = v;
-    }
-  return r;
-}
-template <int D>
-__device__ __forceinline__ Mat<D> lin(const Mat<D>& x, const Mat<D>& y, double sy) {  // x + sy·y
-  Mat<D> r;
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) r.m[a][b] = x.m[a][b] + sy * y.m[a][b];
-  return r;
-}
-template <int D>
-__device__ __forceinline__ void axpy(Mat<D>& z, double s, const Mat<D>& x) {  // z += s·x
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) z.m[a][b] += s * x.m[a][b];
-}
-template <int D>
-__device__ __forceinline__ void axpyT(Mat<D>& z, double s, const Mat<D>& x) {  // z += s·xᵀ
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) z.m[a][b] += s * x.m[b][a];
-}
-template <int D>
-__device__ __forceinline__ void adiag(Mat<D>& z, double s) {  // z += s·I
-#pragma unroll
-  for (int a = 0; a < D; ++a) z.m[a][a] += s;
-}
-template <int D>
-__device__ __forceinline__ void add_mmt(Mat<D>& z, double s, const Mat<D>& x, const Mat<D>& y) {  // z += s·x·yᵀ
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      double v = 0.0;
-#pragma unroll
-      for (int q = 0; q < D; ++q) v += x.m[a][q] * y.m[b][q];
-      z.m[a][b] += s * v;
-    }
-}
-template <int D>
-__device__ __forceinline__ void add_mtm(Mat<D>& z, double s, const Mat<D>& x, const Mat<D>& y) {  // z += s·xᵀ·y
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      double v = 0.0;
-#pragma unroll
-      for (int q = 0; q < D; ++q) v += x.m[q][a] * y.m[q][b];
-      z.m[a][b] += s * v;
-    }
-}
-template <int D>
-__device__ __forceinline__ double mtrace(const Mat<D>& x) {
-  double t = 0.0;
-#pragma unroll
-  for (int a = 0; a < D; ++a) t += x.m[a][a];
-  return t;
-}
-template <int D>
-__device__ __forceinline__ double mdot(const Mat<D>& x, const Mat<D>& y) {  // Σ x_ab y_ab
-  double t = 0.0;
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) t += x.m[a][b] * y.m[a][b];
-  return t;
-}
-
-template <int D>
-__host__ __device__ constexpr int sym_index(int a, int b) {  // [xx, yy, (zz), xy, (xz, yz)], as ins_smagtensor_f64
-  if (a == b) return a;
-  if (D == 2) return 2;
-  const int lo = a < b ? a : b, hi = a < b ? b : a;
-  return lo == 0 ? (hi == 1 ? 3 : 4) : 5;
-}
-
-// ∇(u, I, Δ, Δu) and its symmetric / skew parts at the pressure point I (operators.jl:1023-1033): the expressions of gradu in ins_fields.hip
-template <int D>
-__device__ __forceinline__ void strain_rotation(const GridDev& g, const double* __restrict__ u, long long c, const int (&I)[3], Mat<D>& S, Mat<D>& R) {
-  double G[D][D];
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    const double* ua = u + a * g.sc;
-    const long long sa = g.sx[a];
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      const long long sb = g.sx[b];
-      if (a == b) {
-        G[a][b] = (ua[c] - ua[c - sb]) * g.rdx[b][I[b]];
-      } else {
-        const double r1 = g.rdxu[b][I[b]], r0 = g.rdxu[b][I[b] - 1];
-        G[a][b] = ((ua[c + sb] - ua[c]) * r1 + (ua[c - sa + sb] - ua[c - sa]) * r1 + (ua[c] - ua[c - sb]) * r0 +
-                   (ua[c - sa] - ua[c - sa - sb]) * r0) /
-                  4;
-      }
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      S.m[a][b] = (G[a][b] + G[b][a]) / 2;
-      R.m[a][b] = (G[a][b] - G[b][a]) / 2;
-    }
-}
-
-// The basis tensors in the order of tensorbasis.jl:59-69, handed one at a time to f(i, B_i): they live in registers only.
-template <int D, class F>
-__device__ __forceinline__ void for_each_basis(const Mat<D>& S, const Mat<D>& R, F&& f) {
-  Mat<D> Id = mzero<D>();
-  adiag<D>(Id, 1.0);
-  f(0, Id);
-  f(1, S);
-  const Mat<D> SR = mm<D>(S, R), RS = mm<D>(R, S);
-  f(2, lin<D>(SR, RS, -1.0));
-  if constexpr (D == 3) {
-    const Mat<D> SS = mm<D>(S, S), RR = mm<D>(R, R);
-    f(3, SS);
-    f(4, RR);
-    f(5, lin<D>(mm<D>(SS, R), mm<D>(R, SS), -1.0));    // S S R - R S S
-    f(6, lin<D>(mm<D>(S, RR), mm<D>(RR, S), 1.0));     // S R R + R R S
-    f(7, lin<D>(mm<D>(RS, RR), mm<D>(RR, SR), -1.0));  // R S R R - R R S R
-    f(8, lin<D>(mm<D>(SR, SS), mm<D>(SS, RS), -1.0));  // S R S S - S S R S
-    const Mat<D> P = mm<D>(SS, RR), Q = mm<D>(RR, SS);
-    f(9, lin<D>(P, Q, 1.0));                           // S S R R + R R S S
-    f(10, lin<D>(mm<D>(R, P), mm<D>(Q, R), -1.0));     // R S S R R - R R S S R
-  }
-}
-
-// Invariants (tensorbasis.jl:49-50, 70-74), the expressions of k_tensorbasis
-template <int D>
-__device__ __forceinline__ void invariants(const Mat<D>& S, const Mat<D>& R, double (&V)[5]) {
-  if constexpr (D == 2) {
-    V[0] = mdot<D>(S, S);
-    V[1] = mdot<D>(R, R);
-  } else {
-    const Mat<D> SS = mm<D>(S, S), RR = mm<D>(R, R);
-    V[0] = mtrace<D>(SS);
-    V[1] = mtrace<D>(RR);
-    V[2] = mtrace<D>(mm<D>(SS, S));
-    V[3] = mtrace<D>(mm<D>(S, RR));
-    V[4] = mtrace<D>(mm<D>(SS, RR));
-  }
-}
-
-// Reverse pass at one pressure point: mbar(i) is the cotangent of B_i (i >= 1; B_0 = I is constant), vb that of V.
-template <int D, bool HASB, bool HASV, class MB>
-__device__ __forceinline__ void basis_reverse(const Mat<D>& S, const Mat<D>& R, MB&& mbar, const double (&vb)[5], Mat<D>& bS, Mat<D>& bR) {
-  bS = mzero<D>();
-  bR = mzero<D>();
-  Mat<D> bSR = mzero<D>(), bRS = mzero<D>();
-  if (HASB) {
-    axpy<D>(bS, 1.0, mbar(1));  // B1 = S
-    const Mat<D> M2 = mbar(2);  // B2 = SR - RS
-    axpy<D>(bSR, 1.0, M2);
-    axpy<D>(bRS, -1.0, M2);
-  }
-  if constexpr (D == 2) {
-    if (HASV) {  // V0 = Σ S_ab², V1 = Σ R_ab²
-      axpy<D>(bS, 2.0 * vb[0], S);
-      axpy<D>(bR, 2.0 * vb[1], R);
-    }
-  } else {
-    const Mat<D> SS = mm<D>(S, S), RR = mm<D>(R, R);
-    Mat<D> bSS = mzero<D>(), bRR = mzero<D>();
-    if (HASB) {
-      const Mat<D> SR = mm<D>(S, R), RS = mm<D>(R, S);
-      axpy<D>(bSS, 1.0, mbar(3));  // B3 = SS
-      axpy<D>(bRR, 1.0, mbar(4));  // B4 = RR
-      {                            // B5 = SS·R - R·SS
-        const Mat<D> M = mbar(5);
-        add_mmt<D>(bSS, 1.0, M, R);
-        add_mtm<D>(bR, 1.0, SS, M);
-        add_mmt<D>(bR, -1.0, M, SS);
-        add_mtm<D>(bSS, -1.0, R, M);
-      }
-      {  // B6 = S·RR + RR·S
-        const Mat<D> M = mbar(6);
-        add_mmt<D>(bS, 1.0, M, RR);
-        add_mtm<D>(bRR, 1.0, S, M);
-        add_mmt<D>(bRR, 1.0, M, S);
-        add_mtm<D>(bS, 1.0, RR, M);
-      }
-      {  // B7 = RS·RR - RR·SR
-        const Mat<D> M = mbar(7);
-        add_mmt<D>(bRS, 1.0, M, RR);
-        add_mtm<D>(bRR, 1.0, RS, M);
-        add_mmt<D>(bRR, -1.0, M, SR);
-        add_mtm<D>(bSR, -1.0, RR, M);
-      }
-      {  // B8 = SR·SS - SS·RS
-        const Mat<D> M = mbar(8);
-        add_mmt<D>(bSR, 1.0, M, SS);
-        add_mtm<D>(bSS, 1.0, SR, M);
-        add_mmt<D>(bSS, -1.0, M, RS);
-        add_mtm<D>(bRS, -1.0, SS, M);
-      }
-    }
-    {  // P = SS·RR, Q = RR·SS:  B9 = P + Q,  B10 = R·P - Q·R,  V4 = tr P
-      Mat<D> bP = mzero<D>(), bQ = mzero<D>();
-      if (HASB) {
-        const Mat<D> M9 = mbar(9);
-        axpy<D>(bP, 1.0, M9);
-        axpy<D>(bQ, 1.0, M9);
-        const Mat<D> M = mbar(10);
-        const Mat<D> P = mm<D>(SS, RR), Q = mm<D>(RR, SS);
-        add_mmt<D>(bR, 1.0, M, P);
-        add_mtm<D>(bP, 1.0, R, M);
-        add_mmt<D>(bQ, -1.0, M, R);
-        add_mtm<D>(bR, -1.0, Q, M);
-      }
-      if (HASV) adiag<D>(bP, vb[4]);
-      add_mmt<D>(bSS, 1.0, bP, RR);
-      add_mtm<D>(bRR, 1.0, SS, bP);
-      add_mmt<D>(bRR, 1.0, bQ, SS);
-      add_mtm<D>(bSS, 1.0, RR, bQ);
-    }
-    if (HASV) {
-      adiag<D>(bSS, vb[0]);         // V0 = tr SS
-      adiag<D>(bRR, vb[1]);         // V1 = tr RR
-      axpyT<D>(bSS, vb[2], S);      // V2 = tr(SS·S)
-      axpyT<D>(bS, vb[2], SS);
-      axpyT<D>(bS, vb[3], RR);      // V3 = tr(S·RR)
-      axpyT<D>(bRR, vb[3], S);
-    }
-    add_mmt<D>(bS, 1.0, bSS, S);  // SS = S·S
-    add_mtm<D>(bS, 1.0, S, bSS);
-    add_mmt<D>(bR, 1.0, bRR, R);  // RR = R·R
-    add_mtm<D>(bR, 1.0, R, bRR);
-  }
-  add_mmt<D>(bS, 1.0, bSR, R);  // SR = S·R
-  add_mtm<D>(bR, 1.0, S, bSR);
-  add_mmt<D>(bR, 1.0, bRS, S);  // RS = R·S
-  add_mtm<D>(bS, 1.0, R, bRS);
-}
-
-// ∇ubar = sym(Sbar) + skew(Rbar) into the scratch: entry (a, b) at field a·D + b
-template <int D>
-__device__ __forceinline__ void put_gradbar(const GridDev& g, double* __restrict__ gb, long long c, const Mat<D>& bS, const Mat<D>& bR) {
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) gb[(long long)(a * D + b) * g.sc + c] = (bS.m[a][b] + bS.m[b][a]) / 2 + (bR.m[a][b] - bR.m[b][a]) / 2;
-}
-
-// The symmetric D×D matrix T with <T, B> = Σ_{a<=b} t_ab B_ab for symmetric B: the cotangent of the D(D+1)/2 stored entries of τ
-template <int D>
-__device__ __forceinline__ Mat<D> full_cotangent(const GridDev& g, const double* __restrict__ t, long long c) {
-  Mat<D> T;
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) T.m[a][b] = (a == b ? 1.0 : 0.5) * t[(long long)sym_index<D>(a, b) * g.sc + c];
-  return T;
-}
 
 // --------------------------------------------------------------------------------------------
 // forward: invariants and fused stress (write Ip)
@@ -366,7 +78,7 @@ __global__ __launch_bounds__(256) void k_tc_gradbar(GridDev g, const double* __r
   Mat<D> T = mzero<D>();
   if (HASA) T = full_cotangent<D>(g, taubar, c);
   Mat<D> bS, bR;
-  basis_reverse<D, HASA, HASV>(S, R, [&](int ib) {
+  basis_reverse<D, double, HASA, HASV>(S, R, [&](int ib) {
     Mat<D> M = T;
     const double s = a[ib * g.sc + c];
 #pragma unroll
@@ -391,7 +103,7 @@ __global__ __launch_bounds__(256) void k_tb_gradbar(GridDev g, const double* __r
     for (int q = 0; q < nv; ++q) vb[q] = Vbar[q * g.sc + c];
   }
   Mat<D> bS, bR;
-  basis_reverse<D, HASB, HASV>(S, R, [&](int ib) {
+  basis_reverse<D, double, HASB, HASV>(S, R, [&](int ib) {
     Mat<D> M;
 #pragma unroll
     for (int p = 0; p < D; ++p)
@@ -525,6 +237,9 @@ bool is_slab(const ins_grid* G) {
   } while (0)
 
 }  // namespace
+
+// the same scratch for ins_tensorclosure32.hip, which reads the bytes as float
+int ins_k_gradbar_scratch(const ins_grid* G, double** out) { return gradbar_scratch(G, out); }
 
 // ------------------------------------------------------------------------------------------------
 // C ABI

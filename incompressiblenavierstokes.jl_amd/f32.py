@@ -161,6 +161,62 @@ def project_pullback32_(φbar, setup, psolver, pwork):
     return φbar
 
 
+# ---- tensor-basis closure (csrc/ins_tensorclosure32.hip): the Float32 twins of operators.tensorinvariants_ ... divoftensor_adjoint_
+def _tb_sizes(setup):
+    """(nb, nv, ns): basis tensors, invariants, stored entries of a symmetric tensor."""
+    D = setup.grid.dimension
+    return ((3, 2) if D == 2 else (11, 5)) + (D * (D + 1) // 2,)
+
+
+def nfield32(setup, ncomp):
+    """A zero float32 field of `ncomp` scalar fields, N + (ncomp,)."""
+    return _alloc32(setup, setup.grid.N + (ncomp,))
+
+
+def tensorfield32(setup):
+    """Symmetric tensor field: D(D+1)/2 float32 scalar fields [xx, yy, (zz), xy, (xz, yz)] (operators.tensorfield)."""
+    return nfield32(setup, _tb_sizes(setup)[2])
+
+
+def _ptr_or_null(setup, f, ncomp):
+    return None if f is None else _ptr(setup, f, ncomp)
+
+
+def tensorinvariants32_(V, u, setup):
+    """The invariants of the tensor basis (tensorbasis.jl:49-50, 70-74) with T = Float32: writes `V`, N + (nv,), on Ip."""
+    _lib.call("ins_tensorinvariants_f32", setup.handle, _ptr(setup, u, setup.grid.dimension), _ptr(setup, V, _tb_sizes(setup)[1]), setup.stream)
+    return V
+
+
+def tensorclosure_stress32_(τ, u, a, setup):
+    """τ = Σ_i a_i B_i(u) on Ip (tensorbasis.jl:59-69, 137-146) with T = Float32, without storing B: `a` is N + (nb,), `τ` a `tensorfield32`."""
+    nb, _, ns = _tb_sizes(setup)
+    _lib.call("ins_tensorclosure_stress_f32", setup.handle, _ptr(setup, u, setup.grid.dimension), _ptr(setup, a, nb), _ptr(setup, τ, ns), setup.stream)
+    return τ
+
+
+def tensorclosure_pullback32_(ubar, abar, τbar, Vbar, u, a, setup, accumulate=False):
+    """One backward for `tensorclosure_stress32_` and `tensorinvariants32_`: abar_i = <τbar, B_i> (overwritten), ubar = J_τ(u)ᵀτbar + J_V(u)ᵀVbar
+    (overwritten, or added to with `accumulate`).  `Vbar` may be None; `abar`, `τbar` and `a` may be None together."""
+    nb, nv, ns = _tb_sizes(setup)
+    D = setup.grid.dimension
+    _lib.call("ins_tensorclosure_pullback_f32", setup.handle, _ptr(setup, u, D), _ptr_or_null(setup, a, nb), _ptr_or_null(setup, τbar, ns),
+              _ptr_or_null(setup, Vbar, nv), _ptr_or_null(setup, abar, nb), _ptr(setup, ubar, D), int(bool(accumulate)), setup.stream)
+    return ubar
+
+
+def divoftensor32_(s, σ, setup):
+    """operators.jl:1158-1175, 1203-1236 with T = Float32, on the D(D+1)/2 symmetric fields."""
+    _lib.call("ins_divoftensor_f32", setup.handle, _ptr(setup, σ, _tb_sizes(setup)[2]), _ptr(setup, s, setup.grid.dimension), setup.stream)
+    return s
+
+
+def divoftensor_adjoint32_(σbar, sbar, setup):
+    """operators.jl:1186-1287 with T = Float32 (adds the transpose of divoftensor32_ applied to sbar to the symmetric fields σbar)."""
+    _lib.call("ins_divoftensor_adjoint_f32", setup.handle, _ptr(setup, sbar, setup.grid.dimension), _ptr(setup, σbar, _tb_sizes(setup)[2]), setup.stream)
+    return σbar
+
+
 def max_abs_divergence32(u, setup, psolver):
     out = C.c_float()
     _lib.call("ins_max_abs_divergence_f32", setup.handle, psolver.handle, _ptr(setup, u, setup.grid.dimension), C.byref(out), setup.stream)

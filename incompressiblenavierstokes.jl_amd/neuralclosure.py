@@ -305,17 +305,21 @@ def cnn(*, setup, radii, channels, activations, use_bias, rng=None):
 
 class TensorClosure(torch.nn.Module):
     """Tensor-basis closure of Silvis et al. (tensorbasis.jl): c = divoftensor(bc_p(Σ_i a_i(V) B_i)) with the coefficients a pointwise network of
-    the invariants — linear layers over the channel axis, float64.  Frame-invariant by construction, and defined on every grid the kernels of
-    csrc/ins_tensorclosure.hip accept.  Called on the padded field: `m(u, θ)`."""
+    the invariants — linear layers over the channel axis, float64 (or float32: then the operators are those of `ins_amd.ad32`, on float32
+    fields).  Frame-invariant by construction, and defined on every grid the kernels of csrc/ins_tensorclosure.hip (ins_tensorclosure32.hip)
+    accept.  Called on the padded field: `m(u, θ)`."""
 
-    def __init__(self, setup, hidden, activation, generator=None):
+    def __init__(self, setup, hidden, activation, generator=None, dtype=torch.float64):
         super().__init__()
         from .operators import _tb_sizes
 
+        if dtype not in (torch.float64, torch.float32):
+            raise TypeError("tensorclosure: dtype is torch.float64 or torch.float32")
         self.setup, self.activation = setup, activation
+        self.dtype = dtype
         nb, nv, _ = _tb_sizes(setup)
         c = [nv] + list(hidden) + [nb]
-        self.layers = torch.nn.ModuleList(torch.nn.Linear(c[i], c[i + 1], dtype=torch.float64) for i in range(len(c) - 1))
+        self.layers = torch.nn.ModuleList(torch.nn.Linear(c[i], c[i + 1], dtype=dtype) for i in range(len(c) - 1))
         for layer in self.layers:  # glorot_uniform weights, zero bias, as `cnn`
             torch.nn.init.xavier_uniform_(layer.weight, generator=generator)
             torch.nn.init.zeros_(layer.bias)
@@ -332,22 +336,25 @@ class TensorClosure(torch.nn.Module):
     def forward(self, u, θ=None):
         if θ is not None:
             return torch.func.functional_call(self, θ, (u,))
-        s = self.setup
-        a = self.coefficients(ad.tensorinvariants(u, s))
-        τ = ad.apply_bc_p_fields(ad.tensorclosure_stress(u, a, s), 0.0, s)
-        return ad.divoftensor(τ, s)
+        from . import autodiff32
+
+        s, o = self.setup, (ad if self.dtype == torch.float64 else autodiff32)
+        a = self.coefficients(o.tensorinvariants(u, s))
+        τ = o.apply_bc_p_fields(o.tensorclosure_stress(u, a, s), 0.0, s)
+        return o.divoftensor(τ, s)
 
 
-def tensorclosure(*, setup, hidden, activation, rng=None):
+def tensorclosure(*, setup, hidden, activation, rng=None, dtype=torch.float64):
     """Create tensor-basis closure model: a float64 `torch.nn.Module` on the device of `setup`, callable as `m(u, θ)` on the padded field, so it
     is a `closure_model` for `create_loss_post`, `create_relerr_post` and `ad.timestep` as it stands.  `hidden`: widths of the hidden layers of
     the coefficient network V -> a; `activation`: a callable or None; `rng`: a `torch.Generator` (CPU) or an integer seed for the weights;
     θ = None uses the module's own parameters, a dict goes through `torch.func.functional_call`.  The invariants enter as they are: scale them
-    in `activation` / the first layer if the flow needs it."""
+    in `activation` / the first layer if the flow needs it.  `dtype=torch.float32`: float32 layers on the `ad32` operators, a `closure_model`
+    for `ad32.timestep` and for `create_loss_post` with a Float32 pressure solver."""
     gen = rng
     if rng is not None and not isinstance(rng, torch.Generator):
         gen = torch.Generator().manual_seed(int(rng))
-    return TensorClosure(setup, list(hidden), activation, gen).to(setup.device)
+    return TensorClosure(setup, list(hidden), activation, gen, dtype).to(setup.device)
 
 
 # ------------------------------------------------------------------------------------------------ training.jl
@@ -448,20 +455,28 @@ def _field_of(setup, a):
 
 def create_loss_post(*, setup, method, psolver, closure_model, nsubstep=1):
     """Create a-posteriori loss function (training.jl:120-146): unroll `ad.timestep` from the first state of every trajectory in the batch and
-    average Σ|u − u_ref|² / Σ|u_ref|² (on `Iu`) over the following states.  Differentiable in θ."""
+    average Σ|u − u_ref|² / Σ|u_ref|² (on `Iu`) over the following states.  Differentiable in θ.  With a Float32 pressure solver
+    (`f32.psolver_spectral32`, `f32.psolver_wrap32`) the step is `ad32.timestep` on float32 fields (the trajectories are rounded to float32)."""
+    from . import autodiff32, f32
+
     setup = _SetupView(setup, closure_model)
     inside = _inside(setup)
+    single = isinstance(psolver, f32.psolver_spectral32)
+    step = autodiff32.timestep if single else ad.timestep
 
     def loss_post(data, θ):
         total = 0.0
         for traj in data:
             u, t = traj["u"], traj["t"]
-            stepper = create_stepper(method, setup=setup, psolver=psolver, u=_field_of(setup, u[..., 0]), temp=None, t=float(t[0]))
+            if single:
+                u = u.float()
+            u0 = f32.to_f32(setup, u[..., 0]) if single else _field_of(setup, u[..., 0])
+            stepper = create_stepper(method, setup=setup, psolver=psolver, u=u0, temp=None, t=float(t[0]))
             loss = 0.0
             for it in range(1, len(t)):
                 Δt = float(t[it] - t[it - 1]) / nsubstep
                 for _ in range(nsubstep):
-                    stepper = ad.timestep(method, stepper, Δt, θ)
+                    stepper = step(method, stepper, Δt, θ)
                 uref = u[..., it][inside]
                 d = stepper.u[inside] - uref
                 loss = loss + (d * d).sum() / (uref * uref).sum()
