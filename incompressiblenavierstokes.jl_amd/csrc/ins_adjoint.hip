@@ -1,213 +1,14 @@
-// Reverse-mode pullbacks of the step operators (operators.jl:100-616, boundary_conditions.jl:114-230, 290-516,
+// Reverse-mode pullbacks of the step operators in fp64 (operators.jl:100-616, boundary_conditions.jl:114-230, 290-516,
 // pressure.jl:15-19): each is the exact transpose of THIS library's forward operator on the whole padded array,
 // ghost volumes included (DESIGN.md "Differentiability").
 //
-// Gather form everywhere: one work-item per output volume reads the cotangent stencil around it, so no atomics
-// and every output is written once.  fp64, 2-D and 3-D, any BC mix, uniform and stretched grids; the metric
-// tables and reciprocal conventions are those of the generic forward twins in ins_operators.hip.
-#include "ins_stencil.h"
+// The generic gather kernels are the templates of ins_adjoint_kernels.h with T = double (ins_adjoint32.hip instantiates the same
+// templates with float); the metric tables and reciprocal conventions are those of the generic forward twins in ins_operators.hip.
+// This file adds what is fp64 only: the tiled momentum pullback of uniform periodic 3-D boxes, and the entry points.
+#include "ins_adjoint_kernels.h"
 #include "ins_wave64.h"
 
 namespace {
-
-// --------------------------------------------------------------------------------------------
-// divergence_adjoint                                                     operators.jl:127-145
-//   ubar[α][I] += alpha · (φ[I]/Δα[Iα] [I ∈ Ip] − φ[I+eα]/Δα[Iα+1] [I+eα ∈ Ip])   over the whole padded array
-// --------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_divergence_adjoint(GridDev g, const double* __restrict__ phi, double* __restrict__ ubar, double alpha) {
-  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
-  const bool here = in_ip<D>(g, i, j, k);
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    double v = 0.0;
-    if (here) v += phi[c] * g.rdx[a][I[a]];
-    if (in_ip<D>(g, INS_SH(I, a, 1))) v -= phi[c + g.sx[a]] * g.rdx[a][I[a] + 1];
-    ubar[a * g.sc + c] += alpha * v;
-  }
-}
-
-// --------------------------------------------------------------------------------------------
-// pressuregradient_adjoint                                               operators.jl:180-199
-//   pbar[I] += Σα (φα[I−eα]/Δuα[Iα−1] [I−eα dof of α] − φα[I]/Δuα[Iα] [I dof of α])
-// --------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_pressuregradient_adjoint(GridDev g, const double* __restrict__ phi, double* __restrict__ pbar) {
-  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
-  double v = 0.0;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    const double* pa = phi + a * g.sc;
-    if (dof<D>(g, a, i, j, k)) v -= pa[c] * g.rdxu[a][I[a]];
-    if (dof<D>(g, a, INS_SH(I, a, -1))) v += pa[c - g.sx[a]] * g.rdxu[a][I[a] - 1];
-  }
-  pbar[c] += v;
-}
-
-// --------------------------------------------------------------------------------------------
-// convection / diffusion pullback                               operators.jl:417-519, 575-616
-//   The forward (k_convdiff) adds to a DOF volume c of component α, per direction β,
-//     r(c)·[ ν(mb(c)(u[c+eβ]−u[c]) − ma(c)(u[c]−u[c−eβ])) − (Φ(c) − Φ(c−eβ)) ],
-//     Φ(f) = ½(uα[f]+uα[f+eβ]) · (A₂βα[fα] uβ[f] + A₁βα[fα+1] uβ[f+eα])        (the flux through the upper β-face of f)
-//   with r = 1/Δuβ (α == β) or 1/Δβ.  So ⟨φ, F⟩ = Σ_f ψ(f) Φ(f) + diffusion terms with
-//     ψαβ(f) = −r(f) φα[f] [f dof] + r(f+eβ) φα[f+eβ] [f+eβ dof],
-//   and ubar = J(u)ᵀφ gathers, per output volume x and component γ:
-//     (a) α = γ:  ψγβ(f) · ½(A₂ uβ[f] + A₁ uβ[f+eγ])         for f = x and f = x − eβ
-//     (b) β = γ:  ψαγ(x) · ½(uα[x]+uα[x+eγ]) · A₂γα[xα]    and  ψαγ(x−eα) · ½(uα[x−eα]+uα[x−eα+eγ]) · A₁γα[xα]
-//   (both when α = β = γ: the product rule).  A flux is evaluated only where ψ has a DOF term, i.e. exactly where the
-//   forward evaluated it, so every read stays inside the padded array.
-//   MODE bit0 = convection, bit1 = diffusion.  ACC: ubar += J^T φ, else ubar = J^T φ.
-// --------------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ double rr(const GridDev& g, int al, int be, int ib) {
-  return (al == be ? g.rdxu[be] : g.rdx[be])[ib];
-}
-
-// ψαβ(f) at f = (f0, f1, f2) (linear index cf); `live` = it has a DOF term
-template <int D>
-__device__ __forceinline__ double psi(const GridDev& g, int al, int be, const int (&F)[3], long long cf, const double* __restrict__ phia,
-                                      bool& live) {
-  const bool d0 = dof<D>(g, al, F[0], F[1], F[2]);
-  const bool d1 = dof<D>(g, al, INS_SH(F, be, 1));
-  live = d0 || d1;
-  double v = 0.0;
-  if (d0) v -= rr<D>(g, al, be, F[be]) * phia[cf];
-  if (d1) v += rr<D>(g, al, be, F[be] + 1) * phia[cf + g.sx[be]];
-  return v;
-}
-
-template <int D, int MODE, bool ACC>
-__global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, double visc, const double* __restrict__ u, const double* __restrict__ phi,
-                                                          double* __restrict__ ubar) {
-  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
-
-#pragma unroll
-  for (int ga = 0; ga < D; ++ga) {
-    const double* pg = phi + ga * g.sc;
-    double v = 0.0;
-    if (MODE & 2) {
-      const bool dx = dof<D>(g, ga, i, j, k);
-#pragma unroll
-      for (int be = 0; be < D; ++be) {
-        const int ib = I[be];
-        const long long sb = g.sx[be];
-        // ma(i) = mdx[i] | mdxu[i-1],  mb(i) = mdx[i+1] | mdxu[i]   (k_convdiff)
-        if (dx) {
-          const double ma = ga == be ? g.mdx[be][ib] : g.mdxu[be][ib - 1];
-          const double mb = ga == be ? g.mdx[be][ib + 1] : g.mdxu[be][ib];
-          v -= visc * pg[c] * rr<D>(g, ga, be, ib) * (ma + mb);
-        }
-        if (dof<D>(g, ga, INS_SH(I, be, -1))) {
-          const double mb = ga == be ? g.mdx[be][ib] : g.mdxu[be][ib - 1];
-          v += visc * pg[c - sb] * rr<D>(g, ga, be, ib - 1) * mb;
-        }
-        if (dof<D>(g, ga, INS_SH(I, be, 1))) {
-          const double ma = ga == be ? g.mdx[be][ib + 1] : g.mdxu[be][ib];
-          v += visc * pg[c + sb] * rr<D>(g, ga, be, ib + 1) * ma;
-        }
-      }
-    }
-    if (MODE & 1) {
-      const long long sg = g.sx[ga];
-      // (a) α = γ: ∂Φγβ(f)/∂uγ = ½ (A₂βγ[fγ] uβ[f] + A₁βγ[fγ+1] uβ[f+eγ])
-#pragma unroll
-      for (int be = 0; be < D; ++be) {
-        const long long sb = g.sx[be];
-        const double* ub = u + be * g.sc;
-        const double* A1 = g.A1[be][ga];
-        const double* A2 = g.A2[be][ga];
-#pragma unroll
-        for (int sh = 0; sh < 2; ++sh) {  // f = x, x − eβ
-          const int F[3] = {INS_SH(I, be, -sh)};
-          const long long cf = c - sh * sb;
-          bool live;
-          const double w = psi<D>(g, ga, be, F, cf, pg, live);
-          if (live) v += w * 0.5 * (A2[F[ga]] * ub[cf] + A1[F[ga] + 1] * ub[cf + sg]);
-        }
-      }
-      // (b) β = γ: ∂Φαγ(f)/∂uγ[f] = ½(uα[f]+uα[f+eγ]) A₂γα[fα];  ∂Φαγ(f)/∂uγ[f+eα] = ½(uα[f]+uα[f+eγ]) A₁γα[fα+1]
-#pragma unroll
-      for (int al = 0; al < D; ++al) {
-        const long long sa = g.sx[al];
-        const double* ua = u + al * g.sc;
-        const double* pa = phi + al * g.sc;
-        const double* A1 = g.A1[ga][al];
-        const double* A2 = g.A2[ga][al];
-        {
-          bool live;
-          const double w = psi<D>(g, al, ga, I, c, pa, live);
-          if (live) v += w * 0.5 * (ua[c] + ua[c + sg]) * A2[I[al]];
-        }
-        {
-          const int F[3] = {INS_SH(I, al, -1)};
-          const long long cf = c - sa;
-          bool live;
-          const double w = psi<D>(g, al, ga, F, cf, pa, live);
-          if (live) v += w * 0.5 * (ua[cf] + ua[cf + sg]) * A1[I[al]];
-        }
-      }
-    }
-    double* ob = ubar + ga * g.sc + c;
-    *ob = ACC ? *ob + v : v;
-  }
-}
-
-// --------------------------------------------------------------------------------------------
-// apply_bc_u_pullback / apply_bc_p_pullback           boundary_conditions.jl:169-230, 290-516
-//   The exact transpose of k_bc_u / k_bc_p (ins_bc.hip): the forward sweeps β = 0..D-1 and, per line, left side then
-//   right side, each fill a copy (x[i] = x[j]) or a constant; the transpose walks β = D-1..0 and the sides right then
-//   left, turning x[i] = x[j] into (x̄[j] += x̄[i]; x̄[i] = 0) and x[i] = const into x̄[i] = 0.  Time-dependent Dirichlet
-//   planes only change the constant, so the pullback does not read them.
-// --------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_bc_u_pullback(GridDev g, double* __restrict__ u, int be) {
-  INS_LINE_INDEX(be);
-  const int al = blockIdx.z;
-  const long long sb = g.sx[be];
-  double* ua = u + al * g.sc + base;
-  const int bcl = g.bc[be][0], bcr = g.bc[be][1];
-  if (bcl == INS_BC_PERIODIC) {  // forward: x[ia] = x[ib-1]; x[ib] = x[ia+1]
-    const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
-    move_to(ua, ib * sb, (ia + 1) * sb);
-    move_to(ua, ia * sb, (ib - 1) * sb);
-    return;
-  }
-#pragma unroll
-  for (int side = 1; side >= 0; --side) {
-    const int bc = side ? bcr : bcl;
-    if (bc == INS_BC_HALO) continue;
-    const int i = side ? g.iu_hi[al][be] : g.iu_lo[al][be] - 1;
-    const int jn = side ? i - 1 : i + 1;
-    if (bc == INS_BC_DIRICHLET || (bc == INS_BC_SYMMETRIC && al == be))
-      ua[i * sb] = 0.0;
-    else if (bc == INS_BC_SYMMETRIC || bc == INS_BC_PRESSURE)
-      move_to(ua, i * sb, jn * sb);
-  }
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_bc_p_pullback(GridDev g, double* __restrict__ p, int be) {
-  INS_LINE_INDEX(be);
-  double* pl = p + base;
-  const long long sb = g.sx[be];
-  const int bcl = g.bc[be][0], bcr = g.bc[be][1];
-  const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
-  if (bcl == INS_BC_PERIODIC) {
-    move_to(pl, ib * sb, (ia + 1) * sb);
-    move_to(pl, ia * sb, (ib - 1) * sb);
-    return;
-  }
-#pragma unroll
-  for (int side = 1; side >= 0; --side) {
-    const int bc = side ? bcr : bcl;
-    const int i = side ? ib : ia;
-    const int jn = side ? i - 1 : i + 1;
-    if (bc == INS_BC_SYMMETRIC)
-      move_to(pl, i * sb, jn * sb);
-    else if (bc == INS_BC_PRESSURE)
-      pl[i * sb] = 0.0;
-  }
-}
 
 // --------------------------------------------------------------------------------------------
 // Tiled fused momentum pullback: uniform, all-periodic 3-D boxes (the k_flux64 idioms)
@@ -332,7 +133,7 @@ template <int MODE, bool ACC>
 int launch_convdiff_adjoint(const ins_grid* G, double visc, const double* u, const double* phi, double* ubar, hipStream_t s) {
   const GridDev& g = G->g;
   const Launch3 l = box_launch(g.D, g.N);
-  INS_LAUNCH_D((k_convdiff_adjoint<D, MODE, ACC>), l, s, g, visc, u, phi, ubar);
+  INS_LAUNCH_D((k_convdiff_adjoint<D, double, MODE, ACC>), l, s, g, visc, u, phi, ubar);
   return INS_OK;
 }
 
@@ -383,14 +184,14 @@ int launch_momentum_pullback_tiled(const ins_grid* G, double visc, const double*
 int ins_k_divergence_adjoint(const ins_grid* G, const double* phi, double* ubar, double alpha, hipStream_t s) {
   const GridDev& g = G->g;
   const Launch3 l = box_launch(g.D, g.N);
-  INS_LAUNCH_D((k_divergence_adjoint<D>), l, s, g, phi, ubar, alpha);
+  INS_LAUNCH_D((k_divergence_adjoint<D, double, double>), l, s, g, phi, ubar, alpha);
   return INS_OK;
 }
 
 int ins_k_pressuregradient_adjoint(const ins_grid* G, const double* phi, double* pbar, hipStream_t s) {
   const GridDev& g = G->g;
   const Launch3 l = box_launch(g.D, g.N);
-  INS_LAUNCH_D((k_pressuregradient_adjoint<D>), l, s, g, phi, pbar);
+  INS_LAUNCH_D((k_pressuregradient_adjoint<D, double, double, true>), l, s, g, phi, pbar);
   return INS_OK;
 }
 
@@ -398,7 +199,7 @@ int ins_k_apply_bc_u_pullback(const ins_grid* G, double* u, hipStream_t s) {
   const GridDev& g = G->g;
   for (int be = g.D - 1; be >= 0; --be) {  // reverse of ins_k_apply_bc_u
     if (g.bc[be][0] == INS_BC_HALO && g.bc[be][1] == INS_BC_HALO) continue;
-    INS_LAUNCH_D((k_bc_u_pullback<D>), line_launch(g, be, g.D), s, g, u, be);
+    INS_LAUNCH_D((k_bc_u_pullback<D, double>), line_launch(g, be, g.D), s, g, u, be);
   }
   return INS_OK;
 }
@@ -408,7 +209,7 @@ int ins_k_apply_bc_p_pullback(const ins_grid* G, double* p, hipStream_t s) {
   for (int be = g.D - 1; be >= 0; --be) {  // reverse of ins_k_apply_bc_p_fields
     const int l = g.bc[be][0], r = g.bc[be][1];
     if ((l == INS_BC_DIRICHLET || l == INS_BC_HALO) && (r == INS_BC_DIRICHLET || r == INS_BC_HALO)) continue;
-    INS_LAUNCH_D((k_bc_p_pullback<D>), line_launch(g, be, 1), s, g, p, be);
+    INS_LAUNCH_D((k_bc_p_pullback<D, double>), line_launch(g, be, 1), s, g, p, be);
   }
   return INS_OK;
 }

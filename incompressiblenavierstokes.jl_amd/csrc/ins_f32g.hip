@@ -144,15 +144,6 @@ __global__ __launch_bounds__(256) void k32g_round(long long n, const double* __r
 
 inline dim3 flat_grid(long long n) { return dim3((unsigned)std::min<long long>((n + 255) / 256, 8192)); }
 
-int no_halo(const ins_grid* G, const char* what) {
-  for (int a = 0; a < G->g.D; ++a)
-    if (G->g.bc[a][0] == INS_BC_HALO || G->g.bc[a][1] == INS_BC_HALO) {
-      ins_set_error("%s: slab (halo) grids run in fp64 only", what);
-      return INS_ERR_UNSUPPORTED;
-    }
-  return INS_OK;
-}
-
 }  // namespace
 
 int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s) {

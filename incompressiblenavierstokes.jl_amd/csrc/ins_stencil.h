@@ -60,6 +60,17 @@ inline Launch3 line_launch(const GridDev& g, int be, int ncomp) {
   return l;
 }
 
+// Entries that do not take a z-slab of the multi-GPU decomposition (the Float32 family, the tensor-closure pullbacks) begin with this:
+// INS_ERR_UNSUPPORTED and the error "<what>: <why>" if any side of the grid is a halo side.
+inline int no_halo(const ins_grid* G, const char* what, const char* why = "slab (halo) grids run in fp64 only") {
+  for (int a = 0; a < G->g.D; ++a)
+    if (G->g.bc[a][0] == INS_BC_HALO || G->g.bc[a][1] == INS_BC_HALO) {
+      ins_set_error("%s: %s", what, why);
+      return INS_ERR_UNSUPPORTED;
+    }
+  return INS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Index preambles.  Each declares i, j, k, I[3] and the linear index c = i + j sx[1] + k sx[2] inside a kernel template with `int D`.
 // ------------------------------------------------------------------------------------------------
@@ -149,9 +160,10 @@ __device__ __forceinline__ bool dof(const GridDev& g, int al, int i0, int i1, in
 }
 
 // Transposed ghost copy of the BC pullbacks: x[from] = x[to] becomes (x̄[to] += x̄[from]; x̄[from] = 0).
-__device__ __forceinline__ void move_to(double* __restrict__ x, long long from, long long to) {
-  const double t = x[from];
-  x[from] = 0.0;
+template <typename T>
+__device__ __forceinline__ void move_to(T* __restrict__ x, long long from, long long to) {
+  const T t = x[from];
+  x[from] = T(0);
   x[to] += t;
 }
 

@@ -1,7 +1,9 @@
-// Pointwise part of the tensor-basis closure (tensorbasis.jl:1-95, operators.jl:1023-1033; Silvis et al. eqs. 9 and 11), shared by the fp64
-// kernels (ins_tensorclosure.hip) and the Float32 ones (ins_tensorclosure32.hip): D×D matrices in registers, ∇u and its symmetric / skew
-// parts at a pressure point, the eleven basis tensors, the invariants and the reverse rules, as templates over the scalar type T of the
-// fields.  The grid handle is the fp64 one for both: a metric table entry is converted to T where it enters, and all arithmetic is in T.
+// The tensor-basis closure once for both precisions (tensorbasis.jl:1-95, operators.jl:1023-1033; Silvis et al. eqs. 9 and 11), as templates
+// over the scalar type T of the fields: ins_tensorclosure.hip instantiates them with double, ins_tensorclosure32.hip with float.
+// First the pointwise part: D×D matrices in registers, ∇u and its symmetric / skew parts at a pressure point, the eleven basis tensors, the
+// invariants and the reverse rules.  Then the kernels built on it: the fused forward (k_tc_invariants, k_tc_stress) and pass 1 of the
+// pullbacks (k_tc_abar, k_tc_gradbar, k_tb_gradbar).  The grid handle is the fp64 one for both: a metric table entry is converted to T where
+// it enters, and all arithmetic is in T (ins_adjoint_kernels.h states the rule).
 //
 // Reverse rules (derived, not probed).  Every tensor is a sum of products of S and R, evaluated through the binary products
 //   SR = S·R, RS = R·S, SS = S·S, RR = R·R, P = SS·RR, Q = RR·SS, ...
@@ -288,7 +290,7 @@ __device__ __forceinline__ void put_gradbar(const GridDev& g, T* __restrict__ gb
     for (int b = 0; b < D; ++b) gb[(long long)(a * D + b) * g.sc + c] = (bS.m[a][b] + bS.m[b][a]) / 2 + (bR.m[a][b] - bR.m[b][a]) / 2;
 }
 
-// The symmetric D×D matrix T with <T, B> = Σ_{a<=b} t_ab B_ab for symmetric B: the cotangent of the D(D+1)/2 stored entries of τ
+// The symmetric D×D matrix M with <M, B> = Σ_{a<=b} t_ab B_ab for symmetric B: the cotangent of the D(D+1)/2 stored entries of τ
 template <int D, typename T>
 __device__ __forceinline__ Mat<D, T> full_cotangent(const GridDev& g, const T* __restrict__ t, long long c) {
   Mat<D, T> M;
@@ -297,6 +299,104 @@ __device__ __forceinline__ Mat<D, T> full_cotangent(const GridDev& g, const T* _
 #pragma unroll
     for (int b = 0; b < D; ++b) M.m[a][b] = T(a == b ? 1.0 : 0.5) * t[(long long)sym_index<D>(a, b) * g.sc + c];
   return M;
+}
+
+// --------------------------------------------------------------------------------------------
+// forward: invariants and fused stress (write Ip)
+// --------------------------------------------------------------------------------------------
+template <int D, typename T>
+__global__ __launch_bounds__(256) void k_tc_invariants(GridDev g, const T* __restrict__ u, T* __restrict__ V) {
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
+  Mat<D, T> S, R;
+  strain_rotation<D, T>(g, u, c, I, S, R);
+  T v[5];
+  invariants<D, T>(S, R, v);
+  constexpr int nv = D == 2 ? 2 : 5;
+#pragma unroll
+  for (int q = 0; q < nv; ++q) V[q * g.sc + c] = v[q];
+}
+
+template <int D, typename T>
+__global__ __launch_bounds__(256) void k_tc_stress(GridDev g, const T* __restrict__ u, const T* __restrict__ a, T* __restrict__ tau) {
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
+  Mat<D, T> S, R;
+  strain_rotation<D, T>(g, u, c, I, S, R);
+  Mat<D, T> M = mzero<D, T>();
+  for_each_basis<D, T>(S, R, [&](int ib, const Mat<D, T>& B) { axpy<D, T>(M, a[ib * g.sc + c], B); });
+#pragma unroll
+  for (int p = 0; p < D; ++p)
+#pragma unroll
+    for (int q = p; q < D; ++q) tau[(long long)sym_index<D>(p, q) * g.sc + c] = M.m[p][q];
+}
+
+// --------------------------------------------------------------------------------------------
+// pass 1 of the pullbacks: ∇ubar at every pressure point
+// --------------------------------------------------------------------------------------------
+// abar_i = <τbar, B_i> over the whole padded array (0 outside Ip, where the forward reads no a)
+template <int D, typename T>
+__global__ __launch_bounds__(256) void k_tc_abar(GridDev g, const T* __restrict__ u, const T* __restrict__ taubar, T* __restrict__ abar) {
+  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
+  constexpr int nb = D == 2 ? 3 : 11;
+  if (!in_ip<D>(g, i, j, k)) {
+#pragma unroll
+    for (int ib = 0; ib < nb; ++ib) abar[ib * g.sc + c] = T(0);
+    return;
+  }
+  Mat<D, T> S, R;
+  strain_rotation<D, T>(g, u, c, I, S, R);
+  const Mat<D, T> M = full_cotangent<D, T>(g, taubar, c);
+  for_each_basis<D, T>(S, R, [&](int ib, const Mat<D, T>& B) { abar[ib * g.sc + c] = mdot<D, T>(M, B); });
+}
+
+// closure route: Bbar_i = a_i τbar, plus the invariants' cotangent
+template <int D, typename T, bool HASA, bool HASV>
+__global__ __launch_bounds__(256) void k_tc_gradbar(GridDev g, const T* __restrict__ u, const T* __restrict__ a, const T* __restrict__ taubar,
+                                                    const T* __restrict__ Vbar, T* __restrict__ gb) {
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
+  Mat<D, T> S, R;
+  strain_rotation<D, T>(g, u, c, I, S, R);
+  T vb[5] = {0, 0, 0, 0, 0};
+  constexpr int nv = D == 2 ? 2 : 5;
+  if (HASV) {
+#pragma unroll
+    for (int q = 0; q < nv; ++q) vb[q] = Vbar[q * g.sc + c];
+  }
+  Mat<D, T> tb = mzero<D, T>();
+  if (HASA) tb = full_cotangent<D, T>(g, taubar, c);
+  Mat<D, T> bS, bR;
+  basis_reverse<D, T, HASA, HASV>(S, R, [&](int ib) {
+    Mat<D, T> M = tb;
+    const T s = a[ib * g.sc + c];
+#pragma unroll
+    for (int p = 0; p < D; ++p)
+#pragma unroll
+      for (int q = 0; q < D; ++q) M.m[p][q] *= s;
+    return M; }, vb, bS, bR);
+  put_gradbar<D, T>(g, gb, c, bS, bR);
+}
+
+// operator route: Bbar in the layout of ins_tensorbasis_f64 (element (p, q) of tensor ib at field ib·D·D + p + D·q)
+template <int D, typename T, bool HASB, bool HASV>
+__global__ __launch_bounds__(256) void k_tb_gradbar(GridDev g, const T* __restrict__ u, const T* __restrict__ Bbar, const T* __restrict__ Vbar,
+                                                    T* __restrict__ gb) {
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
+  Mat<D, T> S, R;
+  strain_rotation<D, T>(g, u, c, I, S, R);
+  T vb[5] = {0, 0, 0, 0, 0};
+  constexpr int nv = D == 2 ? 2 : 5;
+  if (HASV) {
+#pragma unroll
+    for (int q = 0; q < nv; ++q) vb[q] = Vbar[q * g.sc + c];
+  }
+  Mat<D, T> bS, bR;
+  basis_reverse<D, T, HASB, HASV>(S, R, [&](int ib) {
+    Mat<D, T> M;
+#pragma unroll
+    for (int p = 0; p < D; ++p)
+#pragma unroll
+      for (int q = 0; q < D; ++q) M.m[p][q] = Bbar[(long long)(ib * D * D + p + D * q) * g.sc + c];
+    return M; }, vb, bS, bR);
+  put_gradbar<D, T>(g, gb, c, bS, bR);
 }
 
 }  // namespace

@@ -9,109 +9,12 @@
 // work-item in a fixed order of additions, so results are bitwise reproducible run to run.  The ∇ubar scratch belongs to the grid
 // handle (grown on first use).
 //
-// The matrix helpers, strain_rotation, the basis tensors, the invariants and the reverse rules are in ins_tensorbasis.h, shared with the
-// Float32 kernels (ins_tensorclosure32.hip).
+// The fused forward and pass 1 of the pullbacks, with the pointwise part they share, are the templates of ins_tensorbasis.h with T = double
+// (ins_tensorclosure32.hip instantiates them with float).  This file holds pass 2 and divoftensor_adjoint (which have float copies in
+// ins_tensorclosure32.hip: change both), the ∇ubar scratch, the launches and the fp64 entry points.
 #include "ins_tensorbasis.h"
 
 namespace {
-
-// --------------------------------------------------------------------------------------------
-// forward: invariants and fused stress (write Ip)
-// --------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_tc_invariants(GridDev g, const double* __restrict__ u, double* __restrict__ V) {
-  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
-  Mat<D> S, R;
-  strain_rotation<D>(g, u, c, I, S, R);
-  double v[5];
-  invariants<D>(S, R, v);
-  constexpr int nv = D == 2 ? 2 : 5;
-#pragma unroll
-  for (int q = 0; q < nv; ++q) V[q * g.sc + c] = v[q];
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_tc_stress(GridDev g, const double* __restrict__ u, const double* __restrict__ a, double* __restrict__ tau) {
-  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
-  Mat<D> S, R;
-  strain_rotation<D>(g, u, c, I, S, R);
-  Mat<D> T = mzero<D>();
-  for_each_basis<D>(S, R, [&](int ib, const Mat<D>& B) { axpy<D>(T, a[ib * g.sc + c], B); });
-#pragma unroll
-  for (int p = 0; p < D; ++p)
-#pragma unroll
-    for (int q = p; q < D; ++q) tau[(long long)sym_index<D>(p, q) * g.sc + c] = T.m[p][q];
-}
-
-// --------------------------------------------------------------------------------------------
-// pass 1 of the pullbacks: ∇ubar at every pressure point
-// --------------------------------------------------------------------------------------------
-// abar_i = <T, B_i> over the whole padded array (0 outside Ip, where the forward reads no a)
-template <int D>
-__global__ __launch_bounds__(256) void k_tc_abar(GridDev g, const double* __restrict__ u, const double* __restrict__ taubar, double* __restrict__ abar) {
-  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
-  constexpr int nb = D == 2 ? 3 : 11;
-  if (!in_ip<D>(g, i, j, k)) {
-#pragma unroll
-    for (int ib = 0; ib < nb; ++ib) abar[ib * g.sc + c] = 0.0;
-    return;
-  }
-  Mat<D> S, R;
-  strain_rotation<D>(g, u, c, I, S, R);
-  const Mat<D> T = full_cotangent<D>(g, taubar, c);
-  for_each_basis<D>(S, R, [&](int ib, const Mat<D>& B) { abar[ib * g.sc + c] = mdot<D>(T, B); });
-}
-
-// closure route: Bbar_i = a_i T, plus the invariants' cotangent
-template <int D, bool HASA, bool HASV>
-__global__ __launch_bounds__(256) void k_tc_gradbar(GridDev g, const double* __restrict__ u, const double* __restrict__ a, const double* __restrict__ taubar,
-                                                    const double* __restrict__ Vbar, double* __restrict__ gb) {
-  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
-  Mat<D> S, R;
-  strain_rotation<D>(g, u, c, I, S, R);
-  double vb[5] = {0, 0, 0, 0, 0};
-  constexpr int nv = D == 2 ? 2 : 5;
-  if (HASV) {
-#pragma unroll
-    for (int q = 0; q < nv; ++q) vb[q] = Vbar[q * g.sc + c];
-  }
-  Mat<D> T = mzero<D>();
-  if (HASA) T = full_cotangent<D>(g, taubar, c);
-  Mat<D> bS, bR;
-  basis_reverse<D, double, HASA, HASV>(S, R, [&](int ib) {
-    Mat<D> M = T;
-    const double s = a[ib * g.sc + c];
-#pragma unroll
-    for (int p = 0; p < D; ++p)
-#pragma unroll
-      for (int q = 0; q < D; ++q) M.m[p][q] *= s;
-    return M; }, vb, bS, bR);
-  put_gradbar<D>(g, gb, c, bS, bR);
-}
-
-// operator route: Bbar in the layout of ins_tensorbasis_f64 (element (p, q) of tensor ib at field ib·D·D + p + D·q)
-template <int D, bool HASB, bool HASV>
-__global__ __launch_bounds__(256) void k_tb_gradbar(GridDev g, const double* __restrict__ u, const double* __restrict__ Bbar, const double* __restrict__ Vbar,
-                                                    double* __restrict__ gb) {
-  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
-  Mat<D> S, R;
-  strain_rotation<D>(g, u, c, I, S, R);
-  double vb[5] = {0, 0, 0, 0, 0};
-  constexpr int nv = D == 2 ? 2 : 5;
-  if (HASV) {
-#pragma unroll
-    for (int q = 0; q < nv; ++q) vb[q] = Vbar[q * g.sc + c];
-  }
-  Mat<D> bS, bR;
-  basis_reverse<D, double, HASB, HASV>(S, R, [&](int ib) {
-    Mat<D> M;
-#pragma unroll
-    for (int p = 0; p < D; ++p)
-#pragma unroll
-      for (int q = 0; q < D; ++q) M.m[p][q] = Bbar[(long long)(ib * D * D + p + D * q) * g.sc + c];
-    return M; }, vb, bS, bR);
-  put_gradbar<D>(g, gb, c, bS, bR);
-}
 
 // --------------------------------------------------------------------------------------------
 // pass 2: transpose of ∇ (operators.jl:1023-1033), gathered per u entry over the whole padded array.  ∇ at I reads
@@ -223,17 +126,9 @@ int launch_gradu_adjoint(const ins_grid* G, const double* gb, double* ubar, bool
 }
 
 // a z-slab of the multi-GPU decomposition: the pullbacks would have to reduce over the neighbours' ghost planes (not implemented)
-bool is_slab(const ins_grid* G) {
-  for (int b = 0; b < G->g.D; ++b)
-    if (G->g.bc[b][0] == INS_BC_HALO || G->g.bc[b][1] == INS_BC_HALO) return true;
-  return false;
-}
-#define INS_TC_NO_SLAB(G)                                                                    \
-  do {                                                                                       \
-    if (is_slab(G)) {                                                                        \
-      ins_set_error("%s: slab (INS_BC_HALO) grids are not supported", __func__);             \
-      return INS_ERR_UNSUPPORTED;                                                            \
-    }                                                                                        \
+#define INS_TC_NO_SLAB(G)                                                                             \
+  do {                                                                                                \
+    if (int rc_ = no_halo(G, __func__, "slab (INS_BC_HALO) grids are not supported")) return rc_;     \
   } while (0)
 
 }  // namespace
@@ -249,7 +144,7 @@ extern "C" int ins_tensorinvariants_f64(const ins_grid_t* G, const double* u, do
   INS_TC_NO_SLAB(G);
   const GridDev& g = G->g;
   const Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
-  INS_LAUNCH_D((k_tc_invariants<D>), l, as_stream(stream), g, u, V);
+  INS_LAUNCH_D((k_tc_invariants<D, double>), l, as_stream(stream), g, u, V);
   return INS_OK;
 }
 
@@ -259,7 +154,7 @@ extern "C" int ins_tensorclosure_stress_f64(const ins_grid_t* G, const double* u
   INS_REQUIRE(tau != u && tau != a, "tensorclosure stress cannot run in place");
   const GridDev& g = G->g;
   const Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
-  INS_LAUNCH_D((k_tc_stress<D>), l, as_stream(stream), g, u, a, tau);
+  INS_LAUNCH_D((k_tc_stress<D, double>), l, as_stream(stream), g, u, a, tau);
   return INS_OK;
 }
 
@@ -276,14 +171,14 @@ extern "C" int ins_tensorclosure_pullback_f64(const ins_grid_t* G, const double*
   double* gb = nullptr;
   int rc = gradbar_scratch(G, &gb);
   if (rc != INS_OK) return rc;
-  if (a) INS_LAUNCH_D((k_tc_abar<D>), box_launch(g.D, g.N), s, g, u, taubar, abar);
+  if (a) INS_LAUNCH_D((k_tc_abar<D, double>), box_launch(g.D, g.N), s, g, u, taubar, abar);
   const Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
   if (a && Vbar)
-    INS_LAUNCH_D((k_tc_gradbar<D, true, true>), l, s, g, u, a, taubar, Vbar, gb);
+    INS_LAUNCH_D((k_tc_gradbar<D, double, true, true>), l, s, g, u, a, taubar, Vbar, gb);
   else if (a)
-    INS_LAUNCH_D((k_tc_gradbar<D, true, false>), l, s, g, u, a, taubar, Vbar, gb);
+    INS_LAUNCH_D((k_tc_gradbar<D, double, true, false>), l, s, g, u, a, taubar, Vbar, gb);
   else
-    INS_LAUNCH_D((k_tc_gradbar<D, false, true>), l, s, g, u, a, taubar, Vbar, gb);
+    INS_LAUNCH_D((k_tc_gradbar<D, double, false, true>), l, s, g, u, a, taubar, Vbar, gb);
   return launch_gradu_adjoint(G, gb, ubar, accumulate != 0, s);
 }
 
@@ -300,11 +195,11 @@ extern "C" int ins_tensorbasis_pullback_f64(const ins_grid_t* G, const double* u
   if (rc != INS_OK) return rc;
   const Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
   if (Bbar && Vbar)
-    INS_LAUNCH_D((k_tb_gradbar<D, true, true>), l, s, g, u, Bbar, Vbar, gb);
+    INS_LAUNCH_D((k_tb_gradbar<D, double, true, true>), l, s, g, u, Bbar, Vbar, gb);
   else if (Bbar)
-    INS_LAUNCH_D((k_tb_gradbar<D, true, false>), l, s, g, u, Bbar, Vbar, gb);
+    INS_LAUNCH_D((k_tb_gradbar<D, double, true, false>), l, s, g, u, Bbar, Vbar, gb);
   else
-    INS_LAUNCH_D((k_tb_gradbar<D, false, true>), l, s, g, u, Bbar, Vbar, gb);
+    INS_LAUNCH_D((k_tb_gradbar<D, double, false, true>), l, s, g, u, Bbar, Vbar, gb);
   return launch_gradu_adjoint(G, gb, ubar, accumulate != 0, s);
 }
 

@@ -1,50 +1,23 @@
 // Differentiable tensor-basis closure with T = Float32 (tensorbasis.jl:1-95, operators.jl:1023-1033, 1155-1287; the reference is generic
-// in T): the Float32 twins of csrc/ins_tensorclosure.hip and of k_divoftensor (ins_fields.hip),
-//   τ = Σ_i a_i B_i(S, R),   V = invariants of (S, R),   s = div τ,   and their pullbacks,
-// on the pointwise templates of ins_tensorbasis.h instantiated with float.
+// in T):
+//   τ = Σ_i a_i B_i(S, R),   V = invariants of (S, R),   s = div τ,   and their pullbacks.
+// The fused forward and pass 1 of the pullbacks are the templates of ins_tensorbasis.h with T = float, the ones ins_tensorclosure.hip
+// instantiates with double.  Three kernels are still kept here as float copies of their fp64 twins (k32_divoftensor of k_divoftensor in
+// ins_fields.hip; k32_gradu_adjoint and k32_divoftensor_adjoint of ins_tensorclosure.hip): the twins spell the shifted index of a mask
+// differently, each spelling compiles to a different schedule, and no single one reproduced both.  A fix to one of these
+// goes into the other as well.
 //
 // The conventions of ins_f32g.hip / ins_adjoint32.hip: float fields in the reference layout, the fp64 grid handle, reciprocal tables read
-// as doubles and rounded to float where they enter the arithmetic, all arithmetic in float.  The launch geometry, index preambles and masks
-// of the fp64 file (ins_stencil.h); 2-D and 3-D, stretched grids, any BC mix.  The pullbacks keep its design: exact transposes on the
-// whole padded array, masked to Ip; two passes in gather form (pass 1 forms ∇ubar per pressure point, pass 2 gathers the transpose of ∇ per
-// u entry); no atomic operations, every output written once by one work-item in a fixed order of additions, so results are bitwise
-// reproducible run to run.  The ∇ubar scratch is the grid handle's (ins_tensorclosure.hip allocates and grows it, D·D doubles per
-// volume); its first half is used here as D·D floats per volume.  A translation unit of its own so that the fp64 kernels keep their
-// register allocation.  Slab (HALO) sides are not taken: the multi-GPU path is fp64.
+// as doubles and rounded to float where they enter the arithmetic, all arithmetic in float.  The ∇ubar scratch is the grid handle's
+// (ins_tensorclosure.hip allocates and grows it, D·D doubles per volume); its first half is used here as D·D floats per volume.  A
+// translation unit of its own so that the fp64 kernels keep their register allocation.  Slab (HALO) sides are not taken: the multi-GPU
+// path is fp64.
 #include "ins_tensorbasis.h"
 
 // csrc/ins_tensorclosure.hip
 int ins_k_gradbar_scratch(const ins_grid* G, double** out);
 
 namespace {
-
-// --------------------------------------------------------------------------------------------
-// forward: invariants and fused stress (write Ip)
-// --------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k32_tc_invariants(GridDev g, const float* __restrict__ u, float* __restrict__ V) {
-  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
-  Mat<D, float> S, R;
-  strain_rotation<D, float>(g, u, c, I, S, R);
-  float v[5];
-  invariants<D, float>(S, R, v);
-  constexpr int nv = D == 2 ? 2 : 5;
-#pragma unroll
-  for (int q = 0; q < nv; ++q) V[q * g.sc + c] = v[q];
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k32_tc_stress(GridDev g, const float* __restrict__ u, const float* __restrict__ a, float* __restrict__ tau) {
-  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
-  Mat<D, float> S, R;
-  strain_rotation<D, float>(g, u, c, I, S, R);
-  Mat<D, float> T = mzero<D, float>();
-  for_each_basis<D, float>(S, R, [&](int ib, const Mat<D, float>& B) { axpy<D, float>(T, a[ib * g.sc + c], B); });
-#pragma unroll
-  for (int p = 0; p < D; ++p)
-#pragma unroll
-    for (int q = p; q < D; ++q) tau[(long long)sym_index<D>(p, q) * g.sc + c] = T.m[p][q];
-}
 
 // divoftensor! on the D(D+1)/2 symmetric fields (operators.jl:1203-1236): k_divoftensor of ins_fields.hip in float
 template <int D>
@@ -71,52 +44,6 @@ __global__ __launch_bounds__(256) void k32_divoftensor(GridDev g, BoxMap L, cons
     }
     s[a * g.sc + c] = acc;
   }
-}
-
-// --------------------------------------------------------------------------------------------
-// pass 1 of the pullbacks: ∇ubar at every pressure point
-// --------------------------------------------------------------------------------------------
-// abar_i = <T, B_i> over the whole padded array (0 outside Ip, where the forward reads no a)
-template <int D>
-__global__ __launch_bounds__(256) void k32_tc_abar(GridDev g, const float* __restrict__ u, const float* __restrict__ taubar, float* __restrict__ abar) {
-  INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
-  constexpr int nb = D == 2 ? 3 : 11;
-  if (!in_ip<D>(g, i, j, k)) {
-#pragma unroll
-    for (int ib = 0; ib < nb; ++ib) abar[ib * g.sc + c] = 0.f;
-    return;
-  }
-  Mat<D, float> S, R;
-  strain_rotation<D, float>(g, u, c, I, S, R);
-  const Mat<D, float> T = full_cotangent<D, float>(g, taubar, c);
-  for_each_basis<D, float>(S, R, [&](int ib, const Mat<D, float>& B) { abar[ib * g.sc + c] = mdot<D, float>(T, B); });
-}
-
-// Bbar_i = a_i T, plus the invariants' cotangent
-template <int D, bool HASA, bool HASV>
-__global__ __launch_bounds__(256) void k32_tc_gradbar(GridDev g, const float* __restrict__ u, const float* __restrict__ a, const float* __restrict__ taubar,
-                                                      const float* __restrict__ Vbar, float* __restrict__ gb) {
-  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
-  Mat<D, float> S, R;
-  strain_rotation<D, float>(g, u, c, I, S, R);
-  float vb[5] = {0, 0, 0, 0, 0};
-  constexpr int nv = D == 2 ? 2 : 5;
-  if (HASV) {
-#pragma unroll
-    for (int q = 0; q < nv; ++q) vb[q] = Vbar[q * g.sc + c];
-  }
-  Mat<D, float> T = mzero<D, float>();
-  if (HASA) T = full_cotangent<D, float>(g, taubar, c);
-  Mat<D, float> bS, bR;
-  basis_reverse<D, float, HASA, HASV>(S, R, [&](int ib) {
-    Mat<D, float> M = T;
-    const float s = a[ib * g.sc + c];
-#pragma unroll
-    for (int p = 0; p < D; ++p)
-#pragma unroll
-      for (int q = 0; q < D; ++q) M.m[p][q] *= s;
-    return M; }, vb, bS, bR);
-  put_gradbar<D, float>(g, gb, c, bS, bR);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -195,15 +122,6 @@ __global__ __launch_bounds__(256) void k32_divoftensor_adjoint(GridDev g, const 
     }
 }
 
-int no_halo(const ins_grid* G, const char* what) {
-  for (int a = 0; a < G->g.D; ++a)
-    if (G->g.bc[a][0] == INS_BC_HALO || G->g.bc[a][1] == INS_BC_HALO) {
-      ins_set_error("%s: slab (halo) grids run in fp64 only", what);
-      return INS_ERR_UNSUPPORTED;
-    }
-  return INS_OK;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -214,7 +132,7 @@ extern "C" int ins_tensorinvariants_f32(const ins_grid_t* G, const float* u, flo
   int rc = no_halo(G, "tensorinvariants (f32)");
   if (rc) return rc;
   const GridDev& g = G->g;
-  INS_LAUNCH_D((k32_tc_invariants<D>), box_launch(g.D, g.ip_lo, g.ip_hi), as_stream(stream), g, u, V);
+  INS_LAUNCH_D((k_tc_invariants<D, float>), box_launch(g.D, g.ip_lo, g.ip_hi), as_stream(stream), g, u, V);
   return INS_OK;
 }
 
@@ -224,7 +142,7 @@ extern "C" int ins_tensorclosure_stress_f32(const ins_grid_t* G, const float* u,
   if (rc) return rc;
   INS_REQUIRE(tau != u && tau != a, "tensorclosure stress cannot run in place");
   const GridDev& g = G->g;
-  INS_LAUNCH_D((k32_tc_stress<D>), box_launch(g.D, g.ip_lo, g.ip_hi), as_stream(stream), g, u, a, tau);
+  INS_LAUNCH_D((k_tc_stress<D, float>), box_launch(g.D, g.ip_lo, g.ip_hi), as_stream(stream), g, u, a, tau);
   return INS_OK;
 }
 
@@ -242,14 +160,14 @@ extern "C" int ins_tensorclosure_pullback_f32(const ins_grid_t* G, const float* 
   double* gb64 = nullptr;
   if ((rc = ins_k_gradbar_scratch(G, &gb64))) return rc;
   float* gb = reinterpret_cast<float*>(gb64);
-  if (a) INS_LAUNCH_D((k32_tc_abar<D>), box_launch(g.D, g.N), s, g, u, taubar, abar);
+  if (a) INS_LAUNCH_D((k_tc_abar<D, float>), box_launch(g.D, g.N), s, g, u, taubar, abar);
   const Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
   if (a && Vbar)
-    INS_LAUNCH_D((k32_tc_gradbar<D, true, true>), l, s, g, u, a, taubar, Vbar, gb);
+    INS_LAUNCH_D((k_tc_gradbar<D, float, true, true>), l, s, g, u, a, taubar, Vbar, gb);
   else if (a)
-    INS_LAUNCH_D((k32_tc_gradbar<D, true, false>), l, s, g, u, a, taubar, Vbar, gb);
+    INS_LAUNCH_D((k_tc_gradbar<D, float, true, false>), l, s, g, u, a, taubar, Vbar, gb);
   else
-    INS_LAUNCH_D((k32_tc_gradbar<D, false, true>), l, s, g, u, a, taubar, Vbar, gb);
+    INS_LAUNCH_D((k_tc_gradbar<D, float, false, true>), l, s, g, u, a, taubar, Vbar, gb);
   if (accumulate)
     INS_LAUNCH_D((k32_gradu_adjoint<D, true>), box_launch(g.D, g.N), s, g, gb, ubar);
   else
