@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "ins_internal.h"
+#include "ins_rk_terms.h"
 
 bool ins_flux64_supported(const ins_grid* G);
 bool ins_k_spectral_own3d(const ins_poisson* ps);
@@ -550,6 +551,13 @@ extern "C" int ins_rk_create_f32(const ins_grid_t* G, ins_poisson32_t* ps, int n
   return INS_OK;
 }
 
+// The in-register correction runs: boxes the 64-wide stage kernel takes, on the fp64 solver's spectral passes
+static bool rk32_incorr(const ins_rk32* rk) {
+  const ins_grid* G = rk->grid;
+  return ins_flux64_supported(G) && rk->ps->ps64 && rk->nstage > 1 && G->uniform_exact && G->g.N[0] >= 8 && G->g.N[1] >= 8 && G->g.N[2] >= 8 &&
+         !ins_opt(OPT_INS_DISABLE_INKERNEL_CORR);
+}
+
 // timestep!(method, stepper, Δt; cache) for closure_model = temp = bodyforce = nothing, T = Float32       step_explicit_runge_kutta.jl:4-59
 // The caller's u is ustart for the whole step; on wide 3-D boxes the stage combination is the stencil kernel's epilogue.  As on the fp64 path (csrc/ins_rk.hip):
 //   * stage-velocity basis: with in-register correction the uncorrected stage velocities stay in memory anyway, so the combination is written in terms of them
@@ -572,14 +580,12 @@ static int rk32_step(ins_rk32* rk, float visc, float* u, float dt, hipStream_t s
   // Wide power-of-two boxes: the fp64 path's stage structure in float — stages >= 2 read the previous stage's UNCORRECTED u* and
   // its pressure and apply u = u* - ∇p in registers (CORR = 1), the solve forms Ω·div(u*) from the float field inside its x
   // pass; only the last stage materialises u (padded p, gradient-subtract, ghosts).
-  const bool incorr = wide && rk->ps->ps64 && ns > 1 && G->uniform_exact && G->g.N[0] >= 8 && G->g.N[1] >= 8 && G->g.N[2] >= 8 &&
-                      !ins_opt(OPT_INS_DISABLE_INKERNEL_CORR);
+  const bool incorr = wide && rk32_incorr(rk);  // wide: not on the general path (walls / stretched spacings)
   const long long ncell_in = (long long)(G->g.N[0] - 2) * (G->g.N[1] - 2) * (G->g.N[2] - 2);
   const bool own32 = rk->ps->own32;  // float2 spectra: the solver's float pI is what the next stage's stencil kernel reads
   if (incorr && !own32 && !rk->pu) INS_HIP_TRY(hipMalloc(&rk->pu, ncell_in * sizeof(float)));
   const float* pcorr = own32 ? rk->ps->pI : rk->pu;
-  bool vbasis = incorr && !ins_opt(OPT_INS_RK_KEEP_K);
-  for (int i = 0; vbasis && i < ns; ++i) vbasis = rk->A[i * ns + i] != 0.0;
+  const bool vbasis = incorr && !ins_opt(OPT_INS_RK_KEEP_K) && ins_rk_vbasis_possible(rk->A.data(), ns);
   if (chain && !(incorr && own32)) {
     ins_set_error("ins_rk_steps_f32: chained steps need the in-register correction on float2 spectra");
     return INS_ERR_UNSUPPORTED;
@@ -588,38 +594,10 @@ static int rk32_step(ins_rk32* rk, float visc, float* u, float dt, hipStream_t s
   for (int i = 0; i < ns; ++i) {
     float* outp = (i == ns - 1 && ns > 1) ? u : (vbasis ? rk->ku[i] : rk->ub[i & 1]);
     if (wide) {
-      RkEpi epi;
-      memset(&epi, 0, sizeof(epi));
-      if (vbasis) {
-        double beta[INS_MAX_STAGES];
-        for (int m = i - 1; m >= 0; --m) {  // β_i · A[0:i,0:i] = A[i,0:i], A lower triangular
-          double v = rk->A[i * ns + m];
-          for (int j = m + 1; j < i; ++j) v -= beta[j] * rk->A[j * ns + m];
-          beta[m] = v / rk->A[m * ns + m];
-        }
-        for (int m = 0; m < i; ++m) {
-          if (beta[m] == 0.0) continue;
-          epi.c0m1 -= beta[m];
-          if (m == i - 1) {  // V_{i-1} is this stage's stencil input
-            epi.self_in = beta[m];
-            continue;
-          }
-          epi.coef[epi.n] = beta[m];
-          epi.k[epi.n] = reinterpret_cast<const double*>(rk->ku[m]);  // float arrays behind RkEpi's untyped pointers (the kernels cast back)
-          ++epi.n;
-        }
-      } else {
-        for (int j = 0; j < i; ++j) {
-          const double coef = (double)dt * rk->A[i * ns + j];
-          if (coef == 0.0) continue;
-          epi.coef[epi.n] = coef;
-          epi.k[epi.n] = reinterpret_cast<const double*>(rk->ku[j]);
-          ++epi.n;
-        }
-        for (int i2 = i + 1; i2 < ns; ++i2)
-          if (rk->A[i2 * ns + i] != 0.0) epi.write_k = 1;
-      }
-      epi.coef_self = (double)dt * rk->A[i * ns + i];
+      // the V_m live in the ku arrays (float arrays behind RkEpi's untyped pointers: the kernels cast back); V_{i-1} is this stage's stencil input and the
+      // kernel always has its uncorrected value in registers
+      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, (double)dt, rk->ku.data(), (const float*)nullptr, vbasis ? RK_V_BASIS : RK_K_BASIS, true,
+                                     RK_FORCE_DIAG_FIRST);
       epi.ustart = i == 0 ? nullptr : reinterpret_cast<const double*>(raw_in ? rk->ustart : u);
       epi.ustar = reinterpret_cast<double*>(outp);
       if (i == 0 && raw_in) epi.ustart_out = reinterpret_cast<double*>(rk->ustart);
@@ -628,14 +606,7 @@ static int rk32_step(ins_rk32* rk, float visc, float* u, float dt, hipStream_t s
     } else {
       if ((rc = ins_momentum_f32(G, visc, cur, rk->ku[i], s))) return rc;       // :21
       Comb32 cb;
-      cb.n = 0;
-      for (int j = 0; j <= i; ++j) {
-        const float coef = dt * (float)rk->A[i * ns + j];
-        if (coef == 0.f) continue;
-        cb.coef[cb.n] = coef;
-        cb.k[cb.n] = rk->ku[j];
-        ++cb.n;
-      }
+      cb.n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), (const float*)nullptr, cb.coef, cb.k);  // Δt (float)A[i,j], in float
       hipLaunchKernelGGL(k32_combine, dim3((unsigned)std::min<long long>((nvec + 255) / 256, 8192)), dim3(256), 0, s, nvec, u, outp, cb);  // :35-38
       INS_LAUNCH_CHECK();
       if (general && (rc = ins_k32g_apply_bc_u(G, outp, s))) return rc;          // :47
@@ -669,10 +640,9 @@ extern "C" int ins_rk_steps_f32(ins_rk32_t* rk, float visc, float* u, float dt, 
   INS_REQUIRE(rk && u && nsteps >= 0, "bad argument");
   const ins_grid* G = rk->grid;
   hipStream_t s = as_stream(stream);
-  const int ns = rk->nstage;
-  bool ok = ins_flux64_supported(G) && rk->ps->ps64 && rk->ps->own32 && ns > 1 && G->uniform_exact && G->g.N[0] >= 8 && G->g.N[1] >= 8 && G->g.N[2] >= 8 &&
-            !ins_opt(OPT_INS_DISABLE_INKERNEL_CORR) && !ins_opt(OPT_INS_DISABLE_STEP_CHAIN) && !ins_opt(OPT_INS_RK_KEEP_K);
-  for (int i = 0; ok && i < ns; ++i) ok = rk->A[i * ns + i] != 0.0;
+  // the chain needs the solver's float pI (float2 spectra) and the stage-velocity basis
+  const bool ok = rk32_incorr(rk) && rk->ps->own32 && !ins_opt(OPT_INS_DISABLE_STEP_CHAIN) && !ins_opt(OPT_INS_RK_KEEP_K) &&
+                  ins_rk_vbasis_possible(rk->A.data(), rk->nstage);
   if (!ok || nsteps < 2) {
     for (int n = 0; n < nsteps; ++n) {
       int rc = rk32_step(rk, visc, u, dt, s, 0);

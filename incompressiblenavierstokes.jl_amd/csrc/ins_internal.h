@@ -377,6 +377,35 @@ int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const 
 bool ins_flux64_stage_rhs_supported(const ins_grid* G, int corr_mode);  // the stage kernel of this box can write that right-hand side (ins_flux64.hip)
 double* ins_poisson_stage_rhs(ins_poisson* ps);                        // its buffer (nullptr: no own-FFT 3-D route, or out of memory)
 int ins_k_poisson_solve(ins_poisson* ps, double* p, hipStream_t s);
+bool ins_fast3d_supported(const ins_grid* G);
+
+// Which stage loop an integrator runs (ins_rk.hip, ins_rk_ext.hip).  Each is the whole condition; what only one caller asks in addition (time-dependent
+// boundary planes, a body force, the closure / temperature state, the solver's own FFT passes) stands at that caller.
+// fused periodic 3-D loop (rk_step_fused_periodic)
+static inline bool ins_rk_fused3d(const ins_rk* rk) {
+  const ins_grid* G = rk->grid;
+  bool ok = !ins_opt(OPT_INS_DISABLE_FUSED_RK) && G->g.D == 3 && G->all_periodic && G->all_dof && rk->ps->kind == POISSON_SPECTRAL && ins_fast3d_supported(G);
+  for (int a = 0; ok && a < 3; ++a) ok = rk->ps->np[a] >= 2;
+  return ok;
+}
+// fused periodic 2-D loop (rk_step_fused_periodic_2d); both conditions imply a periodic box on the spectral solver
+static inline bool ins_rk_fused2d(const ins_rk* rk) {
+  return !ins_opt(OPT_INS_DISABLE_FUSED_RK) && rk->grid->g.D == 2 && ins_poisson_own2d(rk->ps) && ins_flux2d_supported(rk->grid);
+}
+// on those loops: stages >= 2 read the previous stage's uncorrected u* and its pressure and correct in registers
+static inline bool ins_rk_inkernel3d(const ins_rk* rk) {
+  const ins_grid* G = rk->grid;
+  return !ins_opt(OPT_INS_DISABLE_INKERNEL_CORR) && G->uniform_exact && rk->nstage > 1 && G->g.N[0] >= 8 && G->g.N[1] >= 8 && G->g.N[2] >= 8;
+}
+static inline bool ins_rk_inkernel2d(const ins_rk* rk) {
+  return rk->nstage > 1 && !ins_opt(OPT_INS_DISABLE_INKERNEL_CORR) && !ins_opt(OPT_INS_DISABLE_CORR2D) && rk->grid->g.N[0] >= 6 && rk->grid->g.N[1] >= 6;
+}
+// consecutive steps can hand their last correction to the next step's first stage kernel (ins_rk_steps_f64)
+static inline bool ins_rk_chainable(const ins_rk* rk) {
+  return !ins_opt(OPT_INS_DISABLE_STEP_CHAIN) && ((ins_rk_fused3d(rk) && ins_rk_inkernel3d(rk)) || (ins_rk_fused2d(rk) && ins_rk_inkernel2d(rk)));
+}
+// rk->ub[0..1], allocated on first use: zeroed (init_from == nullptr, periodic loops) or a copy of init_from (tiled loops)   (ins_rk.hip)
+int ins_rk_ensure_ub(ins_rk* rk, size_t bytes, hipStream_t s, const double* init_from);
 // blocking reductions over an index box of a scalar field; op: 0 sum(a*b), 1 max|a|, 2 min(a)
 int ins_k_reduce(const ins_grid* grid, int op, const double* a, const double* b, const int lo[3], const int hi[3], double* out,
                  hipStream_t s);

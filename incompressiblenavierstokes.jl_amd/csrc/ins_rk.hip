@@ -3,12 +3,11 @@
 #include <cstdlib>
 
 #include "ins_internal.h"
-
+#include "ins_rk_terms.h"
 
 int ins_k_momentum_generic(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s);
 int ins_k_momentum_fast3d(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s);
 int ins_k_momentum_fast3d_opts(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
-bool ins_fast3d_supported(const ins_grid* G);
 bool ins_flux64_supported(const ins_grid* G);
 
 int ins_k_momentum_rk_fused(const ins_grid* G, double visc, const double* u_in, double* k_out, const RkEpi& epi, hipStream_t s);
@@ -196,6 +195,40 @@ extern "C" int ins_dbg_stage_rhs(ins_rk_t* rk, double visc, const double* u_in, 
   return INS_OK;
 }
 
+// Test hook (tests/test_rk_stage_terms.py; needs no device): the builders of ins_rk_terms.h on the caller's tableau.  kind 0 / 1: ins_rk_stage_terms in
+// the k-basis / the stage-velocity basis (order 0: force sum diagonal first, 1: index order); kind 2 / 3: ins_rk_sum_terms in double / float.
+// stage[q], coef[q] (room for INS_MAX_STAGES + 1): earlier stage and coefficient of term q; the force term reports stage ns and its coefficient also in
+// *coef_force (0 without a force).
+extern "C" int ins_dbg_rk_stage_terms(int32_t ns, const double* A, int32_t i, double dt, int32_t kind, int32_t input_in_regs, int32_t with_force, int32_t order,
+                                      int32_t* n, int32_t* stage, double* coef, double* c0m1, double* self_in, double* coef_self, int32_t* write_k,
+                                      double* coef_force) {
+  INS_REQUIRE(A && n && stage && coef && c0m1 && self_in && coef_self && write_k && coef_force, "null argument");
+  INS_REQUIRE(ns >= 1 && ns <= INS_MAX_STAGES && i >= 0 && i < ns && kind >= 0 && kind <= 3, "bad argument");
+  INS_REQUIRE(kind != 1 || ins_rk_vbasis_possible(A, ns), "the stage-velocity basis needs a non-zero diagonal");
+  static double slot[INS_MAX_STAGES + 1];  // stands for the stage arrays: term q's stage is k[q] - slot
+  double* prev[INS_MAX_STAGES];
+  for (int m = 0; m < ns; ++m) prev[m] = slot + m;
+  const double* force = with_force ? slot + ns : nullptr;
+  RkEpi epi;
+  memset(&epi, 0, sizeof(epi));
+  if (kind <= 1) {
+    epi = ins_rk_stage_terms(A, ns, i, dt, prev, force, kind ? RK_V_BASIS : RK_K_BASIS, input_in_regs != 0, order ? RK_FORCE_INDEX_ORDER : RK_FORCE_DIAG_FIRST);
+  } else if (kind == 2) {
+    epi.n = ins_rk_sum_terms(A, ns, i, dt, prev, force, epi.coef, epi.k);
+  } else {
+    float cf32[INS_MAX_STAGES + 1];
+    epi.n = ins_rk_sum_terms(A, ns, i, (float)dt, prev, force, cf32, epi.k);
+    for (int q = 0; q < epi.n; ++q) epi.coef[q] = cf32[q];
+  }
+  *n = epi.n, *c0m1 = epi.c0m1, *self_in = epi.self_in, *coef_self = epi.coef_self, *write_k = epi.write_k, *coef_force = 0.0;
+  for (int q = 0; q < epi.n; ++q) {
+    stage[q] = (int32_t)(epi.k[q] - slot);
+    coef[q] = epi.coef[q];
+    if (epi.k[q] == force) *coef_force = epi.coef[q];
+  }
+  return INS_OK;
+}
+
 extern "C" int ins_rk_set_bodyforce(ins_rk_t* rk, const double* force) {
   INS_REQUIRE(rk, "null argument");
   rk->force = force;
@@ -206,6 +239,36 @@ extern "C" int ins_rk_stage_force(const ins_rk_t* rk, int i, double** ku) {
   INS_REQUIRE(rk && ku, "null argument");
   INS_REQUIRE(i >= 0 && i < rk->nstage, "stage index out of range");
   *ku = rk->ku[i];
+  return INS_OK;
+}
+
+// rk->profiling: an event pair on the stream around the stage kernel that `launch` enqueues (ins_rk_profile_read); kept only when the launch succeeded
+template <typename F>
+static int timed_stage(ins_rk* rk, hipStream_t s, F&& launch) {
+  if (!rk->profiling) return launch();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  INS_HIP_TRY(hipEventCreate(&e0));
+  INS_HIP_TRY(hipEventCreate(&e1));
+  INS_HIP_TRY(hipEventRecord(e0, s));
+  const int rc = launch();
+  if (rc) return rc;
+  INS_HIP_TRY(hipEventRecord(e1, s));
+  rk->prof_events.push_back(e0);
+  rk->prof_events.push_back(e1);
+  return INS_OK;
+}
+
+// The two ping-pong stage buffers, allocated on first use.  The periodic loops zero them (init_from == nullptr); the tiled loops copy the caller's
+// field into them once: volumes no kernel ever writes.
+int ins_rk_ensure_ub(ins_rk* rk, size_t bytes, hipStream_t s, const double* init_from) {
+  for (int b = 0; b < 2; ++b)
+    if (!rk->ub[b]) {
+      INS_HIP_TRY(hipMalloc(&rk->ub[b], bytes));
+      if (init_from)
+        INS_HIP_TRY(hipMemcpyAsync(rk->ub[b], init_from, bytes, hipMemcpyDeviceToDevice, s));
+      else
+        INS_HIP_TRY(hipMemsetAsync(rk->ub[b], 0, bytes, s));
+    }
   return INS_OK;
 }
 
@@ -222,27 +285,16 @@ static int rk_step_fused_periodic(ins_rk* rk, double visc, double* u, double dt,
   const ins_grid* G = rk->grid;
   const int ns = rk->nstage;
   const size_t vbytes = (size_t)G->ncell * 3 * sizeof(double);
-  for (int b = 0; b < 2; ++b)
-    if (!rk->ub[b]) {
-      INS_HIP_TRY(hipMalloc(&rk->ub[b], vbytes));
-      INS_HIP_TRY(hipMemsetAsync(rk->ub[b], 0, vbytes, s));
-    }
   int rc;
+  if ((rc = ins_rk_ensure_ub(rk, vbytes, s, nullptr))) return rc;
   const bool raw_in = chain & 1, raw_out = chain & 2;
   if (!raw_in && (rc = ins_k_apply_bc_u(G, u, 0, nullptr, s))) return rc;  // :19 (first stage; later ghosts come from K4)
   // On exactly-uniform grids stages >= 2 read the previous stage's UNCORRECTED u* plus its pressure and apply
   // the projection's gradient-subtract in registers (k_momentum_flux<..., CORR>), so K4 runs for the last stage only.
-  const bool no_corr = ins_opt(OPT_INS_DISABLE_INKERNEL_CORR) != 0;
-  const bool inkernel = !no_corr && G->uniform_exact && ns > 1 && G->g.N[0] >= 8 && G->g.N[1] >= 8 && G->g.N[2] >= 8;
-  // Stage-velocity basis.  With in-kernel correction the UNCORRECTED stage velocities V_m = ustart + Δt Σ_{j<=m} A[m,j] k_j stay in
-  // memory anyway (they are the next stencil's input), and when every A[m,m] != 0 they span the same space as {ustart, k_j}:
-  //   V_i = (1 - Σ_m β_im) ustart + Σ_{m<i} β_im V_m + Δt A[i,i] k_i,     β_i · A[0:i,0:i] = A[i,0:i].
-  // So no k_j is ever written or read: RK44 moves 336 instead of 432 B per cell and step through the stage kernels (β_3 = (1/3, 2/3, 1/3),
-  // all other β = 0).  Algebraically the reference's combination (step_explicit_runge_kutta.jl:35-38); rounding differs at the 1e-16 level.
-  // INS_RK_KEEP_K=1 restores the k-basis (and fills the ku cache arrays, which this basis leaves untouched).
-  const bool keep_k = ins_opt(OPT_INS_RK_KEEP_K) != 0;
-  bool vbasis = inkernel && !keep_k;
-  for (int i = 0; vbasis && i < ns; ++i) vbasis = rk->A[i * ns + i] != 0.0;
+  const bool inkernel = ins_rk_inkernel3d(rk);
+  // Stage-velocity basis (ins_rk_terms.h): with the in-kernel correction no k_j is written or read.  INS_RK_KEEP_K=1 restores the k-basis (and fills the
+  // ku cache arrays, which this basis leaves untouched).
+  const bool vbasis = inkernel && !ins_opt(OPT_INS_RK_KEEP_K) && ins_rk_vbasis_possible(rk->A.data(), ns);
   if (vbasis && (int)rk->vb.size() < ns - 1) {
     rk->vb.resize(ns - 1, nullptr);
     for (int m = 0; m < ns - 1; ++m)
@@ -258,47 +310,9 @@ static int rk_step_fused_periodic(ins_rk* rk, double visc, double* u, double dt,
   const double* in = u;
   for (int i = 0; i < ns; ++i) {
     double* out = (i == ns - 1 && ns > 1) ? u : (vbasis ? rk->vb[i] : rk->ub[i & 1]);
-    RkEpi epi;
-    memset(&epi, 0, sizeof(epi));
-    if (vbasis) {
-      double beta[INS_MAX_STAGES];
-      for (int m = i - 1; m >= 0; --m) {  // β_i · A[0:i,0:i] = A[i,0:i], A lower triangular
-        double v = rk->A[i * ns + m];
-        for (int j = m + 1; j < i; ++j) v -= beta[j] * rk->A[j * ns + m];
-        beta[m] = v / rk->A[m * ns + m];
-      }
-      const bool flux64 = ins_flux64_supported(G);  // the 62-wide kernel has no register copy of the uncorrected input
-      for (int m = 0; m < i; ++m) {
-        if (beta[m] == 0.0) continue;
-        epi.c0m1 -= beta[m];
-        if (m == i - 1 && flux64) {  // V_{i-1} is this stage's stencil input
-          epi.self_in = beta[m];
-          continue;
-        }
-        epi.coef[epi.n] = beta[m];
-        epi.k[epi.n] = rk->vb[m];
-        ++epi.n;
-      }
-    } else {
-      for (int j = 0; j < i; ++j) {
-        const double coef = dt * rk->A[i * ns + j];
-        if (coef == 0.0) continue;
-        epi.coef[epi.n] = coef;
-        epi.k[epi.n] = rk->ku[j];
-        ++epi.n;
-      }
-      for (int i2 = i + 1; i2 < ns; ++i2)
-        if (rk->A[i2 * ns + i] != 0.0) epi.write_k = 1;
-    }
-    if (rk->force) {  // steady body force (operators.jl:873-880): k_j = F_j + f, so f enters with Δt A[i,i] in the stage-velocity basis
-      double cf = dt * rk->A[i * ns + i];  // (the V_m already hold their share) and with Δt Σ_{j<=i} A[i,j] in the k-basis (ku[j] = F_j)
-      if (!vbasis)
-        for (int j = 0; j < i; ++j) cf += dt * rk->A[i * ns + j];
-      epi.coef[epi.n] = cf;
-      epi.k[epi.n] = rk->force;
-      ++epi.n;
-    }
-    epi.coef_self = dt * rk->A[i * ns + i];
+    // the V_m live in rk->vb; V_{i-1}, the stencil input, comes from registers on the 64-wide kernel only (the 62-wide one keeps no uncorrected copy)
+    RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, vbasis ? rk->vb.data() : rk->ku.data(), rk->force, vbasis ? RK_V_BASIS : RK_K_BASIS,
+                                   vbasis && ins_flux64_supported(G), RK_FORCE_DIAG_FIRST);
     epi.ustart = (i == 0) ? nullptr : (raw_in ? rk->ustart : u);  // raw_in: the corrected start field lives in the cache array
     epi.ustar = out;
     if (i == 0 && raw_in) epi.ustart_out = rk->ustart;
@@ -309,20 +323,10 @@ static int rk_step_fused_periodic(ins_rk* rk, double visc, double* u, double dt,
     const bool corr = inkernel && (i > 0 || raw_in);
     if (!ins_stage_out_aliases_input(epi, in) && ins_flux64_stage_rhs_supported(G, corr ? 1 : 0) && (epi.rhs_out = ins_poisson_stage_rhs(rk->ps)))
       ++rk->stage_rhs_launches;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (rk->profiling) {
-      INS_HIP_TRY(hipEventCreate(&e0));
-      INS_HIP_TRY(hipEventCreate(&e1));
-      INS_HIP_TRY(hipEventRecord(e0, s));
-    }
-    rc = corr ? ins_k_momentum_rk_fused_corr(G, visc, in, rk->ps->pI, rk->ku[i], epi, s)
-              : ins_k_momentum_rk_fused(G, visc, in, rk->ku[i], epi, s);
+    rc = timed_stage(rk, s, [&] {
+      return corr ? ins_k_momentum_rk_fused_corr(G, visc, in, rk->ps->pI, rk->ku[i], epi, s) : ins_k_momentum_rk_fused(G, visc, in, rk->ku[i], epi, s);
+    });
     if (rc) return rc;
-    if (rk->profiling) {
-      INS_HIP_TRY(hipEventRecord(e1, s));
-      rk->prof_events.push_back(e0);
-      rk->prof_events.push_back(e1);
-    }
     rc = (inkernel && (i < ns - 1 || raw_out)) ? ins_k_project_periodic_solve_only(G, rk->ps, out, s, epi.rhs_out)
                                                : ins_k_project_periodic_fused(G, rk->ps, out, rk->p, i == ns - 1, s, nullptr, epi.rhs_out);
     if (rc) return rc;
@@ -340,15 +344,11 @@ static int rk_step_fused_periodic_2d(ins_rk* rk, double visc, double* u, double 
   const ins_grid* G = rk->grid;
   const int ns = rk->nstage;
   const size_t vbytes = (size_t)G->ncell * 2 * sizeof(double);
-  for (int b = 0; b < 2; ++b)
-    if (!rk->ub[b]) {
-      INS_HIP_TRY(hipMalloc(&rk->ub[b], vbytes));
-      INS_HIP_TRY(hipMemsetAsync(rk->ub[b], 0, vbytes, s));
-    }
   int rc;
+  if ((rc = ins_rk_ensure_ub(rk, vbytes, s, nullptr))) return rc;
   const bool raw_in = chain & 1, raw_out = chain & 2;
   if (!raw_in && (rc = ins_k_apply_bc_u(G, u, 0, nullptr, s))) return rc;  // :19 (first stage; later ghosts come with the gradient-subtract)
-  const bool incorr = ns > 1 && !ins_opt(OPT_INS_DISABLE_INKERNEL_CORR) && !ins_opt(OPT_INS_DISABLE_CORR2D) && G->g.N[0] >= 6 && G->g.N[1] >= 6;
+  const bool incorr = ins_rk_inkernel2d(rk);
   if (chain && !incorr) {
     ins_set_error("chained 2-D steps need the in-register correction");
     return INS_ERR_INVALID;
@@ -356,42 +356,14 @@ static int rk_step_fused_periodic_2d(ins_rk* rk, double visc, double* u, double 
   const double* in = u;
   for (int i = 0; i < ns; ++i) {
     double* out = (i == ns - 1 && ns > 1) ? u : rk->ub[i & 1];
-    RkEpi epi;
-    memset(&epi, 0, sizeof(epi));
-    for (int j = 0; j < i; ++j) {
-      const double coef = dt * rk->A[i * ns + j];
-      if (coef == 0.0) continue;
-      epi.coef[epi.n] = coef;
-      epi.k[epi.n] = rk->ku[j];
-      ++epi.n;
-    }
-    if (rk->force) {
-      double cf = 0.0;
-      for (int j = 0; j <= i; ++j) cf += dt * rk->A[i * ns + j];
-      epi.coef[epi.n] = cf;
-      epi.k[epi.n] = rk->force;
-      ++epi.n;
-    }
-    for (int i2 = i + 1; i2 < ns; ++i2)
-      if (rk->A[i2 * ns + i] != 0.0) epi.write_k = 1;
-    epi.coef_self = dt * rk->A[i * ns + i];
+    RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, RK_K_BASIS, false, RK_FORCE_INDEX_ORDER);  // k-basis only
     epi.ustart = (i == 0) ? nullptr : (raw_in ? rk->ustart : u);  // raw_in: the corrected start field lives in the cache array
     epi.ustar = out;
     if (i == 0 && raw_in) epi.ustart_out = rk->ustart;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (rk->profiling) {
-      INS_HIP_TRY(hipEventCreate(&e0));
-      INS_HIP_TRY(hipEventCreate(&e1));
-      INS_HIP_TRY(hipEventRecord(e0, s));
-    }
     // stages >= 2 read the previous stage's UNCORRECTED u* and its pressure and correct in registers (k_flux2d<…, CORR>): between two stages the projection
     // only solves (three launches instead of four, 48 B per volume less); the last stage's projection materialises u, p and their ghosts
-    if ((rc = ins_k_flux2d(G, visc, in, rk->ku[i], &epi, s, (incorr && (i > 0 || raw_in)) ? rk->ps->pI : nullptr))) return rc;
-    if (rk->profiling) {
-      INS_HIP_TRY(hipEventRecord(e1, s));
-      rk->prof_events.push_back(e0);
-      rk->prof_events.push_back(e1);
-    }
+    rc = timed_stage(rk, s, [&] { return ins_k_flux2d(G, visc, in, rk->ku[i], &epi, s, (incorr && (i > 0 || raw_in)) ? rk->ps->pI : nullptr); });
+    if (rc) return rc;
     rc = (incorr && (i < ns - 1 || raw_out)) ? ins_k_project_periodic_solve_only_2d(G, rk->ps, out, s) : ins_k_project_periodic_fused_2d(G, rk->ps, out, rk->p, i == ns - 1, s);
     if (rc) return rc;
     in = out;
@@ -444,14 +416,8 @@ extern "C" long long ins_dbg_rk_graph_replays(const ins_rk_t* rk) { return (rk &
 static int step_graph_kind(const ins_rk* rk, bool chain_ok) {
   const ins_grid* G = rk->grid;
   if (!ins_opt(OPT_INS_STEP_GRAPH) || ins_opt(OPT_INS_DISABLE_STEP_GRAPH) || rk->profiling || rk->ext) return 0;
-  if (ins_opt(OPT_INS_DISABLE_FUSED_RK) || !G->all_periodic || rk->ps->kind != POISSON_SPECTRAL) return 0;
-  if (G->g.D == 3) {
-    if (!(G->all_dof && ins_fast3d_supported(G) && ins_k_spectral_own3d(rk->ps))) return 0;
-    for (int a = 0; a < 3; ++a)
-      if (rk->ps->np[a] < 2) return 0;
-    return chain_ok ? 1 : 2;
-  }
-  return (ins_poisson_own2d(rk->ps) && ins_flux2d_supported(G)) ? (chain_ok ? 1 : 2) : 0;
+  const bool own = G->g.D == 3 ? ins_rk_fused3d(rk) && ins_k_spectral_own3d(rk->ps) : ins_rk_fused2d(rk);
+  return own ? (chain_ok ? 1 : 2) : 0;
 }
 
 // one step of the chained loop (3-D or 2-D fused periodic path)
@@ -492,15 +458,11 @@ extern "C" int ins_rk_steps_f64(ins_rk_t* rk, double visc, double* u, double t, 
   INS_REQUIRE(rk && u && nsteps >= 0, "bad argument");
   const ins_grid* G = rk->grid;
   hipStream_t s = as_stream(stream);
-  const GridDev& g = G->g;
-  const bool no_fuse = ins_opt(OPT_INS_DISABLE_FUSED_RK) != 0, no_corr = ins_opt(OPT_INS_DISABLE_INKERNEL_CORR) != 0,
-             no_chain = ins_opt(OPT_INS_DISABLE_STEP_CHAIN) != 0;
-  // (boxes too narrow for the 64-wide stage kernel chain on the 62-wide one: it stores the corrected start field too — round 3)
-  bool ok = !no_fuse && !no_corr && !no_chain && !rk->force && g.D == 3 && G->all_periodic && G->all_dof && rk->ps->kind == POISSON_SPECTRAL && ins_fast3d_supported(G) &&
-            G->uniform_exact && rk->nstage > 1 && g.N[0] >= 8 && g.N[1] >= 8 && g.N[2] >= 8;  // = in-kernel correction runs
-  const bool ok2d = !no_fuse && !no_corr && !no_chain && !ins_opt(OPT_INS_DISABLE_CORR2D) && !rk->force && !rk->ext && g.D == 2 && rk->ps->kind == POISSON_SPECTRAL &&
-                    ins_poisson_own2d(rk->ps) && ins_flux2d_supported(G) && rk->nstage > 1 && g.N[0] >= 6 && g.N[1] >= 6;
-  const int gkind = step_graph_kind(rk, (ok || ok2d) && nsteps >= 2);
+  // The in-kernel correction runs on the fused periodic loop of this box (boxes too narrow for the 64-wide stage kernel chain on the 62-wide one: it
+  // stores the corrected start field too); a body force takes single steps.  rk->ext: this entry point never runs the extended loop, and its 2-D
+  // condition has always turned an integrator with closure / temperature state away while the 3-D one never looked — both kept as they were.
+  const bool chain = ins_rk_chainable(rk) && !rk->force && !(G->g.D == 2 && rk->ext);
+  const int gkind = step_graph_kind(rk, chain && nsteps >= 2);
   if (gkind && nsteps >= 3) {
     StepGraph* sg = static_cast<StepGraph*>(rk->step_graph);
     if (!sg) rk->step_graph = sg = new StepGraph();
@@ -536,22 +498,16 @@ extern "C" int ins_rk_steps_f64(ins_rk_t* rk, double visc, double* u, double t, 
     }
     return INS_OK;
   }
-  if (ok2d && nsteps >= 2) {  // 2-D fused path: the same chain (the final gradient-subtract / ghost pass of every step but the last goes into the next step's first stage kernel)
-    for (int n = 0; n < nsteps; ++n) {
-      int rc = chain_step(rk, visc, u, dt, s, (n > 0 ? 1 : 0) | (n < nsteps - 1 ? 2 : 0));
-      if (rc) return rc;
-    }
-    return INS_OK;
-  }
-  if (!ok || nsteps < 2) {
+  if (!chain || nsteps < 2) {
     for (int n = 0; n < nsteps; ++n) {
       int rc = ins_rk_step_f64(rk, visc, u, t + n * dt, dt, nullptr, stream);
       if (rc) return rc;
     }
     return INS_OK;
   }
+  // the final gradient-subtract / ghost pass of every step but the last goes into the next step's first stage kernel
   for (int n = 0; n < nsteps; ++n) {
-    int rc = rk_step_fused_periodic(rk, visc, u, dt, s, (n > 0 ? 1 : 0) | (n < nsteps - 1 ? 2 : 0));
+    int rc = chain_step(rk, visc, u, dt, s, (n > 0 ? 1 : 0) | (n < nsteps - 1 ? 2 : 0));
     if (rc) return rc;
   }
   return INS_OK;
@@ -564,14 +520,8 @@ static int rk_step_any(ins_rk_t* rk, double visc, double* u, double dt, const do
   INS_REQUIRE(rk && u, "null argument");
   const ins_grid* G = rk->grid;
   hipStream_t s = as_stream(stream);
-  {
-    const bool no_fuse = ins_opt(OPT_INS_DISABLE_FUSED_RK) != 0;
-    const GridDev& g = G->g;
-    bool ok = !no_fuse && !planes && g.D == 3 && G->all_periodic && G->all_dof && rk->ps->kind == POISSON_SPECTRAL && ins_fast3d_supported(G);
-    for (int a = 0; ok && a < 3; ++a) ok = rk->ps->np[a] >= 2;
-    if (ok) return rk_step_fused_periodic(rk, visc, u, dt, s);
-    if (!no_fuse && !planes && g.D == 2 && ins_poisson_own2d(rk->ps) && ins_flux2d_supported(G)) return rk_step_fused_periodic_2d(rk, visc, u, dt, s);
-  }
+  if (!planes && ins_rk_fused3d(rk)) return rk_step_fused_periodic(rk, visc, u, dt, s);
+  if (!planes && ins_rk_fused2d(rk)) return rk_step_fused_periodic_2d(rk, visc, u, dt, s);
   const long long nvec = G->ncell * G->g.D;
   const double** dplanes = nullptr;
   struct Guard {
@@ -595,82 +545,31 @@ static int rk_step_any(ins_rk_t* rk, double visc, double* u, double dt, const do
   const bool tiled = ins_fast3d_supported(G);  // else: the generic kernel with the same epilogue (2-D grids, tiny boxes)
   if (!no_fuse_np && !planes) {
     const size_t vbytes = (size_t)nvec * sizeof(double);
-    for (int b = 0; b < 2; ++b)
-      if (!rk->ub[b]) {
-        INS_HIP_TRY(hipMalloc(&rk->ub[b], vbytes));
-        INS_HIP_TRY(hipMemcpyAsync(rk->ub[b], u, vbytes, hipMemcpyDeviceToDevice, s));  // once: volumes no kernel ever writes
-      }
+    if ((rc = ins_rk_ensure_ub(rk, vbytes, s, u))) return rc;
     // Masked grids with Periodic / Dirichlet sides and the direct solver: stages >= 2 read the previous stage's UNCORRECTED u* and its
     // pressure and apply `u = u* - ∇p` in registers on the degrees of freedom (CORR = 3 of the 62-wide stage kernel), so between two
     // stages the projection only solves for p: no gradient-subtract pass over u, no second ghost fill.  Same arithmetic per volume as
     // project! + apply_bc_u! (boundary data is time-independent on this entry point); INS_DISABLE_INKERNEL_CORR restores them.
     const bool incorr = tiled && ns > 1 && !ins_opt(OPT_INS_DISABLE_INKERNEL_CORR) && ins_corr3_supported(G) && ins_k_project_fdm_fused(rk->ps);
-    // Stage-velocity basis, as on the periodic path (rk_step_fused_periodic): with the in-kernel correction the uncorrected stage velocities
-    // V_m (boundary data applied) stay in memory as the next stencil's input, so the stage combination is written in terms of them and no
-    // k_j is stored or read (RK44: 360 instead of 432 B per cell and step through the stage kernels; on volumes that are no DOF every term
-    // holds the same boundary value and the weights sum to one).  The ku arrays serve as the V_m buffers; INS_RK_KEEP_K=1 restores the k-basis.
-    bool vbasis = incorr && !ins_opt(OPT_INS_RK_KEEP_K);
-    for (int i = 0; vbasis && i < ns; ++i) vbasis = rk->A[i * ns + i] != 0.0;
+    // Stage-velocity basis (ins_rk_terms.h), as on the periodic path: with the in-kernel correction the uncorrected stage velocities V_m (boundary data
+    // applied) stay in memory as the next stencil's input (on volumes that are no DOF every term holds the same boundary value and the weights sum to
+    // one).  INS_RK_KEEP_K=1 restores the k-basis.
+    const bool vbasis = incorr && !ins_opt(OPT_INS_RK_KEEP_K) && ins_rk_vbasis_possible(rk->A.data(), ns);
     double* cur = u;
     for (int i = 0; i < ns; ++i) {
       const bool corr_in = incorr && i > 0;
       if (!corr_in && (rc = ins_k_apply_bc_u(G, cur, 0, nullptr, s))) return rc;  // :19 (corr_in: `cur` got its boundary data at :48 already)
       double* out = (i == ns - 1 && ns > 1) ? u : (vbasis ? rk->ku[i] : rk->ub[i & 1]);
-      RkEpi epi;
-      memset(&epi, 0, sizeof(epi));
-      if (vbasis) {
-        double beta[INS_MAX_STAGES];
-        for (int m = i - 1; m >= 0; --m) {  // β_i · A[0:i,0:i] = A[i,0:i], A lower triangular
-          double v = rk->A[i * ns + m];
-          for (int j = m + 1; j < i; ++j) v -= beta[j] * rk->A[j * ns + m];
-          beta[m] = v / rk->A[m * ns + m];
-        }
-        for (int m = 0; m < i; ++m) {
-          if (beta[m] == 0.0) continue;
-          epi.c0m1 -= beta[m];
-          epi.coef[epi.n] = beta[m];
-          epi.k[epi.n] = rk->ku[m];
-          ++epi.n;
-        }
-      } else {
-        for (int j = 0; j < i; ++j) {
-          const double coef = dt * rk->A[i * ns + j];
-          if (coef == 0.0) continue;
-          epi.coef[epi.n] = coef;
-          epi.k[epi.n] = rk->ku[j];
-          ++epi.n;
-        }
-        for (int i2 = i + 1; i2 < ns; ++i2)
-          if (rk->A[i2 * ns + i] != 0.0) epi.write_k = 1;
-      }
-      if (rk->force) {  // k_j = F_j + f: the V_m already hold their share of f (stage-velocity basis)
-        double cf = dt * rk->A[i * ns + i];
-        if (!vbasis)
-          for (int j = 0; j < i; ++j) cf += dt * rk->A[i * ns + j];
-        epi.coef[epi.n] = cf;
-        epi.k[epi.n] = rk->force;
-        ++epi.n;
-      }
-      epi.coef_self = dt * rk->A[i * ns + i];
+      // the V_m live in the ku arrays; the tiled kernels read V_{i-1} from memory like every other term (no self_in)
+      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, vbasis ? RK_V_BASIS : RK_K_BASIS, false, RK_FORCE_DIAG_FIRST);
       epi.ustart = (i == 0) ? nullptr : u;
       epi.ustar = out;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (rk->profiling) {
-        INS_HIP_TRY(hipEventCreate(&e0));
-        INS_HIP_TRY(hipEventCreate(&e1));
-        INS_HIP_TRY(hipEventRecord(e0, s));
-      }
-      if (corr_in)
-        rc = ins_k_momentum_rk_fused_corr3(G, visc, cur, rk->p, rk->ku[i], epi, s);
-      else
-        rc = tiled ? ins_k_momentum_rk_fused(G, visc, cur, rk->ku[i], epi, s)
-                   : (ins_flux2d_supported(G) ? ins_k_flux2d(G, visc, cur, rk->ku[i], &epi, s) : ins_k_momentum_rk_fused_generic(G, visc, cur, rk->ku[i], epi, s));
-      if (rc) return rc;   // :21, :35-38
-      if (rk->profiling) {
-        INS_HIP_TRY(hipEventRecord(e1, s));
-        rk->prof_events.push_back(e0);
-        rk->prof_events.push_back(e1);
-      }
+      rc = timed_stage(rk, s, [&] {  // :21, :35-38
+        if (corr_in) return ins_k_momentum_rk_fused_corr3(G, visc, cur, rk->p, rk->ku[i], epi, s);
+        if (tiled) return ins_k_momentum_rk_fused(G, visc, cur, rk->ku[i], epi, s);
+        return ins_flux2d_supported(G) ? ins_k_flux2d(G, visc, cur, rk->ku[i], &epi, s) : ins_k_momentum_rk_fused_generic(G, visc, cur, rk->ku[i], epi, s);
+      });
+      if (rc) return rc;
       cur = out;
       if ((rc = ins_k_apply_bc_u(G, cur, 0, nullptr, s))) return rc;           // :48
       if (incorr && i < ns - 1)
@@ -686,37 +585,13 @@ static int rk_step_any(ins_rk_t* rk, double visc, double* u, double dt, const do
   INS_HIP_TRY(hipMemcpyAsync(rk->ustart, u, nvec * sizeof(double), hipMemcpyDeviceToDevice, s));
   for (int i = 0; i < ns; ++i) {
     if ((rc = ins_k_apply_bc_u(G, u, 0, pset(i), s))) return rc;             // :19
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (rk->profiling) {
-      INS_HIP_TRY(hipEventCreate(&e0));
-      INS_HIP_TRY(hipEventCreate(&e1));
-      INS_HIP_TRY(hipEventRecord(e0, s));
-    }
     // ku[i]'s ghost shell is zero from ins_rk_create and never written, so the fast path skips re-zeroing it
-    rc = ins_fast3d_supported(G) ? ins_k_momentum_fast3d_opts(G, visc, u, rk->ku[i], false, s)
-                                 : ins_k_momentum_generic(G, visc, u, rk->ku[i], s);   // :21
+    rc = timed_stage(rk, s, [&] {
+      return ins_fast3d_supported(G) ? ins_k_momentum_fast3d_opts(G, visc, u, rk->ku[i], false, s) : ins_k_momentum_generic(G, visc, u, rk->ku[i], s);  // :21
+    });
     if (rc) return rc;
-    if (rk->profiling) {
-      INS_HIP_TRY(hipEventRecord(e1, s));
-      rk->prof_events.push_back(e0);
-      rk->prof_events.push_back(e1);
-    }
     Combine cb;                                                               // :35-38
-    cb.n = 0;
-    for (int j = 0; j <= i; ++j) {
-      const double coef = dt * rk->A[i * ns + j];
-      if (coef == 0.0) continue;
-      cb.coef[cb.n] = coef;
-      cb.k[cb.n] = rk->ku[j];
-      ++cb.n;
-    }
-    if (rk->force) {
-      double cf = 0.0;
-      for (int j = 0; j <= i; ++j) cf += dt * rk->A[i * ns + j];
-      cb.coef[cb.n] = cf;
-      cb.k[cb.n] = rk->force;
-      ++cb.n;
-    }
+    cb.n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, cb.coef, cb.k);
     const unsigned nblk = (unsigned)std::min<long long>((nvec / 2 + 255) / 256, 8192);
     hipLaunchKernelGGL(k_combine, dim3(nblk), dim3(256), 0, s, nvec, rk->ustart, u, cb);
     INS_LAUNCH_CHECK();

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ins_internal.h"
+#include "ins_rk_terms.h"
 
 int ins_k_momentum_generic(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s);
 int ins_k_momentum_fast3d_opts(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
@@ -24,7 +25,6 @@ int ins_k_momentum_rk_fused(const ins_grid* G, double visc, const double* u_in, 
 int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout = nullptr,
                                  const double* rhs = nullptr);
 int ins_k_project(const ins_grid* G, ins_poisson* ps, double* u, double* p, hipStream_t s);
-bool ins_fast3d_supported(const ins_grid* G);
 bool ins_flux64_supported(const ins_grid* G);
 int ins_k_temp_stage(const ins_grid* G, double a4, double coef, const double* u, const double* temp, const double* w, const double* tempstart, int n,
                      const double* coefs, const double* const* ks, double c_self, double* ktemp_out, double* temp_out, hipStream_t s, const double* pI,
@@ -143,17 +143,15 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
     return ins_combine_scalar_f64(G, e->tempstart, temp, n, coefs, ks, stream);
   };
 
-  bool fused = !ins_opt(OPT_INS_DISABLE_FUSED_RK) && !ins_opt(OPT_INS_DISABLE_EXT_FUSED) && D == 3 && G->all_periodic && G->all_dof &&
-               rk->ps->kind == POISSON_SPECTRAL && ins_fast3d_supported(G) && ins_flux64_supported(G);
-  for (int a = 0; fused && a < 3; ++a) fused = rk->ps->np[a] >= 2;
+  // the plain fused periodic loop's boxes, where the 64-wide stage kernel runs (it carries the closure field, gravity and the temperature stage)
+  const bool fused = ins_rk_fused3d(rk) && !ins_opt(OPT_INS_DISABLE_EXT_FUSED) && ins_flux64_supported(G);
 
   if (fused) {
     // Periodic uniform 3-D box, spectral solver.  Per stage: [closure kernels ->] stage kernel (convection-diffusion + closure field + gravity
     // from temp in registers, RK combination, and w = u · diffusion(u) as a by-product) -> one temperature kernel (its right-hand side and its
     // RK combination) -> the five solver passes -> gradient-subtract with ghost fill -> temperature ghost fill.
     ++g_fused_steps;
-    for (int b = 0; b < 2; ++b)
-      if ((rc = zalloc(&rk->ub[b], vbytes, s))) return rc;
+    if ((rc = ins_rk_ensure_ub(rk, vbytes, s, nullptr))) return rc;
     if (with_temp) {
       for (int b = 0; b < 2; ++b)
         if ((rc = zalloc(&e->tb[b], sbytes, s))) return rc;
@@ -161,10 +159,9 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
     }
     if ((rc = ins_k_apply_bc_u(G, u, 0, nullptr, s))) return rc;
     if ((rc = bc_temp())) return rc;
-    // Stage-velocity basis (rk_step_fused_periodic): the projection writes the corrected field to another array, so the uncorrected stage
+    // Stage-velocity basis (ins_rk_terms.h): the projection writes the corrected field to another array, so the uncorrected stage
     // velocities V_m stay in memory (in the ku arrays) and no k_j is stored or read; INS_RK_KEEP_K=1 restores the k-basis.
-    bool vbasis = ns > 1 && !ins_opt(OPT_INS_RK_KEEP_K);
-    for (int i = 0; vbasis && i < ns; ++i) vbasis = rk->A[i * ns + i] != 0.0;
+    const bool vbasis = ns > 1 && !ins_opt(OPT_INS_RK_KEEP_K) && ins_rk_vbasis_possible(rk->A.data(), ns);
     // Every consumer of the stage velocity can correct it on the fly (the stage kernel as on the plain path, the split temperature kernel for
     // its two face velocities, the stress-tensor kernel through periodic images), so the gradient-subtract pass runs for the last stage only —
     // except when the temperature stage rides inside the stage kernel (it has no correcting variant).
@@ -194,46 +191,9 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
         if ((rc = ins_k_apply_bc_p_fields(G, e->sigma, D * (D + 1) / 2, s))) return rc;  // apply_bc_p!(σ, 0, setup)   operators.jl:1302
         if ((rc = ins_divoftensor_f64(G, e->sigma, e->E, stream))) return rc;
       }
-      RkEpi epi;
-      memset(&epi, 0, sizeof(epi));
-      if (vbasis) {
-        double beta[INS_MAX_STAGES];
-        for (int m = i - 1; m >= 0; --m) {  // β_i · A[0:i,0:i] = A[i,0:i], A lower triangular
-          double v = rk->A[i * ns + m];
-          for (int j = m + 1; j < i; ++j) v -= beta[j] * rk->A[j * ns + m];
-          beta[m] = v / rk->A[m * ns + m];
-        }
-        for (int m = 0; m < i; ++m) {
-          if (beta[m] == 0.0) continue;
-          epi.c0m1 -= beta[m];
-          if (corr_in && m == i - 1) {  // V_{i-1} is this stage's stencil input: its uncorrected value is taken from registers
-            epi.self_in = beta[m];
-            continue;
-          }
-          epi.coef[epi.n] = beta[m];
-          epi.k[epi.n] = rk->ku[m];
-          ++epi.n;
-        }
-      } else {
-        for (int j = 0; j < i; ++j) {
-          const double coef = dt * rk->A[i * ns + j];
-          if (coef == 0.0) continue;
-          epi.coef[epi.n] = coef;
-          epi.k[epi.n] = rk->ku[j];
-          ++epi.n;
-        }
-        for (int i2 = i + 1; i2 < ns; ++i2)
-          if (rk->A[i2 * ns + i] != 0.0) epi.write_k = 1;
-      }
-      if (rk->force) {  // the steady force f is not part of what is stored: Δt A[i,i] f on top of the V_m, Δt Σ_{j<=i} A[i,j] f on top of the k_j
-        double cf = dt * rk->A[i * ns + i];
-        if (!vbasis)
-          for (int j = 0; j < i; ++j) cf += dt * rk->A[i * ns + j];
-        epi.coef[epi.n] = cf;
-        epi.k[epi.n] = rk->force;
-        ++epi.n;
-      }
-      epi.coef_self = dt * rk->A[i * ns + i];
+      // the V_m live in the ku arrays; V_{i-1} comes from registers where it is this stage's uncorrected stencil input (corr_in), else the stencil reads
+      // the projection's corrected copy and V_{i-1} is a term like the others.  The steady force is not part of what is stored.
+      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, vbasis ? RK_V_BASIS : RK_K_BASIS, corr_in, RK_FORCE_DIAG_FIRST);
       epi.ustart = (i == 0) ? nullptr : u;
       epi.ustar = out;
       epi.extra = closure ? e->E : nullptr;
@@ -247,9 +207,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
           te.temp = tin;
           te.tempstart = e->tempstart;
           te.temp_out = tout;
-          bool later = false;
-          for (int i2 = i + 1; i2 < ns; ++i2) later = later || rk->A[i2 * ns + i] != 0.0;
-          te.ktemp_out = later ? e->ktemp[i] : nullptr;
+          te.ktemp_out = ins_rk_needed_later(rk->A.data(), ns, i) ? e->ktemp[i] : nullptr;
           for (int j = 0; j < i; ++j) {
             const double c = dt * rk->A[i * ns + j];
             if (c == 0.0) continue;
@@ -276,8 +234,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
           ks[n] = e->ktemp[j];
           ++n;
         }
-        bool later = false;
-        for (int i2 = i + 1; i2 < ns; ++i2) later = later || rk->A[i2 * ns + i] != 0.0;
+        const bool later = ins_rk_needed_later(rk->A.data(), ns, i);
         if ((rc = ins_k_temp_stage(G, td.a4, td.diss_coef, in, tin, td.dodissipation ? e->w : nullptr, e->tempstart, n, coefs, ks, dt * rk->A[i * ns + i],
                                    later ? e->ktemp[i] : nullptr, tout, s, corr_in ? rk->ps->pI : nullptr)))
           return rc;
@@ -302,11 +259,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
   // is ustart for the whole step, stage velocities ping-pong in two library buffers: no snapshot copy, no combination pass, no axpy), one
   // temperature kernel per stage (right-hand side from (u, temp, diffusion(u)) + its RK combination), full projection after every stage.
   if (!ins_opt(OPT_INS_DISABLE_FUSED_RK) && !ins_opt(OPT_INS_DISABLE_EXT_FUSED) && D == 3 && ins_fast3d_supported(G)) {
-    for (int b = 0; b < 2; ++b)
-      if (!rk->ub[b]) {
-        INS_HIP_TRY(hipMalloc(&rk->ub[b], vbytes));
-        INS_HIP_TRY(hipMemcpyAsync(rk->ub[b], u, vbytes, hipMemcpyDeviceToDevice, s));  // once: volumes no kernel ever writes
-      }
+    if ((rc = ins_rk_ensure_ub(rk, vbytes, s, u))) return rc;
     if (with_temp) {
       for (int b = 0; b < 2; ++b)
         if (!e->tb[b]) {
@@ -337,25 +290,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
       }
       if (with_temp && td.dodissipation && !w_from_stage && (rc = ins_k_diffusion_flux3d(G, visc, cur, e->diff, false, s)))
         return rc;  // e->diff: shell zero since its allocation
-      RkEpi epi;
-      memset(&epi, 0, sizeof(epi));
-      for (int j = 0; j < i; ++j) {
-        const double coef = dt * rk->A[i * ns + j];
-        if (coef == 0.0) continue;
-        epi.coef[epi.n] = coef;
-        epi.k[epi.n] = rk->ku[j];
-        ++epi.n;
-      }
-      for (int i2 = i + 1; i2 < ns; ++i2)
-        if (rk->A[i2 * ns + i] != 0.0) epi.write_k = 1;
-      if (rk->force) {
-        double cf = 0.0;
-        for (int j = 0; j <= i; ++j) cf += dt * rk->A[i * ns + j];
-        epi.coef[epi.n] = cf;
-        epi.k[epi.n] = rk->force;
-        ++epi.n;
-      }
-      epi.coef_self = dt * rk->A[i * ns + i];
+      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, RK_K_BASIS, false, RK_FORCE_INDEX_ORDER);  // k-basis only
       epi.ustart = (i == 0) ? nullptr : u;
       epi.ustar = out;
       epi.extra = closure ? e->E : nullptr;
@@ -375,8 +310,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
           ks[n] = e->ktemp[j];
           ++n;
         }
-        bool later = false;
-        for (int i2 = i + 1; i2 < ns; ++i2) later = later || rk->A[i2 * ns + i] != 0.0;
+        const bool later = ins_rk_needed_later(rk->A.data(), ns, i);
         if ((rc = ins_k_temp_stage(G, td.a4, td.diss_coef, cur, tin, w_from_stage ? e->w : nullptr, e->tempstart, n, coefs, ks, dt * rk->A[i * ns + i],
                                    later ? e->ktemp[i] : nullptr, tout, s, nullptr, td.dodissipation && !w_from_stage ? e->diff : nullptr)))
           return rc;
@@ -414,21 +348,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
     }
     double coefs[INS_MAX_STAGES + 1];
     const double* ks[INS_MAX_STAGES + 1];
-    int n = 0;
-    double cf = 0.0;
-    for (int j = 0; j <= i; ++j) {
-      const double c = dt * rk->A[i * ns + j];
-      cf += c;
-      if (c == 0.0) continue;
-      coefs[n] = c;
-      ks[n] = rk->ku[j];
-      ++n;
-    }
-    if (rk->force) {
-      coefs[n] = cf;
-      ks[n] = rk->force;
-      ++n;
-    }
+    const int n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, coefs, ks);
     if ((rc = ins_combine_f64(G, rk->ustart, u, n, coefs, ks, stream))) return rc;
     if ((rc = temp_combine(i))) return rc;
     if ((rc = ins_k_apply_bc_u(G, u, 0, nullptr, s))) return rc;
