@@ -264,6 +264,9 @@ int ins_rk_set_bodyforce(ins_rk_t* rk, const double* force);
 int ins_dbg_stage_rhs_used(const ins_rk_t* rk, int64_t* launches);
 int ins_dbg_stage_rhs(ins_rk_t* rk, double visc, const double* u_in, const double* pI, const double* ustart, const double* kterm, double coef_k,
                       double self_in, double coef_self, double* ustar, double* rhs, int32_t* used, void* stream);
+/* ins_dbg_stage_carry_used: how many stage kernels this integrator has enqueued that also stored a carried combination (RK44 on the fused periodic path:
+ * the second stage stores the part of the last stage's combination it has in registers; INS_DISABLE_STAGE_CARRY=1 switches the route off). */
+int ins_dbg_stage_carry_used(const ins_rk_t* rk, int64_t* launches);
 int ins_rk_pressure(const ins_rk_t* rk, double** p);
 /* The cache array ku[i] of ode_method_cache (time_steppers.jl).  It holds the stage force k_i only on the k-basis paths (INS_RK_KEEP_K=1
  * selects them everywhere); the fused stage loops work in the stage-velocity basis, where the periodic loop leaves the arrays untouched

@@ -127,6 +127,7 @@ SIGNATURES = {
     "ins_rk_profile_read": (C.c_int, [vp, c_double_p, C.POINTER(C.c_int64)]),
     "ins_rk_set_bodyforce": (C.c_int, [vp, vp]),
     "ins_dbg_stage_rhs_used": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+    "ins_dbg_stage_carry_used": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "ins_dbg_stage_rhs": (C.c_int, [vp, C.c_double, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, C.POINTER(C.c_int32), vp]),
     "ins_rk_pressure": (C.c_int, [vp, C.POINTER(vp)]),
     "ins_rk_stage_force": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),

@@ -57,9 +57,12 @@ struct TExt {
 //   y  v*(jb0-1), the row below the wavefront's first output row, belongs to another wavefront: it is computed here again, from the same expressions
 //      in the same order (so it is the value that wavefront stores): one more y-flux (row jb0-2 of v, of p), the v terms of the epilogue at row jb0-1;
 //   z  w*(k-1) is carried along the march; the march starts one plane early (k0-1, nothing stored) so the first plane of a chunk has it.
-template <typename T, int R, int XW, bool FUSE, int CORR, bool SKEL = false, int NW = 4, bool EXTRA = false, bool RHS = false>
+// CARRY (CORR 1, a.epi.carry_out; ins_rk_terms.h, RkCarryPlan): the kernel also stores S = ca0·s + ca1·raw + ca2·u* at the cells it stores u* at, s = the
+// combination before coef_self·f is added, raw = the uncorrected stencil input (kept alive to the stores: 12 more registers, hence a flag of its own).
+template <typename T, int R, int XW, bool FUSE, int CORR, bool SKEL = false, int NW = 4, bool EXTRA = false, bool RHS = false, bool CARRY = false>
 __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a) {
   static_assert(!RHS || (FUSE && CORR <= 1 && !SKEL && !EXTRA), "right-hand side in the stage kernel: fused epilogue, periodic box, no extra terms");
+  static_assert(!CARRY || (FUSE && CORR == 1 && !SKEL && !EXTRA && NW <= 8 && sizeof(T) == 8), "carried combination: the fp64 periodic correcting stage kernel");
   constexpr unsigned EB = (unsigned)sizeof(T);  // element bytes
   const T* const a_u = static_cast<const T*>(a.u);
   const T* const a_pI = static_cast<const T*>(a.pI);
@@ -163,7 +166,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
   };
   // u = u* - ∇p (applypressure!, operators.jl:225-233) for one register plane and its packed halo columns
   auto correct = [&](Plane<T, R>& P, const T (&Pc)[NPR], T PHc, const T (&Pn)[NPR], T PHn) {
-    if (a.epi.self_in != 0.0) {
+    if (CARRY || a.epi.self_in != 0.0) {
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -470,6 +473,14 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
           Pz[2][rr - 1] = Wc;
         }
         emit(rr, k, fu, fv, fw, FUSE ? sacc[0][rr - 1] : (T)0, FUSE ? sacc[1][rr - 1] : (T)0, FUSE ? sacc[2][rr - 1] : (T)0, st);
+        if constexpr (CARRY) {  // S at the cells of u* (the predicate and addressing of emit), with the result stores' cache policy: read once, two stages on
+          if (xout && jb0 + rr - 1 < n1 && st) {
+            const T ca0 = (T)a.epi.ca[0], ca1 = (T)a.epi.ca[1], ca2 = (T)a.epi.ca[2], cs = (T)a.epi.coef_self;
+            const T s0 = sacc[0][rr - 1], s1 = sacc[1][rr - 1], s2 = sacc[2][rr - 1];
+            st3(static_cast<T*>((void*)a.epi.carry_out) + (long long)k * sz, ocol, orow[rr - 1], ca0 * s0 + ca1 * C.raw[0][rr - 1] + ca2 * (s0 + cs * fu),
+                ca0 * s1 + ca1 * C.raw[1][rr - 1] + ca2 * (s1 + cs * fv), ca0 * s2 + ca1 * C.raw[2][rr - 1] + ca2 * (s2 + cs * fw));
+          }
+        }
         if constexpr (RHS) {  // the stored values (the expressions of emit)
           const T su = sacc[0][rr - 1] + (T)a.epi.coef_self * fu, sv = sacc[1][rr - 1] + (T)a.epi.coef_self * fv, sw = sacc[2][rr - 1] + (T)a.epi.coef_self * fw;
           us_u[rr - 1] = su;
@@ -675,7 +686,14 @@ int launch_range(const ins_grid* G, FluxArgs& a, int corr_mode, hipStream_t s) {
   if (corr_mode == 0)
     hipLaunchKernelGGL((k_flux64<T, R, XW, FUSE, 0, false, NW>), dim3(nb), block, (size_t)g_lds, s, a);
   else if constexpr (FUSE && R <= 5) {
-    if (corr_mode == 1)
+    if (corr_mode == 1 && a.epi.carry_out) {
+      if constexpr (R == 2 && NW <= 8 && sizeof(T) == 8) {
+        hipLaunchKernelGGL((k_flux64<T, R, XW, true, 1, false, NW, false, false, true>), dim3(nb), block, (size_t)g_lds, s, a);
+      } else {
+        ins_set_error("stage kernel asked to carry a combination forward on a tile shape it does not do it for");
+        return INS_ERR_UNSUPPORTED;
+      }
+    } else if (corr_mode == 1)
       hipLaunchKernelGGL((k_flux64<T, R, XW, true, 1, false, NW>), dim3(nb), block, (size_t)g_lds, s, a);
     else
       hipLaunchKernelGGL((k_flux64<T, R, XW, true, 2, false, NW>), dim3(nb), block, (size_t)g_lds, s, a);
@@ -714,7 +732,7 @@ int launch(const ins_grid* G, FluxArgs& a, int corr_mode, int part, hipStream_t 
 }
 
 // the instantiations that also write Ω·div(u*) (a.epi.rhs_out): fp64, whole rows per workgroup, every plane in one launch
-template <int R, int XW, int NW, int CORR>
+template <int R, int XW, int NW, int CORR, bool CARRY = false>
 int launch_rhs(const ins_grid* G, FluxArgs& a, hipStream_t s) {
   const GridDev& g = G->g;
   a.ntx = 1;
@@ -724,7 +742,7 @@ int launch_rhs(const ins_grid* G, FluxArgs& a, hipStream_t s) {
   a.kB = 0;
   a.ntz = cdiv(a.k_hi - a.k_lo, a.zc);
   const unsigned nb = (unsigned)(8LL * ((a.nty + 7) / 8) * a.ntz);
-  hipLaunchKernelGGL((k_flux64<double, R, XW, true, CORR, false, NW, false, true>), dim3(nb), dim3(64, NW, 1), 0, s, a);
+  hipLaunchKernelGGL((k_flux64<double, R, XW, true, CORR, false, NW, false, true, CARRY>), dim3(nb), dim3(64, NW, 1), 0, s, a);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
@@ -828,6 +846,15 @@ bool ins_flux64_stage_rhs_supported(const ins_grid* G, int corr_mode) {
   return t.rows == 2 && ((t.xw == 3 && t.nw == 6) || ((t.xw == 2 || t.xw == 4) && (t.nw == 4 || t.nw == 8)));
 }
 
+// A correcting stage (corr_mode 1, fp64, every plane) can also store a carried combination (RkEpi::carry_out): this file's kernel runs it, in the default 2-row
+// shape with 4, 6 or 8 wavefronts (the 16-wavefront form has half the registers).
+bool ins_flux64_stage_carry_supported(const ins_grid* G) {
+  if (ins_opt(OPT_INS_DISABLE_STAGE_CARRY) || !ins_flux64_supported(G) || g_skel) return false;
+  if (ins_flux128_supported(G, nullptr, 1, false)) return false;
+  const TileShape t = tile_shape(G, 1, false, false, false);  // (asking for the right-hand side changes xw and nw of 192-wide rows only: 3 and 6)
+  return t.rows == 2 && t.nw <= 8;
+}
+
 // corr_mode 0: u has valid ghost volumes.  1 / 2: see k_flux64.  fuse: RK epilogue `epi`.
 template <typename T>
 static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, const RkEpi* epi, const T* pI, int corr_mode, hipStream_t s, int part) {
@@ -884,6 +911,17 @@ static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, con
       return launch<T, RR, 1, FUSE>(G, a, corr_mode, part, s);                        \
     }                                                                                 \
   }
+  const bool carry = epi && epi->carry_out;
+  if (carry) {
+    if (ins_stage_carry_aliases(*epi, u) || ins_stage_out_aliases_input(*epi, u)) {  // other workgroups still read the halo rows and planes of the inputs
+      ins_set_error("stage kernel asked to carry a combination forward into, or to store u* over, one of its inputs");
+      return INS_ERR_INVALID;
+    }
+    if (F32 || corr_mode != 1 || part != 0 || !ins_flux64_stage_carry_supported(G)) {
+      ins_set_error("stage kernel asked to carry a combination forward on a path that does not do it");
+      return INS_ERR_UNSUPPORTED;
+    }
+  }
   if (want_rhs) {
     if (ins_stage_out_aliases_input(*epi, u)) {  // the right-hand side reads neighbouring cells of every input
       ins_set_error("stage kernel asked for the Poisson right-hand side while u* overwrites one of its inputs");
@@ -896,6 +934,11 @@ static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, con
         a.rdiv[2] = 1.0 / G->desc.dx[2][1];
         a.om = G->desc.dx[0][1] * G->desc.dx[1][1] * G->desc.dx[2][1];
         if (corr_mode == 0) return launch_rhs<4, 2, 4, 0>(G, a, s);
+        if (carry) {
+          if (xw == 3) return launch_rhs<2, 3, 6, 1, true>(G, a, s);
+          if (xw == 4) return nw == 8 ? launch_rhs<2, 4, 8, 1, true>(G, a, s) : launch_rhs<2, 4, 4, 1, true>(G, a, s);
+          return nw == 8 ? launch_rhs<2, 2, 8, 1, true>(G, a, s) : launch_rhs<2, 2, 4, 1, true>(G, a, s);
+        }
         if (xw == 3) return launch_rhs<2, 3, 6, 1>(G, a, s);
         if (xw == 4) return nw == 8 ? launch_rhs<2, 4, 8, 1>(G, a, s) : launch_rhs<2, 4, 4, 1>(G, a, s);
         return nw == 8 ? launch_rhs<2, 2, 8, 1>(G, a, s) : launch_rhs<2, 2, 4, 1>(G, a, s);
@@ -928,7 +971,13 @@ int ins_k_flux128_f32(const ins_grid* G, double visc, const float* u, float* F, 
 
 int ins_k_flux64(const ins_grid* G, double visc, const double* u, double* F, const RkEpi* epi, const double* pI, int corr_mode, hipStream_t s,
                  int part) {
-  if (ins_flux128_supported(G, epi, corr_mode, false)) return ins_k_flux128(G, visc, u, F, epi, pI, corr_mode, s, part);
+  if (ins_flux128_supported(G, epi, corr_mode, false)) {
+    if (epi && epi->carry_out) {
+      ins_set_error("stage kernel asked to carry a combination forward on a path that does not do it");
+      return INS_ERR_UNSUPPORTED;
+    }
+    return ins_k_flux128(G, visc, u, F, epi, pI, corr_mode, s, part);
+  }
   return flux64_dispatch<double>(G, visc, u, F, epi, pI, corr_mode, s, part);
 }
 // fp32 family (`_f32` entry points): same kernels instantiated for float; RkEpi's pointers are float arrays then

@@ -114,6 +114,7 @@ void ins_set_error(const char* fmt, ...);
   X(INS_DISABLE_FDM_FOLDFUSE)    \
   X(INS_DISABLE_INKERNEL_CORR)   \
   X(INS_DISABLE_STAGE_RHS)       \
+  X(INS_DISABLE_STAGE_CARRY)     \
   X(INS_RK_KEEP_K)               \
   X(INS_DISABLE_EXT_FUSED)       \
   X(INS_EXT_TEMP_SPLIT)          \
@@ -282,6 +283,7 @@ struct ins_rk {
   std::vector<double*> vb;        // all uncorrected stage velocities V_0..V_{s-2} (stage-velocity basis, ins_rk.hip)
   const double* force = nullptr;  // steady body force field (caller-owned), ins_rk_set_bodyforce
   ins_rk_ext* ext = nullptr;
+  long long stage_carry_launches = 0;  // stage kernels enqueued that stored a carried combination (ins_dbg_stage_carry_used)
   long long stage_rhs_launches = 0;  // stage kernels enqueued that wrote the Poisson right-hand side themselves (ins_dbg_stage_rhs_used)
   bool profiling = false;
   std::vector<hipEvent_t> prof_events;  // (start, stop) pairs around momentum launches
@@ -309,9 +311,13 @@ struct RkEpi {
   double coef_self;         // Δt A[i,i]
   double self_in;           // coefficient of the stencil input itself (its uncorrected value, taken from registers: ins_flux64.hip)
   double c0m1;              // ustart enters as (1 + c0m1)·ustart; 0 in the k-basis, -Σ coef in the stage-velocity basis (ins_rk.hip)
-  const double* ustart;     // nullptr: ustart is the stencil input itself (first stage)
+  const double* ustart;     // the array the combination starts from, as (1 + c0m1)·ustart: the step's start velocity, or (c0m1 == 0) the combination S an
+                            // earlier stage carried forward (carry_out below).  nullptr: it starts from the stencil input itself (first stage)
   double* ustar;            // stage velocity out (interior volumes only)
   double* ustart_out;       // optional (first stage of a chained step, ustart == nullptr): the corrected stencil input is stored here
+  double* carry_out;        // optional (ins_flux64_stage_carry_supported; ins_rk_terms.h, RkCarryPlan): S = ca[0]·s + ca[1]·(the uncorrected stencil input) +
+                            // ca[2]·u* is stored here, s = the combination before coef_self·f is added.  An array no input of the launch lives in
+  double ca[3];
   double* rhs_out;          // optional (ins_flux64_stage_rhs_supported): Ω·div(u*) of the stored stage velocity, unpadded n^3 (never the pressure input pI)
   const double* extra;      // optional vector field added to the stage force before it is used and stored (closure term: ins_rk_ext.hip)
   const double* gtemp;      // optional temperature field: gravity! is added to component gdir of the stage force (ga2 = α2)
@@ -326,6 +332,12 @@ struct RkEpi {
 static inline bool ins_stage_out_aliases_input(const RkEpi& epi, const void* in) {
   bool a = (const void*)epi.ustar == in || epi.ustar == epi.ustart;
   for (int q = 0; q < epi.n; ++q) a = a || epi.ustar == epi.k[q];
+  return a;
+}
+// The carried combination goes to an array of its own: other workgroups still read the halo rows and planes of the stencil input, and u* must not land on it.
+static inline bool ins_stage_carry_aliases(const RkEpi& epi, const void* in) {
+  bool a = (const void*)epi.carry_out == in || epi.carry_out == epi.ustart || epi.carry_out == epi.ustar;
+  for (int q = 0; q < epi.n; ++q) a = a || epi.carry_out == epi.k[q];
   return a;
 }
 
@@ -375,6 +387,7 @@ bool ins_poisson_own2d(const ins_poisson* ps);
 // rhs != nullptr (own-FFT routes): the right-hand side Ω·div(u) is already in that buffer (the stage kernel wrote it) and the x pass reads it instead of u
 int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s, const double* rhs = nullptr);
 bool ins_flux64_stage_rhs_supported(const ins_grid* G, int corr_mode);  // the stage kernel of this box can write that right-hand side (ins_flux64.hip)
+bool ins_flux64_stage_carry_supported(const ins_grid* G);            // its correcting stage kernel can store a carried combination (RkEpi::carry_out)
 double* ins_poisson_stage_rhs(ins_poisson* ps);                        // its buffer (nullptr: no own-FFT 3-D route, or out of memory)
 int ins_k_poisson_solve(ins_poisson* ps, double* p, hipStream_t s);
 bool ins_fast3d_supported(const ins_grid* G);

@@ -164,6 +164,31 @@ extern "C" int ins_dbg_stage_rhs_used(const ins_rk_t* rk, int64_t* launches) {
   return INS_OK;
 }
 
+// How many stage kernels of this integrator have stored a carried combination so far (RkCarryPlan, ins_rk_terms.h; a test asserts that the route ran).
+extern "C" int ins_dbg_stage_carry_used(const ins_rk_t* rk, int64_t* launches) {
+  INS_REQUIRE(rk && launches, "null argument");
+  *launches = (int64_t)rk->stage_carry_launches;
+  return INS_OK;
+}
+
+// Test hook (needs no device): the carry plan of the caller's tableau.  *j < 0: no plan.  With a plan: a[3], and the consuming stage's terms as
+// ins_rk_carry_consumer_terms builds them: *self_in, *coef_self and *coef_force (0 without a force); it starts from S with factor 1.
+extern "C" int ins_dbg_rk_carry_plan(int32_t ns, const double* A, double dt, int32_t with_force, int32_t* j, int32_t* i, double* a, double* self_in,
+                                     double* coef_self, double* coef_force) {
+  INS_REQUIRE(A && j && i && a && self_in && coef_self && coef_force, "null argument");
+  INS_REQUIRE(ns >= 1 && ns <= INS_MAX_STAGES, "bad argument");
+  const RkCarryPlan pl = ins_rk_carry_plan(A, ns);
+  *j = pl.j, *i = pl.i, *self_in = 0.0, *coef_self = 0.0, *coef_force = 0.0;
+  for (int q = 0; q < 3; ++q) a[q] = pl.a[q];
+  if (pl.j < 0) return INS_OK;
+  static double slot[2];
+  const RkEpi epi = ins_rk_carry_consumer_terms<double>(A, ns, pl, dt, slot, with_force ? slot + 1 : nullptr);
+  INS_REQUIRE(epi.ustart == slot && epi.c0m1 == 0.0 && epi.n == (with_force ? 1 : 0), "consumer terms");
+  *self_in = epi.self_in, *coef_self = epi.coef_self;
+  if (with_force) *coef_force = epi.coef[0];
+  return INS_OK;
+}
+
 // Test hook: ONE stage kernel through the production dispatch, u* = (1 - self_in) ustart + self_in u_in + coef_k kterm + coef_self F(u_in), stored to ustar
 // (interior volumes), with Ω·div(u*) copied to rhs (unpadded n^3, device) where the stage kernel writes it; *used says whether it did.  pI == nullptr: u_in
 // has valid ghost volumes; else u_in is an uncorrected stage velocity and pI its unpadded pressure (the in-register correction).  ustart / kterm nullable.
@@ -307,21 +332,45 @@ static int rk_step_fused_periodic(ins_rk* rk, double visc, double* u, double dt,
         INS_HIP_TRY(hipMemsetAsync(rk->vb[m], 0, vbytes, s));
       }
   }
+  // Carry plan (ins_rk_terms.h; INS_DISABLE_STAGE_CARRY=1 switches it off): stage pl.j also stores S, the part of the last stage's combination it has in
+  // registers, and the last stage starts from S instead of loading ustart, V_{j-1} and V_j.  Where the 64-wide correcting kernel runs stage pl.j only.
+  // Buffers (rk->vb is private to this loop, the pointers are the same in every step): S takes vb[j+1], which nothing uses before stage j+1 stores into it;
+  // stage j+1 stores V_{j+1} to vb[j-1] instead (V_{j-1} is dead once stage j has finished, and stage j+1 reads no cell of it).  Never S to vb[j-1] during
+  // stage j: other workgroups still read V_{j-1}'s halo rows and planes.
+  RkCarryPlan pl = {-1, -1, {0.0, 0.0, 0.0}};
+  if (vbasis && ins_flux64_stage_carry_supported(G)) pl = ins_rk_carry_plan(rk->A.data(), ns);
+  const bool carry = pl.j >= 0;
   const double* in = u;
   for (int i = 0; i < ns; ++i) {
-    double* out = (i == ns - 1 && ns > 1) ? u : (vbasis ? rk->vb[i] : rk->ub[i & 1]);
+    double* out = (i == ns - 1 && ns > 1) ? u : (vbasis ? rk->vb[(carry && i == pl.j + 1) ? pl.j - 1 : i] : rk->ub[i & 1]);
     // the V_m live in rk->vb; V_{i-1}, the stencil input, comes from registers on the 64-wide kernel only (the 62-wide one keeps no uncorrected copy)
     RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, vbasis ? rk->vb.data() : rk->ku.data(), rk->force, vbasis ? RK_V_BASIS : RK_K_BASIS,
                                    vbasis && ins_flux64_supported(G), RK_FORCE_DIAG_FIRST);
     epi.ustart = (i == 0) ? nullptr : (raw_in ? rk->ustart : u);  // raw_in: the corrected start field lives in the cache array
     epi.ustar = out;
+    // the last stage of a step that is not chained to its predecessor stores u* over the caller's u, its ustart, and keeps the old right-hand-side route for that;
+    // with the plan it no longer reads u, but which stages write the right-hand side does not depend on the plan
+    const bool in_place = ins_stage_out_aliases_input(epi, in);
+    if (carry && i == pl.j) {
+      epi.carry_out = rk->vb[pl.j + 1];
+      for (int q = 0; q < 3; ++q) epi.ca[q] = pl.a[q];
+      if (ins_stage_carry_aliases(epi, in) || in_place) {
+        ins_set_error("carried stage combination: an output of stage %d is one of its inputs", i);
+        return INS_ERR_INVALID;
+      }
+      ++rk->stage_carry_launches;
+    }
+    if (carry && i == pl.i) {
+      epi = ins_rk_carry_consumer_terms(rk->A.data(), ns, pl, dt, rk->vb[pl.j + 1], rk->force);
+      epi.ustar = out;
+    }
     if (i == 0 && raw_in) epi.ustart_out = rk->ustart;
     // Where the stage kernel spans whole rows it also writes Ω·div(u*), and the solver's x pass reads that one array instead of the three components
     // of u* (INS_DISABLE_STAGE_RHS=1: the x pass forms it).  A buffer of its own: pI is the correcting kernel's pressure input.
     // Not where u* overwrites one of the kernel's inputs (the last stage of an unchained step: ustart == out == the caller's u): that is safe cell by cell,
     // but for the right-hand side a wavefront reads its neighbours' cells of the inputs (row jb0-1, plane k0-1), which another workgroup may have overwritten.
     const bool corr = inkernel && (i > 0 || raw_in);
-    if (!ins_stage_out_aliases_input(epi, in) && ins_flux64_stage_rhs_supported(G, corr ? 1 : 0) && (epi.rhs_out = ins_poisson_stage_rhs(rk->ps)))
+    if (!in_place && ins_flux64_stage_rhs_supported(G, corr ? 1 : 0) && (epi.rhs_out = ins_poisson_stage_rhs(rk->ps)))
       ++rk->stage_rhs_launches;
     rc = timed_stage(rk, s, [&] {
       return corr ? ins_k_momentum_rk_fused_corr(G, visc, in, rk->ps->pI, rk->ku[i], epi, s) : ins_k_momentum_rk_fused(G, visc, in, rk->ku[i], epi, s);

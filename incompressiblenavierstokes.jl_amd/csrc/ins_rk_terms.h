@@ -28,6 +28,16 @@ static inline bool ins_rk_needed_later(const double* A, int ns, int i) {
   return false;
 }
 
+// β_i of the stage-velocity basis (beta[0..i-1]): back-substitution, A lower triangular
+static inline void ins_rk_beta(const double* A, int ns, int i, double* beta) {
+  const double* row = A + i * ns;
+  for (int m = i - 1; m >= 0; --m) {
+    double v = row[m];
+    for (int j = m + 1; j < i; ++j) v -= beta[j] * A[j * ns + m];
+    beta[m] = v / A[m * ns + m];
+  }
+}
+
 enum RkBasis { RK_K_BASIS, RK_V_BASIS };
 // The steady body force f (k_j = F_j + f, operators.jl:873-880; the arrays hold F_j only) enters with Δt Σ_{j<=i} A[i,j] in the k-basis and with
 // Δt A[i,i] in the stage-velocity basis (the V_m already hold their share).  The k-basis sum is formed in one of two orders, one ulp apart:
@@ -54,11 +64,7 @@ static inline RkEpi ins_rk_stage_terms(const double* A, int ns, int i, double dt
   };
   if (basis == RK_V_BASIS) {
     double beta[INS_MAX_STAGES];
-    for (int m = i - 1; m >= 0; --m) {  // back-substitution, A lower triangular
-      double v = row[m];
-      for (int j = m + 1; j < i; ++j) v -= beta[j] * A[j * ns + m];
-      beta[m] = v / A[m * ns + m];
-    }
+    ins_rk_beta(A, ns, i, beta);
     for (int m = 0; m < i; ++m) {
       if (beta[m] == 0.0) continue;
       epi.c0m1 -= beta[m];
@@ -82,6 +88,66 @@ static inline RkEpi ins_rk_stage_terms(const double* A, int ns, int i, double dt
     term(cf, force);
   }
   epi.coef_self = dt * row[i];
+  return epi;
+}
+
+// Carrying a combination forward (stage-velocity basis, the stencil input in registers).  The last stage i of RK44 loads ustart, V_0 and V_1 only to form
+//   -1/3 ustart + 1/3 V_0 + 2/3 V_1        (β_3 = (1/3, 2/3, 1/3); V_2 is its stencil input),
+// and stage j = 1 has all three in registers: ustart is its combination s before Δt A[j,j] f is added (its own β_j is zero, so s = 1·ustart), V_0 its
+// stencil input (the uncorrected copy the correcting kernel keeps) and V_1 what it stores.  So stage j also stores S = a0 s + a1 V_{j-1} + a2 V_j (24 B per
+// cell written) and stage i starts from S instead of loading three arrays (48 B per cell not read).
+// A plan exists when
+//   * i = ns - 1 and j = i - 2 >= 1: one stage lies between them, and it gives its output buffer to S and stores V_{j+1} where V_{j-1} was;
+//   * of stage i's loaded terms (β_i[m], m < i - 1) only m = j - 1 and m = j are non-zero, β_i[j] among them, and c0 = 1 - Σ β_i is non-zero;
+//   * β_j = 0, so that stage j's s is ustart exactly (plus the body force's share, below);
+//   * stage j + 1 does not load V_{j-1} (β_{j+1}[j-1] = 0): nothing between j and i needs what the plan displaces.
+// Every other tableau (Wray3, SSP33, FE11, ...) has no plan (j = -1) and runs as without this.
+// With a steady body force stage j's s is ustart + Δt A[j,j] f, so S holds a0 Δt A[j,j] f too much: stage i's own force coefficient gives it back.
+struct RkCarryPlan {
+  int j, i;     // producing and consuming stage; j < 0: no plan
+  double a[3];  // S = a[0] ustart + a[1] V_{j-1} + a[2] V_j: the c0 and β of ins_rk_stage_terms, bit for bit
+};
+static inline RkCarryPlan ins_rk_carry_plan(const double* A, int ns) {
+  RkCarryPlan pl = {-1, -1, {0.0, 0.0, 0.0}};
+  const int i = ns - 1, j = ns - 3;
+  if (j < 1 || !ins_rk_vbasis_possible(A, ns)) return pl;
+  double bi[INS_MAX_STAGES], bj[INS_MAX_STAGES], bn[INS_MAX_STAGES];
+  ins_rk_beta(A, ns, i, bi);
+  ins_rk_beta(A, ns, j, bj);
+  ins_rk_beta(A, ns, j + 1, bn);
+  for (int m = 0; m < j; ++m)
+    if (bj[m] != 0.0) return pl;
+  for (int m = 0; m < j - 1; ++m)
+    if (bi[m] != 0.0) return pl;
+  if (bi[j] == 0.0 || bn[j - 1] != 0.0) return pl;
+  double c0m1 = 0.0;  // the order of ins_rk_stage_terms
+  for (int m = 0; m < i; ++m)
+    if (bi[m] != 0.0) c0m1 -= bi[m];
+  if (1.0 + c0m1 == 0.0) return pl;
+  pl.j = j;
+  pl.i = i;
+  pl.a[0] = 1.0 + c0m1;
+  pl.a[1] = bi[j - 1];
+  pl.a[2] = bi[j];
+  return pl;
+}
+
+// Stage pl.i with the plan: it starts from S (RkEpi::ustart = S, factor 1), adds β_{i,i-1} times its stencil input from registers and, last, the body force.
+template <typename P>
+static inline RkEpi ins_rk_carry_consumer_terms(const double* A, int ns, const RkCarryPlan& pl, double dt, const P* S, const P* force) {
+  RkEpi epi;
+  memset(&epi, 0, sizeof(epi));
+  const int i = pl.i;
+  double beta[INS_MAX_STAGES];
+  ins_rk_beta(A, ns, i, beta);
+  epi.ustart = reinterpret_cast<const double*>(S);
+  epi.self_in = beta[i - 1];
+  if (force) {
+    epi.coef[0] = dt * A[i * ns + i] - pl.a[0] * (dt * A[pl.j * ns + pl.j]);
+    epi.k[0] = reinterpret_cast<const double*>(force);
+    epi.n = 1;
+  }
+  epi.coef_self = dt * A[i * ns + i];
   return epi;
 }
 
