@@ -593,6 +593,32 @@ int ins_tensorclosure_pullback_f32(const ins_grid_t* grid, const float* u, const
 int ins_divoftensor_f32(const ins_grid_t* grid, const float* sigma, float* s, void* stream);
 int ins_divoftensor_adjoint_f32(const ins_grid_t* grid, const float* sbar, float* sigmabar, void* stream);
 
+/* ---------------------------------------------------------------------------------- Float32 temperature equation (csrc/ins_temp32.hip)
+ * The `_f32` twins of the temperature entries above (examples/RayleighBenard2D.jl:71 and examples/RayleighBenard3D.jl:16 run T = Float32): the same write
+ * sets, `+=` rules and BC codes on float fields; the grid handle is the fp64 one, its metric tables are rounded to float where they enter the arithmetic,
+ * and all arithmetic is in float.  2-D and 3-D, any mix of periodic / Dirichlet / symmetric / pressure temperature sides, uniform and stretched
+ * spacings.  Boundary data is constant (no `planes`).  Slab (halo) grids: INS_ERR_UNSUPPORTED — there is no silent fp64 fallback. */
+/* apply_bc_temp!(temp, t, setup)           boundary_conditions.jl:236-246 (+338-339, 391-405, 466-467, 512-513); bc, val as ins_apply_bc_temp_f64 */
+int ins_apply_bc_temp_f32(const ins_grid_t* grid, const int32_t* bc, const float* val, float* temp, void* stream);
+/* convection_diffusion_temp!(c, u, temp, setup)   operators.jl:712-737 (c += ... on Ip); a4 = setup.temperature.α4 */
+int ins_convection_diffusion_temp_f32(const ins_grid_t* grid, float a4, const float* u, const float* temp, float* c, void* stream);
+/* dissipation!(diss, diff, u, setup)       operators.jl:791-814 (diss += ... on Ip); visc = 1/Re, coef = Re·α1/γ.  `diff` is scratch: it receives
+ * diffusion(u) on the degrees of freedom and zeros elsewhere (fill!(diff, 0); diffusion!, :793-798) */
+int ins_dissipation_f32(const ins_grid_t* grid, float visc, float coef, const float* u, float* diff, float* diss, void* stream);
+/* gravity!(F, temp, setup)                 operators.jl:914-931 (F[:, gdir] += α2 avg(temp) on Iu[gdir]); gdir 0-based */
+int ins_gravity_f32(const ins_grid_t* grid, int gdir, float a2, const float* temp, float* F, void* stream);
+/* The temperature equation in the Float32 stage loop (step_explicit_runge_kutta.jl:4-59 with `temp`): the descriptor of ins_rk_set_temperature (its
+ * doubles are rounded to float); NULL removes it.  Scratch belongs to the handle, allocated by the first step and freed by ins_rk_destroy_f32. */
+int ins_rk_set_temperature_f32(ins_rk32_t* rk, const ins_temperature_desc_t* desc);
+/* One step of u and temp                   step_explicit_runge_kutta.jl:4-59: per stage ghost fills, momentum + gravity, the temperature stage (one
+ * kernel over Ip forms ktemp_i and the stage temperature, :23-27 and :39-44; INS_DISABLE_TEMP32_STAGE=1 runs the operators one by one instead), the
+ * combination of u, project!.  Every grid ins_rk_step_f32 takes (walls / stretched spacings: a solver made by ins_poisson_wrap_f32); the 64-wide stage
+ * kernel, the in-register correction and chained steps are not used with a temperature.  `temp` is required exactly when a descriptor is set
+ * (else INS_ERR_INVALID); without either the call is ins_rk_step_f32.  Asynchronous. */
+int ins_rk_step_ext_f32(ins_rk32_t* rk, float visc, float* u, float* temp, float dt, void* stream);
+/* nsteps such steps (the fixed-Δt loop of solve_unsteady, solver.jl:74-83) in one call */
+int ins_rk_steps_ext_f32(ins_rk32_t* rk, float visc, float* u, float* temp, float dt, int nsteps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

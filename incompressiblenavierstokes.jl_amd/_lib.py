@@ -187,6 +187,13 @@ SIGNATURES = {
     "ins_tensorclosure_pullback_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "ins_divoftensor_f32": (C.c_int, [vp, vp, vp, vp]),
     "ins_divoftensor_adjoint_f32": (C.c_int, [vp, vp, vp, vp]),
+    "ins_apply_bc_temp_f32": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ins_convection_diffusion_temp_f32": (C.c_int, [vp, C.c_float, vp, vp, vp, vp]),
+    "ins_dissipation_f32": (C.c_int, [vp, C.c_float, C.c_float, vp, vp, vp, vp]),
+    "ins_gravity_f32": (C.c_int, [vp, C.c_int, C.c_float, vp, vp, vp]),
+    "ins_rk_set_temperature_f32": (C.c_int, [vp, vp]),
+    "ins_rk_step_ext_f32": (C.c_int, [vp, C.c_float, vp, vp, C.c_float, vp]),
+    "ins_rk_steps_ext_f32": (C.c_int, [vp, C.c_float, vp, vp, C.c_float, C.c_int, vp]),
     "ins_comm_unique_id": (C.c_int, [vp]),
     "ins_comm_create": (C.c_int, [C.c_int, C.c_int, vp, C.POINTER(vp)]),
     "ins_comm_create_local": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]),

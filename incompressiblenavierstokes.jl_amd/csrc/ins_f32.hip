@@ -35,6 +35,10 @@ int ins_k32g_momentum(const ins_grid* G, float visc, const float* u, float* F, h
 int ins_k32g_divergence(const ins_grid* G, const float* u, float* div, hipStream_t s);
 int ins_k32g_solve(const ins_grid* G, ins_poisson* ps64, double* p64, float* p, hipStream_t s);
 int ins_k32g_project(const ins_grid* G, ins_poisson* ps64, double* p64, float* u, float* p, hipStream_t s);
+// the temperature equation (any grid): csrc/ins_temp32.hip
+int ins_k32t_diffusion(const ins_grid* G, float visc, const float* u, float* diff, hipStream_t s);
+int ins_k32t_stage(const ins_grid* G, float a4, float coef, const float* u, const float* temp, const float* diff, const float* tempstart, int n,
+                   const float* coefs, const float* const* ks, float c_self, float* ktemp_out, float* temp_out, hipStream_t s);
 
 struct ins_poisson32 {
   const ins_grid* grid = nullptr;
@@ -70,6 +74,13 @@ struct ins_rk32 {
   float* p = nullptr;
   float* pu = nullptr;  // unpadded float copy of the stage pressure (in-register correction of the next stage's stencil kernel)
   float* ustart = nullptr;  // chained steps: the corrected start field of steps 2..K (the caller's array holds the uncorrected last stage velocity then)
+  // temperature equation (ins_rk_set_temperature_f32, ins_rk_step_ext_f32): scalar scratch allocated by the first step that carries a temperature
+  bool temp_on = false;
+  ins_temperature_desc_t td;
+  float* tempstart = nullptr;
+  float* tstage = nullptr;      // the one stage temperature buffer: stage temperatures alternate between it and the caller's array
+  float* diff = nullptr;        // scratch of dissipation! (vector field)
+  std::vector<float*> ktemp;    // nstage scalars
 };
 
 namespace {
@@ -523,6 +534,10 @@ extern "C" int ins_rk_destroy_f32(ins_rk32_t* rk) {
     if (b) (void)hipFree(b);
   if (rk->p) (void)hipFree(rk->p);
   if (rk->pu) (void)hipFree(rk->pu);
+  for (float* b : {rk->tempstart, rk->tstage, rk->diff})
+    if (b) (void)hipFree(b);
+  for (float* k : rk->ktemp)
+    if (k) (void)hipFree(k);
   delete rk;
   return INS_OK;
 }
@@ -658,7 +673,127 @@ extern "C" int ins_rk_steps_f32(ins_rk32_t* rk, float visc, float* u, float dt, 
   return INS_OK;
 }
 
-// maximum(abs, divergence(u)) over Ip (diagnostic; blocking)                              operators.jl:106-125
+// ---------------------------------------------------------------------------------------------- explicit Runge-Kutta with the temperature equation
+extern "C" int ins_rk_set_temperature_f32(ins_rk32_t* rk, const ins_temperature_desc_t* desc) {
+  INS_REQUIRE(rk, "null argument");
+  if (desc) {
+    INS_REQUIRE(desc->gdir >= 0 && desc->gdir < rk->grid->g.D, "gdir out of range");
+    rk->td = *desc;
+  }
+  rk->temp_on = desc != nullptr;
+  return INS_OK;
+}
+
+static int zalloc32(float** p, size_t bytes, hipStream_t s) {
+  if (*p) return INS_OK;
+  INS_HIP_TRY(hipMalloc(p, bytes));
+  INS_HIP_TRY(hipMemsetAsync(*p, 0, bytes, s));
+  return INS_OK;
+}
+
+// timestep!(method, stepper, Δt; cache) with `temp`, T = Float32                                  step_explicit_runge_kutta.jl:4-59
+// Per stage: ku_i = momentum(u) + gravity(temp) (:21), the temperature stage (:23-27, 39-44: one kernel, or operator by operator with
+// INS_DISABLE_TEMP32_STAGE), the combination of u (:35-38), ghost fill, project!, ghost fill (:47-49) and the ghost fill of the new stage temperature, which
+// is also the one the next stage (:19-20) or the end of the step (:55-56) asks for.  General grids run on the kernels of ins_f32g.hip and a wrapped solver,
+// all-periodic uniform boxes (wide ones too) on ins_momentum_f32 / k32_combine / ins_project_f32; the temperature kernels are those of ins_temp32.hip on both.
+// The caller's u is ustart for the whole step.  Stage temperatures alternate between the caller's array and one buffer so that the last stage lands in the
+// caller's array; where that makes the first stage write it, that stage reads tempstart, a copy taken after the first ghost fill.
+static int rk32_step_temp(ins_rk32* rk, float visc, float* u, float* temp, float dt, hipStream_t s) {
+  const ins_grid* G = rk->grid;
+  const GridDev& g = G->g;
+  const int ns = rk->nstage, D = g.D;
+  const long long nvec = G->ncell * D;
+  const size_t sbytes = (size_t)G->ncell * sizeof(float);
+  const bool general = !periodic_uniform(G);
+  const ins_temperature_desc_t& td = rk->td;
+  int rc;
+  for (int a = 0; a < D; ++a)
+    if (g.bc[a][0] == INS_BC_HALO || g.bc[a][1] == INS_BC_HALO) {
+      ins_set_error("ins_rk_step_ext_f32: slab (halo) grids run in fp64 only");
+      return INS_ERR_UNSUPPORTED;
+    }
+  if (general && !rk->ps->wrap64) {
+    ins_set_error("ins_rk_step_ext_f32: this grid needs a solver made by ins_poisson_wrap_f32");
+    return INS_ERR_UNSUPPORTED;
+  }
+  if ((rc = zalloc32(&rk->tempstart, sbytes, s)) || (rc = zalloc32(&rk->tstage, sbytes, s))) return rc;
+  if (td.dodissipation && (rc = zalloc32(&rk->diff, sbytes * D, s))) return rc;
+  if ((int)rk->ktemp.size() < ns) rk->ktemp.resize(ns, nullptr);
+  for (int i = 0; i < ns; ++i)
+    if ((rc = zalloc32(&rk->ktemp[i], sbytes, s))) return rc;
+  float val[6];
+  for (int q = 0; q < 6; ++q) val[q] = (float)td.val[q];
+  auto bc_u = [&](float* v) { return general ? ins_k32g_apply_bc_u(G, v, s) : bc_periodic(G, v, D, s); };
+  auto bc_temp = [&](float* t) { return ins_apply_bc_temp_f32(G, td.bc, val, t, s); };
+  const bool one_pass = !ins_opt(OPT_INS_DISABLE_TEMP32_STAGE);
+  const float a4 = (float)td.a4, a2 = (float)td.a2, dcoef = (float)td.diss_coef;
+
+  if ((rc = bc_u(u))) return rc;                                                                           // :19
+  if ((rc = bc_temp(temp))) return rc;                                                                     // :20
+  INS_HIP_TRY(hipMemcpyAsync(rk->tempstart, temp, sbytes, hipMemcpyDeviceToDevice, s));                    // state_copyto!(xstart, x)   :14
+  const float* cur = u;
+  const float* tin = (ns & 1) ? rk->tempstart : temp;
+  for (int i = 0; i < ns; ++i) {
+    float* outp = (i == ns - 1 && ns > 1) ? u : rk->ub[i & 1];
+    float* tout = ((ns - 1 - i) & 1) ? rk->tstage : temp;
+    if ((rc = ins_momentum_f32(G, visc, cur, rk->ku[i], s))) return rc;                                    // :21
+    if ((rc = ins_gravity_f32(G, td.gdir, a2, tin, rk->ku[i], s))) return rc;
+    float tcoef[INS_MAX_STAGES];
+    const float* tk[INS_MAX_STAGES];
+    for (int j = 0; j <= i; ++j) {
+      tcoef[j] = dt * (float)rk->A[i * ns + j];
+      tk[j] = rk->ktemp[j];
+    }
+    if (one_pass) {                                                                                        // :23-27, 39-44
+      if (td.dodissipation && (rc = ins_k32t_diffusion(G, visc, cur, rk->diff, s))) return rc;
+      const bool later = ins_rk_needed_later(rk->A.data(), ns, i);
+      if ((rc = ins_k32t_stage(G, a4, dcoef, cur, tin, td.dodissipation ? rk->diff : nullptr, rk->tempstart, i, tcoef, tk, tcoef[i],
+                               later ? rk->ktemp[i] : nullptr, tout, s)))
+        return rc;
+    } else {
+      INS_HIP_TRY(hipMemsetAsync(rk->ktemp[i], 0, sbytes, s));
+      if ((rc = ins_convection_diffusion_temp_f32(G, a4, cur, tin, rk->ktemp[i], s))) return rc;
+      if (td.dodissipation && (rc = ins_dissipation_f32(G, visc, dcoef, cur, rk->diff, rk->ktemp[i], s))) return rc;
+      Comb32 cb;
+      cb.n = i + 1;
+      for (int j = 0; j <= i; ++j) {
+        cb.coef[j] = tcoef[j];
+        cb.k[j] = tk[j];
+      }
+      hipLaunchKernelGGL(k32_combine, dim3((unsigned)std::min<long long>((G->ncell + 255) / 256, 8192)), dim3(256), 0, s, G->ncell, rk->tempstart, tout, cb);
+      INS_LAUNCH_CHECK();
+    }
+    Comb32 cb;
+    cb.n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), (const float*)nullptr, cb.coef, cb.k);
+    hipLaunchKernelGGL(k32_combine, dim3((unsigned)std::min<long long>((nvec + 255) / 256, 8192)), dim3(256), 0, s, nvec, u, outp, cb);  // :35-38
+    INS_LAUNCH_CHECK();
+    if (general && (rc = bc_u(outp))) return rc;                                                           // :47
+    if ((rc = ins_project_f32(G, rk->ps, outp, rk->p, s))) return rc;                                      // :48-49 (periodic boxes: fills the ghosts itself)
+    if (general && (rc = bc_u(outp))) return rc;
+    if ((rc = bc_temp(tout))) return rc;
+    cur = outp;
+    tin = tout;
+  }
+  if (ns == 1) INS_HIP_TRY(hipMemcpyAsync(u, rk->ub[0], nvec * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return INS_OK;
+}
+
+extern "C" int ins_rk_steps_ext_f32(ins_rk32_t* rk, float visc, float* u, float* temp, float dt, int nsteps, void* stream) {
+  INS_REQUIRE(rk && u && nsteps >= 0, "null or bad argument");
+  INS_REQUIRE(rk->temp_on == (temp != nullptr), "a temperature field needs ins_rk_set_temperature_f32 and vice versa");
+  if (!temp) return ins_rk_steps_f32(rk, visc, u, dt, nsteps, stream);
+  for (int n = 0; n < nsteps; ++n) {
+    int rc = rk32_step_temp(rk, visc, u, temp, dt, as_stream(stream));
+    if (rc) return rc;
+  }
+  return INS_OK;
+}
+
+extern "C" int ins_rk_step_ext_f32(ins_rk32_t* rk, float visc, float* u, float* temp, float dt, void* stream) {
+  return ins_rk_steps_ext_f32(rk, visc, u, temp, dt, 1, stream);
+}
+
+// maximum(abs, divergence(u)) over Ip (diagnostic; blocking)                            operators.jl:106-125
 extern "C" int ins_max_abs_divergence_f32(const ins_grid_t* G, ins_poisson32_t* ps, const float* u, float* out, void* stream) {
   INS_REQUIRE(G && ps && u && out, "null argument");
   hipStream_t s = as_stream(stream);

@@ -142,6 +142,7 @@ void ins_set_error(const char* fmt, ...);
   X(INS_F32_FP64_SPECTRA)        \
   X(INS_F32_HIPFFT_PROJECT)      \
   X(INS_F32_SPLIT_GRADIENT)      \
+  X(INS_DISABLE_TEMP32_STAGE)    \
   X(INS_FFT_ALLOW_RESET)         \
   X(INS_DISABLE_ADJ_TILED)     \
   X(INS_DISABLE_FILTER_TILED)

@@ -1,6 +1,7 @@
 """Host mirror of the `_f32` entry-point family (include/ins_hip.h; csrc/ins_f32.hip, csrc/ins_f32g.hip): the reference with `T = Float32`
 (docs/src/manual/precision.md:3-16, examples/DecayingTurbulence3D.jl:16): all-periodic uniform boxes on the spectral solver, every other grid
-(walls, symmetric / pressure sides, stretched spacings; constant boundary data) on `psolver_wrap32` around an fp64 solver.
+(walls, symmetric / pressure sides, stretched spacings; constant boundary data) on `psolver_wrap32` around an fp64 solver.  The temperature equation
+(csrc/ins_temp32.hip; examples/RayleighBenard3D.jl:16) rides on both: its operators, and `timestep32_` / `timesteps32_` with `temp=`.
 
 Fields are torch.float32 tensors in the reference layout; `setup` is the ordinary (fp64-metric) Setup."""
 import ctypes as C
@@ -57,11 +58,82 @@ def apply_bc_p32_(p, setup):
     return p
 
 
-def momentum32_(F, u, setup):
-    """momentum!(F, u, nothing, t, setup) with T = Float32 (operators.jl:967-976)."""
+def momentum32_(F, u, setup, temp=None):
+    """momentum!(F, u, temp, t, setup) with T = Float32 (operators.jl:967-976): with `temp` the gravity term is added."""
     D = setup.grid.dimension
     _lib.call("ins_momentum_f32", setup.handle, float(1.0 / setup.Re), _ptr(setup, u, D), _ptr(setup, F, D), setup.stream)
+    if temp is not None:
+        gravity32_(F, temp, setup)
     return F
+
+
+# ---- temperature equation (csrc/ins_temp32.hip): the Float32 twins of operators.apply_bc_temp_ ... gravity_, constant boundary data
+def _temp_desc(setup):
+    """ins_temperature_desc_t of setup.temperature, built as time_steppers._native_ext builds it; callable Dirichlet data is refused."""
+    from .boundary_conditions import DirichletBC
+    from .time_steppers import _TempDesc
+
+    T = setup.temperature
+    if T is None:
+        raise ValueError("the setup has no temperature equation (Setup(temperature=temperature_equation(...)))")
+    desc = _TempDesc(a2=T.α2, a4=T.α4, diss_coef=setup.Re * T.α1 / T.γ, gdir=int(T.gdir), dodissipation=int(T.dodissipation))
+    for be in range(setup.grid.dimension):
+        for side in range(2):
+            bc = T.boundary_conditions[be][side]
+            desc.bc[2 * be + side] = bc.code
+            if isinstance(bc, DirichletBC) and bc.u is not None:
+                if callable(bc.u):
+                    raise NotImplementedError("the _f32 family takes constant boundary data (callable temperature DirichletBC values: use the fp64 "
+                                              "entry points)")
+                desc.val[2 * be + side] = float(bc.u)
+    return desc
+
+
+def apply_bc_temp32_(temp, setup):
+    """apply_bc_temp!(temp, t, setup) with T = Float32, in place (boundary_conditions.jl:236-246)."""
+    desc = _temp_desc(setup)
+    vals = (C.c_float * 6)(*[desc.val[q] for q in range(6)])
+    _lib.call("ins_apply_bc_temp_f32", setup.handle, desc.bc, vals, _ptr(setup, temp, 0), setup.stream)
+    return temp
+
+
+def convection_diffusion_temp32_(c, u, temp, setup):
+    """operators.jl:712-737 with T = Float32 (adds to c)"""
+    _lib.call("ins_convection_diffusion_temp_f32", setup.handle, float(_temp_desc(setup).a4), _ptr(setup, u, setup.grid.dimension), _ptr(setup, temp, 0),
+              _ptr(setup, c, 0), setup.stream)
+    return c
+
+
+def dissipation32_(diss, diff, u, setup):
+    """operators.jl:791-814 with T = Float32 (adds to diss; `diff` is scratch: it receives diffusion(u), zeros off the degrees of freedom)"""
+    D = setup.grid.dimension
+    _lib.call("ins_dissipation_f32", setup.handle, float(1.0 / setup.Re), float(_temp_desc(setup).diss_coef), _ptr(setup, u, D), _ptr(setup, diff, D),
+              _ptr(setup, diss, 0), setup.stream)
+    return diss
+
+
+def gravity32_(F, temp, setup):
+    """operators.jl:914-931 with T = Float32 (adds to F)"""
+    desc = _temp_desc(setup)
+    _lib.call("ins_gravity_f32", setup.handle, int(desc.gdir), float(desc.a2), _ptr(setup, temp, 0), _ptr(setup, F, setup.grid.dimension), setup.stream)
+    return F
+
+
+def temperaturefield32(setup, tempfunc):
+    """temperaturefield(setup, tempfunc) with T = Float32 (initializers.jl:48-57): `tempfunc(x, y[, z])` on the pressure points (evaluated in double on
+    the host, rounded once), then the ghost fill."""
+    g = setup.grid
+    D = g.dimension
+    host = np.zeros(g.N, dtype=np.float64, order="F")
+    xs = []
+    for be in range(D):
+        lo, hi = g.Ip[be]
+        shape = [1] * D
+        shape[be] = hi - lo
+        xs.append(np.asarray(g.xp[be][lo:hi]).reshape(shape))
+    sl = tuple(slice(lo, hi) for lo, hi in g.Ip)
+    host[sl] = np.broadcast_to(tempfunc(*xs), tuple(hi - lo for lo, hi in g.Ip))
+    return apply_bc_temp32_(to_f32(setup, host), setup)
 
 
 class psolver_spectral32:
@@ -244,15 +316,37 @@ class ERKCache32:
                 pass
 
 
-def timestep32_(cache, u, Δt):
-    """One explicit RK step of the float32 field `u` in place (step_explicit_runge_kutta.jl:4-59)."""
+def _set_temperature32(cache, temp):
+    """Hand the temperature descriptor of the cache's setup to its native handle (once per cache)."""
     s = cache.setup
-    _lib.call("ins_rk_step_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), float(Δt), s.stream)
-    return u
+    if s.temperature is None:
+        raise ValueError("timestep32_ with `temp` needs a setup with a temperature equation")
+    desc = _temp_desc(s)
+    if not getattr(cache, "_has_temp", False):
+        _lib.call("ins_rk_set_temperature_f32", cache._handle, C.byref(desc))
+        cache._has_temp = True
+    return _ptr(s, temp, 0)
 
 
-def timesteps32_(cache, u, Δt, nsteps):
-    """`nsteps` explicit RK steps of size Δt of the float32 field `u` in place: the fixed-Δt loop of solve_unsteady (solver.jl:74-83) as one native call."""
+def timestep32_(cache, u, Δt, temp=None):
+    """One explicit RK step of the float32 field `u` in place (step_explicit_runge_kutta.jl:4-59); with `temp` (a float32 scalar field; the setup has a
+    temperature equation) the temperature is advanced with it and (u, temp) is returned."""
     s = cache.setup
-    _lib.call("ins_rk_steps_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), float(Δt), int(nsteps), s.stream)
-    return u
+    if temp is None:
+        _lib.call("ins_rk_step_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), float(Δt), s.stream)
+        return u
+    tp = _set_temperature32(cache, temp)
+    _lib.call("ins_rk_step_ext_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), tp, float(Δt), s.stream)
+    return u, temp
+
+
+def timesteps32_(cache, u, Δt, nsteps, temp=None):
+    """`nsteps` explicit RK steps of size Δt of the float32 field `u` in place: the fixed-Δt loop of solve_unsteady (solver.jl:74-83) as one native call;
+    with `temp` as `timestep32_`."""
+    s = cache.setup
+    if temp is None:
+        _lib.call("ins_rk_steps_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), float(Δt), int(nsteps), s.stream)
+        return u
+    tp = _set_temperature32(cache, temp)
+    _lib.call("ins_rk_steps_ext_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), tp, float(Δt), int(nsteps), s.stream)
+    return u, temp
