@@ -264,6 +264,13 @@ int ins_rk_set_bodyforce(ins_rk_t* rk, const double* force);
 int ins_dbg_stage_rhs_used(const ins_rk_t* rk, int64_t* launches);
 int ins_dbg_stage_rhs(ins_rk_t* rk, double visc, const double* u_in, const double* pI, const double* ustart, const double* kterm, double coef_k,
                       double self_in, double coef_self, double* ustar, double* rhs, int32_t* used, void* stream);
+/* The same route one pass further (256-wide rows; INS_DISABLE_STAGE_XFWD=1 switches it off): the stage kernel stores the half-complex x-spectrum of that right-hand
+ * side into the solver's spectrum buffer and the solve starts at its y pass.  ins_dbg_stage_xfwd_used: how many of the launches ins_dbg_stage_rhs_used counts
+ * stored the spectrum.  ins_dbg_stage_xfwd: ins_dbg_stage_rhs's launch on this route (pI required); spec (device) receives n2 * n1 rows of kxs complex numbers,
+ * kx = 0 .. n0/2 in natural order, kxs = n0/2 + 1 rounded up to a multiple of 8, when *used comes back 1; nothing is launched otherwise. */
+int ins_dbg_stage_xfwd_used(const ins_rk_t* rk, int64_t* launches);
+int ins_dbg_stage_xfwd(ins_rk_t* rk, double visc, const double* u_in, const double* pI, const double* ustart, const double* kterm, double coef_k,
+                       double self_in, double coef_self, double* ustar, double* spec, int32_t* used, void* stream);
 /* ins_dbg_stage_carry_used: how many stage kernels this integrator has enqueued that also stored a carried combination (RK44 on the fused periodic path:
  * the second stage stores the part of the last stage's combination it has in registers; INS_DISABLE_STAGE_CARRY=1 switches the route off). */
 int ins_dbg_stage_carry_used(const ins_rk_t* rk, int64_t* launches);

@@ -129,6 +129,8 @@ SIGNATURES = {
     "ins_dbg_stage_rhs_used": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "ins_dbg_stage_carry_used": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "ins_dbg_stage_rhs": (C.c_int, [vp, C.c_double, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, C.POINTER(C.c_int32), vp]),
+    "ins_dbg_stage_xfwd_used": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+    "ins_dbg_stage_xfwd": (C.c_int, [vp, C.c_double, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, C.POINTER(C.c_int32), vp]),
     "ins_rk_pressure": (C.c_int, [vp, C.POINTER(vp)]),
     "ins_rk_stage_force": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
     "ins_rk_set_temperature": (C.c_int, [vp, vp]),

@@ -59,8 +59,42 @@ struct TExt {
 //   z  w*(k-1) is carried along the march; the march starts one plane early (k0-1, nothing stored) so the first plane of a chunk has it.
 // CARRY (CORR 1, a.epi.carry_out; ins_rk_terms.h, RkCarryPlan): the kernel also stores S = ca0·s + ca1·raw + ca2·u* at the cells it stores u* at, s = the
 // combination before coef_self·f is added, raw = the uncorrected stencil input (kept alive to the stores: 12 more registers, hence a flag of its own).
-template <typename T, int R, int XW, bool FUSE, int CORR, bool SKEL = false, int NW = 4, bool EXTRA = false, bool RHS = false, bool CARRY = false>
+// XF (RHS, CORR 1, fp64, 2 rows, 4 wavefronts per 256-wide row; a.epi.spec_out instead of rhs_out): the kernel stores the half-complex x-spectrum of that right-hand
+// side, the array k_xfwd<8, 4, XSRC_PI> would make of it, and the solve starts at its y pass.  After the plane's barrier a lane holds one point of k_xfwd's packing,
+// z[i] = (rhs(i, jb0), rhs(i, jb0+1)), i = 64 wx + lane.  The first radix-4 stage of the 256-point decimation-in-frequency transform joins the same lane of the four
+// wavefronts of a row and leaves branch wx in wavefront wx; the other three stages are a 64-point transform inside one wavefront (no workgroup barrier); frequency s
+// ends at position digit-reverse(s) (pos_of_freq<8>, ins_fft.hip).  To keep the one barrier per plane the transform lags: iteration k, behind its barrier,
+//   A  writes z of plane k to X1[k & 1];
+//   B  reads the four first-stage inputs of plane k-1 from X1[(k-1) & 1] (written before this barrier), does output wx of the butterfly, runs the three wave-local stages
+//      in place in the wavefront's own quarter of X2[(k-1) & 1] (one point per lane: four reads and one write per stage, ordered by the LDS queue of the wavefront);
+//   C  reads Z[pos(s)], Z[pos(N-s)] of plane k-2 from X2[k & 1] (finished before this barrier), separates the two real rows and stores them.
+// Every slot is written again two iterations later, behind the next barrier.  Two drain iterations end a chunk; the plane below the chunk enters nothing.
+// The finished transform is stored rotated inside groups of 16 (fft_swz, ins_fft.hip: the reads of step C are 1 KB apart otherwise).  The per-lane twiddles (w^m of each stage, the products
+// k_xfwd forms) are computed once and read back per plane from LDS, each lane its own entry: 12 registers less across the march.
+struct Xc {
+  double x, y;
+};
+__device__ __forceinline__ Xc xc_mul(Xc a, Xc b) { return Xc{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+// output m of the radix-4 decimation-in-frequency butterfly (fft_dif, ins_fft.hip): 0: (a0+a2)+(a1+a3), 1: (a0-a2)-i(a1-a3), 2: (a0+a2)-(a1+a3), 3: (a0-a2)+i(a1-a3)
+__device__ __forceinline__ Xc xc_bfly(Xc a0, Xc a1, Xc a2, Xc a3, int m) {
+  const bool odd = m & 1, neg = m & 2;
+  const double s2 = odd ? -1.0 : 1.0;  // (a sign flip is exact: the sums round as the differences do)
+  const Xc p{a0.x + s2 * a2.x, a0.y + s2 * a2.y}, q0{a1.x + s2 * a3.x, a1.y + s2 * a3.y};
+  Xc q = odd ? Xc{q0.y, -q0.x} : q0;
+  const double s1 = neg ? -1.0 : 1.0;
+  return Xc{p.x + s1 * q.x, p.y + s1 * q.y};
+}
+__device__ __forceinline__ int xf_swz(int i) { return (i & ~15) | ((i + ((i >> 4) & 3) + 4 * ((i >> 6) & 3)) & 15); }
+__device__ __forceinline__ int xf_pos(int s) { return ((s & 3) << 6) | (((s >> 2) & 3) << 4) | (((s >> 4) & 3) << 2) | ((s >> 6) & 3); }  // pos_of_freq<8>
+__device__ __forceinline__ void xf_wave_sync() {  // LDS writes of this wavefront before its later LDS reads (program order in the LDS queue; this pins the compiler)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
+
+template <typename T, int R, int XW, bool FUSE, int CORR, bool SKEL = false, int NW = 4, bool EXTRA = false, bool RHS = false, bool CARRY = false, bool XF = false>
 __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a) {
+  static_assert(!XF || (RHS && CORR == 1 && sizeof(T) == 8 && R == 2 && XW == 4 && (NW == 4 || NW == 8)), "x-forward transform in the stage kernel: 256-wide rows, fp64");
   static_assert(!RHS || (FUSE && CORR <= 1 && !SKEL && !EXTRA), "right-hand side in the stage kernel: fused epilogue, periodic box, no extra terms");
   static_assert(!CARRY || (FUSE && CORR == 1 && !SKEL && !EXTRA && NW <= 8 && sizeof(T) == 8), "carried combination: the fp64 periodic correcting stage kernel");
   constexpr unsigned EB = (unsigned)sizeof(T);  // element bytes
@@ -81,6 +115,10 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
   }
   __shared__ T rhs_lds_s[RHS ? 2 * NW * R : 1];  // RHS: u* of lane 63, [plane parity][wavefront][row]
   T* const rhs_lds = rhs_lds_s;
+  constexpr int XSLOT = (NW / 4) * 256;                   // XF: one plane's rows of a workgroup, 256 complex each
+  __shared__ __align__(16) Xc xf_x1[XF ? 2 * XSLOT : 1];  // XF: z, [plane parity][wavefront row][column]
+  __shared__ __align__(16) Xc xf_x2[XF ? 2 * XSLOT : 1];  // XF: the transform, [plane parity][wavefront row][fft_swz(position)]
+  __shared__ __align__(16) Xc xf_tw[XF ? 6 * 64 : 1];     // XF: per-lane twiddles: [wx][lane] of the first stage, [lane] of the stages Q = 16 and Q = 4
   const int lane = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.y);
   const int wx = wave % XW, wy = wave / XW;
@@ -93,7 +131,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
   const int kw0 = RHS ? k0 - 1 : k0;  // first plane of the march
   if (x0 >= n0 || jb0 >= n1) {  // wavefront outside the box: it only keeps the workgroup's barrier count (one per plane)
     if (a.bar || RHS)
-      for (int k = kw0; k < k1; ++k) __builtin_amdgcn_s_barrier();
+      for (int k = kw0; k < k1 + (XF ? 2 : 0); ++k) __builtin_amdgcn_s_barrier();  // (XF: and one per drain iteration)
     return;
   }
   const long long sz = (long long)N0 * N1;
@@ -332,6 +370,74 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
     }
   };
 
+  // XF: one iteration of the lagging transform (steps A, B, C above), behind the barrier of iteration k; z = this wavefront's point of plane k
+  const int xf_row = wy * 256;
+  if constexpr (XF) {
+    const Xc* twg = static_cast<const Xc*>((const void*)a.epi.spec_tw);
+    auto pw = [](Xc w1, int m) {  // w^m as fft_dif forms it
+      const Xc w2 = xc_mul(w1, w1), w3 = xc_mul(w2, w1);
+      return m == 0 ? Xc{1.0, 0.0} : (m == 1 ? w1 : (m == 2 ? w2 : w3));
+    };
+    xf_tw[wx * 64 + lane] = pw(twg[lane], wx);                           // L = 256: W_256^(lane m), m = wx
+    xf_tw[256 + lane] = pw(twg[4 * (lane & 15)], lane >> 4);             // L = 64:  W_64^(j m), j = lane % 16, m = lane / 16
+    xf_tw[320 + lane] = pw(twg[16 * (lane & 3)], (lane >> 2) & 3);       // L = 16:  W_16^(j m), j = lane % 4, m = (lane / 4) % 4
+  }
+  auto xf_step = [&](int k, T z0, T z1) {
+    if constexpr (XF) {
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      if (k >= k0 && k < k1) xf_x1[(k & 1) * XSLOT + xf_row + 64 * wx + ln] = Xc{z0, z1};
+      if (k - 1 >= k0 && k - 1 < k1) {
+        const Xc* x = xf_x1 + ((k - 1) & 1) * XSLOT + xf_row;
+        Xc y = xc_bfly(x[ln], x[ln + 64], x[ln + 128], x[ln + 192], wx);
+        if (wx) y = xc_mul(y, xf_tw[wx * 64 + ln]);
+        // (ln: the lane index behind a compiler barrier, so that the dozen LDS addresses derived from it are formed here, per plane, and hold no registers across the march)
+        Xc* zb = xf_x2 + ((k - 1) & 1) * XSLOT + xf_row + 64 * wx;  // this wavefront's quarter; only the last stage's output is stored rotated
+        zb[ln] = y;
+        xf_wave_sync();
+        {  // Q = 16
+          const Xc* e = zb + (ln & 15);
+          y = xc_bfly(e[0], e[16], e[32], e[48], ln >> 4);
+          y = xc_mul(y, xf_tw[256 + ln]);
+          zb[ln] = y;
+        }
+        xf_wave_sync();
+        {  // Q = 4
+          const Xc* e = zb + (ln & ~12);
+          y = xc_bfly(e[0], e[4], e[8], e[12], (ln >> 2) & 3);
+          y = xc_mul(y, xf_tw[320 + ln]);
+          zb[ln] = y;
+        }
+        xf_wave_sync();
+        {  // Q = 1 (every lane has read its four inputs when the wavefront's write is issued, so the rotated position may be another lane's input)
+          const Xc* e = zb + (ln & ~3);
+          y = xc_bfly(e[0], e[1], e[2], e[3], ln & 3);
+          zb[xf_swz(64 * wx + ln) - 64 * wx] = y;
+        }
+      }
+      if (k - 2 >= k0 && k - 2 < k1) {
+        // the two real rows of plane k-2 (k_xfwd's expressions): A[s] = (Z[s] + conj Z[N-s]) / 2, B[s] = (Z[s] - conj Z[N-s]) / (2i).  Wavefronts 0, 1 store
+        // row jb0 (s = 0 .. 127), wavefronts 2, 3 row jb0+1; the lanes with s = 0 also store s = 128.
+        const Xc* zr = xf_x2 + (k & 1) * XSLOT + xf_row;
+        const int s = (64 * wx + ln) & 127;
+        const bool rowb = wx >= 2;
+        const unsigned kxs = (unsigned)a.epi.spec_kxs;
+        const rsrc_t rs = plane_rsrc(static_cast<double*>((void*)a.epi.spec_out) + 2LL * (k - 3) * kxs * n1, kxs * (unsigned)n1 * 16u);
+        const unsigned soff = (unsigned)(jb0 + (rowb ? 1 : 0)) * kxs * 16u;
+        auto sep_store = [&](int sk, int sm) {
+          const Xc zk = zr[xf_swz(xf_pos(sk))], zm = zr[xf_swz(xf_pos(sm))];
+          const Xc av{0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y)}, bv{0.5 * (zk.y + zm.y), -0.5 * (zk.x - zm.x)};
+          const Xc o = rowb ? bv : av;
+          v4u v;
+          v.x = (unsigned)__double2loint(o.x), v.y = (unsigned)__double2hiint(o.x), v.z = (unsigned)__double2loint(o.y), v.w = (unsigned)__double2hiint(o.y);
+          __builtin_amdgcn_raw_buffer_store_b128(v, rs, (unsigned)sk * 16u, soff, 0);
+        };
+        sep_store(s, (256 - s) & 255);
+        if (s == 0) sep_store(128, 128);
+      }
+    }
+  };
+
   // One output plane.  C = plane k, Nx = plane k+1 (both complete, corrected).  As soon as a row of C has been consumed its
   // registers are re-loaded with the same row of plane `kload` (= k+2, the next plane this buffer has to hold), so the
   // prefetch of plane k+2 is in flight during the whole of plane k without a third register plane.
@@ -545,6 +651,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
       T* ro = static_cast<T*>((void*)a.epi.rhs_out) + (long long)(k - 1) * n0 * n1;
       const rsrc_t rr_ = plane_rsrc(ro, qbytes);
       const T om = (T)a.om;
+      T zz[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const T ul = rhs_lds[((k & 1) * NW + lw) * R + r];
@@ -552,8 +659,10 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
         d += (us_u[r] - prev_h(us_u[r], ul)) * (T)a.rdiv[0];
         d += dvs[r] * (T)a.rdiv[1];
         d += dws[r] * (T)a.rdiv[2];
-        if (st && xout && jb0 + r < n1) stb(rr_, (unsigned)min(ci, n0 - 1) * EB, (unsigned)(min(jb0 + r, n1 - 1) * n0) * EB, d * om);
+        zz[r] = d * om;
+        if (!XF && st && xout && jb0 + r < n1) stb(rr_, (unsigned)min(ci, n0 - 1) * EB, (unsigned)(min(jb0 + r, n1 - 1) * n0) * EB, zz[r]);
       }
+      if constexpr (XF) xf_step(k, zz[0], zz[1]);  // (st == (k >= k0): the plane below the chunk enters nothing)
     }
     if constexpr (TMK) {
       if (tm) {
@@ -637,6 +746,14 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 2) void k_flux64(FluxArgs a
       load_p(Pb, Hb, min(k + 3, k1 + 1));
       body(P0, P1, TE0, TE1, k, min(k + 2, k1), k >= k0);
       if (++k >= k1) break;
+    }
+    if constexpr (XF) {  // the two planes still in the pipeline
+      for (int kd = k1; kd < k1 + 2; ++kd) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+        xf_step(kd, (T)0, (T)0);
+      }
     }
   }
 }
@@ -732,7 +849,7 @@ int launch(const ins_grid* G, FluxArgs& a, int corr_mode, int part, hipStream_t 
 }
 
 // the instantiations that also write Ω·div(u*) (a.epi.rhs_out): fp64, whole rows per workgroup, every plane in one launch
-template <int R, int XW, int NW, int CORR, bool CARRY = false>
+template <int R, int XW, int NW, int CORR, bool CARRY = false, bool XF = false>
 int launch_rhs(const ins_grid* G, FluxArgs& a, hipStream_t s) {
   const GridDev& g = G->g;
   a.ntx = 1;
@@ -742,7 +859,7 @@ int launch_rhs(const ins_grid* G, FluxArgs& a, hipStream_t s) {
   a.kB = 0;
   a.ntz = cdiv(a.k_hi - a.k_lo, a.zc);
   const unsigned nb = (unsigned)(8LL * ((a.nty + 7) / 8) * a.ntz);
-  hipLaunchKernelGGL((k_flux64<double, R, XW, true, CORR, false, NW, false, true, CARRY>), dim3(nb), dim3(64, NW, 1), 0, s, a);
+  hipLaunchKernelGGL((k_flux64<double, R, XW, true, CORR, false, NW, false, true, CARRY, XF>), dim3(nb), dim3(64, NW, 1), 0, s, a);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
@@ -846,6 +963,16 @@ bool ins_flux64_stage_rhs_supported(const ins_grid* G, int corr_mode) {
   return t.rows == 2 && ((t.xw == 3 && t.nw == 6) || ((t.xw == 2 || t.xw == 4) && (t.nw == 4 || t.nw == 8)));
 }
 
+// ... and whether it stores the x-spectrum of that right-hand side instead (XF; INS_DISABLE_STAGE_XFWD=1: never): the right-hand-side route holds, the rows are 256
+// wide and the tile shape is 2 rows x 4 wavefronts side by side, 4 or 8 wavefronts per workgroup.  The solver's half (own x pass in front of the y pass) is
+// ins_poisson_stage_spec_possible's.  128- and 192-wide rows would start with a radix-2 / radix-3 stage across wavefronts: not built, they keep the array.
+bool ins_flux64_stage_xfwd_supported(const ins_grid* G, int corr_mode) {
+  if (ins_opt(OPT_INS_DISABLE_STAGE_XFWD) || corr_mode != 1 || !ins_flux64_stage_rhs_supported(G, corr_mode)) return false;
+  if (G->g.N[0] - 2 != 256 || (G->g.N[1] & 1)) return false;
+  const TileShape t = tile_shape(G, corr_mode, false, false, true);
+  return t.rows == 2 && t.xw == 4 && (t.nw == 4 || t.nw == 8);
+}
+
 // A correcting stage (corr_mode 1, fp64, every plane) can also store a carried combination (RkEpi::carry_out): this file's kernel runs it, in the default 2-row
 // shape with 4, 6 or 8 wavefronts (the 16-wavefront form has half the registers).
 bool ins_flux64_stage_carry_supported(const ins_grid* G) {
@@ -878,7 +1005,8 @@ static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, con
     a.epi.tstage = nullptr;
   }
   const bool ext = epi && (epi->extra || epi->gtemp || epi->wout || epi->tstage);
-  const bool want_rhs = epi && epi->rhs_out;
+  const bool want_spec = epi && epi->spec_out;
+  const bool want_rhs = epi && (epi->rhs_out || want_spec);
   const TileShape ts = tile_shape(G, corr_mode, sizeof(T) == 4, ext, want_rhs);
   const int xw = ts.xw, rows = ts.rows, nw = ts.nw, zc = ts.zc;
   constexpr bool F32 = sizeof(T) == 4;
@@ -927,6 +1055,11 @@ static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, con
       ins_set_error("stage kernel asked for the Poisson right-hand side while u* overwrites one of its inputs");
       return INS_ERR_INVALID;
     }
+    if (want_spec && (epi->rhs_out || F32 || part != 0 || !ins_flux64_stage_xfwd_supported(G, corr_mode) || !epi->spec_tw || epi->spec_kxs < 129 ||
+                      (const void*)epi->spec_out == (const void*)pI)) {
+      ins_set_error("stage kernel asked for the x-spectrum of the Poisson right-hand side on a box, tile shape or buffer it does not write it for");
+      return INS_ERR_UNSUPPORTED;
+    }
     if constexpr (!F32) {
       if (part == 0 && ins_flux64_stage_rhs_supported(G, corr_mode)) {
         a.rdiv[0] = 1.0 / G->desc.dx[0][1];
@@ -934,6 +1067,10 @@ static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, con
         a.rdiv[2] = 1.0 / G->desc.dx[2][1];
         a.om = G->desc.dx[0][1] * G->desc.dx[1][1] * G->desc.dx[2][1];
         if (corr_mode == 0) return launch_rhs<4, 2, 4, 0>(G, a, s);
+        if (want_spec) {
+          if (carry) return nw == 8 ? launch_rhs<2, 4, 8, 1, true, true>(G, a, s) : launch_rhs<2, 4, 4, 1, true, true>(G, a, s);
+          return nw == 8 ? launch_rhs<2, 4, 8, 1, false, true>(G, a, s) : launch_rhs<2, 4, 4, 1, false, true>(G, a, s);
+        }
         if (carry) {
           if (xw == 3) return launch_rhs<2, 3, 6, 1, true>(G, a, s);
           if (xw == 4) return nw == 8 ? launch_rhs<2, 4, 8, 1, true>(G, a, s) : launch_rhs<2, 4, 4, 1, true>(G, a, s);

@@ -114,6 +114,7 @@ void ins_set_error(const char* fmt, ...);
   X(INS_DISABLE_FDM_FOLDFUSE)    \
   X(INS_DISABLE_INKERNEL_CORR)   \
   X(INS_DISABLE_STAGE_RHS)       \
+  X(INS_DISABLE_STAGE_XFWD)      \
   X(INS_DISABLE_STAGE_CARRY)     \
   X(INS_RK_KEEP_K)               \
   X(INS_DISABLE_EXT_FUSED)       \
@@ -249,6 +250,7 @@ struct ins_poisson {
   size_t work_bytes = 0;
   hipStream_t plan_stream = nullptr;
   int kxs = 0;              // own routes: row stride of phat (kmax[0] rounded up to 8 complex = 128 B)
+  bool spec_pending = false;  // a stage kernel has been handed phat for the x-spectrum of its right-hand side (ins_poisson_stage_spec) and no solve has consumed it yet
   double* tw = nullptr;     // z twiddles
   double* tw_x = nullptr;   // x / y twiddles (own routes)
   double* tw_y = nullptr;
@@ -286,6 +288,7 @@ struct ins_rk {
   ins_rk_ext* ext = nullptr;
   long long stage_carry_launches = 0;  // stage kernels enqueued that stored a carried combination (ins_dbg_stage_carry_used)
   long long stage_rhs_launches = 0;  // stage kernels enqueued that wrote the Poisson right-hand side themselves (ins_dbg_stage_rhs_used)
+  long long stage_xfwd_launches = 0;  // those of them that stored its x-spectrum instead of the real-space array (ins_dbg_stage_xfwd_used)
   bool profiling = false;
   std::vector<hipEvent_t> prof_events;  // (start, stop) pairs around momentum launches
   void* step_graph = nullptr;           // launch-bound boxes: one step of ins_rk_steps_f64 captured as a hipGraph (ins_rk.hip)
@@ -320,6 +323,10 @@ struct RkEpi {
                             // ca[2]·u* is stored here, s = the combination before coef_self·f is added.  An array no input of the launch lives in
   double ca[3];
   double* rhs_out;          // optional (ins_flux64_stage_rhs_supported): Ω·div(u*) of the stored stage velocity, unpadded n^3 (never the pressure input pI)
+  double* spec_out;         // optional (ins_flux64_stage_xfwd_supported; instead of rhs_out): the half-complex x-spectrum of that right-hand side, the layout k_xfwd
+                            // writes (kx 0 .. n0/2 natural, spec_kxs complex per row), into the solver's phat; spec_tw: the x twiddle table (n0 complex)
+  const double* spec_tw;
+  int spec_kxs;
   const double* extra;      // optional vector field added to the stage force before it is used and stored (closure term: ins_rk_ext.hip)
   const double* gtemp;      // optional temperature field: gravity! is added to component gdir of the stage force (ga2 = α2)
   double ga2;
@@ -386,10 +393,17 @@ int ins_k_project_fdm_solve_only(const ins_grid* G, ins_poisson* ps, const doubl
 int ins_k_project_periodic_fused_2d(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s);
 bool ins_poisson_own2d(const ins_poisson* ps);
 // rhs != nullptr (own-FFT routes): the right-hand side Ω·div(u) is already in that buffer (the stage kernel wrote it) and the x pass reads it instead of u
-int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s, const double* rhs = nullptr);
+// from_spec: a stage kernel has stored the x-spectrum of the right-hand side in phat (ins_poisson_stage_spec): the solve starts at its y pass
+int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s, const double* rhs = nullptr, bool from_spec = false);
 bool ins_flux64_stage_rhs_supported(const ins_grid* G, int corr_mode);  // the stage kernel of this box can write that right-hand side (ins_flux64.hip)
+// ... and can store the x-forward transform of it instead, so the solve starts at its y pass (256-wide rows; ins_flux64.hip, XF)
+bool ins_flux64_stage_xfwd_supported(const ins_grid* G, int corr_mode);
 bool ins_flux64_stage_carry_supported(const ins_grid* G);            // its correcting stage kernel can store a carried combination (RkEpi::carry_out)
 double* ins_poisson_stage_rhs(ins_poisson* ps);                        // its buffer (nullptr: no own-FFT 3-D route, or out of memory)
+// The solver's spectrum buffer as the output of a stage kernel that reads `pI_in` as its pressure: phat, its row stride and the x twiddles.  nullptr: the solver's
+// route does not begin with the separate x-forward pass, or phat is that kernel's input.  The next solve must be ins_k_project_periodic_solve_only(.., from_spec).
+double* ins_poisson_stage_spec(ins_poisson* ps, const void* pI_in, const double** tw, int* kxs);
+bool ins_poisson_stage_spec_possible(const ins_poisson* ps);
 int ins_k_poisson_solve(ins_poisson* ps, double* p, hipStream_t s);
 bool ins_fast3d_supported(const ins_grid* G);
 
@@ -442,6 +456,7 @@ enum XfwdSrc {
   XSRC_DIV_WALLS = 4,  // Ω·div(u) on a grid with walls: the ghost volumes of u are valid
   XSRC_DIV_U32 = 5,    // as XSRC_DIV from a FLOAT velocity field, differences and metrics in double
   XSRC_FIELD = 6,      // one padded scalar array, ghosts stripped on the fly (observespectrum)
+  XSRC_SPEC = 7,       // no x pass: the x-spectrum is already in phat (the stage kernel stored it, ins_flux64.hip XF); the solver's dispatcher only
 };
 bool ins_zsolve_supported(int nz);
 bool ins_ownfft_supported(const int np[3]);

@@ -923,14 +923,27 @@ static SpectralRoute route_for_source(const ins_poisson* ps, int src) {
 // pI <- solution of L p = f through the solver's route.  u == nullptr: f is in pI.  Own routes only: f = Ω·div(u) is formed from u inside the first
 // pass, as source `src` (3-D: XSRC_DIV, XSRC_DIV_U32; 2-D: XSRC_DIV_2D).
 // rhs != nullptr (own 3-D routes): f is in that buffer instead of pI.
+// src == XSRC_SPEC: a stage kernel has stored the x-spectrum of f in phat (ins_poisson_stage_spec handed the buffer out and marked it pending); the routes that begin
+// with the separate x-forward pass skip it.  A solve from any other source while a spectrum is pending would overwrite it unread: an error.
+static bool route_starts_with_xfwd(SpectralRoute r) { return r == ROUTE_OWN_LDS || r == ROUTE_OWN_LINE3 || r == ROUTE_OWN_YZ; }
 static int spectral_transform(ins_poisson* ps, hipStream_t s, const double* u = nullptr, int src = XSRC_DIV, const double* rhs = nullptr) {
   const GridDev& g = ps->grid->g;
   const int n0 = ps->np[0], n1 = ps->np[1], n2 = ps->np[2], kxn = ps->kmax[0], kxs = ps->kxs;
   double* ph = reinterpret_cast<double*>(ps->phat);
   if (rhs) u = nullptr;
   const double* f = u ? u : (rhs ? rhs : ps->pI);
-  if (!u) src = XSRC_PI;
-  const SpectralRoute route = route_for_source(ps, src);
+  const bool from_spec = src == XSRC_SPEC;
+  if (!u && !from_spec) src = XSRC_PI;
+  const SpectralRoute route = route_for_source(ps, from_spec ? XSRC_PI : src);
+  if (from_spec) {
+    INS_REQUIRE(ps->spec_pending && !u && !rhs, "spectral solve from the stored x-spectrum: no stage kernel was handed phat since the last solve");
+    INS_REQUIRE(route_starts_with_xfwd(route) && g.D == 3 && (const void*)ps->phat != (const void*)ps->pI, "spectral solve from the stored x-spectrum: route without a separate x pass");
+  } else {
+    INS_REQUIRE(!ps->spec_pending, "spectral solve: phat holds a stage kernel's x-spectrum that no solve has read");
+  }
+  ps->spec_pending = false;
+  // the x-forward pass of the routes below; nothing when the spectrum is there already
+  auto xfwd = [&]() { return from_spec ? (int)INS_OK : ins_k_ownfft_xfwd(ps->grid, f, src, ph, n0, n1, n2, ps->tw_x, s, kxs); };
   INS_REQUIRE(!rhs || (own_route(route) && g.D == 3), "spectral solve: a right-hand side outside pI needs an own-FFT 3-D route");
   INS_REQUIRE(ins_spectral_ky_order(route) == ps->ky_order, "spectral solve: the route for this source leaves ky in another order than the solver's symbol");
   const double inv_n = 1.0 / ((double)n0 * n1 * n2);  // own routes (n2 == 1 in 2-D)
@@ -965,7 +978,7 @@ static int spectral_transform(ins_poisson* ps, hipStream_t s, const double* u = 
       if ((rc = zpass())) return rc;
       return ins_k_ownfft_xy(nullptr, nullptr, XSRC_PI, ph, ps->pI, n0, n1, n2, ps->tw_x, ps->tw_y, true, s, kxs);
     case ROUTE_OWN_YZ: {
-      if ((rc = ins_k_ownfft_xfwd(ps->grid, f, src, ph, n0, n1, n2, ps->tw_x, s, kxs))) return rc;
+      if ((rc = xfwd())) return rc;
       const ins_grid* G = ps->grid;
       const double c = G->h[0] * G->h[1] / G->h[2];  // Ω/Δz²
       if ((rc = ins_k_ownfft_yz_solve(ph, kxn, n1, n2, kxs, ps->yz_P, ps->ahat[0], ps->ahat[1], c, -1.0 / ((double)n0 * n1), ps->tw_y, ps->yz_scratch, s))) return rc;
@@ -974,7 +987,7 @@ static int spectral_transform(ins_poisson* ps, hipStream_t s, const double* u = 
     case ROUTE_OWN_LDS:
     case ROUTE_OWN_LINE3: {
       const auto ypass = route == ROUTE_OWN_LINE3 ? ins_k_line3_y : ins_k_ownfft_y;
-      if ((rc = ins_k_ownfft_xfwd(ps->grid, f, src, ph, n0, n1, n2, ps->tw_x, s, kxs))) return rc;
+      if ((rc = xfwd())) return rc;
       if ((rc = ypass(ph, kxn, n1, n2, ps->tw_y, false, s, kxs))) return rc;
       if ((rc = zpass())) return rc;
       if ((rc = ypass(ph, kxn, n1, n2, ps->tw_y, true, s, kxs))) return rc;
@@ -1442,8 +1455,9 @@ int ins_k_project(const ins_grid* G, ins_poisson* ps, double* u, double* p, hipS
 
 // First half of the fused periodic projection only: pI <- solution of L p = Ω div(u) (u: interior volumes valid).
 // The gradient-subtract is left to the next stage's stencil kernel (k_momentum_flux<..., CORR>).
-int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s, const double* rhs) {
+int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s, const double* rhs, bool from_spec) {
   const GridDev& g = G->g;
+  if (from_spec) return spectral_transform(ps, s, nullptr, XSRC_SPEC);
   if (own_route(ps->route)) return spectral_transform(ps, s, u, XSRC_DIV, rhs);  // K2 lives inside the first pass, or the stage kernel has written it to rhs
   INS_REQUIRE(!rhs, "a right-hand side written by the stage kernel needs an own-FFT route");
   dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), ps->np[2]);
@@ -1455,11 +1469,11 @@ int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const 
 // project! for the fused periodic RK stage: u holds valid INTERIOR values only; on return its interior is
 // divergence-free and its ghost volumes are filled.  3-D, all-periodic, spectral solver.
 // uout != nullptr: u stays as it is (uncorrected) and the corrected field with its ghost volumes goes to uout.
-int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout, const double* rhs) {
+int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout, const double* rhs, bool from_spec) {
   const GridDev& g = G->g;
   dim3 block(64, 4, 1), grid(cdiv(ps->np[0], 64), cdiv(ps->np[1], 4), ps->np[2]);
   double* dst = uout ? uout : u;
-  int rc = ins_k_project_periodic_solve_only(G, ps, u, s, rhs);
+  int rc = ins_k_project_periodic_solve_only(G, ps, u, s, rhs, from_spec);
   if (rc) return rc;
   if (keep_p)
     hipLaunchKernelGGL(k_grad_ghost3<true>, grid, block, 0, s, g, dst, p, ps->pI, ps->np[0], ps->np[1], ps->np[2], (const double*)u);
@@ -1499,6 +1513,18 @@ double* ins_poisson_stage_rhs(ins_poisson* ps) {
     ps->rhs = nullptr;
   }
   return ps->rhs;
+}
+// phat as the output of a stage kernel whose pressure input is pI_in (ins_internal.h).  Stream order is the only thing between that launch and the y pass: the
+// buffer is marked pending here and every solve checks the mark (spectral_transform), so a solve from another source in between is an error, not a wrong result.
+bool ins_poisson_stage_spec_possible(const ins_poisson* ps) {
+  return ins_k_spectral_own3d(ps) && route_starts_with_xfwd(ps->route) && ps->phat && ps->tw_x && ps->kxs >= ps->kmax[0];
+}
+double* ins_poisson_stage_spec(ins_poisson* ps, const void* pI_in, const double** tw, int* kxs) {
+  if (!ins_poisson_stage_spec_possible(ps) || (const void*)ps->phat == pI_in || (const void*)ps->phat == (const void*)ps->pI) return nullptr;
+  ps->spec_pending = true;
+  *tw = ps->tw_x;
+  *kxs = ps->kxs;
+  return reinterpret_cast<double*>(ps->phat);
 }
 int ins_k_spectral_solve_from_u32(ins_poisson* ps, const float* u32, hipStream_t s) {
   return spectral_transform(ps, s, reinterpret_cast<const double*>(u32), XSRC_DIV_U32);

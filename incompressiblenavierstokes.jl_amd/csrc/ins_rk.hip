@@ -12,7 +12,7 @@ bool ins_flux64_supported(const ins_grid* G);
 
 int ins_k_momentum_rk_fused(const ins_grid* G, double visc, const double* u_in, double* k_out, const RkEpi& epi, hipStream_t s);
 int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout = nullptr,
-                                 const double* rhs = nullptr);
+                                 const double* rhs = nullptr, bool from_spec = false);
 
 int ins_k_momentum(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s) {
   if (ins_fast3d_supported(G)) return ins_k_momentum_fast3d(G, visc, u, F, s);
@@ -164,6 +164,13 @@ extern "C" int ins_dbg_stage_rhs_used(const ins_rk_t* rk, int64_t* launches) {
   return INS_OK;
 }
 
+// How many of them stored the x-spectrum of the right-hand side instead of the real-space array (ins_flux64.hip, XF).
+extern "C" int ins_dbg_stage_xfwd_used(const ins_rk_t* rk, int64_t* launches) {
+  INS_REQUIRE(rk && launches, "null argument");
+  *launches = (int64_t)rk->stage_xfwd_launches;
+  return INS_OK;
+}
+
 // How many stage kernels of this integrator have stored a carried combination so far (RkCarryPlan, ins_rk_terms.h; a test asserts that the route ran).
 extern "C" int ins_dbg_stage_carry_used(const ins_rk_t* rk, int64_t* launches) {
   INS_REQUIRE(rk && launches, "null argument");
@@ -217,6 +224,38 @@ extern "C" int ins_dbg_stage_rhs(ins_rk_t* rk, double visc, const double* u_in, 
   int rc = pI ? ins_k_momentum_rk_fused_corr(G, visc, u_in, pI, rk->ku[0], epi, s) : ins_k_momentum_rk_fused(G, visc, u_in, rk->ku[0], epi, s);
   if (rc) return rc;
   if (*used) INS_HIP_TRY(hipMemcpyAsync(rhs, epi.rhs_out, (size_t)rk->ps->np[0] * rk->ps->np[1] * rk->ps->np[2] * sizeof(double), hipMemcpyDeviceToDevice, s));
+  return INS_OK;
+}
+
+// Test hook: the same launch on the x-spectrum route.  The stage kernel stores the half-complex x-spectrum of Ω·div(u*) into the solver's spectrum buffer, which is
+// copied to spec (n2 · n1 · kxs complex numbers, kxs = n0/2 + 1 rounded up to 8; device); *used says whether the route was taken (else nothing is launched).
+extern "C" int ins_dbg_stage_xfwd(ins_rk_t* rk, double visc, const double* u_in, const double* pI, const double* ustart, const double* kterm, double coef_k,
+                                  double self_in, double coef_self, double* ustar, double* spec, int32_t* used, void* stream) {
+  INS_REQUIRE(rk && u_in && ustar && spec && used, "null argument");
+  const ins_grid* G = rk->grid;
+  hipStream_t s = as_stream(stream);
+  RkEpi epi;
+  memset(&epi, 0, sizeof(epi));
+  epi.ustart = ustart;
+  epi.ustar = ustar;
+  epi.coef_self = coef_self;
+  if (ustart) {
+    epi.self_in = self_in;
+    epi.c0m1 = -self_in;
+  }
+  if (kterm) {
+    epi.coef[0] = coef_k;
+    epi.k[0] = kterm;
+    epi.n = 1;
+  }
+  *used = 0;
+  INS_REQUIRE(!ins_stage_out_aliases_input(epi, u_in), "ustar must be an array of its own");
+  if (!pI || !ins_flux64_stage_xfwd_supported(G, 1) || !(epi.spec_out = ins_poisson_stage_spec(rk->ps, pI, &epi.spec_tw, &epi.spec_kxs))) return INS_OK;
+  rk->ps->spec_pending = false;  // (no solve follows: the buffer is only read back)
+  *used = 1;
+  int rc = ins_k_momentum_rk_fused_corr(G, visc, u_in, pI, rk->ku[0], epi, s);
+  if (rc) return rc;
+  INS_HIP_TRY(hipMemcpyAsync(spec, epi.spec_out, (size_t)epi.spec_kxs * rk->ps->np[1] * rk->ps->np[2] * 2 * sizeof(double), hipMemcpyDeviceToDevice, s));
   return INS_OK;
 }
 
@@ -370,14 +409,23 @@ static int rk_step_fused_periodic(ins_rk* rk, double visc, double* u, double dt,
     // Not where u* overwrites one of the kernel's inputs (the last stage of an unchained step: ustart == out == the caller's u): that is safe cell by cell,
     // but for the right-hand side a wavefront reads its neighbours' cells of the inputs (row jb0-1, plane k0-1), which another workgroup may have overwritten.
     const bool corr = inkernel && (i > 0 || raw_in);
-    if (!in_place && ins_flux64_stage_rhs_supported(G, corr ? 1 : 0) && (epi.rhs_out = ins_poisson_stage_rhs(rk->ps)))
-      ++rk->stage_rhs_launches;
+    // 256-wide rows: it stores the x-forward transform of that right-hand side into the solver's spectrum buffer instead, and the solve starts at its y pass
+    // (INS_DISABLE_STAGE_XFWD=1: the real-space array and the x pass again).  One predicate decides (ins_flux64_stage_xfwd_supported).
+    if (!in_place && ins_flux64_stage_rhs_supported(G, corr ? 1 : 0)) {
+      if (ins_flux64_stage_xfwd_supported(G, corr ? 1 : 0) && ins_poisson_stage_spec_possible(rk->ps) &&
+          (epi.spec_out = ins_poisson_stage_spec(rk->ps, corr ? rk->ps->pI : nullptr, &epi.spec_tw, &epi.spec_kxs))) {
+        ++rk->stage_rhs_launches;
+        ++rk->stage_xfwd_launches;
+      } else if ((epi.rhs_out = ins_poisson_stage_rhs(rk->ps))) {
+        ++rk->stage_rhs_launches;
+      }
+    }
     rc = timed_stage(rk, s, [&] {
       return corr ? ins_k_momentum_rk_fused_corr(G, visc, in, rk->ps->pI, rk->ku[i], epi, s) : ins_k_momentum_rk_fused(G, visc, in, rk->ku[i], epi, s);
     });
     if (rc) return rc;
-    rc = (inkernel && (i < ns - 1 || raw_out)) ? ins_k_project_periodic_solve_only(G, rk->ps, out, s, epi.rhs_out)
-                                               : ins_k_project_periodic_fused(G, rk->ps, out, rk->p, i == ns - 1, s, nullptr, epi.rhs_out);
+    rc = (inkernel && (i < ns - 1 || raw_out)) ? ins_k_project_periodic_solve_only(G, rk->ps, out, s, epi.rhs_out, epi.spec_out != nullptr)
+                                               : ins_k_project_periodic_fused(G, rk->ps, out, rk->p, i == ns - 1, s, nullptr, epi.rhs_out, epi.spec_out != nullptr);
     if (rc) return rc;
     in = out;
   }

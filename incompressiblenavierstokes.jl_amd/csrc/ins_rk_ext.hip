@@ -23,7 +23,7 @@ int ins_k_momentum_generic(const ins_grid* G, double visc, const double* u, doub
 int ins_k_momentum_fast3d_opts(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
 int ins_k_momentum_rk_fused(const ins_grid* G, double visc, const double* u_in, double* k_out, const RkEpi& epi, hipStream_t s);
 int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout = nullptr,
-                                 const double* rhs = nullptr);
+                                 const double* rhs = nullptr, bool from_spec = false);
 int ins_k_project(const ins_grid* G, ins_poisson* ps, double* u, double* p, hipStream_t s);
 bool ins_flux64_supported(const ins_grid* G);
 int ins_k_temp_stage(const ins_grid* G, double a4, double coef, const double* u, const double* temp, const double* w, const double* tempstart, int n,
