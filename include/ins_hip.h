@@ -626,6 +626,31 @@ int ins_rk_step_ext_f32(ins_rk32_t* rk, float visc, float* u, float* temp, float
 /* nsteps such steps (the fixed-Δt loop of solve_unsteady, solver.jl:74-83) in one call */
 int ins_rk_steps_ext_f32(ins_rk32_t* rk, float visc, float* u, float* temp, float dt, int nsteps, void* stream);
 
+/* ---------------------------------------------------------------------------------- pullbacks of the Float32 temperature equation
+ * (csrc/ins_temp_adjoint32.hip)  The float twins of the `_f64` temperature pullbacks above, argument for argument: each is the exact transpose of
+ * the `_f32` forward operator (csrc/ins_temp32.hip) on the whole padded arrays.  The same kernel templates as the fp64 entries
+ * (csrc/ins_temp_adjoint_kernels.h) with T = float: the metric tables are rounded to float where they enter the arithmetic and the weights are
+ * formed as the Float32 forward forms them, so each is the transpose of the Float32 operator up to float rounding, not the fp64 transpose rounded
+ * at the end.  Gather kernels, no atomics, bitwise reproducible, 2-D and 3-D, any BC mix.  The same aliasing checks (INS_ERR_INVALID) and BC codes
+ * as the `_f64` entries; slab (halo) grids: INS_ERR_UNSUPPORTED. */
+/* apply_bc_temp_pullback!(tempbar, t, setup)   boundary_conditions.jl:248-270, 341-342, 407-412, 469-470, 515-516, in place: the transpose of
+ * the linear part of ins_apply_bc_temp_f32 */
+int ins_apply_bc_temp_pullback_f32(const ins_grid_t* grid, const int32_t* bc, float* tempbar, void* stream);
+/* gravity_adjoint!(tempbar, φbar, setup)       operators.jl:892-908: tempbar += (α2·avg)ᵀ φbar[:, gdir]; gdir 0-based */
+int ins_gravity_adjoint_f32(const ins_grid_t* grid, int gdir, float a2, const float* phibar, float* tempbar, void* stream);
+/* convection_diffusion_temp_adjoint!(ubar, tempbar, cbar, u, temp, setup)   operators.jl:712-737: ubar += (∂c/∂u)ᵀ cbar, tempbar += (∂c/∂temp)ᵀ cbar;
+ * ubar or tempbar may be NULL to skip that half (not both) */
+int ins_convection_diffusion_temp_adjoint_f32(const ins_grid_t* grid, float a4, const float* u, const float* temp, const float* cbar, float* ubar,
+                                              float* tempbar, void* stream);
+/* dissipation_adjoint!(ubar, cbar, u, setup)   operators.jl:791-814: ubar += J(u)ᵀ cbar, diffusion(u) recomputed in the kernel (no scratch field);
+ * visc = 1/Re, coef = Re·α1/γ as in ins_dissipation_f32 */
+int ins_dissipation_adjoint_f32(const ins_grid_t* grid, float visc, float coef, const float* u, const float* cbar, float* ubar, void* stream);
+/* One Runge-Kutta stage's temperature-coupled pullback in one launch (step_explicit_runge_kutta.jl:79-83): tempbar = gravityᵀ Fbar + (∂c/∂temp)ᵀ cbar
+ * overwrites tempbar; ubar += (∂c/∂u)ᵀ cbar + [desc->dodissipation] dissipationᵀ cbar accumulates on top of what ins_momentum_pullback_f32 wrote.
+ * Only a2, a4, diss_coef (rounded to float), gdir and dodissipation of `desc` are read. */
+int ins_temperature_pullback_f32(const ins_grid_t* grid, const ins_temperature_desc_t* desc, float visc, const float* u, const float* temp,
+                                 const float* Fbar, const float* cbar, float* ubar, float* tempbar, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,26 @@
-"""Reverse-mode differentiability of the isothermal step with `T = Float32`, exported as `ins_amd.ad32`: `ins_amd.ad` over float32 fields, on the
-`_f32` forwards (ins_amd.f32) and their pullbacks (csrc/ins_adjoint32.hip), each the exact transpose of its forward on the whole padded array
-(DESIGN.md "Differentiability").
+"""Reverse-mode differentiability of the step with `T = Float32`, exported as `ins_amd.ad32`: `ins_amd.ad` over float32 fields, on the
+`_f32` forwards (ins_amd.f32) and their pullbacks (csrc/ins_adjoint32.hip, csrc/ins_temp_adjoint32.hip), each the exact transpose of its forward on
+the whole padded array (DESIGN.md "Differentiability").
 
     st = ins.create_stepper(method, setup=setup, psolver=ins.f32.default_psolver32(setup), u=u0)        # u0: float32, requires_grad
     u = ad32.timestep(method, st, Δt).u
     (u * u).sum().backward()                                                                              # u0.grad = ∂loss/∂u0
 
 A closure model given as a torch function `m(u, θ)` on float32 fields is added as F + m(u, θ); its parameters get gradients from torch.  What the `_f32`
-family does not run raises NotImplementedError: a temperature field, the library's fused fp64 Smagorinsky closure `ins_amd.smagorinsky_closure`
-(its differentiable Float32 form is `ad32.smagorinsky_closure`, below), callable boundary data, an unsteady body force, slab setups, and `psolver_wrap32` around `psolver_spectral` on an all-periodic box.
+family does not run raises NotImplementedError: a temperature field on a setup without a temperature equation, the library's fused fp64 Smagorinsky
+closure `ins_amd.smagorinsky_closure` (its differentiable Float32 form is `ad32.smagorinsky_closure`, below), callable boundary data (of the velocity
+or of the temperature), an unsteady body force, slab setups, and `psolver_wrap32` around `psolver_spectral` on an all-periodic box.
+
+With a temperature equation (`Setup(temperature=temperature_equation(...))`, constant boundary data) the step is differentiable in `stepper.temp`
+too: `timestep` fills the ghosts of `temp` before each stage, a stage's right-hand side (u, temp) -> (F, Ftemp) is one Function whose backward is
+two launches (`momentum_pullback32_`, then `temperature_pullback32_`), the `ktemp` combinations are torch arithmetic, and `momentum(u, temp, t,
+setup)` adds the gravity term.  The operators are module attributes with the semantics of their `ad` namesakes on float32 tensors (they are not
+in `__all__`):
+
+    apply_bc_temp(temp, t, setup)                                 ghost fill of the temperature (`t` does not enter)
+    gravity(temp, setup)                                          the vector field α2 avg(temp) e_gdir
+    convection_diffusion_temp(u, temp, setup)                     differentiable in `u` and in `temp`
+    dissipation(u, setup)                                         the pullback recomputes diffusion(u) in the kernel
 
 The tensor-basis closure runs in Float32 too (csrc/ins_tensorclosure32.hip), through module attributes with the semantics of their `ad` namesakes on
 float32 tensors (they are not in `__all__`):
@@ -140,13 +152,154 @@ def _bodyforce32(setup):
 
 
 def momentum(u, temp, t, setup):
-    """operators.jl:940-976 with T = Float32, isothermal: convection + diffusion (momentum32_; the pullback is one launch) + a steady body
-    force, which is additive and drops out of the pullback."""
-    if temp is not None:
-        raise NotImplementedError("ad32.momentum: the temperature equation has no Float32 pullbacks (use ins_amd.ad)")
+    """operators.jl:940-976 with T = Float32: convection + diffusion (momentum32_; the pullback is one launch) + a steady body force, which
+    is additive and drops out of the pullback.  With a temperature field (and a temperature equation in `setup`) the gravity term is added
+    (operators.jl:974), differentiable in `u` and in `temp`."""
+    if temp is not None and setup.temperature is None:
+        raise NotImplementedError("ad32.momentum: a temperature field needs setup.temperature (temperature_equation)")
     _check_setup(setup, "momentum")
     F = _Momentum.apply(u, setup)
+    if temp is not None:
+        F = F + gravity(temp, setup)
     return F if setup.bodyforce is None else F + _bodyforce32(setup)
+
+
+# ------------------------------------------------------------------------------------ temperature equation
+def _save_inputs(ctx, setup, items):
+    """The fields a backward reads, `items` = (tensor, vector) pairs: an input that already is a library field goes through
+    save_for_backward, so an in-place change of it before backward() raises; a layout copy is private to the Function."""
+    fields, saved, copies = [], [], []
+    for x, vector in items:
+        f = _field(setup, x, vector)
+        fields.append(f)
+        if f is x:
+            saved.append(x)
+            copies.append(None)
+        else:
+            copies.append(f)
+    ctx.save_for_backward(*saved)
+    ctx.copies = copies
+    return fields
+
+
+def _saved_inputs(ctx):
+    saved = list(ctx.saved_tensors)
+    return [saved.pop(0) if c is None else c for c in ctx.copies]
+
+
+class _ApplyBCTemp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, temp, setup):
+        ctx.setup = setup
+        return F32.apply_bc_temp32_(_copy(setup, temp, False), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return F32.apply_bc_temp_pullback32_(_copy(s, g, False), s), None
+
+
+class _Gravity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, temp, setup):
+        ctx.setup = setup
+        return F32.gravity32_(F32.vectorfield32(setup), _field(setup, temp, False), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        return F32.gravity_adjoint32_(F32.scalarfield32(s), _field(s, g, True), s), None
+
+
+class _ConvectionDiffusionTemp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, temp, setup):
+        ctx.setup = setup
+        uf, tf = _save_inputs(ctx, setup, [(u, True), (temp, False)])
+        return F32.convection_diffusion_temp32_(F32.scalarfield32(setup), uf, tf, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        u, temp = _saved_inputs(ctx)
+        ubar = F32.vectorfield32(s) if ctx.needs_input_grad[0] else None
+        tempbar = F32.scalarfield32(s) if ctx.needs_input_grad[1] else None
+        if ubar is not None or tempbar is not None:
+            F32.convection_diffusion_temp_adjoint32_(ubar, tempbar, _field(s, g, False), u, temp, s)
+        return ubar, tempbar, None
+
+
+class _Dissipation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup):
+        ctx.setup = setup
+        (uf,) = _save_inputs(ctx, setup, [(u, True)])
+        return F32.dissipation32_(F32.scalarfield32(setup), F32.vectorfield32(setup), uf, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.setup
+        (u,) = _saved_inputs(ctx)
+        return F32.dissipation_adjoint32_(F32.vectorfield32(s), _field(s, g, False), u, s), None
+
+
+class _StageRightHandSide(torch.autograd.Function):
+    """(u, temp) -> (F, Ftemp) of one Runge-Kutta stage (step_explicit_runge_kutta.jl:79-83) with T = Float32: F = momentum(u, temp) without
+    the body force, Ftemp = convection_diffusion_temp(u, temp) + dissipation(u).  The backward is two launches: momentum_pullback32_, then
+    temperature_pullback32_."""
+
+    @staticmethod
+    def forward(ctx, u, temp, setup):
+        ctx.setup = setup
+        ctx.set_materialize_grads(False)
+        uf, tf = _save_inputs(ctx, setup, [(u, True), (temp, False)])
+        F = F32.momentum32_(F32.vectorfield32(setup), uf, setup, temp=tf)
+        Ftemp = F32.convection_diffusion_temp32_(F32.scalarfield32(setup), uf, tf, setup)
+        if setup.temperature.dodissipation:
+            F32.dissipation32_(Ftemp, F32.vectorfield32(setup), uf, setup)
+        return F, Ftemp
+
+    @staticmethod
+    def backward(ctx, gF, gT):
+        s = ctx.setup
+        if gF is None and gT is None:
+            return None, None, None
+        u, temp = _saved_inputs(ctx)
+        Fbar = F32.vectorfield32(s) if gF is None else _field(s, gF, True)
+        cbar = F32.scalarfield32(s) if gT is None else _field(s, gT, False)
+        ubar = F32.momentum_pullback32_(F32.vectorfield32(s), Fbar, u, s)
+        ubar, tempbar = F32.temperature_pullback32_(ubar, F32.scalarfield32(s), Fbar, cbar, u, temp, s)
+        return ubar, tempbar, None
+
+
+def _check_temperature(setup, what):
+    _check_slab(setup, what)
+    if setup.temperature is None:
+        raise ValueError(f"ad32.{what} needs setup.temperature (temperature_equation)")
+
+
+def apply_bc_temp(temp, t, setup):
+    """boundary_conditions.jl:236-246 with T = Float32 and constant boundary data (`t` does not enter); pullback: apply_bc_temp_pullback32_."""
+    _check_temperature(setup, "apply_bc_temp")
+    return _ApplyBCTemp.apply(temp, setup)
+
+
+def gravity(temp, setup):
+    """operators.jl:884-931 with T = Float32; pullback: gravity_adjoint32_."""
+    _check_temperature(setup, "gravity")
+    return _Gravity.apply(temp, setup)
+
+
+def convection_diffusion_temp(u, temp, setup):
+    """operators.jl:692-737 with T = Float32, differentiable in `u` and in `temp`; pullback: convection_diffusion_temp_adjoint32_."""
+    _check_temperature(setup, "convection_diffusion_temp")
+    return _ConvectionDiffusionTemp.apply(u, temp, setup)
+
+
+def dissipation(u, setup):
+    """operators.jl:770-814 with T = Float32; the pullback (dissipation_adjoint32_) recomputes diffusion(u) in the kernel."""
+    _check_temperature(setup, "dissipation")
+    return _Dissipation.apply(u, setup)
 
 
 def project(u, setup, psolver):
@@ -324,20 +477,29 @@ def smagorinsky_closure(setup):
 
 
 def timestep(method, stepper, Δt, θ=None):
-    """step_explicit_runge_kutta.jl:61-120 with T = Float32: one explicit Runge-Kutta step without mutation, differentiable in `stepper.u`
-    and (through a torch closure model `m(u, θ)`) in θ; `ad.timestep` on the Float32 operators, stage combinations in torch arithmetic."""
-    setup, psolver, u, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.t, stepper.n
-    if stepper.temp is not None:
-        raise NotImplementedError("ad32.timestep: the temperature equation has no Float32 pullbacks (use ins_amd.ad)")
+    """step_explicit_runge_kutta.jl:61-120 with T = Float32: one explicit Runge-Kutta step without mutation, differentiable in `stepper.u`,
+    in `stepper.temp` (with the temperature equation) and (through a torch closure model `m(u, θ)`) in θ; `ad.timestep` on the Float32
+    operators, stage combinations in torch arithmetic.  With a temperature field the right-hand side of a stage, (u, temp) -> (F, Ftemp), is
+    one Function whose backward is two launches."""
+    setup, psolver, u, temp, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.temp, stepper.t, stepper.n
+    if temp is not None and setup.temperature is None:
+        raise NotImplementedError("ad32.timestep: a temperature field needs setup.temperature (temperature_equation)")
     _check_setup(setup, "timestep")
     _check_psolver(setup, psolver, "timestep")
     m = setup.closure_model
     erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
     A, c = erk.A, erk.c
-    tstart, ustart, ku = t, u, []
+    tstart, ustart, tempstart, ku, ktemp = t, u, temp, [], []
     for i in range(len(erk.b)):
         u = apply_bc_u(u, t, setup)
-        F = momentum(u, None, t, setup)
+        if temp is None:
+            F = momentum(u, None, t, setup)
+        else:
+            temp = apply_bc_temp(temp, t, setup)
+            F, Ftemp = _StageRightHandSide.apply(u, temp, setup)
+            if setup.bodyforce is not None:
+                F = F + _bodyforce32(setup)
+            ktemp.append(Ftemp)
         if m is not None:
             F = F + m(u, θ)
         ku.append(F)
@@ -346,7 +508,14 @@ def timestep(method, stepper, Δt, θ=None):
         for j in range(i + 1):
             if A[i, j] != 0:
                 u = u + (Δt * A[i, j]) * ku[j]
+        if temp is not None:
+            temp = tempstart
+            for j in range(i + 1):
+                if A[i, j] != 0:
+                    temp = temp + (Δt * A[i, j]) * ktemp[j]
         u = apply_bc_u(u, t, setup)
         u = project(u, setup, psolver)
     u = apply_bc_u(u, t, setup)
-    return create_stepper(method, setup=setup, psolver=psolver, u=u, t=t, n=n + 1)
+    if temp is not None:
+        temp = apply_bc_temp(temp, t, setup)
+    return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=t, n=n + 1)

@@ -1,238 +1,12 @@
-// Reverse-mode pullbacks of the temperature equation (operators.jl:712-737, 791-814, 884-931; boundary_conditions.jl:236-270, 338-342,
+// Reverse-mode pullbacks of the temperature equation in fp64 (operators.jl:712-737, 791-814, 884-931; boundary_conditions.jl:236-270, 338-342,
 // 391-412, 466-470, 512-516): each is the exact transpose of THIS library's forward operator (ins_fields.hip: k_bc_temp, k_gravity,
 // k_convdiff_temp, diffusion + k_dissipation_interp) on the whole padded arrays (DESIGN.md "Differentiability", "Temperature equation").
-// The reference's own rules stop short here: the rrule of convection_diffusion_temp returns undefined names (operators.jl:699-704) and
-// dissipation's is @test_broken; only gravity and apply_bc_temp have working pullbacks.
 //
-// Gather form as in ins_adjoint.hip: one work-item per volume of the padded array reads the cotangent stencil around it, every output is
-// written once by one work-item, no atomics, so every result is bitwise reproducible.  fp64, 2-D and 3-D, any BC mix, uniform and stretched
-// grids.  One kernel template serves the four operator-level entries and the fused per-stage entry: PARTS selects the terms, so the fused
-// launch forms exactly the sums of the operator-level ones.
-#include "ins_stencil.h"
+// The kernels are the templates of ins_temp_adjoint_kernels.h with T = double, the ones ins_temp_adjoint32.hip instantiates with float.
+// This file holds no stencil arithmetic of its own: the slab refusal and the entry points.
+#include "ins_temp_adjoint_kernels.h"
 
 namespace {
-
-// --------------------------------------------------------------------------------------------
-// gravity_adjoint                                                        operators.jl:892-908
-//   forward: F[J, g] += α2 avg(temp, J, g), J ∈ Iu[g], avg(ϕ, J, g) = (Δ[Jg+1] ϕ[J] + Δ[Jg] ϕ[J+eg]) / (Δ[Jg] + Δ[Jg+1])   (avg_at)
-//   tempbar[K] gets α2 (φ[K] Δ[Kg+1]/(Δ[Kg]+Δ[Kg+1]) [K ∈ Iu[g]] + φ[K−eg] Δ[Kg−1]/(Δ[Kg−1]+Δ[Kg]) [K−eg ∈ Iu[g]])
-// --------------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ double gravity_tempbar(const GridDev& g, int gdir, double a2, const double* __restrict__ phig, const int (&I)[3],
-                                                  long long c) {
-  const int ig = I[gdir];
-  const double* dx = g.dx[gdir];
-  double v = 0.0;
-  if (in_iu<D>(g, gdir, I[0], I[1], I[2])) {
-    const double d0 = dx[ig], d1 = dx[ig + 1];
-    v += phig[c] * (d1 / (d0 + d1));
-  }
-  if (in_iu<D>(g, gdir, INS_SH(I, gdir, -1))) {
-    const double d0 = dx[ig - 1], d1 = dx[ig];
-    v += phig[c - g.sx[gdir]] * (d0 / (d0 + d1));
-  }
-  return a2 * v;
-}
-
-// --------------------------------------------------------------------------------------------
-// convection_diffusion_temp_adjoint                                      operators.jl:712-737
-//   forward, I ∈ Ip:  c[I] += Σ_β [ −(uβ[I] avg(T, I, β) − uβ[I−eβ] avg(T, I−eβ, β)) + α4 ((T[I+eβ] − T[I])/Δuβ[Iβ] − (T[I] − T[I−eβ])/Δuβ[Iβ−1]) ] / Δβ[Iβ]
-//   With q = cbar masked to Ip, the flux uβ[J] avg(T, J, β) through the upper β-face of J carries ψβ(J) = q[J+eβ]/Δβ[Jβ+1] − q[J]/Δβ[Jβ]:
-//     ubar[J, β]  gets avg(T, J, β) ψβ(J)
-//     tempbar[K]  gets Σ_β uβ[K] ψβ(K) Δ[Kβ+1]/(Δ[Kβ]+Δ[Kβ+1]) + uβ[K−eβ] ψβ(K−eβ) Δ[Kβ−1]/(Δ[Kβ−1]+Δ[Kβ])       (the two averages that read T[K])
-//                 + α4 Σ_β ( q[K−eβ]/(Δβ Δuβ)[Kβ−1] − q[K] (1/Δuβ[Kβ] + 1/Δuβ[Kβ−1])/Δβ[Kβ] + q[K+eβ]/(Δβ[Kβ+1] Δuβ[Kβ]) )
-//   A face is evaluated only where ψ has a term, i.e. exactly where the forward evaluated it, so every table and field read is one the
-//   forward made (no 0 · inf from a zero-width ghost volume, no read outside the array).
-// --------------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ double cdt_tempbar(const GridDev& g, double a4, const double* __restrict__ u, const double* __restrict__ cbar,
-                                              const int (&I)[3], long long c) {
-  const bool here = in_ip<D>(g, I[0], I[1], I[2]);
-  const double qc = here ? cbar[c] : 0.0;
-  double v = 0.0;
-#pragma unroll
-  for (int b = 0; b < D; ++b) {
-    const long long sb = g.sx[b];
-    const int ib = I[b];
-    const double* ub = u + b * g.sc;
-    const double* dx = g.dx[b];
-    const double* rdx = g.rdx[b];
-    const double* rdxu = g.rdxu[b];
-    const bool up = in_ip<D>(g, INS_SH(I, b, 1)), dn = in_ip<D>(g, INS_SH(I, b, -1));
-    const double qp = up ? cbar[c + sb] : 0.0, qm = dn ? cbar[c - sb] : 0.0;
-    if (here || up) {  // face of K
-      double psi = 0.0;
-      if (up) psi += qp * rdx[ib + 1];
-      if (here) psi -= qc * rdx[ib];
-      const double d0 = dx[ib], d1 = dx[ib + 1];
-      v += ub[c] * psi * (d1 / (d0 + d1));
-    }
-    if (dn || here) {  // face of K − eβ
-      double psi = 0.0;
-      if (here) psi += qc * rdx[ib];
-      if (dn) psi -= qm * rdx[ib - 1];
-      const double d0 = dx[ib - 1], d1 = dx[ib];
-      v += ub[c - sb] * psi * (d0 / (d0 + d1));
-    }
-    if (dn) v += a4 * qm * rdx[ib - 1] * rdxu[ib - 1];
-    if (here) v -= a4 * qc * rdx[ib] * (rdxu[ib] + rdxu[ib - 1]);
-    if (up) v += a4 * qp * rdx[ib + 1] * rdxu[ib];
-  }
-  return v;
-}
-
-template <int D>
-__device__ __forceinline__ double cdt_ubar(const GridDev& g, int b, const double* __restrict__ temp, const double* __restrict__ cbar,
-                                           const int (&I)[3], long long c) {
-  const bool here = in_ip<D>(g, I[0], I[1], I[2]);
-  const bool up = in_ip<D>(g, INS_SH(I, b, 1));
-  if (!(here || up)) return 0.0;
-  const int ib = I[b];
-  double psi = 0.0;
-  if (up) psi += cbar[c + g.sx[b]] * g.rdx[b][ib + 1];
-  if (here) psi -= cbar[c] * g.rdx[b][ib];
-  const double d0 = g.dx[b][ib], d1 = g.dx[b][ib + 1];
-  return psi * ((d1 * temp[c] + d0 * temp[c + g.sx[b]]) / (d0 + d1));
-}
-
-// --------------------------------------------------------------------------------------------
-// dissipation_adjoint                                                    operators.jl:791-814
-//   forward: d = diffusion(u) on the degrees of freedom of u and zero elsewhere (fill! + diffusion!, :797-798), then for I ∈ Ip
-//     φ[I] += coef Σ_β (uβ[I−eβ] dβ[I−eβ] + uβ[I] dβ[I]) / 2.
-//   With wbar[J, γ] = coef/2 (q[J] + q[J+eγ]) [J dof of γ], q = cbar masked to Ip:
-//     ubar[J, γ] gets wbar[J, γ] dγ[J] + (diffusionᵀ z)[J, γ],   z = wbar ⊙ u.
-//   d and z are recomputed from their stencils (no D-component scratch field); the ranges (dof) and boundary-volume widths (mdx / mdxu, r) are
-//   those of k_convdiff (ins_diffusion_f64) and of k_convdiff_adjoint (ins_diffusion_adjoint_f64).
-// --------------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ double diss_z(const GridDev& g, double halfcoef, int ga, const double* __restrict__ ua, const double* __restrict__ cbar,
-                                         int i0, int i1, int i2, long long c) {
-  double q = 0.0;
-  if (in_ip<D>(g, i0, i1, i2)) q += cbar[c];
-  if (in_ip<D>(g, i0 + (ga == 0), i1 + (ga == 1), i2 + (ga == 2))) q += cbar[c + g.sx[ga]];
-  return halfcoef * q * ua[c];
-}
-
-template <int D>
-__device__ __forceinline__ double diss_ubar(const GridDev& g, double visc, double coef, int ga, const double* __restrict__ u,
-                                            const double* __restrict__ cbar, const int (&I)[3], long long c) {
-  const double* ua = u + ga * g.sc;
-  const double hc = 0.5 * coef;
-  const bool dx = dof<D>(g, ga, I[0], I[1], I[2]);
-  double v = 0.0;
-  double zc = 0.0;
-  if (dx) {
-    const double uc = ua[c];
-    double q = 0.0;
-    if (in_ip<D>(g, I[0], I[1], I[2])) q += cbar[c];
-    if (in_ip<D>(g, INS_SH(I, ga, 1))) q += cbar[c + g.sx[ga]];
-    const double wb = hc * q;
-    zc = wb * uc;
-    double d = 0.0;
-#pragma unroll
-    for (int be = 0; be < D; ++be) {
-      const long long sb = g.sx[be];
-      const int ib = I[be];
-      const double r = (ga == be ? g.rdxu[be] : g.rdx[be])[ib];
-      const double ma = ga == be ? g.mdx[be][ib] : g.mdxu[be][ib - 1];
-      const double mb = ga == be ? g.mdx[be][ib + 1] : g.mdxu[be][ib];
-      d += visc * ((ua[c + sb] - uc) * mb - (uc - ua[c - sb]) * ma) * r;
-    }
-    v += wb * d;
-  }
-#pragma unroll
-  for (int be = 0; be < D; ++be) {
-    const long long sb = g.sx[be];
-    const int ib = I[be];
-    const double* rt = ga == be ? g.rdxu[be] : g.rdx[be];
-    if (dx) {
-      const double ma = ga == be ? g.mdx[be][ib] : g.mdxu[be][ib - 1];
-      const double mb = ga == be ? g.mdx[be][ib + 1] : g.mdxu[be][ib];
-      v -= visc * zc * rt[ib] * (ma + mb);
-    }
-    if (dof<D>(g, ga, INS_SH(I, be, -1))) {
-      const double mb = ga == be ? g.mdx[be][ib] : g.mdxu[be][ib - 1];
-      v += visc * diss_z<D>(g, hc, ga, ua, cbar, INS_SH(I, be, -1), c - sb) * rt[ib - 1] * mb;
-    }
-    if (dof<D>(g, ga, INS_SH(I, be, 1))) {
-      const double ma = ga == be ? g.mdx[be][ib + 1] : g.mdxu[be][ib];
-      v += visc * diss_z<D>(g, hc, ga, ua, cbar, INS_SH(I, be, 1), c + sb) * rt[ib + 1] * ma;
-    }
-  }
-  return v;
-}
-
-// PARTS bit0: gravityᵀ -> tempbar   bit1: (∂c/∂temp)ᵀ -> tempbar   bit2: (∂c/∂u)ᵀ -> ubar   bit3: dissipationᵀ -> ubar
-// TOVER: tempbar is overwritten, else added to.  ubar is always added to.
-enum { P_GRAV = 1, P_CDT_T = 2, P_CDT_U = 4, P_DISS = 8 };
-struct TempAdjArgs {
-  int gdir;
-  double a2, a4, visc, coef;
-  const double* u;
-  const double* temp;
-  const double* Fbar;
-  const double* cbar;
-  double* ubar;
-  double* tempbar;
-};
-
-template <int D, int PARTS, bool TOVER>
-__global__ __launch_bounds__(256) void k_temp_adjoint(GridDev g, BoxMap L, TempAdjArgs a) {
-  INS_BANDED_INDEX(0, 0, 0, g.N[0], g.N[1]);
-  if (PARTS & (P_GRAV | P_CDT_T)) {
-    double v = 0.0;
-    if (PARTS & P_GRAV) v += gravity_tempbar<D>(g, a.gdir, a.a2, a.Fbar + a.gdir * g.sc, I, c);
-    if (PARTS & P_CDT_T) v += cdt_tempbar<D>(g, a.a4, a.u, a.cbar, I, c);
-    a.tempbar[c] = TOVER ? v : a.tempbar[c] + v;
-  }
-  if (PARTS & (P_CDT_U | P_DISS)) {
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      double v = 0.0;
-      if (PARTS & P_CDT_U) v += cdt_ubar<D>(g, b, a.temp, a.cbar, I, c);
-      if (PARTS & P_DISS) v += diss_ubar<D>(g, a.visc, a.coef, b, a.u, a.cbar, I, c);
-      a.ubar[b * g.sc + c] += v;
-    }
-  }
-}
-
-template <int PARTS, bool TOVER>
-int launch_temp_adjoint(const ins_grid* G, const TempAdjArgs& a, hipStream_t s) {
-  const GridDev& g = G->g;
-  const Launch3 l = banded_launch(g.D, g.N);
-  INS_LAUNCH_D((k_temp_adjoint<D, PARTS, TOVER>), l, s, g, l.map, a);
-  return INS_OK;
-}
-
-// --------------------------------------------------------------------------------------------
-// apply_bc_temp_pullback         boundary_conditions.jl:142-157, 248-270, 341-342, 407-412, 469-470, 515-516
-//   The exact transpose of k_bc_temp (ins_fields.hip): the forward sweeps β = 0..D-1 and fills, per line, the left then the right ghost
-//   volume with a copy (x[i] = x[j]) or a Dirichlet value; the transpose walks β = D-1..0 and the sides right then left, turning
-//   x[i] = x[j] into (x̄[j] += x̄[i]; x̄[i] = 0) and x[i] = value into x̄[i] = 0.  The Dirichlet values (constant or callable) only change the
-//   constant part, so neither they nor t enter.
-// --------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_bc_temp_pullback(GridDev g, double* __restrict__ tb, int be, int bcl, int bcr) {
-  INS_LINE_INDEX(be);
-  double* x = tb + base;
-  const long long sb = g.sx[be];
-  const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
-  if (bcl == INS_BC_PERIODIC) {  // forward: x[ia] = x[ib-1]; x[ib] = x[ia+1]
-    move_to(x, ib * sb, (ia + 1) * sb);
-    move_to(x, ia * sb, (ib - 1) * sb);
-    return;
-  }
-#pragma unroll
-  for (int side = 1; side >= 0; --side) {
-    const int bc = side ? bcr : bcl;
-    const int i = side ? ib : ia;
-    const int jn = side ? i - 1 : i + 1;
-    if (bc == INS_BC_DIRICHLET)
-      x[i * sb] = 0.0;
-    else if (bc == INS_BC_SYMMETRIC || bc == INS_BC_PRESSURE)
-      move_to(x, i * sb, jn * sb);
-  }
-}
 
 // z-slab grids (INS_BC_HALO sides): the ghost planes belong to another rank, whose cotangents this rank does not hold
 int refuse_slab(const ins_grid* G, const char* what) {
@@ -249,38 +23,30 @@ int refuse_slab(const ins_grid* G, const char* what) {
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
+// apply_bc_temp_pullback!   boundary_conditions.jl:142-157, 248-270, 341-342, 407-412, 469-470, 515-516 (in place)
 extern "C" int ins_apply_bc_temp_pullback_f64(const ins_grid_t* G, const int32_t* bc, double* tempbar, void* stream) {
   INS_REQUIRE(G && bc && tempbar, "null argument");
   int rc;
   if ((rc = refuse_slab(G, "ins_apply_bc_temp_pullback_f64"))) return rc;
-  const GridDev& g = G->g;
-  for (int be = 0; be < g.D; ++be) {
-    for (int side = 0; side < 2; ++side) {
-      const int c = bc[2 * be + side];
-      INS_REQUIRE(c == INS_BC_PERIODIC || c == INS_BC_DIRICHLET || c == INS_BC_SYMMETRIC || c == INS_BC_PRESSURE, "temperature boundary condition");
-    }
-    INS_REQUIRE((bc[2 * be] == INS_BC_PERIODIC) == (bc[2 * be + 1] == INS_BC_PERIODIC), "periodic on both sides");
-  }
-  for (int be = g.D - 1; be >= 0; --be) {  // reverse of ins_apply_bc_temp_f64
-    INS_LAUNCH_D((k_bc_temp_pullback<D>), line_launch(g, be, 1), as_stream(stream), g, tempbar, be, (int)bc[2 * be], (int)bc[2 * be + 1]);
-  }
-  return INS_OK;
+  return bc_temp_pullback<double>(G, bc, tempbar, as_stream(stream));
 }
 
+// gravity_adjoint!   operators.jl:892-908 (tempbar += ...)
 extern "C" int ins_gravity_adjoint_f64(const ins_grid_t* G, int gdir, double a2, const double* phibar, double* tempbar, void* stream) {
   INS_REQUIRE(G && phibar && tempbar, "null argument");
   INS_REQUIRE(gdir >= 0 && gdir < G->g.D, "gravity direction");
   INS_REQUIRE(tempbar != phibar + (long long)gdir * G->g.sc, "gravity_adjoint! cannot run in place");
   int rc;
   if ((rc = refuse_slab(G, "ins_gravity_adjoint_f64"))) return rc;
-  TempAdjArgs a{};
+  TempAdjArgs<double> a{};
   a.gdir = gdir;
   a.a2 = a2;
   a.Fbar = phibar;
   a.tempbar = tempbar;
-  return launch_temp_adjoint<P_GRAV, false>(G, a, as_stream(stream));
+  return launch_temp_adjoint<double, P_GRAV, false>(G, a, as_stream(stream));
 }
 
+// convection_diffusion_temp_adjoint!   operators.jl:712-737 (ubar += ..., tempbar += ...; either may be NULL)
 extern "C" int ins_convection_diffusion_temp_adjoint_f64(const ins_grid_t* G, double a4, const double* u, const double* temp, const double* cbar,
                                                          double* ubar, double* tempbar, void* stream) {
   INS_REQUIRE(G && u && temp && cbar, "null argument");
@@ -289,33 +55,35 @@ extern "C" int ins_convection_diffusion_temp_adjoint_f64(const ins_grid_t* G, do
   INS_REQUIRE(ubar != u, "convection_diffusion_temp_adjoint! cannot run in place");
   int rc;
   if ((rc = refuse_slab(G, "ins_convection_diffusion_temp_adjoint_f64"))) return rc;
-  TempAdjArgs a{};
+  TempAdjArgs<double> a{};
   a.a4 = a4;
   a.u = u;
   a.temp = temp;
   a.cbar = cbar;
   a.ubar = ubar;
   a.tempbar = tempbar;
-  if (ubar && tempbar) return launch_temp_adjoint<P_CDT_T | P_CDT_U, false>(G, a, as_stream(stream));
-  if (tempbar) return launch_temp_adjoint<P_CDT_T, false>(G, a, as_stream(stream));
-  return launch_temp_adjoint<P_CDT_U, false>(G, a, as_stream(stream));
+  if (ubar && tempbar) return launch_temp_adjoint<double, P_CDT_T | P_CDT_U, false>(G, a, as_stream(stream));
+  if (tempbar) return launch_temp_adjoint<double, P_CDT_T, false>(G, a, as_stream(stream));
+  return launch_temp_adjoint<double, P_CDT_U, false>(G, a, as_stream(stream));
 }
 
+// dissipation_adjoint!   operators.jl:791-814 (ubar += ...)
 extern "C" int ins_dissipation_adjoint_f64(const ins_grid_t* G, double visc, double coef, const double* u, const double* cbar, double* ubar,
                                            void* stream) {
   INS_REQUIRE(G && u && cbar && ubar, "null argument");
   INS_REQUIRE(ubar != u, "dissipation_adjoint! cannot run in place");
   int rc;
   if ((rc = refuse_slab(G, "ins_dissipation_adjoint_f64"))) return rc;
-  TempAdjArgs a{};
+  TempAdjArgs<double> a{};
   a.visc = visc;
   a.coef = coef;
   a.u = u;
   a.cbar = cbar;
   a.ubar = ubar;
-  return launch_temp_adjoint<P_DISS, false>(G, a, as_stream(stream));
+  return launch_temp_adjoint<double, P_DISS, false>(G, a, as_stream(stream));
 }
 
+// One stage's temperature-coupled pullback in one launch   step_explicit_runge_kutta.jl:79-83 (tempbar = ..., ubar += ...)
 extern "C" int ins_temperature_pullback_f64(const ins_grid_t* G, const ins_temperature_desc_t* desc, double visc, const double* u, const double* temp,
                                             const double* Fbar, const double* cbar, double* ubar, double* tempbar, void* stream) {
   INS_REQUIRE(G && desc && u && temp && Fbar && cbar && ubar && tempbar, "null argument");
@@ -324,7 +92,7 @@ extern "C" int ins_temperature_pullback_f64(const ins_grid_t* G, const ins_tempe
   INS_REQUIRE(tempbar != temp && tempbar != cbar, "temperature pullback cannot run in place");
   int rc;
   if ((rc = refuse_slab(G, "ins_temperature_pullback_f64"))) return rc;
-  TempAdjArgs a{};
+  TempAdjArgs<double> a{};
   a.gdir = desc->gdir;
   a.a2 = desc->a2;
   a.a4 = desc->a4;
@@ -336,6 +104,6 @@ extern "C" int ins_temperature_pullback_f64(const ins_grid_t* G, const ins_tempe
   a.cbar = cbar;
   a.ubar = ubar;
   a.tempbar = tempbar;
-  if (desc->dodissipation) return launch_temp_adjoint<P_GRAV | P_CDT_T | P_CDT_U | P_DISS, true>(G, a, as_stream(stream));
-  return launch_temp_adjoint<P_GRAV | P_CDT_T | P_CDT_U, true>(G, a, as_stream(stream));
+  if (desc->dodissipation) return launch_temp_adjoint<double, P_GRAV | P_CDT_T | P_CDT_U | P_DISS, true>(G, a, as_stream(stream));
+  return launch_temp_adjoint<double, P_GRAV | P_CDT_T | P_CDT_U, true>(G, a, as_stream(stream));
 }

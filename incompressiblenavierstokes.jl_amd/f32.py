@@ -233,6 +233,51 @@ def project_pullback32_(φbar, setup, psolver, pwork):
     return φbar
 
 
+# ---- temperature pullbacks (csrc/ins_temp_adjoint32.hip): the Float32 twins of operators.apply_bc_temp_pullback_ ... temperature_pullback_, the exact
+# transposes of the Float32 temperature operators above on the whole padded float arrays.  The scalars come from _temp_desc(setup): callable
+# temperature Dirichlet data raises NotImplementedError there.
+def apply_bc_temp_pullback32_(tempbar, setup):
+    """boundary_conditions.jl:248-270, in place: the transpose of the linear part of apply_bc_temp32_ (the Dirichlet values do not enter)."""
+    _lib.call("ins_apply_bc_temp_pullback_f32", setup.handle, _temp_desc(setup).bc, _ptr(setup, tempbar, 0), setup.stream)
+    return tempbar
+
+
+def gravity_adjoint32_(tempbar, φbar, setup):
+    """operators.jl:892-908 (adds (α2 avg)ᵀ φbar[..., gdir] to tempbar)"""
+    desc = _temp_desc(setup)
+    _lib.call("ins_gravity_adjoint_f32", setup.handle, int(desc.gdir), float(desc.a2), _ptr(setup, φbar, setup.grid.dimension), _ptr(setup, tempbar, 0),
+              setup.stream)
+    return tempbar
+
+
+def convection_diffusion_temp_adjoint32_(ubar, tempbar, cbar, u, temp, setup):
+    """operators.jl:712-737 at the ghost-filled (u, temp): adds (∂c/∂u)ᵀ cbar to `ubar` and (∂c/∂temp)ᵀ cbar to `tempbar`; either may be
+    None to skip that half.  Returns (ubar, tempbar)."""
+    D = setup.grid.dimension
+    _lib.call("ins_convection_diffusion_temp_adjoint_f32", setup.handle, float(_temp_desc(setup).a4), _ptr(setup, u, D), _ptr(setup, temp, 0),
+              _ptr(setup, cbar, 0), _ptr_or_null(setup, ubar, D), _ptr_or_null(setup, tempbar, 0), setup.stream)
+    return ubar, tempbar
+
+
+def dissipation_adjoint32_(ubar, cbar, u, setup):
+    """operators.jl:791-814 at the ghost-filled `u` (adds J(u)ᵀ cbar to ubar; diffusion(u) is recomputed in the kernel, no scratch field)"""
+    D = setup.grid.dimension
+    _lib.call("ins_dissipation_adjoint_f32", setup.handle, float(1.0 / setup.Re), float(_temp_desc(setup).diss_coef), _ptr(setup, u, D),
+              _ptr(setup, cbar, 0), _ptr(setup, ubar, D), setup.stream)
+    return ubar
+
+
+def temperature_pullback32_(ubar, tempbar, Fbar, cbar, u, temp, setup):
+    """One Runge-Kutta stage's temperature-coupled pullback in one launch: tempbar = gravityᵀ Fbar + (∂c/∂temp)ᵀ cbar (overwritten),
+    ubar += (∂c/∂u)ᵀ cbar + dissipationᵀ cbar (the latter with `dodissipation`), on top of what `momentum_pullback32_` wrote.
+    Returns (ubar, tempbar)."""
+    D = setup.grid.dimension
+    desc = _temp_desc(setup)
+    _lib.call("ins_temperature_pullback_f32", setup.handle, C.byref(desc), float(1.0 / setup.Re), _ptr(setup, u, D), _ptr(setup, temp, 0),
+              _ptr(setup, Fbar, D), _ptr(setup, cbar, 0), _ptr(setup, ubar, D), _ptr(setup, tempbar, 0), setup.stream)
+    return ubar, tempbar
+
+
 # ---- tensor-basis closure (csrc/ins_tensorclosure32.hip): the Float32 twins of operators.tensorinvariants_ ... divoftensor_adjoint_
 def _tb_sizes(setup):
     """(nb, nv, ns): basis tensors, invariants, stored entries of a symmetric tensor."""
