@@ -6,7 +6,9 @@
 //
 // The one rule for both precisions: the grid handle is the fp64 one, a metric table entry is read as a double and converted with (T) where
 // it enters the arithmetic, constants are written T(…), and everything else is in T.  With T = double the conversions vanish and the
-// expressions are those of the generic forward twins in ins_operators.hip; with T = float they are those of ins_f32g.hip.
+// expressions are those of the generic forward operators.  The forward twins: ins_operator_kernels.h (k_divergence, k_bc_u, k_bc_p, both
+// precisions) and, for the two stencils whose precisions contract their FMAs differently, k_convdiff / k_pressuregradient in
+// ins_operators.hip with the float copies k32g_momentum / k32g_applypressure in ins_f32g.hip.
 #pragma once
 
 #include "ins_stencil.h"
@@ -17,7 +19,7 @@ namespace {
 // divergence_adjoint                                                     operators.jl:127-145
 //   ubar[α][I] += alpha · (φ[I]/Δα[Iα] [I ∈ Ip] − φ[I+eα]/Δα[Iα+1] [I+eα ∈ Ip])   over the whole padded array
 //   φ and alpha have type P, ubar type T: the sum is taken in P and rounded to T once.  <double, float>: φ is the pressure of the fp64
-//   solver that a Float32 solver handle wraps (the mirror of k32g_div<D, double, true>, which forms that solver's right-hand side in double
+//   solver that a Float32 solver handle wraps (the mirror of k_divergence<D, float, double, true>, which forms that solver's right-hand side in double
 //   from the float field).
 // --------------------------------------------------------------------------------------------
 template <int D, typename P, typename T>
@@ -160,7 +162,7 @@ __global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, T visc, con
 
 // --------------------------------------------------------------------------------------------
 // apply_bc_u_pullback / apply_bc_p_pullback           boundary_conditions.jl:169-230, 290-516
-//   The exact transpose of k_bc_u / k_bc_p (ins_bc.hip) and of k32g_bc_u / k32g_bc_p (and, on periodic boxes, of k32_bc_periodic, which
+//   The exact transpose of k_bc_u / k_bc_p (ins_operator_kernels.h, both precisions; and, on periodic boxes, of k32_bc_periodic, which
 //   does the same copies): the forward sweeps β = 0..D-1 and, per line, left side then right side, each fill a copy (x[i] = x[j]) or a
 //   constant; the transpose walks β = D-1..0 and the sides right then left, turning x[i] = x[j] into (x̄[j] += x̄[i]; x̄[i] = 0) and
 //   x[i] = const into x̄[i] = 0.  Time-dependent Dirichlet planes only change the constant, so the pullback does not read them.

@@ -1,75 +1,9 @@
 // Ghost-volume fill (boundary_conditions.jl:159-206, 276-318, 344-388, 414-502) and the blocking
-// box reductions used by diagnostics and the CG solver.
-#include "ins_stencil.h"
+// box reductions used by diagnostics and the CG solver.  The fill kernels k_bc_u / k_bc_p are the double instantiations of
+// ins_operator_kernels.h (shared with ins_f32g.hip).
+#include "ins_operator_kernels.h"
 
 namespace {
-
-// One launch per direction β (the reference sweeps β = 1..D in order so that edges and corners come
-// out right, boundary_conditions.jl:162-165); work-items span the full padded extent of the other
-// directions (`boundary()`, boundary_conditions.jl:97-103) times the D components.
-//
-// Plane coordinates (q0, q1) enumerate the two directions != β in memory order.
-template <int D>
-__global__ __launch_bounds__(256) void k_bc_u(GridDev g, double* __restrict__ u, int be, int dudt, const double* const* planes) {
-  INS_LINE_INDEX(be);
-  const int al = blockIdx.z;
-  const long long sb = g.sx[be];
-  double* ua = u + al * g.sc;
-  const int bcl = g.bc[be][0], bcr = g.bc[be][1];
-
-  if (bcl == INS_BC_PERIODIC) {  // boundary_conditions.jl:276-288 (both sides in one go)
-    const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
-    ua[base + ia * sb] = ua[base + (ib - 1) * sb];
-    ua[base + ib * sb] = ua[base + (ia + 1) * sb];
-    return;
-  }
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const int bc = side ? bcr : bcl;
-    if (bc == INS_BC_HALO) continue;  // filled by the caller (slab neighbour exchange)
-    const int i = side ? g.iu_hi[al][be] : g.iu_lo[al][be] - 1;
-    const int jn = side ? i - 1 : i + 1;
-    double* dst = ua + base + i * sb;
-    if (bc == INS_BC_DIRICHLET) {  // boundary_conditions.jl:344-375
-      const double* pl = planes ? planes[(be * 2 + side) * 3 + al] : nullptr;
-      double v;
-      if (pl)
-        v = pl[q0 + (D == 3 ? (long long)q1 * g.N[o0] : 0)];
-      else
-        v = dudt ? 0.0 : g.bc_u[be][side][al];
-      *dst = v;
-    } else if (bc == INS_BC_SYMMETRIC) {  // boundary_conditions.jl:414-428
-      *dst = (al == be) ? 0.0 : ua[base + jn * sb];
-    } else if (bc == INS_BC_PRESSURE) {  // boundary_conditions.jl:472-482
-      *dst = ua[base + jn * sb];
-    }
-  }
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_bc_p(GridDev g, double* __restrict__ p, int be, long long fstride = 0) {
-  p += (long long)blockIdx.z * fstride;  // several scalar fields in one launch (the stress components of the closure, ins_k_apply_bc_p_fields)
-  INS_LINE_INDEX(be);
-  const long long sb = g.sx[be];
-  const int bcl = g.bc[be][0], bcr = g.bc[be][1];
-  const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
-  if (bcl == INS_BC_PERIODIC) {  // boundary_conditions.jl:306-318
-    p[base + ia * sb] = p[base + (ib - 1) * sb];
-    p[base + ib * sb] = p[base + (ia + 1) * sb];
-    return;
-  }
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const int bc = side ? bcr : bcl;
-    const int i = side ? ib : ia;
-    const int jn = side ? i - 1 : i + 1;
-    if (bc == INS_BC_SYMMETRIC)  // boundary_conditions.jl:445-453
-      p[base + i * sb] = p[base + jn * sb];
-    else if (bc == INS_BC_PRESSURE)  // boundary_conditions.jl:497-502
-      p[base + i * sb] = 0.0;
-    // Dirichlet: no-op (boundary_conditions.jl:388); HALO: caller
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // Box reductions: per-block partials (wavefront shuffles + LDS), finished on the host — these calls
@@ -123,7 +57,7 @@ int ins_k_apply_bc_u(const ins_grid* G, double* u, int dudt, const double* const
   const GridDev& g = G->g;
   for (int be = 0; be < g.D; ++be) {
     if (g.bc[be][0] == INS_BC_HALO && g.bc[be][1] == INS_BC_HALO) continue;
-    INS_LAUNCH_D((k_bc_u<D>), line_launch(g, be, g.D), s, g, u, be, dudt, planes);
+    INS_LAUNCH_D((k_bc_u<D, double>), line_launch(g, be, g.D), s, g, u, be, dudt, planes);
   }
   return INS_OK;
 }
@@ -135,7 +69,7 @@ int ins_k_apply_bc_p_fields(const ins_grid* G, double* p, int nf, hipStream_t s)
     const int l = g.bc[be][0], r = g.bc[be][1];
     const bool noop = (l == INS_BC_DIRICHLET || l == INS_BC_HALO) && (r == INS_BC_DIRICHLET || r == INS_BC_HALO);
     if (noop) continue;
-    INS_LAUNCH_D((k_bc_p<D>), line_launch(g, be, nf), s, g, p, be, G->ncell);
+    INS_LAUNCH_D((k_bc_p<D, double>), line_launch(g, be, nf), s, g, p, be, G->ncell);
   }
   return INS_OK;
 }

@@ -3,71 +3,25 @@
 //
 //   fields      : Float32 arrays in the reference layout; the grid handle is the fp64 one — metric tables are read as doubles and rounded to float where
 //                 they enter the arithmetic (one table for both families; the tables are a few KB and stay in cache);
-//   operators   : one work-item per volume, x along the wavefront, the same index rules as csrc/ins_operators.hip / ins_bc.hip (which cite the reference
-//                 lines); all arithmetic in float;
+//   operators   : all arithmetic in float.  The ghost fills and the divergence are the float instantiations of csrc/ins_operator_kernels.h (k_bc_u, k_bc_p,
+//                 k_divergence; boundary data constant: no plane buffers).  k32g_momentum and k32g_applypressure stay copies of k_convdiff<D, 3, true>
+//                 and k_pressuregradient<D, true> (csrc/ins_operators.hip, which cites the reference lines) — see the note at k32g_momentum;
 //   projection  : Ω·div(u) is formed from the float field in DOUBLE, the fp64 solver the caller wrapped (direct = fast diagonalisation, CG, spectral) runs
 //                 unchanged, and the pressure is rounded to float once: a mixed-precision projection whose pressure is at least as accurate as a
 //                 Float32 factorisation's (the reference's T = Float32 runs its sparse LU in Float32, pressure.jl:101-154).
 // Slab (HALO) sides are not taken: the multi-GPU path is fp64.
 #include <cmath>
 
-#include "ins_stencil.h"
+#include "ins_operator_kernels.h"
 
 namespace {
 
-// apply_bc_u!                                   boundary_conditions.jl:159-206, 276-288, 344-375, 414-428, 472-482 (constant boundary data)
-template <int D>
-__global__ __launch_bounds__(256) void k32g_bc_u(GridDev g, float* __restrict__ u, int be) {
-  INS_LINE_INDEX(be);
-  const int al = blockIdx.z;
-  const long long sb = g.sx[be];
-  float* ua = u + al * g.sc;
-  const int bcl = g.bc[be][0], bcr = g.bc[be][1];
-  if (bcl == INS_BC_PERIODIC) {
-    const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
-    ua[base + ia * sb] = ua[base + (ib - 1) * sb];
-    ua[base + ib * sb] = ua[base + (ia + 1) * sb];
-    return;
-  }
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const int bc = side ? bcr : bcl;
-    const int i = side ? g.iu_hi[al][be] : g.iu_lo[al][be] - 1;
-    const int jn = side ? i - 1 : i + 1;
-    float* dst = ua + base + i * sb;
-    if (bc == INS_BC_DIRICHLET)
-      *dst = (float)g.bc_u[be][side][al];
-    else if (bc == INS_BC_SYMMETRIC)
-      *dst = (al == be) ? 0.f : ua[base + jn * sb];
-    else if (bc == INS_BC_PRESSURE)
-      *dst = ua[base + jn * sb];
-  }
-}
-
-// apply_bc_p!                                   boundary_conditions.jl:306-318, 388, 445-453, 497-502
-template <int D>
-__global__ __launch_bounds__(256) void k32g_bc_p(GridDev g, float* __restrict__ p, int be) {
-  INS_LINE_INDEX(be);
-  const long long sb = g.sx[be];
-  const int bcl = g.bc[be][0], bcr = g.bc[be][1];
-  const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
-  if (bcl == INS_BC_PERIODIC) {
-    p[base + ia * sb] = p[base + (ib - 1) * sb];
-    p[base + ib * sb] = p[base + (ia + 1) * sb];
-    return;
-  }
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const int bc = side ? bcr : bcl;
-    const int i = side ? ib : ia;
-    const int jn = side ? i - 1 : i + 1;
-    if (bc == INS_BC_SYMMETRIC)
-      p[base + i * sb] = p[base + jn * sb];
-    else if (bc == INS_BC_PRESSURE)
-      p[base + i * sb] = 0.f;
-  }
-}
-
+// k32g_momentum / k32g_applypressure (and k32t_diffusion, csrc/ins_temp32.hip) are NOT instantiations of one template shared with k_convdiff /
+// k_pressuregradient, and cannot be: under -ffp-contract=on a fused multiply-add forms only inside one expression, and the twins are spelled
+// with different statement boundaries.  These form the diffusive difference, ν·(…) − (…) and `u -= ∇p` as FMAs (54 per volume in k32g_momentum<3>); the
+// fp64 kernels round d1, d2, the viscous term and the gradient separately (36).  Either spelling, used for both, changes the results of the other
+// precision (profiles/forward_generic_isa.md).  So a fix to one of these stencils goes into its twin as well.
+//
 // momentum! = fill!(F, 0) + convectiondiffusion!                                         operators.jl:647-690, 971
 template <int D>
 __global__ __launch_bounds__(256) void k32g_momentum(GridDev g, float visc, const float* __restrict__ u, float* __restrict__ F) {
@@ -106,25 +60,6 @@ __global__ __launch_bounds__(256) void k32g_momentum(GridDev g, float visc, cons
   }
 }
 
-// divergence! on Ip (operators.jl:117-125); SCALE: times the volume (scalewithvolume!, operators.jl:81-95).  P = double: the differences are taken in double
-// (the right-hand side of the fp64 solver); P = float: the diagnostic.
-template <int D, typename P, bool SCALE>
-__global__ __launch_bounds__(256) void k32g_div(GridDev g, const float* __restrict__ u, P* __restrict__ out) {
-  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], i >= g.ip_hi[0] || j >= g.ip_hi[1]);
-  P d = 0;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    const float* ua = u + a * g.sc;
-    d += ((P)ua[c] - (P)ua[c - g.sx[a]]) * (P)g.rdx[a][I[a]];
-  }
-  if (SCALE) {
-    P om = (P)g.dx[0][i] * (P)g.dx[1][j];
-    if (D == 3) om *= (P)g.dx[2][k];
-    d *= om;
-  }
-  out[c] = d;
-}
-
 // applypressure!                                                                          operators.jl:225-233
 template <int D>
 __global__ __launch_bounds__(256) void k32g_applypressure(GridDev g, float* __restrict__ u, const float* __restrict__ p) {
@@ -151,7 +86,7 @@ int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s) {
   int rc = no_halo(G, "apply_bc_u (f32)");
   if (rc) return rc;
   for (int be = 0; be < g.D; ++be) {  // direction after direction: edges and corners come out as in the reference (boundary_conditions.jl:162-165)
-    INS_LAUNCH_D((k32g_bc_u<D>), line_launch(g, be, g.D), s, g, u, be);
+    INS_LAUNCH_D((k_bc_u<D, float>), line_launch(g, be, g.D), s, g, u, be, 0, (const float* const*)nullptr);  // constant boundary data
   }
   return INS_OK;
 }
@@ -162,7 +97,7 @@ int ins_k32g_apply_bc_p(const ins_grid* G, float* p, hipStream_t s) {
   if (rc) return rc;
   for (int be = 0; be < g.D; ++be) {
     if (g.bc[be][0] == INS_BC_DIRICHLET && g.bc[be][1] == INS_BC_DIRICHLET) continue;  // no-op (boundary_conditions.jl:388)
-    INS_LAUNCH_D((k32g_bc_p<D>), line_launch(g, be, 1), s, g, p, be);
+    INS_LAUNCH_D((k_bc_p<D, float>), line_launch(g, be, 1), s, g, p, be, 0LL);
   }
   return INS_OK;
 }
@@ -176,7 +111,7 @@ int ins_k32g_momentum(const ins_grid* G, float visc, const float* u, float* F, h
 // div[Ip] = divergence(u) (padded float array; volumes outside Ip are left as they are)
 int ins_k32g_divergence(const ins_grid* G, const float* u, float* div, hipStream_t s) {
   const GridDev& g = G->g;
-  INS_LAUNCH_D((k32g_div<D, float, false>), box_launch(g.D, g.ip_lo, g.ip_hi), s, g, u, div);
+  INS_LAUNCH_D((k_divergence<D, float, float, false>), box_launch(g.D, g.ip_lo, g.ip_hi), s, g, u, div);
   return INS_OK;
 }
 
@@ -197,7 +132,7 @@ int ins_k32g_project(const ins_grid* G, ins_poisson* ps64, double* p64, float* u
   const GridDev& g = G->g;
   int rc = no_halo(G, "project (f32)");
   if (rc) return rc;
-  INS_LAUNCH_D((k32g_div<D, double, true>), box_launch(g.D, g.ip_lo, g.ip_hi), s, g, u, p64);
+  INS_LAUNCH_D((k_divergence<D, float, double, true>), box_launch(g.D, g.ip_lo, g.ip_hi), s, g, u, p64);
   if ((rc = ins_k_poisson_solve(ps64, p64, s))) return rc;
   hipLaunchKernelGGL(k32g_round, flat_grid(G->ncell), dim3(256), 0, s, G->ncell, p64, p);
   INS_LAUNCH_CHECK();

@@ -3,7 +3,9 @@
 // Same conventions as ins_operators.hip: one work-item per volume, x along the 64-lane wavefront (unit-stride row segments),
 // any boundary conditions, 2-D and 3-D, stretched grids.  All are single HBM passes; reciprocal metric tables replace the
 // reference's divisions (<= 1 ulp per term, inside the 1e-12 parity tolerance).
-#include "ins_stencil.h"
+// k_gravity, k_dissipation_interp, k_bc_temp and avg_at are the double instantiations of ins_temp_kernels.h (shared with ins_temp32.hip);
+// k_convdiff_temp and k_temp_stage are written here and have float copies in ins_temp32.hip: a fix to one goes into the other as well.
+#include "ins_temp_kernels.h"
 
 namespace {
 
@@ -525,12 +527,6 @@ __global__ __launch_bounds__(256) void k_gradient_rows(GridDev g, BoxMap L, int 
 // --------------------------------------------------------------------------------------------
 // temperature equation
 // --------------------------------------------------------------------------------------------
-// avg(ϕ, Δ, I, α)                                                               operators.jl:59-62
-__device__ __forceinline__ double avg_at(const GridDev& g, const double* __restrict__ phi, long long c, int ia, int a) {
-  const double d0 = g.dx[a][ia], d1 = g.dx[a][ia + 1];
-  return (d1 * phi[c] + d0 * phi[c + g.sx[a]]) / (d0 + d1);
-}
-
 // convection_diffusion_temp!  (c += ...)                                       operators.jl:712-737
 template <int D>
 __global__ __launch_bounds__(256) void k_convdiff_temp(GridDev g, BoxMap L, double a4, const double* __restrict__ u, const double* __restrict__ temp,
@@ -549,21 +545,6 @@ __global__ __launch_bounds__(256) void k_convdiff_temp(GridDev g, BoxMap L, doub
     acc += (-(uT2 - uT1) + a4 * (dT2 - dT1)) * g.rdx[b][I[b]];
   }
   out[c] += acc;
-}
-
-// dissipation!: interpolation of u · diffusion(u) to the pressure points  (diss += ...)   operators.jl:800-810
-template <int D>
-__global__ __launch_bounds__(256) void k_dissipation_interp(GridDev g, BoxMap L, double coef, const double* __restrict__ u, const double* __restrict__ diff,
-                                                            double* __restrict__ diss) {
-  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
-  double d = 0.0;
-#pragma unroll
-  for (int b = 0; b < D; ++b) {
-    const double* ub = u + b * g.sc;
-    const double* db = diff + b * g.sc;
-    d += coef * (ub[c - g.sx[b]] * db[c - g.sx[b]] + ub[c] * db[c]) / 2;
-  }
-  diss[c] += d;
 }
 
 // One stage of the temperature equation in one pass (extended stage loop, ins_rk_ext.hip; step_explicit_runge_kutta.jl:23-27, 39-44):
@@ -632,42 +613,6 @@ __global__ __launch_bounds__(256) void k_temp_stage(GridDev g, BoxMap L, double 
   t += ts.c_self * acc;
   if (ts.ktemp_out) ts.ktemp_out[c] = acc;
   ts.temp_out[c] = t;
-}
-
-// gravity!  (F[:, gdir] += α2 avg(temp))   over the whole Iu[gdir]                     operators.jl:914-931
-template <int D>
-__global__ __launch_bounds__(256) void k_gravity(GridDev g, BoxMap L, int gdir, double a2, const double* __restrict__ temp, double* __restrict__ F) {
-  INS_BANDED_INDEX(g.iu_lo[gdir][0], g.iu_lo[gdir][1], g.iu_lo[gdir][2], g.iu_hi[gdir][0], g.iu_hi[gdir][1]);
-  F[gdir * g.sc + c] += a2 * avg_at(g, temp, c, gdir == 0 ? i : (gdir == 1 ? j : k), gdir);
-}
-
-// apply_bc_temp!                               boundary_conditions.jl:236-246, 338-339, 391-405, 466-467, 512-513
-// One work-item per point of the full padded plane (boundary(), :97-103).  Dirichlet value: constant, or a plane buffer.
-struct TempBC {
-  int bc[2];
-  double val[2];
-  const double* plane[2];
-};
-template <int D>
-__global__ __launch_bounds__(256) void k_bc_temp(GridDev g, double* __restrict__ temp, int be, TempBC t) {
-  INS_LINE_INDEX(be);
-  const long long sb = g.sx[be];
-  const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
-  if (t.bc[0] == INS_BC_PERIODIC) {
-    temp[base + ia * sb] = temp[base + (ib - 1) * sb];
-    temp[base + ib * sb] = temp[base + (ia + 1) * sb];
-    return;
-  }
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const int bc = t.bc[side];
-    const int i = side ? ib : ia;
-    const int jn = side ? i - 1 : i + 1;
-    if (bc == INS_BC_DIRICHLET)
-      temp[base + i * sb] = t.plane[side] ? t.plane[side][q0 + (long long)q1 * g.N[o0]] : t.val[side];
-    else if (bc == INS_BC_SYMMETRIC || bc == INS_BC_PRESSURE)
-      temp[base + i * sb] = temp[base + jn * sb];
-  }
 }
 
 // --------------------------------------------------------------------------------------------
@@ -934,7 +879,7 @@ extern "C" int ins_apply_bc_temp_f64(const ins_grid_t* G, const int32_t* bc, con
   INS_REQUIRE(G && bc && val && temp, "null argument");
   const GridDev& g = G->g;
   for (int be = 0; be < g.D; ++be) {
-    TempBC t;
+    TempBC<double> t;
     for (int side = 0; side < 2; ++side) {
       t.bc[side] = bc[2 * be + side];
       t.val[side] = val[2 * be + side];
@@ -943,7 +888,7 @@ extern "C" int ins_apply_bc_temp_f64(const ins_grid_t* G, const int32_t* bc, con
                   "temperature boundary condition");
     }
     INS_REQUIRE((t.bc[0] == INS_BC_PERIODIC) == (t.bc[1] == INS_BC_PERIODIC), "periodic on both sides");
-    INS_LAUNCH_D((k_bc_temp<D>), line_launch(g, be, 1), as_stream(stream), g, temp, be, t);
+    INS_LAUNCH_D((k_bc_temp<D, double>), line_launch(g, be, 1), as_stream(stream), g, temp, be, t);
   }
   return INS_OK;
 }
@@ -992,7 +937,7 @@ extern "C" int ins_dissipation_f64(const ins_grid_t* G, double visc, double coef
   if (rc == INS_ERR_UNSUPPORTED) rc = ins_k_diffusion_overwrite(G, visc, u, diff, as_stream(stream));
   if (rc != INS_OK) return rc;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D((k_dissipation_interp<D>), l, as_stream(stream), g, l.map, coef, u, (const double*)diff, diss);
+  INS_LAUNCH_D((k_dissipation_interp<D, double>), l, as_stream(stream), g, l.map, coef, u, (const double*)diff, diss);
   return INS_OK;
 }
 
@@ -1001,7 +946,7 @@ extern "C" int ins_gravity_f64(const ins_grid_t* G, int gdir, double a2, const d
   const GridDev& g = G->g;
   INS_REQUIRE(gdir >= 0 && gdir < g.D, "gravity direction");
   Launch3 l = banded_launch(g.D, g.iu_lo[gdir], g.iu_hi[gdir]);
-  INS_LAUNCH_D((k_gravity<D>), l, as_stream(stream), g, l.map, gdir, a2, temp, F);
+  INS_LAUNCH_D((k_gravity<D, double>), l, as_stream(stream), g, l.map, gdir, a2, temp, F);
   return INS_OK;
 }
 

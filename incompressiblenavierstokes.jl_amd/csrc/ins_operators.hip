@@ -2,7 +2,10 @@
 // x along the 64-lane wavefront so every global access is a unit-stride row segment.
 // These are the reference-faithful twins of operators.jl; the tiled 3-D fast paths live in
 // ins_fast3d.hip and are parity-tested against these and against the CPU oracle.
-#include "ins_stencil.h"
+// k_divergence is the double instantiation of ins_operator_kernels.h (shared with ins_f32g.hip); k_convdiff and k_pressuregradient have
+// float copies there (k32g_momentum, k32g_applypressure; k32t_diffusion in ins_temp32.hip) that contract their FMAs differently: a fix to
+// one goes into the other as well.
+#include "ins_operator_kernels.h"
 
 namespace {
 
@@ -117,21 +120,6 @@ int launch_convdiff(const ins_grid* G, double visc, const double* u, double* F, 
   return INS_OK;
 }
 
-// --------------------------------------------------------------------------------------------
-// divergence                                                              operators.jl:117-125
-// --------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_divergence(GridDev g, const double* __restrict__ u, double* __restrict__ div) {
-  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], i >= g.ip_hi[0] || j >= g.ip_hi[1]);
-  double d = 0.0;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    const double* ua = u + a * g.sc;
-    d += (ua[c] - ua[c - g.sx[a]]) * g.rdx[a][I[a]];
-  }
-  div[c] = d;
-}
-
 // scalewithvolume!                                                          operators.jl:81-95
 template <int D>
 __global__ __launch_bounds__(256) void k_scalewithvolume(GridDev g, double* __restrict__ p) {
@@ -237,7 +225,7 @@ int ins_k_diffusion_overwrite(const ins_grid* G, double visc, const double* u, d
 int ins_k_divergence(const ins_grid* G, const double* u, double* div, hipStream_t s) {
   const GridDev& g = G->g;
   Launch3 l = box_launch(g.D, g.ip_lo, g.ip_hi);
-  INS_LAUNCH_D((k_divergence<D>), l, s, g, u, div);
+  INS_LAUNCH_D((k_divergence<D, double, double, false>), l, s, g, u, div);
   return INS_OK;
 }
 

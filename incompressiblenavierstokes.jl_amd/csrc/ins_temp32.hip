@@ -1,16 +1,20 @@
 // The temperature equation of the `_f32` family (T = Float32; examples/RayleighBenard2D.jl:71 and examples/RayleighBenard3D.jl:16 run it in single precision):
-// the float twins of the temperature kernels of csrc/ins_fields.hip (which cite the reference lines), on ANY grid the fp64 ones take — 2-D / 3-D, periodic,
+// the temperature kernels of csrc/ins_fields.hip and csrc/ins_temp_kernels.h (which cite the reference lines) in float, on ANY grid the fp64 ones take — 2-D / 3-D, periodic,
 // Dirichlet, symmetric and pressure temperature sides, uniform and stretched spacings.
 //
 //   fields      : Float32 arrays in the reference layout; the grid handle is the fp64 one, metric tables are read as doubles and rounded to float where they
 //                 enter the arithmetic (as csrc/ins_f32g.hip); all arithmetic in float;
 //   operators   : apply_bc_temp!, convection_diffusion_temp! (c += ...), dissipation! (diss += ...; needs a float diffusion! alone, k32t_diffusion),
-//                 gravity! (F[:, gdir] += ...): the write sets, += rules and BC codes of the `_f64` entries; boundary data constant;
+//                 gravity! (F[:, gdir] += ...): the write sets, += rules and BC codes of the `_f64` entries; boundary data constant (no plane buffers).
+//                 k_bc_temp, k_gravity and k_dissipation_interp are the float instantiations of csrc/ins_temp_kernels.h;
+//   kept copies : k32t_convdiff_temp and k32t_stage (of k_convdiff_temp and k_temp_stage without its in-kernel pressure correction and `w` input,
+//                 csrc/ins_fields.hip): the same arithmetic, but no spelling tried reproduces the instruction schedule of both precisions
+//                 (profiles/forward_generic_isa.md lists them); k32t_diffusion (of k_convdiff<D, 2, true>): other FMA contraction, see k32g_momentum in
+//                 csrc/ins_f32g.hip.  A fix to one of these goes into its fp64 twin as well;
 //   stage kernel: one pass over Ip forms ktemp_i = convection_diffusion_temp(u, temp) + dissipation(u) and temp_out = tempstart + Σ_j Δt A[i,j] ktemp_j
-//                 (k32t_stage, the twin of k_temp_stage without in-kernel pressure correction); the stage loop that calls it is ins_rk_step_ext_f32
-//                 (csrc/ins_f32.hip, beside the isothermal loop whose handle it extends).
+//                 (k32t_stage); the stage loop that calls it is ins_rk_step_ext_f32 (csrc/ins_f32.hip, beside the isothermal loop whose handle it extends).
 // Slab (HALO) sides are not taken: the multi-GPU path is fp64.
-#include "ins_stencil.h"
+#include "ins_temp_kernels.h"
 
 namespace {
 
@@ -72,21 +76,6 @@ __global__ __launch_bounds__(256) void k32t_diffusion(GridDev g, float visc, con
   }
 }
 
-// dissipation!: interpolation of u · diffusion(u) to the pressure points  (diss += ...)   operators.jl:800-810
-template <int D>
-__global__ __launch_bounds__(256) void k32t_dissipation_interp(GridDev g, BoxMap L, float coef, const float* __restrict__ u, const float* __restrict__ diff,
-                                                               float* __restrict__ diss) {
-  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
-  float d = 0.f;
-#pragma unroll
-  for (int b = 0; b < D; ++b) {
-    const float* ub = u + b * g.sc;
-    const float* db = diff + b * g.sc;
-    d += coef * (ub[c - g.sx[b]] * db[c - g.sx[b]] + ub[c] * db[c]) / 2;
-  }
-  diss[c] += d;
-}
-
 // One stage of the temperature equation in one pass over Ip (ins_rk_step_ext_f32; step_explicit_runge_kutta.jl:23-27, 39-44):
 //   ktemp_i  = convection_diffusion_temp(u, temp) + coef · Σ_β (u_β diff_β at the two faces) / 2        (diff = diffusion(u): zero off the DOFs; nullable)
 //   temp_out = tempstart + Σ_j c_j ktemp_j + c_self ktemp_i
@@ -125,42 +114,6 @@ __global__ __launch_bounds__(256) void k32t_stage(GridDev g, BoxMap L, float a4,
   t += ts.c_self * acc;
   if (ts.ktemp_out) ts.ktemp_out[c] = acc;
   ts.temp_out[c] = t;
-}
-
-// gravity!  (F[:, gdir] += α2 avg(temp))   over the whole Iu[gdir]                     operators.jl:914-931
-template <int D>
-__global__ __launch_bounds__(256) void k32t_gravity(GridDev g, BoxMap L, int gdir, float a2, const float* __restrict__ temp, float* __restrict__ F) {
-  INS_BANDED_INDEX(g.iu_lo[gdir][0], g.iu_lo[gdir][1], g.iu_lo[gdir][2], g.iu_hi[gdir][0], g.iu_hi[gdir][1]);
-  const int ia = gdir == 0 ? i : (gdir == 1 ? j : k);
-  F[gdir * g.sc + c] += a2 * avg32((float)g.dx[gdir][ia], (float)g.dx[gdir][ia + 1], temp[c], temp[c + g.sx[gdir]]);
-}
-
-// apply_bc_temp!, constant boundary data       boundary_conditions.jl:236-246, 338-339, 391-405, 466-467, 512-513
-// One work-item per point of the full padded plane (boundary(), :97-103).
-struct TempBC32 {
-  int bc[2];
-  float val[2];
-};
-template <int D>
-__global__ __launch_bounds__(256) void k32t_bc_temp(GridDev g, float* __restrict__ temp, int be, TempBC32 t) {
-  INS_LINE_INDEX(be);
-  const long long sb = g.sx[be];
-  const int ia = g.ip_lo[be] - 1, ib = g.ip_hi[be];
-  if (t.bc[0] == INS_BC_PERIODIC) {
-    temp[base + ia * sb] = temp[base + (ib - 1) * sb];
-    temp[base + ib * sb] = temp[base + (ia + 1) * sb];
-    return;
-  }
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const int bc = t.bc[side];
-    const int i = side ? ib : ia;
-    const int jn = side ? i - 1 : i + 1;
-    if (bc == INS_BC_DIRICHLET)
-      temp[base + i * sb] = t.val[side];
-    else if (bc == INS_BC_SYMMETRIC || bc == INS_BC_PRESSURE)
-      temp[base + i * sb] = temp[base + jn * sb];
-  }
 }
 
 inline Launch3 ip_launch(const GridDev& g) { return banded_launch(g.D, g.ip_lo, g.ip_hi); }
@@ -203,15 +156,16 @@ extern "C" int ins_apply_bc_temp_f32(const ins_grid_t* G, const int32_t* bc, con
   int rc = no_halo(G, "ins_apply_bc_temp_f32");
   if (rc) return rc;
   for (int be = 0; be < g.D; ++be) {  // direction after direction, as apply_bc_temp!: edges and corners come out as in the reference
-    TempBC32 t;
+    TempBC<float> t;
     for (int side = 0; side < 2; ++side) {
       t.bc[side] = bc[2 * be + side];
       t.val[side] = val[2 * be + side];
+      t.plane[side] = nullptr;  // constant boundary data
       INS_REQUIRE(t.bc[side] == INS_BC_PERIODIC || t.bc[side] == INS_BC_DIRICHLET || t.bc[side] == INS_BC_SYMMETRIC || t.bc[side] == INS_BC_PRESSURE,
                   "temperature boundary condition");
     }
     INS_REQUIRE((t.bc[0] == INS_BC_PERIODIC) == (t.bc[1] == INS_BC_PERIODIC), "periodic on both sides");
-    INS_LAUNCH_D((k32t_bc_temp<D>), line_launch(g, be, 1), as_stream(stream), g, temp, be, t);
+    INS_LAUNCH_D((k_bc_temp<D, float>), line_launch(g, be, 1), as_stream(stream), g, temp, be, t);
   }
   return INS_OK;
 }
@@ -234,7 +188,7 @@ extern "C" int ins_dissipation_f32(const ins_grid_t* G, float visc, float coef, 
   if (rc) return rc;
   if ((rc = ins_k32t_diffusion(G, visc, u, diff, as_stream(stream)))) return rc;  // fill!(diff, 0); diffusion!(diff, u, setup)     operators.jl:797-798
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D((k32t_dissipation_interp<D>), l, as_stream(stream), g, l.map, coef, u, (const float*)diff, diss);
+  INS_LAUNCH_D((k_dissipation_interp<D, float>), l, as_stream(stream), g, l.map, coef, u, (const float*)diff, diss);
   return INS_OK;
 }
 
@@ -245,6 +199,6 @@ extern "C" int ins_gravity_f32(const ins_grid_t* G, int gdir, float a2, const fl
   int rc = no_halo(G, "ins_gravity_f32");
   if (rc) return rc;
   Launch3 l = banded_launch(g.D, g.iu_lo[gdir], g.iu_hi[gdir]);
-  INS_LAUNCH_D((k32t_gravity<D>), l, as_stream(stream), g, l.map, gdir, a2, temp, F);
+  INS_LAUNCH_D((k_gravity<D, float>), l, as_stream(stream), g, l.map, gdir, a2, temp, F);
   return INS_OK;
 }

@@ -1,6 +1,6 @@
 // Reverse-mode pullbacks of the temperature equation of the `_f32` family (operators.jl:712-737, 791-814, 884-931; boundary_conditions.jl:236-270,
-// 338-342, 391-412, 466-470, 512-516): each the exact transpose of the `_f32` forward operator (csrc/ins_temp32.hip: k32t_bc_temp, k32t_gravity,
-// k32t_convdiff_temp, k32t_diffusion + k32t_dissipation_interp) on the whole padded arrays, ghost volumes included (DESIGN.md "Differentiability").
+// 338-342, 391-412, 466-470, 512-516): each the exact transpose of the `_f32` forward operator (csrc/ins_temp32.hip: k_bc_temp, k_gravity,
+// k32t_convdiff_temp, k32t_diffusion + k_dissipation_interp) on the whole padded arrays, ghost volumes included (DESIGN.md "Differentiability").
 //
 // The kernels are the templates of ins_temp_adjoint_kernels.h with T = float, the ones ins_temp_adjoint.hip instantiates with double: float
 // fields in the reference layout, the fp64 grid handle, metric tables read as doubles and rounded to float where they enter the arithmetic,

@@ -2,8 +2,8 @@
 // 391-412, 466-470, 512-516), once for both precisions: templates over the scalar type T of the fields, instantiated with double by
 // ins_temp_adjoint.hip and with float by ins_temp_adjoint32.hip (two translation units, so that each keeps its register allocation).  Each
 // is the exact transpose of THIS library's forward operator on the whole padded arrays (DESIGN.md "Differentiability", "Temperature
-// equation"): with T = double of k_bc_temp, k_gravity, k_convdiff_temp, diffusion + k_dissipation_interp (ins_fields.hip), with T = float of
-// k32t_bc_temp, k32t_gravity, k32t_convdiff_temp, k32t_diffusion + k32t_dissipation_interp (ins_temp32.hip).
+// equation"): of k_bc_temp, k_gravity and k_dissipation_interp (ins_temp_kernels.h, both precisions), with T = double of k_convdiff_temp and
+// diffusion (ins_fields.hip, ins_operators.hip), with T = float of k32t_convdiff_temp and k32t_diffusion (ins_temp32.hip).
 // The reference's own rules stop short here: the rrule of convection_diffusion_temp returns undefined names (operators.jl:699-704) and
 // dissipation's is @test_broken; only gravity and apply_bc_temp have working pullbacks.
 //
@@ -15,7 +15,7 @@
 // The one rule for both precisions (ins_adjoint_kernels.h): the grid handle is the fp64 one, a metric table entry is read as a double and
 // converted with (T) where it enters the arithmetic, constants are written T(…), and everything else is in T.  With T = double the
 // conversions vanish.  With T = float the weights are formed as the Float32 forward forms them — (float)Δ first, then d1 / (d0 + d1) in
-// float, as avg32 — so the pullback is the transpose of the Float32 operator up to float rounding, not the fp64 transpose rounded at the end.
+// float, as avg_at<float> and avg32 — so the pullback is the transpose of the Float32 operator up to float rounding, not the fp64 transpose rounded at the end.
 //
 // A face is evaluated only where the forward evaluated it: the in_ip / in_iu / dof masks are branches around the reads, never factors.  A
 // zero-width ghost volume has Δ = eps(Float64), so 1/Δ ≈ 4.5e15: finite in float, and so is the product of two such entries, but a masked-out
@@ -220,7 +220,7 @@ int launch_temp_adjoint(const ins_grid* G, const TempAdjArgs<T>& a, hipStream_t 
 
 // --------------------------------------------------------------------------------------------
 // apply_bc_temp_pullback         boundary_conditions.jl:142-157, 248-270, 341-342, 407-412, 469-470, 515-516
-//   The exact transpose of k_bc_temp (ins_fields.hip) and k32t_bc_temp (ins_temp32.hip): the forward sweeps β = 0..D-1 and fills, per line,
+//   The exact transpose of k_bc_temp (ins_temp_kernels.h): the forward sweeps β = 0..D-1 and fills, per line,
 //   the left then the right ghost volume with a copy (x[i] = x[j]) or a Dirichlet value; the transpose walks β = D-1..0 and the sides right
 //   then left, turning x[i] = x[j] into (x̄[j] += x̄[i]; x̄[i] = 0) and x[i] = value into x̄[i] = 0.  The Dirichlet values (constant or
 //   callable) only change the constant part, so neither they nor t enter.

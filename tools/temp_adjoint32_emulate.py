@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """CPU emulation of the Float32 dissipation pullback (csrc/ins_temp_adjoint_kernels.h, diss_ubar) and of its Float32 forward
-(csrc/ins_temp32.hip, k32t_diffusion + k32t_dissipation_interp): the kernels' formulas in numpy with the metric tables and the inputs cast
+(csrc/ins_temp32.hip, k32t_diffusion + k_dissipation_interp<D, float>): the kernels' formulas in numpy with the metric tables and the inputs cast
 to float32 and every operation in float32, against the same formulas in float64.  No GPU: the figures say what Float32 rounding alone does
 to the pullback's longer chain (it recomputes diffusion(u) and applies diffusionᵀ to wbar ⊙ u) relative to the forward, on the geometries
 of tests/test_gpu_temp_adjoint32.py, whose docstring records them.
