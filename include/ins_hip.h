@@ -621,10 +621,30 @@ int ins_rk_set_temperature_f32(ins_rk32_t* rk, const ins_temperature_desc_t* des
  * kernel over Ip forms ktemp_i and the stage temperature, :23-27 and :39-44; INS_DISABLE_TEMP32_STAGE=1 runs the operators one by one instead), the
  * combination of u, project!.  Every grid ins_rk_step_f32 takes (walls / stretched spacings: a solver made by ins_poisson_wrap_f32); the 64-wide stage
  * kernel, the in-register correction and chained steps are not used with a temperature.  `temp` is required exactly when a descriptor is set
- * (else INS_ERR_INVALID); without either the call is ins_rk_step_f32.  Asynchronous. */
+ * (else INS_ERR_INVALID).  A closure (ins_rk_set_closure_f32) and a steady body force (ins_rk_set_bodyforce_f32) join the stage force in any
+ * combination with the temperature, which may then be absent; with none of the three the call is ins_rk_step_f32.  Asynchronous. */
 int ins_rk_step_ext_f32(ins_rk32_t* rk, float visc, float* u, float* temp, float dt, void* stream);
 /* nsteps such steps (the fixed-Δt loop of solve_unsteady, solver.jl:74-83) in one call */
 int ins_rk_steps_ext_f32(ins_rk32_t* rk, float visc, float* u, float* temp, float dt, int nsteps, void* stream);
+
+/* ---------------------------------------------------------------------------------- Float32 Smagorinsky closure and steady body force
+ * (csrc/ins_smagforce32.hip, csrc/ins_f32.hip).  The `_f32` twins of ins_smagtensor_f64, ins_smagorinsky_force_f64, ins_rk_set_closure and
+ * ins_rk_set_bodyforce: the same layouts and write sets on float fields (the grid handle is the fp64 one; all arithmetic in float).
+ * Slab grids: INS_ERR_UNSUPPORTED. */
+/* smagtensor!(σ, u, θ, setup)              operators.jl:1135-1150.  σ: D(D+1)/2 scalar fields [xx, yy, (zz), xy, (xz, yz)], written on Ip;
+ * ghost-fill each with ins_apply_bc_p_f32 as smagorinsky_closure does (:1296). */
+int ins_smagtensor_f32(const ins_grid_t* grid, float theta, const float* u, float* sigma, void* stream);
+/* smagorinsky_closure(setup)(u, θ) = divoftensor(apply_bc_p(smagtensor(u, θ)))   operators.jl:1284-1300 as one call.  The route is that of
+ * ins_smagorinsky_force_f64: one kernel with the stress in registers where ins_smagorinsky_force_needs_sigma answers 0 (sigma may be NULL),
+ * else the three kernels with `sigma` (D(D+1)/2 scalar fields) as scratch.  Writes the degrees of freedom of s. */
+int ins_smagorinsky_force_f32(const ins_grid_t* grid, float theta, const float* u, float* sigma, float* s, void* stream);
+/* kind 0: no closure; 1: smagorinsky_closure(setup) with constant θ (operators.jl:1294-1305), added to every stage force of
+ * ins_rk_step_ext_f32 / ins_rk_steps_ext_f32 (step_explicit_runge_kutta.jl:31-34). */
+int ins_rk_set_closure_f32(ins_rk32_t* rk, int32_t kind, float theta);
+/* Steady body force (setup.bodyforce with issteadybodyforce, setup.jl:25-32; operators.jl:873-880 `F .+= bodyforce`): a DEVICE float vector
+ * field the caller keeps alive, added to every stage force of ins_rk_step_ext_f32 / ins_rk_steps_ext_f32 as one more term of the stage
+ * combination.  NULL removes it. */
+int ins_rk_set_bodyforce_f32(ins_rk32_t* rk, const float* force);
 
 /* ---------------------------------------------------------------------------------- pullbacks of the Float32 temperature equation
  * (csrc/ins_temp_adjoint32.hip)  The float twins of the `_f64` temperature pullbacks above, argument for argument: each is the exact transpose of

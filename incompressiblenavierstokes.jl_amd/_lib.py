@@ -196,6 +196,10 @@ SIGNATURES = {
     "ins_rk_set_temperature_f32": (C.c_int, [vp, vp]),
     "ins_rk_step_ext_f32": (C.c_int, [vp, C.c_float, vp, vp, C.c_float, vp]),
     "ins_rk_steps_ext_f32": (C.c_int, [vp, C.c_float, vp, vp, C.c_float, C.c_int, vp]),
+    "ins_smagtensor_f32": (C.c_int, [vp, C.c_float, vp, vp, vp]),
+    "ins_smagorinsky_force_f32": (C.c_int, [vp, C.c_float, vp, vp, vp, vp]),
+    "ins_rk_set_closure_f32": (C.c_int, [vp, C.c_int32, C.c_float]),
+    "ins_rk_set_bodyforce_f32": (C.c_int, [vp, vp]),
     "ins_apply_bc_temp_pullback_f32": (C.c_int, [vp, C.POINTER(C.c_int32), vp, vp]),
     "ins_gravity_adjoint_f32": (C.c_int, [vp, C.c_int, C.c_float, vp, vp, vp]),
     "ins_convection_diffusion_temp_adjoint_f32": (C.c_int, [vp, C.c_float, vp, vp, vp, vp, vp, vp]),

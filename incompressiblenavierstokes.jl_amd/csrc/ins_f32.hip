@@ -31,12 +31,16 @@ int ins_k_flux64_f32(const ins_grid* G, double visc, const float* u, float* F, c
 // any other grid (walls, stretched spacings, 2-D or 3-D): csrc/ins_f32g.hip
 int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s);
 int ins_k32g_apply_bc_p(const ins_grid* G, float* p, hipStream_t s);
+int ins_k32g_apply_bc_p_fields(const ins_grid* G, float* p, int nf, hipStream_t s);
 int ins_k32g_momentum(const ins_grid* G, float visc, const float* u, float* F, hipStream_t s);
 int ins_k32g_divergence(const ins_grid* G, const float* u, float* div, hipStream_t s);
 int ins_k32g_solve(const ins_grid* G, ins_poisson* ps64, double* p64, float* p, hipStream_t s);
 int ins_k32g_project(const ins_grid* G, ins_poisson* ps64, double* p64, float* u, float* p, hipStream_t s);
 // the temperature equation (any grid): csrc/ins_temp32.hip
 int ins_k32t_diffusion(const ins_grid* G, float visc, const float* u, float* diff, hipStream_t s);
+// the Smagorinsky closure: csrc/ins_smagforce32.hip (one kernel), csrc/ins_smagforce.hip (the route predicate of both precisions)
+bool ins_smagforce_supported(const ins_grid* G);
+int ins_k_smagforce_f32(const ins_grid* G, float theta, const float* u, float* sout, hipStream_t s);
 int ins_k32t_stage(const ins_grid* G, float a4, float coef, const float* u, const float* temp, const float* diff, const float* tempstart, int n,
                    const float* coefs, const float* const* ks, float c_self, float* ktemp_out, float* temp_out, hipStream_t s);
 
@@ -76,11 +80,17 @@ struct ins_rk32 {
   float* ustart = nullptr;  // chained steps: the corrected start field of steps 2..K (the caller's array holds the uncorrected last stage velocity then)
   // temperature equation (ins_rk_set_temperature_f32, ins_rk_step_ext_f32): scalar scratch allocated by the first step that carries a temperature
   bool temp_on = false;
-  ins_temperature_desc_t td;
+  ins_temperature_desc_t td = {};
   float* tempstart = nullptr;
   float* tstage = nullptr;      // the one stage temperature buffer: stage temperatures alternate between it and the caller's array
   float* diff = nullptr;        // scratch of dissipation! (vector field)
   std::vector<float*> ktemp;    // nstage scalars
+  // Smagorinsky closure and steady body force (ins_rk_set_closure_f32, ins_rk_set_bodyforce_f32)
+  int closure = 0;              // 0 none, 1 Smagorinsky
+  float theta = 0.f;
+  const float* force = nullptr; // the caller's device field
+  float* E = nullptr;           // closure force (vector field; only its degrees of freedom are ever written)
+  float* sigma = nullptr;       // D(D+1)/2 scalar fields (three-kernel route)
 };
 
 namespace {
@@ -274,6 +284,11 @@ __global__ __launch_bounds__(256) void k32_combine(long long n, const float* __r
     for (int q = 0; q < cb.n; ++q) v += cb.coef[q] * cb.k[q][t];
     out[t] = v;
   }
+}
+
+// a += b (the closure force joins the stage force)                                     step_explicit_runge_kutta.jl:31-34
+__global__ __launch_bounds__(256) void k32_add(long long n, float* __restrict__ a, const float* __restrict__ b) {
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) a[t] += b[t];
 }
 
 __global__ __launch_bounds__(256) void k32_cvt(long long n, const double* __restrict__ a, float* __restrict__ b) {
@@ -534,7 +549,7 @@ extern "C" int ins_rk_destroy_f32(ins_rk32_t* rk) {
     if (b) (void)hipFree(b);
   if (rk->p) (void)hipFree(rk->p);
   if (rk->pu) (void)hipFree(rk->pu);
-  for (float* b : {rk->tempstart, rk->tstage, rk->diff})
+  for (float* b : {rk->tempstart, rk->tstage, rk->diff, rk->E, rk->sigma})
     if (b) (void)hipFree(b);
   for (float* k : rk->ktemp)
     if (k) (void)hipFree(k);
@@ -691,14 +706,33 @@ static int zalloc32(float** p, size_t bytes, hipStream_t s) {
   return INS_OK;
 }
 
-// timestep!(method, stepper, Δt; cache) with `temp`, T = Float32                                  step_explicit_runge_kutta.jl:4-59
-// Per stage: ku_i = momentum(u) + gravity(temp) (:21), the temperature stage (:23-27, 39-44: one kernel, or operator by operator with
-// INS_DISABLE_TEMP32_STAGE), the combination of u (:35-38), ghost fill, project!, ghost fill (:47-49) and the ghost fill of the new stage temperature, which
-// is also the one the next stage (:19-20) or the end of the step (:55-56) asks for.  General grids run on the kernels of ins_f32g.hip and a wrapped solver,
-// all-periodic uniform boxes (wide ones too) on ins_momentum_f32 / k32_combine / ins_project_f32; the temperature kernels are those of ins_temp32.hip on both.
+// kind 0: no closure; 1: smagorinsky_closure(setup) with constant θ (operators.jl:1294-1305)
+extern "C" int ins_rk_set_closure_f32(ins_rk32_t* rk, int32_t kind, float theta) {
+  INS_REQUIRE(kind == 0 || kind == 1, "closure kind: 0 (none) or 1 (Smagorinsky)");
+  INS_REQUIRE(rk, "null argument");
+  rk->closure = kind;
+  rk->theta = theta;
+  return INS_OK;
+}
+
+// steady body force (setup.jl:25-32; operators.jl:873-880): a device vector field the caller keeps alive; NULL removes it
+extern "C" int ins_rk_set_bodyforce_f32(ins_rk32_t* rk, const float* force) {
+  INS_REQUIRE(rk, "null argument");
+  rk->force = force;
+  return INS_OK;
+}
+
+// timestep!(method, stepper, Δt; cache) with any of `temp`, a Smagorinsky closure and a steady body force, T = Float32       step_explicit_runge_kutta.jl:4-59
+// Per stage: ku_i = momentum(u) + gravity(temp) + closure(u, θ) (:21, :31-34; operators.jl:873-880, 1294-1305) — the steady body force is not added to
+// ku_i but rides in the combination as one more term (ins_rk_sum_terms); the closure force is formed in E, a field zeroed at its allocation of which only
+// the degrees of freedom are ever written (one kernel where ins_smagforce_supported says so, else smagtensor! -> apply_bc_p! -> divoftensor!), and added
+// to ku_i.  Then the temperature stage (:23-27, 39-44: one kernel, or operator by operator with INS_DISABLE_TEMP32_STAGE), the combination of u (:35-38),
+// ghost fill, project!, ghost fill (:47-49) and the ghost fill of the new stage temperature, which is also the one the next stage (:19-20) or the end of
+// the step (:55-56) asks for.  General grids run on the kernels of ins_f32g.hip and a wrapped solver, all-periodic uniform boxes (wide ones too) on
+// ins_momentum_f32 / k32_combine / ins_project_f32; the temperature kernels are those of ins_temp32.hip on both.
 // The caller's u is ustart for the whole step.  Stage temperatures alternate between the caller's array and one buffer so that the last stage lands in the
 // caller's array; where that makes the first stage write it, that stage reads tempstart, a copy taken after the first ghost fill.
-static int rk32_step_temp(ins_rk32* rk, float visc, float* u, float* temp, float dt, hipStream_t s) {
+static int rk32_step_ext(ins_rk32* rk, float visc, float* u, float* temp, float dt, hipStream_t s) {
   const ins_grid* G = rk->grid;
   const GridDev& g = G->g;
   const int ns = rk->nstage, D = g.D;
@@ -706,6 +740,7 @@ static int rk32_step_temp(ins_rk32* rk, float visc, float* u, float* temp, float
   const size_t sbytes = (size_t)G->ncell * sizeof(float);
   const bool general = !periodic_uniform(G);
   const ins_temperature_desc_t& td = rk->td;
+  const bool closure = rk->closure == 1;
   int rc;
   for (int a = 0; a < D; ++a)
     if (g.bc[a][0] == INS_BC_HALO || g.bc[a][1] == INS_BC_HALO) {
@@ -716,61 +751,82 @@ static int rk32_step_temp(ins_rk32* rk, float visc, float* u, float* temp, float
     ins_set_error("ins_rk_step_ext_f32: this grid needs a solver made by ins_poisson_wrap_f32");
     return INS_ERR_UNSUPPORTED;
   }
-  if ((rc = zalloc32(&rk->tempstart, sbytes, s)) || (rc = zalloc32(&rk->tstage, sbytes, s))) return rc;
-  if (td.dodissipation && (rc = zalloc32(&rk->diff, sbytes * D, s))) return rc;
-  if ((int)rk->ktemp.size() < ns) rk->ktemp.resize(ns, nullptr);
-  for (int i = 0; i < ns; ++i)
-    if ((rc = zalloc32(&rk->ktemp[i], sbytes, s))) return rc;
+  if (temp) {
+    if ((rc = zalloc32(&rk->tempstart, sbytes, s)) || (rc = zalloc32(&rk->tstage, sbytes, s))) return rc;
+    if (td.dodissipation && (rc = zalloc32(&rk->diff, sbytes * D, s))) return rc;
+    if ((int)rk->ktemp.size() < ns) rk->ktemp.resize(ns, nullptr);
+    for (int i = 0; i < ns; ++i)
+      if ((rc = zalloc32(&rk->ktemp[i], sbytes, s))) return rc;
+  }
+  const bool smag1 = closure && ins_smagforce_supported(G);
+  if (closure && (rc = zalloc32(&rk->E, sbytes * D, s))) return rc;
+  if (closure && !smag1 && (rc = zalloc32(&rk->sigma, sbytes * (D * (D + 1) / 2), s))) return rc;
   float val[6];
-  for (int q = 0; q < 6; ++q) val[q] = (float)td.val[q];
+  for (int q = 0; q < 6; ++q) val[q] = temp ? (float)td.val[q] : 0.f;
   auto bc_u = [&](float* v) { return general ? ins_k32g_apply_bc_u(G, v, s) : bc_periodic(G, v, D, s); };
   auto bc_temp = [&](float* t) { return ins_apply_bc_temp_f32(G, td.bc, val, t, s); };
   const bool one_pass = !ins_opt(OPT_INS_DISABLE_TEMP32_STAGE);
   const float a4 = (float)td.a4, a2 = (float)td.a2, dcoef = (float)td.diss_coef;
 
   if ((rc = bc_u(u))) return rc;                                                                           // :19
-  if ((rc = bc_temp(temp))) return rc;                                                                     // :20
-  INS_HIP_TRY(hipMemcpyAsync(rk->tempstart, temp, sbytes, hipMemcpyDeviceToDevice, s));                    // state_copyto!(xstart, x)   :14
+  const float* tin = nullptr;
+  if (temp) {
+    if ((rc = bc_temp(temp))) return rc;                                                                   // :20
+    INS_HIP_TRY(hipMemcpyAsync(rk->tempstart, temp, sbytes, hipMemcpyDeviceToDevice, s));                  // state_copyto!(xstart, x)   :14
+    tin = (ns & 1) ? rk->tempstart : temp;
+  }
   const float* cur = u;
-  const float* tin = (ns & 1) ? rk->tempstart : temp;
   for (int i = 0; i < ns; ++i) {
     float* outp = (i == ns - 1 && ns > 1) ? u : rk->ub[i & 1];
-    float* tout = ((ns - 1 - i) & 1) ? rk->tstage : temp;
+    float* tout = temp ? (((ns - 1 - i) & 1) ? rk->tstage : temp) : nullptr;
     if ((rc = ins_momentum_f32(G, visc, cur, rk->ku[i], s))) return rc;                                    // :21
-    if ((rc = ins_gravity_f32(G, td.gdir, a2, tin, rk->ku[i], s))) return rc;
-    float tcoef[INS_MAX_STAGES];
-    const float* tk[INS_MAX_STAGES];
-    for (int j = 0; j <= i; ++j) {
-      tcoef[j] = dt * (float)rk->A[i * ns + j];
-      tk[j] = rk->ktemp[j];
-    }
-    if (one_pass) {                                                                                        // :23-27, 39-44
-      if (td.dodissipation && (rc = ins_k32t_diffusion(G, visc, cur, rk->diff, s))) return rc;
-      const bool later = ins_rk_needed_later(rk->A.data(), ns, i);
-      if ((rc = ins_k32t_stage(G, a4, dcoef, cur, tin, td.dodissipation ? rk->diff : nullptr, rk->tempstart, i, tcoef, tk, tcoef[i],
-                               later ? rk->ktemp[i] : nullptr, tout, s)))
-        return rc;
-    } else {
-      INS_HIP_TRY(hipMemsetAsync(rk->ktemp[i], 0, sbytes, s));
-      if ((rc = ins_convection_diffusion_temp_f32(G, a4, cur, tin, rk->ktemp[i], s))) return rc;
-      if (td.dodissipation && (rc = ins_dissipation_f32(G, visc, dcoef, cur, rk->diff, rk->ktemp[i], s))) return rc;
-      Comb32 cb;
-      cb.n = i + 1;
-      for (int j = 0; j <= i; ++j) {
-        cb.coef[j] = tcoef[j];
-        cb.k[j] = tk[j];
+    if (temp && (rc = ins_gravity_f32(G, td.gdir, a2, tin, rk->ku[i], s))) return rc;
+    if (closure) {                                                                                         // :31-34
+      if (smag1) {
+        if ((rc = ins_k_smagforce_f32(G, rk->theta, cur, rk->E, s))) return rc;
+      } else {
+        if ((rc = ins_smagtensor_f32(G, rk->theta, cur, rk->sigma, s))) return rc;
+        if ((rc = ins_k32g_apply_bc_p_fields(G, rk->sigma, D * (D + 1) / 2, s))) return rc;                // apply_bc_p!(σ, 0, setup)   operators.jl:1302
+        if ((rc = ins_divoftensor_f32(G, rk->sigma, rk->E, s))) return rc;
       }
-      hipLaunchKernelGGL(k32_combine, dim3((unsigned)std::min<long long>((G->ncell + 255) / 256, 8192)), dim3(256), 0, s, G->ncell, rk->tempstart, tout, cb);
+      hipLaunchKernelGGL(k32_add, dim3((unsigned)std::min<long long>((nvec + 255) / 256, 8192)), dim3(256), 0, s, nvec, rk->ku[i], (const float*)rk->E);
       INS_LAUNCH_CHECK();
     }
+    if (temp) {
+      float tcoef[INS_MAX_STAGES];
+      const float* tk[INS_MAX_STAGES];
+      for (int j = 0; j <= i; ++j) {
+        tcoef[j] = dt * (float)rk->A[i * ns + j];
+        tk[j] = rk->ktemp[j];
+      }
+      if (one_pass) {                                                                                      // :23-27, 39-44
+        if (td.dodissipation && (rc = ins_k32t_diffusion(G, visc, cur, rk->diff, s))) return rc;
+        const bool later = ins_rk_needed_later(rk->A.data(), ns, i);
+        if ((rc = ins_k32t_stage(G, a4, dcoef, cur, tin, td.dodissipation ? rk->diff : nullptr, rk->tempstart, i, tcoef, tk, tcoef[i],
+                                 later ? rk->ktemp[i] : nullptr, tout, s)))
+          return rc;
+      } else {
+        INS_HIP_TRY(hipMemsetAsync(rk->ktemp[i], 0, sbytes, s));
+        if ((rc = ins_convection_diffusion_temp_f32(G, a4, cur, tin, rk->ktemp[i], s))) return rc;
+        if (td.dodissipation && (rc = ins_dissipation_f32(G, visc, dcoef, cur, rk->diff, rk->ktemp[i], s))) return rc;
+        Comb32 cb;
+        cb.n = i + 1;
+        for (int j = 0; j <= i; ++j) {
+          cb.coef[j] = tcoef[j];
+          cb.k[j] = tk[j];
+        }
+        hipLaunchKernelGGL(k32_combine, dim3((unsigned)std::min<long long>((G->ncell + 255) / 256, 8192)), dim3(256), 0, s, G->ncell, rk->tempstart, tout, cb);
+        INS_LAUNCH_CHECK();
+      }
+    }
     Comb32 cb;
-    cb.n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), (const float*)nullptr, cb.coef, cb.k);
+    cb.n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, cb.coef, cb.k);                // the body force: one more term
     hipLaunchKernelGGL(k32_combine, dim3((unsigned)std::min<long long>((nvec + 255) / 256, 8192)), dim3(256), 0, s, nvec, u, outp, cb);  // :35-38
     INS_LAUNCH_CHECK();
     if (general && (rc = bc_u(outp))) return rc;                                                           // :47
     if ((rc = ins_project_f32(G, rk->ps, outp, rk->p, s))) return rc;                                      // :48-49 (periodic boxes: fills the ghosts itself)
     if (general && (rc = bc_u(outp))) return rc;
-    if ((rc = bc_temp(tout))) return rc;
+    if (temp && (rc = bc_temp(tout))) return rc;
     cur = outp;
     tin = tout;
   }
@@ -781,9 +837,9 @@ static int rk32_step_temp(ins_rk32* rk, float visc, float* u, float* temp, float
 extern "C" int ins_rk_steps_ext_f32(ins_rk32_t* rk, float visc, float* u, float* temp, float dt, int nsteps, void* stream) {
   INS_REQUIRE(rk && u && nsteps >= 0, "null or bad argument");
   INS_REQUIRE(rk->temp_on == (temp != nullptr), "a temperature field needs ins_rk_set_temperature_f32 and vice versa");
-  if (!temp) return ins_rk_steps_f32(rk, visc, u, dt, nsteps, stream);
+  if (!temp && !rk->closure && !rk->force) return ins_rk_steps_f32(rk, visc, u, dt, nsteps, stream);  // the plain loop: fused stages, chained steps
   for (int n = 0; n < nsteps; ++n) {
-    int rc = rk32_step_temp(rk, visc, u, temp, dt, as_stream(stream));
+    int rc = rk32_step_ext(rk, visc, u, temp, dt, as_stream(stream));
     if (rc) return rc;
   }
   return INS_OK;

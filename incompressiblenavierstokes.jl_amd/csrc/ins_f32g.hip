@@ -91,16 +91,18 @@ int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s) {
   return INS_OK;
 }
 
-int ins_k32g_apply_bc_p(const ins_grid* G, float* p, hipStream_t s) {
+// apply_bc_p! on nf scalar fields laid out back to back (field f at p + f·ncell), as ins_k_apply_bc_p_fields: one launch per direction for all of them
+int ins_k32g_apply_bc_p_fields(const ins_grid* G, float* p, int nf, hipStream_t s) {
   const GridDev& g = G->g;
   int rc = no_halo(G, "apply_bc_p (f32)");
   if (rc) return rc;
   for (int be = 0; be < g.D; ++be) {
     if (g.bc[be][0] == INS_BC_DIRICHLET && g.bc[be][1] == INS_BC_DIRICHLET) continue;  // no-op (boundary_conditions.jl:388)
-    INS_LAUNCH_D((k_bc_p<D, float>), line_launch(g, be, 1), s, g, p, be, 0LL);
+    INS_LAUNCH_D((k_bc_p<D, float>), line_launch(g, be, nf), s, g, p, be, nf > 1 ? G->ncell : 0LL);
   }
   return INS_OK;
 }
+int ins_k32g_apply_bc_p(const ins_grid* G, float* p, hipStream_t s) { return ins_k32g_apply_bc_p_fields(G, p, 1, s); }
 
 int ins_k32g_momentum(const ins_grid* G, float visc, const float* u, float* F, hipStream_t s) {
   const GridDev& g = G->g;

@@ -188,6 +188,10 @@ __host__ __device__ constexpr int sym_index(int a, int b) {  // [xx, yy, (zz), x
 
 // OP 0: dissipation_from_strain! (operators.jl:836-854, par = 1/Re)   OP 1: eig2field! (:1472-1492)
 // OP 2: smagtensor! (:1135-1150, par = θ; D(D+1)/2 outputs)
+// WARNING: the OP 2 branch below has a Float32 twin, k_smagtensor<D, T> in ins_tensorbasis.h (instantiated with float in ins_smagforce32.hip), spelled on
+// strain_rotation / mdot instead of gradu / strain_norm2: a fix to one goes into the other as well.  They are two copies because this function is shared by the
+// one-cell, LDS-ring and register-row kernels of three fp64 operators (OP 0, 1, 2; eig2_of is double only), whose float instantiations nobody needs; merging
+// was not attempted beyond that reading ("The rule for a kernel that serves both precisions").
 template <int D, int OP>
 __device__ __forceinline__ void gradient_result(const GridDev& g, const double (&G)[D][D], const int (&I)[3], long long c, double par,
                                                 double* __restrict__ out) {

@@ -329,6 +329,24 @@ __global__ __launch_bounds__(256) void k_tc_stress(GridDev g, const T* __restric
     for (int q = p; q < D; ++q) tau[(long long)sym_index<D>(p, q) * g.sc + c] = M.m[p][q];
 }
 
+// smagtensor! (operators.jl:1135-1150) on the pointwise gradient above: σ = 2 νt S with νt = θ² Δ² sqrt(2 S:S), Δ² = Σ Δα² (gridsize), written on Ip
+// as D(D+1)/2 fields.  The expressions of gradient_result<D, 2> in ins_fields.hip, whose register-row and LDS-ring kernels serve fp64 only.
+// WARNING: a copy, not an instantiation, of that fp64 code: a fix to one goes into the other as well (ins_fields.hip says why).
+template <int D, typename T>
+__global__ __launch_bounds__(256) void k_smagtensor(GridDev g, T theta, const T* __restrict__ u, T* __restrict__ sig) {
+  INS_VOL_INDEX(g.sx, g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], !in_ip<D>(g, i, j, k));
+  Mat<D, T> S, R;
+  strain_rotation<D, T>(g, u, c, I, S, R);
+  T d2 = T(0);
+#pragma unroll
+  for (int a = 0; a < D; ++a) d2 += (T)g.dx[a][I[a]] * (T)g.dx[a][I[a]];
+  const T eddy = theta * theta * d2 * sqrt(2 * mdot<D, T>(S, S));
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+#pragma unroll
+    for (int b = a; b < D; ++b) sig[(long long)sym_index<D>(a, b) * g.sc + c] = 2 * eddy * S.m[a][b];
+}
+
 // --------------------------------------------------------------------------------------------
 // pass 1 of the pullbacks: ∇ubar at every pressure point
 // --------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """Host mirror of the `_f32` entry-point family (include/ins_hip.h; csrc/ins_f32.hip, csrc/ins_f32g.hip): the reference with `T = Float32`
 (docs/src/manual/precision.md:3-16, examples/DecayingTurbulence3D.jl:16): all-periodic uniform boxes on the spectral solver, every other grid
 (walls, symmetric / pressure sides, stretched spacings; constant boundary data) on `psolver_wrap32` around an fp64 solver.  The temperature equation
-(csrc/ins_temp32.hip; examples/RayleighBenard3D.jl:16) rides on both: its operators, and `timestep32_` / `timesteps32_` with `temp=`.
+(csrc/ins_temp32.hip; examples/RayleighBenard3D.jl:16) rides on both: its operators, and `timestep32_` / `timesteps32_` with `temp=`.  So do the
+Smagorinsky closure (csrc/ins_smagforce32.hip: `smagorinsky_closure32`, `θ=` of the step functions) and a steady `setup.bodyforce`.
 
 Fields are torch.float32 tensors in the reference layout; `setup` is the ordinary (fp64-metric) Setup."""
 import ctypes as C
@@ -334,6 +335,40 @@ def divoftensor_adjoint32_(σbar, sbar, setup):
     return σbar
 
 
+# ---- Smagorinsky closure (csrc/ins_smagforce32.hip): the Float32 twins of operators.smagtensor_ and operators.smagorinsky_closure
+def smagtensor32_(σ, u, θ, setup):
+    """operators.jl:1135-1150 with T = Float32: writes the `tensorfield32` σ on Ip."""
+    _lib.call("ins_smagtensor_f32", setup.handle, float(θ), _ptr(setup, u, setup.grid.dimension), _ptr(setup, σ, _tb_sizes(setup)[2]), setup.stream)
+    return σ
+
+
+def smagorinsky_force32_(s, u, θ, setup, σ=None):
+    """s = divoftensor(apply_bc_p(smagtensor(u, θ))) on the degrees of freedom (operators.jl:1284-1300) with T = Float32: one kernel where the
+    grid allows it, else the three kernels with the `tensorfield32` σ as scratch (required there: `ins_smagorinsky_force_needs_sigma`)."""
+    D = setup.grid.dimension
+    _lib.call("ins_smagorinsky_force_f32", setup.handle, float(θ), _ptr(setup, u, D), _ptr_or_null(setup, σ, _tb_sizes(setup)[2]), _ptr(setup, s, D),
+              setup.stream)
+    return s
+
+
+def smagorinsky_closure32(setup):
+    """Create the Smagorinsky closure model `m(u, θ)` on float32 padded fields (operators.jl:1284-1300), marked like `smagorinsky_closure` so that
+    `timestep32_` / `timesteps32_` run it inside the native stage loop (ins_rk_set_closure_f32)."""
+    s = vectorfield32(setup)
+    scratch = {}
+
+    def closure(u, θ):
+        σ = None
+        if _lib.load().ins_smagorinsky_force_needs_sigma(setup.handle):  # answers for both precisions; asked per call: an option may switch the route
+            if "σ" not in scratch:
+                scratch["σ"] = tensorfield32(setup)
+            σ = scratch["σ"]
+        return smagorinsky_force32_(s, u, θ, setup, σ)
+
+    closure._ins_closure, closure._ins_setup = "smagorinsky", setup
+    return closure
+
+
 def max_abs_divergence32(u, setup, psolver):
     out = C.c_float()
     _lib.call("ins_max_abs_divergence_f32", setup.handle, psolver.handle, _ptr(setup, u, setup.grid.dimension), C.byref(out), setup.stream)
@@ -373,25 +408,58 @@ def _set_temperature32(cache, temp):
     return _ptr(s, temp, 0)
 
 
-def timestep32_(cache, u, Δt, temp=None):
-    """One explicit RK step of the float32 field `u` in place (step_explicit_runge_kutta.jl:4-59); with `temp` (a float32 scalar field; the setup has a
-    temperature equation) the temperature is advanced with it and (u, temp) is returned."""
+def _set_force_closure32(cache, θ):
+    """Hand the steady body force and the Smagorinsky closure of the cache's setup to its native handle; True if the extended loop is needed.
+    What the Float32 stage loop does not run is refused: it would otherwise be dropped from the step without a word."""
     s = cache.setup
-    if temp is None:
+    if s.bodyforce is not None and not s.issteadybodyforce:
+        raise NotImplementedError("the _f32 family takes a steady body force (an unsteady one: the fp64 entry points, timestep_ / solve_unsteady)")
+    f = s.bodyforce
+    if getattr(cache, "_force_src", None) is not f:  # cast once per cache; the float32 field is kept alive here
+        cache._force32 = to_f32(s, f) if f is not None else None
+        _lib.call("ins_rk_set_bodyforce_f32", cache._handle, _ptr(s, cache._force32, s.grid.dimension) if f is not None else None)
+        cache._force_src = f
+    m = s.closure_model
+    if m is None:
+        kind, θ = 0, 0.0  # (a θ without a closure model has nothing to act on, as in timestep_)
+    else:
+        if getattr(m, "_ins_closure", None) != "smagorinsky" or getattr(m, "_ins_setup", None) is not s:
+            raise NotImplementedError("the _f32 stage loop runs the library's Smagorinsky closure of this setup (smagorinsky_closure / "
+                                      "smagorinsky_closure32); another closure_model: the fp64 entry points, or ad32.timestep with a torch closure")
+        if θ is None:
+            raise NotImplementedError("the setup has a closure_model: give its parameter as θ= (a scalar); without one the closure would be dropped "
+                                      "(fp64 entry points: timestep_(..., θ=θ))")
+        if not np.isscalar(θ):
+            raise NotImplementedError("the _f32 stage loop takes a scalar θ (a tensor θ: ad32.timestep with ad32.smagorinsky_closure)")
+        kind, θ = 1, float(θ)
+    if getattr(cache, "_closure", (0, 0.0)) != (kind, θ):
+        _lib.call("ins_rk_set_closure_f32", cache._handle, kind, θ)
+        cache._closure = (kind, θ)
+    return f is not None or kind != 0
+
+
+def timestep32_(cache, u, Δt, temp=None, θ=None):
+    """One explicit RK step of the float32 field `u` in place (step_explicit_runge_kutta.jl:4-59); with `temp` (a float32 scalar field; the setup has a
+    temperature equation) the temperature is advanced with it and (u, temp) is returned.  A steady `setup.bodyforce` and the library's Smagorinsky
+    `setup.closure_model` with the scalar parameter `θ` join every stage force (operators.jl:873-880, 1294-1305)."""
+    s = cache.setup
+    ext = _set_force_closure32(cache, θ)
+    if temp is None and not ext:
         _lib.call("ins_rk_step_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), float(Δt), s.stream)
         return u
-    tp = _set_temperature32(cache, temp)
+    tp = _set_temperature32(cache, temp) if temp is not None else None
     _lib.call("ins_rk_step_ext_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), tp, float(Δt), s.stream)
-    return u, temp
+    return u if temp is None else (u, temp)
 
 
-def timesteps32_(cache, u, Δt, nsteps, temp=None):
+def timesteps32_(cache, u, Δt, nsteps, temp=None, θ=None):
     """`nsteps` explicit RK steps of size Δt of the float32 field `u` in place: the fixed-Δt loop of solve_unsteady (solver.jl:74-83) as one native call;
-    with `temp` as `timestep32_`."""
+    with `temp` and `θ` as `timestep32_`."""
     s = cache.setup
-    if temp is None:
+    ext = _set_force_closure32(cache, θ)
+    if temp is None and not ext:
         _lib.call("ins_rk_steps_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), float(Δt), int(nsteps), s.stream)
         return u
-    tp = _set_temperature32(cache, temp)
+    tp = _set_temperature32(cache, temp) if temp is not None else None
     _lib.call("ins_rk_steps_ext_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), tp, float(Δt), int(nsteps), s.stream)
-    return u, temp
+    return u if temp is None else (u, temp)
