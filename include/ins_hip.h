@@ -671,6 +671,27 @@ int ins_dissipation_adjoint_f32(const ins_grid_t* grid, float visc, float coef, 
 int ins_temperature_pullback_f32(const ins_grid_t* grid, const ins_temperature_desc_t* desc, float visc, const float* u, const float* temp,
                                  const float* Fbar, const float* cbar, float* ubar, float* tempbar, void* stream);
 
+/* ---------------------------------------------------------------------------------- Float32 driver: CFL time step, observers, spectrum
+ * (csrc/ins_fields32.hip, csrc/ins_spectrum.hip)  What solve_unsteady (solver.jl:18-92) and the processors (processors.jl:78-197, 303-332) need of a
+ * float state.  The `_f32` twins of their fp64 namesakes: the same layouts and write sets on float fields, the fp64 grid handle, metric tables
+ * rounded to float where they enter, all arithmetic in float.  Slab (halo) grids: INS_ERR_UNSUPPORTED. */
+/* get_cfl_timestep!(buf, u, setup)         solver.jl:101-125.  Blocking.  One pass over u (every component in one launch; Δu[α] / |u_α| is formed
+ * on Iu[α] only, ghost volumes and faces outside Iu[α] are not read) and a one-workgroup finish on the grid's reduction scratch: no allocation.
+ * The diffusive bound Re·min(Δu)²/2 is formed on the host in double; the result is rounded to float once. */
+int ins_cfl_timestep_f32(const ins_grid_t* grid, float Re, const float* u, float* out, void* stream);
+/* vorticity!(ω, u, setup)                  operators.jl:985-1020  (2-D: scalar ω; 3-D: vector ω; written on 0 .. N-2) */
+int ins_vorticity_f32(const ins_grid_t* grid, const float* u, float* w, void* stream);
+/* interpolate_u_p!(up, u, setup)           operators.jl:1311-1326 (writes Ip) */
+int ins_interpolate_u_p_f32(const ins_grid_t* grid, const float* u, float* up, void* stream);
+/* interpolate_ω_p!(ωp, ω, setup)           operators.jl:1336-1370 (writes Ip) */
+int ins_interpolate_w_p_f32(const ins_grid_t* grid, const float* w, float* wp, void* stream);
+/* Qfield!(Q, u, setup)                     operators.jl:1440-1460 */
+int ins_qfield_f32(const ins_grid_t* grid, const float* u, float* Q, void* stream);
+/* observespectrum(state; setup, npoint, a)   processors.jl:303-332 of a float field, on the handle ins_spectrum_f64 takes.  Only the ghost strip
+ * reads floats: it widens every value exactly to double, the transform and the shell sums are the fp64 ones, so ehat (DEVICE, double) is bit for
+ * bit ins_spectrum_f64 of the widened field, and no fp64 copy of the field is made. */
+int ins_spectrum_f32(ins_spectrum_t* spectrum, const float* u, double* ehat, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

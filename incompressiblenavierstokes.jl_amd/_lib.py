@@ -205,6 +205,12 @@ SIGNATURES = {
     "ins_convection_diffusion_temp_adjoint_f32": (C.c_int, [vp, C.c_float, vp, vp, vp, vp, vp, vp]),
     "ins_dissipation_adjoint_f32": (C.c_int, [vp, C.c_float, C.c_float, vp, vp, vp, vp]),
     "ins_temperature_pullback_f32": (C.c_int, [vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp]),
+    "ins_cfl_timestep_f32": (C.c_int, [vp, C.c_float, vp, C.POINTER(C.c_float), vp]),
+    "ins_vorticity_f32": (C.c_int, [vp, vp, vp, vp]),
+    "ins_interpolate_u_p_f32": (C.c_int, [vp, vp, vp, vp]),
+    "ins_interpolate_w_p_f32": (C.c_int, [vp, vp, vp, vp]),
+    "ins_qfield_f32": (C.c_int, [vp, vp, vp, vp]),
+    "ins_spectrum_f32": (C.c_int, [vp, vp, vp, vp]),
     "ins_comm_unique_id": (C.c_int, [vp]),
     "ins_comm_create": (C.c_int, [C.c_int, C.c_int, vp, C.POINTER(vp)]),
     "ins_comm_create_local": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]),

@@ -5,57 +5,11 @@
 // reference's divisions (<= 1 ulp per term, inside the 1e-12 parity tolerance).
 // k_gravity, k_dissipation_interp, k_bc_temp and avg_at are the double instantiations of ins_temp_kernels.h (shared with ins_temp32.hip);
 // k_convdiff_temp and k_temp_stage are written here and have float copies in ins_temp32.hip: a fix to one goes into the other as well.
+// k_vorticity, k_interp_u_p, k_interp_w_p and k_Qfield are the double instantiations of ins_fields_kernels.h (shared with ins_fields32.hip).
 #include "ins_temp_kernels.h"
+#include "ins_fields_kernels.h"
 
 namespace {
-
-// --------------------------------------------------------------------------------------------
-// vorticity!                                             operators.jl:985-1020 (ndrange = N .- 1)
-// --------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_vorticity(GridDev g, BoxMap L, const double* __restrict__ u, double* __restrict__ w) {
-  INS_BANDED_INDEX(0, 0, 0, g.N[0] - 1, g.N[1] - 1);
-  if (D == 2) {
-    const double* u0 = u;
-    const double* u1 = u + g.sc;
-    w[c] = (u1[c + g.sx[0]] - u1[c]) * g.rdxu[0][i] - (u0[c + g.sx[1]] - u0[c]) * g.rdxu[1][j];
-  } else {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const int ap = (a + 1) % 3, am = (a + 2) % 3;
-      const double* up = u + ap * g.sc;
-      const double* um = u + am * g.sc;
-      w[a * g.sc + c] = (um[c + g.sx[ap]] - um[c]) * g.rdxu[ap][I[ap]] - (up[c + g.sx[am]] - up[c]) * g.rdxu[am][I[am]];
-    }
-  }
-}
-
-// interpolate_u_p!                                                     operators.jl:1311-1326
-template <int D>
-__global__ __launch_bounds__(256) void k_interp_u_p(GridDev g, BoxMap L, const double* __restrict__ u, double* __restrict__ up) {
-  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    const double* ua = u + a * g.sc;
-    up[a * g.sc + c] = (ua[c - g.sx[a]] + ua[c]) / 2;
-  }
-}
-
-// interpolate_ω_p!                                                     operators.jl:1336-1370
-template <int D>
-__global__ __launch_bounds__(256) void k_interp_w_p(GridDev g, BoxMap L, const double* __restrict__ w, double* __restrict__ wp) {
-  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
-  if (D == 2) {
-    wp[c] = (w[c - g.sx[0] - g.sx[1]] + w[c]) / 2;
-  } else {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const int ap = (a + 1) % 3, am = (a + 2) % 3;
-      const double* wa = w + a * g.sc;
-      wp[a * g.sc + c] = (wa[c - g.sx[ap] - g.sx[am]] + wa[c]) / 2;
-    }
-  }
-}
 
 // Dfield! (after pressuregradient!)                                    operators.jl:1385-1422
 template <int D>
@@ -71,23 +25,6 @@ __global__ __launch_bounds__(256) void k_Dfield(GridDev g, BoxMap L, const doubl
   }
   lap = lap > 0 ? fmax(lap, eps) : fmin(lap, -eps);
   d[c] = sqrt(gg) / 2 / lap;
-}
-
-// Qfield!                                                              operators.jl:1440-1460
-template <int D>
-__global__ __launch_bounds__(256) void k_Qfield(GridDev g, BoxMap L, const double* __restrict__ u, double* __restrict__ Q) {
-  INS_BANDED_INDEX(g.ip_lo[0], g.ip_lo[1], g.ip_lo[2], g.ip_hi[0], g.ip_hi[1]);
-  double q = 0.0;
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    const double* ua = u + a * g.sc;
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      const double* ub = u + b * g.sc;
-      q -= (ua[c] - ua[c - g.sx[b]]) * g.rdx[b][I[b]] * (ub[c] - ub[c - g.sx[a]]) * g.rdx[a][I[a]] / 2;
-    }
-  }
-  Q[c] = q;
 }
 
 // ∇(u, I, Δ, Δu): velocity gradient at the pressure point I                operators.jl:1023-1034, 1069-1085
@@ -829,7 +766,7 @@ extern "C" int ins_vorticity_f64(const ins_grid_t* G, const double* u, double* w
   const GridDev& g = G->g;
   const int hi[3] = {g.N[0] - 1, g.N[1] - 1, g.N[2] - 1};
   Launch3 l = banded_launch(g.D, hi);
-  INS_LAUNCH_D((k_vorticity<D>), l, as_stream(stream), g, l.map, u, w);
+  INS_LAUNCH_D((k_vorticity<D, double>), l, as_stream(stream), g, l.map, u, w);
   return INS_OK;
 }
 
@@ -837,7 +774,7 @@ extern "C" int ins_interpolate_u_p_f64(const ins_grid_t* G, const double* u, dou
   INS_REQUIRE(G && u && up, "null argument");
   const GridDev& g = G->g;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D((k_interp_u_p<D>), l, as_stream(stream), g, l.map, u, up);
+  INS_LAUNCH_D((k_interp_u_p<D, double>), l, as_stream(stream), g, l.map, u, up);
   return INS_OK;
 }
 
@@ -845,7 +782,7 @@ extern "C" int ins_interpolate_w_p_f64(const ins_grid_t* G, const double* w, dou
   INS_REQUIRE(G && w && wp, "null argument");
   const GridDev& g = G->g;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D((k_interp_w_p<D>), l, as_stream(stream), g, l.map, w, wp);
+  INS_LAUNCH_D((k_interp_w_p<D, double>), l, as_stream(stream), g, l.map, w, wp);
   return INS_OK;
 }
 
@@ -863,7 +800,7 @@ extern "C" int ins_qfield_f64(const ins_grid_t* G, const double* u, double* Q, v
   INS_REQUIRE(G && u && Q, "null argument");
   const GridDev& g = G->g;
   Launch3 l = ip_launch(g);
-  INS_LAUNCH_D((k_Qfield<D>), l, as_stream(stream), g, l.map, u, Q);
+  INS_LAUNCH_D((k_Qfield<D, double>), l, as_stream(stream), g, l.map, u, Q);
   return INS_OK;
 }
 

@@ -35,14 +35,15 @@ struct ins_spectrum {
 
 namespace {
 
-template <int D>
-__global__ __launch_bounds__(256) void k_strip(GridDev g, const double* __restrict__ f, double* __restrict__ out, int n0, int n1) {
+// T = float (ins_spectrum_f32): every value widens exactly to double, so what follows is the fp64 spectrum of the widened field
+template <int D, typename T>
+__global__ __launch_bounds__(256) void k_strip(GridDev g, const T* __restrict__ f, double* __restrict__ out, int n0, int n1) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   const int j = blockIdx.y * 4 + threadIdx.y;
   const int k = D == 3 ? (int)blockIdx.z : 0;
   if (i >= n0 || j >= n1) return;
   const long long c = (g.ip_lo[0] + i) + (g.ip_lo[1] + j) * g.sx[1] + (D == 3 ? (g.ip_lo[2] + k) * g.sx[2] : 0);
-  out[i + (long long)n0 * (j + (long long)n1 * k)] = f[c];
+  out[i + (long long)n0 * (j + (long long)n1 * k)] = (double)f[c];
 }
 
 // one workgroup per chunk of the index list (a chunk lies inside one shell)
@@ -187,22 +188,25 @@ extern "C" int ins_spectrum_create_weighted(const ins_grid_t* G, int nbin, const
   return INS_OK;
 }
 
-extern "C" int ins_spectrum_f64(ins_spectrum_t* S, const double* u, double* ehat, void* stream) {
-  INS_REQUIRE(S && u && ehat, "null argument");
+// T = double: the own passes strip the ghosts inside their x pass.  T = float: k_strip<D, float> gathers and widens into S->real on every route, and
+// the own x pass reads those rows (XSRC_PI) — the same values through the same transform, so the result is bit for bit that of the widened field.
+template <typename T>
+static int spectrum_run(ins_spectrum_t* S, const T* u, double* ehat, hipStream_t s) {
+  constexpr bool F32 = sizeof(T) == sizeof(float);
   const GridDev& g = S->grid->g;
-  hipStream_t s = as_stream(stream);
   if (!S->own) INS_FFT_TRY(hipfftSetStream(S->plan, s));
   INS_HIP_TRY(hipMemsetAsync(ehat, 0, S->nbin * sizeof(double), s));
   dim3 block(64, 4, 1), grid(cdiv(S->np[0], 64), cdiv(S->np[1], 4), (unsigned)S->np[2]);
   for (int a = 0; a < g.D; ++a) {
-    if (!S->own) {
-      INS_LAUNCH_D((k_strip<D>), (Launch3{grid, block}), s, g, u + a * g.sc, S->real, S->np[0], S->np[1]);
+    if (!S->own || F32) {
+      INS_LAUNCH_D((k_strip<D, T>), (Launch3{grid, block}), s, g, u + a * g.sc, S->real, S->np[0], S->np[1]);
     }
     if (S->own) {
       double* ph = reinterpret_cast<double*>(S->hat);
       const int kxn = S->np[0] / 2 + 1;
+      const double* src = F32 ? S->real : reinterpret_cast<const double*>(u + a * g.sc);  // T = double: ghosts stripped inside the x pass
       int rc;
-      if ((rc = ins_k_ownfft_xfwd(S->grid, u + a * g.sc, XSRC_FIELD, ph, S->np[0], S->np[1], S->np[2], S->tw[0], s, S->kxs))) return rc;  // ghosts stripped inside the x pass
+      if ((rc = ins_k_ownfft_xfwd(S->grid, src, F32 ? XSRC_PI : XSRC_FIELD, ph, S->np[0], S->np[1], S->np[2], S->tw[0], s, S->kxs))) return rc;
       if ((rc = ins_k_line3_y(ph, kxn, S->np[1], S->np[2], S->tw[1], false, s, S->kxs))) return rc;
       if ((rc = ins_k_line3_z(ph, kxn, S->np[1], S->np[2], S->tw[2], s, S->kxs))) return rc;
     } else {
@@ -213,4 +217,16 @@ extern "C" int ins_spectrum_f64(ins_spectrum_t* S, const double* u, double* ehat
     INS_LAUNCH_CHECK();
   }
   return INS_OK;
+}
+
+extern "C" int ins_spectrum_f64(ins_spectrum_t* S, const double* u, double* ehat, void* stream) {
+  INS_REQUIRE(S && u && ehat, "null argument");
+  return spectrum_run<double>(S, u, ehat, as_stream(stream));
+}
+
+extern "C" int ins_spectrum_f32(ins_spectrum_t* S, const float* u, double* ehat, void* stream) {
+  INS_REQUIRE(S && u && ehat, "null argument");
+  int rc = no_halo(S->grid, "spectrum (f32)");
+  if (rc) return rc;
+  return spectrum_run<float>(S, u, ehat, as_stream(stream));
 }

@@ -3,6 +3,8 @@
 (walls, symmetric / pressure sides, stretched spacings; constant boundary data) on `psolver_wrap32` around an fp64 solver.  The temperature equation
 (csrc/ins_temp32.hip; examples/RayleighBenard3D.jl:16) rides on both: its operators, and `timestep32_` / `timesteps32_` with `temp=`.  So do the
 Smagorinsky closure (csrc/ins_smagforce32.hip: `smagorinsky_closure32`, `θ=` of the step functions) and a steady `setup.bodyforce`.
+`solve_unsteady` with a float32 `ustart` drives all of it (solver.py), with `get_cfl_timestep32_` for the adaptive Δt and the float observers
+(csrc/ins_fields32.hip) behind the processors.
 
 Fields are torch.float32 tensors in the reference layout; `setup` is the ordinary (fp64-metric) Setup."""
 import ctypes as C
@@ -373,6 +375,45 @@ def max_abs_divergence32(u, setup, psolver):
     out = C.c_float()
     _lib.call("ins_max_abs_divergence_f32", setup.handle, psolver.handle, _ptr(setup, u, setup.grid.dimension), C.byref(out), setup.stream)
     return float(out.value)
+
+
+# ---- what solve_unsteady and the processors need of a float32 state (csrc/ins_fields32.hip): the Float32 twins of solver.get_cfl_timestep_ and of
+# operators.vorticity_, interpolate_u_p_, interpolate_ω_p_, Qfield_
+def get_cfl_timestep32_(u, setup):
+    """Proposed maximum time step for the convection and diffusion terms (solver.jl:101-125) of the float32 field `u`: one pass over `u`, the
+    convective quotients Δu / |u| in float, the diffusive bound in double on the host.  Blocking; returns a Python float."""
+    out = C.c_float()
+    _lib.call("ins_cfl_timestep_f32", setup.handle, float(setup.Re), _ptr(setup, u, setup.grid.dimension), C.byref(out), setup.stream)
+    return float(out.value)
+
+
+def _ncomp_ω(setup):
+    return 0 if setup.grid.dimension == 2 else 3
+
+
+def vorticity32_(ω, u, setup):
+    """operators.jl:985-1020 with T = Float32 (2-D: a scalar field; 3-D: a vector field); `u` ghost-filled."""
+    _lib.call("ins_vorticity_f32", setup.handle, _ptr(setup, u, setup.grid.dimension), _ptr(setup, ω, _ncomp_ω(setup)), setup.stream)
+    return ω
+
+
+def interpolate_u_p32_(up, u, setup):
+    """operators.jl:1311-1326 with T = Float32 (writes Ip)"""
+    D = setup.grid.dimension
+    _lib.call("ins_interpolate_u_p_f32", setup.handle, _ptr(setup, u, D), _ptr(setup, up, D), setup.stream)
+    return up
+
+
+def interpolate_ω_p32_(ωp, ω, setup):
+    """operators.jl:1336-1370 with T = Float32 (writes Ip)"""
+    _lib.call("ins_interpolate_w_p_f32", setup.handle, _ptr(setup, ω, _ncomp_ω(setup)), _ptr(setup, ωp, _ncomp_ω(setup)), setup.stream)
+    return ωp
+
+
+def Qfield32_(Q, u, setup):
+    """operators.jl:1440-1460 with T = Float32 (writes Ip)"""
+    _lib.call("ins_qfield_f32", setup.handle, _ptr(setup, u, setup.grid.dimension), _ptr(setup, Q, 0), setup.stream)
+    return Q
 
 
 class ERKCache32:

@@ -121,9 +121,12 @@ def fieldsaver(*, setup, nupdate=1):
 def observefield(state, *, setup, fieldname, logtol=np.finfo(np.float64).eps, psolver=None):
     """Observe field `fieldname` at pressure points (processors.jl:78-197): an Observable of a host array over Ip, recomputed on the
     device whenever `state` changes.  fieldname: 0/1/2 (velocity component), "velocity", "velocitynorm", "vorticity", "pressure",
-    "Dfield", "Qfield", "eig2field", "temperature", "B1".."B11" (tensor-valued), "V1".."V5"."""
+    "Dfield", "Qfield", "eig2field", "temperature", "B1".."B11" (tensor-valued), "V1".."V5".
+    A float32 state is observed by the float kernels (`_observefield32`): host arrays are float32."""
     if not isinstance(state, Observable):
         state = Observable(state)
+    if _is_f32(state.value["u"]):
+        return _observefield32(state, setup=setup, fieldname=fieldname, logtol=logtol)
     g = setup.grid
     D = g.dimension
     sl = tuple(slice(lo, hi) for lo, hi in g.Ip)
@@ -176,6 +179,53 @@ def observefield(state, *, setup, fieldname, logtol=np.finfo(np.float64).eps, ps
     return state.map(observe)
 
 
+def _is_f32(f):
+    return isinstance(f, torch.Tensor) and f.dtype == torch.float32
+
+
+def _observefield32(state, *, setup, fieldname, logtol):
+    """observefield on a float32 state (processors.jl:78-197 with T = Float32): velocity components, "velocity", "velocitynorm", "vorticity", "Qfield"
+    and "temperature" on the float kernels of f32.py with float32 scratch.  The observers that need a pressure solve or the fp64-only gradient
+    kernels are refused, not cast."""
+    from . import f32
+
+    if fieldname in ("pressure", "Dfield", "eig2field") or (isinstance(fieldname, str) and fieldname[:1] in "BV" and fieldname[1:].isdigit()):
+        raise NotImplementedError(f"observefield {fieldname!r} on a float32 state: this observer runs in fp64 only — observe u.double() "
+                                  "(a state dict with u=state['u'].double())")
+    if fieldname not in (0, 1, 2, "velocity", "velocitynorm", "vorticity", "Qfield", "temperature"):
+        raise ValueError(f"Unknown fieldname {fieldname!r}")
+    g = setup.grid
+    D = g.dimension
+    sl = tuple(slice(lo, hi) for lo, hi in g.Ip)
+    if fieldname == "vorticity":
+        ω = f32.scalarfield32(setup) if D == 2 else f32.vectorfield32(setup)
+        ωp = f32.scalarfield32(setup) if D == 2 else f32.vectorfield32(setup)
+    elif fieldname == "Qfield":
+        Q = f32.scalarfield32(setup)
+    elif fieldname != "temperature":
+        up = f32.vectorfield32(setup)
+
+    def observe(s):
+        u, temp = s["u"], s["temp"]
+        if fieldname == "vorticity":
+            f32.apply_bc_u32_(u, setup)
+            f = f32.interpolate_ω_p32_(ωp, f32.vorticity32_(ω, u, setup), setup)
+        elif fieldname == "Qfield":
+            f = f32.Qfield32_(Q, u, setup).clone()
+            f[sl] = torch.log(torch.clamp(f[sl], min=logtol))
+        elif fieldname == "temperature":
+            f = temp
+        elif fieldname == "velocity":
+            f = f32.interpolate_u_p32_(up, u, setup)
+        elif fieldname == "velocitynorm":
+            f = torch.sqrt((f32.interpolate_u_p32_(up, u, setup) ** 2).sum(-1))
+        else:
+            f = f32.interpolate_u_p32_(up, u, setup)[..., fieldname]
+        return to_numpy(f[sl])
+
+    return state.map(observe)
+
+
 def spectral_stuff(setup, *, npoint=100, a=(1 + math.sqrt(5)) / 2):
     """Wavenumber shells of the energy spectrum (utils.jl:49-108): `inds[i]` = 0-based column-major positions in the K = Np .÷ 2 array."""
     g = setup.grid
@@ -212,6 +262,12 @@ class _Spectrum:
         self.ehat = torch.zeros(self.nbin, dtype=torch.float64, device=setup.device)
 
     def __call__(self, u):
+        if _is_f32(u):  # the ghost strip widens the float values: the fp64 spectrum of u.double(), without that copy
+            from . import f32
+
+            _lib.call("ins_spectrum_f32", self._handle, f32._ptr(self.setup, u, self.setup.grid.dimension), C.c_void_p(self.ehat.data_ptr()),
+                      self.setup.stream)
+            return self.ehat
         _lib.call("ins_spectrum_f64", self._handle, self.setup.ptr(u, True), C.c_void_p(self.ehat.data_ptr()), self.setup.stream)
         return self.ehat
 
@@ -239,6 +295,8 @@ def get_scale_numbers(u, setup):
     from .boundary_conditions import PeriodicBC
     from .operators import dissipation_from_strain
 
+    if _is_f32(u):
+        raise TypeError("get_scale_numbers takes a float64 field (a float32 state: get_scale_numbers(u.double(), setup))")
     if not all(isinstance(bc, PeriodicBC) for side in setup.boundary_conditions for bc in side):
         raise ValueError("Scale numbers: the integral length scale needs a uniform periodic grid")  # assert_uniform_periodic, utils.jl:1-13
     g = setup.grid

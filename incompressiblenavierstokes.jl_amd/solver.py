@@ -3,10 +3,12 @@ import ctypes as C
 import math
 import os
 
+import torch
+
 from . import _lib
 from .pressure import default_psolver
 from .setup import copyfield
-from .time_steppers import RKMethods, create_stepper, ode_method_cache, timestep_, timesteps_
+from .time_steppers import LMWray3, RKMethods, create_stepper, ode_method_cache, timestep_, timesteps_
 
 
 def get_state(stepper):
@@ -22,12 +24,98 @@ def get_cfl_timestep_(buf, u, setup):
     return out.value
 
 
+def _is_float32_run(ustart, tempstart, psolver, cache):
+    """True if `ustart` selects the Float32 family.  A solver, cache or temperature of the other precision is refused (TypeError), never cast."""
+    from . import f32
+
+    is32 = getattr(ustart, "dtype", None) == torch.float32
+    mine, other = ("float32", "float64") if is32 else ("float64", "float32")
+    if tempstart is not None and (getattr(tempstart, "dtype", None) == torch.float32) != is32:
+        raise TypeError(f"solve_unsteady: a {mine} ustart with a {other} tempstart: give both fields in one precision")
+    if psolver is not None and isinstance(psolver, f32.psolver_spectral32) != is32:
+        raise TypeError(f"solve_unsteady: a {mine} ustart with a {other} psolver (float32 fields: f32.default_psolver32 / f32.psolver_wrap32; "
+                        "float64 fields: default_psolver and its kin)")
+    if cache is not None and isinstance(cache, f32.ERKCache32) != is32:
+        raise TypeError(f"solve_unsteady: a {mine} ustart with a {other} cache (float32 fields: f32.ERKCache32; float64 fields: ode_method_cache)")
+    return is32
+
+
+def _solve_unsteady32(*, setup, tlims, u, temp, method, psolver, Δt, Δt_min, cfl, n_adapt_Δt, docopy, processors, θ, cache):
+    """solve_unsteady (solver.jl:18-92) with T = Float32: the loop of the fp64 path on `f32.timestep32_` / `f32.timesteps32_` and
+    `f32.get_cfl_timestep32_`.  `t` and `n` are kept on the host in double; `temp`, `θ`, a steady body force and the Smagorinsky closure go to the
+    step functions as they are (what those refuse is refused here)."""
+    from . import f32
+
+    method = method or RKMethods.RK44()
+    if isinstance(method, LMWray3):
+        raise NotImplementedError("solve_unsteady on float32 fields runs the explicit Runge-Kutta methods (LMWray3: float64 fields)")
+    if (temp is None) != (setup.temperature is None):
+        raise ValueError("a temperature field needs setup.temperature (temperature_equation) and vice versa")
+    psolver = psolver or f32.default_psolver32(setup)
+    cache = cache or f32.ERKCache32(method, setup, psolver)
+    if cache.psolver is not psolver:
+        raise ValueError("cache was created for a different psolver")
+    processors = processors or {}
+    if docopy:
+        u = copyfield(u)
+        temp = None if temp is None else copyfield(temp)
+    tstart, tend = tlims
+    stepper = create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=tstart)
+    state = {"value": get_state(stepper)}
+    initialized = {k: v.initialize(lambda: state["value"]) for k, v in processors.items()}
+
+    def advance(k, Δt, t_new=None):
+        if k > 1:
+            f32.timesteps32_(cache, u, Δt, k, temp=temp, θ=θ)
+        else:
+            f32.timestep32_(cache, u, Δt, temp=temp, θ=θ)
+        stepper.t = stepper.t + k * Δt if t_new is None else t_new
+        stepper.n += k
+        state["value"] = get_state(stepper)
+        for v in processors.values():
+            if hasattr(v, "on_step"):
+                v.on_step(state["value"])
+
+    if Δt is None:
+        while stepper.t < tend:
+            if stepper.n % n_adapt_Δt == 0:
+                Δt = cfl * f32.get_cfl_timestep32_(u, setup)
+                Δt = Δt if Δt_min is None else max(Δt, Δt_min)
+            last = Δt >= tend - stepper.t  # the step that is clipped to tend lands on it exactly
+            Δt = min(Δt, tend - stepper.t)
+            advance(1, Δt, tend if last else None)
+    else:
+        nstep = int(round((tend - tstart) / Δt))
+        Δt = (tend - tstart) / nstep
+        if not processors:  # nobody looks at the intermediate states: the whole loop is one native call
+            advance(nstep, Δt)
+        else:  # the batching of the fp64 path: the steps between the multiples of gcd(nupdate...) run as one native call
+            g = 0
+            for v in processors.values():
+                g = math.gcd(g, int(getattr(v, "nupdate", 1)))
+            if g <= 1 or os.environ.get("INS_NO_PROCESSOR_BATCH"):
+                g = 1
+            done = 0
+            while done < nstep:
+                k = min(g - (stepper.n % g), nstep - done)
+                advance(k, Δt)
+                done += k
+    outputs = {k: processors[k].finalize(initialized[k], lambda: state["value"]) for k in processors}
+    return (stepper.u, stepper.temp, stepper.t), outputs
+
+
 def solve_unsteady(*, setup, tlims, ustart, tempstart=None, method=None, psolver=None, Δt=None, Δt_min=None,
                    cfl=0.9, n_adapt_Δt=1, docopy=True, processors=None, θ=None, cache=None):
     """Solve unsteady problem using `method` (solver.jl:18-92).
 
     `processors` is a dict name -> object with `initialize(state_getter)` / `finalize(init, state_getter)`
-    and an optional `on_step(state)`; returns `((u, temp, t), outputs)` like the reference."""
+    and an optional `on_step(state)`; returns `((u, temp, t), outputs)` like the reference.
+
+    A `torch.float32` `ustart` (and `tempstart`) selects the Float32 family (`T = Float32` of the reference; f32.py): the default solver is
+    `f32.default_psolver32(setup)`, the default cache `f32.ERKCache32(method, setup, psolver)`; mixing precisions raises TypeError."""
+    if _is_float32_run(ustart, tempstart, psolver, cache):
+        return _solve_unsteady32(setup=setup, tlims=tlims, u=ustart, temp=tempstart, method=method, psolver=psolver, Δt=Δt, Δt_min=Δt_min, cfl=cfl,
+                                 n_adapt_Δt=n_adapt_Δt, docopy=docopy, processors=processors, θ=θ, cache=cache)
     method = method or RKMethods.RK44()
     psolver = psolver or default_psolver(setup)
     cache = cache or ode_method_cache(method, setup, psolver)
