@@ -546,6 +546,8 @@ int ins_comm_alltoall_f64(ins_comm_t* comm, const double* send, double* recv, in
  *     (csrc/ins_f32g.hip) and a Float32 solver handle wrapped around an fp64 solver of any kind (ins_poisson_wrap_f32).
  * Slab (halo) grids and time-dependent boundary data return INS_ERR_UNSUPPORTED — there is no silent fp64 fallback. */
 int ins_apply_bc_u_f32(const ins_grid_t* grid, float* u, void* stream);                                  /* boundary_conditions.jl:276-288 */
+/* apply_bc_u!(u, t, setup; dudt = true) with constant boundary data: the ghost fill of a time derivative (the Dirichlet data term is zero) */
+int ins_apply_bc_u_dudt_f32(const ins_grid_t* grid, float* u, void* stream);
 int ins_apply_bc_p_f32(const ins_grid_t* grid, float* p, void* stream);                                  /* boundary_conditions.jl:306-318 */
 int ins_momentum_f32(const ins_grid_t* grid, float visc, const float* u, float* F, void* stream);        /* operators.jl:967-976 */
 int ins_poisson_spectral_create_f32(const ins_grid_t* grid, ins_poisson32_t** out);                      /* pressure.jl:289-351 */
@@ -588,6 +590,17 @@ int ins_apply_bc_p_pullback_f32(const ins_grid_t* grid, float* phibar, void* str
  *     ghosts, P projects the interior, B fills the ghosts); P is symmetric on a uniform periodic box, so φbar ← Z·P·Bᵀ·φbar.
  * `pwork`: a float scalar field of scratch.  A wrapped spectral solver on an all-periodic box: INS_ERR_UNSUPPORTED. */
 int ins_project_pullback_f32(const ins_grid_t* grid, ins_poisson32_t* ps, float* phibar, float* pwork, void* stream);
+
+/* ---------------------------------------------------------------------------------- Float32 DNS-to-LES filters (csrc/ins_filter32.hip)
+ * The `_f32` twins of ins_filter_face_f64 ... ins_filter_volume_pullback_f64 (lib/NeuralClosure runs T = Float32): the same argument order, write
+ * sets, checks and refusals (null or aliased fields, grids that are not nested, differing boundary conditions: INS_ERR_INVALID; volume average and
+ * reconstruct off all-periodic grids: INS_ERR_UNSUPPORTED) on float fields; both grid handles are fp64 ones.  Loads and stores are float, every sum
+ * is formed in double and rounded once at the store.  Slab (halo) grids: INS_ERR_UNSUPPORTED. */
+int ins_filter_face_f32(const ins_grid_t* les, const ins_grid_t* dns, int comp, const float* u, float* v, void* stream);
+int ins_filter_volume_f32(const ins_grid_t* les, const ins_grid_t* dns, int comp, const float* u, float* v, void* stream);
+int ins_reconstruct_f32(const ins_grid_t* dns, const ins_grid_t* les, int comp, const float* v, float* u, void* stream);
+int ins_filter_face_pullback_f32(const ins_grid_t* les, const ins_grid_t* dns, int comp, const float* w, float* ubar, void* stream);
+int ins_filter_volume_pullback_f32(const ins_grid_t* les, const ins_grid_t* dns, int comp, const float* w, float* ubar, void* stream);
 
 /* ---------------------------------------------------------------------------------- Float32 tensor-basis closure (csrc/ins_tensorclosure32.hip)
  * The `_f32` twins of ins_tensorinvariants_f64, ins_tensorclosure_stress_f64, ins_tensorclosure_pullback_f64, ins_divoftensor_f64 and

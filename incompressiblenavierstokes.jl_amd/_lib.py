@@ -166,7 +166,13 @@ SIGNATURES = {
     "ins_slab_fft_forward_packed": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp]),
     "ins_slab_fft_inverse_packed": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
     "ins_apply_bc_u_f32": (C.c_int, [vp, vp, vp]),
+    "ins_apply_bc_u_dudt_f32": (C.c_int, [vp, vp, vp]),
     "ins_apply_bc_p_f32": (C.c_int, [vp, vp, vp]),
+    "ins_filter_face_f32": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "ins_filter_volume_f32": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "ins_reconstruct_f32": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "ins_filter_face_pullback_f32": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "ins_filter_volume_pullback_f32": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
     "ins_momentum_f32": (C.c_int, [vp, C.c_float, vp, vp, vp]),
     "ins_poisson_spectral_create_f32": (C.c_int, [vp, C.POINTER(vp)]),
     "ins_poisson_wrap_f32": (C.c_int, [vp, vp, C.POINTER(vp)]),

@@ -309,6 +309,45 @@ def project(u, setup, psolver):
     return _Project.apply(u, setup, psolver)
 
 
+# ------------------------------------------------------------------------------------ DNS-to-LES filters
+class _Filter(torch.autograd.Function):
+    """`v = Φ(u, setup_les, comp)` (lib/NeuralClosure filter.jl) on float32 fields with the exact transpose as backward (csrc/ins_filter32.hip):
+    the Float32 twin of `ad.FaceAverage` / `ad.VolumeAverage`.  `Filter.apply(u, setup_les, comp, setup_dns=None)`."""
+
+    _kind = None
+
+    @classmethod
+    def _filter(cls):
+        from . import neuralclosure as nc
+
+        return nc.FaceAverage() if cls._kind == "face" else nc.VolumeAverage()
+
+    @classmethod
+    def forward(cls, ctx, u, setup_les, comp, setup_dns=None):
+        from .neuralclosure import dns_setup_of
+
+        dns = setup_dns or dns_setup_of(setup_les, int(comp))
+        ctx.les, ctx.dns, ctx.comp = setup_les, dns, int(comp)
+        return cls._filter()(_field(dns, u.detach(), True), setup_les, int(comp), setup_dns=dns)
+
+    @classmethod
+    def backward(cls, ctx, g):
+        ubar = cls._filter().pullback_(F32.vectorfield32(ctx.dns), _field(ctx.les, g, True), ctx.les, ctx.comp, ctx.dns)
+        return ubar, None, None, None
+
+
+class FaceAverage(_Filter):
+    """filter.jl:26-46"""
+
+    _kind = "face"
+
+
+class VolumeAverage(_Filter):
+    """filter.jl:82-116"""
+
+    _kind = "volume"
+
+
 # ------------------------------------------------------------------------------------ tensor-basis closure
 def _vec(setup, u):
     """`u` as a float32 vector field in the library's layout; another dtype raises TypeError, another shape ValueError."""

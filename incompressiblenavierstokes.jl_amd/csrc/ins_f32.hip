@@ -29,7 +29,7 @@ int ins_zsolve_twiddles_f32(int nz, float** out);
 int ins_k_flux64_f32(const ins_grid* G, double visc, const float* u, float* F, const RkEpi* epi, const float* pI, int corr_mode, hipStream_t s,
                      int part = 0);
 // any other grid (walls, stretched spacings, 2-D or 3-D): csrc/ins_f32g.hip
-int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s);
+int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s, int dudt = 0);
 int ins_k32g_apply_bc_p(const ins_grid* G, float* p, hipStream_t s);
 int ins_k32g_apply_bc_p_fields(const ins_grid* G, float* p, int nf, hipStream_t s);
 int ins_k32g_momentum(const ins_grid* G, float visc, const float* u, float* F, hipStream_t s);
@@ -305,6 +305,13 @@ dim3 grid_over(const Box32& b, bool padded) {
 extern "C" int ins_apply_bc_u_f32(const ins_grid_t* G, float* u, void* stream) {
   INS_REQUIRE(G && u, "null argument");
   if (!periodic_uniform(G)) return ins_k32g_apply_bc_u(G, u, as_stream(stream));
+  return bc_periodic(G, u, G->g.D, as_stream(stream));
+}
+
+// apply_bc_u!(u, t, setup; dudt = true): the ghost fill of a time derivative — constant Dirichlet data contributes zero.  Periodic copies are the same.
+extern "C" int ins_apply_bc_u_dudt_f32(const ins_grid_t* G, float* u, void* stream) {
+  INS_REQUIRE(G && u, "null argument");
+  if (!periodic_uniform(G)) return ins_k32g_apply_bc_u(G, u, as_stream(stream), 1);
   return bc_periodic(G, u, G->g.D, as_stream(stream));
 }
 

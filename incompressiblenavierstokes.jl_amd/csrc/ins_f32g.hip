@@ -81,12 +81,12 @@ inline dim3 flat_grid(long long n) { return dim3((unsigned)std::min<long long>((
 
 }  // namespace
 
-int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s) {
+int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s, int dudt) {
   const GridDev& g = G->g;
   int rc = no_halo(G, "apply_bc_u (f32)");
   if (rc) return rc;
   for (int be = 0; be < g.D; ++be) {  // direction after direction: edges and corners come out as in the reference (boundary_conditions.jl:162-165)
-    INS_LAUNCH_D((k_bc_u<D, float>), line_launch(g, be, g.D), s, g, u, be, 0, (const float* const*)nullptr);  // constant boundary data
+    INS_LAUNCH_D((k_bc_u<D, float>), line_launch(g, be, g.D), s, g, u, be, dudt, (const float* const*)nullptr);  // constant boundary data
   }
   return INS_OK;
 }

@@ -1,361 +1,23 @@
-// DNS-to-LES filters of lib/NeuralClosure (filter.jl): face average, volume average, reconstruction, and the exact
-// transposes of the two filters.  fp64, 2-D and 3-D.
-//
-// A coarse ("LES") and a fine ("DNS") grid are two handles with n_dns = comp·n_les interior volumes per direction and
-// nested faces.  All indices below are 0-based positions in the padded arrays (N = n + ghosts, x fastest).
-//
-//   face    v[I, α] = mean of u[f, α],  f_α = lo_α + comp·(I_α − lo_α) + comp − 1,  f_β = lo_β + comp·(I_β − lo_β) + 0..comp−1   (β ≠ α)
-//           for I ∈ Iu[α] of the coarse grid, lo = first index of Iu[α]                                            filter.jl:26-46
-//   volume  v[I, α] = mean of u[f, α],  f_α = comp·I_α − h .. comp·I_α + h  (h = comp/2: comp + 1 planes for even comp, comp for odd),
-//           f_β = comp·(I_β − 1) + 1..comp, f wrapped into the fine interior 1..n_dns; all-periodic grids           filter.jl:82-116
-//   reconstruct  u[f, α] = ((comp − i_α)·v[c, α] + i_α·v[c − e_α, α]) / comp,  c = ceil(f / comp),  i = comp·c − f,
-//           c − e_α wrapped into the coarse interior; all-periodic grids                                            filter.jl:48-80
-//
-// The filters write Iu[α] of the coarse field only; reconstruct writes the fine interior only.  The pullbacks overwrite the whole padded
-// fine cotangent (zeros where the forward reads nothing), gather form, no atomics, as ins_adjoint.hip.
-//
-// Two kernels serve the filters: a generic one (one coarse face per work-item, every case) and a tiled one for the case that matters, a 3-D
-// all-periodic box with comp ∈ {2, 4, 8} (the face average from comp = 4): a wavefront reads whole contiguous fine x-rows (8 B per lane), sums the y and z window in registers,
-// and reduces the x window over an LDS row.  INS_DISABLE_FILTER_TILED forces the generic kernel.
-#include <cmath>
-
-#include "ins_stencil.h"
-
-namespace {
-
-struct FilterArgs {
-  int comp;
-  int Nc[3], Nf[3];  // padded sizes
-  int nf[3], nc[3];  // interior volumes (periodic wrap length)
-  long long sxc[3], scc, sxf[3], scf;
-  int lo[3][3], hi[3][3];  // coarse Iu[α] in direction β
-  const double* u;
-  double* v;
-};
-
-// --------------------------------------------------------------------------------------------
-// generic filters: one work-item per coarse volume, all components
-// --------------------------------------------------------------------------------------------
-template <int D, bool VOL>
-__global__ __launch_bounds__(256) void k_filter(FilterArgs a) {
-  INS_VOL_INDEX(a.sxc, 0, 0, 0, i >= a.Nc[0] || j >= a.Nc[1]);
-  const int C = a.comp;
-  const int h = C / 2;
-#pragma unroll
-  for (int al = 0; al < D; ++al) {
-    bool in = true;
-    int s[3] = {0, 0, 0}, n[3] = {1, 1, 1};
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      in = in && I[b] >= a.lo[al][b] && I[b] < a.hi[al][b];
-      if (VOL) {
-        s[b] = b == al ? C * I[b] - h : C * (I[b] - 1) + 1;
-        n[b] = b == al ? (C % 2 == 0 ? C + 1 : C) : C;
-      } else {
-        s[b] = a.lo[al][b] + C * (I[b] - a.lo[al][b]) + (b == al ? C - 1 : 0);
-        n[b] = b == al ? 1 : C;
-      }
-    }
-    if (!in) continue;
-    const double cnt = (double)(n[0] * n[1] * n[2]);
-    const double* __restrict__ u = a.u + al * a.scf;
-    double sum = 0.0;
-    for (int q2 = 0; q2 < n[2]; ++q2) {
-      int f2 = s[2] + q2;
-      if (VOL && D == 3 && f2 > a.nf[2]) f2 -= a.nf[2];
-      for (int q1 = 0; q1 < n[1]; ++q1) {
-        int f1 = s[1] + q1;
-        if (VOL && f1 > a.nf[1]) f1 -= a.nf[1];
-        const long long row = f1 * a.sxf[1] + f2 * a.sxf[2];
-        for (int q0 = 0; q0 < n[0]; ++q0) {
-          int f0 = s[0] + q0;
-          if (VOL && f0 > a.nf[0]) f0 -= a.nf[0];
-          sum += u[row + f0];
-        }
-      }
-    }
-    a.v[al * a.scc + c] = sum / cnt;
-  }
-}
-
-// --------------------------------------------------------------------------------------------
-// tiled filters: 3-D, all-periodic, comp = C ∈ {2, 4, 8}.  Block = 4 wavefronts = 4 coarse y-rows of one coarse z-plane; a wavefront owns
-// 64 contiguous fine x-volumes (fine index 64·bx + 1 + lane) = 64/C coarse outputs.  Every load is one whole 512-B row segment; the α = x
-// component of the face average needs one lane in C of them and loads the whole row all the same (8·C ≤ 64 B between the lanes it needs:
-// every cache line of the row is touched either way).
-// --------------------------------------------------------------------------------------------
-template <int C, bool VOL, int AL>
-__device__ __forceinline__ void tiled_component(const FilterArgs& a, const double* __restrict__ ufield, double* __restrict__ vfield, double* t, int bx,
-                                                int Jc, int Kc, bool rowok) {
-  constexpr int H = C / 2;
-  constexpr int NY = VOL ? (AL == 1 ? C + 1 : C) : (AL == 1 ? 1 : C);
-  constexpr int NZ = VOL ? (AL == 2 ? C + 1 : C) : (AL == 2 ? 1 : C);
-  const int lane = threadIdx.x;
-  const int n0 = a.nf[0];
-  const int valid = min(64, n0 - 64 * bx);  // fine volumes of this tile (a multiple of C)
-  const int sy = VOL ? (AL == 1 ? C * Jc - H : C * (Jc - 1) + 1) : (AL == 1 ? C * Jc : C * (Jc - 1) + 1);
-  const int sz = VOL ? (AL == 2 ? C * Kc - H : C * (Kc - 1) + 1) : (AL == 2 ? C * Kc : C * (Kc - 1) + 1);
-  const double* __restrict__ u = ufield + AL * a.scf;
-  const bool main_ok = rowok && lane < valid;
-  const bool halo_ok = VOL && AL == 0 && rowok && lane < H;  // the x window of the last output reaches H volumes into the next tile
-  int ih = 64 * bx + 1 + valid + lane;
-  if (ih > n0) ih -= n0;
-  const int i = 64 * bx + 1 + lane;
-  double acc = 0.0, acch = 0.0;
-#pragma unroll
-  for (int qz = 0; qz < NZ; ++qz) {
-    int fz = sz + qz;
-    if (VOL && fz > a.nf[2]) fz -= a.nf[2];
-#pragma unroll
-    for (int qy = 0; qy < NY; ++qy) {
-      int fy = sy + qy;
-      if (VOL && fy > a.nf[1]) fy -= a.nf[1];
-      const long long row = fy * a.sxf[1] + fz * a.sxf[2];
-      if (main_ok) acc += u[row + i];
-      if (halo_ok) acch += u[row + ih];
-    }
-  }
-  if (main_ok) t[lane] = acc;
-  if (halo_ok) t[valid + lane] = acch;
-  __syncthreads();
-  if (rowok && lane < valid / C) {
-    double s = 0.0;
-    if (VOL && AL == 0) {
-#pragma unroll
-      for (int q = -H; q <= H; ++q) s += t[C * (lane + 1) - 1 + q];
-    } else if (AL == 0) {
-      s = t[C * (lane + 1) - 1];
-    } else {
-#pragma unroll
-      for (int q = 0; q < C; ++q) s += t[C * lane + q];
-    }
-    constexpr double cnt = VOL ? (double)((C + 1) * C * C) : (double)(C * C);
-    vfield[AL * a.scc + (64 * bx / C + 1 + lane) + Jc * a.sxc[1] + Kc * a.sxc[2]] = s / cnt;
-  }
-}
-
-template <int C, bool VOL>
-__global__ __launch_bounds__(256) void k_filter_tiled(FilterArgs a) {
-  __shared__ double lds[3][4][64 + 4];  // one row per component and wavefront: no row is reused, so one barrier per component
-  const int bx = blockIdx.x;
-  const int Jc = blockIdx.y * 4 + threadIdx.y + 1;
-  const int Kc = blockIdx.z + 1;
-  const bool rowok = Jc <= a.nc[1];
-  tiled_component<C, VOL, 0>(a, a.u, a.v, lds[0][threadIdx.y], bx, Jc, Kc, rowok);
-  tiled_component<C, VOL, 1>(a, a.u, a.v, lds[1][threadIdx.y], bx, Jc, Kc, rowok);
-  tiled_component<C, VOL, 2>(a, a.u, a.v, lds[2][threadIdx.y], bx, Jc, Kc, rowok);
-}
-
-// --------------------------------------------------------------------------------------------
-// reconstruct: one work-item per fine volume (interior only)
-// --------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_reconstruct(FilterArgs a, const double* __restrict__ v, double* __restrict__ u) {
-  INS_VOL_INDEX(a.sxf, 0, 0, 0, false);
-  bool in = true;
-#pragma unroll
-  for (int b = 0; b < D; ++b) in = in && I[b] >= 1 && I[b] <= a.nf[b];
-  if (!in) return;
-  const int C = a.comp;
-  int ci[3] = {0, 0, 0}, off[3] = {0, 0, 0};
-  long long cc = 0;
-#pragma unroll
-  for (int b = 0; b < D; ++b) {
-    ci[b] = (I[b] + C - 1) / C;
-    off[b] = C * ci[b] - I[b];
-    cc += ci[b] * a.sxc[b];
-  }
-#pragma unroll
-  for (int al = 0; al < D; ++al) {
-    const int cl = ci[al] == 1 ? a.nc[al] : ci[al] - 1;
-    const long long cleft = cc + (long long)(cl - ci[al]) * a.sxc[al];
-    double s = 0.0;
-    s += (double)(C - off[al]) * v[al * a.scc + cc];
-    s += (double)off[al] * v[al * a.scc + cleft];
-    u[al * a.scf + c] = s / (double)C;
-  }
-}
-
-// --------------------------------------------------------------------------------------------
-// pullbacks: one work-item per fine volume of the whole padded array; ubar = Φᵀ w
-// --------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_filter_face_pullback(FilterArgs a, const double* __restrict__ w, double* __restrict__ ubar) {
-  INS_VOL_INDEX(a.sxf, 0, 0, 0, i >= a.Nf[0] || j >= a.Nf[1]);
-  const int C = a.comp;
-  double cnt = 1.0;
-  for (int b = 1; b < D; ++b) cnt *= (double)C;
-#pragma unroll
-  for (int al = 0; al < D; ++al) {
-    bool hit = true;
-    long long cc = 0;
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      const int q = I[b] - a.lo[al][b] - (b == al ? C - 1 : 0);
-      hit = hit && q >= 0 && (b != al || q % C == 0);
-      const int Ic = a.lo[al][b] + (q >= 0 ? q / C : 0);
-      hit = hit && Ic < a.hi[al][b];
-      cc += Ic * a.sxc[b];
-    }
-    ubar[al * a.scf + c] = hit ? w[al * a.scc + cc] / cnt : 0.0;
-  }
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void k_filter_volume_pullback(FilterArgs a, const double* __restrict__ w, double* __restrict__ ubar) {
-  INS_VOL_INDEX(a.sxf, 0, 0, 0, i >= a.Nf[0] || j >= a.Nf[1]);
-  const int C = a.comp;
-  const int h = C / 2;
-  bool in = true;
-  int ct[3] = {0, 0, 0};  // coarse volume whose tangential window holds F
-#pragma unroll
-  for (int b = 0; b < D; ++b) {
-    in = in && I[b] >= 1 && I[b] <= a.nf[b];
-    ct[b] = (I[b] + C - 1) / C;
-  }
-  double cnt = (double)(C % 2 == 0 ? C + 1 : C);
-  for (int b = 1; b < D; ++b) cnt *= (double)C;
-#pragma unroll
-  for (int al = 0; al < D; ++al) {
-    double s = 0.0;
-    if (in) {
-      long long base = 0;
-#pragma unroll
-      for (int b = 0; b < D; ++b)
-        if (b != al) base += ct[b] * a.sxc[b];
-      // coarse faces comp·Ic within h of I[al] (periodic): at most two, and two only for even comp at the shared plane
-      const int q = I[al] / C, r = I[al] % C;
-      if (r <= h) {
-        const int Ic = q == 0 ? a.nc[al] : q;
-        s += w[al * a.scc + base + Ic * a.sxc[al]];
-      }
-      if (C - r <= h) {
-        const int Ic = q + 1 > a.nc[al] ? 1 : q + 1;
-        s += w[al * a.scc + base + Ic * a.sxc[al]];
-      }
-    }
-    ubar[al * a.scf + c] = s / cnt;
-  }
-}
-
-// --------------------------------------------------------------------------------------------
-// host side
-// --------------------------------------------------------------------------------------------
-inline int ghosts_left(const ins_grid* G, int b) { return G->desc.bc[b][0] == INS_BC_PRESSURE ? 2 : 1; }
-
-// Checks the pair of grids and fills the index part of the arguments.  `need_periodic`: volume average / reconstruct.
-int prepare(const ins_grid* les, const ins_grid* dns, int comp, bool need_periodic, const char* what, FilterArgs& a) {
-  INS_REQUIRE(les && dns, "null grid handle");
-  INS_REQUIRE(comp >= 1, "compression must be >= 1");
-  const int D = les->g.D;
-  INS_REQUIRE(dns->g.D == D, "the two grids differ in dimension");
-  memset(&a, 0, sizeof(a));
-  a.comp = comp;
-  for (int b = 0; b < 3; ++b) {
-    a.Nc[b] = les->g.N[b];
-    a.Nf[b] = dns->g.N[b];
-    a.sxc[b] = les->g.sx[b];
-    a.sxf[b] = dns->g.sx[b];
-    a.nc[b] = a.nf[b] = 1;
-  }
-  a.scc = les->g.sc;
-  a.scf = dns->g.sc;
-  for (int b = 0; b < D; ++b) {
-    for (int s = 0; s < 2; ++s) INS_REQUIRE(les->desc.bc[b][s] == dns->desc.bc[b][s], "the two grids differ in boundary conditions");
-    const int gl = ghosts_left(les, b);
-    a.nc[b] = les->g.N[b] - gl - 1;
-    a.nf[b] = dns->g.N[b] - gl - 1;
-    INS_REQUIRE((long long)comp * a.nc[b] == a.nf[b], "n_dns must be comp * n_les in every direction");
-    // nested faces: every coarse volume is the union of its comp fine volumes
-    for (int I = 0; I < a.nc[b]; ++I) {
-      double sum = 0.0;
-      for (int q = 0; q < comp; ++q) sum += dns->desc.dx[b][gl + comp * I + q];
-      const double w = les->desc.dx[b][gl + I];
-      INS_REQUIRE(std::fabs(sum - w) <= 1e-8 * std::fabs(w), "the grids are not nested (x_les[i] != x_dns[comp*i])");
-    }
-  }
-  for (int al = 0; al < D; ++al)
-    for (int b = 0; b < D; ++b) {
-      a.lo[al][b] = les->g.iu_lo[al][b];
-      a.hi[al][b] = les->g.iu_hi[al][b];
-      // last fine index the face average reads
-      const long long last = a.lo[al][b] + (long long)comp * (a.hi[al][b] - 1 - a.lo[al][b]) + comp - 1;
-      INS_REQUIRE(last <= dns->g.N[b] - 1, "the face window leaves the fine array");
-    }
-  if (need_periodic && !(les->all_periodic && dns->all_periodic)) {
-    ins_set_error("%s needs an all-periodic grid", what);
-    return INS_ERR_UNSUPPORTED;
-  }
-  return INS_OK;
-}
-
-// The face average at comp = 2 stays on the generic kernel: measured equal at 256³ and 10 % slower tiled at 512³.
-bool tiled_supported(const ins_grid* les, const ins_grid* dns, int comp, bool vol) {
-  return les->g.D == 3 && les->all_periodic && dns->all_periodic && (comp == 4 || comp == 8 || (comp == 2 && vol)) &&
-         !ins_opt(OPT_INS_DISABLE_FILTER_TILED);
-}
-
-template <bool VOL>
-int launch_filter(const ins_grid* les, const ins_grid* dns, int comp, const double* u, double* v, hipStream_t s) {
-  FilterArgs a;
-  int rc = prepare(les, dns, comp, VOL, VOL ? "the volume average" : "the face average", a);
-  if (rc) return rc;
-  INS_REQUIRE(u && v, "null field");
-  INS_REQUIRE(u != v, "the filter cannot run in place");
-  a.u = u;
-  a.v = v;
-  const GridDev& g = les->g;
-  if (tiled_supported(les, dns, comp, VOL)) {
-    dim3 block(64, 4, 1), grid(cdiv(a.nf[0], 64), cdiv(a.nc[1], 4), (unsigned)a.nc[2]);
-    if (comp == 2)
-      hipLaunchKernelGGL((k_filter_tiled<2, VOL>), grid, block, 0, s, a);
-    else if (comp == 4)
-      hipLaunchKernelGGL((k_filter_tiled<4, VOL>), grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL((k_filter_tiled<8, VOL>), grid, block, 0, s, a);
-    INS_LAUNCH_CHECK();
-  } else {
-    INS_LAUNCH_D((k_filter<D, VOL>), box_launch(g.D, a.Nc), s, a);
-  }
-  return INS_OK;
-}
-
-}  // namespace
+// DNS-to-LES filters of lib/NeuralClosure (filter.jl), fp64: the double instantiations of ins_filter_kernels.h behind the _f64 entries
+// (DESIGN.md §6c).  The tiled kernel keeps one fine x-volume (8 B) per lane.
+#include "ins_filter_kernels.h"
 
 extern "C" int ins_filter_face_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, const double* u, double* v, void* stream) {
-  return launch_filter<false>(les, dns, comp, u, v, as_stream(stream));
+  return launch_filter<false, double, 1>(les, dns, comp, u, v, as_stream(stream));
 }
 
 extern "C" int ins_filter_volume_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, const double* u, double* v, void* stream) {
-  return launch_filter<true>(les, dns, comp, u, v, as_stream(stream));
+  return launch_filter<true, double, 1>(les, dns, comp, u, v, as_stream(stream));
 }
 
 extern "C" int ins_reconstruct_f64(const ins_grid_t* dns, const ins_grid_t* les, int comp, const double* v, double* u, void* stream) {
-  FilterArgs a;
-  int rc = prepare(les, dns, comp, true, "reconstruct", a);
-  if (rc) return rc;
-  INS_REQUIRE(u && v && u != v, "null or aliased field");
-  const GridDev& g = les->g;
-  INS_LAUNCH_D((k_reconstruct<D>), box_launch(g.D, a.Nf), as_stream(stream), a, v, u);
-  return INS_OK;
+  return launch_reconstruct<double>(dns, les, comp, v, u, as_stream(stream));
 }
 
 extern "C" int ins_filter_face_pullback_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, const double* w, double* ubar, void* stream) {
-  FilterArgs a;
-  int rc = prepare(les, dns, comp, false, "the face average", a);
-  if (rc) return rc;
-  INS_REQUIRE(w && ubar && w != ubar, "null or aliased field");
-  const GridDev& g = les->g;
-  INS_LAUNCH_D((k_filter_face_pullback<D>), box_launch(g.D, a.Nf), as_stream(stream), a, w, ubar);
-  return INS_OK;
+  return launch_filter_pullback<false, double>(les, dns, comp, w, ubar, as_stream(stream));
 }
 
 extern "C" int ins_filter_volume_pullback_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, const double* w, double* ubar, void* stream) {
-  FilterArgs a;
-  int rc = prepare(les, dns, comp, true, "the volume average", a);
-  if (rc) return rc;
-  INS_REQUIRE(w && ubar && w != ubar, "null or aliased field");
-  const GridDev& g = les->g;
-  INS_LAUNCH_D((k_filter_volume_pullback<D>), box_launch(g.D, a.Nf), as_stream(stream), a, w, ubar);
-  return INS_OK;
+  return launch_filter_pullback<true, double>(les, dns, comp, w, ubar, as_stream(stream));
 }

@@ -50,9 +50,11 @@ def _constant_bc_only(setup):
         raise NotImplementedError("the _f32 family takes constant boundary data (callable DirichletBC values: use the fp64 entry points)")
 
 
-def apply_bc_u32_(u, setup):
+def apply_bc_u32_(u, setup, dudt=False):
+    """apply_bc_u!(u, t, setup; dudt) with T = Float32 and constant boundary data: with `dudt` the field is a time derivative and the Dirichlet
+    data contributes zero."""
     _constant_bc_only(setup)
-    _lib.call("ins_apply_bc_u_f32", setup.handle, _ptr(setup, u, setup.grid.dimension), setup.stream)
+    _lib.call("ins_apply_bc_u_dudt_f32" if dudt else "ins_apply_bc_u_f32", setup.handle, _ptr(setup, u, setup.grid.dimension), setup.stream)
     return u
 
 

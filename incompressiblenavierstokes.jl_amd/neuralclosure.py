@@ -2,7 +2,8 @@
 closure wrappers and the CNN (closure.jl, cnn.jl), data loaders, a-priori / a-posteriori losses and the training loop (training.jl).
 Exported as `ins_amd.neuralclosure`; the main names also from `ins_amd`.
 
-The filters run in csrc/ins_filter.hip.  The network is torch (float64): a closure is a callable `m(u, θ)`; for a
+The filters run in csrc/ins_filter.hip and, on float32 fields, csrc/ins_filter32.hip.  The network is torch (float64, or
+float32 with `dtype=torch.float32`; a Float32 DNS is filtered, stored and trained on in Float32): a closure is a callable `m(u, θ)`; for a
 `torch.nn.Module` built by `cnn`, θ is `None` (the module's own parameters, which a `torch.optim` optimiser updates in place) or a
 dict name -> tensor as `torch.func.functional_call` takes it.
 
@@ -21,6 +22,7 @@ import torch
 
 from . import _lib
 from . import autodiff as ad
+from . import f32
 from .initializers import random_field
 from .operators import apply_bc_u_, momentum_
 from .pressure import default_psolver, project_
@@ -56,30 +58,53 @@ def dns_setup_of(setup_les, comp):
     return cache[comp]
 
 
+def _is32(f):
+    return isinstance(f, torch.Tensor) and f.dtype == torch.float32
+
+
+def _one_precision(fine, coarse, what):
+    if isinstance(fine, torch.Tensor) and isinstance(coarse, torch.Tensor) and fine.dtype != coarse.dtype:
+        raise TypeError(f"{what}: the fine field is {fine.dtype}, the coarse field {coarse.dtype}; a filter call takes one precision")
+
+
+def _filter_ptrs(dns, fine, les, coarse, what):
+    """Entry suffix and the two field pointers of a filter call, by the precision of the fields: float64 -> `_f64`, float32 -> `_f32`
+    (csrc/ins_filter32.hip).  The two fields are of one precision (TypeError, raised before a setup is touched)."""
+    _one_precision(fine, coarse, what)
+    if _is32(fine):
+        D = dns.grid.dimension
+        return "f32", f32._ptr(dns, fine, D), f32._ptr(les, coarse, D)
+    return "f64", dns.ptr(fine, True), les.ptr(coarse, True)
+
+
 class AbstractFilter:
     """Discrete DNS filter (filter.jl:1-15): `Φ(v, u, setup_les, comp)` filters the DNS field `u` into the LES field `v` (only `Iu[α]` is
     written: ghosts are the caller's `apply_bc_u_`); `Φ(u, setup_les, comp)` allocates `v`.  `setup_dns` names the fine grid; without it
-    the fine grid is `setup_les` subdivided (`dns_setup_of`)."""
+    the fine grid is `setup_les` subdivided (`dns_setup_of`).  float32 fields take the `_f32` kernels (float loads and stores, sums in double,
+    one rounding) and the allocating forms return a `f32.vectorfield32`; `u` and `v` of different precisions: TypeError."""
 
     _entry = None
 
     def __call__(self, *args, setup_dns=None):
         if len(args) == 3:
             u, setup_les, comp = args
-            v = vectorfield(setup_les)
+            v = f32.vectorfield32(setup_les) if _is32(u) else vectorfield(setup_les)
         elif len(args) == 4:
             v, u, setup_les, comp = args
         else:
             raise TypeError("Φ(u, setup_les, comp) or Φ(v, u, setup_les, comp)")
+        _one_precision(u, v, "Φ(v, u, …)")
         dns = setup_dns or dns_setup_of(setup_les, int(comp))
-        _lib.call(f"ins_filter_{self._entry}_f64", setup_les.handle, dns.handle, int(comp), dns.ptr(u, True), setup_les.ptr(v, True), setup_les.stream)
+        sfx, pu, pv = _filter_ptrs(dns, u, setup_les, v, "Φ(v, u, …)")
+        _lib.call(f"ins_filter_{self._entry}_{sfx}", setup_les.handle, dns.handle, int(comp), pu, pv, setup_les.stream)
         return v
 
     def pullback_(self, ubar, w, setup_les, comp, setup_dns=None):
         """ubar = Φᵀ w over the whole padded fine array."""
+        _one_precision(ubar, w, "pullback_(ubar, w, …)")
         dns = setup_dns or dns_setup_of(setup_les, int(comp))
-        _lib.call(f"ins_filter_{self._entry}_pullback_f64", setup_les.handle, dns.handle, int(comp), setup_les.ptr(w, True), dns.ptr(ubar, True),
-                  setup_les.stream)
+        sfx, pubar, pw = _filter_ptrs(dns, ubar, setup_les, w, "pullback_(ubar, w, …)")
+        _lib.call(f"ins_filter_{self._entry}_pullback_{sfx}", setup_les.handle, dns.handle, int(comp), pw, pubar, setup_les.stream)
         return ubar
 
     def __repr__(self):
@@ -99,32 +124,56 @@ class VolumeAverage(AbstractFilter):
 
 
 def reconstruct_(u, v, setup_dns, setup_les, comp):
-    """Reconstruct DNS velocity `u` from LES velocity `v` (filter.jl:48-76): writes the fine interior."""
-    _lib.call("ins_reconstruct_f64", setup_dns.handle, setup_les.handle, int(comp), setup_les.ptr(v, True), setup_dns.ptr(u, True), setup_les.stream)
+    """Reconstruct DNS velocity `u` from LES velocity `v` (filter.jl:48-76): writes the fine interior.  float64 or float32 fields."""
+    sfx, pu, pv = _filter_ptrs(setup_dns, u, setup_les, v, "reconstruct_(u, v, …)")
+    _lib.call(f"ins_reconstruct_{sfx}", setup_dns.handle, setup_les.handle, int(comp), pv, pu, setup_les.stream)
     return u
 
 
 def reconstruct(v, setup_dns, setup_les, comp):
     """filter.jl:78-80"""
-    return reconstruct_(vectorfield(setup_dns), v, setup_dns, setup_les, comp)
+    return reconstruct_(f32.vectorfield32(setup_dns) if _is32(v) else vectorfield(setup_dns), v, setup_dns, setup_les, comp)
 
 
 # ------------------------------------------------------------------------------------------------ data generation (data_generation.jl)
+def _ops(single):
+    """The operator chain of the data generation in one precision: (vectorfield, scalarfield, bc_u(u, t, setup, dudt), momentum(F, u, t, setup),
+    project(u, setup, psolver, p)).  float32: the `_f32` family (f32.py), constant boundary data."""
+    if single:
+        return (f32.vectorfield32, f32.scalarfield32, lambda u, t, s, dudt=False: f32.apply_bc_u32_(u, s, dudt=dudt),
+                lambda F, u, t, s: f32.momentum32_(F, u, s), f32.project32_)
+    return (vectorfield, scalarfield, lambda u, t, s, dudt=False: apply_bc_u_(u, t, s, dudt=dudt), lambda F, u, t, s: momentum_(F, u, None, t, s),
+            project_)
+
+
+def _check_precision(single, psolvers, what):
+    """A float32 state takes Float32 solvers (`f32.psolver_spectral32` / `f32.psolver_wrap32`), a float64 state fp64 ones: TypeError otherwise."""
+    mine, other = ("float32", "float64") if single else ("float64", "float32")
+    for ps in psolvers:
+        if isinstance(ps, f32.psolver_spectral32) != single:
+            raise TypeError(f"{what}: a {mine} state with a {other} pressure solver ({type(ps).__name__}); float32 states take "
+                            "f32.psolver_spectral32 / f32.psolver_wrap32 / f32.default_psolver32, float64 states default_psolver and its kin")
+
+
 def lesdatagen(dnsobs, Φ, les, compression, psolver, dns=None):
     """data_generation.jl:37-60: on every DNS observation `(u, F, t)` store `ū = bc(Φu)` and the commutator error
-    `c = ΦF − project(bc(momentum(ū)))` on the host."""
-    p = scalarfield(les)
-    Φu, FΦ, ΦF = vectorfield(les), vectorfield(les), vectorfield(les)
+    `c = ΦF − project(bc(momentum(ū)))` on the host.  The precision is that of the observed `u`: a float32 state runs the chain on the `_f32`
+    family and stores float32 arrays."""
+    single = _is32(dnsobs.value["u"])
+    _check_precision(single, [psolver], "lesdatagen")
+    vfield, sfield, bc_u, momentum, project = _ops(single)
+    p = sfield(les)
+    Φu, FΦ, ΦF = vfield(les), vfield(les), vfield(les)
     results = dict(u=[], c=[])
 
     def step(obs):
         u, F, t = obs["u"], obs["F"], obs["t"]
         Φ(Φu, u, les, compression, setup_dns=dns)
-        apply_bc_u_(Φu, t, les)
+        bc_u(Φu, t, les)
         Φ(ΦF, F, les, compression, setup_dns=dns)
-        momentum_(FΦ, Φu, None, t, les)
-        apply_bc_u_(FΦ, t, les, dudt=True)
-        project_(FΦ, les, psolver, p)
+        momentum(FΦ, Φu, t, les)
+        bc_u(FΦ, t, les, dudt=True)
+        project(FΦ, les, psolver, p)
         results["u"].append(to_numpy(Φu))
         results["c"].append(to_numpy(ΦF - FΦ))
 
@@ -136,15 +185,23 @@ def filtersaver(dns, les, filters, compression, psolver_dns, psolver_les, *, nup
     """Save filtered DNS data (data_generation.jl:62-120): a processor that every `nupdate` steps (and for the initial state) forms
     `F = project(bc(momentum(u)))` on the DNS grid and hands `(u, F, t)` to one `lesdatagen` per (LES grid, filter), LES grid fastest.
     `finalize` returns one dict `(u, c, t, comptime)` per pair, `u` and `c` stacked along a last axis; `filenames` (one per pair) are written
-    with `np.savez`.  `F` and `p` are scratch on the DNS grid, allocated here unless given; the processor never writes into the state."""
+    with `np.savez`.  `F` and `p` are scratch on the DNS grid, allocated here unless given; the processor never writes into the state.
+    A float32 state (a Float32 `solve_unsteady`) runs the whole chain in Float32 and stores float32 `u` and `c` (`t` stays double); the solvers are
+    then Float32 solvers, and a mix of precisions raises TypeError in `initialize`, before any launch."""
     les, filters, compression, psolver_les = list(les), list(filters), list(compression), list(psolver_les)
     if filenames is not None and len(filenames) != len(les) * len(filters):
         raise ValueError("one file name per (LES grid, filter) pair")
-    F = vectorfield(dns) if F is None else F
-    p = scalarfield(dns) if p is None else p
+    scratch = dict(F=F, p=p)
 
     def initialize(state):
         s0 = state.value
+        single = _is32(s0["u"])
+        _check_precision(single, [psolver_dns] + psolver_les, "filtersaver")
+        vfield, sfield, bc_u, momentum, project = _ops(single)
+        F = vfield(dns) if scratch["F"] is None else scratch["F"]
+        p = sfield(dns) if scratch["p"] is None else scratch["p"]
+        if _is32(F) != single or _is32(p) != single:
+            raise TypeError(f"filtersaver: the scratch fields F ({F.dtype}) and p ({p.dtype}) must have the precision of the state ({s0['u'].dtype})")
         dnsobs = Observable(dict(u=s0["u"], F=F, t=s0["t"]))
         data = [lesdatagen(dnsobs, Φ, les[i], compression[i], psolver_les[i], dns) for Φ in filters for i in range(len(les))]
         results = dict(data=data, t=[], comptime=time.time())
@@ -153,9 +210,9 @@ def filtersaver(dns, les, filters, compression, psolver_dns, psolver_les, *, nup
             if s["n"] % nupdate != 0:
                 return
             u, t = s["u"], s["t"]
-            momentum_(F, u, None, t, dns)
-            apply_bc_u_(F, t, dns, dudt=True)
-            project_(F, dns, psolver_dns, p)
+            momentum(F, u, t, dns)
+            bc_u(F, t, dns, dudt=True)
+            project(F, dns, psolver_dns, p)
             results["t"].append(t)
             dnsobs.value = dict(u=u, F=F, t=t)
 
@@ -176,10 +233,17 @@ def filtersaver(dns, les, filters, compression, psolver_dns, psolver_les, *, nup
     return processor(initialize, finalize, nupdate=nupdate)
 
 
-def create_les_data(*, D, Re, lims, nles, ndns, filters, tburn, tsim, savefreq, Δt=None, method=None, create_psolver=default_psolver, icfunc=None,
-                    processors=None, rng=None, filenames=None, device=None, **kwargs):
+def create_les_data(*, D, Re, lims, nles, ndns, filters, tburn, tsim, savefreq, Δt=None, method=None, create_psolver=None, icfunc=None,
+                    processors=None, rng=None, filenames=None, device=None, dtype=torch.float64, **kwargs):
     """Create filtered DNS data (data_generation.jl:125-223): burn-in DNS from `icfunc(setup, psolver, rng)`, then a DNS of length `tsim` whose
-    state is filtered every `savefreq` steps onto every grid of `nles` by every filter.  Returns `filtersaver`'s list."""
+    state is filtered every `savefreq` steps onto every grid of `nles` by every filter.  Returns `filtersaver`'s list.
+    `create_psolver` defaults to `default_psolver`.  `dtype=torch.float32` (the reference's `T = Float32`): `create_psolver` defaults to
+    `f32.default_psolver32`, the initial field comes from `icfunc` on an fp64 solver, is rounded once and projected with the Float32 solver,
+    and burn-in, run, filters and stored arrays are Float32."""
+    if dtype not in (torch.float64, torch.float32):
+        raise TypeError("create_les_data: dtype is torch.float64 or torch.float32")
+    single = dtype == torch.float32
+    create_psolver = create_psolver or (f32.default_psolver32 if single else default_psolver)
     method = method or RKMethods.RK44()
     rng = rng if rng is not None else np.random.default_rng()
     nles = list(nles)
@@ -193,11 +257,16 @@ def create_les_data(*, D, Re, lims, nles, ndns, filters, tburn, tsim, savefreq, 
     if icfunc is None:
         def icfunc(setup, psolver, rng):
             return random_field(setup, 0.0, psolver=psolver, seed=int(rng.integers(2**31 - 1)))
-    u = icfunc(dns, psolver, rng)
+    if single:
+        _check_precision(True, [psolver] + psolver_les, "create_les_data(dtype=torch.float32)")
+        u = f32.to_f32(dns, icfunc(dns, default_psolver(dns), rng))
+        f32.apply_bc_u32_(f32.project32_(f32.apply_bc_u32_(u, dns), dns, psolver, f32.scalarfield32(dns)), dns)
+    else:
+        u = icfunc(dns, psolver, rng)
     if bool(torch.isnan(u).any()):
         print("Warning: initial conditions contain NaNs")
     processors = dict(processors or {})
-    cache = ode_method_cache(method, dns, psolver)
+    cache = f32.ERKCache32(method, dns, psolver) if single else ode_method_cache(method, dns, psolver)
     if tburn > 0:  # the initial spectrum is artificial: a short simulation makes it realistic
         (u, _, _), _ = solve_unsteady(setup=dns, ustart=u, docopy=False, tlims=(0.0, tburn), Δt=Δt, method=method, psolver=psolver, cache=cache,
                                       processors=processors)
@@ -210,7 +279,7 @@ def create_les_data(*, D, Re, lims, nles, ndns, filters, tburn, tsim, savefreq, 
 def create_io_arrays(data, setup):
     """Create (ū, c) pairs for a-priori training (data_generation.jl:228-252): `data` is a list of trajectories `dict(u, c, t)` on the grid of
     `setup`; returns `dict(u, c)` of numpy arrays `(n…, D, nsample)` holding `Iu[α]` of every component, trajectories joined along the
-    sample axis."""
+    sample axis.  The arrays have the dtype of the data: float32 trajectories give float32 arrays."""
     g = setup.grid
     D = g.dimension
     out = {}
@@ -218,10 +287,11 @@ def create_io_arrays(data, setup):
         parts = []
         for traj in data:
             nt = len(traj["t"])
-            a = np.zeros(tuple(n - 2 for n in g.N) + (D, nt))
+            src = np.asarray(traj[key])
+            a = np.zeros(tuple(n - 2 for n in g.N) + (D, nt), dtype=src.dtype if src.dtype == np.float32 else np.float64)
             for α in range(D):
                 sl = tuple(slice(lo, hi) for lo, hi in g.Iu[α])
-                a[..., α, :] = np.asarray(traj[key])[sl + (α, slice(None))]
+                a[..., α, :] = src[sl + (α, slice(None))]
             parts.append(a)
         out[key] = np.concatenate(parts, axis=-1)
     return out
@@ -264,16 +334,19 @@ def decollocate(u):
 
 
 class CNN(torch.nn.Module):
-    """collocate → circular padding by Σ radii → convolutions (kernel 2r+1, no further padding) → decollocate, float64 (cnn.jl)."""
+    """collocate → circular padding by Σ radii → convolutions (kernel 2r+1, no further padding) → decollocate (cnn.jl); float64 parameters, or
+    float32 with `dtype=torch.float32`."""
 
-    def __init__(self, D, radii, channels, activations, use_bias, generator=None):
+    def __init__(self, D, radii, channels, activations, use_bias, generator=None, dtype=torch.float64):
         super().__init__()
+        if dtype not in (torch.float64, torch.float32):
+            raise TypeError("cnn: dtype is torch.float64 or torch.float32")
         if channels[-1] != D:
             raise ValueError("the last layer must have D channels (one force field per direction)")
         self.D, self.pad, self.activations = D, int(sum(radii)), list(activations)
         c = [D] + list(channels)
         Conv = torch.nn.Conv2d if D == 2 else torch.nn.Conv3d
-        self.convs = torch.nn.ModuleList(Conv(c[i], c[i + 1], 2 * radii[i] + 1, bias=bool(use_bias[i]), dtype=torch.float64) for i in range(len(radii)))
+        self.convs = torch.nn.ModuleList(Conv(c[i], c[i + 1], 2 * radii[i] + 1, bias=bool(use_bias[i]), dtype=dtype) for i in range(len(radii)))
         for conv in self.convs:  # glorot_uniform weights, zero bias, as Lux's Conv with init_weight = glorot_uniform
             torch.nn.init.xavier_uniform_(conv.weight, generator=generator)
             if conv.bias is not None:
@@ -294,13 +367,14 @@ class CNN(torch.nn.Module):
         return decollocate(x)
 
 
-def cnn(*, setup, radii, channels, activations, use_bias, rng=None):
+def cnn(*, setup, radii, channels, activations, use_bias, rng=None, dtype=torch.float64):
     """Create CNN closure model (cnn.jl): a `torch.nn.Module` on the device of `setup`, callable as `m(x, θ)`.  `activations[i]` is a
-    callable or None (identity); `rng`: a `torch.Generator` (CPU) or an integer seed for the weights."""
+    callable or None (identity); `rng`: a `torch.Generator` (CPU) or an integer seed for the weights; `dtype`: the precision of the
+    parameters, and so of the arrays the model takes (torch.float64 or torch.float32)."""
     gen = rng
     if rng is not None and not isinstance(rng, torch.Generator):
         gen = torch.Generator().manual_seed(int(rng))
-    return CNN(setup.grid.dimension, list(radii), list(channels), activations, use_bias, gen).to(setup.device)
+    return CNN(setup.grid.dimension, list(radii), list(channels), activations, use_bias, gen, dtype).to(setup.device)
 
 
 class TensorClosure(torch.nn.Module):
@@ -358,26 +432,27 @@ def tensorclosure(*, setup, hidden, activation, rng=None, dtype=torch.float64):
 
 
 # ------------------------------------------------------------------------------------------------ training.jl
-def _as_tensor(a, device):
-    return torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a, dtype=torch.float64, device=device)
+def _as_tensor(a, device, dtype=None):
+    """`a` on `device`; `dtype=None`: float64."""
+    return torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a, dtype=dtype or torch.float64, device=device)
 
 
-def create_dataloader_prior(data, *, batchsize=50, device=None):
+def create_dataloader_prior(data, *, batchsize=50, device=None, dtype=None):
     """training.jl:1-23: `dataloader(rng) -> ((x, y), rng)`, a batch of `batchsize` random samples (sorted indices) on `device`.
-    `rng` is a `numpy.random.Generator`."""
+    `rng` is a `numpy.random.Generator`.  `dtype`: the precision of the batches (None: float64)."""
     x, y = data
     nsample = x.shape[-1]
 
     def dataloader(rng):
         i = np.sort(rng.permutation(nsample)[:batchsize])
-        return (_as_tensor(x[..., i], device), _as_tensor(y[..., i], device)), rng
+        return (_as_tensor(x[..., i], device, dtype), _as_tensor(y[..., i], device, dtype)), rng
 
     return dataloader
 
 
-def create_dataloader_post(trajectories, *, ntrajectory, nunroll, device=None):
+def create_dataloader_post(trajectories, *, ntrajectory, nunroll, device=None, dtype=None):
     """Create trajectory dataloader (training.jl:25-41): `ntrajectory` random trajectories, of each `nunroll + 1` consecutive states from a
-    random start."""
+    random start.  `dtype`: the precision of the states (None: float64); `t` stays a double array."""
 
     def dataloader(rng):
         data = []
@@ -388,7 +463,7 @@ def create_dataloader_post(trajectories, *, ntrajectory, nunroll, device=None):
                 raise ValueError(f"Trajectory too short for nunroll = {nunroll}")
             istart = int(rng.integers(0, nt - nunroll))
             it = slice(istart, istart + nunroll + 1)
-            data.append(dict(u=_as_tensor(u[..., it], device), t=t[it]))
+            data.append(dict(u=_as_tensor(u[..., it], device, dtype), t=t[it]))
         return data, rng
 
     return dataloader
@@ -457,7 +532,7 @@ def create_loss_post(*, setup, method, psolver, closure_model, nsubstep=1):
     """Create a-posteriori loss function (training.jl:120-146): unroll `ad.timestep` from the first state of every trajectory in the batch and
     average Σ|u − u_ref|² / Σ|u_ref|² (on `Iu`) over the following states.  Differentiable in θ.  With a Float32 pressure solver
     (`f32.psolver_spectral32`, `f32.psolver_wrap32`) the step is `ad32.timestep` on float32 fields (the trajectories are rounded to float32)."""
-    from . import autodiff32, f32
+    from . import autodiff32
 
     setup = _SetupView(setup, closure_model)
     inside = _inside(setup)
@@ -488,10 +563,28 @@ def create_loss_post(*, setup, method, psolver, closure_model, nsubstep=1):
 
 def create_relerr_post(*, data, setup, method, psolver, closure_model, nsubstep=1):
     """Create a-posteriori relative error (training.jl:148-180): θ -> mean over the trajectory of ‖u − u_ref‖ / ‖u_ref‖ (on `Iu`), the LES run
-    with the native mutating `timestep_`."""
+    with the native mutating `timestep_`.  With a Float32 pressure solver the fields are float32 and the step is `ad32.timestep` under
+    `torch.no_grad()`: the native Float32 stage loop runs the library's Smagorinsky closure only, not a torch closure."""
+    from . import autodiff32
+
     setup = _SetupView(setup, closure_model)
     inside = _inside(setup)
-    u, t = _as_tensor(data["u"], setup.device), np.asarray(data["t"])
+    single = isinstance(psolver, f32.psolver_spectral32)
+    u, t = _as_tensor(data["u"], setup.device, torch.float32 if single else None), np.asarray(data["t"])
+    if single:
+        def relerr_post32(θ):
+            with torch.no_grad():
+                stepper = create_stepper(method, setup=setup, psolver=psolver, u=f32.to_f32(setup, u[..., 0]), temp=None, t=float(t[0]))
+                e = 0.0
+                for it in range(1, len(t)):
+                    Δt = float(t[it] - t[it - 1]) / nsubstep
+                    for _ in range(nsubstep):
+                        stepper = autodiff32.timestep(method, stepper, Δt, θ)
+                    uref = u[..., it][inside]
+                    e += float(torch.linalg.vector_norm(stepper.u[inside] - uref) / torch.linalg.vector_norm(uref))
+                return e / (len(t) - 1)
+
+        return relerr_post32
     v = vectorfield(setup)
     cache = ode_method_cache(method, setup, psolver)
 
