@@ -46,6 +46,7 @@ extern "C" {
 
 typedef struct ins_grid ins_grid_t;       /* device copy of `setup.grid` metrics   (grid.jl:100-276)   */
 typedef struct ins_poisson ins_poisson_t; /* a `psolver` closure                   (pressure.jl:85-351) */
+typedef struct ins_rk_adjoint ins_rk_adjoint_t; /* work arrays of the reverse Runge-Kutta step (ins_rk_step_pullback_f64) */
 typedef struct ins_rk ins_rk_t;           /* `ode_method_cache` + stepper state    (time_stepper_caches.jl:34-49) */
 typedef struct ins_poisson32 ins_poisson32_t; /* `psolver_spectral` closure for T = Float32 */
 typedef struct ins_rk32 ins_rk32_t;           /* `ode_method_cache` for T = Float32 */
@@ -202,6 +203,19 @@ int ins_apply_bc_p_pullback_f64(const ins_grid_t* grid, double* phibar, void* st
 /* Pullback of project (pressure.jl:52-82), in place: φbar ← φbar − Dᵀ·Ω·poisson·bc_pᵀ·Gᵀ·φbar, the Poisson solve being its own
  * transpose (pressure.jl:15-19).  `pwork`: a scalar field of scratch.  Stream-ordered, like the solve (CG: blocking). */
 int ins_project_pullback_f64(const ins_grid_t* grid, ins_poisson_t* ps, double* phibar, double* pwork, void* stream);
+
+/* Pullback of one whole explicit Runge-Kutta step (step_explicit_runge_kutta.jl:4-59, closure_model = temp = nothing) with respect to the field it starts
+ * from: the reverse stage loop of a checkpointed rollout.  `A`, `c`: the shifted tableau as for ins_rk_create.  The handle owns nstage stage inputs v_i,
+ * nstage stage cotangents ȳ_i, one k̄ and one scalar of scratch.  A slab grid: INS_ERR_UNSUPPORTED. */
+int ins_rk_adjoint_create(const ins_grid_t* grid, ins_poisson_t* ps, int nstage, const double* A, const double* c, ins_rk_adjoint_t** out);
+int ins_rk_adjoint_destroy(ins_rk_adjoint_t* adj);
+/* `ustart`: the field the step started from (ghosts filled or not); `bodyforce`: the steady force of the forward (ins_rk_set_bodyforce) or NULL;
+ * `ubar`: on entry ∂L/∂u_out over the whole padded array, on return ∂L/∂ustart.  The call first recomputes the stage inputs v_i from ustart with the
+ * operator-level kernels (apply_bc_u!, momentum!, the combination, apply_bc_u!, project!), then sweeps the stages in reverse:
+ *   g = ubar;  for i = nstage-1 .. 0:  ȳ_i = bcᵀ Pᵀ bcᵀ g;  k̄_i = Δt Σ_{i' >= i} A[i',i] ȳ_{i'};  g = J(v_i)ᵀ k̄_i;   ubar = Σ_i ȳ_i + bcᵀ g.
+ * One combination pass writes k̄_i and the plain momentum pullback reads it; INS_ADJ_STAGE_FUSED=1 forms it inside the pullback kernel where the
+ * cotangent is loaded instead (up to 4 non-zero terms).  ubar == ustart: INS_ERR_INVALID.  Asynchronous on `stream` (CG solver: blocking). */
+int ins_rk_step_pullback_f64(ins_rk_adjoint_t* adj, double visc, const double* ustart, const double* bodyforce, double dt, double* ubar, void* stream);
 
 /* ---------------------------------------------------------------------------------- DNS-to-LES filters  (lib/NeuralClosure/src/filter.jl) */
 /* `les` and `dns` are two grids with the same boundary conditions, n_dns = comp·n_les interior volumes in every direction and nested faces

@@ -102,6 +102,9 @@ SIGNATURES = {
     "ins_apply_bc_u_pullback_f64": (C.c_int, [vp, vp, vp]),
     "ins_apply_bc_p_pullback_f64": (C.c_int, [vp, vp, vp]),
     "ins_project_pullback_f64": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ins_rk_adjoint_create": (C.c_int, [vp, vp, C.c_int, c_double_p, c_double_p, C.POINTER(vp)]),
+    "ins_rk_adjoint_destroy": (C.c_int, [vp]),
+    "ins_rk_step_pullback_f64": (C.c_int, [vp, C.c_double, vp, vp, C.c_double, vp, vp]),
     "ins_tensorbasis_pullback_f64": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp]),
     "ins_divoftensor_adjoint_f64": (C.c_int, [vp, vp, vp, vp]),
     "ins_tensorinvariants_f64": (C.c_int, [vp, vp, vp, vp]),

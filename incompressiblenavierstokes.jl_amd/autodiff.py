@@ -8,6 +8,10 @@ csrc/ins_adjoint.hip and csrc/ins_temp_adjoint.hip (the temperature equation, wh
     u = ad.timestep(method, stepper, Δt).u
     loss = (u * u).sum(); loss.backward()          # stepper.u.grad = ∂loss/∂u0
 
+`ad.timesteps(method, stepper, Δt, nsteps)` is `nsteps` of them as ONE Function for closure-free isothermal rollouts: the forward is the native
+multi-step call in chunks, only the chunk-start states are kept, and the backward recomputes a chunk and runs one native call per reversed step
+(csrc/ins_rk_adjoint.hip).
+
 A closure model given as a torch function `m(u, θ)` is added as F + m(u, θ), and its parameters get gradients from torch.
 """
 import numpy as np
@@ -20,7 +24,7 @@ from .setup import _fortran_strides, scalarfield, vectorfield
 from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
 
 __all__ = ["apply_bc_u", "apply_bc_p", "apply_bc_temp", "gravity", "convection_diffusion_temp", "dissipation", "scalewithvolume", "divergence", "pressuregradient", "applypressure", "poisson", "convection", "diffusion",
-           "momentum", "project", "right_hand_side", "create_right_hand_side", "timestep", "FaceAverage", "VolumeAverage", "tensorbasis", "divoftensor",
+           "momentum", "project", "right_hand_side", "create_right_hand_side", "timestep", "timesteps", "FaceAverage", "VolumeAverage", "tensorbasis", "divoftensor",
            "lastdimcontract", "tensorinvariants", "tensorclosure_stress", "apply_bc_p_fields", "smagorinsky_closure"]
 
 
@@ -682,3 +686,137 @@ def timestep(method, stepper, Δt, θ=None):
     if temp is not None:
         temp = apply_bc_temp(temp, t, setup)
     return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=t, n=n + 1)
+
+
+# ------------------------------------------------------------------------------------ checkpointed rollouts
+class _StepAdjoint:
+    """`ins_rk_adjoint_t` (csrc/ins_rk_adjoint.hip): the work arrays of the native reverse step, with the forward's native cache beside it."""
+
+    def __init__(self, erk, setup, psolver):
+        import ctypes as C
+
+        from . import _lib
+        from .time_steppers import ERKCache
+
+        self.erk, self.setup, self.cache = erk, setup, ERKCache(erk, setup, psolver)
+        A = np.ascontiguousarray(erk.A, dtype=np.float64)
+        c = np.ascontiguousarray(erk.c, dtype=np.float64)
+        self._handle = C.c_void_p()
+        _lib.call("ins_rk_adjoint_create", setup.handle, psolver.handle, len(erk.b), A.ctypes.data_as(_lib.c_double_p), c.ctypes.data_as(_lib.c_double_p),
+                  C.byref(self._handle))
+
+    def step_pullback_(self, ubar, ustart, Δt):
+        """ubar: ∂L/∂u_out -> ∂L/∂ustart, in place: the whole reverse sweep of one step is this one call."""
+        from . import _lib
+
+        setup = self.setup
+        f = setup.bodyforce if (setup.bodyforce is not None and setup.issteadybodyforce) else None
+        _lib.call("ins_rk_step_pullback_f64", self._handle, 1.0 / setup.Re, setup.ptr(ustart, True), setup.ptr(f, True) if f is not None else None, float(Δt),
+                  setup.ptr(ubar, True), setup.stream)
+        return ubar
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            try:
+                from . import _lib
+
+                _lib.load().ins_rk_adjoint_destroy(h)
+            except Exception:
+                pass
+
+
+def _step_adjoint(erk, setup, psolver):
+    """One `_StepAdjoint` per (solver, tableau), kept on the solver."""
+    key = (np.asarray(erk.A, dtype=np.float64).tobytes(), np.asarray(erk.c, dtype=np.float64).tobytes())
+    store = psolver.__dict__.setdefault("_ad_step_adjoints", {})
+    if key not in store:
+        store[key] = _StepAdjoint(erk, setup, psolver)
+    return store[key]
+
+
+def _native_steps_(adj, u, t, Δt, nsteps):
+    """`nsteps` native steps on `u`, in place (`timesteps_` = ins_rk_steps_f64; one step: ins_rk_step_f64)."""
+    from .time_steppers import timesteps_
+
+    setup, cache = adj.setup, adj.cache
+    timesteps_(adj.erk, create_stepper(adj.erk, setup=setup, psolver=cache.psolver, u=u, t=t), Δt, nsteps, cache=cache)
+    return u
+
+
+class _TimeSteps(torch.autograd.Function):
+    """u -> u after nsteps Runge-Kutta steps.  Saved: the state at the start of every chunk of `every` steps, nothing else."""
+
+    @staticmethod
+    def forward(ctx, u, adj, t, Δt, nsteps, every):
+        setup = adj.setup
+        out = _copy(setup, u, True)
+        ctx.adj, ctx.t, ctx.Δt, ctx.nsteps, ctx.every = adj, t, Δt, nsteps, every
+        ctx.checkpoints = []
+        for start in range(0, nsteps, every):
+            ctx.checkpoints.append(_copy(setup, out, True))
+            _native_steps_(adj, out, t + start * Δt, Δt, min(every, nsteps - start))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from .time_steppers import combine_
+
+        adj, Δt, nsteps, every = ctx.adj, ctx.Δt, ctx.nsteps, ctx.every
+        setup = adj.setup
+        ubar = _copy(setup, g, True)
+        bufs = [vectorfield(setup) for _ in range(min(every, nsteps) - 1)]  # the step-start states of one chunk after its checkpoint
+        starts = list(range(0, nsteps, every))
+        for q in reversed(range(len(starts))):
+            n = min(every, nsteps - starts[q])
+            states = [ctx.checkpoints[q]]
+            for j in range(1, n):
+                combine_(bufs[j - 1], states[j - 1], [], [], setup)  # a copy by the library's own pass
+                states.append(_native_steps_(adj, bufs[j - 1], ctx.t + (starts[q] + j - 1) * Δt, Δt, 1))
+            for j in reversed(range(n)):
+                adj.step_pullback_(ubar, states[j], Δt)
+            ctx.checkpoints[q] = None
+        return ubar, None, None, None, None, None
+
+
+def timesteps(method, stepper, Δt, nsteps, *, checkpoint_every=None):
+    """`nsteps` calls of `ad.timestep(method, ·, Δt)` as one Function: nothing is mutated, the result is differentiable in `stepper.u`.
+
+    The forward is the native multi-step loop (`timesteps_`, ins_rk_steps_f64) in chunks of `checkpoint_every` steps (default ceil(sqrt(nsteps)));
+    only the state at the start of every chunk is kept.  The backward walks the chunks in reverse: it recomputes the chunk's step-start states with the
+    native step and calls the native step pullback (ins_rk_step_pullback_f64) once per step.  Memory: ceil(nsteps/c) + c - 1 vector fields and the
+    2s + 1 work arrays of the reverse step, instead of the unrolled graph's ~10 fields per stage.
+
+    Scope: what the native isothermal loop runs — fp64, ExplicitRungeKuttaMethod or LMWray3, 2-D / 3-D, any boundary conditions with constant data, any
+    solver, no body force or a steady one.  Anything else raises NotImplementedError: use `ad.timestep` step by step."""
+    nsteps = int(nsteps)
+    if nsteps < 1:
+        raise ValueError(f"ad.timesteps: nsteps must be >= 1, got {nsteps}")
+    every = int(np.ceil(np.sqrt(nsteps))) if checkpoint_every is None else int(checkpoint_every)
+    if every < 1:
+        raise ValueError(f"ad.timesteps: checkpoint_every must be >= 1, got {checkpoint_every}")
+    setup, psolver, u = stepper.setup, stepper.psolver, stepper.u
+    if u.dtype != torch.float64:
+        raise TypeError("ad.timesteps: fields must be float64 torch tensors (the Float32 family has ad32.timestep)")
+    from .boundary_conditions import HaloBC
+
+    if setup.closure_model is not None:
+        raise NotImplementedError("ad.timesteps: a closure model is not part of the native reverse loop; use ad.timestep step by step")
+    if stepper.temp is not None or setup.temperature is not None:
+        raise NotImplementedError("ad.timesteps: the temperature equation is not part of the native reverse loop; use ad.timestep step by step")
+    if setup.needs_bc_planes:
+        raise NotImplementedError("ad.timesteps: callable Dirichlet data needs the host between the stages; use ad.timestep step by step")
+    if setup.bodyforce is not None and not setup.issteadybodyforce:
+        raise NotImplementedError("ad.timesteps: an unsteady body force is evaluated on the host; use ad.timestep step by step")
+    if any(isinstance(bc, HaloBC) for side in setup.boundary_conditions for bc in side):
+        raise NotImplementedError("ad.timesteps: slab (halo) setups are not supported; use ad.timestep step by step")
+    _check_f64(setup, u)
+    erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
+    adj = _step_adjoint(erk, setup, psolver)
+    t = float(stepper.t)
+    if torch.is_grad_enabled() and u.requires_grad:
+        out = _TimeSteps.apply(u, adj, t, float(Δt), nsteps, min(every, nsteps))
+    else:  # nothing to save: one native call
+        out = _native_steps_(adj, _copy(setup, u, True), t, float(Δt), nsteps)
+    return create_stepper(method, setup=setup, psolver=psolver, u=out, temp=None, t=t + nsteps * erk.c[-1] * Δt, n=stepper.n + nsteps)

@@ -42,8 +42,18 @@ __device__ __forceinline__ double at(const double (&W)[3][3][3], int q, int dx, 
   return dx == 1 ? next_h(v, 0.0) : dx == -1 ? prev_h(v, 0.0) : v;
 }
 
-template <bool ACC>
-__global__ __launch_bounds__(64 * ADJ_NW) void k_momentum_pullback_tiled(AdjTiledArgs a) {
+// The cotangent at linear index idx of the vector field: a.phi[idx], or, with one more kernel argument, the combination of ins_adjoint_kernels.h
+// (PhiComb) formed at this one load site.
+template <typename... PC>
+__device__ __forceinline__ double tiled_phi(const AdjTiledArgs& a, long long idx, const PC&... pc) {
+  if constexpr (sizeof...(PC) == 0)
+    return a.phi[idx];
+  else
+    return (PhiCombAt<double, INS_ADJ_COMB_MAX>{pc, 0}[idx], ...);
+}
+
+template <bool ACC, typename... PC>
+__global__ __launch_bounds__(64 * ADJ_NW) void k_momentum_pullback_tiled(AdjTiledArgs a, PC... pc) {
   const int nty_local = (a.nty + 7) >> 3;
   int seq = (int)(blockIdx.x >> 3);
   if (seq >= a.ntx * nty_local * a.nzc) return;
@@ -72,7 +82,7 @@ __global__ __launch_bounds__(64 * ADJ_NW) void k_momentum_pullback_tiled(AdjTile
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
         U[q][dy][slot] = ok ? a.u[q * a.sc + c] : 0.0;
-        F[q][dy][slot] = okp ? a.phi[q * a.sc + c] : 0.0;
+        F[q][dy][slot] = okp ? tiled_phi(a, q * a.sc + c, pc...) : 0.0;
       }
     }
   };
@@ -142,7 +152,8 @@ bool adj_tiled_supported(const ins_grid* G) {
   return G->g.D == 3 && G->all_periodic && G->all_dof && G->uniform_exact && !ins_opt(OPT_INS_DISABLE_ADJ_TILED);
 }
 
-int launch_momentum_pullback_tiled(const ins_grid* G, double visc, const double* u, const double* phi, double* ubar, bool acc, hipStream_t s) {
+int launch_momentum_pullback_tiled(const ins_grid* G, double visc, const double* u, const double* phi, double* ubar, bool acc, hipStream_t s,
+                                   const PhiComb<double, INS_ADJ_COMB_MAX>* comb = nullptr) {
   const GridDev& g = G->g;
   const ins_grid_desc_t& d = G->desc;  // host copy of the tables
   AdjTiledArgs a;
@@ -169,7 +180,9 @@ int launch_momentum_pullback_tiled(const ins_grid* G, double visc, const double*
   a.zc = ADJ_ZC;
   a.nzc = (int)cdiv(a.N2, ADJ_ZC);
   const unsigned nb = (unsigned)(8LL * a.ntx * ((a.nty + 7) / 8) * a.nzc);
-  if (acc)
+  if (comb)
+    hipLaunchKernelGGL((k_momentum_pullback_tiled<false, PhiComb<double, INS_ADJ_COMB_MAX>>), dim3(nb), dim3(64, ADJ_NW), 0, s, a, *comb);
+  else if (acc)
     hipLaunchKernelGGL(k_momentum_pullback_tiled<true>, dim3(nb), dim3(64, ADJ_NW), 0, s, a);
   else
     hipLaunchKernelGGL(k_momentum_pullback_tiled<false>, dim3(nb), dim3(64, ADJ_NW), 0, s, a);
@@ -211,6 +224,24 @@ int ins_k_apply_bc_p_pullback(const ins_grid* G, double* p, hipStream_t s) {
     if ((l == INS_BC_DIRICHLET || l == INS_BC_HALO) && (r == INS_BC_DIRICHLET || r == INS_BC_HALO)) continue;
     INS_LAUNCH_D((k_bc_p_pullback<D, double>), line_launch(g, be, 1), s, g, p, be);
   }
+  return INS_OK;
+}
+
+// ubar = J(u)ᵀ (Σ_q coefs[q]·ks[q]), 1 <= nterms <= INS_ADJ_COMB_MAX: the momentum pullback with the cotangent combined where it is loaded
+// (the reverse Runge-Kutta stage, ins_rk_adjoint.hip).  Same dispatch as ins_momentum_pullback_f64.
+int ins_k_momentum_pullback_comb(const ins_grid* G, double visc, const double* u, int nterms, const double* coefs, const double* const* ks, double* ubar,
+                                 hipStream_t s) {
+  INS_REQUIRE(nterms >= 1 && nterms <= INS_ADJ_COMB_MAX, "bad number of cotangent terms");
+  PhiComb<double, INS_ADJ_COMB_MAX> pc;
+  pc.n = nterms;
+  for (int q = 0; q < INS_ADJ_COMB_MAX; ++q) {
+    pc.p[q] = q < nterms ? ks[q] : nullptr;
+    pc.w[q] = q < nterms ? coefs[q] : 0.0;
+  }
+  if (adj_tiled_supported(G)) return launch_momentum_pullback_tiled(G, visc, u, nullptr, ubar, false, s, &pc);
+  const GridDev& g = G->g;
+  const Launch3 l = box_launch(g.D, g.N);
+  INS_LAUNCH_D((k_convdiff_adjoint<D, double, 3, false, PhiComb<double, INS_ADJ_COMB_MAX>>), l, s, g, visc, u, pc, ubar);
   return INS_OK;
 }
 

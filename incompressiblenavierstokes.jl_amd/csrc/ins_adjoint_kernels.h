@@ -74,8 +74,8 @@ __device__ __forceinline__ T rr(const GridDev& g, int al, int be, int ib) {
 }
 
 // ψαβ(f) at f = (f0, f1, f2) (linear index cf); `live` = it has a DOF term
-template <int D, typename T>
-__device__ __forceinline__ T psi(const GridDev& g, int al, int be, const int (&F)[3], long long cf, const T* __restrict__ phia, bool& live) {
+template <int D, typename T, typename PA>
+__device__ __forceinline__ T psi(const GridDev& g, int al, int be, const int (&F)[3], long long cf, PA phia, bool& live) {
   const bool d0 = dof<D>(g, al, F[0], F[1], F[2]);
   const bool d1 = dof<D>(g, al, INS_SH(F, be, 1));
   live = d0 || d1;
@@ -85,13 +85,58 @@ __device__ __forceinline__ T psi(const GridDev& g, int al, int be, const int (&F
   return v;
 }
 
-template <int D, typename T, int MODE, bool ACC>
-__global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, T visc, const T* __restrict__ u, const T* __restrict__ phi, T* __restrict__ ubar) {
+// The cotangent φ is read through phi_comp(φ, component offset)[volume]: an array (const T*), or a PhiComb, the combination Σ_q w[q]·p[q] of up to
+// S arrays formed where it is read.  The reverse Runge-Kutta stage (ins_rk_adjoint.hip) takes the second: its φ is k̄_i = Δt Σ_{i'≥i} A[i',i] ȳ_{i'},
+// which then is never written to memory (one write and one read of a vector field less per stage; the stencil's repeated reads hit the cache, but
+// re-forming the sum at every stencil point costs more than the traffic saved: opt-in, INS_ADJ_STAGE_FUSED=1).
+constexpr int INS_ADJ_COMB_MAX = 4;  // arrays of a combined cotangent in the instantiations (RK44's first reverse stage has 4); longer sums go through memory
+
+template <typename T, int S>
+struct PhiComb {
+  const T* p[S];
+  T w[S];
+  int n;
+};
+
+template <typename T, int S>
+struct PhiCombAt {
+  const PhiComb<T, S>& a;
+  long long off;
+  __device__ __forceinline__ T operator[](long long idx) const {
+    T v = T(0);
+#pragma unroll
+    for (int q = 0; q < S; ++q)
+      if (q < a.n) v += a.w[q] * a.p[q][off + idx];
+    return v;
+  }
+};
+
+template <typename T>
+__device__ __forceinline__ const T* phi_comp(const T* phi, long long off) {
+  return phi + off;
+}
+template <typename T, int S>
+__device__ __forceinline__ PhiCombAt<T, S> phi_comp(const PhiComb<T, S>& phi, long long off) {
+  return PhiCombAt<T, S>{phi, off};
+}
+
+// the kernel parameter of a cotangent source: a restrict-qualified pointer, as before the source became a template parameter, or the PhiComb by value
+template <typename Phi>
+struct PhiParam {
+  using type = Phi;
+};
+template <typename T>
+struct PhiParam<const T*> {
+  using type = const T* __restrict__;
+};
+
+template <int D, typename T, int MODE, bool ACC, typename Phi = const T*>
+__global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, T visc, const T* __restrict__ u, typename PhiParam<Phi>::type phi, T* __restrict__ ubar) {
   INS_VOL_INDEX(g.sx, 0, 0, 0, i >= g.N[0] || j >= g.N[1]);
 
 #pragma unroll
   for (int ga = 0; ga < D; ++ga) {
-    const T* pg = phi + ga * g.sc;
+    const auto pg = phi_comp(phi, ga * g.sc);
     T v = T(0);
     if (MODE & 2) {
       const bool dx = dof<D>(g, ga, i, j, k);
@@ -138,7 +183,7 @@ __global__ __launch_bounds__(256) void k_convdiff_adjoint(GridDev g, T visc, con
       for (int al = 0; al < D; ++al) {
         const long long sa = g.sx[al];
         const T* ua = u + al * g.sc;
-        const T* pa = phi + al * g.sc;
+        const auto pa = phi_comp(phi, al * g.sc);
         const double* A1 = g.A1[ga][al];
         const double* A2 = g.A2[ga][al];
         {

@@ -146,6 +146,7 @@ void ins_set_error(const char* fmt, ...);
   X(INS_DISABLE_TEMP32_STAGE)    \
   X(INS_FFT_ALLOW_RESET)         \
   X(INS_DISABLE_ADJ_TILED)     \
+  X(INS_ADJ_STAGE_FUSED)       \
   X(INS_DISABLE_FILTER_TILED)
 #define INS_OPT_ENUM(id) OPT_##id,
 enum InsOptId { INS_OPT_LIST(INS_OPT_ENUM) INS_OPT_COUNT };
