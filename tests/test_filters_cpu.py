@@ -50,6 +50,38 @@ def test_face_average_inverts_reconstruct(oracle, D, n_les, comp):
         assert np.max(np.abs(back[sl] - w[sl])) <= 4 * EPS * np.max(np.abs(w))
 
 
+def _dense_transpose_apply(L, shape, w):
+    """(dL)ᵀ w of a linear map L on numpy fields of `shape`, by unit probes (as tests/test_gpu_adjoint.py)."""
+    n = int(np.prod(shape))
+    out = np.empty(n)
+    e = np.zeros(n)
+    for k in range(n):
+        e[k] = 1.0
+        out[k] = np.sum(w * L(e.reshape(shape, order="F")))
+        e[k] = 0.0
+    return out.reshape(shape, order="F")
+
+
+@pytest.mark.parametrize("n_les,comp", [((3, 2, 2), 2), ((3, 2, 2), 3), ((4, 3), 4)])
+@pytest.mark.parametrize("kind", ["face", "volume"])
+def test_scatter_pullbacks_are_the_dense_transposes(oracle, kind, n_les, comp):
+    """Every value of the scatter restatements against the transpose of the forward restatement.  A fine volume receives at most two coarse
+    cotangents (the shared plane of an even volume average), each w / count against w · (1 / count): two roundings of terms ≤ max|w| each."""
+    D = len(n_les)
+    les = setup_periodic(oracle, n_les, D)
+    shape_dns = tuple(comp * n + 2 for n in n_les) + (D,)
+    rng = np.random.default_rng(17)
+    w = np.asfortranarray(rng.standard_normal(tuple(les.grid.N) + (D,)))  # non-zero in the ghost volumes: the pullbacks must not read them
+    if kind == "face":
+        got = fr.face_average_pullback(w, les.grid.Iu, shape_dns[:-1], comp)
+        ref = _dense_transpose_apply(lambda u: fr.face_average(u, les.grid.Iu, les.grid.N, comp), shape_dns, w)
+    else:
+        got = fr.volume_average_pullback(w, n_les, comp)
+        ref = _dense_transpose_apply(lambda u: fr.volume_average(u, n_les, comp), shape_dns, w)
+    assert got.shape == ref.shape and np.any(ref != 0)
+    assert np.max(np.abs(got - ref)) <= 4 * EPS * np.max(np.abs(w))
+
+
 def test_subdivide_is_nested():
     x = np.array([0.0, 0.1, 0.35, 1.0])
     for comp in (1, 2, 3):

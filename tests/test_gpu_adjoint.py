@@ -92,6 +92,11 @@ def solvers(ins, sp, name):
 @pytest.mark.parametrize("name", list(GEOMS))
 def test_linear_transposes(ins, oracle, name):
     sp = mirror(ins, GEOMS[name](oracle), oracle)
+    check_linear_transposes(ins, sp, solvers(ins, sp, name))
+
+
+def check_linear_transposes(ins, sp, pss):
+    """Every linear pullback of setup `sp`; the Poisson solve and the projection on each solver of `pss`."""
     z = ins.vectorfield(sp)
     v, w = rand(ins, sp, True, 1), rand(ins, sp, True, 2)
     p, q = rand(ins, sp, False, 3), rand(ins, sp, False, 4)
@@ -114,7 +119,7 @@ def test_linear_transposes(ins, oracle, name):
     lhs = dot(out.detach(), w)
     assert abs(lhs - dot(ub, v) - dot(pb, p)) <= TOL * nrm(out.detach()) * nrm(w)
     # the Poisson solve and the projection
-    for ps in solvers(ins, sp, name):
+    for ps in pss:
         check_transpose(ps(ins.copyfield(p)), p, q, ps(ins.copyfield(q)))
         Pv = ins.project_(ins.copyfield(v), sp, ps, ins.scalarfield(sp))
         check_transpose(Pv, v, w, ins.project_pullback_(ins.copyfield(w), sp, ps, ins.scalarfield(sp)))
@@ -133,7 +138,10 @@ def test_project_transpose_cg(ins, oracle):
 # ------------------------------------------------------------------------------------ 2. quadratic operators
 @pytest.mark.parametrize("name", list(GEOMS))
 def test_convection_and_momentum_pullbacks(ins, oracle, name):
-    sp = mirror(ins, GEOMS[name](oracle), oracle)
+    check_convection_and_momentum_pullbacks(ins, mirror(ins, GEOMS[name](oracle), oracle))
+
+
+def check_convection_and_momentum_pullbacks(ins, sp):
     u, v, w = rand(ins, sp, True, 7), rand(ins, sp, True, 8), rand(ins, sp, True, 9)
     Jv = (ins.convection(u + v, sp) - ins.convection(u - v, sp)) / 2
     ub = ins.convection_adjoint_(ins.vectorfield(sp), w, u, sp)
@@ -191,13 +199,21 @@ def test_pullbacks_match_oracle_transposes(ins, oracle, name):
     o = oracle
     so = GEOMS[name](o)
     sp = mirror(ins, so, o)
+    for what, L, shape, cot, got in oracle_transpose_cases(ins, o, so, sp):
+        ref = dense_transpose_apply(L, shape, cot)
+        err = relmax(ins.to_numpy(got), ref)
+        assert err <= TOL, (what, err)
+
+
+def oracle_transpose_cases(ins, o, so, sp):
+    """(name, the oracle's linear map L, shape of its argument, cotangent, the library's L^T cotangent) of every pullback that has an oracle forward"""
     N, D = tuple(so.grid.N), so.grid.D
     vs, ss = N + (D,), N
     u = fx.randn_field(vs, 20)
     w, q = fx.randn_field(vs, 21), fx.randn_field(ss, 22)
     ug, wg, qg = ins.from_numpy(sp, u), ins.from_numpy(sp, w), ins.from_numpy(sp, q)
     z, zs = np.zeros(vs, order="F"), np.zeros(ss, order="F")
-    cases = [
+    return [
         ("divergence", lambda x: o.divergence(x, so), vs, q, ins.divergence_adjoint_(ins.vectorfield(sp), qg, sp)),
         ("pressuregradient", lambda x: o.pressuregradient(x, so), ss, w, ins.pressuregradient_adjoint_(ins.scalarfield(sp), wg, sp)),
         ("diffusion", lambda x: o.diffusion(x, so), vs, w, ins.diffusion_adjoint_(ins.vectorfield(sp), wg, sp)),
@@ -208,10 +224,6 @@ def test_pullbacks_match_oracle_transposes(ins, oracle, name):
         ("apply_bc_p", lambda x: o.apply_bc_p(x, 0.0, so) - o.apply_bc_p(zs, 0.0, so), ss, q,
          ins.apply_bc_p_pullback_(ins.copyfield(qg), 0.0, sp)),
     ]
-    for what, L, shape, cot, got in cases:
-        ref = dense_transpose_apply(L, shape, cot)
-        err = relmax(ins.to_numpy(got), ref)
-        assert err <= TOL, (what, err)
 
 
 # ------------------------------------------------------------------------------------ 4. torch.autograd

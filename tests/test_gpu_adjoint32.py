@@ -162,8 +162,12 @@ def report(name, what, err, yard):
 # ------------------------------------------------------------------------------------ 1. transpose identities
 @pytest.mark.parametrize("name", list(GEOMS))
 def test_transpose_identities(ins, oracle, name):
+    check_transpose_identities(ins, mirror(ins, GEOMS[name](oracle), oracle), name)
+
+
+def check_transpose_identities(ins, sp, name):
+    """`name` labels the printed figures; a name that starts with "periodic32" adds the spectral solver pair (solver_pairs)."""
     F = ins.f32
-    sp = mirror(ins, GEOMS[name](oracle), oracle)
     D = sp.grid.dimension
     v32, v64 = pair(ins, sp, True, 1)
     w32, w64 = pair(ins, sp, True, 2)
@@ -207,8 +211,11 @@ def test_transpose_identities(ins, oracle, name):
 # ------------------------------------------------------------------------------------ 2. values against the fp64 twins
 @pytest.mark.parametrize("name", list(GEOMS))
 def test_values_against_fp64(ins, oracle, name):
+    check_values_against_fp64(ins, mirror(ins, GEOMS[name](oracle), oracle), name)
+
+
+def check_values_against_fp64(ins, sp, name):
     F = ins.f32
-    sp = mirror(ins, GEOMS[name](oracle), oracle)
     D = sp.grid.dimension
     u32, u64 = pair(ins, sp, True, 11)
     w32, w64 = pair(ins, sp, True, 12)

@@ -2,7 +2,11 @@
 
 Tolerance.  A mean of n terms summed in one order differs from the same mean summed in another order by at most 2·n·eps·max|u|
 (each of the ≤ n − 1 additions of either order rounds a partial sum of magnitude ≤ n·max|u| by eps/2, then one division): n = comp^(D−1)
-for the face average, (comp + 1)·comp^(D−1) for the volume average.  Nothing here is tuned to what the kernels give."""
+for the face average, (comp + 1)·comp^(D−1) for the volume average.  Nothing here is tuned to what the kernels give.
+
+Shapes.  Cubes with one spacing hide a swap of two directions, so section 3b repeats the value-by-value checks on boxes with three different sizes
+and lengths whose fine width sits at the edges of the 64-wide x tile, and section 4 checks every value of the pullbacks and of reconstruct there
+against the scatter restatements of tests/filter_ref.py (pinned to the dense transposes by tests/test_filters_cpu.py)."""
 import numpy as np
 import pytest
 
@@ -28,7 +32,11 @@ def ins():
 
 
 def periodic(ins, n, D, L=1.0):
-    return ins.Setup(x=tuple(np.linspace(0.0, L, n + 1) for _ in range(D)), Re=1000.0)
+    """`n` and `L`: one value for every direction, or one per direction."""
+    n = (n,) * D if isinstance(n, int) else tuple(n)
+    L = (L,) * D if isinstance(L, (int, float)) else tuple(L)
+    assert len(n) == D and len(L) == D
+    return ins.Setup(x=tuple(np.linspace(0.0, Li, ni + 1) for ni, Li in zip(n, L)), Re=1000.0)
 
 
 def randf(ins, sp, seed):
@@ -76,23 +84,27 @@ def test_filters_match_restatement(ins, kind, D, n_les, comp):
     check_filter(ins, kind, les, dns, comp, seed=comp)
 
 
-@pytest.mark.parametrize("comp", [1, 2, 3, 4, 8])
-@pytest.mark.parametrize("D,n_les", [(2, 12), (3, 6)])
-def test_reconstruct_matches_restatement(ins, D, n_les, comp):
-    les, dns = periodic(ins, n_les, D), periodic(ins, n_les * comp, D)
+def check_reconstruct(ins, les, dns, comp):
     v = ins.apply_bc_u(randf(ins, les, 5), 0.0, les)
     u = ins.vectorfield(dns)
     u.fill_(SENTINEL)
     ins.reconstruct_(u, v, dns, les, comp)
     got = ins.to_numpy(u)
     ref = np.full_like(got, SENTINEL)
-    fr.reconstruct(ins.to_numpy(v), (n_les,) * D, comp, out=ref)
+    fr.reconstruct(ins.to_numpy(v), tuple(n - 2 for n in les.grid.N), comp, out=ref)
     inner = tuple(slice(1, n - 1) for n in dns.grid.N)
     mask = np.zeros(got.shape, dtype=bool)
     mask[inner] = True
     assert np.all(got[~mask] == SENTINEL)
     # two products and one sum of terms ≤ comp·max|v|, then a division: well inside 2·2·eps·max|v|·comp / comp
     assert np.max(np.abs(got[mask] - ref[mask])) <= bound(2, np.max(np.abs(ins.to_numpy(v))))
+
+
+@pytest.mark.parametrize("comp", [1, 2, 3, 4, 8])
+@pytest.mark.parametrize("D,n_les", [(2, 12), (3, 6)])
+def test_reconstruct_matches_restatement(ins, D, n_les, comp):
+    les, dns = periodic(ins, n_les, D), periodic(ins, n_les * comp, D)
+    check_reconstruct(ins, les, dns, comp)
 
 
 @pytest.mark.parametrize("comp", [1, 2, 3])
@@ -148,6 +160,10 @@ def test_identities_on_device(ins, D, n_les, comp):
 def test_tiled_matches_generic(ins, kind, n_dns, n_les):
     comp = n_dns // n_les
     les, dns = periodic(ins, n_les, 3), periodic(ins, n_dns, 3)
+    check_tiled_matches_generic(ins, kind, les, dns, comp)
+
+
+def check_tiled_matches_generic(ins, kind, les, dns, comp):
     u = randf(ins, dns, 21)
     Φ = ins.FaceAverage() if kind == "face" else ins.VolumeAverage()
     out = {}
@@ -159,11 +175,12 @@ def test_tiled_matches_generic(ins, kind, n_dns, n_les):
     inner = tuple(slice(1, n - 1) for n in les.grid.N)
     err = float((out[0] - out[1])[inner].abs().max())
     b = bound(nterms(kind, comp, 3), float(u.abs().max()))
-    print(f"{kind} {n_dns}^3 -> {n_les}^3: tiled - generic max {err:.3e}, bound {b:.3e}")
+    print(f"{kind} {tuple(dns.grid.N)} -> {tuple(les.grid.N)}: tiled - generic max {err:.3e}, bound {b:.3e}")
     assert err <= b
     ghosts = out[0].clone()
     ghosts[inner] = SENTINEL
     assert bool((ghosts == SENTINEL).all())
+    return out
 
 
 @pytest.mark.parametrize("case", ["odd_comp", "two_d", "walls"])
@@ -182,6 +199,43 @@ def test_sizes_the_tiled_kernel_refuses(ins, oracle, case):
     assert np.array_equal(ref, again)
 
 
+# ------------------------------------------------------------------------------------ 3b. anisotropic boxes at the edges of the x tile
+# Three different sizes and three different lengths per box, so a y / z swap of a wrap length, a stride or a window changes the result.  The fp64
+# tile is 64 fine x-volumes (the Float32 one 128, tests/test_gpu_filters32.py).  (comp, n_les): n_dns = comp · n_les.
+ANISO_L = (1.0, 0.7, 1.9)
+ANISO_CASES = [
+    (8, (8, 5, 2)),   # n_dns0 = 64: exactly one tile, the x halo of the last volume-average output wraps to fine index 1; 4 + 1 coarse rows
+    (8, (9, 3, 3)),   # 72: a tile plus one coarse output
+    (4, (18, 5, 3)),  # 72: a tile plus two outputs
+    (2, (36, 5, 3)),  # comp 2: the volume average is tiled, the fp64 face average generic
+    (3, (24, 5, 3)),  # odd comp: the generic kernel across an x seam of its 64-wide launch
+]
+
+
+def aniso(ins, comp, n_les):
+    D = len(n_les)
+    return periodic(ins, n_les, D, ANISO_L[:D]), periodic(ins, tuple(comp * n for n in n_les), D, ANISO_L[:D])
+
+
+def tiled_route(kind, comp, D=3, face2=False):
+    """csrc/ins_filter_kernels.h tiled_supported: `face2` is the Float32 face average at comp 2."""
+    return D == 3 and (comp in (4, 8) or (comp == 2 and (kind == "volume" or face2)))
+
+
+@pytest.mark.parametrize("comp,n_les", ANISO_CASES)
+@pytest.mark.parametrize("kind", ["face", "volume"])
+def test_anisotropic_tile_edges_match_restatement(ins, kind, comp, n_les):
+    les, dns = aniso(ins, comp, n_les)
+    assert tuple(dns.grid.N) == tuple(comp * n + 2 for n in n_les)
+    got = check_filter(ins, kind, les, dns, comp, seed=40 + comp)
+    with ins._lib.options(INS_DISABLE_FILTER_TILED=1):
+        generic = check_filter(ins, kind, les, dns, comp, seed=40 + comp)
+    if tiled_route(kind, comp):
+        check_tiled_matches_generic(ins, kind, les, dns, comp)
+    else:  # the switch must change nothing where no tiled kernel serves
+        assert np.array_equal(got, generic)
+
+
 # ------------------------------------------------------------------------------------ 4. transposes and autograd
 @pytest.mark.parametrize("comp", [1, 2, 3, 4])
 @pytest.mark.parametrize("D,n_les", [(2, 8), (3, 4)])
@@ -196,6 +250,40 @@ def test_pullbacks_are_transposes(ins, kind, D, n_les, comp):
     Φ.pullback_(ΦTw, w, les, comp, dns)
     lhs, rhs = dot(Φu, w), dot(u, ΦTw)
     assert abs(lhs - rhs) <= TOL * nrm(Φu) * nrm(w), (lhs, rhs)
+
+
+PULLBACK_CASES = [(c, n) for c, n in ANISO_CASES if c in (2, 3, 4)] + [(4, (33, 5))]  # 2-D: n_dns0 = 132, three x tiles of the 64-wide launch
+
+
+def scatter_pullback(kind, wn, les, dns, comp):
+    if kind == "face":
+        return fr.face_average_pullback(wn, les.grid.Iu, dns.grid.N, comp)
+    return fr.volume_average_pullback(wn, tuple(n - 2 for n in les.grid.N), comp)
+
+
+@pytest.mark.parametrize("comp,n_les", PULLBACK_CASES)
+@pytest.mark.parametrize("kind", ["face", "volume"])
+def test_pullbacks_match_scatter_restatement(ins, kind, comp, n_les):
+    """Every value of the whole padded fine cotangent.  A fine volume receives at most nterms / comp^D ≤ nterms contributions w / count, so the
+    bound of a sum of nterms terms of size max|w| holds."""
+    les, dns = aniso(ins, comp, n_les)
+    D = len(n_les)
+    Φ = ins.FaceAverage() if kind == "face" else ins.VolumeAverage()
+    w = randf(ins, les, 50 + comp)  # non-zero in the coarse ghost volumes
+    ΦTw = ins.vectorfield(dns)
+    ΦTw.fill_(SENTINEL)  # the pullback overwrites the whole padded array
+    Φ.pullback_(ΦTw, w, les, comp, dns)
+    got, wn = ins.to_numpy(ΦTw), ins.to_numpy(w)
+    ref = scatter_pullback(kind, wn, les, dns, comp)
+    err, b = np.max(np.abs(got - ref)), bound(nterms(kind, comp, D), np.max(np.abs(wn)))
+    print(f"{kind} pullback D={D} comp={comp} N_les={tuple(les.grid.N)}: max err {err:.3e}, bound {b:.3e}")
+    assert np.max(np.abs(ref)) > 0 and err <= b
+
+
+@pytest.mark.parametrize("comp,n_les", [(c, n) for c, n in ANISO_CASES if c in (3, 4)])
+def test_reconstruct_on_anisotropic_boxes(ins, comp, n_les):
+    les, dns = aniso(ins, comp, n_les)
+    check_reconstruct(ins, les, dns, comp)
 
 
 def test_face_pullback_on_mixed_bc_grid(ins, oracle):

@@ -10,6 +10,7 @@ import pytest
 from tests import filter_ref as fr
 from tests import fixtures as fx
 from tests.test_gpu_adjoint import mirror
+from tests.test_gpu_filters import ANISO_CASES, PULLBACK_CASES, aniso, periodic, scatter_pullback, tiled_route
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +27,6 @@ def ins():
     import ins_amd
 
     return ins_amd
-
-
-def periodic(ins, n, D, L=1.0):
-    return ins.Setup(x=tuple(np.linspace(0.0, L, n + 1) for _ in range(D)), Re=1000.0)
 
 
 def randf32(ins, sp, seed):
@@ -91,16 +88,20 @@ def test_filters_match_restatement(ins, kind, D, n_les, comp):
 @pytest.mark.parametrize("comp", [1, 2, 3, 4, 8])
 @pytest.mark.parametrize("D,n_les", [(2, 12), (3, 6)])
 def test_reconstruct_matches_restatement(ins, D, n_les, comp):
+    les, dns = periodic(ins, n_les, D), periodic(ins, n_les * comp, D)
+    check_reconstruct(ins, les, dns, comp)
+
+
+def check_reconstruct(ins, les, dns, comp):
     import torch
 
-    les, dns = periodic(ins, n_les, D), periodic(ins, n_les * comp, D)
     v = ins.f32.apply_bc_u32_(randf32(ins, les, 5), les)
     u = ins.f32.vectorfield32(dns)
     u.fill_(SENTINEL)
     ins.reconstruct_(u, v, dns, les, comp)
     got, vn = wide(u), wide(v)
     ref = np.full_like(got, SENTINEL)
-    fr.reconstruct(vn, (n_les,) * D, comp, out=ref)
+    fr.reconstruct(vn, tuple(n - 2 for n in les.grid.N), comp, out=ref)
     mask = np.zeros(got.shape, dtype=bool)
     mask[tuple(slice(1, n - 1) for n in dns.grid.N)] = True
     assert np.all(got[~mask] == SENTINEL), "reconstruct wrote outside the fine interior"
@@ -144,6 +145,10 @@ def test_face_average_on_wall_bounded_and_stretched_grids(ins, oracle, name, com
 def test_tiled_matches_generic(ins, kind, n_dns, n_les):
     comp = n_dns // n_les
     les, dns = periodic(ins, n_les, 3), periodic(ins, n_dns, 3)
+    check_tiled_matches_generic(ins, kind, les, dns, comp)
+
+
+def check_tiled_matches_generic(ins, kind, les, dns, comp):
     u = randf32(ins, dns, 21)
     out = {}
     for off in (0, 1):
@@ -154,12 +159,40 @@ def test_tiled_matches_generic(ins, kind, n_dns, n_les):
     inner = tuple(slice(1, n - 1) for n in les.grid.N)
     err = float((out[0].double() - out[1].double())[inner].abs().max())
     b = EPS32 * float(u.abs().max())
-    print(f"f32 {kind} {n_dns}^3 -> {n_les}^3: tiled - generic max {err:.3e}, bound {b:.3e}")
+    print(f"f32 {kind} {tuple(dns.grid.N)} -> {tuple(les.grid.N)}: tiled - generic max {err:.3e}, bound {b:.3e}")
     assert err <= b
     for o in out.values():
         ghosts = o.clone()
         ghosts[inner] = SENTINEL
         assert bool((ghosts == SENTINEL).all())
+
+
+# ------------------------------------------------------------------------------------ 4b. anisotropic boxes at the edges of the x tile
+# The cases of tests/test_gpu_filters.py (the fp64 tile of 64 fine x-volumes) and the float tile of 128 (two volumes per lane).
+ANISO32_CASES = ANISO_CASES + [
+    (4, (32, 5, 2)),  # n_dns0 = 128: exactly one float tile, the x halo of the last volume-average output wraps to fine index 1
+    (8, (17, 3, 2)),  # 136: a tile plus one coarse output
+    (2, (68, 5, 3)),  # 136: the float face average at comp 2 is tiled
+]
+
+
+@pytest.mark.parametrize("comp,n_les", ANISO32_CASES)
+@pytest.mark.parametrize("kind", ["face", "volume"])
+def test_anisotropic_tile_edges_match_restatement(ins, kind, comp, n_les):
+    les, dns = aniso(ins, comp, n_les)
+    got = check_filter(ins, kind, les, dns, comp, seed=40 + comp)
+    with ins._lib.options(INS_DISABLE_FILTER_TILED=1):
+        generic = check_filter(ins, kind, les, dns, comp, seed=40 + comp)
+    if tiled_route(kind, comp, face2=True):
+        check_tiled_matches_generic(ins, kind, les, dns, comp)
+    else:  # the switch must change nothing where no tiled kernel serves
+        assert np.array_equal(got, generic)
+
+
+@pytest.mark.parametrize("comp,n_les", [(c, n) for c, n in ANISO32_CASES if c in (3, 4)])
+def test_reconstruct_on_anisotropic_boxes(ins, comp, n_les):
+    les, dns = aniso(ins, comp, n_les)
+    check_reconstruct(ins, les, dns, comp)
 
 
 # ------------------------------------------------------------------------------------ 5. transposes
@@ -189,6 +222,26 @@ def test_pullbacks_are_transposes(ins, kind, D, n_les, comp):
         g = wide(ΦTw)
         g[tuple(slice(1, n - 1) for n in dns.grid.N)] = 0.0
         assert not g.any()
+
+
+PULLBACK32_CASES = PULLBACK_CASES + [(c, n) for c, n in ANISO32_CASES[len(ANISO_CASES):] if c in (2, 4)]
+
+
+@pytest.mark.parametrize("comp,n_les", PULLBACK32_CASES)
+@pytest.mark.parametrize("kind", ["face", "volume"])
+def test_pullbacks_match_scatter_restatement(ins, kind, comp, n_les):
+    """Every value of the whole padded fine cotangent against the scatter restatement applied to the widened float cotangent, in double: the gather
+    is summed in double and rounded once at the store, and no value exceeds max|w|, so the bound of this file holds."""
+    les, dns = aniso(ins, comp, n_les)
+    w = randf32(ins, les, 50 + comp)  # non-zero in the coarse ghost volumes
+    ΦTw = ins.f32.vectorfield32(dns)
+    ΦTw.fill_(SENTINEL)
+    filt(ins, kind).pullback_(ΦTw, w, les, comp, dns)
+    got, wn = wide(ΦTw), wide(w)
+    ref = scatter_pullback(kind, wn, les, dns, comp)
+    err, b = np.max(np.abs(got - ref)), EPS32 * np.max(np.abs(wn))
+    print(f"f32 {kind} pullback D={len(n_les)} comp={comp} N_les={tuple(les.grid.N)}: max err {err:.3e}, bound {b:.3e}")
+    assert np.max(np.abs(ref)) > 0 and err <= b
 
 
 def test_face_pullback_on_mixed_bc_grid(ins, oracle):

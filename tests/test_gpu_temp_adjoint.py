@@ -65,26 +65,31 @@ def trel(a, b):
 def test_transpose_identities(ins, oracle, name, kind):
     for gdir in gdirs(oracle, name):
         _, sp = with_temperature(ins, oracle, name, kind, gdir)
-        u, v, w = rand(ins, sp, True, 1), rand(ins, sp, True, 2), rand(ins, sp, True, 3)
-        temp, p, q = rand(ins, sp, False, 4), rand(ins, sp, False, 5), rand(ins, sp, False, 6)
-        zs, zv = ins.scalarfield(sp), ins.vectorfield(sp)
-        # ghost fill: L p = bc(p) - bc(0)
-        Lp = ins.apply_bc_temp(p, 0.3, sp) - ins.apply_bc_temp(zs, 0.3, sp)
-        check_transpose(Lp, p, q, ins.apply_bc_temp_pullback_(ins.copyfield(q), 0.3, sp))
-        # gravity: temp -> u
-        check_transpose(ins.gravity(p, sp), p, w, ins.gravity_adjoint_(ins.scalarfield(sp), w, sp))
-        # convection_diffusion_temp in temp at fixed u, and in u at fixed temp (affine in each: the constant part removed)
-        Lt = ins.convection_diffusion_temp(u, p, sp) - ins.convection_diffusion_temp(u, zs, sp)
-        check_transpose(Lt, p, q, ins.convection_diffusion_temp_adjoint_(None, ins.scalarfield(sp), q, u, temp, sp)[1])
-        Lu = ins.convection_diffusion_temp(v, temp, sp) - ins.convection_diffusion_temp(zv, temp, sp)
-        check_transpose(Lu, v, q, ins.convection_diffusion_temp_adjoint_(ins.vectorfield(sp), None, q, u, temp, sp)[0])
-        # both halves in one call give the same two results
-        ub, tb = ins.convection_diffusion_temp_adjoint_(ins.vectorfield(sp), ins.scalarfield(sp), q, u, temp, sp)
-        check_transpose(Lu, v, q, ub)
-        check_transpose(Lt, p, q, tb)
-        # dissipation: quadratic in u
-        Jv = (ins.dissipation(u + v, sp) - ins.dissipation(u - v, sp)) / 2
-        check_transpose(Jv, v, q, ins.dissipation_adjoint_(ins.vectorfield(sp), q, u, sp), tol=DISS_TOL)
+        check_transpose_identities(ins, sp)
+
+
+def check_transpose_identities(ins, sp):
+    """The transpose identities of every temperature pullback on one setup with a temperature equation."""
+    u, v, w = rand(ins, sp, True, 1), rand(ins, sp, True, 2), rand(ins, sp, True, 3)
+    temp, p, q = rand(ins, sp, False, 4), rand(ins, sp, False, 5), rand(ins, sp, False, 6)
+    zs, zv = ins.scalarfield(sp), ins.vectorfield(sp)
+    # ghost fill: L p = bc(p) - bc(0)
+    Lp = ins.apply_bc_temp(p, 0.3, sp) - ins.apply_bc_temp(zs, 0.3, sp)
+    check_transpose(Lp, p, q, ins.apply_bc_temp_pullback_(ins.copyfield(q), 0.3, sp))
+    # gravity: temp -> u
+    check_transpose(ins.gravity(p, sp), p, w, ins.gravity_adjoint_(ins.scalarfield(sp), w, sp))
+    # convection_diffusion_temp in temp at fixed u, and in u at fixed temp (affine in each: the constant part removed)
+    Lt = ins.convection_diffusion_temp(u, p, sp) - ins.convection_diffusion_temp(u, zs, sp)
+    check_transpose(Lt, p, q, ins.convection_diffusion_temp_adjoint_(None, ins.scalarfield(sp), q, u, temp, sp)[1])
+    Lu = ins.convection_diffusion_temp(v, temp, sp) - ins.convection_diffusion_temp(zv, temp, sp)
+    check_transpose(Lu, v, q, ins.convection_diffusion_temp_adjoint_(ins.vectorfield(sp), None, q, u, temp, sp)[0])
+    # both halves in one call give the same two results
+    ub, tb = ins.convection_diffusion_temp_adjoint_(ins.vectorfield(sp), ins.scalarfield(sp), q, u, temp, sp)
+    check_transpose(Lu, v, q, ub)
+    check_transpose(Lt, p, q, tb)
+    # dissipation: quadratic in u
+    Jv = (ins.dissipation(u + v, sp) - ins.dissipation(u - v, sp)) / 2
+    check_transpose(Jv, v, q, ins.dissipation_adjoint_(ins.vectorfield(sp), q, u, sp), tol=DISS_TOL)
 
 
 # ------------------------------------------------------------------------------------ 2. against the oracle, value by value
@@ -156,14 +161,21 @@ def test_fused_pullback_equals_the_operator_level_sum(ins, oracle, name, diss):
 
     for gdir in gdirs(oracle, name):
         _, sp = with_temperature(ins, oracle, name, "dirichlet", gdir, dodissipation=diss)
-        u, Fbar = rand(ins, sp, True, 7), rand(ins, sp, True, 8)
-        temp, cbar = rand(ins, sp, False, 9), rand(ins, sp, False, 10)
-        for base in (ins.vectorfield(sp), ins.momentum_pullback_(ins.vectorfield(sp), Fbar, u, sp)):
-            ub, tb, rub, rtb = _fused_and_sum(ins, sp, u, temp, Fbar, cbar, base)
-            assert trel(ub, rub) <= TOL and trel(tb, rtb) <= TOL, (trel(ub, rub), trel(tb, rtb))
-            ub2, tb2, _, _ = _fused_and_sum(ins, sp, u, temp, Fbar, cbar, base)
-            assert torch.equal(ub, ub2) and torch.equal(tb, tb2)
+        check_fused_pullback(ins, sp)
     torch.cuda.synchronize()
+
+
+def check_fused_pullback(ins, sp):
+    """temperature_pullback_ against the sum of the operator-level entries, on zeros and on top of a momentum pullback; bitwise reproducible."""
+    import torch
+
+    u, Fbar = rand(ins, sp, True, 7), rand(ins, sp, True, 8)
+    temp, cbar = rand(ins, sp, False, 9), rand(ins, sp, False, 10)
+    for base in (ins.vectorfield(sp), ins.momentum_pullback_(ins.vectorfield(sp), Fbar, u, sp)):
+        ub, tb, rub, rtb = _fused_and_sum(ins, sp, u, temp, Fbar, cbar, base)
+        assert trel(ub, rub) <= TOL and trel(tb, rtb) <= TOL, (trel(ub, rub), trel(tb, rtb))
+        ub2, tb2, _, _ = _fused_and_sum(ins, sp, u, temp, Fbar, cbar, base)
+        assert torch.equal(ub, ub2) and torch.equal(tb, tb2)
 
 
 def _scalar_randn(ins, sp, seed):

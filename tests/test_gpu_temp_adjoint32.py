@@ -106,85 +106,93 @@ def yardsticks(ins, sp, u, temp):
 # ------------------------------------------------------------------------------------ 1. transpose identities
 @pytest.mark.parametrize("name,kind", CASES)
 def test_transpose_identities(ins, oracle, name, kind):
-    F = ins.f32
     D = GEOMS[name](oracle).grid.D
     for gdir in range(D):
-        sp = with_temperature(ins, oracle, name, kind, gdir)
-        u = pair(ins, sp, True, 1)
-        v32, v64 = pair(ins, sp, True, 2)
-        w32, w64 = pair(ins, sp, True, 3)
-        temp = pair(ins, sp, False, 4)
-        p32, p64 = pair(ins, sp, False, 5)
-        q32, q64 = pair(ins, sp, False, 6)
-        u32, t32 = u[0], temp[0]
-        Eg, Ec, Ed = yardsticks(ins, sp, u, temp)
-        zs, zv = (lambda: F.scalarfield32(sp)), (lambda: F.vectorfield32(sp))
-        results = []
-        # gravity: linear in temp
-        results.append(("gravity_adjoint", defect(F.gravity32_(zv(), p32, sp), p64, w64, F.gravity_adjoint32_(zs(), w32, sp)), Eg))
-        # convection_diffusion_temp is affine in temp at fixed u and in u at fixed temp: subtract the constant part
-        Lp = F.convection_diffusion_temp32_(zs(), u32, p32, sp).double() - F.convection_diffusion_temp32_(zs(), u32, zs(), sp).double()
-        _, tb = F.convection_diffusion_temp_adjoint32_(None, zs(), q32, u32, t32, sp)
-        results.append(("convection_diffusion_temp_adjoint[temp]", defect(Lp, p64, q64, tb), Ec))
-        Lv = F.convection_diffusion_temp32_(zs(), v32, t32, sp).double() - F.convection_diffusion_temp32_(zs(), zv(), t32, sp).double()
-        ub, _ = F.convection_diffusion_temp_adjoint32_(zv(), None, q32, u32, t32, sp)
-        results.append(("convection_diffusion_temp_adjoint[u]", defect(Lv, v64, q64, ub), Ec))
-        # dissipation is quadratic: (f(u+v) - f(u-v))/2 = J(u) v, with u + v and u - v exact in float
-        Jv = (F.dissipation32_(zs(), zv(), u32 + v32, sp).double() - F.dissipation32_(zs(), zv(), u32 - v32, sp).double()) / 2
-        results.append(("dissipation_adjoint", defect(Jv, v64, q64, F.dissipation_adjoint32_(zv(), q32, u32, sp)), Ed))
-        for what, err, yard in results:
-            report(f"{name}/{kind}/gdir{gdir}", "transpose " + what, err, yard)
-        # the affine ghost fill: L v = bc(v) - bc(0); the fill copies exactly, the pullback's float sums round: D 2^-24 <|v|, L^T|w|>
-        Lb = F.apply_bc_temp32_(c32(ins, p32), sp) - F.apply_bc_temp32_(zs(), sp)
-        LTq = F.apply_bc_temp_pullback32_(c32(ins, q32), sp)
-        bound = D * EPS32 * dot(p64.abs(), ins.apply_bc_temp_pullback_(q64.abs(), 0.0, sp))
-        db = abs(dot(Lb, q64) - dot(p64, LTq))
-        print(f"RATIO {name}/{kind}/gdir{gdir} transpose apply_bc_temp defect={db:.3e} bound={bound:.3e}")
-        assert nrm(Lb) > 0 and db <= bound
-        for what, err, yard in results:
-            assert err <= MARGIN * yard, (what, gdir, err, yard)
+        check_transpose_identities(ins, with_temperature(ins, oracle, name, kind, gdir), f"{name}/{kind}/gdir{gdir}")
+
+
+def check_transpose_identities(ins, sp, label):
+    F = ins.f32
+    D = sp.grid.dimension
+    u = pair(ins, sp, True, 1)
+    v32, v64 = pair(ins, sp, True, 2)
+    w32, w64 = pair(ins, sp, True, 3)
+    temp = pair(ins, sp, False, 4)
+    p32, p64 = pair(ins, sp, False, 5)
+    q32, q64 = pair(ins, sp, False, 6)
+    u32, t32 = u[0], temp[0]
+    Eg, Ec, Ed = yardsticks(ins, sp, u, temp)
+    zs, zv = (lambda: F.scalarfield32(sp)), (lambda: F.vectorfield32(sp))
+    results = []
+    # gravity: linear in temp
+    results.append(("gravity_adjoint", defect(F.gravity32_(zv(), p32, sp), p64, w64, F.gravity_adjoint32_(zs(), w32, sp)), Eg))
+    # convection_diffusion_temp is affine in temp at fixed u and in u at fixed temp: subtract the constant part
+    Lp = F.convection_diffusion_temp32_(zs(), u32, p32, sp).double() - F.convection_diffusion_temp32_(zs(), u32, zs(), sp).double()
+    _, tb = F.convection_diffusion_temp_adjoint32_(None, zs(), q32, u32, t32, sp)
+    results.append(("convection_diffusion_temp_adjoint[temp]", defect(Lp, p64, q64, tb), Ec))
+    Lv = F.convection_diffusion_temp32_(zs(), v32, t32, sp).double() - F.convection_diffusion_temp32_(zs(), zv(), t32, sp).double()
+    ub, _ = F.convection_diffusion_temp_adjoint32_(zv(), None, q32, u32, t32, sp)
+    results.append(("convection_diffusion_temp_adjoint[u]", defect(Lv, v64, q64, ub), Ec))
+    # dissipation is quadratic: (f(u+v) - f(u-v))/2 = J(u) v, with u + v and u - v exact in float
+    Jv = (F.dissipation32_(zs(), zv(), u32 + v32, sp).double() - F.dissipation32_(zs(), zv(), u32 - v32, sp).double()) / 2
+    results.append(("dissipation_adjoint", defect(Jv, v64, q64, F.dissipation_adjoint32_(zv(), q32, u32, sp)), Ed))
+    for what, err, yard in results:
+        report(label, "transpose " + what, err, yard)
+    # the affine ghost fill: L v = bc(v) - bc(0); the fill copies exactly, the pullback's float sums round: D 2^-24 <|v|, L^T|w|>
+    Lb = F.apply_bc_temp32_(c32(ins, p32), sp) - F.apply_bc_temp32_(zs(), sp)
+    LTq = F.apply_bc_temp_pullback32_(c32(ins, q32), sp)
+    bound = D * EPS32 * dot(p64.abs(), ins.apply_bc_temp_pullback_(q64.abs(), 0.0, sp))
+    db = abs(dot(Lb, q64) - dot(p64, LTq))
+    print(f"RATIO {label} transpose apply_bc_temp defect={db:.3e} bound={bound:.3e}")
+    assert nrm(Lb) > 0 and db <= bound
+    for what, err, yard in results:
+        assert err <= MARGIN * yard, (what, label, err, yard)
 
 
 # ------------------------------------------------------------------------------------ 2. values against the fp64 twins
 @pytest.mark.parametrize("name,kind", CASES)
 def test_values_against_fp64(ins, oracle, name, kind):
-    F = ins.f32
     D = GEOMS[name](oracle).grid.D
     for gdir in range(D):
-        sp = with_temperature(ins, oracle, name, kind, gdir)
-        u = pair(ins, sp, True, 11)
-        temp = pair(ins, sp, False, 12)
-        (u32, u64), (t32, t64) = u, temp
-        w32, w64 = pair(ins, sp, True, 13)
-        q32, q64 = pair(ins, sp, False, 14)
-        Eg, Ec, Ed = yardsticks(ins, sp, u, temp)
-        zs, zv = (lambda: F.scalarfield32(sp)), (lambda: F.vectorfield32(sp))
-        results = []
-        results.append(("gravity_adjoint", relmax(F.gravity_adjoint32_(zs(), w32, sp), ins.gravity_adjoint_(ins.scalarfield(sp), w64, sp)), Eg))
-        ub, tb = F.convection_diffusion_temp_adjoint32_(zv(), zs(), q32, u32, t32, sp)
-        rub, rtb = ins.convection_diffusion_temp_adjoint_(ins.vectorfield(sp), ins.scalarfield(sp), q64, u64, t64, sp)
-        results.append(("convection_diffusion_temp_adjoint[u]", relmax(ub, rub), Ec))
-        results.append(("convection_diffusion_temp_adjoint[temp]", relmax(tb, rtb), Ec))
-        ub1, _ = F.convection_diffusion_temp_adjoint32_(zv(), None, q32, u32, t32, sp)
-        _, tb1 = F.convection_diffusion_temp_adjoint32_(None, zs(), q32, u32, t32, sp)
-        results.append(("convection_diffusion_temp_adjoint[u alone]", relmax(ub1, rub), Ec))
-        results.append(("convection_diffusion_temp_adjoint[temp alone]", relmax(tb1, rtb), Ec))
-        results.append(("dissipation_adjoint", relmax(F.dissipation_adjoint32_(zv(), q32, u32, sp),
-                                                      ins.dissipation_adjoint_(ins.vectorfield(sp), q64, u64, sp)), Ed))
-        for diss in (True, False):
-            set_dissipation(ins, sp, diss)
-            junk = zs().fill_(7.0)  # tempbar is overwritten
-            ub, tb = F.temperature_pullback32_(zv(), junk, w32, q32, u32, t32, sp)
-            rub, rtb = ins.temperature_pullback_(ins.vectorfield(sp), ins.scalarfield(sp), w64, q64, u64, t64, sp)
-            results.append((f"temperature_pullback[diss={diss}][temp]", relmax(tb, rtb), max(Eg, Ec)))
-            results.append((f"temperature_pullback[diss={diss}][u]", relmax(ub, rub), max(Ec, Ed) if diss else Ec))
-        for what, err, yard in results:
-            report(f"{name}/{kind}/gdir{gdir}", "value " + what, err, yard)
-        # ghost fill, elementwise: |r32 - r64| <= D 2^-24 sum|terms|, the sum of the terms' magnitudes being the fp64 pullback of |w|
-        gb = (F.apply_bc_temp_pullback32_(c32(ins, q32), sp).double() - ins.apply_bc_temp_pullback_(ins.copyfield(q64), 0.0, sp)).abs()
-        assert bool((gb <= D * EPS32 * ins.apply_bc_temp_pullback_(q64.abs(), 0.0, sp)).all())
-        for what, err, yard in results:
-            assert err <= MARGIN * yard, (what, gdir, err, yard)
+        check_values_against_fp64(ins, with_temperature(ins, oracle, name, kind, gdir), f"{name}/{kind}/gdir{gdir}")
+
+
+def check_values_against_fp64(ins, sp, label):
+    F = ins.f32
+    D = sp.grid.dimension
+    u = pair(ins, sp, True, 11)
+    temp = pair(ins, sp, False, 12)
+    (u32, u64), (t32, t64) = u, temp
+    w32, w64 = pair(ins, sp, True, 13)
+    q32, q64 = pair(ins, sp, False, 14)
+    Eg, Ec, Ed = yardsticks(ins, sp, u, temp)
+    zs, zv = (lambda: F.scalarfield32(sp)), (lambda: F.vectorfield32(sp))
+    results = []
+    results.append(("gravity_adjoint", relmax(F.gravity_adjoint32_(zs(), w32, sp), ins.gravity_adjoint_(ins.scalarfield(sp), w64, sp)), Eg))
+    ub, tb = F.convection_diffusion_temp_adjoint32_(zv(), zs(), q32, u32, t32, sp)
+    rub, rtb = ins.convection_diffusion_temp_adjoint_(ins.vectorfield(sp), ins.scalarfield(sp), q64, u64, t64, sp)
+    results.append(("convection_diffusion_temp_adjoint[u]", relmax(ub, rub), Ec))
+    results.append(("convection_diffusion_temp_adjoint[temp]", relmax(tb, rtb), Ec))
+    ub1, _ = F.convection_diffusion_temp_adjoint32_(zv(), None, q32, u32, t32, sp)
+    _, tb1 = F.convection_diffusion_temp_adjoint32_(None, zs(), q32, u32, t32, sp)
+    results.append(("convection_diffusion_temp_adjoint[u alone]", relmax(ub1, rub), Ec))
+    results.append(("convection_diffusion_temp_adjoint[temp alone]", relmax(tb1, rtb), Ec))
+    results.append(("dissipation_adjoint", relmax(F.dissipation_adjoint32_(zv(), q32, u32, sp),
+                                                  ins.dissipation_adjoint_(ins.vectorfield(sp), q64, u64, sp)), Ed))
+    for diss in (True, False):
+        set_dissipation(ins, sp, diss)
+        junk = zs().fill_(7.0)  # tempbar is overwritten
+        ub, tb = F.temperature_pullback32_(zv(), junk, w32, q32, u32, t32, sp)
+        rub, rtb = ins.temperature_pullback_(ins.vectorfield(sp), ins.scalarfield(sp), w64, q64, u64, t64, sp)
+        results.append((f"temperature_pullback[diss={diss}][temp]", relmax(tb, rtb), max(Eg, Ec)))
+        results.append((f"temperature_pullback[diss={diss}][u]", relmax(ub, rub), max(Ec, Ed) if diss else Ec))
+    for what, err, yard in results:
+        report(label, "value " + what, err, yard)
+    # ghost fill, elementwise: |r32 - r64| <= D 2^-24 sum|terms|, the sum of the terms' magnitudes being the fp64 pullback of |w|
+    gb = (F.apply_bc_temp_pullback32_(c32(ins, q32), sp).double() - ins.apply_bc_temp_pullback_(ins.copyfield(q64), 0.0, sp)).abs()
+    assert bool((gb <= D * EPS32 * ins.apply_bc_temp_pullback_(q64.abs(), 0.0, sp)).all())
+    for what, err, yard in results:
+        assert err <= MARGIN * yard, (what, label, err, yard)
 
 
 # ------------------------------------------------------------------------------------ 3. fused against operator-level
