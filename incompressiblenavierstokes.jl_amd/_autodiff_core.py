@@ -1,0 +1,389 @@
+"""The autograd layer that `ins_amd.ad` (autodiff.py, fp64) and `ins_amd.ad32` (autodiff32.py, Float32) share: the layout and save-for-backward
+helpers, the `torch.autograd.Function`s over the in-place forwards and their pullbacks, the differentiable Smagorinsky closure and the Runge-Kutta
+stage loop of `timestep`, each written once against a precision table `ops`.
+
+A public module builds one table and passes it as the last, non-tensor argument of every Function (`_Momentum.apply(u, t, setup, ops)`).  The table
+gives every native call ONE calling convention; what `operators.py` and `f32.py` spell differently (a time argument the Float32 family does not take,
+the literal 0.0 time of the fp64 pullbacks, `momentum32_(F, u, setup, temp=)`) is absorbed by the table's adapters, and where the two modules differ
+in policy (dtype strictness, where the body force is added) the table carries a hook.  The refusals of the public entry points stay in the public
+modules.  Nothing here touches the native library except through the table, so a table of plain torch maps drives all of it without a device
+(tests/test_autodiff_core_cpu.py).
+"""
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from .setup import _fortran_strides
+from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
+
+# The precision table `ops` is a namespace of
+#   name, dtype                 "ad" / "ad32" for messages, the torch dtype of the fields
+#   allocators of zero fields   scalarfield(setup), vectorfield(setup), nfield(setup, ncomp), tensorfield(setup); tb_sizes(setup) -> (nb, nv, ns)
+#   policy hooks                check_dtype(x): ad32 raises TypeError for a tensor that is not float32, ad converts silently
+#                               check_closure_inputs(setup, u or None, *others): what the tensor-basis Functions refuse before converting anything
+#                               bodyforce(setup): the field added to F outside the Functions, or None (fp64 adds it inside `momentum_`)
+#   in-place forwards           apply_bc_u_(u, t, setup, dudt), apply_bc_p_(p, t, setup), apply_bc_temp_(temp, t, setup),
+#                               momentum_(F, u, temp or None, t, setup), gravity_(F, temp, setup), convection_diffusion_temp_(c, u, temp, setup),
+#                               dissipation_(diss, diff, u, setup), project_(u, setup, psolver, p), divoftensor_(s, σ, setup),
+#                               tensorinvariants_(V, u, setup), tensorclosure_stress_(τ, u, a, setup)
+#   pullbacks                   apply_bc_u_pullback_(φbar, setup), apply_bc_p_pullback_(φbar, setup), apply_bc_temp_pullback_(tempbar, setup),
+#                               momentum_pullback_(ubar, φbar, u, setup), gravity_adjoint_(tempbar, φbar, setup),
+#                               convection_diffusion_temp_adjoint_(ubar or None, tempbar or None, cbar, u, temp, setup),
+#                               dissipation_adjoint_(ubar, cbar, u, setup), temperature_pullback_(ubar, tempbar, Fbar, cbar, u, temp, setup),
+#                               project_pullback_(φbar, setup, psolver, pwork), divoftensor_adjoint_(σbar, sbar, setup),
+#                               tensorclosure_pullback_(ubar, abar, τbar, Vbar, u, a, setup)
+# Every call works in place on its first argument(s) and returns what it wrote.
+
+
+# ------------------------------------------------------------------------------------ layout and save-for-backward
+def _field(ops, setup, x, vector):
+    """`x` itself when it already has the library's field layout, else a copy in that layout (cotangents from torch are often expanded
+    views with zero strides, or permuted the other way).  `vector` as in `Setup.ptr`: False (scalar field), True (D components) or an int
+    (an N + (n,) field; only there another shape raises ValueError)."""
+    ops.check_dtype(x)
+    g = setup.grid
+    shape = tuple(g.N) + ((g.dimension,) if vector is True else (vector,) if vector is not False else ())
+    if vector is not True and vector is not False and tuple(x.shape) != shape:
+        raise ValueError(f"expected a field of shape {shape}, got {tuple(x.shape)}")
+    if x.dtype == ops.dtype and x.device == setup.device and tuple(x.shape) == shape and tuple(x.stride()) == _fortran_strides(shape):
+        return x
+    return _copy(ops, setup, x, vector)
+
+
+def _copy(ops, setup, x, vector):
+    """A fresh field (library layout) holding `x`: the in-place forwards and pullbacks work on it."""
+    ops.check_dtype(x)
+    f = ops.vectorfield(setup) if vector is True else ops.scalarfield(setup) if vector is False else ops.nfield(setup, vector)
+    f.copy_(x.detach())
+    return f
+
+
+def _save_inputs(ops, ctx, setup, items):
+    """The fields a backward reads, `items` = (tensor, vector) pairs: an input that already is a library field goes through
+    save_for_backward, so an in-place change of it before backward() raises instead of giving a wrong gradient; a layout copy is private
+    to the Function."""
+    fields, saved, copies = [], [], []
+    for x, vector in items:
+        f = _field(ops, setup, x, vector)
+        fields.append(f)
+        if f is x:
+            saved.append(x)
+            copies.append(None)
+        else:
+            copies.append(f)
+    ctx.save_for_backward(*saved)
+    ctx.copies = copies
+    return fields
+
+
+def _saved_inputs(ctx):
+    saved = list(ctx.saved_tensors)
+    return [saved.pop(0) if c is None else c for c in ctx.copies]
+
+
+# ------------------------------------------------------------------------------------ ghost fill
+class _ApplyBCU(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, t, setup, dudt, ops):
+        ctx.setup, ctx.ops = setup, ops
+        return ops.apply_bc_u_(_copy(ops, setup, u, True), t, setup, dudt)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        return ops.apply_bc_u_pullback_(_copy(ops, s, g, True), s), None, None, None, None
+
+
+class _ApplyBCP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, t, setup, ops):
+        ctx.setup, ctx.ops = setup, ops
+        return ops.apply_bc_p_(_copy(ops, setup, p, False), t, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        return ops.apply_bc_p_pullback_(_copy(ops, s, g, False), s), None, None, None
+
+
+class _ApplyBCTemp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, temp, t, setup, ops):
+        ctx.setup, ctx.ops = setup, ops
+        return ops.apply_bc_temp_(_copy(ops, setup, temp, False), t, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        return ops.apply_bc_temp_pullback_(_copy(ops, s, g, False), s), None, None, None
+
+
+# ------------------------------------------------------------------------------------ momentum and the temperature equation
+class _Momentum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, t, setup, ops):
+        ctx.setup, ctx.ops = setup, ops
+        (uf,) = _save_inputs(ops, ctx, setup, [(u, True)])
+        return ops.momentum_(ops.vectorfield(setup), uf, None, t, setup)
+
+    @staticmethod
+    def backward(ctx, g):  # the body force is additive: it drops out
+        s, ops = ctx.setup, ctx.ops
+        (u,) = _saved_inputs(ctx)
+        return ops.momentum_pullback_(ops.vectorfield(s), _field(ops, s, g, True), u, s), None, None, None
+
+
+class _Gravity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, temp, setup, ops):
+        ctx.setup, ctx.ops = setup, ops
+        return ops.gravity_(ops.vectorfield(setup), _field(ops, setup, temp, False), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        return ops.gravity_adjoint_(ops.scalarfield(s), _field(ops, s, g, True), s), None, None
+
+
+class _ConvectionDiffusionTemp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, temp, setup, ops):
+        ctx.setup, ctx.ops = setup, ops
+        uf, tf = _save_inputs(ops, ctx, setup, [(u, True), (temp, False)])
+        return ops.convection_diffusion_temp_(ops.scalarfield(setup), uf, tf, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        u, temp = _saved_inputs(ctx)
+        ubar = ops.vectorfield(s) if ctx.needs_input_grad[0] else None
+        tempbar = ops.scalarfield(s) if ctx.needs_input_grad[1] else None
+        if ubar is not None or tempbar is not None:
+            ops.convection_diffusion_temp_adjoint_(ubar, tempbar, _field(ops, s, g, False), u, temp, s)
+        return ubar, tempbar, None, None
+
+
+class _Dissipation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup, ops):
+        ctx.setup, ctx.ops = setup, ops
+        (uf,) = _save_inputs(ops, ctx, setup, [(u, True)])
+        return ops.dissipation_(ops.scalarfield(setup), ops.vectorfield(setup), uf, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        (u,) = _saved_inputs(ctx)
+        return ops.dissipation_adjoint_(ops.vectorfield(s), _field(ops, s, g, False), u, s), None, None
+
+
+class _StageRightHandSide(torch.autograd.Function):
+    """(u, temp) -> (F, Ftemp) of one Runge-Kutta stage (step_explicit_runge_kutta.jl:79-83): F = momentum(u, temp) (in Float32 without the
+    body force, which `timestep` adds outside), Ftemp = convection_diffusion_temp(u, temp) + dissipation(u).  The backward is two launches:
+    momentum_pullback_, then temperature_pullback_."""
+
+    @staticmethod
+    def forward(ctx, u, temp, t, setup, ops):
+        ctx.setup, ctx.ops = setup, ops
+        ctx.set_materialize_grads(False)
+        uf, tf = _save_inputs(ops, ctx, setup, [(u, True), (temp, False)])
+        F = ops.momentum_(ops.vectorfield(setup), uf, tf, t, setup)
+        Ftemp = ops.convection_diffusion_temp_(ops.scalarfield(setup), uf, tf, setup)
+        if setup.temperature.dodissipation:
+            ops.dissipation_(Ftemp, ops.vectorfield(setup), uf, setup)
+        return F, Ftemp
+
+    @staticmethod
+    def backward(ctx, gF, gT):
+        s, ops = ctx.setup, ctx.ops
+        if gF is None and gT is None:
+            return None, None, None, None, None
+        u, temp = _saved_inputs(ctx)
+        Fbar = ops.vectorfield(s) if gF is None else _field(ops, s, gF, True)
+        cbar = ops.scalarfield(s) if gT is None else _field(ops, s, gT, False)
+        ubar = ops.momentum_pullback_(ops.vectorfield(s), Fbar, u, s)
+        ubar, tempbar = ops.temperature_pullback_(ubar, ops.scalarfield(s), Fbar, cbar, u, temp, s)
+        return ubar, tempbar, None, None, None
+
+
+def momentum(ops, u, temp, t, setup):
+    """F = momentum(u) [+ gravity(temp)] [+ the body force, where the precision adds it outside the Function], in this order."""
+    F = _Momentum.apply(u, t, setup, ops)
+    if temp is not None:
+        F = F + _Gravity.apply(temp, setup, ops)
+    f = ops.bodyforce(setup)
+    return F if f is None else F + f
+
+
+# ------------------------------------------------------------------------------------ projection
+class _Project(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup, psolver, ops):
+        ctx.setup, ctx.psolver, ctx.ops = setup, psolver, ops
+        return ops.project_(_copy(ops, setup, u, True), setup, psolver, ops.scalarfield(setup))
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        return ops.project_pullback_(_copy(ops, s, g, True), s, ctx.psolver, ops.scalarfield(s)), None, None, None
+
+
+# ------------------------------------------------------------------------------------ DNS-to-LES filters
+class _Filter(torch.autograd.Function):
+    """`v = Φ(u, setup_les, comp)` (lib/NeuralClosure filter.jl) with the exact transpose as backward (csrc/ins_filter.hip, csrc/ins_filter32.hip):
+    a loss on filtered quantities of a differentiable DNS step.  `kind` names the filter in `neuralclosure`, which dispatches on the dtype itself."""
+
+    @staticmethod
+    def forward(ctx, u, setup_les, comp, setup_dns, kind, ops):
+        from . import neuralclosure as nc
+
+        dns = setup_dns or nc.dns_setup_of(setup_les, int(comp))
+        ctx.les, ctx.dns, ctx.comp, ctx.filter, ctx.ops = setup_les, dns, int(comp), getattr(nc, kind)(), ops
+        return ctx.filter(_field(ops, dns, u, True), setup_les, int(comp), setup_dns=dns)
+
+    @staticmethod
+    def backward(ctx, g):
+        ops = ctx.ops
+        ubar = ctx.filter.pullback_(ops.vectorfield(ctx.dns), _field(ops, ctx.les, g, True), ctx.les, ctx.comp, ctx.dns)
+        return ubar, None, None, None, None, None
+
+
+def filter_function(kind, ops, doc):
+    """`FaceAverage` / `VolumeAverage` of one precision: `.apply(u, setup_les, comp, setup_dns=None)`."""
+    return SimpleNamespace(apply=lambda u, setup_les, comp, setup_dns=None: _Filter.apply(u, setup_les, comp, setup_dns, kind, ops), __doc__=doc)
+
+
+# ------------------------------------------------------------------------------------ tensor-basis closure
+class _DivOfTensor(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, σ, setup, ops):
+        ctx.setup, ctx.ops = setup, ops
+        ops.check_closure_inputs(setup, None, σ)
+        return ops.divoftensor_(ops.vectorfield(setup), _field(ops, setup, σ, ops.tb_sizes(setup)[2]), setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        return ops.divoftensor_adjoint_(ops.tensorfield(s), _field(ops, s, g, True), s), None, None
+
+
+class _TensorInvariants(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, setup, ops):
+        ctx.setup, ctx.ops = setup, ops
+        ops.check_closure_inputs(setup, u)
+        V = ops.nfield(setup, ops.tb_sizes(setup)[1])
+        (uf,) = _save_inputs(ops, ctx, setup, [(u, True)])
+        return ops.tensorinvariants_(V, uf, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        (u,) = _saved_inputs(ctx)
+        Vbar = _field(ops, s, g, ops.tb_sizes(s)[1])
+        return ops.tensorclosure_pullback_(ops.vectorfield(s), None, None, Vbar, u, None, s), None, None
+
+
+class _TensorClosureStress(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, a, setup, ops):
+        ctx.setup, ctx.ops = setup, ops
+        ops.check_closure_inputs(setup, u, a)
+        uf, af = _save_inputs(ops, ctx, setup, [(u, True), (a, ops.tb_sizes(setup)[0])])
+        return ops.tensorclosure_stress_(ops.tensorfield(setup), uf, af, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        u, a = _saved_inputs(ctx)
+        nb, _, ns = ops.tb_sizes(s)
+        abar = ops.nfield(s, nb)
+        ubar = ops.tensorclosure_pullback_(ops.vectorfield(s), abar, _field(ops, s, g, ns), None, u, a, s)
+        return ubar, abar, None, None
+
+
+def lastdimcontract(a, b):
+    """tensorbasis.jl:97-157: c[I] = Σ_i a[I, i] b[I, i, ...] — plain torch (its pullback is torch's)."""
+    return (a.reshape(a.shape + (1,) * (b.dim() - a.dim())) * b).sum(dim=a.dim() - 1)
+
+
+def apply_bc_p_fields(apply_bc_p, σ, t, setup):
+    """`apply_bc_p(p, t, setup)` on every channel of an N + (n,) field (the stress tensor's ghost fill, operators.jl:1296)."""
+    return torch.stack([apply_bc_p(σ[..., q], t, setup) for q in range(σ.shape[-1])], dim=-1)
+
+
+def _gridsize2(setup):
+    """gridsize² = Σ_α Δ_α[I_α]² over the padded array (operators.jl:1137), in float64."""
+    g = setup.grid
+    D = g.dimension
+    d2 = torch.zeros(tuple(g.N), dtype=torch.float64, device=setup.device)
+    for α in range(D):
+        shape = [1] * D
+        shape[α] = g.N[α]
+        d2 = d2 + torch.as_tensor(np.asarray(g.Δ[α], dtype=np.float64) ** 2, device=setup.device).reshape(shape)
+    return d2
+
+
+def smagorinsky_closure(ops, setup):
+    """The differentiable Smagorinsky closure `m(u, θ)` (operators.jl:1284-1300): the member a_2 = 2 θ² d² sqrt(2 V_1), every other a_i = 0, of
+    the tensor-basis family.  gridsize² d² is summed in float64, cut to Ip, and held in the precision's dtype."""
+    g = setup.grid
+    D = g.dimension
+    nb = ops.tb_sizes(setup)[0]
+    ip = tuple(slice(lo, hi) for lo, hi in g.Ip)
+    pads = [q for α in reversed(range(D)) for q in (g.Ip[α][0], g.N[α] - g.Ip[α][1])]
+    d2 = _gridsize2(setup)[ip].to(ops.dtype)
+
+    def closure(u, θ):
+        θ = torch.as_tensor(θ, dtype=ops.dtype, device=setup.device)
+        V = _TensorInvariants.apply(u, setup, ops)
+        a2 = torch.nn.functional.pad(2 * θ * θ * d2 * torch.sqrt(2 * V[ip + (0,)]), pads)  # Ip only: sqrt has no derivative at the zeros outside
+        z = torch.zeros_like(a2)
+        a = torch.stack([z, a2] + [z] * (nb - 2), dim=-1)
+        τ = apply_bc_p_fields(lambda p, t, s: _ApplyBCP.apply(p, t, s, ops), _TensorClosureStress.apply(u, a, setup, ops), 0.0, setup)
+        return _DivOfTensor.apply(τ, setup, ops)
+
+    return closure
+
+
+# ------------------------------------------------------------------------------------ time stepping
+def timestep(ops, method, stepper, Δt, θ):
+    """step_explicit_runge_kutta.jl:61-120: one explicit Runge-Kutta step without mutation (the refusals are the caller's).  The stage
+    combinations are torch arithmetic; with a temperature field the right-hand side of a stage, (u, temp) -> (F, Ftemp), is one Function whose
+    backward is two launches.  F is summed in the order momentum (+ gravity), body force, closure."""
+    setup, psolver, u, temp, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.temp, stepper.t, stepper.n
+    m = setup.closure_model
+    erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
+    A, c = erk.A, erk.c
+    tstart, ustart, tempstart, ku, ktemp = t, u, temp, [], []
+    for i in range(len(erk.b)):
+        u = _ApplyBCU.apply(u, t, setup, False, ops)
+        if temp is None:
+            F = momentum(ops, u, None, t, setup)
+        else:
+            temp = _ApplyBCTemp.apply(temp, t, setup, ops)
+            F, Ftemp = _StageRightHandSide.apply(u, temp, t, setup, ops)
+            f = ops.bodyforce(setup)
+            if f is not None:
+                F = F + f
+            ktemp.append(Ftemp)
+        if m is not None:
+            F = F + m(u, θ)
+        ku.append(F)
+        t = tstart + c[i] * Δt
+        u = ustart
+        for j in range(i + 1):
+            if A[i, j] != 0:
+                u = u + (Δt * A[i, j]) * ku[j]
+        if temp is not None:
+            temp = tempstart
+            for j in range(i + 1):
+                if A[i, j] != 0:
+                    temp = temp + (Δt * A[i, j]) * ktemp[j]
+        u = _ApplyBCU.apply(u, t, setup, False, ops)
+        u = _Project.apply(u, setup, psolver, ops)
+    u = _ApplyBCU.apply(u, t, setup, False, ops)
+    if temp is not None:
+        temp = _ApplyBCTemp.apply(temp, t, setup, ops)
+    return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=t, n=n + 1)

@@ -14,13 +14,17 @@ multi-step call in chunks, only the chunk-start states are kept, and the backwar
 
 A closure model given as a torch function `m(u, θ)` is added as F + m(u, θ), and its parameters get gradients from torch.
 """
+from functools import partial
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
+from . import _autodiff_core as core
 from . import operators as O
 from .boundary_conditions import DirichletBC
 from .pressure import project_, project_pullback_
-from .setup import _fortran_strides, scalarfield, vectorfield
+from .setup import _alloc, scalarfield, vectorfield
 from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
 
 __all__ = ["apply_bc_u", "apply_bc_p", "apply_bc_temp", "gravity", "convection_diffusion_temp", "dissipation", "scalewithvolume", "divergence", "pressuregradient", "applypressure", "poisson", "convection", "diffusion",
@@ -28,73 +32,52 @@ __all__ = ["apply_bc_u", "apply_bc_p", "apply_bc_temp", "gravity", "convection_d
            "lastdimcontract", "tensorinvariants", "tensorclosure_stress", "apply_bc_p_fields", "smagorinsky_closure"]
 
 
-def _field(setup, x, vector):
-    """`x` itself when it already has the library's field layout, else a copy in that layout (cotangents from torch are often expanded
-    views with zero strides, or permuted the other way)."""
-    g = setup.grid
-    shape = tuple(g.N) + ((g.dimension,) if vector else ())
-    if (x.dtype == torch.float64 and x.device == setup.device and tuple(x.shape) == shape and tuple(x.stride()) == _fortran_strides(shape)):
-        return x
-    return _copy(setup, x, vector)
+def _check_f64(setup, *xs):
+    for x in xs:
+        if x.dtype != torch.float64:
+            raise TypeError("fields must be float64 torch tensors")
+        if x.device != setup.device:
+            raise ValueError(f"field lives on {x.device}, setup on {setup.device}")
 
 
-def _saved_field(ctx, setup, u):
-    """The velocity a stencil reads, kept for backward: the input itself goes through save_for_backward, so an in-place change of it
-    before backward() raises instead of giving a wrong gradient; a layout copy is private to the Function."""
-    uf = _field(setup, u, True)
-    if uf is u:
-        ctx.save_for_backward(u)
-        ctx.ucopy = None
-    else:
-        ctx.save_for_backward()
-        ctx.ucopy = uf
-    return uf
-
-
-def _saved(ctx):
-    return ctx.saved_tensors[0] if ctx.ucopy is None else ctx.ucopy
-
-
-def _copy(setup, x, vector):
-    """A fresh field (library layout) holding `x`: the pullbacks work in place on it."""
-    f = vectorfield(setup) if vector else scalarfield(setup)
-    f.copy_(x.detach())
-    return f
+# The fp64 precision table of the shared autograd layer (_autodiff_core.py): `operators.py` under the table's calling conventions.  Other dtypes
+# are converted silently, except by the tensor-basis Functions (`_check_f64`); the body force is inside `O.momentum_` and may depend on `t`; the
+# pullbacks of the ghost fills take a time that does not enter (0.0).
+_OPS = SimpleNamespace(
+    name="ad", dtype=torch.float64,
+    scalarfield=scalarfield, vectorfield=vectorfield, nfield=lambda setup, ncomp: _alloc(setup, tuple(setup.grid.N) + (ncomp,)),
+    tensorfield=O.tensorfield, tb_sizes=O._tb_sizes,
+    check_dtype=lambda x: None,
+    check_closure_inputs=lambda setup, u, *others: _check_f64(setup, *(() if u is None else (u,)), *others),
+    bodyforce=lambda setup: None,
+    apply_bc_u_=lambda u, t, setup, dudt: O.apply_bc_u_(u, t, setup, dudt=dudt),
+    apply_bc_p_=O.apply_bc_p_, apply_bc_temp_=O.apply_bc_temp_, momentum_=O.momentum_, gravity_=O.gravity_,
+    convection_diffusion_temp_=O.convection_diffusion_temp_, dissipation_=O.dissipation_, project_=project_, divoftensor_=O.divoftensor_,
+    tensorinvariants_=O.tensorinvariants_, tensorclosure_stress_=O.tensorclosure_stress_,
+    apply_bc_u_pullback_=lambda φbar, setup: O.apply_bc_u_pullback_(φbar, 0.0, setup),
+    apply_bc_p_pullback_=lambda φbar, setup: O.apply_bc_p_pullback_(φbar, 0.0, setup),
+    apply_bc_temp_pullback_=lambda tempbar, setup: O.apply_bc_temp_pullback_(tempbar, 0.0, setup),
+    momentum_pullback_=O.momentum_pullback_, gravity_adjoint_=O.gravity_adjoint_,
+    convection_diffusion_temp_adjoint_=O.convection_diffusion_temp_adjoint_, dissipation_adjoint_=O.dissipation_adjoint_,
+    temperature_pullback_=O.temperature_pullback_, project_pullback_=project_pullback_, divoftensor_adjoint_=O.divoftensor_adjoint_,
+    tensorclosure_pullback_=O.tensorclosure_pullback_,
+)
+# the shared helpers, for the fp64-only Functions below
+_field, _copy, _save_inputs, _saved_inputs = partial(core._field, _OPS), partial(core._copy, _OPS), partial(core._save_inputs, _OPS), core._saved_inputs
+# private names the tests reach for, under their fp64 spelling
+_gridsize2 = core._gridsize2
+_StageRightHandSide = SimpleNamespace(apply=lambda u, temp, t, setup: core._StageRightHandSide.apply(u, temp, t, setup, _OPS))
 
 
 # ------------------------------------------------------------------------------------ ghost fill
-class _ApplyBCU(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, t, setup, dudt):
-        ctx.setup = setup
-        return O.apply_bc_u_(_copy(setup, u, True), t, setup, dudt=dudt)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return O.apply_bc_u_pullback_(_copy(s, g, True), 0.0, s), None, None, None
-
-
-class _ApplyBCP(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, p, t, setup):
-        ctx.setup = setup
-        return O.apply_bc_p_(_copy(setup, p, False), t, setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return O.apply_bc_p_pullback_(_copy(s, g, False), 0.0, s), None, None
-
-
 def apply_bc_u(u, t, setup, dudt=False):
     """boundary_conditions.jl:114-167 (rrule: apply_bc_u_pullback!)"""
-    return _ApplyBCU.apply(u, t, setup, bool(dudt))
+    return core._ApplyBCU.apply(u, t, setup, bool(dudt), _OPS)
 
 
 def apply_bc_p(p, t, setup):
     """boundary_conditions.jl:114-206 (rrule: apply_bc_p_pullback!)"""
-    return _ApplyBCP.apply(p, t, setup)
+    return core._ApplyBCP.apply(p, t, setup, _OPS)
 
 
 # ------------------------------------------------------------------------------------ linear operators
@@ -191,13 +174,14 @@ class _Convection(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, setup):
         ctx.setup = setup
-        uf = _saved_field(ctx, setup, u)
+        (uf,) = _save_inputs(ctx, setup, [(u, True)])
         return O.convection(uf, setup)
 
     @staticmethod
     def backward(ctx, g):
         s = ctx.setup
-        return O.convection_adjoint_(vectorfield(s), _field(s, g, True), _saved(ctx), s), None
+        (u,) = _saved_inputs(ctx)
+        return O.convection_adjoint_(vectorfield(s), _field(s, g, True), u, s), None
 
 
 class _Diffusion(torch.autograd.Function):
@@ -210,19 +194,6 @@ class _Diffusion(torch.autograd.Function):
     def backward(ctx, g):
         s = ctx.setup
         return O.diffusion_adjoint_(vectorfield(s), _field(s, g, True), s, ctx.use_viscosity), None, None
-
-
-class _Momentum(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, t, setup):
-        ctx.setup = setup
-        uf = _saved_field(ctx, setup, u)
-        return O.momentum(uf, None, t, setup)
-
-    @staticmethod
-    def backward(ctx, g):  # the body force is additive: it drops out
-        s = ctx.setup
-        return O.momentum_pullback_(vectorfield(s), _field(s, g, True), _saved(ctx), s), None, None
 
 
 def convection(u, setup):
@@ -238,120 +209,12 @@ def diffusion(u, setup, use_viscosity=True):
 def momentum(u, temp, t, setup):
     """operators.jl:940-976 (convection + diffusion + body force; the pullback is one fused kernel).  With a temperature field the gravity term
     is added (operators.jl:974), differentiable in `u` and in `temp`."""
-    if temp is None:
-        return _Momentum.apply(u, t, setup)
-    if setup.temperature is None:
+    if temp is not None and setup.temperature is None:
         raise NotImplementedError("ad.momentum: a temperature field needs setup.temperature (temperature_equation)")
-    return _Momentum.apply(u, t, setup) + gravity(temp, setup)
+    return core.momentum(_OPS, u, temp, t, setup)
 
 
 # ------------------------------------------------------------------------------------ temperature equation
-def _save_inputs(ctx, setup, items):
-    """The fields a backward reads, `items` = (tensor, vector) pairs: an input that already is a library field goes through
-    save_for_backward, so an in-place change of it before backward() raises; a layout copy is private to the Function."""
-    fields, saved, copies = [], [], []
-    for x, vector in items:
-        f = _field(setup, x, vector)
-        fields.append(f)
-        if f is x:
-            saved.append(x)
-            copies.append(None)
-        else:
-            copies.append(f)
-    ctx.save_for_backward(*saved)
-    ctx.copies = copies
-    return fields
-
-
-def _saved_inputs(ctx):
-    saved = list(ctx.saved_tensors)
-    return [saved.pop(0) if c is None else c for c in ctx.copies]
-
-
-class _ApplyBCTemp(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, temp, t, setup):
-        ctx.setup = setup
-        return O.apply_bc_temp_(_copy(setup, temp, False), t, setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return O.apply_bc_temp_pullback_(_copy(s, g, False), 0.0, s), None, None
-
-
-class _Gravity(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, temp, setup):
-        ctx.setup = setup
-        return O.gravity(_field(setup, temp, False), setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return O.gravity_adjoint_(scalarfield(s), _field(s, g, True), s), None
-
-
-class _ConvectionDiffusionTemp(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, temp, setup):
-        ctx.setup = setup
-        uf, tf = _save_inputs(ctx, setup, [(u, True), (temp, False)])
-        return O.convection_diffusion_temp(uf, tf, setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        u, temp = _saved_inputs(ctx)
-        ubar = vectorfield(s) if ctx.needs_input_grad[0] else None
-        tempbar = scalarfield(s) if ctx.needs_input_grad[1] else None
-        if ubar is not None or tempbar is not None:
-            O.convection_diffusion_temp_adjoint_(ubar, tempbar, _field(s, g, False), u, temp, s)
-        return ubar, tempbar, None
-
-
-class _Dissipation(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, setup):
-        ctx.setup = setup
-        (uf,) = _save_inputs(ctx, setup, [(u, True)])
-        return O.dissipation(uf, setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        (u,) = _saved_inputs(ctx)
-        return O.dissipation_adjoint_(vectorfield(s), _field(s, g, False), u, s), None
-
-
-class _StageRightHandSide(torch.autograd.Function):
-    """(u, temp) -> (F, Ftemp) of one Runge-Kutta stage (step_explicit_runge_kutta.jl:79-83): F = momentum(u, temp), Ftemp =
-    convection_diffusion_temp(u, temp) + dissipation(u).  The backward is two launches: momentum_pullback_, then temperature_pullback_."""
-
-    @staticmethod
-    def forward(ctx, u, temp, t, setup):
-        ctx.setup = setup
-        ctx.set_materialize_grads(False)
-        uf, tf = _save_inputs(ctx, setup, [(u, True), (temp, False)])
-        F = O.momentum_(vectorfield(setup), uf, tf, t, setup)
-        Ftemp = O.convection_diffusion_temp_(scalarfield(setup), uf, tf, setup)
-        if setup.temperature.dodissipation:
-            O.dissipation_(Ftemp, vectorfield(setup), uf, setup)
-        return F, Ftemp
-
-    @staticmethod
-    def backward(ctx, gF, gT):
-        s = ctx.setup
-        if gF is None and gT is None:
-            return None, None, None, None
-        u, temp = _saved_inputs(ctx)
-        Fbar = vectorfield(s) if gF is None else _field(s, gF, True)
-        cbar = scalarfield(s) if gT is None else _field(s, gT, False)
-        ubar = O.momentum_pullback_(vectorfield(s), Fbar, u, s)
-        ubar, tempbar = O.temperature_pullback_(ubar, scalarfield(s), Fbar, cbar, u, temp, s)
-        return ubar, tempbar, None, None
-
-
 def _need_temperature(setup, what):
     if setup.temperature is None:
         raise ValueError(f"ad.{what} needs setup.temperature (temperature_equation)")
@@ -360,40 +223,28 @@ def _need_temperature(setup, what):
 def apply_bc_temp(temp, t, setup):
     """boundary_conditions.jl:236-246 (rrule: apply_bc_temp_pullback!)"""
     _need_temperature(setup, "apply_bc_temp")
-    return _ApplyBCTemp.apply(temp, t, setup)
+    return core._ApplyBCTemp.apply(temp, t, setup, _OPS)
 
 
 def gravity(temp, setup):
     """operators.jl:884-931 (rrule: gravity_adjoint!)"""
     _need_temperature(setup, "gravity")
-    return _Gravity.apply(temp, setup)
+    return core._Gravity.apply(temp, setup, _OPS)
 
 
 def convection_diffusion_temp(u, temp, setup):
     """operators.jl:692-737, differentiable in `u` and in `temp` (the reference's rrule, :699-704, returns undefined names)."""
     _need_temperature(setup, "convection_diffusion_temp")
-    return _ConvectionDiffusionTemp.apply(u, temp, setup)
+    return core._ConvectionDiffusionTemp.apply(u, temp, setup, _OPS)
 
 
 def dissipation(u, setup):
     """operators.jl:770-814 (the reference's rrule is @test_broken); the pullback recomputes diffusion(u) in the kernel."""
     _need_temperature(setup, "dissipation")
-    return _Dissipation.apply(u, setup)
+    return core._Dissipation.apply(u, setup, _OPS)
 
 
 # ------------------------------------------------------------------------------------ projection and right-hand side
-class _Project(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, setup, psolver):
-        ctx.setup, ctx.psolver = setup, psolver
-        return project_(_copy(setup, u, True), setup, psolver, scalarfield(setup))
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return project_pullback_(_copy(s, g, True), s, ctx.psolver, scalarfield(s)), None, None
-
-
 class _RightHandSide(torch.autograd.Function):
     """project(bc_dudt(momentum(bc(u)))) forward and backward, each as one sequence of native calls on the setup's stream."""
 
@@ -418,7 +269,7 @@ class _RightHandSide(torch.autograd.Function):
 
 def project(u, setup, psolver):
     """pressure.jl:52-82: u − G bc_p(poisson(Ω D u)); pullback φ − Dᵀ Ω poisson bc_pᵀ Gᵀ φ in one native sequence."""
-    return _Project.apply(u, setup, psolver)
+    return core._Project.apply(u, setup, psolver, _OPS)
 
 
 def right_hand_side(u, params, t):
@@ -437,75 +288,21 @@ def create_right_hand_side(setup, psolver):
 
 
 # ------------------------------------------------------------------------------------ DNS-to-LES filters
-class _Filter(torch.autograd.Function):
-    """`v = Φ(u, setup_les, comp)` (lib/NeuralClosure filter.jl) with the exact transpose as backward (csrc/ins_filter.hip): a loss on
-    filtered quantities of a differentiable DNS step.  `Filter.apply(u, setup_les, comp, setup_dns=None)`."""
-
-    _kind = None
-
-    @classmethod
-    def _filter(cls):
-        from . import neuralclosure as nc
-
-        return nc.FaceAverage() if cls._kind == "face" else nc.VolumeAverage()
-
-    @classmethod
-    def forward(cls, ctx, u, setup_les, comp, setup_dns=None):
-        from .neuralclosure import dns_setup_of
-
-        dns = setup_dns or dns_setup_of(setup_les, int(comp))
-        ctx.les, ctx.dns, ctx.comp = setup_les, dns, int(comp)
-        return cls._filter()(_field(dns, u, True), setup_les, int(comp), setup_dns=dns)
-
-    @classmethod
-    def backward(cls, ctx, g):
-        ubar = cls._filter().pullback_(vectorfield(ctx.dns), _field(ctx.les, g, True), ctx.les, ctx.comp, ctx.dns)
-        return ubar, None, None, None
-
-
-class FaceAverage(_Filter):
-    """filter.jl:26-46"""
-
-    _kind = "face"
-
-
-class VolumeAverage(_Filter):
-    """filter.jl:82-116"""
-
-    _kind = "volume"
+# `v = Φ(u, setup_les, comp)` (lib/NeuralClosure filter.jl) with the exact transpose as backward (csrc/ins_filter.hip): a loss on filtered
+# quantities of a differentiable DNS step.  `Filter.apply(u, setup_les, comp, setup_dns=None)`.
+FaceAverage = core.filter_function("FaceAverage", _OPS, "filter.jl:26-46")
+VolumeAverage = core.filter_function("VolumeAverage", _OPS, "filter.jl:82-116")
 
 
 # ------------------------------------------------------------------------------------ tensor-basis closure
-def _nfield(setup, x, ncomp, fresh=False):
-    """`x` as an N + (ncomp,) field in the library's layout (a copy when it has another one, or when `fresh`)."""
-    from .setup import _alloc
-
-    shape = tuple(setup.grid.N) + (ncomp,)
-    if (not fresh and x.dtype == torch.float64 and x.device == setup.device and tuple(x.shape) == shape
-            and tuple(x.stride()) == _fortran_strides(shape)):
-        return x.detach()
-    if tuple(x.shape) != shape:
-        raise ValueError(f"expected a field of shape {shape}, got {tuple(x.shape)}")
-    f = _alloc(setup, shape)
-    f.copy_(x.detach())
-    return f
-
-
-def _check_f64(setup, *xs):
-    for x in xs:
-        if x.dtype != torch.float64:
-            raise TypeError("fields must be float64 torch tensors")
-        if x.device != setup.device:
-            raise ValueError(f"field lives on {x.device}, setup on {setup.device}")
-
-
 class _TensorBasis(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, setup):
         ctx.setup = setup
         ctx.set_materialize_grads(False)
         _check_f64(setup, u)
-        return O.tensorbasis(_saved_field(ctx, setup, u), setup)
+        (uf,) = _save_inputs(ctx, setup, [(u, True)])
+        return O.tensorbasis(uf, setup)
 
     @staticmethod
     def backward(ctx, gB, gV):
@@ -514,66 +311,10 @@ class _TensorBasis(torch.autograd.Function):
             return None, None
         D = s.grid.dimension
         nb, nv, _ = O._tb_sizes(s)
-        Bbar = None if gB is None else _nfield(s, gB, nb * D * D)
-        Vbar = None if gV is None else _nfield(s, gV, nv)
-        return O.tensorbasis_pullback_(vectorfield(s), Bbar, Vbar, _saved(ctx), s), None
-
-
-class _DivOfTensor(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, σ, setup):
-        ctx.setup = setup
-        _check_f64(setup, σ)
-        return O.divoftensor_(vectorfield(setup), _nfield(setup, σ, O._tb_sizes(setup)[2]), setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return O.divoftensor_adjoint_(O.tensorfield(s), _field(s, g, True), s), None
-
-
-class _TensorInvariants(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, setup):
-        from .setup import _alloc
-
-        ctx.setup = setup
-        _check_f64(setup, u)
-        V = _alloc(setup, tuple(setup.grid.N) + (O._tb_sizes(setup)[1],))
-        return O.tensorinvariants_(V, _saved_field(ctx, setup, u), setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        Vbar = _nfield(s, g, O._tb_sizes(s)[1])
-        return O.tensorclosure_pullback_(vectorfield(s), None, None, Vbar, _saved(ctx), None, s), None
-
-
-class _TensorClosureStress(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, a, setup):
-        ctx.setup = setup
-        _check_f64(setup, u, a)
-        uf = _field(setup, u, True)
-        af = _nfield(setup, a, O._tb_sizes(setup)[0])
-        # both inputs go through save_for_backward when they already are library fields: an in-place change before backward() raises
-        ctx.ucopy = None if uf is u else uf
-        ctx.acopy = None if af.data_ptr() == a.data_ptr() else af
-        ctx.save_for_backward(*([u] if ctx.ucopy is None else []), *([a] if ctx.acopy is None else []))
-        return O.tensorclosure_stress_(O.tensorfield(setup), uf, af, setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        from .setup import _alloc
-
-        s = ctx.setup
-        saved = list(ctx.saved_tensors)
-        u = saved.pop(0) if ctx.ucopy is None else ctx.ucopy
-        a = saved.pop(0).detach() if ctx.acopy is None else ctx.acopy
-        nb, _, ns = O._tb_sizes(s)
-        abar = _alloc(s, tuple(s.grid.N) + (nb,))
-        ubar = O.tensorclosure_pullback_(vectorfield(s), abar, _nfield(s, g, ns), None, u, a, s)
-        return ubar, abar, None
+        Bbar = None if gB is None else _field(s, gB, nb * D * D)
+        Vbar = None if gV is None else _field(s, gV, nv)
+        (u,) = _saved_inputs(ctx)
+        return O.tensorbasis_pullback_(vectorfield(s), Bbar, Vbar, u, s), None
 
 
 def tensorbasis(u, setup):
@@ -583,62 +324,32 @@ def tensorbasis(u, setup):
 
 def divoftensor(σ, setup):
     """operators.jl:1155-1184 (rrule: divoftensor_adjoint!) on a symmetric `tensorfield` N + (D(D+1)/2,)."""
-    return _DivOfTensor.apply(σ, setup)
+    return core._DivOfTensor.apply(σ, setup, _OPS)
 
 
-def lastdimcontract(a, b):
-    """tensorbasis.jl:97-157: c[I] = Σ_i a[I, i] b[I, i, ...] — plain torch (its pullback is torch's)."""
-    return (a.reshape(a.shape + (1,) * (b.dim() - a.dim())) * b).sum(dim=a.dim() - 1)
+lastdimcontract = core.lastdimcontract  # tensorbasis.jl:97-157
 
 
 def tensorinvariants(u, setup):
     """The invariants V of `tensorbasis` alone (N + (nv,), written on Ip), without forming B."""
-    return _TensorInvariants.apply(u, setup)
+    return core._TensorInvariants.apply(u, setup, _OPS)
 
 
 def tensorclosure_stress(u, a, setup):
     """τ = Σ_i a_i B_i(u) as a symmetric `tensorfield` (written on Ip): `lastdimcontract(a, tensorbasis(u)[0])` in one kernel that keeps the
     basis in registers; the backward gives ubar and abar_i = <τbar, B_i>.  `a` is N + (nb,)."""
-    return _TensorClosureStress.apply(u, a, setup)
+    return core._TensorClosureStress.apply(u, a, setup, _OPS)
 
 
 def apply_bc_p_fields(σ, t, setup):
     """`apply_bc_p` on every channel of an N + (n,) field (the stress tensor's ghost fill, operators.jl:1296)."""
-    return torch.stack([apply_bc_p(σ[..., q], t, setup) for q in range(σ.shape[-1])], dim=-1)
-
-
-def _gridsize2(setup):
-    """gridsize² = Σ_α Δ_α[I_α]² over the padded array (operators.jl:1137)."""
-    g = setup.grid
-    D = g.dimension
-    d2 = torch.zeros(tuple(g.N), dtype=torch.float64, device=setup.device)
-    for α in range(D):
-        shape = [1] * D
-        shape[α] = g.N[α]
-        d2 = d2 + torch.as_tensor(np.asarray(g.Δ[α], dtype=np.float64) ** 2, device=setup.device).reshape(shape)
-    return d2
+    return core.apply_bc_p_fields(apply_bc_p, σ, t, setup)
 
 
 def smagorinsky_closure(setup):
     """Differentiable Smagorinsky closure `m(u, θ)` (operators.jl:1284-1300), θ a 0-dim tensor: the member a_2 = 2 θ² d² sqrt(2 V_1), every
     other a_i = 0, of the tensor-basis family, so ∂/∂u runs in the fused kernels and ∂/∂θ is torch's: a learnable Smagorinsky constant."""
-    g = setup.grid
-    D = g.dimension
-    nb = O._tb_sizes(setup)[0]
-    ip = tuple(slice(lo, hi) for lo, hi in g.Ip)
-    pads = [q for α in reversed(range(D)) for q in (g.Ip[α][0], g.N[α] - g.Ip[α][1])]
-    d2 = _gridsize2(setup)[ip]
-
-    def closure(u, θ):
-        θ = torch.as_tensor(θ, dtype=torch.float64, device=setup.device)
-        V = tensorinvariants(u, setup)
-        a2 = torch.nn.functional.pad(2 * θ * θ * d2 * torch.sqrt(2 * V[ip + (0,)]), pads)  # Ip only: sqrt has no derivative at the zeros outside
-        z = torch.zeros_like(a2)
-        a = torch.stack([z, a2] + [z] * (nb - 2), dim=-1)
-        τ = apply_bc_p_fields(tensorclosure_stress(u, a, setup), 0.0, setup)
-        return divoftensor(τ, setup)
-
-    return closure
+    return core.smagorinsky_closure(_OPS, setup)
 
 
 # ------------------------------------------------------------------------------------ time stepping
@@ -646,7 +357,7 @@ def timestep(method, stepper, Δt, θ=None):
     """step_explicit_runge_kutta.jl:61-120: one explicit Runge-Kutta step without mutation, differentiable in `stepper.u`, in `stepper.temp`
     (with the temperature equation) and (through a torch closure model `m(u, θ)`) in θ.  The stage combinations are torch arithmetic; with a
     temperature field the right-hand side of a stage, (u, temp) -> (F, Ftemp), is one Function whose backward is two launches."""
-    setup, psolver, u, temp, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.temp, stepper.t, stepper.n
+    setup, temp = stepper.setup, stepper.temp
     if temp is not None and setup.temperature is None:
         raise ValueError("a temperature field needs setup.temperature (temperature_equation)")
     m = setup.closure_model
@@ -656,36 +367,7 @@ def timestep(method, stepper, Δt, θ=None):
     if isinstance(method, LMWray3) and (setup.needs_bc_planes or tempplanes or (setup.bodyforce is not None and not setup.issteadybodyforce)):
         # the native step runs the low-storage loop then (step_lmwray3.jl), whose ghost fills happen at other times than the ERK form's
         raise NotImplementedError("ad.timestep: LMWray3 with time-dependent boundary data or body force; use an ExplicitRungeKuttaMethod")
-    erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
-    A, c = erk.A, erk.c
-    tstart, ustart, tempstart, ku, ktemp = t, u, temp, [], []
-    for i in range(len(erk.b)):
-        u = apply_bc_u(u, t, setup)
-        if temp is None:
-            F = momentum(u, None, t, setup)
-        else:
-            temp = apply_bc_temp(temp, t, setup)
-            F, Ftemp = _StageRightHandSide.apply(u, temp, t, setup)
-            ktemp.append(Ftemp)
-        if m is not None:
-            F = F + m(u, θ)
-        ku.append(F)
-        t = tstart + c[i] * Δt
-        u = ustart
-        for j in range(i + 1):
-            if A[i, j] != 0:
-                u = u + (Δt * A[i, j]) * ku[j]
-        if temp is not None:
-            temp = tempstart
-            for j in range(i + 1):
-                if A[i, j] != 0:
-                    temp = temp + (Δt * A[i, j]) * ktemp[j]
-        u = apply_bc_u(u, t, setup)
-        u = project(u, setup, psolver)
-    u = apply_bc_u(u, t, setup)
-    if temp is not None:
-        temp = apply_bc_temp(temp, t, setup)
-    return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=t, n=n + 1)
+    return core.timestep(_OPS, method, stepper, Δt, θ)
 
 
 # ------------------------------------------------------------------------------------ checkpointed rollouts

@@ -34,13 +34,13 @@ float32 tensors (they are not in `__all__`):
 `neuralclosure.tensorclosure(..., dtype=torch.float32)` is built from them, and both are closure models for `ad32.timestep`.  A float64 tensor raises
 TypeError, a field of another shape ValueError, a slab setup NotImplementedError.
 """
-import numpy as np
+from types import SimpleNamespace
+
 import torch
 
+from . import _autodiff_core as core
 from . import f32 as F32
 from .boundary_conditions import HaloBC, PeriodicBC
-from .setup import _fortran_strides
-from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
 
 __all__ = ["apply_bc_u", "momentum", "project", "timestep"]
 
@@ -72,75 +72,25 @@ def _check_psolver(setup, psolver, what):
         raise NotImplementedError(f"ad32.{what}: psolver_wrap32 around psolver_spectral on an all-periodic box is not taken; use f32.psolver_spectral32")
 
 
-def _field(setup, x, vector):
-    """`x` itself when it already is a float32 field in the library's layout, else a copy in that layout."""
-    g = setup.grid
-    shape = tuple(g.N) + ((g.dimension,) if vector else ())
+def _check_temperature(setup, what):
+    _check_slab(setup, what)
+    if setup.temperature is None:
+        raise ValueError(f"ad32.{what} needs setup.temperature (temperature_equation)")
+
+
+def _check_dtype(x):
     if x.dtype != torch.float32:
         raise TypeError("ad32 takes float32 torch tensors")
-    if x.device == setup.device and tuple(x.shape) == shape and tuple(x.stride()) == _fortran_strides(shape):
-        return x
-    return _copy(setup, x, vector)
 
 
-def _copy(setup, x, vector):
-    """A fresh float32 field (library layout) holding `x`: the in-place forwards and pullbacks work on it."""
-    if x.dtype != torch.float32:
-        raise TypeError("ad32 takes float32 torch tensors")
-    f = F32.vectorfield32(setup) if vector else F32.scalarfield32(setup)
-    f.copy_(x.detach())
-    return f
-
-
-class _ApplyBCU(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, setup):
-        ctx.setup = setup
-        return F32.apply_bc_u32_(_copy(setup, u, True), setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return F32.apply_bc_u_pullback32_(_copy(s, g, True), s), None
-
-
-class _Momentum(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, setup):
-        ctx.setup = setup
-        uf = _field(setup, u, True)
-        # the input itself goes through save_for_backward (an in-place change before backward() raises); a layout copy is private
-        if uf is u:
-            ctx.save_for_backward(u)
-            ctx.ucopy = None
-        else:
-            ctx.save_for_backward()
-            ctx.ucopy = uf
-        return F32.momentum32_(F32.vectorfield32(setup), uf, setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        u = ctx.saved_tensors[0] if ctx.ucopy is None else ctx.ucopy
-        return F32.momentum_pullback32_(F32.vectorfield32(s), _field(s, g, True), u, s), None
-
-
-class _Project(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, setup, psolver):
-        ctx.setup, ctx.psolver = setup, psolver
-        return F32.project32_(_copy(setup, u, True), setup, psolver, F32.scalarfield32(setup))
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return F32.project_pullback32_(_copy(s, g, True), s, ctx.psolver, F32.scalarfield32(s)), None, None
-
-
-def apply_bc_u(u, t, setup):
-    """boundary_conditions.jl:114-167 with T = Float32 and constant boundary data (`t` does not enter); pullback: apply_bc_u_pullback32_."""
-    _check_setup(setup, "apply_bc_u")
-    return _ApplyBCU.apply(u, setup)
+def _check_vec(setup, u, *others):
+    """`u` is a float32 vector field of the setup's shape: another dtype raises TypeError, another shape ValueError (the N + (n,) inputs are
+    checked where they are converted)."""
+    if u is not None:
+        shape = tuple(setup.grid.N) + (setup.grid.dimension,)
+        _check_dtype(u)
+        if tuple(u.shape) != shape:
+            raise ValueError(f"expected a field of shape {shape}, got {tuple(u.shape)}")
 
 
 def _bodyforce32(setup):
@@ -151,6 +101,37 @@ def _bodyforce32(setup):
     return f[1]
 
 
+# The Float32 precision table of the shared autograd layer (_autodiff_core.py): `f32.py` under the table's calling conventions.  The boundary
+# data is constant, so `t` does not enter; any dtype but float32 raises; the steady body force is added outside the Functions, from a cached cast.
+_OPS = SimpleNamespace(
+    name="ad32", dtype=torch.float32,
+    scalarfield=F32.scalarfield32, vectorfield=F32.vectorfield32, nfield=F32.nfield32, tensorfield=F32.tensorfield32, tb_sizes=F32._tb_sizes,
+    check_dtype=_check_dtype, check_closure_inputs=_check_vec,
+    bodyforce=lambda setup: None if setup.bodyforce is None else _bodyforce32(setup),
+    apply_bc_u_=lambda u, t, setup, dudt: F32.apply_bc_u32_(u, setup, dudt=dudt),
+    apply_bc_p_=lambda p, t, setup: F32.apply_bc_p32_(p, setup),
+    apply_bc_temp_=lambda temp, t, setup: F32.apply_bc_temp32_(temp, setup),
+    momentum_=lambda F, u, temp, t, setup: F32.momentum32_(F, u, setup, temp=temp),
+    gravity_=F32.gravity32_, convection_diffusion_temp_=F32.convection_diffusion_temp32_, dissipation_=F32.dissipation32_,
+    project_=F32.project32_, divoftensor_=F32.divoftensor32_, tensorinvariants_=F32.tensorinvariants32_,
+    tensorclosure_stress_=F32.tensorclosure_stress32_,
+    apply_bc_u_pullback_=F32.apply_bc_u_pullback32_, apply_bc_p_pullback_=F32.apply_bc_p_pullback32_,
+    apply_bc_temp_pullback_=F32.apply_bc_temp_pullback32_, momentum_pullback_=F32.momentum_pullback32_, gravity_adjoint_=F32.gravity_adjoint32_,
+    convection_diffusion_temp_adjoint_=F32.convection_diffusion_temp_adjoint32_, dissipation_adjoint_=F32.dissipation_adjoint32_,
+    temperature_pullback_=F32.temperature_pullback32_, project_pullback_=F32.project_pullback32_,
+    divoftensor_adjoint_=F32.divoftensor_adjoint32_, tensorclosure_pullback_=F32.tensorclosure_pullback32_,
+)
+
+# the stage Function under its Float32 spelling (`t` does not enter), as the tests call it
+_StageRightHandSide = SimpleNamespace(apply=lambda u, temp, setup: core._StageRightHandSide.apply(u, temp, 0.0, setup, _OPS))
+
+
+def apply_bc_u(u, t, setup):
+    """boundary_conditions.jl:114-167 with T = Float32 and constant boundary data (`t` does not enter); pullback: apply_bc_u_pullback32_."""
+    _check_setup(setup, "apply_bc_u")
+    return core._ApplyBCU.apply(u, t, setup, False, _OPS)
+
+
 def momentum(u, temp, t, setup):
     """operators.jl:940-976 with T = Float32: convection + diffusion (momentum32_; the pullback is one launch) + a steady body force, which
     is additive and drops out of the pullback.  With a temperature field (and a temperature equation in `setup`) the gravity term is added
@@ -158,361 +139,91 @@ def momentum(u, temp, t, setup):
     if temp is not None and setup.temperature is None:
         raise NotImplementedError("ad32.momentum: a temperature field needs setup.temperature (temperature_equation)")
     _check_setup(setup, "momentum")
-    F = _Momentum.apply(u, setup)
-    if temp is not None:
-        F = F + gravity(temp, setup)
-    return F if setup.bodyforce is None else F + _bodyforce32(setup)
+    return core.momentum(_OPS, u, temp, t, setup)
 
 
 # ------------------------------------------------------------------------------------ temperature equation
-def _save_inputs(ctx, setup, items):
-    """The fields a backward reads, `items` = (tensor, vector) pairs: an input that already is a library field goes through
-    save_for_backward, so an in-place change of it before backward() raises; a layout copy is private to the Function."""
-    fields, saved, copies = [], [], []
-    for x, vector in items:
-        f = _field(setup, x, vector)
-        fields.append(f)
-        if f is x:
-            saved.append(x)
-            copies.append(None)
-        else:
-            copies.append(f)
-    ctx.save_for_backward(*saved)
-    ctx.copies = copies
-    return fields
-
-
-def _saved_inputs(ctx):
-    saved = list(ctx.saved_tensors)
-    return [saved.pop(0) if c is None else c for c in ctx.copies]
-
-
-class _ApplyBCTemp(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, temp, setup):
-        ctx.setup = setup
-        return F32.apply_bc_temp32_(_copy(setup, temp, False), setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return F32.apply_bc_temp_pullback32_(_copy(s, g, False), s), None
-
-
-class _Gravity(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, temp, setup):
-        ctx.setup = setup
-        return F32.gravity32_(F32.vectorfield32(setup), _field(setup, temp, False), setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return F32.gravity_adjoint32_(F32.scalarfield32(s), _field(s, g, True), s), None
-
-
-class _ConvectionDiffusionTemp(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, temp, setup):
-        ctx.setup = setup
-        uf, tf = _save_inputs(ctx, setup, [(u, True), (temp, False)])
-        return F32.convection_diffusion_temp32_(F32.scalarfield32(setup), uf, tf, setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        u, temp = _saved_inputs(ctx)
-        ubar = F32.vectorfield32(s) if ctx.needs_input_grad[0] else None
-        tempbar = F32.scalarfield32(s) if ctx.needs_input_grad[1] else None
-        if ubar is not None or tempbar is not None:
-            F32.convection_diffusion_temp_adjoint32_(ubar, tempbar, _field(s, g, False), u, temp, s)
-        return ubar, tempbar, None
-
-
-class _Dissipation(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, setup):
-        ctx.setup = setup
-        (uf,) = _save_inputs(ctx, setup, [(u, True)])
-        return F32.dissipation32_(F32.scalarfield32(setup), F32.vectorfield32(setup), uf, setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        (u,) = _saved_inputs(ctx)
-        return F32.dissipation_adjoint32_(F32.vectorfield32(s), _field(s, g, False), u, s), None
-
-
-class _StageRightHandSide(torch.autograd.Function):
-    """(u, temp) -> (F, Ftemp) of one Runge-Kutta stage (step_explicit_runge_kutta.jl:79-83) with T = Float32: F = momentum(u, temp) without
-    the body force, Ftemp = convection_diffusion_temp(u, temp) + dissipation(u).  The backward is two launches: momentum_pullback32_, then
-    temperature_pullback32_."""
-
-    @staticmethod
-    def forward(ctx, u, temp, setup):
-        ctx.setup = setup
-        ctx.set_materialize_grads(False)
-        uf, tf = _save_inputs(ctx, setup, [(u, True), (temp, False)])
-        F = F32.momentum32_(F32.vectorfield32(setup), uf, setup, temp=tf)
-        Ftemp = F32.convection_diffusion_temp32_(F32.scalarfield32(setup), uf, tf, setup)
-        if setup.temperature.dodissipation:
-            F32.dissipation32_(Ftemp, F32.vectorfield32(setup), uf, setup)
-        return F, Ftemp
-
-    @staticmethod
-    def backward(ctx, gF, gT):
-        s = ctx.setup
-        if gF is None and gT is None:
-            return None, None, None
-        u, temp = _saved_inputs(ctx)
-        Fbar = F32.vectorfield32(s) if gF is None else _field(s, gF, True)
-        cbar = F32.scalarfield32(s) if gT is None else _field(s, gT, False)
-        ubar = F32.momentum_pullback32_(F32.vectorfield32(s), Fbar, u, s)
-        ubar, tempbar = F32.temperature_pullback32_(ubar, F32.scalarfield32(s), Fbar, cbar, u, temp, s)
-        return ubar, tempbar, None
-
-
-def _check_temperature(setup, what):
-    _check_slab(setup, what)
-    if setup.temperature is None:
-        raise ValueError(f"ad32.{what} needs setup.temperature (temperature_equation)")
-
-
 def apply_bc_temp(temp, t, setup):
     """boundary_conditions.jl:236-246 with T = Float32 and constant boundary data (`t` does not enter); pullback: apply_bc_temp_pullback32_."""
     _check_temperature(setup, "apply_bc_temp")
-    return _ApplyBCTemp.apply(temp, setup)
+    return core._ApplyBCTemp.apply(temp, t, setup, _OPS)
 
 
 def gravity(temp, setup):
     """operators.jl:884-931 with T = Float32; pullback: gravity_adjoint32_."""
     _check_temperature(setup, "gravity")
-    return _Gravity.apply(temp, setup)
+    return core._Gravity.apply(temp, setup, _OPS)
 
 
 def convection_diffusion_temp(u, temp, setup):
     """operators.jl:692-737 with T = Float32, differentiable in `u` and in `temp`; pullback: convection_diffusion_temp_adjoint32_."""
     _check_temperature(setup, "convection_diffusion_temp")
-    return _ConvectionDiffusionTemp.apply(u, temp, setup)
+    return core._ConvectionDiffusionTemp.apply(u, temp, setup, _OPS)
 
 
 def dissipation(u, setup):
     """operators.jl:770-814 with T = Float32; the pullback (dissipation_adjoint32_) recomputes diffusion(u) in the kernel."""
     _check_temperature(setup, "dissipation")
-    return _Dissipation.apply(u, setup)
+    return core._Dissipation.apply(u, setup, _OPS)
 
 
 def project(u, setup, psolver):
     """pressure.jl:52-82 with T = Float32 (project32_); pullback: project_pullback32_, the transpose for this kind of solver."""
     _check_setup(setup, "project")
     _check_psolver(setup, psolver, "project")
-    return _Project.apply(u, setup, psolver)
+    return core._Project.apply(u, setup, psolver, _OPS)
 
 
 # ------------------------------------------------------------------------------------ DNS-to-LES filters
-class _Filter(torch.autograd.Function):
-    """`v = Φ(u, setup_les, comp)` (lib/NeuralClosure filter.jl) on float32 fields with the exact transpose as backward (csrc/ins_filter32.hip):
-    the Float32 twin of `ad.FaceAverage` / `ad.VolumeAverage`.  `Filter.apply(u, setup_les, comp, setup_dns=None)`."""
-
-    _kind = None
-
-    @classmethod
-    def _filter(cls):
-        from . import neuralclosure as nc
-
-        return nc.FaceAverage() if cls._kind == "face" else nc.VolumeAverage()
-
-    @classmethod
-    def forward(cls, ctx, u, setup_les, comp, setup_dns=None):
-        from .neuralclosure import dns_setup_of
-
-        dns = setup_dns or dns_setup_of(setup_les, int(comp))
-        ctx.les, ctx.dns, ctx.comp = setup_les, dns, int(comp)
-        return cls._filter()(_field(dns, u.detach(), True), setup_les, int(comp), setup_dns=dns)
-
-    @classmethod
-    def backward(cls, ctx, g):
-        ubar = cls._filter().pullback_(F32.vectorfield32(ctx.dns), _field(ctx.les, g, True), ctx.les, ctx.comp, ctx.dns)
-        return ubar, None, None, None
-
-
-class FaceAverage(_Filter):
-    """filter.jl:26-46"""
-
-    _kind = "face"
-
-
-class VolumeAverage(_Filter):
-    """filter.jl:82-116"""
-
-    _kind = "volume"
+# `v = Φ(u, setup_les, comp)` (lib/NeuralClosure filter.jl) on float32 fields with the exact transpose as backward (csrc/ins_filter32.hip):
+# the Float32 twin of `ad.FaceAverage` / `ad.VolumeAverage`.  `Filter.apply(u, setup_les, comp, setup_dns=None)`.
+FaceAverage = core.filter_function("FaceAverage", _OPS, "filter.jl:26-46")
+VolumeAverage = core.filter_function("VolumeAverage", _OPS, "filter.jl:82-116")
 
 
 # ------------------------------------------------------------------------------------ tensor-basis closure
-def _vec(setup, u):
-    """`u` as a float32 vector field in the library's layout; another dtype raises TypeError, another shape ValueError."""
-    shape = tuple(setup.grid.N) + (setup.grid.dimension,)
-    if u.dtype != torch.float32:
-        raise TypeError("ad32 takes float32 torch tensors")
-    if tuple(u.shape) != shape:
-        raise ValueError(f"expected a field of shape {shape}, got {tuple(u.shape)}")
-    return _field(setup, u, True)
-
-
-def _nfield(setup, x, ncomp):
-    """`x` as an N + (ncomp,) float32 field in the library's layout (a copy when it has another one)."""
-    shape = tuple(setup.grid.N) + (ncomp,)
-    if x.dtype != torch.float32:
-        raise TypeError("ad32 takes float32 torch tensors")
-    if tuple(x.shape) != shape:
-        raise ValueError(f"expected a field of shape {shape}, got {tuple(x.shape)}")
-    if x.device == setup.device and tuple(x.stride()) == _fortran_strides(shape):
-        return x.detach()
-    f = F32.nfield32(setup, ncomp)
-    f.copy_(x.detach())
-    return f
-
-
-def _saved_field(ctx, setup, u):
-    """The velocity a stencil reads, kept for backward: the input itself goes through save_for_backward (an in-place change before
-    backward() raises); a layout copy is private to the Function."""
-    uf = _vec(setup, u)
-    if uf is u:
-        ctx.save_for_backward(u)
-        ctx.ucopy = None
-    else:
-        ctx.save_for_backward()
-        ctx.ucopy = uf
-    return uf
-
-
-class _ApplyBCP(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, p, setup):
-        ctx.setup = setup
-        return F32.apply_bc_p32_(_copy(setup, p, False), setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return F32.apply_bc_p_pullback32_(_copy(s, g, False), s), None
-
-
-class _DivOfTensor(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, σ, setup):
-        ctx.setup = setup
-        return F32.divoftensor32_(F32.vectorfield32(setup), _nfield(setup, σ, F32._tb_sizes(setup)[2]), setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        return F32.divoftensor_adjoint32_(F32.tensorfield32(s), _field(s, g, True), s), None
-
-
-class _TensorInvariants(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, setup):
-        ctx.setup = setup
-        return F32.tensorinvariants32_(F32.nfield32(setup, F32._tb_sizes(setup)[1]), _saved_field(ctx, setup, u), setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        u = ctx.saved_tensors[0] if ctx.ucopy is None else ctx.ucopy
-        Vbar = _nfield(s, g, F32._tb_sizes(s)[1])
-        return F32.tensorclosure_pullback32_(F32.vectorfield32(s), None, None, Vbar, u, None, s), None
-
-
-class _TensorClosureStress(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, a, setup):
-        ctx.setup = setup
-        uf = _vec(setup, u)
-        af = _nfield(setup, a, F32._tb_sizes(setup)[0])
-        # both inputs go through save_for_backward when they already are library fields: an in-place change before backward() raises
-        ctx.ucopy = None if uf is u else uf
-        ctx.acopy = None if af.data_ptr() == a.data_ptr() else af
-        ctx.save_for_backward(*([u] if ctx.ucopy is None else []), *([a] if ctx.acopy is None else []))
-        return F32.tensorclosure_stress32_(F32.tensorfield32(setup), uf, af, setup)
-
-    @staticmethod
-    def backward(ctx, g):
-        s = ctx.setup
-        saved = list(ctx.saved_tensors)
-        u = saved.pop(0) if ctx.ucopy is None else ctx.ucopy
-        a = saved.pop(0).detach() if ctx.acopy is None else ctx.acopy
-        nb, _, ns = F32._tb_sizes(s)
-        abar = F32.nfield32(s, nb)
-        ubar = F32.tensorclosure_pullback32_(F32.vectorfield32(s), abar, _nfield(s, g, ns), None, u, a, s)
-        return ubar, abar, None
-
-
 def apply_bc_p(p, t, setup):
     """boundary_conditions.jl:114-206 with T = Float32 (`t` does not enter); pullback: apply_bc_p_pullback32_."""
     _check_slab(setup, "apply_bc_p")
     if tuple(p.shape) != tuple(setup.grid.N):
         raise ValueError(f"expected a field of shape {tuple(setup.grid.N)}, got {tuple(p.shape)}")
-    return _ApplyBCP.apply(p, setup)
+    return core._ApplyBCP.apply(p, t, setup, _OPS)
 
 
 def apply_bc_p_fields(σ, t, setup):
     """`apply_bc_p` on every channel of an N + (n,) field (the stress tensor's ghost fill, operators.jl:1296)."""
     if σ.dim() != setup.grid.dimension + 1:
         raise ValueError(f"expected a field of shape {tuple(setup.grid.N)} + (n,), got {tuple(σ.shape)}")
-    return torch.stack([apply_bc_p(σ[..., q], t, setup) for q in range(σ.shape[-1])], dim=-1)
+    return core.apply_bc_p_fields(apply_bc_p, σ, t, setup)
 
 
 def tensorinvariants(u, setup):
     """The invariants V of the tensor basis (N + (nv,), written on Ip) with T = Float32, without forming B."""
     _check_slab(setup, "tensorinvariants")
-    return _TensorInvariants.apply(u, setup)
+    return core._TensorInvariants.apply(u, setup, _OPS)
 
 
 def tensorclosure_stress(u, a, setup):
     """τ = Σ_i a_i B_i(u) as a symmetric `tensorfield32` (written on Ip) in one kernel that keeps the basis in registers; the backward gives
     ubar and abar_i = <τbar, B_i>.  `a` is N + (nb,)."""
     _check_slab(setup, "tensorclosure_stress")
-    return _TensorClosureStress.apply(u, a, setup)
+    return core._TensorClosureStress.apply(u, a, setup, _OPS)
 
 
 def divoftensor(σ, setup):
     """operators.jl:1155-1184 with T = Float32 (pullback: divoftensor_adjoint32_) on a symmetric `tensorfield32` N + (D(D+1)/2,)."""
     _check_slab(setup, "divoftensor")
-    return _DivOfTensor.apply(σ, setup)
+    return core._DivOfTensor.apply(σ, setup, _OPS)
 
 
-def lastdimcontract(a, b):
-    """tensorbasis.jl:97-157: c[I] = Σ_i a[I, i] b[I, i, ...] — plain torch (its pullback is torch's)."""
-    return (a.reshape(a.shape + (1,) * (b.dim() - a.dim())) * b).sum(dim=a.dim() - 1)
+lastdimcontract = core.lastdimcontract  # tensorbasis.jl:97-157
 
 
 def smagorinsky_closure(setup):
     """Differentiable Smagorinsky closure `m(u, θ)` with T = Float32 (operators.jl:1284-1300), θ a 0-dim tensor: the member
     a_2 = 2 θ² d² sqrt(2 V_1), every other a_i = 0, of the tensor-basis family, as `ad.smagorinsky_closure`; gridsize² d² is held in float32."""
     _check_slab(setup, "smagorinsky_closure")
-    g = setup.grid
-    D = g.dimension
-    nb = F32._tb_sizes(setup)[0]
-    ip = tuple(slice(lo, hi) for lo, hi in g.Ip)
-    pads = [q for α in reversed(range(D)) for q in (g.Ip[α][0], g.N[α] - g.Ip[α][1])]
-    d2 = torch.zeros(tuple(g.N), dtype=torch.float64, device=setup.device)
-    for α in range(D):
-        shape = [1] * D
-        shape[α] = g.N[α]
-        d2 = d2 + torch.as_tensor(np.asarray(g.Δ[α], dtype=np.float64) ** 2, device=setup.device).reshape(shape)
-    d2 = d2[ip].float()
-
-    def closure(u, θ):
-        θ = torch.as_tensor(θ, dtype=torch.float32, device=setup.device)
-        V = tensorinvariants(u, setup)
-        a2 = torch.nn.functional.pad(2 * θ * θ * d2 * torch.sqrt(2 * V[ip + (0,)]), pads)  # Ip only: sqrt has no derivative at the zeros outside
-        z = torch.zeros_like(a2)
-        a = torch.stack([z, a2] + [z] * (nb - 2), dim=-1)
-        τ = apply_bc_p_fields(tensorclosure_stress(u, a, setup), 0.0, setup)
-        return divoftensor(τ, setup)
-
-    return closure
+    return core.smagorinsky_closure(_OPS, setup)
 
 
 def timestep(method, stepper, Δt, θ=None):
@@ -520,41 +231,9 @@ def timestep(method, stepper, Δt, θ=None):
     in `stepper.temp` (with the temperature equation) and (through a torch closure model `m(u, θ)`) in θ; `ad.timestep` on the Float32
     operators, stage combinations in torch arithmetic.  With a temperature field the right-hand side of a stage, (u, temp) -> (F, Ftemp), is
     one Function whose backward is two launches."""
-    setup, psolver, u, temp, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.temp, stepper.t, stepper.n
-    if temp is not None and setup.temperature is None:
+    setup = stepper.setup
+    if stepper.temp is not None and setup.temperature is None:
         raise NotImplementedError("ad32.timestep: a temperature field needs setup.temperature (temperature_equation)")
     _check_setup(setup, "timestep")
-    _check_psolver(setup, psolver, "timestep")
-    m = setup.closure_model
-    erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
-    A, c = erk.A, erk.c
-    tstart, ustart, tempstart, ku, ktemp = t, u, temp, [], []
-    for i in range(len(erk.b)):
-        u = apply_bc_u(u, t, setup)
-        if temp is None:
-            F = momentum(u, None, t, setup)
-        else:
-            temp = apply_bc_temp(temp, t, setup)
-            F, Ftemp = _StageRightHandSide.apply(u, temp, setup)
-            if setup.bodyforce is not None:
-                F = F + _bodyforce32(setup)
-            ktemp.append(Ftemp)
-        if m is not None:
-            F = F + m(u, θ)
-        ku.append(F)
-        t = tstart + c[i] * Δt
-        u = ustart
-        for j in range(i + 1):
-            if A[i, j] != 0:
-                u = u + (Δt * A[i, j]) * ku[j]
-        if temp is not None:
-            temp = tempstart
-            for j in range(i + 1):
-                if A[i, j] != 0:
-                    temp = temp + (Δt * A[i, j]) * ktemp[j]
-        u = apply_bc_u(u, t, setup)
-        u = project(u, setup, psolver)
-    u = apply_bc_u(u, t, setup)
-    if temp is not None:
-        temp = apply_bc_temp(temp, t, setup)
-    return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=t, n=n + 1)
+    _check_psolver(setup, stepper.psolver, "timestep")
+    return core.timestep(_OPS, method, stepper, Δt, θ)
