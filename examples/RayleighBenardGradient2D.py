@@ -2,7 +2,9 @@
 """Sensitivity of a Rayleigh-Bénard cell (the setting of RayleighBenard2D.py): the gradient of the lower-plate Nusselt number after a short
 run with respect to the initial temperature field, ∂Nu/∂temp0, by reverse mode through `ins.ad.timestep` (temperature equation with viscous
 heating and buoyancy, all on the HIP pullback kernels), checked against a central difference in one direction.  With `dtype=torch.float32`
-the same problem runs on `ins.ad32` (the reference runs its Rayleigh-Bénard examples in Float32, examples/RayleighBenard2D.jl:71).
+the same problem runs on `ins.ad32` (the reference runs its Rayleigh-Bénard examples in Float32, examples/RayleighBenard2D.jl:71).  With
+`rollout=True` the same gradient comes from ONE `ad.timesteps` / `ad32.timesteps` call (the native multi-step loop forward, per-chunk
+checkpoints, one native reverse step per step backward), so its memory does not grow with `nstep`.
     python examples/RayleighBenardGradient2D.py n=32 nstep=20 dt=5e-3"""
 import numpy as np
 import torch
@@ -11,7 +13,8 @@ import _common  # noqa: F401
 import ins_amd as ins
 
 
-def main(n=32, nstep=20, dt=5e-3, Pr=0.71, Ra=1e6, Ge=1.0, seed=0, verbose=True, dtype=torch.float64):
+def main(n=32, nstep=20, dt=5e-3, Pr=0.71, Ra=1e6, Ge=1.0, seed=0, verbose=True, dtype=torch.float64, rollout=False,
+         checkpoint_every=None):
     f32 = dtype == torch.float32
     temperature = ins.temperature_equation(
         Pr=Pr, Ra=Ra, Ge=Ge, dodissipation=True, gdir=1, nondim_type=1,
@@ -39,8 +42,11 @@ def main(n=32, nstep=20, dt=5e-3, Pr=0.71, Ra=1e6, Ge=1.0, seed=0, verbose=True,
 
     def run(temp, final=None):
         st = ins.create_stepper(method, setup=setup, psolver=psolver, u=u0, temp=temp)
-        for _ in range(nstep):
-            st = ad.timestep(method, st, dt)
+        if rollout:
+            st = ad.timesteps(method, st, dt, nstep, checkpoint_every=checkpoint_every)
+        else:
+            for _ in range(nstep):
+                st = ad.timestep(method, st, dt)
         if final is not None:
             final.append(st.temp.detach())
         return nusselt(st.temp)

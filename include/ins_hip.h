@@ -47,6 +47,7 @@ extern "C" {
 typedef struct ins_grid ins_grid_t;       /* device copy of `setup.grid` metrics   (grid.jl:100-276)   */
 typedef struct ins_poisson ins_poisson_t; /* a `psolver` closure                   (pressure.jl:85-351) */
 typedef struct ins_rk_adjoint ins_rk_adjoint_t; /* work arrays of the reverse Runge-Kutta step (ins_rk_step_pullback_f64) */
+typedef struct ins_rk_adjoint32 ins_rk_adjoint32_t; /* the same for T = Float32 (ins_rk_step_pullback_f32) */
 typedef struct ins_rk ins_rk_t;           /* `ode_method_cache` + stepper state    (time_stepper_caches.jl:34-49) */
 typedef struct ins_poisson32 ins_poisson32_t; /* `psolver_spectral` closure for T = Float32 */
 typedef struct ins_rk32 ins_rk32_t;           /* `ode_method_cache` for T = Float32 */
@@ -216,6 +217,14 @@ int ins_rk_adjoint_destroy(ins_rk_adjoint_t* adj);
  * One combination pass writes k̄_i and the plain momentum pullback reads it; INS_ADJ_STAGE_FUSED=1 forms it inside the pullback kernel where the
  * cotangent is loaded instead (up to 4 non-zero terms).  ubar == ustart: INS_ERR_INVALID.  Asynchronous on `stream` (CG solver: blocking). */
 int ins_rk_step_pullback_f64(ins_rk_adjoint_t* adj, double visc, const double* ustart, const double* bodyforce, double dt, double* ubar, void* stream);
+/* The same step with T = Float32 (the reverse of ins_rk_step_f32 / ins_rk_step_ext_f32 without closure): float work arrays, `ps` either kind of
+ * Float32 solver handle that ins_project_pullback_f32 takes; the kind it refuses (a wrapped spectral solver on an all-periodic box) is refused here,
+ * at create time, with INS_ERR_UNSUPPORTED, like a slab grid.  The stage inputs are recomputed with ins_apply_bc_u_f32, ins_momentum_f32, a float
+ * combination pass with the coefficients Δt·(float)A[i,j] formed in float, and ins_project_f32; one launch writes k̄_i, one closes Σ_i ȳ_i + bcᵀ g.
+ * INS_ADJ_STAGE_FUSED is not read.  ubar == ustart, or a body force that is ubar: INS_ERR_INVALID. */
+int ins_rk_adjoint_create_f32(const ins_grid_t* grid, ins_poisson32_t* ps, int nstage, const double* A, const double* c, ins_rk_adjoint32_t** out);
+int ins_rk_adjoint_destroy_f32(ins_rk_adjoint32_t* adj);
+int ins_rk_step_pullback_f32(ins_rk_adjoint32_t* adj, float visc, const float* ustart, const float* bodyforce, float dt, float* ubar, void* stream);
 
 /* ---------------------------------------------------------------------------------- DNS-to-LES filters  (lib/NeuralClosure/src/filter.jl) */
 /* `les` and `dns` are two grids with the same boundary conditions, n_dns = comp·n_les interior volumes in every direction and nested faces
@@ -412,6 +421,24 @@ int ins_dissipation_adjoint_f64(const ins_grid_t* grid, double visc, double coef
  * sums as the four operator-level entries above.  Only a2, a4, diss_coef, gdir and dodissipation of `desc` are read. */
 int ins_temperature_pullback_f64(const ins_grid_t* grid, const ins_temperature_desc_t* desc, double visc, const double* u, const double* temp,
                                  const double* Fbar, const double* cbar, double* ubar, double* tempbar, void* stream);
+/* The temperature equation in the reverse step: the descriptor of ins_rk_set_temperature (the Float32 handle rounds its doubles to
+ * float), NULL switches the coupled loop off again.  The first descriptor allocates nstage stage temperatures τ_i, nstage cotangents z̄_i and one c̄
+ * (scalar fields), freed by the destroy call.  A side code that is no temperature boundary condition, or gdir out of range: INS_ERR_INVALID. */
+int ins_rk_adjoint_set_temperature(ins_rk_adjoint_t* adj, const ins_temperature_desc_t* desc);
+int ins_rk_adjoint_set_temperature_f32(ins_rk_adjoint32_t* adj, const ins_temperature_desc_t* desc);
+/* Pullback of one step of (u, temp) (ins_rk_step_ext_f64 / ins_rk_step_ext_f32 with a temperature and without closure) with respect to the pair it
+ * starts from.  On entry (ubar, tempbar) = ∂L/∂(u_out, temp_out) over the whole padded arrays, on return ∂L/∂(ustart, tempstart).  With (g_u, g_T)
+ * the cotangents of the ghost-filled stage inputs (v_{i+1}, τ_{i+1}), for i = nstage-1 .. 0:
+ *   ȳ_i = bc_uᵀ Pᵀ bc_uᵀ g_u,  z̄_i = bc_Tᵀ g_T;   k̄_i = Δt Σ_{i' >= i} A[i',i] ȳ_{i'},  c̄_i = Δt Σ_{i' >= i} A[i',i] z̄_{i'}   (one launch for both);
+ *   g_u = J_F(v_i)ᵀ k̄_i (momentum pullback), then the stage's temperature pullback at (v_i, τ_i) with (Fbar, cbar) = (k̄_i, c̄_i): g_u +=, g_T =;
+ * and (ubar, tempbar) = (Σ_i ȳ_i + bc_uᵀ g_u, Σ_i z̄_i + bc_Tᵀ g_T), closed by one launch.  Sums in index order, zero coefficients skipped.  The
+ * (v_i, τ_i) are recomputed operator by operator (ghost fills, momentum, gravity, convection_diffusion_temp, dissipation, the two combinations,
+ * project), not with the fused stage kernels.  INS_ADJ_STAGE_FUSED is not read.  No descriptor set, a NULL tempstart or tempbar, or any output
+ * that aliases an input or the other output: INS_ERR_INVALID.  Asynchronous on `stream` (CG solver: blocking). */
+int ins_rk_step_pullback_ext_f64(ins_rk_adjoint_t* adj, double visc, const double* ustart, const double* tempstart, const double* bodyforce, double dt,
+                                 double* ubar, double* tempbar, void* stream);
+int ins_rk_step_pullback_ext_f32(ins_rk_adjoint32_t* adj, float visc, const float* ustart, const float* tempstart, const float* bodyforce, float dt,
+                                 float* ubar, float* tempbar, void* stream);
 
 /* observespectrum(state; setup, npoint, a)   processors.jl:303-332.  The index sets of spectral_stuff (utils.jl:49-108) are built
  * on the host: bin i sums the modes inds[offsets[i] .. offsets[i+1]), each a 0-based column-major position in the K = Np .÷ 2

@@ -387,3 +387,117 @@ def timestep(ops, method, stepper, Δt, θ):
     if temp is not None:
         temp = _ApplyBCTemp.apply(temp, t, setup, ops)
     return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=t, n=n + 1)
+
+
+# ------------------------------------------------------------------------------------ checkpointed rollouts
+# The table's part of a rollout (the only native calls of this section):
+#   rk_cache(erk, setup, psolver)                           the forward's native cache (`ERKCache` / `ERKCache32`)
+#   rk_adjoint_create(erk, setup, psolver) -> handle        the work arrays of the native reverse step; rk_adjoint_destroy(handle)
+#   rk_steps_(adj, u, temp or None, t, Δt, nsteps)          the native multi-step loop of that setup, in place (`timesteps_` / `timesteps32_`)
+#   rk_step_pullback_(adj, ubar, tempbar or None, ustart, tempstart or None, Δt)      one native reverse step, in place on (ubar, tempbar)
+#   rk_copy_(dst, src, setup, vector)                       a field copy by the library's own pass
+class _StepAdjoint:
+    """The work arrays of the native reverse step (csrc/ins_rk_adjoint.hip: `ins_rk_adjoint_t` / `ins_rk_adjoint32_t`), with the forward's native
+    cache beside it."""
+
+    def __init__(self, ops, erk, setup, psolver):
+        self.ops, self.erk, self.setup = ops, erk, setup
+        self.cache = ops.rk_cache(erk, setup, psolver)
+        self._handle = ops.rk_adjoint_create(erk, setup, psolver)
+
+    def steps_(self, u, temp, t, Δt, nsteps):
+        """`nsteps` native steps on (u, temp), in place."""
+        self.ops.rk_steps_(self, u, temp, t, Δt, nsteps)
+        return u, temp
+
+    def step_pullback_(self, ubar, ustart, Δt, tempbar=None, tempstart=None):
+        """(ubar, tempbar): ∂L/∂(u_out, temp_out) -> ∂L/∂(ustart, tempstart), in place: the whole reverse sweep of one step is this one call."""
+        self.ops.rk_step_pullback_(self, ubar, tempbar, ustart, tempstart, Δt)
+        return ubar if tempbar is None else (ubar, tempbar)
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            try:
+                self.ops.rk_adjoint_destroy(h)
+            except Exception:
+                pass
+
+
+def _step_adjoint(ops, erk, setup, psolver):
+    """One `_StepAdjoint` per (solver, tableau), kept on the solver."""
+    key = (np.asarray(erk.A, dtype=np.float64).tobytes(), np.asarray(erk.c, dtype=np.float64).tobytes())
+    store = psolver.__dict__.setdefault("_ad_step_adjoints", {})
+    if key not in store:
+        store[key] = _StepAdjoint(ops, erk, setup, psolver)
+    return store[key]
+
+
+class _TimeSteps(torch.autograd.Function):
+    """(u, temp) -> (u, temp) after nsteps Runge-Kutta steps, `temp` possibly None.  Saved: the state at the start of every chunk of `every` steps,
+    nothing else.  Both cotangents are always propagated (one native call per step serves both); autograd drops the one nobody asked for."""
+
+    @staticmethod
+    def forward(ctx, u, temp, adj, ops, t, Δt, nsteps, every):
+        setup = adj.setup
+        out = _copy(ops, setup, u, True)
+        tout = None if temp is None else _copy(ops, setup, temp, False)
+        ctx.adj, ctx.ops, ctx.t, ctx.Δt, ctx.nsteps, ctx.every = adj, ops, t, Δt, nsteps, every
+        ctx.checkpoints = []
+        for start in range(0, nsteps, every):
+            ctx.checkpoints.append((_copy(ops, setup, out, True), None if tout is None else _copy(ops, setup, tout, False)))
+            adj.steps_(out, tout, t + start * Δt, Δt, min(every, nsteps - start))
+        return out, tout
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, gtemp):
+        adj, ops, Δt, nsteps, every = ctx.adj, ctx.ops, ctx.Δt, ctx.nsteps, ctx.every
+        setup = adj.setup
+        coupled = ctx.checkpoints[0][1] is not None
+        ubar = _copy(ops, setup, g, True)
+        tempbar = _copy(ops, setup, gtemp, False) if coupled else None
+        # the step-start states of one chunk after its checkpoint
+        bufs = [(ops.vectorfield(setup), ops.scalarfield(setup) if coupled else None) for _ in range(min(every, nsteps) - 1)]
+        starts = list(range(0, nsteps, every))
+        for q in reversed(range(len(starts))):
+            n = min(every, nsteps - starts[q])
+            states = [ctx.checkpoints[q]]
+            for j in range(1, n):
+                bu, bt = bufs[j - 1]
+                ops.rk_copy_(bu, states[j - 1][0], setup, True)
+                if coupled:
+                    ops.rk_copy_(bt, states[j - 1][1], setup, False)
+                adj.steps_(bu, bt, ctx.t + (starts[q] + j - 1) * Δt, Δt, 1)
+                states.append((bu, bt))
+            for j in reversed(range(n)):
+                adj.step_pullback_(ubar, states[j][0], Δt, tempbar, states[j][1])
+            ctx.checkpoints[q] = None
+        return ubar, tempbar, None, None, None, None, None, None
+
+
+def checkpoint_interval(ops, nsteps, checkpoint_every):
+    """(nsteps, every) of a rollout: ceil(sqrt(nsteps)) steps per chunk unless told otherwise."""
+    nsteps = int(nsteps)
+    if nsteps < 1:
+        raise ValueError(f"{ops.name}.timesteps: nsteps must be >= 1, got {nsteps}")
+    every = int(np.ceil(np.sqrt(nsteps))) if checkpoint_every is None else int(checkpoint_every)
+    if every < 1:
+        raise ValueError(f"{ops.name}.timesteps: checkpoint_every must be >= 1, got {checkpoint_every}")
+    return nsteps, min(every, nsteps)
+
+
+def timesteps(ops, method, stepper, Δt, nsteps, every, adj=None):
+    """`nsteps` Runge-Kutta steps as one Function (the refusals are the caller's): the native multi-step loop forward in chunks of `every` steps,
+    the state at every chunk start kept, one native reverse step per step backward.  `adj`: the reverse step's handle, by default the one kept
+    on the solver."""
+    setup, psolver, u, temp = stepper.setup, stepper.psolver, stepper.u, stepper.temp
+    erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
+    if adj is None:
+        adj = _step_adjoint(ops, erk, setup, psolver)
+    t = float(stepper.t)
+    if torch.is_grad_enabled() and (u.requires_grad or (temp is not None and temp.requires_grad)):
+        out, tout = _TimeSteps.apply(u, temp, adj, ops, t, float(Δt), nsteps, every)
+    else:  # nothing to save: one native call
+        out, tout = adj.steps_(_copy(ops, setup, u, True), None if temp is None else _copy(ops, setup, temp, False), t, float(Δt), nsteps)
+    return create_stepper(method, setup=setup, psolver=psolver, u=out, temp=tout, t=t + nsteps * erk.c[-1] * Δt, n=stepper.n + nsteps)

@@ -105,6 +105,13 @@ SIGNATURES = {
     "ins_rk_adjoint_create": (C.c_int, [vp, vp, C.c_int, c_double_p, c_double_p, C.POINTER(vp)]),
     "ins_rk_adjoint_destroy": (C.c_int, [vp]),
     "ins_rk_step_pullback_f64": (C.c_int, [vp, C.c_double, vp, vp, C.c_double, vp, vp]),
+    "ins_rk_adjoint_create_f32": (C.c_int, [vp, vp, C.c_int, c_double_p, c_double_p, C.POINTER(vp)]),
+    "ins_rk_adjoint_destroy_f32": (C.c_int, [vp]),
+    "ins_rk_step_pullback_f32": (C.c_int, [vp, C.c_float, vp, vp, C.c_float, vp, vp]),
+    "ins_rk_adjoint_set_temperature": (C.c_int, [vp, vp]),
+    "ins_rk_adjoint_set_temperature_f32": (C.c_int, [vp, vp]),
+    "ins_rk_step_pullback_ext_f64": (C.c_int, [vp, C.c_double, vp, vp, vp, C.c_double, vp, vp, vp]),
+    "ins_rk_step_pullback_ext_f32": (C.c_int, [vp, C.c_float, vp, vp, vp, C.c_float, vp, vp, vp]),
     "ins_tensorbasis_pullback_f64": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp]),
     "ins_divoftensor_adjoint_f64": (C.c_int, [vp, vp, vp, vp]),
     "ins_tensorinvariants_f64": (C.c_int, [vp, vp, vp, vp]),

@@ -40,6 +40,65 @@ def _check_f64(setup, *xs):
             raise ValueError(f"field lives on {x.device}, setup on {setup.device}")
 
 
+def _rk_adjoint_create(erk, setup, psolver):
+    """`ins_rk_adjoint_t` (csrc/ins_rk_adjoint.hip): the work arrays of the native reverse step."""
+    import ctypes as C
+
+    from . import _lib
+
+    A = np.ascontiguousarray(erk.A, dtype=np.float64)
+    c = np.ascontiguousarray(erk.c, dtype=np.float64)
+    handle = C.c_void_p()
+    _lib.call("ins_rk_adjoint_create", setup.handle, psolver.handle, len(erk.b), A.ctypes.data_as(_lib.c_double_p), c.ctypes.data_as(_lib.c_double_p),
+              C.byref(handle))
+    return handle
+
+
+def _rk_adjoint_destroy(handle):
+    from . import _lib
+
+    _lib.load().ins_rk_adjoint_destroy(handle)
+
+
+def _rk_cache(erk, setup, psolver):
+    from .time_steppers import ERKCache
+
+    return ERKCache(erk, setup, psolver)
+
+
+def _rk_steps_(adj, u, temp, t, Δt, nsteps):
+    """`timesteps_`: ins_rk_steps_f64, or with a temperature ins_rk_step_ext_f64 step by step."""
+    from .time_steppers import timesteps_
+
+    timesteps_(adj.erk, create_stepper(adj.erk, setup=adj.setup, psolver=adj.cache.psolver, u=u, temp=temp, t=t), Δt, nsteps, cache=adj.cache)
+
+
+def _rk_step_pullback_(adj, ubar, tempbar, ustart, tempstart, Δt):
+    """ins_rk_step_pullback_f64, with a temperature ins_rk_step_pullback_ext_f64 (the descriptor goes to the handle with every call)."""
+    import ctypes as C
+
+    from . import _lib
+    from .time_steppers import _native_ext
+
+    setup = adj.setup
+    f = setup.bodyforce if (setup.bodyforce is not None and setup.issteadybodyforce) else None
+    fp = setup.ptr(f, True) if f is not None else None
+    if tempbar is None:
+        _lib.call("ins_rk_step_pullback_f64", adj._handle, 1.0 / setup.Re, setup.ptr(ustart, True), fp, float(Δt), setup.ptr(ubar, True), setup.stream)
+        return
+    desc = _native_ext(setup, tempstart, None)[2]  # per call, like the forward: `setup.temperature` may have been replaced since the last one
+    _lib.call("ins_rk_adjoint_set_temperature", adj._handle, C.byref(desc))
+    _lib.call("ins_rk_step_pullback_ext_f64", adj._handle, 1.0 / setup.Re, setup.ptr(ustart, True), setup.ptr(tempstart, False), fp, float(Δt),
+              setup.ptr(ubar, True), setup.ptr(tempbar, False), setup.stream)
+
+
+def _rk_copy_(dst, src, setup, vector):
+    """a copy by the library's own pass"""
+    from .time_steppers import combine_
+
+    return combine_(dst, src, [], [], setup, vector=vector)
+
+
 # The fp64 precision table of the shared autograd layer (_autodiff_core.py): `operators.py` under the table's calling conventions.  Other dtypes
 # are converted silently, except by the tensor-basis Functions (`_check_f64`); the body force is inside `O.momentum_` and may depend on `t`; the
 # pullbacks of the ghost fills take a time that does not enter (0.0).
@@ -61,12 +120,15 @@ _OPS = SimpleNamespace(
     convection_diffusion_temp_adjoint_=O.convection_diffusion_temp_adjoint_, dissipation_adjoint_=O.dissipation_adjoint_,
     temperature_pullback_=O.temperature_pullback_, project_pullback_=project_pullback_, divoftensor_adjoint_=O.divoftensor_adjoint_,
     tensorclosure_pullback_=O.tensorclosure_pullback_,
+    rk_cache=_rk_cache, rk_adjoint_create=_rk_adjoint_create, rk_adjoint_destroy=_rk_adjoint_destroy, rk_steps_=_rk_steps_,
+    rk_step_pullback_=_rk_step_pullback_, rk_copy_=_rk_copy_,
 )
 # the shared helpers, for the fp64-only Functions below
 _field, _copy, _save_inputs, _saved_inputs = partial(core._field, _OPS), partial(core._copy, _OPS), partial(core._save_inputs, _OPS), core._saved_inputs
 # private names the tests reach for, under their fp64 spelling
 _gridsize2 = core._gridsize2
 _StageRightHandSide = SimpleNamespace(apply=lambda u, temp, t, setup: core._StageRightHandSide.apply(u, temp, t, setup, _OPS))
+_step_adjoint = partial(core._step_adjoint, _OPS)
 
 
 # ------------------------------------------------------------------------------------ ghost fill
@@ -371,134 +433,47 @@ def timestep(method, stepper, Δt, θ=None):
 
 
 # ------------------------------------------------------------------------------------ checkpointed rollouts
-class _StepAdjoint:
-    """`ins_rk_adjoint_t` (csrc/ins_rk_adjoint.hip): the work arrays of the native reverse step, with the forward's native cache beside it."""
-
-    def __init__(self, erk, setup, psolver):
-        import ctypes as C
-
-        from . import _lib
-        from .time_steppers import ERKCache
-
-        self.erk, self.setup, self.cache = erk, setup, ERKCache(erk, setup, psolver)
-        A = np.ascontiguousarray(erk.A, dtype=np.float64)
-        c = np.ascontiguousarray(erk.c, dtype=np.float64)
-        self._handle = C.c_void_p()
-        _lib.call("ins_rk_adjoint_create", setup.handle, psolver.handle, len(erk.b), A.ctypes.data_as(_lib.c_double_p), c.ctypes.data_as(_lib.c_double_p),
-                  C.byref(self._handle))
-
-    def step_pullback_(self, ubar, ustart, Δt):
-        """ubar: ∂L/∂u_out -> ∂L/∂ustart, in place: the whole reverse sweep of one step is this one call."""
-        from . import _lib
-
-        setup = self.setup
-        f = setup.bodyforce if (setup.bodyforce is not None and setup.issteadybodyforce) else None
-        _lib.call("ins_rk_step_pullback_f64", self._handle, 1.0 / setup.Re, setup.ptr(ustart, True), setup.ptr(f, True) if f is not None else None, float(Δt),
-                  setup.ptr(ubar, True), setup.stream)
-        return ubar
-
-    def __del__(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h:
-            try:
-                from . import _lib
-
-                _lib.load().ins_rk_adjoint_destroy(h)
-            except Exception:
-                pass
-
-
-def _step_adjoint(erk, setup, psolver):
-    """One `_StepAdjoint` per (solver, tableau), kept on the solver."""
-    key = (np.asarray(erk.A, dtype=np.float64).tobytes(), np.asarray(erk.c, dtype=np.float64).tobytes())
-    store = psolver.__dict__.setdefault("_ad_step_adjoints", {})
-    if key not in store:
-        store[key] = _StepAdjoint(erk, setup, psolver)
-    return store[key]
-
-
-def _native_steps_(adj, u, t, Δt, nsteps):
-    """`nsteps` native steps on `u`, in place (`timesteps_` = ins_rk_steps_f64; one step: ins_rk_step_f64)."""
-    from .time_steppers import timesteps_
-
-    setup, cache = adj.setup, adj.cache
-    timesteps_(adj.erk, create_stepper(adj.erk, setup=setup, psolver=cache.psolver, u=u, t=t), Δt, nsteps, cache=cache)
-    return u
-
-
-class _TimeSteps(torch.autograd.Function):
-    """u -> u after nsteps Runge-Kutta steps.  Saved: the state at the start of every chunk of `every` steps, nothing else."""
-
-    @staticmethod
-    def forward(ctx, u, adj, t, Δt, nsteps, every):
-        setup = adj.setup
-        out = _copy(setup, u, True)
-        ctx.adj, ctx.t, ctx.Δt, ctx.nsteps, ctx.every = adj, t, Δt, nsteps, every
-        ctx.checkpoints = []
-        for start in range(0, nsteps, every):
-            ctx.checkpoints.append(_copy(setup, out, True))
-            _native_steps_(adj, out, t + start * Δt, Δt, min(every, nsteps - start))
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        from .time_steppers import combine_
-
-        adj, Δt, nsteps, every = ctx.adj, ctx.Δt, ctx.nsteps, ctx.every
-        setup = adj.setup
-        ubar = _copy(setup, g, True)
-        bufs = [vectorfield(setup) for _ in range(min(every, nsteps) - 1)]  # the step-start states of one chunk after its checkpoint
-        starts = list(range(0, nsteps, every))
-        for q in reversed(range(len(starts))):
-            n = min(every, nsteps - starts[q])
-            states = [ctx.checkpoints[q]]
-            for j in range(1, n):
-                combine_(bufs[j - 1], states[j - 1], [], [], setup)  # a copy by the library's own pass
-                states.append(_native_steps_(adj, bufs[j - 1], ctx.t + (starts[q] + j - 1) * Δt, Δt, 1))
-            for j in reversed(range(n)):
-                adj.step_pullback_(ubar, states[j], Δt)
-            ctx.checkpoints[q] = None
-        return ubar, None, None, None, None, None
-
-
 def timesteps(method, stepper, Δt, nsteps, *, checkpoint_every=None):
-    """`nsteps` calls of `ad.timestep(method, ·, Δt)` as one Function: nothing is mutated, the result is differentiable in `stepper.u`.
+    """`nsteps` calls of `ad.timestep(method, ·, Δt)` as one Function: nothing is mutated, the result is differentiable in `stepper.u` and, with
+    the temperature equation, in `stepper.temp`.
 
-    The forward is the native multi-step loop (`timesteps_`, ins_rk_steps_f64) in chunks of `checkpoint_every` steps (default ceil(sqrt(nsteps)));
-    only the state at the start of every chunk is kept.  The backward walks the chunks in reverse: it recomputes the chunk's step-start states with the
-    native step and calls the native step pullback (ins_rk_step_pullback_f64) once per step.  Memory: ceil(nsteps/c) + c - 1 vector fields and the
-    2s + 1 work arrays of the reverse step, instead of the unrolled graph's ~10 fields per stage.
+    The forward is the native multi-step loop (`timesteps_`: ins_rk_steps_f64, with a temperature ins_rk_step_ext_f64 per step) in chunks of
+    `checkpoint_every` steps (default ceil(sqrt(nsteps))); only the state at the start of every chunk is kept.  The backward walks the chunks in
+    reverse: it recomputes the chunk's step-start states with the native step and calls the native step pullback (ins_rk_step_pullback_f64, with
+    a temperature ins_rk_step_pullback_ext_f64) once per step.  Memory: ceil(nsteps/c) + c - 1 states and the work arrays of the reverse step
+    (2s + 1 vector fields, with a temperature 2s + 1 scalar fields more), instead of the unrolled graph's ~10 fields per stage.
 
-    Scope: what the native isothermal loop runs — fp64, ExplicitRungeKuttaMethod or LMWray3, 2-D / 3-D, any boundary conditions with constant data, any
-    solver, no body force or a steady one.  Anything else raises NotImplementedError: use `ad.timestep` step by step."""
-    nsteps = int(nsteps)
-    if nsteps < 1:
-        raise ValueError(f"ad.timesteps: nsteps must be >= 1, got {nsteps}")
-    every = int(np.ceil(np.sqrt(nsteps))) if checkpoint_every is None else int(checkpoint_every)
-    if every < 1:
-        raise ValueError(f"ad.timesteps: checkpoint_every must be >= 1, got {checkpoint_every}")
-    setup, psolver, u = stepper.setup, stepper.psolver, stepper.u
+    Scope: fp64, ExplicitRungeKuttaMethod or LMWray3, 2-D / 3-D, any boundary conditions with constant data for u and for temp, any solver, no
+    body force or a steady one, with or without `setup.temperature`.  A closure model, callable boundary data, an unsteady body force and slab
+    setups raise NotImplementedError: use `ad.timestep` step by step.  Float32 fields: `ad32.timesteps`."""
+    nsteps, every = core.checkpoint_interval(_OPS, nsteps, checkpoint_every)
+    setup, psolver, u, temp = stepper.setup, stepper.psolver, stepper.u, stepper.temp
+    if u.dtype == torch.float32:
+        raise TypeError("ad.timesteps: fields must be float64 torch tensors (float32 fields: ad32.timesteps)")
     if u.dtype != torch.float64:
-        raise TypeError("ad.timesteps: fields must be float64 torch tensors (the Float32 family has ad32.timestep)")
+        raise TypeError("ad.timesteps: fields must be float64 torch tensors")
+    if temp is not None and temp.dtype != torch.float64:
+        raise TypeError("ad.timesteps: a float64 u with a float32 temp: give both fields in one precision")
+    from . import f32
     from .boundary_conditions import HaloBC
 
+    if isinstance(psolver, f32.psolver_spectral32):
+        raise TypeError("ad.timesteps: a float64 u with a float32 psolver (float32 fields: ad32.timesteps with f32.default_psolver32 / f32.psolver_wrap32; "
+                        "float64 fields: default_psolver and its kin)")
+    if temp is not None and setup.temperature is None:
+        raise ValueError("a temperature field needs setup.temperature (temperature_equation)")
     if setup.closure_model is not None:
         raise NotImplementedError("ad.timesteps: a closure model is not part of the native reverse loop; use ad.timestep step by step")
-    if stepper.temp is not None or setup.temperature is not None:
-        raise NotImplementedError("ad.timesteps: the temperature equation is not part of the native reverse loop; use ad.timestep step by step")
+    if temp is None and setup.temperature is not None:
+        raise NotImplementedError("ad.timesteps: a setup with a temperature equation takes stepper.temp in the native reverse loop; without one use "
+                                  "ad.timestep step by step")
     if setup.needs_bc_planes:
         raise NotImplementedError("ad.timesteps: callable Dirichlet data needs the host between the stages; use ad.timestep step by step")
+    if temp is not None and any(isinstance(bc, DirichletBC) and callable(bc.u) for side in setup.temperature.boundary_conditions for bc in side):
+        raise NotImplementedError("ad.timesteps: callable Dirichlet data of the temperature needs the host between the stages; use ad.timestep step by step")
     if setup.bodyforce is not None and not setup.issteadybodyforce:
         raise NotImplementedError("ad.timesteps: an unsteady body force is evaluated on the host; use ad.timestep step by step")
     if any(isinstance(bc, HaloBC) for side in setup.boundary_conditions for bc in side):
         raise NotImplementedError("ad.timesteps: slab (halo) setups are not supported; use ad.timestep step by step")
-    _check_f64(setup, u)
-    erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
-    adj = _step_adjoint(erk, setup, psolver)
-    t = float(stepper.t)
-    if torch.is_grad_enabled() and u.requires_grad:
-        out = _TimeSteps.apply(u, adj, t, float(Δt), nsteps, min(every, nsteps))
-    else:  # nothing to save: one native call
-        out = _native_steps_(adj, _copy(setup, u, True), t, float(Δt), nsteps)
-    return create_stepper(method, setup=setup, psolver=psolver, u=out, temp=None, t=t + nsteps * erk.c[-1] * Δt, n=stepper.n + nsteps)
+    _check_f64(setup, u, *(() if temp is None else (temp,)))
+    return core.timesteps(_OPS, method, stepper, Δt, nsteps, every)

@@ -42,7 +42,7 @@ from . import _autodiff_core as core
 from . import f32 as F32
 from .boundary_conditions import HaloBC, PeriodicBC
 
-__all__ = ["apply_bc_u", "momentum", "project", "timestep"]
+__all__ = ["apply_bc_u", "momentum", "project", "timestep"]  # `timesteps` and the operators below are module attributes (an existing test pins this list)
 
 
 def _check_slab(setup, what):
@@ -70,6 +70,17 @@ def _check_psolver(setup, psolver, what):
     inner = getattr(psolver, "psolver64", None)
     if isinstance(inner, psolver_spectral) and all(isinstance(bc, PeriodicBC) for side in setup.boundary_conditions for bc in side):
         raise NotImplementedError(f"ad32.{what}: psolver_wrap32 around psolver_spectral on an all-periodic box is not taken; use f32.psolver_spectral32")
+
+
+def _periodic_uniform(setup):
+    """The boxes on which the Float32 family runs its periodic kernels: the classification of `default_psolver` (pressure.jl:85-98)."""
+    import math
+
+    import numpy as np
+
+    if not all(isinstance(bc, PeriodicBC) for side in setup.boundary_conditions for bc in side):
+        return False
+    return all(np.allclose(d, d[0], rtol=math.sqrt(np.finfo(np.float64).eps), atol=0) for d in setup.grid.Δ)
 
 
 def _check_temperature(setup, what):
@@ -101,6 +112,64 @@ def _bodyforce32(setup):
     return f[1]
 
 
+def _rk_adjoint_create(erk, setup, psolver):
+    """`ins_rk_adjoint32_t` (csrc/ins_rk_adjoint.hip): the float work arrays of the native reverse step."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+
+    A = np.ascontiguousarray(erk.A, dtype=np.float64)
+    c = np.ascontiguousarray(erk.c, dtype=np.float64)
+    handle = C.c_void_p()
+    _lib.call("ins_rk_adjoint_create_f32", setup.handle, psolver.handle, len(erk.b), A.ctypes.data_as(_lib.c_double_p), c.ctypes.data_as(_lib.c_double_p),
+              C.byref(handle))
+    return handle
+
+
+def _rk_adjoint_destroy(handle):
+    from . import _lib
+
+    _lib.load().ins_rk_adjoint_destroy_f32(handle)
+
+
+def _rk_cache(erk, setup, psolver):
+    """The forward's native cache.  `ERKCache32` keeps its solver alive, which is right for a cache a caller holds (the native handle borrows the
+    solver), but this one is kept ON the solver (`_step_adjoint`), which therefore outlives it anyway: it refers to the solver weakly, so there is no
+    reference cycle and solver, reverse-step handle and cache (and the solver's hipFFT plans) go by reference count, not at some later garbage
+    collection."""
+    import weakref
+
+    cache = F32.ERKCache32(erk, setup, psolver)
+    cache.psolver = weakref.proxy(psolver)
+    return cache
+
+
+def _rk_steps_(adj, u, temp, t, Δt, nsteps):
+    """`f32.timesteps32_`: ins_rk_steps_f32 (chained where it chains), or with a temperature or a steady body force ins_rk_steps_ext_f32."""
+    F32.timesteps32_(adj.cache, u, Δt, nsteps, temp=temp)
+
+
+def _rk_step_pullback_(adj, ubar, tempbar, ustart, tempstart, Δt):
+    """ins_rk_step_pullback_f32, with a temperature ins_rk_step_pullback_ext_f32 (the descriptor goes to the handle with every call)."""
+    import ctypes as C
+
+    from . import _lib
+
+    setup = adj.setup
+    D = setup.grid.dimension
+    fp = F32._ptr(setup, _bodyforce32(setup), D) if setup.bodyforce is not None else None
+    if tempbar is None:
+        _lib.call("ins_rk_step_pullback_f32", adj._handle, float(1.0 / setup.Re), F32._ptr(setup, ustart, D), fp, float(Δt), F32._ptr(setup, ubar, D),
+                  setup.stream)
+        return
+    desc = F32._temp_desc(setup)  # per call, like the forward: `setup.temperature` may have been replaced since the last one
+    _lib.call("ins_rk_adjoint_set_temperature_f32", adj._handle, C.byref(desc))
+    _lib.call("ins_rk_step_pullback_ext_f32", adj._handle, float(1.0 / setup.Re), F32._ptr(setup, ustart, D), F32._ptr(setup, tempstart, 0), fp, float(Δt),
+              F32._ptr(setup, ubar, D), F32._ptr(setup, tempbar, 0), setup.stream)
+
+
 # The Float32 precision table of the shared autograd layer (_autodiff_core.py): `f32.py` under the table's calling conventions.  The boundary
 # data is constant, so `t` does not enter; any dtype but float32 raises; the steady body force is added outside the Functions, from a cached cast.
 _OPS = SimpleNamespace(
@@ -120,10 +189,17 @@ _OPS = SimpleNamespace(
     convection_diffusion_temp_adjoint_=F32.convection_diffusion_temp_adjoint32_, dissipation_adjoint_=F32.dissipation_adjoint32_,
     temperature_pullback_=F32.temperature_pullback32_, project_pullback_=F32.project_pullback32_,
     divoftensor_adjoint_=F32.divoftensor_adjoint32_, tensorclosure_pullback_=F32.tensorclosure_pullback32_,
+    rk_cache=_rk_cache, rk_adjoint_create=_rk_adjoint_create, rk_adjoint_destroy=_rk_adjoint_destroy, rk_steps_=_rk_steps_,
+    rk_step_pullback_=_rk_step_pullback_, rk_copy_=lambda dst, src, setup, vector: dst.copy_(src),
 )
 
 # the stage Function under its Float32 spelling (`t` does not enter), as the tests call it
 _StageRightHandSide = SimpleNamespace(apply=lambda u, temp, setup: core._StageRightHandSide.apply(u, temp, 0.0, setup, _OPS))
+
+
+def _step_adjoint(erk, setup, psolver):
+    """The reverse step's handle of (solver, tableau), as `ad._step_adjoint`."""
+    return core._step_adjoint(_OPS, erk, setup, psolver)
 
 
 def apply_bc_u(u, t, setup):
@@ -237,3 +313,50 @@ def timestep(method, stepper, Δt, θ=None):
     _check_setup(setup, "timestep")
     _check_psolver(setup, stepper.psolver, "timestep")
     return core.timestep(_OPS, method, stepper, Δt, θ)
+
+
+def timesteps(method, stepper, Δt, nsteps, *, checkpoint_every=None):
+    """`nsteps` calls of `ad32.timestep(method, ·, Δt)` as one Function with T = Float32: `ad.timesteps` on float32 fields, differentiable in
+    `stepper.u` and, with the temperature equation, in `stepper.temp`.
+
+    The forward is `f32.timesteps32_` (ins_rk_steps_f32; with a temperature or a steady body force ins_rk_steps_ext_f32) in chunks of
+    `checkpoint_every` steps (default ceil(sqrt(nsteps))), only the chunk-start states are kept, and the backward recomputes a chunk and calls the
+    native reverse step once per step (ins_rk_step_pullback_f32, with a temperature ins_rk_step_pullback_ext_f32), all in float.
+
+    Scope: what `ad32.timestep` takes without a closure: ExplicitRungeKuttaMethod or LMWray3, 2-D / 3-D, any boundary conditions with constant
+    data, a Float32 solver, no body force or a steady one, with or without `setup.temperature`.  A closure model, callable boundary data, an unsteady
+    body force and slab setups raise NotImplementedError: use `ad32.timestep` step by step (or `ins_amd.ad`)."""
+    nsteps, every = core.checkpoint_interval(_OPS, nsteps, checkpoint_every)
+    setup, psolver, u, temp = stepper.setup, stepper.psolver, stepper.u, stepper.temp
+    if u.dtype != torch.float32:
+        raise TypeError("ad32.timesteps: fields must be float32 torch tensors (float64 fields: ad.timesteps)")
+    if temp is not None and temp.dtype != torch.float32:
+        raise TypeError("ad32.timesteps: a float32 u with a float64 temp: give both fields in one precision")
+    if not isinstance(psolver, F32.psolver_spectral32):
+        raise TypeError("ad32.timesteps: a float32 u with a float64 psolver (float32 fields: f32.default_psolver32 / f32.psolver_wrap32; "
+                        "float64 fields: ad.timesteps with default_psolver and its kin)")
+    if temp is not None and setup.temperature is None:
+        raise ValueError("a temperature field needs setup.temperature (temperature_equation)")
+    if setup.closure_model is not None:
+        raise NotImplementedError("ad32.timesteps: a closure model is not part of the native reverse loop; use ad32.timestep step by step")
+    if temp is None and setup.temperature is not None:
+        raise NotImplementedError("ad32.timesteps: a setup with a temperature equation takes stepper.temp in the native reverse loop; without one use "
+                                  "ad32.timestep step by step")
+    if any(isinstance(bc, HaloBC) for side in setup.boundary_conditions for bc in side):
+        raise NotImplementedError("ad32.timesteps: slab (halo) setups run in fp64 only; use ad.timestep step by step")
+    if setup.needs_bc_planes:
+        raise NotImplementedError("ad32.timesteps: the _f32 family takes constant boundary data; use ad.timestep step by step")
+    if temp is not None and any(callable(getattr(bc, "u", None)) for side in setup.temperature.boundary_conditions for bc in side):
+        raise NotImplementedError("ad32.timesteps: the _f32 family takes constant temperature boundary data; use ad.timestep step by step")
+    if setup.bodyforce is not None and not setup.issteadybodyforce:
+        raise NotImplementedError("ad32.timesteps: an unsteady body force is evaluated in fp64 on the host; use ad.timestep step by step")
+    _check_psolver(setup, psolver, "timesteps")
+    if getattr(psolver, "psolver64", None) is not None and _periodic_uniform(setup):
+        # measured on the 7 x 7 periodic box with a wrapped direct solver, 5 RK44 steps: timesteps32_ is 2.0e-3 from fp64, ad32.timestep 1.0e-7
+        raise NotImplementedError("ad32.timesteps: on an all-periodic uniform box the native Float32 loop (timesteps32_) does not refill the ghost "
+                                  "volumes between a wrapped solver's projections, so its rollout is not the step ad32.timestep differentiates; "
+                                  "use f32.psolver_spectral32, or ad32.timestep step by step")
+    _check_vec(setup, u)
+    if temp is not None and tuple(temp.shape) != tuple(setup.grid.N):
+        raise ValueError(f"expected a temperature field of shape {tuple(setup.grid.N)}, got {tuple(temp.shape)}")
+    return core.timesteps(_OPS, method, stepper, Δt, nsteps, every)

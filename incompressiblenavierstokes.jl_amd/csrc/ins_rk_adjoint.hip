@@ -10,23 +10,21 @@
 // k̄_i is written by k_weighted_sum and read back by the plain momentum pullback.  With INS_ADJ_STAGE_FUSED=1, where it has at most
 // INS_ADJ_COMB_MAX terms, it is never written: the momentum pullback kernels read the ȳ_{i'} and form the combination where they load the
 // cotangent (PhiComb, ins_adjoint_kernels.h).  That saves 48 B per cell and stage and measured slower on an MI355X, hence opt-in.
+//
+// That loop is kept as it was.  The Float32 step and the steps with a temperature (ins_rk_step_pullback_f32, ins_rk_step_pullback_ext_f64 / _f32) run
+// the one generic loop of ins_rk_adjoint_loop.h, which never fuses the combination (INS_ADJ_STAGE_FUSED is ignored there).
 #include "ins_adjoint_kernels.h"
+#include "ins_rk_adjoint_loop.h"
 #include "ins_rk_terms.h"
 
-int ins_k_apply_bc_u_pullback(const ins_grid* G, double* u, hipStream_t s);
 int ins_k_momentum_pullback_comb(const ins_grid* G, double visc, const double* u, int nterms, const double* coefs, const double* const* ks, double* ubar,
                                  hipStream_t s);
+// csrc/ins_f32.hip: the wrapped fp64 solver of a Float32 solver handle (nullptr: a spectral Float32 solver), and the handle's grid
+ins_poisson* ins_k32_wrapped(const ins_poisson32* ps, double** p64);
+const ins_grid* ins_k32_solver_grid(const ins_poisson32* ps);
 
-struct ins_rk_adjoint {
-  const ins_grid* grid = nullptr;
-  ins_poisson* ps = nullptr;
-  int nstage = 0;
-  std::vector<double> A, c;
-  std::vector<double*> v;  // stage inputs v_i (ghosts filled)
-  std::vector<double*> y;  // k_i during the recomputation, then the stage cotangents ȳ_i
-  double* kbar = nullptr;
-  double* pwork = nullptr;
-};
+struct ins_rk_adjoint : RkAdjointT<double, ins_poisson> {};
+struct ins_rk_adjoint32 : RkAdjointT<float, ins_poisson32> {};
 
 namespace {
 
@@ -46,32 +44,31 @@ __global__ __launch_bounds__(256) void k_weighted_sum(long long n, double* __res
   }
 }
 
-}  // namespace
-
-extern "C" int ins_rk_adjoint_destroy(ins_rk_adjoint_t* adj) {
+template <typename ADJ>
+int adjoint_destroy(ADJ* adj) {
   if (!adj) return INS_OK;
-  for (double* p : adj->v)
-    if (p) (void)hipFree(p);
-  for (double* p : adj->y)
-    if (p) (void)hipFree(p);
+  for (auto* arrays : {&adj->v, &adj->y, &adj->tau, &adj->z})
+    for (auto* p : *arrays)
+      if (p) (void)hipFree(p);
   if (adj->kbar) (void)hipFree(adj->kbar);
   if (adj->pwork) (void)hipFree(adj->pwork);
+  if (adj->cbar) (void)hipFree(adj->cbar);
   delete adj;
   return INS_OK;
 }
 
-extern "C" int ins_rk_adjoint_create(const ins_grid_t* G, ins_poisson_t* ps, int nstage, const double* A, const double* c, ins_rk_adjoint_t** out) {
-  INS_REQUIRE(G && ps && A && c && out, "null argument");
-  INS_REQUIRE(ps->grid == G, "psolver was created for a different grid");
+// the checks that need no device, then the 2·nstage + 1 vector fields and one scalar of the isothermal step, zeroed
+template <typename ADJ, typename T, typename PS>
+int adjoint_create(const ins_grid* G, PS* ps, int nstage, const double* A, const double* c, ADJ** out, const char* name) {
   INS_REQUIRE(nstage >= 1 && nstage <= INS_MAX_STAGES, "unsupported number of stages");
   for (int i = 0; i < nstage; ++i)
     for (int j = i + 1; j < nstage; ++j) INS_REQUIRE(A[i * nstage + j] == 0.0, "shifted tableau must be lower triangular (explicit method)");
   for (int b = 0; b < G->g.D; ++b)
     if (G->g.bc[b][0] == INS_BC_HALO || G->g.bc[b][1] == INS_BC_HALO) {
-      ins_set_error("ins_rk_adjoint_create: slab grids are not supported");
+      ins_set_error("%s: slab grids are not supported", name);
       return INS_ERR_UNSUPPORTED;
     }
-  ins_rk_adjoint* adj = new ins_rk_adjoint();
+  ADJ* adj = new ADJ();
   adj->grid = G;
   adj->ps = ps;
   adj->nstage = nstage;
@@ -79,19 +76,116 @@ extern "C" int ins_rk_adjoint_create(const ins_grid_t* G, ins_poisson_t* ps, int
   adj->c.assign(c, c + nstage);
   adj->v.assign(nstage, nullptr);
   adj->y.assign(nstage, nullptr);
-  const size_t vbytes = (size_t)G->ncell * G->g.D * sizeof(double), sbytes = (size_t)G->ncell * sizeof(double);
+  const size_t vbytes = (size_t)G->ncell * G->g.D * sizeof(T), sbytes = (size_t)G->ncell * sizeof(T);
   bool ok = hipMalloc(&adj->kbar, vbytes) == hipSuccess && hipMalloc(&adj->pwork, sbytes) == hipSuccess;
   for (int i = 0; ok && i < nstage; ++i) ok = hipMalloc(&adj->v[i], vbytes) == hipSuccess && hipMalloc(&adj->y[i], vbytes) == hipSuccess;
   if (ok) ok = hipMemset(adj->pwork, 0, sbytes) == hipSuccess && hipMemset(adj->kbar, 0, vbytes) == hipSuccess;
   for (int i = 0; ok && i < nstage; ++i) ok = hipMemset(adj->v[i], 0, vbytes) == hipSuccess && hipMemset(adj->y[i], 0, vbytes) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    ins_set_error("ins_rk_adjoint_create: device allocation of %d vector fields failed", 2 * nstage + 1);
-    ins_rk_adjoint_destroy(adj);
+    ins_set_error("%s: device allocation of %d vector fields failed", name, 2 * nstage + 1);
+    adjoint_destroy(adj);
     return INS_ERR_HIP;
   }
   *out = adj;
   return INS_OK;
+}
+
+// the descriptor, and on its first arrival the 2·nstage + 1 scalar fields of the coupled step, zeroed
+template <typename T, typename PS>
+int adjoint_set_temperature(RkAdjointT<T, PS>* adj, const ins_temperature_desc_t* desc) {
+  if (!desc) {
+    adj->temp_on = false;
+    return INS_OK;
+  }
+  const int D = adj->grid->g.D, ns = adj->nstage;
+  INS_REQUIRE(desc->gdir >= 0 && desc->gdir < D, "gdir out of range");
+  for (int q = 0; q < 2 * D; ++q)
+    INS_REQUIRE(desc->bc[q] == INS_BC_PERIODIC || desc->bc[q] == INS_BC_DIRICHLET || desc->bc[q] == INS_BC_SYMMETRIC || desc->bc[q] == INS_BC_PRESSURE,
+                "unsupported temperature boundary condition");
+  const size_t sbytes = (size_t)adj->grid->ncell * sizeof(T);
+  if (!adj->cbar) {
+    adj->tau.assign(ns, nullptr);
+    adj->z.assign(ns, nullptr);
+    bool ok = hipMalloc(&adj->cbar, sbytes) == hipSuccess && hipMemset(adj->cbar, 0, sbytes) == hipSuccess;
+    for (int i = 0; ok && i < ns; ++i)
+      ok = hipMalloc(&adj->tau[i], sbytes) == hipSuccess && hipMalloc(&adj->z[i], sbytes) == hipSuccess && hipMemset(adj->tau[i], 0, sbytes) == hipSuccess &&
+           hipMemset(adj->z[i], 0, sbytes) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      for (auto* arrays : {&adj->tau, &adj->z})
+        for (auto*& p : *arrays)
+          if (p) (void)hipFree(p), p = nullptr;
+      if (adj->cbar) (void)hipFree(adj->cbar), adj->cbar = nullptr;
+      ins_set_error("ins_rk_adjoint_set_temperature: device allocation of %d scalar fields failed", 2 * ns + 1);
+      return INS_ERR_HIP;
+    }
+  }
+  adj->td = *desc;
+  adj->temp_on = true;
+  return INS_OK;
+}
+
+// ∂L/∂(u_out, temp_out) -> ∂L/∂(ustart, tempstart): the argument checks of the coupled entries, then the generic loop
+template <typename T, typename PS>
+int step_pullback_ext(RkAdjointT<T, PS>* adj, T visc, const T* ustart, const T* tempstart, const T* bodyforce, T dt, T* ubar, T* tempbar, void* stream) {
+  INS_REQUIRE(adj && ustart && ubar, "null argument");
+  INS_REQUIRE(adj->temp_on, "the coupled step pullback needs ins_rk_adjoint_set_temperature");
+  INS_REQUIRE(tempstart && tempbar, "null temperature argument");
+  INS_REQUIRE(ubar != ustart && tempbar != tempstart, "the step pullback cannot run in place (ubar aliases ustart or tempbar aliases tempstart)");
+  INS_REQUIRE(ubar != tempstart && tempbar != ustart && ubar != tempbar && ustart != tempstart, "the step pullback's arguments alias one another");
+  INS_REQUIRE(!bodyforce || (bodyforce != ubar && bodyforce != tempbar), "the body force aliases an output");
+  return rkadj::step_pullback(adj, true, visc, ustart, tempstart, bodyforce, dt, ubar, tempbar, as_stream(stream));
+}
+
+}  // namespace
+
+extern "C" int ins_rk_adjoint_destroy(ins_rk_adjoint_t* adj) { return adjoint_destroy(adj); }
+extern "C" int ins_rk_adjoint_destroy_f32(ins_rk_adjoint32_t* adj) { return adjoint_destroy(adj); }
+
+extern "C" int ins_rk_adjoint_create(const ins_grid_t* G, ins_poisson_t* ps, int nstage, const double* A, const double* c, ins_rk_adjoint_t** out) {
+  INS_REQUIRE(G && ps && A && c && out, "null argument");
+  INS_REQUIRE(ps->grid == G, "psolver was created for a different grid");
+  return adjoint_create<ins_rk_adjoint, double>(G, ps, nstage, A, c, out, "ins_rk_adjoint_create");
+}
+
+extern "C" int ins_rk_adjoint_create_f32(const ins_grid_t* G, ins_poisson32_t* ps, int nstage, const double* A, const double* c, ins_rk_adjoint32_t** out) {
+  INS_REQUIRE(G && ps && A && c && out, "null argument");
+  INS_REQUIRE(ins_k32_solver_grid(ps) == G, "psolver was created for a different grid");
+  double* p64 = nullptr;
+  const ins_poisson* ps64 = ins_k32_wrapped(ps, &p64);
+  if (ps64 && ps64->kind == POISSON_SPECTRAL && G->all_periodic) {  // what ins_project_pullback_f32 refuses
+    ins_set_error("ins_rk_adjoint_create_f32: a wrapped spectral solver on an all-periodic box is not taken (use ins_poisson_spectral_create_f32)");
+    return INS_ERR_UNSUPPORTED;
+  }
+  return adjoint_create<ins_rk_adjoint32, float>(G, ps, nstage, A, c, out, "ins_rk_adjoint_create_f32");
+}
+
+extern "C" int ins_rk_adjoint_set_temperature(ins_rk_adjoint_t* adj, const ins_temperature_desc_t* desc) {
+  INS_REQUIRE(adj, "null argument");
+  return adjoint_set_temperature(adj, desc);
+}
+
+extern "C" int ins_rk_adjoint_set_temperature_f32(ins_rk_adjoint32_t* adj, const ins_temperature_desc_t* desc) {
+  INS_REQUIRE(adj, "null argument");
+  return adjoint_set_temperature(adj, desc);
+}
+
+extern "C" int ins_rk_step_pullback_f32(ins_rk_adjoint32_t* adj, float visc, const float* ustart, const float* bodyforce, float dt, float* ubar, void* stream) {
+  INS_REQUIRE(adj && ustart && ubar, "null argument");
+  INS_REQUIRE(ubar != ustart, "the step pullback cannot run in place (ubar aliases ustart)");
+  INS_REQUIRE(!bodyforce || bodyforce != ubar, "the body force aliases the output");
+  return rkadj::step_pullback<float, ins_poisson32>(adj, false, visc, ustart, nullptr, bodyforce, dt, ubar, nullptr, as_stream(stream));
+}
+
+extern "C" int ins_rk_step_pullback_ext_f64(ins_rk_adjoint_t* adj, double visc, const double* ustart, const double* tempstart, const double* bodyforce, double dt,
+                                            double* ubar, double* tempbar, void* stream) {
+  return step_pullback_ext<double, ins_poisson>(adj, visc, ustart, tempstart, bodyforce, dt, ubar, tempbar, stream);
+}
+
+extern "C" int ins_rk_step_pullback_ext_f32(ins_rk_adjoint32_t* adj, float visc, const float* ustart, const float* tempstart, const float* bodyforce, float dt,
+                                            float* ubar, float* tempbar, void* stream) {
+  return step_pullback_ext<float, ins_poisson32>(adj, visc, ustart, tempstart, bodyforce, dt, ubar, tempbar, stream);
 }
 
 extern "C" int ins_rk_step_pullback_f64(ins_rk_adjoint_t* adj, double visc, const double* ustart, const double* bodyforce, double dt, double* ubar,
