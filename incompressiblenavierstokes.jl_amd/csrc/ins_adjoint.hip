@@ -194,14 +194,14 @@ int launch_momentum_pullback_tiled(const ins_grid* G, double visc, const double*
 // ------------------------------------------------------------------------------------------------
 // internal launchers
 // ------------------------------------------------------------------------------------------------
-int ins_k_divergence_adjoint(const ins_grid* G, const double* phi, double* ubar, double alpha, hipStream_t s) {
+static int ins_k_divergence_adjoint(const ins_grid* G, const double* phi, double* ubar, double alpha, hipStream_t s) {
   const GridDev& g = G->g;
   const Launch3 l = box_launch(g.D, g.N);
   INS_LAUNCH_D((k_divergence_adjoint<D, double, double>), l, s, g, phi, ubar, alpha);
   return INS_OK;
 }
 
-int ins_k_pressuregradient_adjoint(const ins_grid* G, const double* phi, double* pbar, hipStream_t s) {
+static int ins_k_pressuregradient_adjoint(const ins_grid* G, const double* phi, double* pbar, hipStream_t s) {
   const GridDev& g = G->g;
   const Launch3 l = box_launch(g.D, g.N);
   INS_LAUNCH_D((k_pressuregradient_adjoint<D, double, double, true>), l, s, g, phi, pbar);

@@ -8,12 +8,7 @@
 // zeroing and the host logic of the projection pullback, and the entry points.  A translation unit of its own so that the fp64 kernels keep
 // their register allocation (ins_stencil.h).  Slab (HALO) sides are not taken: the multi-GPU path is fp64.
 #include "ins_adjoint_kernels.h"
-
-// csrc/ins_f32.hip: the wrapped fp64 solver of a Float32 solver handle (nullptr: a spectral Float32 solver) and its padded fp64 scratch
-ins_poisson* ins_k32_wrapped(const ins_poisson32* ps, double** p64);
-const ins_grid* ins_k32_solver_grid(const ins_poisson32* ps);
-// csrc/ins_adjoint.hip
-int ins_k_apply_bc_p_pullback(const ins_grid* G, double* p, hipStream_t s);
+#include "ins_f32_internal.h"
 
 namespace {
 

@@ -15,34 +15,8 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "ins_internal.h"
+#include "ins_f32_internal.h"
 #include "ins_rk_terms.h"
-
-bool ins_flux64_supported(const ins_grid* G);
-bool ins_k_spectral_own3d(const ins_poisson* ps);
-int ins_k_spectral_solve_from_u32(ins_poisson* ps, const float* u32, hipStream_t s);
-const double* ins_k_spectral_pI(const ins_poisson* ps);
-bool ins_k_spectral_own3d_f32(const ins_poisson* ps);
-int ins_k_spectral_solve_f32(ins_poisson* ps, const float* u32, float* pI32, float* phat32, int kxs32, const float* twx, const float* twy,
-                             const float* twz, hipStream_t s);
-int ins_zsolve_twiddles_f32(int nz, float** out);
-int ins_k_flux64_f32(const ins_grid* G, double visc, const float* u, float* F, const RkEpi* epi, const float* pI, int corr_mode, hipStream_t s,
-                     int part = 0);
-// any other grid (walls, stretched spacings, 2-D or 3-D): csrc/ins_f32g.hip
-int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s, int dudt = 0);
-int ins_k32g_apply_bc_p(const ins_grid* G, float* p, hipStream_t s);
-int ins_k32g_apply_bc_p_fields(const ins_grid* G, float* p, int nf, hipStream_t s);
-int ins_k32g_momentum(const ins_grid* G, float visc, const float* u, float* F, hipStream_t s);
-int ins_k32g_divergence(const ins_grid* G, const float* u, float* div, hipStream_t s);
-int ins_k32g_solve(const ins_grid* G, ins_poisson* ps64, double* p64, float* p, hipStream_t s);
-int ins_k32g_project(const ins_grid* G, ins_poisson* ps64, double* p64, float* u, float* p, hipStream_t s);
-// the temperature equation (any grid): csrc/ins_temp32.hip
-int ins_k32t_diffusion(const ins_grid* G, float visc, const float* u, float* diff, hipStream_t s);
-// the Smagorinsky closure: csrc/ins_smagforce32.hip (one kernel), csrc/ins_smagforce.hip (the route predicate of both precisions)
-bool ins_smagforce_supported(const ins_grid* G);
-int ins_k_smagforce_f32(const ins_grid* G, float theta, const float* u, float* sout, hipStream_t s);
-int ins_k32t_stage(const ins_grid* G, float a4, float coef, const float* u, const float* temp, const float* diff, const float* tempstart, int n,
-                   const float* coefs, const float* const* ks, float c_self, float* ktemp_out, float* temp_out, hipStream_t s);
 
 struct ins_poisson32 {
   const ins_grid* grid = nullptr;

@@ -12,6 +12,7 @@
 // Slab (HALO) sides are not taken: the multi-GPU path is fp64.
 #include <cmath>
 
+#include "ins_f32_internal.h"
 #include "ins_operator_kernels.h"
 
 namespace {

@@ -10,6 +10,7 @@
 // wavefront-uniform and come through scalar loads.  Algorithmic traffic: 48 B / cell.
 #include <cstdlib>
 
+#include "ins_debug.h"
 #include "ins_internal.h"
 
 namespace {
@@ -249,8 +250,6 @@ bool ins_fast3d_supported(const ins_grid* G) {
   if (ins_opt(OPT_INS_DISABLE_FAST3D)) return false;
   return g.N[0] >= 4 && g.N[1] >= 4 && g.N[2] >= 4;
 }
-
-int ins_k_momentum_flux3d(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
 
 int ins_k_momentum_fast3d_opts(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s) {
   const bool use_lds = ins_opt(OPT_INS_K1_LDS) != 0;  // A/B switch for experiments

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "ins_debug.h"
 #include "ins_internal.h"
 
 // (struct Rec, the per-direction metric record, lives in ins_internal.h: ins_flux64m.hip reads the same tables)
@@ -564,11 +565,7 @@ static int launch_flux_any(const ins_grid* G, const double* u, double* F, const 
   return INS_ERR_INVALID;
 }
 
-// 64-outputs-per-wavefront specialisation for periodic, exactly-uniform boxes (ins_flux64.hip)
-bool ins_flux64_supported(const ins_grid* G);
-int ins_k_flux64(const ins_grid* G, double visc, const double* u, double* F, const RkEpi* epi, const double* pI, int corr_mode, hipStream_t s,
-                 int part = 0);
-
+// 64-outputs-per-wavefront specialisation for periodic, exactly-uniform boxes: ins_k_flux64 (ins_flux64.hip)
 int ins_k_momentum_flux3d(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s) {
   int rc;
   // plain K1: the 64-wide kernel (workgroup barrier per plane, 8 wavefronts per workgroup on large boxes) runs at the flat-copy rate;
@@ -594,7 +591,6 @@ int ins_k_momentum_flux3d(const ins_grid* G, double visc, const double* u, doubl
 // fill!(F, 0) + diffusion!(F, u) (operators.jl:537-573) on the tiled kernel: the same face-flux sweep with records whose interpolation weights are
 // zero, so every face flux is its diffusive part alone (dissipation! needs diffusion(u) as a field of its own: ins_rk_ext.hip, ins_fields.hip).
 // zero_shell: also zero the ghost shell of F (a caller's array; the library's own scratch fields keep theirs zero).
-bool ins_fast3d_supported(const ins_grid* G);
 int ins_k_diffusion_flux3d(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s) {
   const GridDev& g = G->g;
   if (!ins_fast3d_supported(G)) return INS_ERR_UNSUPPORTED;
@@ -624,10 +620,7 @@ int ins_k_diffusion_flux3d(const ins_grid* G, double visc, const double* u, doub
 }
 
 // K1 + K6: k_i = momentum(u_in) (stored when epi.write_k) and the stage velocity u* (interior) in one pass.
-// 64 outputs per wavefront on stretched / masked grids (ins_flux64m.hip)
-bool ins_flux64m_supported(const ins_grid* G);
-int ins_k_flux64m(const ins_grid* G, double visc, const double* u, double* k_out, const RkEpi& epi, const double* p_padded, hipStream_t s);
-
+// 64 outputs per wavefront on stretched / masked grids: ins_k_flux64m (ins_flux64m.hip)
 int ins_k_momentum_rk_fused(const ins_grid* G, double visc, const double* u_in, double* k_out, const RkEpi& epi, hipStream_t s) {
   if (ins_flux64_supported(G)) return ins_k_flux64(G, visc, u_in, k_out, &epi, nullptr, 0, s);
   // (INS_FLUX64M_SKIP_FIRST=1 keeps the 62-wide kernel for the non-correcting first stage: cavity 256^3 4.15 vs 4.11 ms/step)
@@ -647,7 +640,6 @@ int ins_k_momentum_rk_fused_corr(const ins_grid* G, double visc, const double* u
   return launch_flux_any<true>(G, ustar_prev, k_out, epi, pI, 1, s);
 }
 
-bool ins_fast3d_supported(const ins_grid* G);
 // Masked / stretched grids whose sides are all Periodic or Dirichlet (cavities, channels): ustar_prev is the previous stage's uncorrected
 // u* with apply_bc_u! applied, p_padded that stage's pressure (padded layout; only interior values and periodic images are read).
 bool ins_corr3_supported(const ins_grid* G) {

@@ -14,7 +14,7 @@
 // this path clear of the ROCm 7.2 real-plan cache bug (ins_fftcheck.hip).
 #include <cmath>
 
-#include "ins_internal.h"
+#include "ins_f32_internal.h"
 
 namespace {
 

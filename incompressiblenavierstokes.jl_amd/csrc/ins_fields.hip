@@ -835,7 +835,6 @@ extern "C" int ins_apply_bc_temp_f64(const ins_grid_t* G, const int32_t* bc, con
 }
 
 // internal (ins_rk_ext.hip): w nullable (no dissipation term); ks / coefs: the previous ktemp_j with non-zero coefficient
-int ins_k_diffusion_flux3d(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
 int ins_k_temp_stage(const ins_grid* G, double a4, double coef, const double* u, const double* temp, const double* w, const double* tempstart, int n,
                      const double* coefs, const double* const* ks, double c_self, double* ktemp_out, double* temp_out, hipStream_t s, const double* pI,
                      const double* diff) {

@@ -13,7 +13,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "ins_internal.h"
+#include "ins_f32_internal.h"
 #include "ins_wave64.h"
 #include "ins_flux_common.h"
 

@@ -20,7 +20,8 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "ins_internal.h"
+#include "ins_debug.h"
+#include "ins_f32_internal.h"
 #include "ins_wave64.h"
 #include "ins_flux_common.h"
 
@@ -951,7 +952,6 @@ static TileShape tile_shape(const ins_grid* G, int corr_mode, bool f32, bool ext
   return TileShape{xw, rows, nw, zc};
 }
 
-bool ins_flux128_supported(const ins_grid* G, const RkEpi* epi, int corr_mode, bool f32);
 // The one place that decides whether a stage kernel launch (fp64, fused epilogue, no extra terms, every plane) writes the Poisson right-hand side: the launch is
 // this file's kernel, its workgroups span whole rows (so u*(i-1) never belongs to another workgroup) and the tile shape is one the route is built for.
 bool ins_flux64_stage_rhs_supported(const ins_grid* G, int corr_mode) {
@@ -1102,10 +1102,6 @@ static int flux64_dispatch(const ins_grid* G, double visc, const T* u, T* F, con
 }
 
 // two x-columns per lane (16 B per lane and memory instruction) wherever the box allows it: ins_flux128.hip
-bool ins_flux128_supported(const ins_grid* G, const RkEpi* epi, int corr_mode, bool f32);
-int ins_k_flux128(const ins_grid* G, double visc, const double* u, double* F, const RkEpi* epi, const double* pI, int corr_mode, hipStream_t s, int part);
-int ins_k_flux128_f32(const ins_grid* G, double visc, const float* u, float* F, const RkEpi* epi, const float* pI, int corr_mode, hipStream_t s, int part);
-
 int ins_k_flux64(const ins_grid* G, double visc, const double* u, double* F, const RkEpi* epi, const double* pI, int corr_mode, hipStream_t s,
                  int part) {
   if (ins_flux128_supported(G, epi, corr_mode, false)) {

@@ -20,9 +20,6 @@
 #include "ins_internal.h"
 #include "ins_wave64.h"
 
-int ins_flux3d_prepare(const ins_grid* G, double visc, hipStream_t s);
-bool ins_fast3d_supported(const ins_grid* G);
-
 namespace {
 
 struct FluxMArgs {

@@ -215,7 +215,8 @@ int ins_fdm_enable_zdct(ins_fdm* F, double hz, const double* lam_z_host);
 int ins_fdm_enable_xfft(ins_fdm* F, double hx, const double* lam_x_host);
 int ins_fdm_enable_xyfft(ins_fdm* F, double hx, double hy, const double* lam_x_host, const double* lam_y_host);
 int ins_fdm_solve(ins_fdm* F, hipStream_t s, const ins_grid* G = nullptr, const double* u = nullptr, bool folded_io = false);
-int ins_fdm_fold_mask(const ins_fdm* F);
+int ins_fdm_fold_mask(const ins_fdm* F);  // which directions run as folded half-size GEMMs (bit a = direction a)
+int ins_fdm_modes(const ins_fdm* F);      // which directions run in trigonometric modes (1 Fourier z, 2 Fourier x, 4 Fourier x and y, 8 cosine z)
 bool ins_fdm_takes_u(const ins_fdm* F);
 double* ins_fdm_buffer(ins_fdm* F);
 const double* ins_fdm_mean(ins_fdm* F);  // device scalar the consumer subtracts (singular systems), or nullptr
@@ -371,6 +372,24 @@ int ins_k_apply_bc_u(const ins_grid* grid, double* u, int dudt, const double* co
 int ins_k_apply_bc_p(const ins_grid* grid, double* p, hipStream_t s);
 int ins_k_apply_bc_p_fields(const ins_grid* grid, double* p, int nf, hipStream_t s);
 int ins_k_momentum(const ins_grid* grid, double visc, const double* u, double* F, hipStream_t s);
+// ins_operators.hip: momentum! on any grid, one volume per work-item
+int ins_k_momentum_generic(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s);
+// ins_fast3d.hip: momentum! on the tiled 3-D kernels (ins_fast3d_supported); zero_shell: also zero the ghost shell of F
+int ins_k_momentum_fast3d(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s);
+int ins_k_momentum_fast3d_opts(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
+// ins_fast3d_flux.hip: the flux-form kernels' metric records for this viscosity (struct Rec), built on first use; momentum!; fill!(F, 0) + diffusion!(F, u)
+int ins_flux3d_prepare(const ins_grid* G, double visc, hipStream_t s);
+int ins_k_momentum_flux3d(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
+int ins_k_diffusion_flux3d(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
+// ins_flux64.hip: the 64-outputs-per-wavefront stage kernel for periodic, exactly-uniform 3-D boxes; corr_mode != 0: u is uncorrected, pI its pressure
+bool ins_flux64_supported(const ins_grid* G);
+int ins_k_flux64(const ins_grid* G, double visc, const double* u, double* F, const RkEpi* epi, const double* pI, int corr_mode, hipStream_t s, int part = 0);
+// ins_flux64m.hip: the same width on stretched / masked grids; p_padded != nullptr: u is the previous stage's uncorrected u* (boundary data applied)
+bool ins_flux64m_supported(const ins_grid* G);
+int ins_k_flux64m(const ins_grid* G, double visc, const double* u, double* k_out, const RkEpi& epi, const double* p_padded, hipStream_t s);
+// ins_flux128.hip: two x-columns per lane wherever the box allows it (ins_k_flux64 dispatches to it)
+bool ins_flux128_supported(const ins_grid* G, const RkEpi* epi, int corr_mode, bool f32);
+int ins_k_flux128(const ins_grid* G, double visc, const double* u, double* F, const RkEpi* epi, const double* pI, int corr_mode, hipStream_t s, int part);
 int ins_k_divergence(const ins_grid* grid, const double* u, double* div, hipStream_t s);
 int ins_k_diffusion_overwrite(const ins_grid* grid, double visc, const double* u, double* F, hipStream_t s);
 int ins_k_scalewithvolume(const ins_grid* grid, double* p, hipStream_t s);
@@ -393,6 +412,10 @@ bool ins_k_project_fdm_fused(const ins_poisson* ps);
 int ins_k_project_fdm_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, double* p, hipStream_t s);
 int ins_k_project_periodic_fused_2d(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s);
 bool ins_poisson_own2d(const ins_poisson* ps);
+bool ins_k_spectral_own3d(const ins_poisson* ps);  // 3-D spectral solver every pass of which is one of the library's own kernels
+// project! of the fused periodic 3-D stage from interior values, ghost volumes filled; uout != nullptr: u stays and the corrected field goes to uout
+int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout = nullptr,
+                                 const double* rhs = nullptr, bool from_spec = false);
 // rhs != nullptr (own-FFT routes): the right-hand side Ω·div(u) is already in that buffer (the stage kernel wrote it) and the x pass reads it instead of u
 // from_spec: a stage kernel has stored the x-spectrum of the right-hand side in phat (ins_poisson_stage_spec): the solve starts at its y pass
 int ins_k_project_periodic_solve_only(const ins_grid* G, ins_poisson* ps, const double* u, hipStream_t s, const double* rhs = nullptr, bool from_spec = false);
@@ -407,6 +430,27 @@ double* ins_poisson_stage_spec(ins_poisson* ps, const void* pI_in, const double*
 bool ins_poisson_stage_spec_possible(const ins_poisson* ps);
 int ins_k_poisson_solve(ins_poisson* ps, double* p, hipStream_t s);
 bool ins_fast3d_supported(const ins_grid* G);
+
+// ins_fields.hip: one stage of the temperature equation (w, diff nullable; pI != nullptr: u is uncorrected); smagtensor! of u = ustar - ∇p formed in registers
+int ins_k_temp_stage(const ins_grid* G, double a4, double coef, const double* u, const double* temp, const double* w, const double* tempstart, int n,
+                     const double* coefs, const double* const* ks, double c_self, double* ktemp_out, double* temp_out, hipStream_t s, const double* pI,
+                     const double* diff = nullptr);
+int ins_k_smagtensor_corr(const ins_grid* G, double theta, const double* ustar, const double* pI, double* sig, hipStream_t s);
+// ins_smagforce.hip: the Smagorinsky closure force in one kernel, and the grids it takes (both precisions).  pI != nullptr: u is an uncorrected stage velocity
+bool ins_smagforce_supported(const ins_grid* G);
+int ins_k_smagforce(const ins_grid* G, double theta, const double* u, const double* pI, double* sout, hipStream_t s);
+// ins_tensorclosure.hip: the grid handle's ∇ubar scratch (D·D doubles per volume), allocated and grown on demand
+int ins_k_gradbar_scratch(const ins_grid* G, double** out);
+// ins_adjoint.hip: transposes of apply_bc_u! / apply_bc_p! in place, and ubar = J(u)ᵀ (Σ_q coefs[q]·ks[q]) (the reverse Runge-Kutta stage)
+int ins_k_apply_bc_u_pullback(const ins_grid* G, double* u, hipStream_t s);
+int ins_k_apply_bc_p_pullback(const ins_grid* G, double* p, hipStream_t s);
+int ins_k_momentum_pullback_comb(const ins_grid* G, double visc, const double* u, int nterms, const double* coefs, const double* const* ks, double* ubar,
+                                 hipStream_t s);
+// ins_ztri.hip: the z-slab solver's distributed tridiagonal passes over the line range [l_lo, l_lo + l_cnt) of the kxn·n1 lines, launched by ins_slab.hip
+int ins_k_ztri_forward(double* work, int kxn, int kxs, int n1, int m, int nranks, int rank, const double* ax, const double* ay, double c,
+                       double scale, double* edge, long long l_lo, long long l_cnt, hipStream_t s);
+int ins_k_ztri_finish(double* work, int kxn, int kxs, int n1, int m, int nranks, int rank, const double* ax, const double* ay, double c,
+                      const double* edges_all, long long stride, double* bc, long long l_lo, long long l_cnt, hipStream_t s);
 
 // Which stage loop an integrator runs (ins_rk.hip, ins_rk_ext.hip).  Each is the whole condition; what only one caller asks in addition (time-dependent
 // boundary planes, a body force, the closure / temperature state, the solver's own FFT passes) stands at that caller.
@@ -480,7 +524,6 @@ void ins_line3_permute_symbol(int n, const double* ay, double* out);
 int ins_line3_pos_of_freq(int n, int k);
 int ins_k_line3_z(double* phat, int kxn, int n1, int n2, const double* tw, hipStream_t s, int kxs);
 int ins_k_line3_y(double* phat, int kxn, int n1, int n2, const double* tw, bool inverse, hipStream_t s, int kxs);
-int ins_k_line3_y_f32(float* phat, int kxn, int n1, int n2, const float* tw, bool inverse, hipStream_t s, int kxs);
 int ins_ownfft_yz_partitions(int kxn, int n1, int n2);
 long long ins_ownfft_yz_scratch(int kxn, int n1, int n2, int P);
 int ins_k_ownfft_yz_solve(double* phat, int kxn, int n1, int n2, int kxs, int P, const double* ax, const double* ay, double c, double scale, const double* tw_y,

@@ -8,6 +8,8 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "ins_debug.h"
+#include "ins_f32_internal.h"
 #include "ins_stencil.h"
 
 namespace {
@@ -1317,8 +1319,6 @@ extern "C" int ins_poisson_solve_f64(ins_poisson_t* ps, double* p, void* stream)
   return ins_k_poisson_solve(ps, p, as_stream(stream));
 }
 
-// experiment / test hook (not in the public header): which directions of a direct solver run as folded half-size GEMMs (bit a = direction a)
-int ins_fdm_modes(const ins_fdm* F);
 // test hook: which directions of the direct solver run in trigonometric modes (1 Fourier z, 2 Fourier x, 4 Fourier x and y, 8 cosine z)
 extern "C" int ins_dbg_fdm_modes(const ins_poisson_t* ps) { return (ps && ps->kind == POISSON_FDM) ? ins_fdm_modes(ps->fdm) : -1; }
 // test hooks: a live spectral solver's route and ky order (SpectralRoute / KyOrder values; -1: not a spectral solver); the choice for a box under the
@@ -1535,12 +1535,6 @@ const double* ins_k_spectral_pI(const ins_poisson* ps) { return ps->pI; }
 // pass here is the float twin of the one that leaves that order) and the grid; the float work arrays and float2 twiddles belong to the caller.
 // u32 != nullptr: right-hand side Ω·div(u) from the float velocity field inside the x pass (periodic images); else the right-hand side is in pI32.
 // Solution in pI32 (unpadded).
-bool ins_zsolve_f32_supported(int nz);
-int ins_k_zsolve_f32(float* data, int nz, long long nl, const double* ax, int kxn, const double* ay, const double* az, const float* tw, double inv_n,
-                     bool zero_mean, hipStream_t s, int kxs);
-int ins_k_ownfft_xfwd_f32(const ins_grid* G, const float* src, int from_u, float* phat, int n0, int n1, int n2, const float* tw, hipStream_t s, int kxs);
-int ins_k_ownfft_xinv_f32(const float* phat, float* pI, int n0, int n1, int n2, const float* tw, hipStream_t s, int kxs);
-int ins_k_ownfft_y_f32(float* phat, int kxn, int n1, int n2, const float* tw, bool inverse, hipStream_t s, int kxs);
 bool ins_k_spectral_own3d_f32(const ins_poisson* ps) { return ins_k_spectral_own3d(ps) && ins_zsolve_f32_supported(ps->np[2]); }
 int ins_k_spectral_solve_f32(ins_poisson* ps, const float* u32, float* pI32, float* phat32, int kxs32, const float* twx, const float* twy,
                              const float* twz, hipStream_t s) {

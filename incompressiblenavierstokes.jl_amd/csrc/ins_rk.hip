@@ -2,17 +2,9 @@
 // (time_stepper_caches.jl:34-49).
 #include <cstdlib>
 
+#include "ins_debug.h"
 #include "ins_internal.h"
 #include "ins_rk_terms.h"
-
-int ins_k_momentum_generic(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s);
-int ins_k_momentum_fast3d(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s);
-int ins_k_momentum_fast3d_opts(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
-bool ins_flux64_supported(const ins_grid* G);
-
-int ins_k_momentum_rk_fused(const ins_grid* G, double visc, const double* u_in, double* k_out, const RkEpi& epi, hipStream_t s);
-int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout = nullptr,
-                                 const double* rhs = nullptr, bool from_spec = false);
 
 int ins_k_momentum(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s) {
   if (ins_fast3d_supported(G)) return ins_k_momentum_fast3d(G, visc, u, F, s);
@@ -82,7 +74,6 @@ static int combine_n(long long nvec, const double* base, double* out, int nterms
 }
 
 static void step_graph_free(ins_rk* rk);
-bool ins_k_spectral_own3d(const ins_poisson* ps);  // every pass of the solver is one of the library's own kernels (ins_poisson.hip)
 
 extern "C" int ins_rk_create(const ins_grid_t* G, ins_poisson_t* ps, int nstage, const double* A, const double* c, ins_rk_t** out) {
   INS_REQUIRE(G && ps && A && c && out, "null argument");

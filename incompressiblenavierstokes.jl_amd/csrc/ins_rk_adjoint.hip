@@ -14,14 +14,9 @@
 // That loop is kept as it was.  The Float32 step and the steps with a temperature (ins_rk_step_pullback_f32, ins_rk_step_pullback_ext_f64 / _f32) run
 // the one generic loop of ins_rk_adjoint_loop.h, which never fuses the combination (INS_ADJ_STAGE_FUSED is ignored there).
 #include "ins_adjoint_kernels.h"
+#include "ins_f32_internal.h"
 #include "ins_rk_adjoint_loop.h"
 #include "ins_rk_terms.h"
-
-int ins_k_momentum_pullback_comb(const ins_grid* G, double visc, const double* u, int nterms, const double* coefs, const double* const* ks, double* ubar,
-                                 hipStream_t s);
-// csrc/ins_f32.hip: the wrapped fp64 solver of a Float32 solver handle (nullptr: a spectral Float32 solver), and the handle's grid
-ins_poisson* ins_k32_wrapped(const ins_poisson32* ps, double** p64);
-const ins_grid* ins_k32_solver_grid(const ins_poisson32* ps);
 
 struct ins_rk_adjoint : RkAdjointT<double, ins_poisson> {};
 struct ins_rk_adjoint32 : RkAdjointT<float, ins_poisson32> {};

@@ -23,8 +23,6 @@
 
 #include <cstdint>
 
-int ins_k_apply_bc_u_pullback(const ins_grid* G, double* u, hipStream_t s);  // csrc/ins_adjoint.hip
-
 // Work arrays of the reverse step.  v, y: nstage vector fields each; kbar: one; pwork: one scalar.  With a temperature: tau, z (nstage scalars each)
 // and cbar, allocated by set_temperature.
 template <typename T, typename PS>

@@ -16,26 +16,9 @@
 #include <cstring>
 #include <vector>
 
+#include "ins_debug.h"
 #include "ins_internal.h"
 #include "ins_rk_terms.h"
-
-int ins_k_momentum_generic(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s);
-int ins_k_momentum_fast3d_opts(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
-int ins_k_momentum_rk_fused(const ins_grid* G, double visc, const double* u_in, double* k_out, const RkEpi& epi, hipStream_t s);
-int ins_k_project_periodic_fused(const ins_grid* G, ins_poisson* ps, double* u, double* p, bool keep_p, hipStream_t s, double* uout = nullptr,
-                                 const double* rhs = nullptr, bool from_spec = false);
-int ins_k_project(const ins_grid* G, ins_poisson* ps, double* u, double* p, hipStream_t s);
-bool ins_flux64_supported(const ins_grid* G);
-int ins_k_temp_stage(const ins_grid* G, double a4, double coef, const double* u, const double* temp, const double* w, const double* tempstart, int n,
-                     const double* coefs, const double* const* ks, double c_self, double* ktemp_out, double* temp_out, hipStream_t s, const double* pI,
-                     const double* diff = nullptr);
-int ins_k_diffusion_overwrite(const ins_grid* G, double visc, const double* u, double* F, hipStream_t s);
-bool ins_flux64m_supported(const ins_grid* G);
-bool ins_smagforce_supported(const ins_grid* G);
-int ins_k_smagforce(const ins_grid* G, double theta, const double* u, const double* pI, double* sout, hipStream_t s);
-int ins_k_diffusion_flux3d(const ins_grid* G, double visc, const double* u, double* F, bool zero_shell, hipStream_t s);
-int ins_k_momentum_rk_fused_corr(const ins_grid* G, double visc, const double* ustar_prev, const double* pI, double* k_out, const RkEpi& epi, hipStream_t s);
-int ins_k_smagtensor_corr(const ins_grid* G, double theta, const double* ustar, const double* pI, double* sig, hipStream_t s);
 
 struct ins_rk_ext {
   int closure = 0;  // 0 none, 1 Smagorinsky

@@ -14,8 +14,6 @@
 
 #include "ins_internal.h"
 
-bool ins_flux64_supported(const ins_grid* G);
-
 struct ins_slab_fft {
   int np[3];         // global interior sizes
   int rank, nranks;
@@ -37,11 +35,6 @@ struct ins_slab_fft {
   double* ztri_bc = nullptr;
   int kxs = 0;  // row stride of `work` on the transpose-free route: kxn rounded up to whole 128-B lines with the own passes
 };
-
-int ins_k_ztri_forward(double* work, int kxn, int kxs, int n1, int m, int nranks, int rank, const double* ax, const double* ay, double c,
-                       double scale, double* edge, long long l_lo, long long l_cnt, hipStream_t s);
-int ins_k_ztri_finish(double* work, int kxn, int kxs, int n1, int m, int nranks, int rank, const double* ax, const double* ay, double c,
-                      const double* edges_all, long long stride, double* bc, long long l_lo, long long l_cnt, hipStream_t s);
 
 namespace {
 

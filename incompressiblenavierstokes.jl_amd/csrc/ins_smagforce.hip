@@ -15,8 +15,6 @@ bool ins_smagforce_supported(const ins_grid* G) {
       if ((g.bc[d][side] == INS_BC_PRESSURE && side == 0) || g.bc[d][side] == INS_BC_HALO) return false;
   return true;
 }
-// the correcting form (uncorrected input + pressure) exists for all-periodic uniform boxes only
-bool ins_smagforce_corr_supported(const ins_grid* G) { return ins_smagforce_supported(G) && smagforce_uniform(G); }
 
 // s (degrees of freedom of the three components; everything else untouched) = closure force of u.  pI == nullptr: u is a velocity field with its
 // boundary data applied (periodic directions: ghost volumes not read); else (all-periodic uniform boxes) u is an uncorrected stage velocity and
@@ -45,7 +43,6 @@ int ins_k_smagforce(const ins_grid* G, double theta, const double* u, const doub
 
 // smagorinsky_closure(setup)(u, θ)   operators.jl:1284-1300 as one kernel where the box allows it, else the reference's three steps
 // (sigma: scratch of D(D+1)/2 scalar fields, used by the three-step route only)
-int ins_k_apply_bc_p_fields(const ins_grid* G, double* p, int nf, hipStream_t s);
 extern "C" int ins_smagorinsky_force_needs_sigma(const ins_grid_t* G) { return (G && ins_smagforce_supported(G)) ? 0 : 1; }
 extern "C" int ins_smagorinsky_force_f64(const ins_grid_t* G, double theta, const double* u, double* sigma, double* s, void* stream) {
   INS_REQUIRE(G && u && s, "null argument");

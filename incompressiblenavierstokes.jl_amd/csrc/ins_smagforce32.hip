@@ -12,11 +12,9 @@
 // the fp64 file is not concerned).  With the folding the GEN + STR float form returned values off by 4e-4 .. 6e-3 of max|s| on an MI355X — on the second
 // output row of a wavefront's row pair, mostly one plane in four — while the uniform and GEN float forms were right; without it the same source is right to
 // 1.7e-7 (profiles/smagforce_generic_isa.md: the 19 folded instructions, all in full-EXEC regions; which fold is at fault is not identified).
+#include "ins_f32_internal.h"
 #include "ins_smagforce_kernels.h"
 #include "ins_tensorbasis.h"
-
-bool ins_smagforce_supported(const ins_grid* G);
-int ins_k32g_apply_bc_p_fields(const ins_grid* G, float* p, int nf, hipStream_t s);
 
 // s (degrees of freedom of the three components; everything else untouched) = closure force of the velocity field u with its boundary data applied
 // (periodic directions: ghost volumes not read)

@@ -14,6 +14,7 @@
 //   stage kernel: one pass over Ip forms ktemp_i = convection_diffusion_temp(u, temp) + dissipation(u) and temp_out = tempstart + Σ_j Δt A[i,j] ktemp_j
 //                 (k32t_stage); the stage loop that calls it is ins_rk_step_ext_f32 (csrc/ins_f32.hip, beside the isothermal loop whose handle it extends).
 // Slab (HALO) sides are not taken: the multi-GPU path is fp64.
+#include "ins_f32_internal.h"
 #include "ins_temp_kernels.h"
 
 namespace {

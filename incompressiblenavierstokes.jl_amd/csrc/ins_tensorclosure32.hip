@@ -14,9 +14,6 @@
 // path is fp64.
 #include "ins_tensorbasis.h"
 
-// csrc/ins_tensorclosure.hip
-int ins_k_gradbar_scratch(const ins_grid* G, double** out);
-
 namespace {
 
 // divoftensor! on the D(D+1)/2 symmetric fields (operators.jl:1203-1236): k_divoftensor of ins_fields.hip in float

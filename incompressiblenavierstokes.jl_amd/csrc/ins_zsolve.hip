@@ -15,7 +15,8 @@
 #include <cstdlib>
 #include <vector>
 
-#include "ins_internal.h"
+#include "ins_debug.h"
+#include "ins_f32_internal.h"
 
 namespace {
 
@@ -770,7 +771,6 @@ int ins_line3_pos_of_freq(int n, int k) {
 }
 // forward transform along z of data[kz][ky][kx] (rows of kxs complex values, n1 rows per plane): the "planes" of the kernel are the ky rows, elements of a
 // line are kxs * n1 apart (observespectrum on the library's own passes, ins_spectrum.hip)
-int ins_k_line3_z(double* phat, int kxn, int n1, int n2, const double* tw, hipStream_t s, int kxs);
 int ins_k_line3_y(double* phat, int kxn, int n1, int n2, const double* tw, bool inverse, hipStream_t s, int kxs) {
   return line3_y<double2>(reinterpret_cast<double2*>(phat), kxn, kxs, n1, n2, reinterpret_cast<const double2*>(tw), inverse, s);
 }
