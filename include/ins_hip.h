@@ -440,6 +440,27 @@ int ins_rk_step_pullback_ext_f64(ins_rk_adjoint_t* adj, double visc, const doubl
 int ins_rk_step_pullback_ext_f32(ins_rk_adjoint32_t* adj, float visc, const float* ustart, const float* tempstart, const float* bodyforce, float dt,
                                  float* ubar, float* tempbar, void* stream);
 
+/* ---------------------------------------------------------------------------------- pullback of the Smagorinsky closure force
+ * (csrc/ins_smagpullback_kernels.h).  Transpose of ins_smagorinsky_force_f64 / _f32 at a ghost-filled u, with respect to u and θ:
+ *   ubar (+)= (∂s/∂u)ᵀ sbar over the whole padded array (accumulate != 0 adds),   *thetabar += 2θ <σ̄, σ̂> = (∂s/∂θ)ᵀ sbar.
+ * sbar is read on Iu[α] only.  Pass 1, one work-item per pressure point, gathers σ̄ = bc_pᵀ divoftensorᵀ sbar from sbar (the ghost volumes filled from the
+ * point included), recomputes ∇u, writes Ḡ = (∂σ/∂∇u)ᵀ σ̄ to the grid handle's ∇ubar scratch (zero where |S| = 0) and one double partial of <σ̄, σ̂> per
+ * workgroup; pass 2 is the transpose-of-∇ gather of ins_tensorclosure_pullback_*; a one-workgroup tail sums the partials in a fixed order.  No atomic
+ * operations, bitwise reproducible.  thetabar: a DEVICE double the caller zeroes, nullable (then no reduction runs).  2-D and 3-D, stretched grids,
+ * every BC mix.  ubar aliasing u or sbar: INS_ERR_INVALID.  Slab grids: INS_ERR_UNSUPPORTED.  Asynchronous. */
+int ins_smagorinsky_force_pullback_f64(const ins_grid_t* grid, double theta, const double* u, const double* sbar, double* ubar, int accumulate,
+                                       double* thetabar, void* stream);
+int ins_smagorinsky_force_pullback_f32(const ins_grid_t* grid, float theta, const float* u, const float* sbar, float* ubar, int accumulate,
+                                       double* thetabar, void* stream);
+/* The Smagorinsky closure in the reverse step.  kind 0: no closure; 1: smagorinsky_closure(setup) with constant θ, as ins_rk_set_closure.  With kind 1
+ * every later step pullback of the handle recomputes k_i = F(v_i) [+ gravity] + f + m(v_i, θ) (ins_smagorinsky_force_*), adds the closure's pullback at
+ * (v_i, k̄_i) to the stage's momentum pullback, and adds ∂L/∂θ of the step to *thetabar, a DEVICE double the caller zeroes (nullable: no θ cotangent).
+ * The first call with kind 1 allocates one vector field and, where ins_smagorinsky_force_needs_sigma answers 1, the D(D+1)/2 fields of `sigma`; the
+ * destroy call frees them.  With a closure set ins_rk_step_pullback_f64 runs the generic loop (INS_ADJ_STAGE_FUSED is not read).  Another kind:
+ * INS_ERR_INVALID. */
+int ins_rk_adjoint_set_closure(ins_rk_adjoint_t* adj, int32_t kind, double theta, double* thetabar);
+int ins_rk_adjoint_set_closure_f32(ins_rk_adjoint32_t* adj, int32_t kind, double theta, double* thetabar);
+
 /* observespectrum(state; setup, npoint, a)   processors.jl:303-332.  The index sets of spectral_stuff (utils.jl:49-108) are built
  * on the host: bin i sums the modes inds[offsets[i] .. offsets[i+1]), each a 0-based column-major position in the K = Np .÷ 2
  * array of retained non-negative wavenumbers.  ins_spectrum_f64 writes ehat[0 .. nbin) (DEVICE): per component one ghost strip,

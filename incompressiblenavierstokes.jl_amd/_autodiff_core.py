@@ -33,6 +33,9 @@ from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
 #                               dissipation_adjoint_(ubar, cbar, u, setup), temperature_pullback_(ubar, tempbar, Fbar, cbar, u, temp, setup),
 #                               project_pullback_(φbar, setup, psolver, pwork), divoftensor_adjoint_(σbar, sbar, setup),
 #                               tensorclosure_pullback_(ubar, abar, τbar, Vbar, u, a, setup)
+#   Smagorinsky closure force   smagorinsky_force_(s, u, θ, setup): the one-call native force, θ a Python float;
+#                               smagorinsky_force_pullback_(ubar, θbar, sbar, u, θ, setup): ubar overwritten, θbar (a 0-dim float64 tensor on the
+#                               setup's device, or None) added to
 # Every call works in place on its first argument(s) and returns what it wrote.
 
 
@@ -338,13 +341,87 @@ def smagorinsky_closure(ops, setup):
     def closure(u, θ):
         θ = torch.as_tensor(θ, dtype=ops.dtype, device=setup.device)
         V = _TensorInvariants.apply(u, setup, ops)
-        a2 = torch.nn.functional.pad(2 * θ * θ * d2 * torch.sqrt(2 * V[ip + (0,)]), pads)  # Ip only: sqrt has no derivative at the zeros outside
+        # Ip only: sqrt has no derivative at the zeros outside.  Inside, where S:S = 0 the contribution is defined as zero: sqrt is taken of 1 there and
+        # the result masked, so its backward is 0 instead of 0 / 0 (the forward value, 0, and everything where S:S > 0 are unchanged)
+        V1 = V[ip + (0,)]
+        live = V1 > 0
+        mag = torch.where(live, torch.sqrt(2 * torch.where(live, V1, torch.ones_like(V1))), torch.zeros_like(V1))
+        a2 = torch.nn.functional.pad(2 * θ * θ * d2 * mag, pads)
         z = torch.zeros_like(a2)
         a = torch.stack([z, a2] + [z] * (nb - 2), dim=-1)
         τ = apply_bc_p_fields(lambda p, t, s: _ApplyBCP.apply(p, t, s, ops), _TensorClosureStress.apply(u, a, setup, ops), 0.0, setup)
         return _DivOfTensor.apply(τ, setup, ops)
 
+    closure._ad_smagorinsky = (ops.name, setup)  # `timesteps` takes it for the closure of its native loops (not `_ins_closure`: the step functions route on that)
     return closure
+
+
+class _SmagorinskyForce(torch.autograd.Function):
+    """s = m(u, θ), the Smagorinsky closure force of the ghost-filled `u` (operators.jl:1284-1300) as the one native call, θ a 0-dim tensor.  The
+    backward is the fused pullback (csrc/ins_smagpullback_kernels.h): ubar, and θbar = 2θ <σ̄, σ̂> from the same pass."""
+
+    @staticmethod
+    def forward(ctx, u, θ, setup, ops):
+        ctx.setup, ctx.ops, ctx.θ = setup, ops, float(θ)
+        ops.check_closure_inputs(setup, u)
+        (uf,) = _save_inputs(ops, ctx, setup, [(u, True)])
+        return ops.smagorinsky_force_(ops.vectorfield(setup), uf, ctx.θ, setup)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, ops = ctx.setup, ctx.ops
+        (u,) = _saved_inputs(ctx)
+        θbar = torch.zeros((), dtype=torch.float64, device=s.device) if ctx.needs_input_grad[1] else None
+        ubar, θbar = ops.smagorinsky_force_pullback_(ops.vectorfield(s), θbar, _field(ops, s, g, True), u, ctx.θ, s)
+        return ubar, θbar, None, None
+
+
+def smagorinsky_force(ops, u, θ, setup):
+    """`_SmagorinskyForce` with θ a Python scalar or a 0-dim tensor; θbar comes back in θ's dtype and on its device."""
+    θ = θ if isinstance(θ, torch.Tensor) else torch.tensor(float(θ), dtype=ops.dtype)
+    if θ.dim() != 0:
+        raise ValueError(f"{ops.name}.smagorinsky_force: θ must be a scalar or a 0-dim tensor")
+    return _SmagorinskyForce.apply(u, θ, setup, ops)
+
+
+def smagorinsky_of(setup, name, dtype):
+    """True when `setup.closure_model` is the library's Smagorinsky closure of this setup in the precision `dtype`: the fused one
+    (`smagorinsky_closure` / `smagorinsky_closure32`) or the differentiable one of the module `name` (`ad` / `ad32`)."""
+    m = setup.closure_model
+    if getattr(m, "_ins_closure", None) == "smagorinsky" and getattr(m, "_ins_setup", None) is setup and getattr(m, "_ins_dtype", None) == dtype:
+        return True
+    tag = getattr(m, "_ad_smagorinsky", None)
+    return tag is not None and tag[0] == name and tag[1] is setup
+
+
+class native_closure:
+    """While a rollout's native forward runs: `setup.closure_model` carries the tags on which `timesteps_` / `timesteps32_` put the Smagorinsky
+    closure into the native stage loop.  The fused closure has them; the differentiable one is replaced, for the duration, by a stand-in made by
+    `make(setup)` on first use and kept on the setup."""
+
+    def __init__(self, setup, θ, make):
+        self.setup, self.on, self.make = setup, θ is not None and getattr(setup.closure_model, "_ins_closure", None) != "smagorinsky", make
+
+    def __enter__(self):
+        if self.on:
+            s = self.setup
+            self.saved = s.closure_model
+            if getattr(s, "_ad_native_closure", None) is None:
+                real = []
+
+                def closure(u, θ):  # only a host-driven stage loop evaluates it
+                    if not real:
+                        real.append(self.make(s))
+                    return real[0](u, θ)
+
+                closure._ins_closure, closure._ins_setup = "smagorinsky", s
+                s._ad_native_closure = closure
+            s.closure_model = s._ad_native_closure
+
+    def __exit__(self, *exc):
+        if self.on:
+            self.setup.closure_model = self.saved
+        return False
 
 
 # ------------------------------------------------------------------------------------ time stepping
@@ -393,7 +470,10 @@ def timestep(ops, method, stepper, Δt, θ):
 # The table's part of a rollout (the only native calls of this section):
 #   rk_cache(erk, setup, psolver)                           the forward's native cache (`ERKCache` / `ERKCache32`)
 #   rk_adjoint_create(erk, setup, psolver) -> handle        the work arrays of the native reverse step; rk_adjoint_destroy(handle)
-#   rk_steps_(adj, u, temp or None, t, Δt, nsteps)          the native multi-step loop of that setup, in place (`timesteps_` / `timesteps32_`)
+#   rk_steps_(adj, u, temp or None, t, Δt, nsteps[, θ])     the native multi-step loop of that setup, in place (`timesteps_` / `timesteps32_`); θ: a
+#                                                           Python float, given only with the Smagorinsky closure
+#   rk_adjoint_set_closure(adj, θ or None, θbar or None)    the Smagorinsky closure on the reverse step's handle (θbar: 0-dim float64 device tensor
+#                                                           that every later step pullback adds to), None switches it off
 #   rk_step_pullback_(adj, ubar, tempbar or None, ustart, tempstart or None, Δt)      one native reverse step, in place on (ubar, tempbar)
 #   rk_copy_(dst, src, setup, vector)                       a field copy by the library's own pass
 class _StepAdjoint:
@@ -404,11 +484,21 @@ class _StepAdjoint:
         self.ops, self.erk, self.setup = ops, erk, setup
         self.cache = ops.rk_cache(erk, setup, psolver)
         self._handle = ops.rk_adjoint_create(erk, setup, psolver)
+        self.closure_on = False
 
-    def steps_(self, u, temp, t, Δt, nsteps):
-        """`nsteps` native steps on (u, temp), in place."""
-        self.ops.rk_steps_(self, u, temp, t, Δt, nsteps)
+    def steps_(self, u, temp, t, Δt, nsteps, θ=None):
+        """`nsteps` native steps on (u, temp), in place; θ (a Python float): with the Smagorinsky closure."""
+        if θ is None:
+            self.ops.rk_steps_(self, u, temp, t, Δt, nsteps)
+        else:
+            self.ops.rk_steps_(self, u, temp, t, Δt, nsteps, θ)
         return u, temp
+
+    def set_closure_(self, θ, θbar=None):
+        """The Smagorinsky closure with constant θ on the handle: every later `step_pullback_` carries it and adds ∂L/∂θ to `θbar`.  None clears it."""
+        if θ is not None or self.closure_on:
+            self.ops.rk_adjoint_set_closure(self, θ, θbar)
+            self.closure_on = θ is not None
 
     def step_pullback_(self, ubar, ustart, Δt, tempbar=None, tempstart=None):
         """(ubar, tempbar): ∂L/∂(u_out, temp_out) -> ∂L/∂(ustart, tempstart), in place: the whole reverse sweep of one step is this one call."""
@@ -434,19 +524,23 @@ def _step_adjoint(ops, erk, setup, psolver):
 
 
 class _TimeSteps(torch.autograd.Function):
-    """(u, temp) -> (u, temp) after nsteps Runge-Kutta steps, `temp` possibly None.  Saved: the state at the start of every chunk of `every` steps,
-    nothing else.  Both cotangents are always propagated (one native call per step serves both); autograd drops the one nobody asked for."""
+    """(u, temp) -> (u, temp) after nsteps Runge-Kutta steps, `temp` possibly None; θ: None, or the 0-dim tensor of the Smagorinsky constant.  Saved:
+    the state at the start of every chunk of `every` steps, nothing else.  Both field cotangents are always propagated (one native call per step
+    serves both); autograd drops the one nobody asked for.  θbar is collected in one device double, zeroed once per backward, that every reverse
+    step of every chunk adds to."""
 
     @staticmethod
-    def forward(ctx, u, temp, adj, ops, t, Δt, nsteps, every):
+    def forward(ctx, u, temp, θ, adj, ops, t, Δt, nsteps, every):
         setup = adj.setup
         out = _copy(ops, setup, u, True)
         tout = None if temp is None else _copy(ops, setup, temp, False)
         ctx.adj, ctx.ops, ctx.t, ctx.Δt, ctx.nsteps, ctx.every = adj, ops, t, Δt, nsteps, every
+        ctx.θ, ctx.θlike = (None, None) if θ is None else (float(θ), (θ.dtype, θ.device))
+        kw = {} if θ is None else {"θ": ctx.θ}
         ctx.checkpoints = []
         for start in range(0, nsteps, every):
             ctx.checkpoints.append((_copy(ops, setup, out, True), None if tout is None else _copy(ops, setup, tout, False)))
-            adj.steps_(out, tout, t + start * Δt, Δt, min(every, nsteps - start))
+            adj.steps_(out, tout, t + start * Δt, Δt, min(every, nsteps - start), **kw)
         return out, tout
 
     @staticmethod
@@ -460,20 +554,32 @@ class _TimeSteps(torch.autograd.Function):
         # the step-start states of one chunk after its checkpoint
         bufs = [(ops.vectorfield(setup), ops.scalarfield(setup) if coupled else None) for _ in range(min(every, nsteps) - 1)]
         starts = list(range(0, nsteps, every))
-        for q in reversed(range(len(starts))):
-            n = min(every, nsteps - starts[q])
-            states = [ctx.checkpoints[q]]
-            for j in range(1, n):
-                bu, bt = bufs[j - 1]
-                ops.rk_copy_(bu, states[j - 1][0], setup, True)
-                if coupled:
-                    ops.rk_copy_(bt, states[j - 1][1], setup, False)
-                adj.steps_(bu, bt, ctx.t + (starts[q] + j - 1) * Δt, Δt, 1)
-                states.append((bu, bt))
-            for j in reversed(range(n)):
-                adj.step_pullback_(ubar, states[j][0], Δt, tempbar, states[j][1])
-            ctx.checkpoints[q] = None
-        return ubar, tempbar, None, None, None, None, None, None
+        kw, θbar = {}, None
+        if ctx.θ is not None:
+            kw = {"θ": ctx.θ}
+            if ctx.needs_input_grad[2]:
+                θbar = torch.zeros((), dtype=torch.float64, device=setup.device)
+            adj.set_closure_(ctx.θ, θbar)
+        try:
+            for q in reversed(range(len(starts))):
+                n = min(every, nsteps - starts[q])
+                states = [ctx.checkpoints[q]]
+                for j in range(1, n):
+                    bu, bt = bufs[j - 1]
+                    ops.rk_copy_(bu, states[j - 1][0], setup, True)
+                    if coupled:
+                        ops.rk_copy_(bt, states[j - 1][1], setup, False)
+                    adj.steps_(bu, bt, ctx.t + (starts[q] + j - 1) * Δt, Δt, 1, **kw)
+                    states.append((bu, bt))
+                for j in reversed(range(n)):
+                    adj.step_pullback_(ubar, states[j][0], Δt, tempbar, states[j][1])
+                ctx.checkpoints[q] = None
+        finally:
+            if ctx.θ is not None:
+                adj.set_closure_(None)
+        if θbar is not None:
+            θbar = θbar.to(dtype=ctx.θlike[0], device=ctx.θlike[1])
+        return ubar, tempbar, θbar, None, None, None, None, None, None
 
 
 def checkpoint_interval(ops, nsteps, checkpoint_every):
@@ -487,17 +593,22 @@ def checkpoint_interval(ops, nsteps, checkpoint_every):
     return nsteps, min(every, nsteps)
 
 
-def timesteps(ops, method, stepper, Δt, nsteps, every, adj=None):
+def timesteps(ops, method, stepper, Δt, nsteps, every, adj=None, θ=None):
     """`nsteps` Runge-Kutta steps as one Function (the refusals are the caller's): the native multi-step loop forward in chunks of `every` steps,
     the state at every chunk start kept, one native reverse step per step backward.  `adj`: the reverse step's handle, by default the one kept
-    on the solver."""
+    on the solver.  θ: None, or the constant of the setup's Smagorinsky closure (a Python scalar, or a 0-dim tensor that may require grad)."""
     setup, psolver, u, temp = stepper.setup, stepper.psolver, stepper.u, stepper.temp
     erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
     if adj is None:
         adj = _step_adjoint(ops, erk, setup, psolver)
     t = float(stepper.t)
-    if torch.is_grad_enabled() and (u.requires_grad or (temp is not None and temp.requires_grad)):
-        out, tout = _TimeSteps.apply(u, temp, adj, ops, t, float(Δt), nsteps, every)
+    if θ is not None:
+        θ = θ if isinstance(θ, torch.Tensor) else torch.tensor(float(θ), dtype=ops.dtype)
+        if θ.dim() != 0:
+            raise ValueError(f"{ops.name}.timesteps: θ must be a scalar or a 0-dim tensor")
+    if torch.is_grad_enabled() and (u.requires_grad or (temp is not None and temp.requires_grad) or (θ is not None and θ.requires_grad)):
+        out, tout = _TimeSteps.apply(u, temp, θ, adj, ops, t, float(Δt), nsteps, every)
     else:  # nothing to save: one native call
-        out, tout = adj.steps_(_copy(ops, setup, u, True), None if temp is None else _copy(ops, setup, temp, False), t, float(Δt), nsteps)
+        kw = {} if θ is None else {"θ": float(θ)}
+        out, tout = adj.steps_(_copy(ops, setup, u, True), None if temp is None else _copy(ops, setup, temp, False), t, float(Δt), nsteps, **kw)
     return create_stepper(method, setup=setup, psolver=psolver, u=out, temp=tout, t=t + nsteps * erk.c[-1] * Δt, n=stepper.n + nsteps)

@@ -77,6 +77,8 @@ SIGNATURES = {
     "ins_divoftensor_f64": (C.c_int, [vp, vp, vp, vp]),
     "ins_smagorinsky_force_f64": (C.c_int, [vp, C.c_double, vp, vp, vp, vp]),
     "ins_smagorinsky_force_needs_sigma": (C.c_int, [vp]),
+    "ins_smagorinsky_force_pullback_f64": (C.c_int, [vp, C.c_double, vp, vp, vp, C.c_int, vp, vp]),
+    "ins_smagorinsky_force_pullback_f32": (C.c_int, [vp, C.c_float, vp, vp, vp, C.c_int, vp, vp]),
     "ins_tensorbasis_f64": (C.c_int, [vp, vp, vp, vp, vp]),
     "ins_combine_scalar_f64": (C.c_int, [vp, vp, vp, C.c_int, c_double_p, C.POINTER(vp), vp]),
     "ins_spectrum_create": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(vp)]),
@@ -110,6 +112,8 @@ SIGNATURES = {
     "ins_rk_step_pullback_f32": (C.c_int, [vp, C.c_float, vp, vp, C.c_float, vp, vp]),
     "ins_rk_adjoint_set_temperature": (C.c_int, [vp, vp]),
     "ins_rk_adjoint_set_temperature_f32": (C.c_int, [vp, vp]),
+    "ins_rk_adjoint_set_closure": (C.c_int, [vp, C.c_int32, C.c_double, vp]),
+    "ins_rk_adjoint_set_closure_f32": (C.c_int, [vp, C.c_int32, C.c_double, vp]),
     "ins_rk_step_pullback_ext_f64": (C.c_int, [vp, C.c_double, vp, vp, vp, C.c_double, vp, vp, vp]),
     "ins_rk_step_pullback_ext_f32": (C.c_int, [vp, C.c_float, vp, vp, vp, C.c_float, vp, vp, vp]),
     "ins_tensorbasis_pullback_f64": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp]),

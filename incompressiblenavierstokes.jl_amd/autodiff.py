@@ -29,7 +29,7 @@ from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
 
 __all__ = ["apply_bc_u", "apply_bc_p", "apply_bc_temp", "gravity", "convection_diffusion_temp", "dissipation", "scalewithvolume", "divergence", "pressuregradient", "applypressure", "poisson", "convection", "diffusion",
            "momentum", "project", "right_hand_side", "create_right_hand_side", "timestep", "timesteps", "FaceAverage", "VolumeAverage", "tensorbasis", "divoftensor",
-           "lastdimcontract", "tensorinvariants", "tensorclosure_stress", "apply_bc_p_fields", "smagorinsky_closure"]
+           "lastdimcontract", "tensorinvariants", "tensorclosure_stress", "apply_bc_p_fields", "smagorinsky_closure", "smagorinsky_force"]
 
 
 def _check_f64(setup, *xs):
@@ -66,11 +66,22 @@ def _rk_cache(erk, setup, psolver):
     return ERKCache(erk, setup, psolver)
 
 
-def _rk_steps_(adj, u, temp, t, Δt, nsteps):
-    """`timesteps_`: ins_rk_steps_f64, or with a temperature ins_rk_step_ext_f64 step by step."""
+def _rk_steps_(adj, u, temp, t, Δt, nsteps, θ=None):
+    """`timesteps_`: ins_rk_steps_f64, or with a temperature or the Smagorinsky closure (θ) ins_rk_step_ext_f64 step by step."""
     from .time_steppers import timesteps_
 
-    timesteps_(adj.erk, create_stepper(adj.erk, setup=adj.setup, psolver=adj.cache.psolver, u=u, temp=temp, t=t), Δt, nsteps, cache=adj.cache)
+    with core.native_closure(adj.setup, θ, O.smagorinsky_closure):
+        timesteps_(adj.erk, create_stepper(adj.erk, setup=adj.setup, psolver=adj.cache.psolver, u=u, temp=temp, t=t), Δt, nsteps, θ=θ, cache=adj.cache)
+
+
+def _rk_adjoint_set_closure(adj, θ, θbar):
+    """ins_rk_adjoint_set_closure: kind 1 with θ and the device double of `θbar`, or kind 0."""
+    from . import _lib
+
+    if θ is None:
+        _lib.call("ins_rk_adjoint_set_closure", adj._handle, 0, 0.0, None)
+    else:
+        _lib.call("ins_rk_adjoint_set_closure", adj._handle, 1, float(θ), O._thetabar_ptr(adj.setup, θbar))
 
 
 def _rk_step_pullback_(adj, ubar, tempbar, ustart, tempstart, Δt):
@@ -78,7 +89,7 @@ def _rk_step_pullback_(adj, ubar, tempbar, ustart, tempstart, Δt):
     import ctypes as C
 
     from . import _lib
-    from .time_steppers import _native_ext
+    from .time_steppers import _temperature_desc
 
     setup = adj.setup
     f = setup.bodyforce if (setup.bodyforce is not None and setup.issteadybodyforce) else None
@@ -86,7 +97,7 @@ def _rk_step_pullback_(adj, ubar, tempbar, ustart, tempstart, Δt):
     if tempbar is None:
         _lib.call("ins_rk_step_pullback_f64", adj._handle, 1.0 / setup.Re, setup.ptr(ustart, True), fp, float(Δt), setup.ptr(ubar, True), setup.stream)
         return
-    desc = _native_ext(setup, tempstart, None)[2]  # per call, like the forward: `setup.temperature` may have been replaced since the last one
+    desc = _temperature_desc(setup)  # per call, like the forward: `setup.temperature` may have been replaced since the last one
     _lib.call("ins_rk_adjoint_set_temperature", adj._handle, C.byref(desc))
     _lib.call("ins_rk_step_pullback_ext_f64", adj._handle, 1.0 / setup.Re, setup.ptr(ustart, True), setup.ptr(tempstart, False), fp, float(Δt),
               setup.ptr(ubar, True), setup.ptr(tempbar, False), setup.stream)
@@ -120,6 +131,9 @@ _OPS = SimpleNamespace(
     convection_diffusion_temp_adjoint_=O.convection_diffusion_temp_adjoint_, dissipation_adjoint_=O.dissipation_adjoint_,
     temperature_pullback_=O.temperature_pullback_, project_pullback_=project_pullback_, divoftensor_adjoint_=O.divoftensor_adjoint_,
     tensorclosure_pullback_=O.tensorclosure_pullback_,
+    smagorinsky_force_=O.smagorinsky_force_,
+    smagorinsky_force_pullback_=lambda ubar, θbar, sbar, u, θ, setup: O.smagorinsky_force_pullback_(ubar, θbar, sbar, u, θ, setup),
+    rk_adjoint_set_closure=_rk_adjoint_set_closure,
     rk_cache=_rk_cache, rk_adjoint_create=_rk_adjoint_create, rk_adjoint_destroy=_rk_adjoint_destroy, rk_steps_=_rk_steps_,
     rk_step_pullback_=_rk_step_pullback_, rk_copy_=_rk_copy_,
 )
@@ -414,6 +428,17 @@ def smagorinsky_closure(setup):
     return core.smagorinsky_closure(_OPS, setup)
 
 
+def smagorinsky_force(u, θ, setup):
+    """The Smagorinsky closure force `smagorinsky_closure(setup)(u, θ)` of a ghost-filled `u` (operators.jl:1284-1300) as ONE native call, with the
+    fused pullback as backward (csrc/ins_smagpullback_kernels.h): ubar, and for a 0-dim tensor θ that requires grad θbar = 2θ <σ̄, σ̂>, which falls
+    out of the same pass.  The same function of (u, θ) as `ad.smagorinsky_closure(setup)`, without its per-stage tensor-basis fields."""
+    from .boundary_conditions import HaloBC
+
+    if any(isinstance(bc, HaloBC) for side in setup.boundary_conditions for bc in side):
+        raise NotImplementedError("ad.smagorinsky_force: slab (halo) setups are not supported")
+    return core.smagorinsky_force(_OPS, u, θ, setup)
+
+
 # ------------------------------------------------------------------------------------ time stepping
 def timestep(method, stepper, Δt, θ=None):
     """step_explicit_runge_kutta.jl:61-120: one explicit Runge-Kutta step without mutation, differentiable in `stepper.u`, in `stepper.temp`
@@ -433,9 +458,15 @@ def timestep(method, stepper, Δt, θ=None):
 
 
 # ------------------------------------------------------------------------------------ checkpointed rollouts
-def timesteps(method, stepper, Δt, nsteps, *, checkpoint_every=None):
-    """`nsteps` calls of `ad.timestep(method, ·, Δt)` as one Function: nothing is mutated, the result is differentiable in `stepper.u` and, with
-    the temperature equation, in `stepper.temp`.
+def timesteps(method, stepper, Δt, nsteps, *, θ=None, checkpoint_every=None):
+    """`nsteps` calls of `ad.timestep(method, ·, Δt)` as one Function: nothing is mutated, the result is differentiable in `stepper.u`, with
+    the temperature equation in `stepper.temp`, and with the Smagorinsky closure in its constant θ.
+
+    With `setup.closure_model` the library's Smagorinsky closure of this setup (`ins.smagorinsky_closure(setup)` or `ad.smagorinsky_closure(setup)`)
+    and `θ` its constant (a Python scalar, or a 0-dim tensor that may require grad) the closure runs inside both native loops: the forward is
+    `timesteps_(…, θ=float(θ))`, the reverse step recomputes k_i = F(v_i) [+ gravity] + f + m(v_i, θ) and adds the closure's fused pullback
+    (ins_smagorinsky_force_pullback_f64) to every stage; ∂L/∂θ of all steps and chunks is summed in one device double.  The handle then holds one
+    vector field more, and the grid handle the D·D fields of ∇ubar.
 
     The forward is the native multi-step loop (`timesteps_`: ins_rk_steps_f64, with a temperature ins_rk_step_ext_f64 per step) in chunks of
     `checkpoint_every` steps (default ceil(sqrt(nsteps))); only the state at the start of every chunk is kept.  The backward walks the chunks in
@@ -444,8 +475,9 @@ def timesteps(method, stepper, Δt, nsteps, *, checkpoint_every=None):
     (2s + 1 vector fields, with a temperature 2s + 1 scalar fields more), instead of the unrolled graph's ~10 fields per stage.
 
     Scope: fp64, ExplicitRungeKuttaMethod or LMWray3, 2-D / 3-D, any boundary conditions with constant data for u and for temp, any solver, no
-    body force or a steady one, with or without `setup.temperature`.  A closure model, callable boundary data, an unsteady body force and slab
-    setups raise NotImplementedError: use `ad.timestep` step by step.  Float32 fields: `ad32.timesteps`."""
+    body force or a steady one, with or without `setup.temperature`.  Any other closure model, a Smagorinsky closure without θ, θ without a closure,
+    callable boundary data, an unsteady body force and slab setups raise NotImplementedError: use `ad.timestep` step by step.  Float32 fields:
+    `ad32.timesteps`."""
     nsteps, every = core.checkpoint_interval(_OPS, nsteps, checkpoint_every)
     setup, psolver, u, temp = stepper.setup, stepper.psolver, stepper.u, stepper.temp
     if u.dtype == torch.float32:
@@ -462,7 +494,7 @@ def timesteps(method, stepper, Δt, nsteps, *, checkpoint_every=None):
                         "float64 fields: default_psolver and its kin)")
     if temp is not None and setup.temperature is None:
         raise ValueError("a temperature field needs setup.temperature (temperature_equation)")
-    if setup.closure_model is not None:
+    if (setup.closure_model is not None or θ is not None) and not (θ is not None and core.smagorinsky_of(setup, "ad", torch.float64)):
         raise NotImplementedError("ad.timesteps: a closure model is not part of the native reverse loop; use ad.timestep step by step")
     if temp is None and setup.temperature is not None:
         raise NotImplementedError("ad.timesteps: a setup with a temperature equation takes stepper.temp in the native reverse loop; without one use "
@@ -476,4 +508,4 @@ def timesteps(method, stepper, Δt, nsteps, *, checkpoint_every=None):
     if any(isinstance(bc, HaloBC) for side in setup.boundary_conditions for bc in side):
         raise NotImplementedError("ad.timesteps: slab (halo) setups are not supported; use ad.timestep step by step")
     _check_f64(setup, u, *(() if temp is None else (temp,)))
-    return core.timesteps(_OPS, method, stepper, Δt, nsteps, every)
+    return core.timesteps(_OPS, method, stepper, Δt, nsteps, every, θ=θ)

@@ -146,9 +146,22 @@ def _rk_cache(erk, setup, psolver):
     return cache
 
 
-def _rk_steps_(adj, u, temp, t, Δt, nsteps):
-    """`f32.timesteps32_`: ins_rk_steps_f32 (chained where it chains), or with a temperature or a steady body force ins_rk_steps_ext_f32."""
-    F32.timesteps32_(adj.cache, u, Δt, nsteps, temp=temp)
+def _rk_steps_(adj, u, temp, t, Δt, nsteps, θ=None):
+    """`f32.timesteps32_`: ins_rk_steps_f32 (chained where it chains), or with a temperature, a steady body force or the Smagorinsky closure (θ)
+    ins_rk_steps_ext_f32."""
+    with core.native_closure(adj.setup, θ, F32.smagorinsky_closure32):
+        F32.timesteps32_(adj.cache, u, Δt, nsteps, temp=temp, θ=θ)
+
+
+def _rk_adjoint_set_closure(adj, θ, θbar):
+    """ins_rk_adjoint_set_closure_f32: kind 1 with θ and the device double of `θbar`, or kind 0."""
+    from . import _lib
+    from .operators import _thetabar_ptr
+
+    if θ is None:
+        _lib.call("ins_rk_adjoint_set_closure_f32", adj._handle, 0, 0.0, None)
+    else:
+        _lib.call("ins_rk_adjoint_set_closure_f32", adj._handle, 1, float(θ), _thetabar_ptr(adj.setup, θbar))
 
 
 def _rk_step_pullback_(adj, ubar, tempbar, ustart, tempstart, Δt):
@@ -189,6 +202,10 @@ _OPS = SimpleNamespace(
     convection_diffusion_temp_adjoint_=F32.convection_diffusion_temp_adjoint32_, dissipation_adjoint_=F32.dissipation_adjoint32_,
     temperature_pullback_=F32.temperature_pullback32_, project_pullback_=F32.project_pullback32_,
     divoftensor_adjoint_=F32.divoftensor_adjoint32_, tensorclosure_pullback_=F32.tensorclosure_pullback32_,
+    smagorinsky_force_=lambda s, u, θ, setup: F32.smagorinsky_force32_(
+        s, u, θ, setup, F32.tensorfield32(setup) if F32._lib.load().ins_smagorinsky_force_needs_sigma(setup.handle) else None),
+    smagorinsky_force_pullback_=lambda ubar, θbar, sbar, u, θ, setup: F32.smagorinsky_force_pullback32_(ubar, θbar, sbar, u, θ, setup),
+    rk_adjoint_set_closure=_rk_adjoint_set_closure,
     rk_cache=_rk_cache, rk_adjoint_create=_rk_adjoint_create, rk_adjoint_destroy=_rk_adjoint_destroy, rk_steps_=_rk_steps_,
     rk_step_pullback_=_rk_step_pullback_, rk_copy_=lambda dst, src, setup, vector: dst.copy_(src),
 )
@@ -302,6 +319,13 @@ def smagorinsky_closure(setup):
     return core.smagorinsky_closure(_OPS, setup)
 
 
+def smagorinsky_force(u, θ, setup):
+    """The Smagorinsky closure force of a ghost-filled float32 `u` as ONE native call (ins_smagorinsky_force_f32), with the fused pullback as backward
+    (ins_smagorinsky_force_pullback_f32): `ad.smagorinsky_force` with T = Float32.  θbar is summed in double and returned in θ's dtype."""
+    _check_slab(setup, "smagorinsky_force")
+    return core.smagorinsky_force(_OPS, u, θ, setup)
+
+
 def timestep(method, stepper, Δt, θ=None):
     """step_explicit_runge_kutta.jl:61-120 with T = Float32: one explicit Runge-Kutta step without mutation, differentiable in `stepper.u`,
     in `stepper.temp` (with the temperature equation) and (through a torch closure model `m(u, θ)`) in θ; `ad.timestep` on the Float32
@@ -315,17 +339,23 @@ def timestep(method, stepper, Δt, θ=None):
     return core.timestep(_OPS, method, stepper, Δt, θ)
 
 
-def timesteps(method, stepper, Δt, nsteps, *, checkpoint_every=None):
+def timesteps(method, stepper, Δt, nsteps, *, θ=None, checkpoint_every=None):
     """`nsteps` calls of `ad32.timestep(method, ·, Δt)` as one Function with T = Float32: `ad.timesteps` on float32 fields, differentiable in
-    `stepper.u` and, with the temperature equation, in `stepper.temp`.
+    `stepper.u`, with the temperature equation in `stepper.temp`, and with the Smagorinsky closure in its constant θ.
+
+    With `setup.closure_model` the library's Smagorinsky closure of this setup (`f32.smagorinsky_closure32(setup)` or
+    `ad32.smagorinsky_closure(setup)`) and `θ` its constant (a Python scalar, or a 0-dim tensor that may require grad) the closure runs inside both
+    native loops (`timesteps32_(…, θ=float(θ))`; ins_smagorinsky_force_f32 and ins_smagorinsky_force_pullback_f32 in the reverse step), and ∂L/∂θ
+    of all steps and chunks is summed in one device double.
 
     The forward is `f32.timesteps32_` (ins_rk_steps_f32; with a temperature or a steady body force ins_rk_steps_ext_f32) in chunks of
     `checkpoint_every` steps (default ceil(sqrt(nsteps))), only the chunk-start states are kept, and the backward recomputes a chunk and calls the
     native reverse step once per step (ins_rk_step_pullback_f32, with a temperature ins_rk_step_pullback_ext_f32), all in float.
 
     Scope: what `ad32.timestep` takes without a closure: ExplicitRungeKuttaMethod or LMWray3, 2-D / 3-D, any boundary conditions with constant
-    data, a Float32 solver, no body force or a steady one, with or without `setup.temperature`.  A closure model, callable boundary data, an unsteady
-    body force and slab setups raise NotImplementedError: use `ad32.timestep` step by step (or `ins_amd.ad`)."""
+    data, a Float32 solver, no body force or a steady one, with or without `setup.temperature`.  Any other closure model, a Smagorinsky closure
+    without θ, θ without a closure, callable boundary data, an unsteady body force and slab setups raise NotImplementedError: use `ad32.timestep`
+    step by step (or `ins_amd.ad`)."""
     nsteps, every = core.checkpoint_interval(_OPS, nsteps, checkpoint_every)
     setup, psolver, u, temp = stepper.setup, stepper.psolver, stepper.u, stepper.temp
     if u.dtype != torch.float32:
@@ -337,7 +367,7 @@ def timesteps(method, stepper, Δt, nsteps, *, checkpoint_every=None):
                         "float64 fields: ad.timesteps with default_psolver and its kin)")
     if temp is not None and setup.temperature is None:
         raise ValueError("a temperature field needs setup.temperature (temperature_equation)")
-    if setup.closure_model is not None:
+    if (setup.closure_model is not None or θ is not None) and not (θ is not None and core.smagorinsky_of(setup, "ad32", torch.float32)):
         raise NotImplementedError("ad32.timesteps: a closure model is not part of the native reverse loop; use ad32.timestep step by step")
     if temp is None and setup.temperature is not None:
         raise NotImplementedError("ad32.timesteps: a setup with a temperature equation takes stepper.temp in the native reverse loop; without one use "
@@ -359,4 +389,4 @@ def timesteps(method, stepper, Δt, nsteps, *, checkpoint_every=None):
     _check_vec(setup, u)
     if temp is not None and tuple(temp.shape) != tuple(setup.grid.N):
         raise ValueError(f"expected a temperature field of shape {tuple(setup.grid.N)}, got {tuple(temp.shape)}")
-    return core.timesteps(_OPS, method, stepper, Δt, nsteps, every)
+    return core.timesteps(_OPS, method, stepper, Δt, nsteps, every, θ=θ)

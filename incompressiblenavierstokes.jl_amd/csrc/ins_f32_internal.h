@@ -25,6 +25,9 @@ int ins_k32t_stage(const ins_grid* G, float a4, float coef, const float* u, cons
 // ins_smagforce32.hip: the Smagorinsky closure force in one kernel (grids: ins_smagforce_supported); u with its boundary data applied
 int ins_k_smagforce_f32(const ins_grid* G, float theta, const float* u, float* sout, hipStream_t s);
 
+// ins_tensorclosure32.hip: pass 2 of the tensor-basis pullbacks, ubar (+)= ∇ᵀ of the ∇ubar scratch gb read as floats
+int ins_k32_gradu_adjoint(const ins_grid* G, const float* gb, float* ubar, bool accumulate, hipStream_t s);
+
 // ins_flux64.hip, ins_flux128.hip: the stage kernels instantiated for float; RkEpi's pointers are float arrays then
 int ins_k_flux64_f32(const ins_grid* G, double visc, const float* u, float* F, const RkEpi* epi, const float* pI, int corr_mode, hipStream_t s, int part = 0);
 int ins_k_flux128_f32(const ins_grid* G, double visc, const float* u, float* F, const RkEpi* epi, const float* pI, int corr_mode, hipStream_t s, int part);

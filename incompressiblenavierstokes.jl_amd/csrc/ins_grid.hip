@@ -192,6 +192,7 @@ extern "C" int ins_grid_destroy(ins_grid_t* G) {
   if (G->rec_dev) (void)hipFree(G->rec_dev);
   if (G->rec_diff_dev) (void)hipFree(G->rec_diff_dev);
   if (G->gradbar_dev) (void)hipFree(G->gradbar_dev);
+  if (G->smagpart_dev) (void)hipFree(G->smagpart_dev);
   if (G->red_host) (void)hipHostFree(G->red_host);
   delete G;
   return INS_OK;

@@ -202,6 +202,9 @@ struct ins_grid {
   // ∇ubar of the tensor-basis pullbacks (ins_tensorclosure.hip): D·D scalar fields, allocated on first use
   double* gradbar_dev = nullptr;
   size_t gradbar_count = 0;
+  // workgroup partials of the Smagorinsky force pullback's θ cotangent (ins_smagpullback.hip), allocated on first use
+  double* smagpart_dev = nullptr;
+  size_t smagpart_count = 0;
 };
 
 enum PoissonKind { POISSON_SPECTRAL = 0, POISSON_CG = 1, POISSON_FDM = 2 };
@@ -441,6 +444,10 @@ bool ins_smagforce_supported(const ins_grid* G);
 int ins_k_smagforce(const ins_grid* G, double theta, const double* u, const double* pI, double* sout, hipStream_t s);
 // ins_tensorclosure.hip: the grid handle's ∇ubar scratch (D·D doubles per volume), allocated and grown on demand
 int ins_k_gradbar_scratch(const ins_grid* G, double** out);
+// ... and pass 2 of its pullbacks: ubar (+)= ∇ᵀ of the ∇ubar scratch gb, over the whole padded array
+int ins_k_gradu_adjoint(const ins_grid* G, const double* gb, double* ubar, bool accumulate, hipStream_t s);
+// ins_smagpullback.hip: the grid handle's scratch for the workgroup partials of the Smagorinsky force pullback (one double per workgroup of its pass 1)
+int ins_k_smag_partials(const ins_grid* G, double** out);
 // ins_adjoint.hip: transposes of apply_bc_u! / apply_bc_p! in place, and ubar = J(u)ᵀ (Σ_q coefs[q]·ks[q]) (the reverse Runge-Kutta stage)
 int ins_k_apply_bc_u_pullback(const ins_grid* G, double* u, hipStream_t s);
 int ins_k_apply_bc_p_pullback(const ins_grid* G, double* p, hipStream_t s);

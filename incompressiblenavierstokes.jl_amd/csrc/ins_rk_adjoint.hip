@@ -11,8 +11,9 @@
 // INS_ADJ_COMB_MAX terms, it is never written: the momentum pullback kernels read the ȳ_{i'} and form the combination where they load the
 // cotangent (PhiComb, ins_adjoint_kernels.h).  That saves 48 B per cell and stage and measured slower on an MI355X, hence opt-in.
 //
-// That loop is kept as it was.  The Float32 step and the steps with a temperature (ins_rk_step_pullback_f32, ins_rk_step_pullback_ext_f64 / _f32) run
-// the one generic loop of ins_rk_adjoint_loop.h, which never fuses the combination (INS_ADJ_STAGE_FUSED is ignored there).
+// That loop is kept as it was; with a closure set (ins_rk_adjoint_set_closure) ins_rk_step_pullback_f64 runs the generic loop instead.  The Float32
+// step and the steps with a temperature (ins_rk_step_pullback_f32, ins_rk_step_pullback_ext_f64 / _f32) run the one generic loop of
+// ins_rk_adjoint_loop.h, which never fuses the combination (INS_ADJ_STAGE_FUSED is ignored there).
 #include "ins_adjoint_kernels.h"
 #include "ins_f32_internal.h"
 #include "ins_rk_adjoint_loop.h"
@@ -48,6 +49,8 @@ int adjoint_destroy(ADJ* adj) {
   if (adj->kbar) (void)hipFree(adj->kbar);
   if (adj->pwork) (void)hipFree(adj->pwork);
   if (adj->cbar) (void)hipFree(adj->cbar);
+  if (adj->mforce) (void)hipFree(adj->mforce);
+  if (adj->sigma) (void)hipFree(adj->sigma);
   delete adj;
   return INS_OK;
 }
@@ -121,6 +124,32 @@ int adjoint_set_temperature(RkAdjointT<T, PS>* adj, const ins_temperature_desc_t
   return INS_OK;
 }
 
+// kind, θ and the θ cotangent's address; on the first kind 1 the closure force's vector field and, where the force runs as three kernels, its `sigma`
+// scratch, zeroed (the force writes degrees of freedom only)
+template <typename T, typename PS>
+int adjoint_set_closure(RkAdjointT<T, PS>* adj, int32_t kind, double theta, double* thetabar) {
+  INS_REQUIRE(kind == 0 || kind == 1, "unknown closure kind");
+  if (kind == 1 && !adj->mforce) {
+    const ins_grid* G = adj->grid;
+    const int D = G->g.D;
+    const size_t vbytes = (size_t)G->ncell * D * sizeof(T), tbytes = (size_t)G->ncell * (D * (D + 1) / 2) * sizeof(T);
+    const bool need_sigma = ins_smagorinsky_force_needs_sigma(G) != 0;
+    bool ok = hipMalloc(&adj->mforce, vbytes) == hipSuccess && hipMemset(adj->mforce, 0, vbytes) == hipSuccess;
+    if (ok && need_sigma) ok = hipMalloc(&adj->sigma, tbytes) == hipSuccess && hipMemset(adj->sigma, 0, tbytes) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      if (adj->mforce) (void)hipFree(adj->mforce), adj->mforce = nullptr;
+      if (adj->sigma) (void)hipFree(adj->sigma), adj->sigma = nullptr;
+      ins_set_error("ins_rk_adjoint_set_closure: device allocation of the closure scratch failed");
+      return INS_ERR_HIP;
+    }
+  }
+  adj->closure_kind = kind;
+  adj->theta = kind ? theta : 0.0;
+  adj->thetabar = kind ? thetabar : nullptr;
+  return INS_OK;
+}
+
 // ∂L/∂(u_out, temp_out) -> ∂L/∂(ustart, tempstart): the argument checks of the coupled entries, then the generic loop
 template <typename T, typename PS>
 int step_pullback_ext(RkAdjointT<T, PS>* adj, T visc, const T* ustart, const T* tempstart, const T* bodyforce, T dt, T* ubar, T* tempbar, void* stream) {
@@ -166,6 +195,16 @@ extern "C" int ins_rk_adjoint_set_temperature_f32(ins_rk_adjoint32_t* adj, const
   return adjoint_set_temperature(adj, desc);
 }
 
+extern "C" int ins_rk_adjoint_set_closure(ins_rk_adjoint_t* adj, int32_t kind, double theta, double* thetabar) {
+  INS_REQUIRE(adj, "null argument");
+  return adjoint_set_closure(adj, kind, theta, thetabar);
+}
+
+extern "C" int ins_rk_adjoint_set_closure_f32(ins_rk_adjoint32_t* adj, int32_t kind, double theta, double* thetabar) {
+  INS_REQUIRE(adj, "null argument");
+  return adjoint_set_closure(adj, kind, theta, thetabar);
+}
+
 extern "C" int ins_rk_step_pullback_f32(ins_rk_adjoint32_t* adj, float visc, const float* ustart, const float* bodyforce, float dt, float* ubar, void* stream) {
   INS_REQUIRE(adj && ustart && ubar, "null argument");
   INS_REQUIRE(ubar != ustart, "the step pullback cannot run in place (ubar aliases ustart)");
@@ -187,6 +226,10 @@ extern "C" int ins_rk_step_pullback_f64(ins_rk_adjoint_t* adj, double visc, cons
                                         void* stream) {
   INS_REQUIRE(adj && ustart && ubar, "null argument");
   INS_REQUIRE(ubar != ustart, "the step pullback cannot run in place (ubar aliases ustart)");
+  if (adj->closure_kind) {  // the closure lives in the generic loop
+    INS_REQUIRE(!bodyforce || bodyforce != ubar, "the body force aliases the output");
+    return rkadj::step_pullback<double, ins_poisson>(adj, false, visc, ustart, nullptr, bodyforce, dt, ubar, nullptr, as_stream(stream));
+  }
   const ins_grid* G = adj->grid;
   hipStream_t s = as_stream(stream);
   const int ns = adj->nstage;

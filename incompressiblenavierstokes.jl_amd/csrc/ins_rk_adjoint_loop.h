@@ -4,7 +4,7 @@
 //
 // Forward, stage i = 0..s-1, u_0 = ustart, T_0 = tempstart (A the shifted tableau, f the steady body force or 0):
 //     v_i = bc_u(u_i)   τ_i = bc_T(T_i)
-//     k_i = F(v_i) + gravity(τ_i) + f                       c_i = convdiff_temp(v_i, τ_i) + [diss] dissipation(v_i)
+//     k_i = F(v_i) + gravity(τ_i) + f [+ m(v_i, θ)]         c_i = convdiff_temp(v_i, τ_i) + [diss] dissipation(v_i)
 //     w_i = ustart + Δt Σ_j A[i,j] k_j                      T_{i+1} = tempstart + Δt Σ_j A[i,j] c_j
 //     u_{i+1} = P(bc_u(w_i));                               u_out = bc_u(u_s), temp_out = bc_T(T_s)
 // Reverse, (g_u, g_T) the cotangents of (v_{i+1}, τ_{i+1}), of (u_out, temp_out) at the start:
@@ -12,6 +12,9 @@
 //     k̄_i = Δt Σ_{i'>=i} A[i',i] ȳ_{i'}                     c̄_i = Δt Σ_{i'>=i} A[i',i] z̄_{i'}
 //     g_u = J_F(v_i)ᵀ k̄_i, then the temperature stage pullback at (v_i, τ_i) with (Fbar, cbar) = (k̄_i, c̄_i): g_u +=, g_T =
 // and ∂L/∂ustart = Σ_i ȳ_i + bc_uᵀ g_u, ∂L/∂tempstart = Σ_i z̄_i + bc_Tᵀ g_T.
+// With the Smagorinsky closure m (set_closure; the order of `_autodiff_core.timestep`: momentum (+ gravity), body force, closure) the recomputation adds
+// ins_smagorinsky_force_* at v_i as one more term of the combination, and the reverse sweep adds its pullback at (v_i, k̄_i) after the momentum
+// pullback:  g_u += (∂m/∂u)ᵀ k̄_i,  *thetabar += (∂m/∂θ)ᵀ k̄_i  (ins_smagorinsky_force_pullback_*).
 //
 // The (v_i, τ_i) are recomputed with the operator-level entries of the respective family, as the isothermal fp64 loop does.  k̄_i and c̄_i are
 // formed by ONE launch (k_adj_stage_sums) and the two closing sums by one more (k_adj_close_sums): streaming kernels, 16-byte accesses where
@@ -40,6 +43,13 @@ struct RkAdjointT {
   std::vector<T*> tau;  // stage temperatures τ_i (ghosts filled)
   std::vector<T*> z;    // c_i during the recomputation, then the stage cotangents z̄_i
   T* cbar = nullptr;
+  // Smagorinsky closure (set_closure): θ, the device double that collects ∂L/∂θ (nullable), the closure force of the stage being recomputed and the
+  // `sigma` scratch of the three-kernel force (where ins_smagorinsky_force_needs_sigma answers 1)
+  int closure_kind = 0;
+  double theta = 0.0;
+  double* thetabar = nullptr;
+  T* mforce = nullptr;
+  T* sigma = nullptr;
 };
 
 namespace rkadj {
@@ -223,6 +233,18 @@ inline int momentum_pullback(const ins_grid* G, double visc, const double* u, co
 inline int momentum_pullback(const ins_grid* G, float visc, const float* u, const float* phibar, float* ubar, hipStream_t s) {
   return ins_momentum_pullback_f32(G, visc, u, phibar, ubar, 0, s);
 }
+inline int closure_force(const ins_grid* G, double theta, const double* u, double* sigma, double* m, hipStream_t s) {
+  return ins_smagorinsky_force_f64(G, theta, u, sigma, m, s);
+}
+inline int closure_force(const ins_grid* G, double theta, const float* u, float* sigma, float* m, hipStream_t s) {
+  return ins_smagorinsky_force_f32(G, (float)theta, u, sigma, m, s);
+}
+inline int closure_pullback(const ins_grid* G, double theta, const double* u, const double* sbar, double* ubar, double* thetabar, hipStream_t s) {
+  return ins_smagorinsky_force_pullback_f64(G, theta, u, sbar, ubar, 1, thetabar, s);
+}
+inline int closure_pullback(const ins_grid* G, double theta, const float* u, const float* sbar, float* ubar, double* thetabar, hipStream_t s) {
+  return ins_smagorinsky_force_pullback_f32(G, (float)theta, u, sbar, ubar, 1, thetabar, s);
+}
 inline int temperature_pullback(const ins_grid* G, const ins_temperature_desc_t& td, double visc, const double* u, const double* t, const double* Fbar,
                                 const double* cbar, double* ubar, double* tempbar, hipStream_t s) {
   return ins_temperature_pullback_f64(G, &td, visc, u, t, Fbar, cbar, ubar, tempbar, s);
@@ -254,6 +276,7 @@ int step_pullback(RkAdjointT<T, PS>* adj, bool with_temp, T visc, const T* ustar
     if ((rc = momentum(G, visc, adj->v[i], adj->y[i], s))) return rc;                         // :21
     T coef[INS_MAX_STAGES + 1];
     const T* k[INS_MAX_STAGES + 1];
+    const bool closure = adj->closure_kind == 1;
     if (with_temp) {
       if ((rc = gravity(G, td, adj->tau[i], adj->y[i], s))) return rc;
       INS_HIP_TRY(hipMemsetAsync(adj->z[i], 0, sbytes, s));                                   // :23-27
@@ -261,6 +284,12 @@ int step_pullback(RkAdjointT<T, PS>* adj, bool with_temp, T visc, const T* ustar
       if (td.dodissipation && (rc = dissipation(G, td, visc, adj->v[i], adj->kbar, adj->z[i], s))) return rc;
       const int n = ins_rk_sum_terms(A, ns, i, dt, adj->z.data(), (const T*)nullptr, coef, k);  // :39-44
       if ((rc = combine(G, G->ncell, tempstart, adj->tau[i + 1], n, coef, k, s))) return rc;
+    }
+    if (closure) {                                                                            // :31-34, the last term of k_i: k_i += m(v_i, θ)
+      if ((rc = closure_force(G, adj->theta, adj->v[i], adj->sigma, adj->mforce, s))) return rc;
+      const T one = 1;
+      const T* both[1] = {adj->mforce};
+      if ((rc = combine(G, nvec, adj->y[i], adj->y[i], 1, &one, both, s))) return rc;
     }
     const int n = ins_rk_sum_terms(A, ns, i, dt, adj->y.data(), bodyforce, coef, k);          // :35-38
     if ((rc = combine(G, nvec, ustart, adj->v[i + 1], n, coef, k, s))) return rc;
@@ -297,6 +326,7 @@ int step_pullback(RkAdjointT<T, PS>* adj, bool with_temp, T visc, const T* ustar
     }
     if ((rc = launch_sums<T, false>(nvec, nsc, adj->kbar, adj->cbar, ts, s))) return rc;
     if ((rc = momentum_pullback(G, visc, adj->v[i], adj->kbar, out, s))) return rc;
+    if (adj->closure_kind == 1 && (rc = closure_pullback(G, adj->theta, adj->v[i], adj->kbar, out, adj->thetabar, s))) return rc;
     if (with_temp && (rc = temperature_pullback(G, td, visc, adj->v[i], adj->tau[i], adj->kbar, adj->cbar, out, tout, s))) return rc;
   }
   if ((rc = bc_u_pullback(G, ubar, s))) return rc;                                            // :19 of stage 0

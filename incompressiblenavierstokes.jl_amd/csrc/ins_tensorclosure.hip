@@ -135,6 +135,8 @@ int launch_gradu_adjoint(const ins_grid* G, const double* gb, double* ubar, bool
 
 // the same scratch for ins_tensorclosure32.hip, which reads the bytes as float
 int ins_k_gradbar_scratch(const ins_grid* G, double** out) { return gradbar_scratch(G, out); }
+// pass 2 for ins_smagpullback.hip
+int ins_k_gradu_adjoint(const ins_grid* G, const double* gb, double* ubar, bool accumulate, hipStream_t s) { return launch_gradu_adjoint(G, gb, ubar, accumulate, s); }
 
 // ------------------------------------------------------------------------------------------------
 // C ABI

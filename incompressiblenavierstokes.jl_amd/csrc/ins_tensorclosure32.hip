@@ -12,6 +12,7 @@
 // (ins_tensorclosure.hip allocates and grows it, D·D doubles per volume); its first half is used here as D·D floats per volume.  A
 // translation unit of its own so that the fp64 kernels keep their register allocation.  Slab (HALO) sides are not taken: the multi-GPU
 // path is fp64.
+#include "ins_f32_internal.h"
 #include "ins_tensorbasis.h"
 
 namespace {
@@ -120,6 +121,16 @@ __global__ __launch_bounds__(256) void k32_divoftensor_adjoint(GridDev g, const 
 }
 
 }  // namespace
+
+// pass 2 for ins_smagpullback32.hip
+int ins_k32_gradu_adjoint(const ins_grid* G, const float* gb, float* ubar, bool accumulate, hipStream_t s) {
+  const GridDev& g = G->g;
+  if (accumulate)
+    INS_LAUNCH_D((k32_gradu_adjoint<D, true>), box_launch(g.D, g.N), s, g, gb, ubar);
+  else
+    INS_LAUNCH_D((k32_gradu_adjoint<D, false>), box_launch(g.D, g.N), s, g, gb, ubar);
+  return INS_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // C ABI

@@ -355,6 +355,18 @@ def smagorinsky_force32_(s, u, θ, setup, σ=None):
     return s
 
 
+def smagorinsky_force_pullback32_(ubar, θbar, sbar, u, θ, setup, accumulate=False):
+    """Pullback of `smagorinsky_force32_` at the ghost-filled float32 `u` (csrc/ins_smagpullback_kernels.h with T = float): ubar = (∂s/∂u)ᵀ sbar
+    (overwritten, or added to with `accumulate`) and θbar += (∂s/∂θ)ᵀ sbar, `θbar` a 0-dim FLOAT64 device tensor the caller zeroes (the cells' terms are
+    formed in float and summed in double), or None."""
+    from .operators import _thetabar_ptr
+
+    D = setup.grid.dimension
+    _lib.call("ins_smagorinsky_force_pullback_f32", setup.handle, float(θ), _ptr(setup, u, D), _ptr(setup, sbar, D), _ptr(setup, ubar, D),
+              int(bool(accumulate)), _thetabar_ptr(setup, θbar), setup.stream)
+    return ubar, θbar
+
+
 def smagorinsky_closure32(setup):
     """Create the Smagorinsky closure model `m(u, θ)` on float32 padded fields (operators.jl:1284-1300), marked like `smagorinsky_closure` so that
     `timestep32_` / `timesteps32_` run it inside the native stage loop (ins_rk_set_closure_f32)."""
@@ -370,6 +382,7 @@ def smagorinsky_closure32(setup):
         return smagorinsky_force32_(s, u, θ, setup, σ)
 
     closure._ins_closure, closure._ins_setup = "smagorinsky", setup
+    closure._ins_dtype = torch.float32
     return closure
 
 

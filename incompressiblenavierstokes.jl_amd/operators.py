@@ -495,7 +495,36 @@ def smagorinsky_closure(setup):
         return s
 
     closure._ins_closure, closure._ins_setup = "smagorinsky", setup  # lets timestep_ run it inside the native stage loop (ins_rk_set_closure)
+    closure._ins_dtype = torch.float64
     return closure
+
+
+def smagorinsky_force_(s, u, θ, setup, σ=None):
+    """s = divoftensor(apply_bc_p(smagtensor(u, θ))) on the degrees of freedom (operators.jl:1284-1300) as one native call: one kernel where the
+    grid allows it, else the three kernels with the `tensorfield` σ as scratch (allocated here when needed and not given)."""
+    D = setup.grid.dimension
+    σp = None
+    if _lib.load().ins_smagorinsky_force_needs_sigma(setup.handle):
+        σp = setup.ptr(tensorfield(setup) if σ is None else σ, D * (D + 1) // 2)
+    _lib.call("ins_smagorinsky_force_f64", setup.handle, float(θ), setup.ptr(u, True), σp, setup.ptr(s, True), setup.stream)
+    return s
+
+
+def _thetabar_ptr(setup, θbar):
+    """Device pointer of the 0-dim float64 tensor that collects ∂L/∂θ (both precisions), or NULL."""
+    if θbar is None:
+        return None
+    if not isinstance(θbar, torch.Tensor) or θbar.dtype != torch.float64 or θbar.dim() != 0 or θbar.device != setup.device:
+        raise TypeError("θbar must be a 0-dim float64 tensor on the setup's device")
+    return C.c_void_p(θbar.data_ptr())
+
+
+def smagorinsky_force_pullback_(ubar, θbar, sbar, u, θ, setup, accumulate=False):
+    """Pullback of `smagorinsky_force_` at the ghost-filled `u` (csrc/ins_smagpullback_kernels.h): ubar = (∂s/∂u)ᵀ sbar (overwritten, or added to
+    with `accumulate`) and θbar += (∂s/∂θ)ᵀ sbar, `θbar` a 0-dim float64 device tensor the caller zeroes, or None.  `sbar` is read on Iu only."""
+    _lib.call("ins_smagorinsky_force_pullback_f64", setup.handle, float(θ), setup.ptr(u, True), setup.ptr(sbar, True), setup.ptr(ubar, True),
+              int(bool(accumulate)), _thetabar_ptr(setup, θbar), setup.stream)
+    return ubar, θbar
 
 
 # ------------------------------------------------------------------------------------ tensor basis

@@ -247,16 +247,24 @@ def _native_ext(setup, temp, θ):
         kind = 1
     desc = None
     if temp is not None:
-        from .operators import _temp_bc_args
-
-        T = setup.temperature
-        codes, vals, planes, _ = _temp_bc_args(setup, 0.0)
-        if planes is not None:
+        desc = _temperature_desc(setup)
+        if desc is None:
             return None  # callable temperature boundary data
-        desc = _TempDesc(a2=T.α2, a4=T.α4, diss_coef=setup.Re * T.α1 / T.γ, gdir=int(T.gdir), dodissipation=int(T.dodissipation))
-        for q in range(6):
-            desc.bc[q], desc.val[q] = codes[q], vals[q]
     return kind, float(θ) if kind else 0.0, desc
+
+
+def _temperature_desc(setup):
+    """The descriptor of `setup.temperature` for the native loops (ins_temperature_desc_t), or None with callable temperature boundary data."""
+    from .operators import _temp_bc_args
+
+    T = setup.temperature
+    codes, vals, planes, _ = _temp_bc_args(setup, 0.0)
+    if planes is not None:
+        return None
+    desc = _TempDesc(a2=T.α2, a4=T.α4, diss_coef=setup.Re * T.α1 / T.γ, gdir=int(T.gdir), dodissipation=int(T.dodissipation))
+    for q in range(6):
+        desc.bc[q], desc.val[q] = codes[q], vals[q]
+    return desc
 
 
 def _temp_rhs_(ktemp, diff, u, temp, setup):
