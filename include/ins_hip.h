@@ -50,7 +50,8 @@ typedef struct ins_rk_adjoint ins_rk_adjoint_t; /* work arrays of the reverse Ru
 typedef struct ins_rk_adjoint32 ins_rk_adjoint32_t; /* the same for T = Float32 (ins_rk_step_pullback_f32) */
 typedef struct ins_rk ins_rk_t;           /* `ode_method_cache` + stepper state    (time_stepper_caches.jl:34-49) */
 typedef struct ins_poisson32 ins_poisson32_t; /* `psolver_spectral` closure for T = Float32 */
-typedef struct ins_rk32 ins_rk32_t;           /* `ode_method_cache` for T = Float32 */
+typedef struct ins_rk_ensemble ins_rk_ensemble_t; /* B-fold work arrays of the ensemble stepper (ins_rk_ensemble_steps_f64) */
+typedef struct ins_rk32 ins_rk32_t;          /* `ode_method_cache` for T = Float32 */
 typedef struct ins_comm ins_comm_t;       /* one rank of an RCCL communicator (multi-GPU z-slabs; no reference counterpart) */
 
 /* Host-side description of `setup.grid` + `setup.boundary_conditions`; all pointers are HOST pointers
@@ -263,6 +264,19 @@ int ins_rk_step_bc_f64(ins_rk_t* rk, double visc, double* u, double t, double dt
  * but the last is applied in registers by the next step's first stage kernel (same arithmetic per cell; the uncorrected intermediate
  * fields are never visible); elsewhere this is exactly nsteps calls of ins_rk_step_f64. */
 int ins_rk_steps_f64(ins_rk_t* rk, double visc, double* u, double t, double dt, int nsteps, void* stream);
+/* Ensemble stepping (csrc/ins_rk_ensemble.hip): nbatch independent velocity fields of ONE 2-D setup advanced by the chained loop of ins_rk_steps_f64 with
+ * the member as one more launch dimension, so a step costs the launches of a single field whatever nbatch is.  Re, Δt and the tableau are shared; no
+ * member sees another, and member b comes out bitwise as ins_rk_steps_f64 leaves that field on its own.
+ * Boxes: exactly those on which ins_rk_steps_f64 runs its chained 2-D loop — all-periodic, exactly uniform, fp64, power-of-two sides 16 .. 1024, a spectral
+ * solver on its own 2-D passes, nstage > 1 (and none of the INS_DISABLE_* switches that turn that loop off).  Anything else: INS_ERR_UNSUPPORTED from
+ * ins_rk_ensemble_create, with a message that names ins_rk_steps_f64 per member.  No body force, closure, temperature or boundary data.
+ * The handle owns the nbatch-fold work arrays (stage forces, two stage buffers, start field, pressure, spectrum); it reads the solver's symbol and twiddle
+ * tables and never writes the solver's own arrays.  `grid` and `poisson` must outlive it.
+ * U: member b is an ordinary vector field of the grid (padded N0 x N1, component stride ncell) at U + b·ustride, ustride >= 2·ncell elements; what lies
+ * between two members is not touched.  Ghost volumes of every member are valid on return.  Asynchronous on `stream`. */
+int ins_rk_ensemble_create(const ins_grid_t* grid, ins_poisson_t* poisson, int nstage, const double* A, const double* c, int nbatch, ins_rk_ensemble_t** out);
+int ins_rk_ensemble_destroy(ins_rk_ensemble_t* ens);
+int ins_rk_ensemble_steps_f64(ins_rk_ensemble_t* ens, double visc, double* U, int64_t ustride, double t, double dt, int nsteps, void* stream);
 /* Device pointers into the cache (valid until ins_rk_destroy): the stage pressure `p` and `ku[i]`. */
 /* K6 alone: out = base + Σ_q coefs[q]·ks[q] over whole vector fields, summed in index order — the stage-combination
  * broadcasts `u .= ustart; u .+= Δt A[i,j] ku[j]` (step_explicit_runge_kutta.jl:35-38) and LMWray3's state_copyto! /

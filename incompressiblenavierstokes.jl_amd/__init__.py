@@ -101,10 +101,11 @@ from .pressure import (
 )
 from .processors import (Observable, fieldsaver, get_scale_numbers, observefield, observespectrum, processor, save_vtk, spectral_stuff, timelogger,
                          vtk_writer)
-from .setup import Setup, copyfield, from_numpy, scalarfield, temperature_equation, to_numpy, vectorfield
+from .setup import Setup, copyfield, from_numpy, scalarfield, temperature_equation, to_numpy, vectorfield, vectorfields
 from .sciml import create_right_hand_side, right_hand_side_
 from .solver import get_cfl_timestep_, get_state, solve_unsteady
 from .time_steppers import (
+    EnsembleCache,
     ExplicitRungeKuttaMethod,
     LMWray3,
     RKMethods,
@@ -114,6 +115,7 @@ from .time_steppers import (
     timestep,
     timestep_,
     timesteps_,
+    timesteps_ensemble_,
 )
 from . import autodiff as ad  # noqa: E402  (torch.autograd Functions over the pullback kernels: ins_amd.ad)
 from . import autodiff32 as ad32  # noqa: E402  (the same over float32 fields and the `_f32` pullbacks: ins_amd.ad32)

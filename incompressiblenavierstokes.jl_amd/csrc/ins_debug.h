@@ -43,6 +43,10 @@ int ins_dbg_rk_stage_terms(int32_t ns, const double* A, int32_t i, double dt, in
 /* test / lab hook, not part of the public ABI: how many steps this integrator's cache has run as graph replays */
 long long ins_dbg_rk_graph_replays(const ins_rk_t* rk);
 
+/* ins_rk_ensemble.hip.  Test hook, not part of the public ABI (needs no device): the argument checks ins_rk_ensemble_create and ins_rk_ensemble_steps_f64 make
+ * once they know the grid's ncell — the member count, the step count and the member stride */
+int ins_dbg_rk_ensemble_args(int64_t ncell, int32_t nbatch, int64_t ustride, int32_t nsteps);
+
 /* ins_rk_ext.hip.  Test hooks, not part of the public ABI: how many steps of the extended stage loop took the tiled / the fused path */
 long long ins_dbg_ext_tiled_steps(void);
 long long ins_dbg_ext_fused_steps(void);

@@ -353,10 +353,14 @@ __global__ __launch_bounds__(256) void k_yfft(C* __restrict__ data, int kxn, int
 // Pass 1: x forward, NP row pairs per workgroup.  SRC 0: rows come from pI; SRC 1: rows = Ω·div(u) (K2 fused, periodic
 // wrap in all directions); SRC 2: the same on a z-slab (z neighbour from the ghost plane); SRC 3: the 2-D divergence; SRC 4: the divergence on a grid with walls (ghost volumes of u valid).
 // ------------------------------------------------------------------------------------------------------------
-template <int LOGN, int NP, int SRC, typename C = double2>
+// MEMBERS (2-D ensembles, ins_rk_ensemble.hip; SRC 3): blockIdx.y is the member, its field lies kz·mstride elements behind `src`, and row j of its spectrum
+// goes to row j·gridDim.y + kz of `out` — the members' lines side by side in every ky row, which is the layout the fused y solve takes as one more run of lines.
+template <int LOGN, int NP, int SRC, typename C = double2, bool MEMBERS = false>
 __global__ __launch_bounds__(256) void k_xfwd(GridDev g, const double* __restrict__ src, C* __restrict__ out, int n1,
-                                              const C* __restrict__ tw_g, int kxs, int kz0, int skel) {
+                                              const C* __restrict__ tw_g, int kxs, int kz0, int skel, long long mstride) {
   using T = real_t<C>;  // (C = float2: `src` points to float data — SRC 0: the float pI; SRC 5: the float velocity field)
+  static_assert(!MEMBERS || SRC == XSRC_DIV_2D, "members: the 2-D divergence source only");
+  if (MEMBERS) src += (long long)blockIdx.y * mstride;
   constexpr int N = fft_len(LOGN);
   constexpr int KXN = N / 2 + 1;
   extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -446,16 +450,18 @@ __global__ __launch_bounds__(256) void k_xfwd(GridDev g, const double* __restric
     const C zm = buf[p * N + fft_swz<SWZ>(pos_of_freq<LOGN>((N - s) % N))];
     const C a = mkc<C>((T)0.5 * (zk.x + zm.x), (T)0.5 * (zk.y - zm.y));
     const C b = mkc<C>((T)0.5 * (zk.y + zm.y), (T)-0.5 * (zk.x - zm.x));
-    const long long o = s + (long long)kxs * (j + (long long)n1 * kz);
+    const long long rs = MEMBERS ? (long long)kxs * gridDim.y : (long long)kxs;  // one ky row down
+    const long long o = MEMBERS ? s + (long long)kxs * kz + rs * j : s + (long long)kxs * (j + (long long)n1 * kz);
     out[o] = a;
-    out[o + kxs] = b;  // row j + 1 (n1 is even)
+    out[o + rs] = b;  // row j + 1 (n1 is even)
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------
 // Pass 5: x inverse for NP row pairs: Z[k] = A[k] + i B[k], Z[N-k] = conj A[k] + i conj B[k]  ->  DIT  ->  pI rows.
 // ------------------------------------------------------------------------------------------------------------
-template <int LOGN, int NP, typename C = double2>
+// MEMBERS: the spectrum in the layout k_xfwd<.., MEMBERS> writes (blockIdx.y = member); pI member after member, as planes.
+template <int LOGN, int NP, typename C = double2, bool MEMBERS = false>
 __global__ __launch_bounds__(256) void k_xinv(const C* __restrict__ in, real_t<C>* __restrict__ pI, int n1,
                                               const C* __restrict__ tw_g, int kxs, int skel) {
   using T = real_t<C>;
@@ -478,9 +484,10 @@ __global__ __launch_bounds__(256) void k_xinv(const C* __restrict__ in, real_t<C
       const int idx = min(t + 256 * q, NP * KXN - 1);
       const int p = idx / KXN, s = idx - p * KXN;
       const int j = min(j0 + 2 * p, n1 - 2);
-      const long long o = s + (long long)kxs * (j + (long long)n1 * kz);
+      const long long rs = MEMBERS ? (long long)kxs * gridDim.y : (long long)kxs;
+      const long long o = MEMBERS ? s + (long long)kxs * kz + rs * j : s + (long long)kxs * (j + (long long)n1 * kz);
       av[q] = in[o];
-      bv[q] = in[o + kxs];
+      bv[q] = in[o + rs];
     }
 #pragma unroll
     for (int q = 0; q < NIT; ++q) {
@@ -700,19 +707,19 @@ int launch_xfwd(const GridDev& g, const double* src, int from_u, double2* out, i
   constexpr size_t lds = ((size_t)NP * N + N) * sizeof(double2);
   dim3 grid((n1 + 2 * NP - 1) / (2 * NP), n2);
   if (from_u == XSRC_FIELD)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_FIELD>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_FIELD>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL), 0LL);
   else if (from_u == XSRC_DIV_U32)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_U32>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_U32>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL), 0LL);
   else if (from_u == XSRC_DIV_WALLS)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_WALLS>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_WALLS>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL), 0LL);
   else if (from_u == XSRC_DIV_2D)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_2D>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_2D>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL), 0LL);
   else if (from_u == XSRC_DIV_SLAB)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_SLAB>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_SLAB>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL), 0LL);
   else if (from_u)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL), 0LL);
   else
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_PI>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_PI>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, kz0, (int)ins_opt(OPT_INS_X_SKEL), 0LL);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
@@ -725,9 +732,33 @@ int launch_xfwd32(const GridDev& g, const float* src, int from_u, float2* out, i
   dim3 grid((n1 + 2 * NP - 1) / (2 * NP), n2);
   const double* srcd = reinterpret_cast<const double*>(src);  // the kernel reads float data behind this pointer (C = float2)
   if (from_u)
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_U32, float2>), grid, dim3(256), lds, s, g, srcd, out, n1, tw, kxs, 0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_U32, float2>), grid, dim3(256), lds, s, g, srcd, out, n1, tw, kxs, 0, (int)ins_opt(OPT_INS_X_SKEL), 0LL);
   else
-    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_PI, float2>), grid, dim3(256), lds, s, g, srcd, out, n1, tw, kxs, 0, (int)ins_opt(OPT_INS_X_SKEL));
+    hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_PI, float2>), grid, dim3(256), lds, s, g, srcd, out, n1, tw, kxs, 0, (int)ins_opt(OPT_INS_X_SKEL), 0LL);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+
+// 2-D ensembles: nb members, each n1 rows, the 2-D divergence of member b's field (src + b·mstride) as its source
+template <int LOGN>
+int launch_xfwd_members(const GridDev& g, const double* src, double2* out, int n1, int nb, const double2* tw, int kxs, hipStream_t s, long long mstride) {
+  constexpr int N = fft_len(LOGN);
+  constexpr int NP = N >= 1024 ? 2 : (1024 / N > 16 ? 16 : 1024 / N);  // as launch_xfwd on power-of-two lengths
+  static_assert(fft_r3(LOGN) == 1, "ensembles: power-of-two sides");
+  constexpr size_t lds = ((size_t)NP * N + N) * sizeof(double2);
+  dim3 grid((n1 + 2 * NP - 1) / (2 * NP), nb);
+  hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_2D, double2, true>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, 0, (int)ins_opt(OPT_INS_X_SKEL), mstride);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+template <int LOGN>
+int launch_xinv_members(const double2* in, double* pI, int n1, int nb, const double2* tw, int kxs, hipStream_t s) {
+  constexpr int N = fft_len(LOGN);
+  constexpr int NP = N >= 1024 ? 2 : (1024 / N > 16 ? 16 : 1024 / N);
+  static_assert(fft_r3(LOGN) == 1, "ensembles: power-of-two sides");
+  constexpr size_t lds = ((size_t)NP * N + N) * sizeof(double2);
+  dim3 grid((n1 + 2 * NP - 1) / (2 * NP), nb);
+  hipLaunchKernelGGL((k_xinv<LOGN, NP, double2, true>), grid, dim3(256), lds, s, in, pI, n1, tw, kxs, (int)ins_opt(OPT_INS_X_SKEL));
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
@@ -1306,10 +1337,16 @@ __global__ __launch_bounds__(NT) void k_xyinv(const double2* __restrict__ in, do
 
 // 2-D grids of up to 64 x 64 volumes: the WHOLE spectral solve (x forward with the divergence formed inside, y forward, symbol, y inverse, x inverse) as one
 // workgroup — one launch instead of three; such a grid is 4096 volumes, and its step is nothing but launch latency.  SRC 0: rows from pI; SRC 3: Ω·div(u), 2-D, periodic wrap.
-template <int LX, int LY, int SRC, int NT>
+// MEMBERS (ensembles, ins_rk_ensemble.hip): one workgroup per member; member blockIdx.x reads its field mstride elements further on and writes its own N0·N1 block of pI.
+template <int LX, int LY, int SRC, int NT, bool MEMBERS = false>
 __global__ __launch_bounds__(NT) void k_xysolve2d(GridDev g, const double* __restrict__ src, double* __restrict__ pI, const double2* __restrict__ twx_g,
-                                                  const double2* __restrict__ twy_g, const double* __restrict__ ax, const double* __restrict__ ay, double inv_n) {
+                                                  const double2* __restrict__ twy_g, const double* __restrict__ ax, const double* __restrict__ ay, double inv_n,
+                                                  long long mstride) {
   using C = double2;
+  if (MEMBERS) {
+    src += (long long)blockIdx.x * mstride;
+    pI += (long long)blockIdx.x * ((1 << LX) * (1 << LY));
+  }
   constexpr int N0 = 1 << LX, N1 = 1 << LY, KXN = N0 / 2 + 1, NP = N1 / 2, KP = KXN;
   extern __shared__ __align__(16) unsigned char lds_raw_xy[];
   C* bufx = reinterpret_cast<C*>(lds_raw_xy);
@@ -1376,18 +1413,21 @@ __global__ __launch_bounds__(NT) void k_xysolve2d(GridDev g, const double* __res
 
 template <int LX, int LY>
 int launch_xysolve2d(const GridDev& g, const double* src, int from_u, double* pI, const double2* twx, const double2* twy, const double* ax, const double* ay,
-                     hipStream_t s) {
+                     hipStream_t s, int nb = 0, long long mstride = 0) {
   constexpr int N0 = 1 << LX, N1 = 1 << LY, KXN = N0 / 2 + 1;
   constexpr int NT = N0 * N1 >= 2048 ? 1024 : 256;
   constexpr size_t lds = ((size_t)(N1 / 2) * N0 + (size_t)N1 * KXN + N0 + N1) * sizeof(double2);
   const double inv_n = 1.0 / ((double)N0 * N1);
   int rc;
-  if (from_u) {
+  if (nb > 0) {  // an ensemble: the divergence source only
+    if ((rc = set_lds(&k_xysolve2d<LX, LY, XSRC_DIV_2D, NT, true>, lds))) return rc;
+    hipLaunchKernelGGL((k_xysolve2d<LX, LY, XSRC_DIV_2D, NT, true>), dim3(nb), dim3(NT), lds, s, g, src, pI, twx, twy, ax, ay, inv_n, mstride);
+  } else if (from_u) {
     if ((rc = set_lds(&k_xysolve2d<LX, LY, XSRC_DIV_2D, NT>, lds))) return rc;
-    hipLaunchKernelGGL((k_xysolve2d<LX, LY, XSRC_DIV_2D, NT>), dim3(1), dim3(NT), lds, s, g, src, pI, twx, twy, ax, ay, inv_n);
+    hipLaunchKernelGGL((k_xysolve2d<LX, LY, XSRC_DIV_2D, NT>), dim3(1), dim3(NT), lds, s, g, src, pI, twx, twy, ax, ay, inv_n, 0LL);
   } else {
     if ((rc = set_lds(&k_xysolve2d<LX, LY, XSRC_PI, NT>, lds))) return rc;
-    hipLaunchKernelGGL((k_xysolve2d<LX, LY, XSRC_PI, NT>), dim3(1), dim3(NT), lds, s, g, src, pI, twx, twy, ax, ay, inv_n);
+    hipLaunchKernelGGL((k_xysolve2d<LX, LY, XSRC_PI, NT>), dim3(1), dim3(NT), lds, s, g, src, pI, twx, twy, ax, ay, inv_n, 0LL);
   }
   INS_LAUNCH_CHECK();
   return INS_OK;
@@ -1536,6 +1576,50 @@ int ins_k_ownfft_xinv(const double* phat, double* pI, int n0, int n1, int n2, co
 #define CALL(LG) launch_xinv<LG>(in, pI, n1, n2, w, kxs, s)
   INS_POW2_SWITCH(n0, CALL)
 #undef CALL
+}
+
+// 2-D ensembles (ins_rk_ensemble.hip): the passes above for nb members in one launch each.  Member b's field lies b·mstride elements behind u; phat holds
+// [ky][member][kxs], pI member after member.  Power-of-two sides only (the boxes of ROUTE_OWN2D / ROUTE_OWN2D_ONE).
+#define INS_POW2_ONLY_SWITCH(n, CALL)       \
+  switch (n) {                              \
+    case 16: return CALL(4);                \
+    case 32: return CALL(5);                \
+    case 64: return CALL(6);                \
+    case 128: return CALL(7);               \
+    case 256: return CALL(8);               \
+    case 512: return CALL(9);               \
+    case 1024: return CALL(10);             \
+  }                                         \
+  ins_set_error("own FFT (ensemble): unsupported length %d", n); \
+  return INS_ERR_UNSUPPORTED;
+
+int ins_k_ownfft_xfwd_members(const ins_grid* G, const double* u, long long mstride, double* phat, int n0, int n1, int nb, const double* tw, hipStream_t s, int kxs) {
+  double2* out = reinterpret_cast<double2*>(phat);
+  const double2* w = reinterpret_cast<const double2*>(tw);
+#define CALL(LG) launch_xfwd_members<LG>(G->g, u, out, n1, nb, w, kxs, s, mstride)
+  INS_POW2_ONLY_SWITCH(n0, CALL)
+#undef CALL
+}
+
+int ins_k_ownfft_xinv_members(const double* phat, double* pI, int n0, int n1, int nb, const double* tw, hipStream_t s, int kxs) {
+  const double2* in = reinterpret_cast<const double2*>(phat);
+  const double2* w = reinterpret_cast<const double2*>(tw);
+#define CALL(LG) launch_xinv_members<LG>(in, pI, n1, nb, w, kxs, s)
+  INS_POW2_ONLY_SWITCH(n0, CALL)
+#undef CALL
+}
+
+// the whole solve of every member as one launch, one workgroup per member: pI + b·n0·n1 <- solution of L p = Ω·div(u + b·mstride)
+int ins_k_ownfft_xysolve2d_members(const ins_grid* G, const double* u, long long mstride, double* pI, int n0, int n1, int nb, const double* twx, const double* twy,
+                                   const double* ax, const double* ay, hipStream_t s) {
+  const double2 *wx = reinterpret_cast<const double2*>(twx), *wy = reinterpret_cast<const double2*>(twy);
+  auto lg = [](int n) { return n == 16 ? 4 : (n == 32 ? 5 : 6); };
+#define INS_XY(A, B) \
+  if (lg(n0) == A && lg(n1) == B) return launch_xysolve2d<A, B>(G->g, u, 1, pI, wx, wy, ax, ay, s, nb, mstride);
+  INS_XY(4, 4) INS_XY(4, 5) INS_XY(4, 6) INS_XY(5, 4) INS_XY(5, 5) INS_XY(5, 6) INS_XY(6, 4) INS_XY(6, 5) INS_XY(6, 6)
+#undef INS_XY
+  ins_set_error("ins_k_ownfft_xysolve2d_members: unsupported grid %d x %d", n0, n1);
+  return INS_ERR_UNSUPPORTED;
 }
 
 // The fused y + z passes (k_yz_*): partition count for a box, scratch size (complex numbers), and the solve itself on the spectrum after the x pass.

@@ -35,8 +35,14 @@ struct Flux2dArgs {
 // CORR (the 2-D sibling of the 3-D kernels' in-register pressure correction): `u` is the previous stage's UNCORRECTED u* (interior volumes only) and `p` the
 // unpadded pressure of its projection; every row is corrected as it is loaded, u = u* - ∇p (applypressure!, operators.jl:225-233), rows and columns
 // outside the interior are read through their periodic images.  The stage loop then needs no gradient-subtract / ghost-fill pass between its stages.
-template <bool FUSE, bool CORR = false>
-__global__ __launch_bounds__(256) void k_flux2d(Flux2dArgs a) {
+// M: element offsets of the member of an ensemble this workgroup works on (ins_rk_ensemble.hip): member b of every operand lies b member strides behind the
+// pointer in the arguments.  The single-field kernel passes NoMember, whose offsets are the constant 0 and fold away; the per-cell arithmetic is one text.
+struct NoMember {
+  static constexpr long long u = 0, p = 0, F = 0, ustart = 0, k = 0, ustar = 0, ustart_out = 0;
+};
+
+template <bool FUSE, bool CORR, typename M>
+__device__ __forceinline__ void flux2d_rows(const Flux2dArgs& a, const M m) {
   const int lane = threadIdx.x;
   const int x0 = 1 + (int)blockIdx.x * 62;                       // first output column of this wavefront
   const int j0 = 1 + ((int)blockIdx.y * 4 + (int)threadIdx.y) * a.yc;  // first output row
@@ -47,8 +53,9 @@ __global__ __launch_bounds__(256) void k_flux2d(Flux2dArgs a) {
   const int n0 = a.N0 - 2, n1 = a.N1 - 2;
   auto wrap = [](int q, int n) { return q < 0 ? q + n : (q >= n ? q - n : q); };
   const int ii = CORR ? wrap(ci - 1, n0) : 0, iip = CORR ? wrap(ii + 1, n0) : 0;  // interior column of this lane and its right neighbour
-  const double* u0 = a.u + (CORR ? ii + 1 : ci);
-  const double* v0 = a.u + a.sc + (CORR ? ii + 1 : ci);
+  const double* u0 = a.u + m.u + (CORR ? ii + 1 : ci);
+  const double* v0 = a.u + m.u + a.sc + (CORR ? ii + 1 : ci);
+  const double* pp = a.p + m.p;
   auto row = [&](int j) { return (long long)j * a.N0; };
   double pcur = 0.0;  // CORR: p(ii, row being loaded), carried from the previous load
   // one row of the two components, corrected when CORR (j: padded row index, possibly a ghost row -> its periodic image)
@@ -59,8 +66,8 @@ __global__ __launch_bounds__(256) void k_flux2d(Flux2dArgs a) {
       return;
     }
     const int jj = wrap(j - 1, n1), jjp = wrap(jj + 1, n1);
-    if (first) pcur = a.p[ii + (long long)n0 * jj];
-    const double pnext = a.p[ii + (long long)n0 * jjp], px = a.p[iip + (long long)n0 * jj];
+    if (first) pcur = pp[ii + (long long)n0 * jj];
+    const double pnext = pp[ii + (long long)n0 * jjp], px = pp[iip + (long long)n0 * jj];
     uu = u0[row(jj + 1)] - (px - pcur) * a.rx;
     vv = v0[row(jj + 1)] - (pnext - pcur) * a.ry;
     pcur = pnext;
@@ -78,11 +85,11 @@ __global__ __launch_bounds__(256) void k_flux2d(Flux2dArgs a) {
     double su = 0.0, sv = 0.0;
     const long long c = row(j) + ci;
     if (FUSE) {
-      su = a.epi.ustart ? a.epi.ustart[c] : uc;
-      sv = a.epi.ustart ? a.epi.ustart[a.sc + c] : vc;
+      su = a.epi.ustart ? a.epi.ustart[m.ustart + c] : uc;
+      sv = a.epi.ustart ? a.epi.ustart[m.ustart + a.sc + c] : vc;
       for (int q = 0; q < a.epi.n; ++q) {
-        su += a.epi.coef[q] * a.epi.k[q][c];
-        sv += a.epi.coef[q] * a.epi.k[q][a.sc + c];
+        su += a.epi.coef[q] * a.epi.k[q][m.k + c];
+        sv += a.epi.coef[q] * a.epi.k[q][m.k + a.sc + c];
       }
     }
     // right-face x fluxes of this lane's cell (left faces = the left neighbour's right faces)
@@ -96,16 +103,16 @@ __global__ __launch_bounds__(256) void k_flux2d(Flux2dArgs a) {
     const double fv = (gxv - from_prev(gxv)) * a.rx + (gyv2 - gyv) * a.ry;
     if (xout) {
       if (FUSE) {
-        a.epi.ustar[c] = su + a.epi.coef_self * fu;
-        a.epi.ustar[a.sc + c] = sv + a.epi.coef_self * fv;
+        a.epi.ustar[m.ustar + c] = su + a.epi.coef_self * fu;
+        a.epi.ustar[m.ustar + a.sc + c] = sv + a.epi.coef_self * fv;
         if (CORR && a.epi.ustart_out) {  // first stage of a chained step: the corrected input is this step's ustart
-          a.epi.ustart_out[c] = uc;
-          a.epi.ustart_out[a.sc + c] = vc;
+          a.epi.ustart_out[m.ustart_out + c] = uc;
+          a.epi.ustart_out[m.ustart_out + a.sc + c] = vc;
         }
       }
       if (!FUSE || a.epi.write_k) {
-        a.F[c] = fu;
-        a.F[a.sc + c] = fv;
+        a.F[m.F + c] = fu;
+        a.F[m.F + a.sc + c] = fv;
       }
     }
     gyu = gyu2;
@@ -117,6 +124,18 @@ __global__ __launch_bounds__(256) void k_flux2d(Flux2dArgs a) {
   }
 }
 
+template <bool FUSE, bool CORR = false>
+__global__ __launch_bounds__(256) void k_flux2d(Flux2dArgs a) {
+  flux2d_rows<FUSE, CORR>(a, NoMember{});
+}
+
+// The same rows for member blockIdx.z of an ensemble: one launch for all members, the chunking (a.yc) and the tile walk are the single field's
+template <bool CORR>
+__global__ __launch_bounds__(256) void k_flux2d_members(Flux2dArgs a, RkMemberStrides st) {
+  const long long b = blockIdx.z;
+  flux2d_rows<true, CORR>(a, RkMemberStrides{b * st.u, b * st.p, b * st.F, b * st.ustart, b * st.k, b * st.ustar, b * st.ustart_out});
+}
+
 }  // namespace
 
 bool ins_flux2d_supported(const ins_grid* G) {
@@ -125,8 +144,8 @@ bool ins_flux2d_supported(const ins_grid* G) {
   return !off && G->g.D == 2 && G->all_periodic && G->all_dof && G->uniform_exact && G->g.N[0] >= 4 && G->g.N[1] >= 4;
 }
 
-// epi == nullptr: plain momentum! into F (ghost ring of F untouched: the caller's F has a zero ring or does not read it)
-int ins_k_flux2d(const ins_grid* G, double visc, const double* u, double* F, const RkEpi* epi, hipStream_t s, const double* pI) {
+// the kernel arguments and launch shape of a field of this grid: a function of the grid and the viscosity only, so an ensemble walks the tiles of one field
+static Flux2dArgs flux2d_args(const ins_grid* G, double visc, const double* u, double* F, const RkEpi* epi, const double* pI, dim3* grid) {
   const GridDev& g = G->g;
   Flux2dArgs a;
   a.u = u;
@@ -146,7 +165,14 @@ int ins_k_flux2d(const ins_grid* G, double visc, const double* u, double* F, con
   a.vy = visc * a.ry;
   if (epi) a.epi = *epi;
   else memset(&a.epi, 0, sizeof(a.epi));
-  dim3 block(64, 4, 1), grid(cdiv(g.N[0] - 2, 62), cdiv(cdiv(n1, a.yc), 4), 1);
+  *grid = dim3(cdiv(g.N[0] - 2, 62), cdiv(cdiv(n1, a.yc), 4), 1);
+  return a;
+}
+
+// epi == nullptr: plain momentum! into F (ghost ring of F untouched: the caller's F has a zero ring or does not read it)
+int ins_k_flux2d(const ins_grid* G, double visc, const double* u, double* F, const RkEpi* epi, hipStream_t s, const double* pI) {
+  dim3 block(64, 4, 1), grid;
+  const Flux2dArgs a = flux2d_args(G, visc, u, F, epi, pI, &grid);
   if (pI && !epi) {
     ins_set_error("ins_k_flux2d: the correcting form exists for the fused stage kernel only");
     return INS_ERR_INVALID;
@@ -157,6 +183,25 @@ int ins_k_flux2d(const ins_grid* G, double visc, const double* u, double* F, con
     hipLaunchKernelGGL(k_flux2d<true>, grid, block, 0, s, a);
   else
     hipLaunchKernelGGL(k_flux2d<false>, grid, block, 0, s, a);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+
+// The fused stage kernel for nb members in one launch (blockIdx.z = member): every operand of member b lies b·(its stride in st) elements behind the pointer
+// given here.  pI != nullptr: the correcting form (u uncorrected, member b's pressure at pI + b·st.p).
+int ins_k_flux2d_members(const ins_grid* G, double visc, const double* u, double* F, const RkEpi& epi, hipStream_t s, const double* pI, int nb,
+                         const RkMemberStrides& st) {
+  dim3 block(64, 4, 1), grid;
+  const Flux2dArgs a = flux2d_args(G, visc, u, F, &epi, pI, &grid);
+  if (nb < 1 || nb > 65535) {
+    ins_set_error("ins_k_flux2d_members: %d members do not fit one launch", nb);
+    return INS_ERR_INVALID;
+  }
+  grid.z = (unsigned)nb;
+  if (pI)
+    hipLaunchKernelGGL(k_flux2d_members<true>, grid, block, 0, s, a, st);
+  else
+    hipLaunchKernelGGL(k_flux2d_members<false>, grid, block, 0, s, a, st);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }

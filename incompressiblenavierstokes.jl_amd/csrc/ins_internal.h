@@ -484,6 +484,23 @@ static inline bool ins_rk_inkernel2d(const ins_rk* rk) {
 static inline bool ins_rk_chainable(const ins_rk* rk) {
   return !ins_opt(OPT_INS_DISABLE_STEP_CHAIN) && ((ins_rk_fused3d(rk) && ins_rk_inkernel3d(rk)) || (ins_rk_fused2d(rk) && ins_rk_inkernel2d(rk)));
 }
+// Ensemble stepping (ins_rk_ensemble.hip): the launchers of the chained 2-D loop with the member as one more launch dimension.  Member b of an operand
+// lies b·(its stride) elements behind the pointer handed over; RkMemberStrides names the operands of the stage kernel (u: stencil input, p: its unpadded
+// pressure, F: k_i out, then the RkEpi operands: ustart, every k[q], ustar, ustart_out).
+struct RkMemberStrides {
+  long long u, p, F, ustart, k, ustar, ustart_out;
+};
+int ins_k_flux2d_members(const ins_grid* G, double visc, const double* u, double* F, const RkEpi& epi, hipStream_t s, const double* pI, int nb,
+                         const RkMemberStrides& st);
+int ins_k_solve_members_2d(const ins_grid* G, const ins_poisson* ps, const double* u, long long ustride, int nb, double* pI, double* phat, const double* zrows,
+                           hipStream_t s);
+int ins_k_grad_ghost_members_2d(const ins_grid* G, const ins_poisson* ps, double* u, long long ustride, int nb, const double* pI, hipStream_t s);
+int ins_k_ownfft_xfwd_members(const ins_grid* G, const double* u, long long mstride, double* phat, int n0, int n1, int nb, const double* tw, hipStream_t s, int kxs);
+int ins_k_ownfft_xinv_members(const double* phat, double* pI, int n0, int n1, int nb, const double* tw, hipStream_t s, int kxs);
+int ins_k_ownfft_xysolve2d_members(const ins_grid* G, const double* u, long long mstride, double* pI, int n0, int n1, int nb, const double* twx, const double* twy,
+                                   const double* ax, const double* ay, hipStream_t s);
+int ins_k_zsolve_members(double* data, int nz, long long nl, const double* ax, int kxn, const double* ay_rows, const double* az, const double* tw, double inv_n,
+                         hipStream_t s, int kxs);
 // rk->ub[0..1], allocated on first use: zeroed (init_from == nullptr, periodic loops) or a copy of init_from (tiled loops)   (ins_rk.hip)
 int ins_rk_ensure_ub(ins_rk* rk, size_t bytes, hipStream_t s, const double* init_from);
 // blocking reductions over an index box of a scalar field; op: 0 sum(a*b), 1 max|a|, 2 min(a)

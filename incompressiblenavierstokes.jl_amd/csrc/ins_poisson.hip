@@ -415,9 +415,15 @@ __global__ __launch_bounds__(256) void k_grad_from_pI(GridDev g, double* __restr
 // (operators.jl:225-233, p read from the unpadded pI with periodic wrap) and ALSO writes the periodic ghost
 // images of the updated velocity (boundary_conditions.jl:276-288) — up to 7 images for a corner volume — so no
 // separate apply_bc_u! pass is needed before the next stage.  KEEP_P: also store the padded, ghost-filled p.
-template <int D, bool KEEP_P>
+// MEMBERS (D == 2, ensembles: ins_rk_ensemble.hip): blockIdx.z is the member; its field lies mstride elements further on, its pressure n0·n1.
+template <int D, bool KEEP_P, bool MEMBERS = false>
 __global__ __launch_bounds__(256) void k_grad_ghost(GridDev g, double* __restrict__ u, double* __restrict__ p, const double* __restrict__ pI, int n0,
-                                                    int n1, int n2) {
+                                                    int n1, int n2, long long mstride) {
+  static_assert(!MEMBERS || (D == 2 && !KEEP_P), "members: 2-D, no padded pressure");
+  if (MEMBERS) {
+    u += (long long)blockIdx.z * mstride;
+    pI += (long long)blockIdx.z * n0 * n1;
+  }
   const int ii = blockIdx.x * 64 + threadIdx.x;
   const int jj = blockIdx.y * 4 + threadIdx.y;
   const int kk = D == 3 ? (int)blockIdx.z : 0;
@@ -1496,9 +1502,38 @@ int ins_k_project_periodic_fused_2d(const ins_grid* G, ins_poisson* ps, double* 
   if (rc) return rc;
   dim3 block(64, 4, 1), grid(cdiv(n0, 64), cdiv(n1, 4), 1);
   if (keep_p)
-    hipLaunchKernelGGL((k_grad_ghost<2, true>), grid, block, 0, s, g, u, p, ps->pI, n0, n1, 1);
+    hipLaunchKernelGGL((k_grad_ghost<2, true>), grid, block, 0, s, g, u, p, ps->pI, n0, n1, 1, 0LL);
   else
-    hipLaunchKernelGGL((k_grad_ghost<2, false>), grid, block, 0, s, g, u, p, ps->pI, n0, n1, 1);
+    hipLaunchKernelGGL((k_grad_ghost<2, false>), grid, block, 0, s, g, u, p, ps->pI, n0, n1, 1, 0LL);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+
+// The two halves of that projection for the nb members of an ensemble (ins_rk_ensemble.hip), one launch per pass whatever nb is.  The solver `ps` lends its
+// symbol and twiddle tables and decides the route; the work arrays (pI: nb·n0·n1 reals; phat: n1·nb·kxs complex, unused on ROUTE_OWN2D_ONE; zrows: nb zeros)
+// are the caller's, so the solver's own single-field state is not touched.  Member b's velocity lies b·ustride elements behind u.
+int ins_k_solve_members_2d(const ins_grid* G, const ins_poisson* ps, const double* u, long long ustride, int nb, double* pI, double* phat, const double* zrows,
+                           hipStream_t s) {
+  const int n0 = ps->np[0], n1 = ps->np[1], kxn = ps->kmax[0], kxs = ps->kxs;
+  int rc;
+  switch (ps->route) {
+    case ROUTE_OWN2D_ONE:
+      return ins_k_ownfft_xysolve2d_members(G, u, ustride, pI, n0, n1, nb, ps->tw_x, ps->tw, ps->ahat[0], ps->ahat[1], s);
+    case ROUTE_OWN2D: {
+      const double inv_n = 1.0 / ((double)n0 * n1 * 1);  // as spectral_transform (n2 == 1)
+      if ((rc = ins_k_ownfft_xfwd_members(G, u, ustride, phat, n0, n1, nb, ps->tw_x, s, kxs))) return rc;
+      if ((rc = ins_k_zsolve_members(phat, n1, (long long)kxs * nb, ps->ahat[0], kxn, zrows, ps->ahat[1], ps->tw, inv_n, s, kxs))) return rc;
+      return ins_k_ownfft_xinv_members(phat, pI, n0, n1, nb, ps->tw_x, s, kxs);
+    }
+    default: break;
+  }
+  ins_set_error("ensemble solve: the solver is not on a 2-D own-FFT route");
+  return INS_ERR_UNSUPPORTED;
+}
+int ins_k_grad_ghost_members_2d(const ins_grid* G, const ins_poisson* ps, double* u, long long ustride, int nb, const double* pI, hipStream_t s) {
+  const int n0 = ps->np[0], n1 = ps->np[1];
+  dim3 block(64, 4, 1), grid(cdiv(n0, 64), cdiv(n1, 4), (unsigned)nb);
+  hipLaunchKernelGGL((k_grad_ghost<2, false, true>), grid, block, 0, s, G->g, u, (double*)nullptr, pI, n0, n1, 1, ustride);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }

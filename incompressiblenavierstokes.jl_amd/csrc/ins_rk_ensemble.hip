@@ -1,0 +1,173 @@
+// Ensemble stepping: B independent velocity fields of one 2-D periodic setup advanced by the chained loop of ins_rk_steps_f64 (ins_rk.hip,
+// rk_step_fused_periodic_2d) with the member as one more launch dimension.  A 2-D RK44 step of a 64² .. 256² grid is a chain of dependent launches of a few
+// microseconds each, with a few thousand cells of work behind every one of them: here every launch of that chain carries all B members, so the
+// count per step is the single field's whatever B is.
+//   * the stage kernel (ins_flux2d.hip, k_flux2d_members), the solve (ins_fft.hip k_xysolve2d / k_xfwd / k_xinv with MEMBERS, ins_zsolve.hip with MEANROWS)
+//     and the last stage's gradient-subtract + ghost pass (ins_poisson.hip, k_grad_ghost with MEMBERS) are the single field's kernels instantiated with a
+//     member index: per-cell and per-line arithmetic is the same text, row chunking, tile walks and FFT stage order depend on the grid only, so member b comes
+//     out bitwise as ins_rk_steps_f64 leaves that field on its own (tests/test_gpu_ensemble.py);
+//   * the handle owns every B-fold work array; of the solver it reads the route, the symbols and the twiddle tables and writes nothing.
+#include "ins_debug.h"
+#include "ins_internal.h"
+#include "ins_rk_terms.h"
+
+struct ins_rk_ensemble {
+  const ins_grid* grid = nullptr;
+  ins_poisson* ps = nullptr;
+  int nstage = 0, nb = 0;
+  std::vector<double> A, c;
+  long long ms = 0;  // member stride of the work arrays: 2·ncell
+  double* ustart = nullptr;
+  std::vector<double*> ku;
+  double* ub[2] = {nullptr, nullptr};
+  double* pI = nullptr;    // nb · n0 · n1
+  double* phat = nullptr;  // ROUTE_OWN2D: n1 · nb · kxs complex, [ky][member][kxs]
+  double* zrows = nullptr;  // nb zeros: the per-row part of the symbol in the fused y solve
+};
+
+namespace {
+
+// First-stage ghost fill of every member (apply_bc_u! on a periodic 2-D box, boundary_conditions.jl:276-288): direction be of all members in one launch,
+// work-items along the full padded extent of the other direction (so the second direction also fills the corners), blockIdx.y = member, blockIdx.z = component.
+__global__ __launch_bounds__(256) void k_bc_u_periodic2d_members(double* __restrict__ U, long long ustride, long long sc, int N0, int N1, int be) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= (be == 0 ? N1 : N0)) return;
+  double* ua = U + (long long)blockIdx.y * ustride + (long long)blockIdx.z * sc;
+  const long long base = be == 0 ? (long long)q * N0 : q, sb = be == 0 ? 1 : N0;
+  const int last = (be == 0 ? N0 : N1) - 1;
+  ua[base] = ua[base + (last - 1) * sb];
+  ua[base + last * sb] = ua[base + sb];
+}
+
+// the arguments that need no handle: shared by the entries and the test hook
+int check_args(long long ncell, int nbatch, long long ustride, int nsteps) {
+  INS_REQUIRE(nbatch >= 1 && nbatch <= 65535, "an ensemble has 1 .. 65535 members");
+  INS_REQUIRE(nsteps >= 0, "negative number of steps");
+  INS_REQUIRE(ustride >= 2 * ncell, "member stride shorter than a vector field (2 ncell)");
+  return INS_OK;
+}
+
+// the boxes of the chained 2-D loop, asked of the single-field predicates themselves
+bool supported(const ins_grid* G, ins_poisson* ps, int nstage) {
+  if (G->g.D != 2) return false;
+  ins_rk probe;
+  probe.grid = G;
+  probe.ps = ps;
+  probe.nstage = nstage;
+  return ins_rk_fused2d(&probe) && ins_rk_inkernel2d(&probe);
+}
+
+int refuse(const char* why) {
+  ins_set_error("ins_rk_ensemble: %s; the ensemble loop runs the boxes of the chained 2-D loop only (all-periodic, exactly uniform, power-of-two sides 16 .. 1024, "
+                "spectral solver on its own passes, more than one stage): advance each member with ins_rk_steps_f64 (timesteps_ per member)", why);
+  return INS_ERR_UNSUPPORTED;
+}
+
+int fill_ghosts(const ins_rk_ensemble* e, double* U, long long ustride, hipStream_t s) {
+  const GridDev& g = e->grid->g;
+  for (int be = 0; be < 2; ++be) {
+    const dim3 grid(cdiv(g.N[be == 0 ? 1 : 0], 256), (unsigned)e->nb, 2);
+    hipLaunchKernelGGL(k_bc_u_periodic2d_members, grid, dim3(256), 0, s, U, ustride, g.sc, g.N[0], g.N[1], be);
+    INS_LAUNCH_CHECK();
+  }
+  return INS_OK;
+}
+
+// One step of all members: rk_step_fused_periodic_2d (ins_rk.hip) launch for launch.  chain as there: bit 1 = U holds the previous step's uncorrected
+// result and pI its pressure; bit 2 = leave this step's result uncorrected.
+int step(ins_rk_ensemble* e, double visc, double* U, long long ustride, double dt, hipStream_t s, int chain) {
+  const ins_grid* G = e->grid;
+  const int ns = e->nstage;
+  const long long np = (long long)e->ps->np[0] * e->ps->np[1];
+  const bool raw_in = chain & 1, raw_out = chain & 2;
+  int rc;
+  if (!raw_in && (rc = fill_ghosts(e, U, ustride, s))) return rc;
+  const double* in = U;
+  long long in_stride = ustride;
+  for (int i = 0; i < ns; ++i) {
+    const bool last = i == ns - 1;
+    double* out = last ? U : e->ub[i & 1];
+    const long long out_stride = last ? ustride : e->ms;
+    RkEpi epi = ins_rk_stage_terms(e->A.data(), ns, i, dt, e->ku.data(), (const double*)nullptr, RK_K_BASIS, false, RK_FORCE_INDEX_ORDER);
+    epi.ustart = (i == 0) ? nullptr : (raw_in ? e->ustart : U);
+    epi.ustar = out;
+    if (i == 0 && raw_in) epi.ustart_out = e->ustart;
+    const bool corr = i > 0 || raw_in;
+    const RkMemberStrides st = {in_stride, corr ? np : 0, e->ms, raw_in ? e->ms : ustride, e->ms, out_stride, e->ms};
+    if ((rc = ins_k_flux2d_members(G, visc, in, e->ku[i], epi, s, corr ? e->pI : nullptr, e->nb, st))) return rc;
+    if ((rc = ins_k_solve_members_2d(G, e->ps, out, out_stride, e->nb, e->pI, e->phat, e->zrows, s))) return rc;
+    if (last && !raw_out && (rc = ins_k_grad_ghost_members_2d(G, e->ps, out, out_stride, e->nb, e->pI, s))) return rc;
+    in = out;
+    in_stride = out_stride;
+  }
+  return INS_OK;
+}
+
+}  // namespace
+
+extern "C" int ins_dbg_rk_ensemble_args(int64_t ncell, int32_t nbatch, int64_t ustride, int32_t nsteps) { return check_args(ncell, nbatch, ustride, nsteps); }
+
+extern "C" int ins_rk_ensemble_create(const ins_grid_t* G, ins_poisson_t* ps, int nstage, const double* A, const double* c, int nbatch, ins_rk_ensemble_t** out) {
+  INS_REQUIRE(G && ps && A && c && out, "null argument");
+  INS_REQUIRE(ps->grid == G, "psolver was created for a different grid");
+  int rc = check_args(G->ncell, nbatch, 2 * G->ncell, 0);
+  if (rc) return rc;
+  INS_REQUIRE(nstage >= 1 && nstage <= INS_MAX_STAGES, "unsupported number of stages");
+  for (int i = 0; i < nstage; ++i)
+    for (int j = i + 1; j < nstage; ++j) INS_REQUIRE(A[i * nstage + j] == 0.0, "shifted tableau must be lower triangular (explicit method)");
+  if (G->g.D != 2) return refuse("a 3-D grid");
+  if (nstage < 2) return refuse("a one-stage method");
+  if (!supported(G, ps, nstage)) return refuse("this grid / solver does not run the chained 2-D loop");
+  ins_rk_ensemble* e = new ins_rk_ensemble();
+  e->grid = G;
+  e->ps = ps;
+  e->nstage = nstage;
+  e->nb = nbatch;
+  e->A.assign(A, A + nstage * nstage);
+  e->c.assign(c, c + nstage);
+  e->ms = 2 * G->ncell;
+  const size_t vbytes = (size_t)e->ms * nbatch * sizeof(double);
+  const size_t pbytes = (size_t)ps->np[0] * ps->np[1] * nbatch * sizeof(double);
+  const size_t hbytes = (size_t)ps->kxs * ps->np[1] * nbatch * 2 * sizeof(double);
+  // every array zeroed once: ghost rings and padding columns that no kernel writes are read by none either, but hold defined values
+  auto alloc0 = [](double** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess; };
+  bool ok = alloc0(&e->ustart, vbytes) && alloc0(&e->ub[0], vbytes) && alloc0(&e->ub[1], vbytes) && alloc0(&e->pI, pbytes) &&
+            alloc0(&e->zrows, (size_t)nbatch * sizeof(double));
+  if (ok && ps->route == ROUTE_OWN2D) ok = alloc0(&e->phat, hbytes);
+  e->ku.assign(nstage, nullptr);
+  for (int i = 0; ok && i < nstage; ++i) ok = alloc0(&e->ku[i], vbytes);
+  if (!ok) {
+    (void)hipGetLastError();
+    ins_set_error("ins_rk_ensemble_create: device allocation of %d x %d vector fields failed", nstage + 3, nbatch);
+    ins_rk_ensemble_destroy(e);
+    return INS_ERR_HIP;
+  }
+  *out = e;
+  return INS_OK;
+}
+
+extern "C" int ins_rk_ensemble_destroy(ins_rk_ensemble_t* e) {
+  if (!e) return INS_OK;
+  for (double* p : {e->ustart, e->ub[0], e->ub[1], e->pI, e->phat, e->zrows})
+    if (p) (void)hipFree(p);
+  for (double* k : e->ku)
+    if (k) (void)hipFree(k);
+  delete e;
+  return INS_OK;
+}
+
+// nsteps steps of every member: the loop of ins_rk_steps_f64 — chained (the final gradient-subtract / ghost pass of every step but the last goes into the next
+// step's first stage kernel) where that entry chains a single field, whole steps where it does not (one step, INS_DISABLE_STEP_CHAIN).
+extern "C" int ins_rk_ensemble_steps_f64(ins_rk_ensemble_t* e, double visc, double* U, int64_t ustride, double t, double dt, int nsteps, void* stream) {
+  (void)t;  // no boundary data, no force: nothing depends on time
+  INS_REQUIRE(e && U, "null argument");
+  int rc = check_args(e->grid->ncell, e->nb, ustride, nsteps);
+  if (rc) return rc;
+  // the switches that shape the single-field loop are read per call there; a handle whose box they have since turned away is refused, not run another way
+  if (!supported(e->grid, e->ps, e->nstage)) return refuse("an option has switched the chained 2-D loop off since the handle was created");
+  hipStream_t s = as_stream(stream);
+  const bool chain = !ins_opt(OPT_INS_DISABLE_STEP_CHAIN) && nsteps >= 2;
+  for (int n = 0; n < nsteps; ++n)
+    if ((rc = step(e, visc, U, ustride, dt, s, chain ? ((n > 0 ? 1 : 0) | (n < nsteps - 1 ? 2 : 0)) : 0))) return rc;
+  return INS_OK;
+}

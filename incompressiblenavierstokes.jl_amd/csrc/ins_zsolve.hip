@@ -55,7 +55,8 @@ __device__ __forceinline__ int freq_of_pos(int p) {
 // NT threads per workgroup.  The workgroup is PERSISTENT: it walks tiles blockIdx.x, blockIdx.x + gridDim.x, ... and loads the next tile
 // into registers while the transform of the current one runs in LDS, so HBM stays busy during the LDS stages (the one-tile-per-workgroup
 // form left HBM idle while a CU's workgroups computed: 0.83 ms at 512^3 against 0.64 ms for its loads and stores alone).
-template <int LOGN, int TK, int NT>
+// MEANROWS (2-D ensembles, ins_rk_ensemble.hip: every row of kxs lines is one member's kx run): the mean mode that zero_mean drops is line 0 of EVERY row.
+template <int LOGN, int TK, int NT, bool MEANROWS = false>
 __global__ __launch_bounds__(NT) void k_zsolve(double2* __restrict__ data, long long nl, const double* __restrict__ ax, int kxn,
                                                const double* __restrict__ ay, const double* __restrict__ az,
                                                const double2* __restrict__ tw_g, double inv_n, int zero_mean, int kxs, int skel, int ntiles) {
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(NT) void k_zsolve(double2* __restrict__ data, long 
   // 1/((âx + ây) + âz): the (x,y) part of the symbol is fixed per line
   double axy = 1.0;
   if (live) axy = ax[lkx] + ay[(int)(line / kxs)];
-  const bool mean_line = zero_mean && line == 0;
+  const bool mean_line = zero_mean && (MEANROWS ? lkx == 0 : line == 0);
   __syncthreads();
   if (tile + (int)gridDim.x < ntiles) prefetch(tile + gridDim.x);  // in flight during the LDS stages below
 
@@ -370,7 +371,7 @@ __device__ __forceinline__ void twiddle(C (&x)[R], C w1) {
   }
 }
 
-template <int LOGN, int TK, int NT, typename C = double2>
+template <int LOGN, int TK, int NT, typename C = double2, bool MEANROWS = false>
 __global__ __launch_bounds__(NT) void k_zsolve3(C* __restrict__ data, long long nl, const double* __restrict__ ax, int kxn,
                                                 const double* __restrict__ ay, const double* __restrict__ az,
                                                 const C* __restrict__ tw_g, double inv_n, int zero_mean, int kxs, int skel, int ntiles) {
@@ -415,7 +416,7 @@ __global__ __launch_bounds__(NT) void k_zsolve3(C* __restrict__ data, long long 
     const bool live = is_live(line);
     double axy = 1.0;
     if (live) axy = ax[lkx] + ay[(int)(line / kxs)];
-    const bool mean_line = zero_mean && line == 0;
+    const bool mean_line = zero_mean && (MEANROWS ? lkx == 0 : line == 0);
 
     // ---- forward pass 1: (global ->) registers -> LDS
 #pragma unroll
@@ -675,7 +676,7 @@ int launch_line3(C* data, int kxn, int kxs, int nplanes, const C* tw, bool inver
   return INS_OK;
 }
 
-template <int LOGN, int TK, int NT, typename C = double2>
+template <int LOGN, int TK, int NT, typename C = double2, bool MEANROWS = false>
 int launch_zsolve3(C* data, long long nl, const double* ax, int kxn, const double* ay, const double* az, const C* tw,
                    double inv_n, bool zero_mean, hipStream_t s, int kxs) {
   const int ntiles = (int)((nl + TK - 1) / TK);
@@ -683,7 +684,7 @@ int launch_zsolve3(C* data, long long nl, const double* ax, int kxn, const doubl
   constexpr size_t lds = ((size_t)N * TK + N) * sizeof(C);
   static bool attr_set = false;
   if (lds > 64 * 1024 && !attr_set) {
-    INS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_zsolve3<LOGN, TK, NT, C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    INS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_zsolve3<LOGN, TK, NT, C, MEANROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
   // 16-line tiles (136 KB of LDS: one workgroup per CU) run persistent, one workgroup per CU walking its share of the tiles with the next
@@ -692,20 +693,20 @@ int launch_zsolve3(C* data, long long nl, const double* ax, int kxn, const doubl
   const int fit = std::max(1, std::min((int)(160 * 1024 / lds), 2048 / NT));
   const long long per_cu = ins_opt(OPT_INS_ZSOLVE_WGS) > 0 ? ins_opt(OPT_INS_ZSOLVE_WGS) : (TK >= 16 ? fit : (1LL << 20));
   const unsigned nb = (unsigned)std::min<long long>(ntiles, 256LL * per_cu);
-  hipLaunchKernelGGL((k_zsolve3<LOGN, TK, NT, C>), dim3(nb), dim3(NT), lds, s, data, nl, ax, kxn, ay, az, tw, inv_n, zero_mean ? 1 : 0, kxs,
+  hipLaunchKernelGGL((k_zsolve3<LOGN, TK, NT, C, MEANROWS>), dim3(nb), dim3(NT), lds, s, data, nl, ax, kxn, ay, az, tw, inv_n, zero_mean ? 1 : 0, kxs,
                      ins_opt(OPT_INS_ZSOLVE_SKEL) ? 1 : 0, ntiles);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
 
-template <int LOGN, int TK, int NT = 256>
+template <int LOGN, int TK, int NT = 256, bool MEANROWS = false>
 int launch_zsolve(double2* data, long long nl, const double* ax, int kxn, const double* ay, const double* az, const double2* tw,
                   double inv_n, bool zero_mean, hipStream_t s, int kxs) {
   const int ntiles = (int)((nl + TK - 1) / TK);
   constexpr size_t lds = ((size_t)(1 << LOGN) * TK + (1 << LOGN)) * sizeof(double2);
   static bool attr_set = false;
   if (lds > 64 * 1024 && !attr_set) {
-    INS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_zsolve<LOGN, TK, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    INS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_zsolve<LOGN, TK, NT, MEANROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
   // persistent workgroups: as many as are resident at once (LDS per workgroup decides), each walks its share of the tiles.
@@ -713,7 +714,7 @@ int launch_zsolve(double2* data, long long nl, const double* ax, int kxn, const 
   const int fit = std::max(1, std::min((int)(160 * 1024 / lds), 2048 / NT));
   const long long per_cu = ins_opt(OPT_INS_ZSOLVE_WGS) > 0 ? ins_opt(OPT_INS_ZSOLVE_WGS) : fit;
   const unsigned nb = (unsigned)std::min<long long>(ntiles, 256LL * per_cu);
-  hipLaunchKernelGGL((k_zsolve<LOGN, TK, NT>), dim3(nb), dim3(NT), lds, s, data, nl, ax, kxn, ay, az, tw, inv_n, zero_mean ? 1 : 0, kxs,
+  hipLaunchKernelGGL((k_zsolve<LOGN, TK, NT, MEANROWS>), dim3(nb), dim3(NT), lds, s, data, nl, ax, kxn, ay, az, tw, inv_n, zero_mean ? 1 : 0, kxs,
                      ins_opt(OPT_INS_ZSOLVE_SKEL) ? 1 : 0, ntiles);
   INS_LAUNCH_CHECK();
   return INS_OK;
@@ -854,6 +855,31 @@ int ins_k_zsolve_f32(float* data, int nz, long long nl, const double* ax, int kx
     }
   }
   ins_set_error("ins_k_zsolve_f32: unsupported nz = %d", nz);
+  return INS_ERR_UNSUPPORTED;
+}
+
+// The fused solve along y of a 2-D ensemble: data[ky][member][kxs], nl = nb·kxs lines, ay_rows = nb zeros (the per-row part of the symbol), the mean mode
+// of every member dropped.  The kernel per length is the one ins_k_zsolve picks for a single field (radix-4 or three-pass: the stage order decides the bits;
+// the tile shape does not), so a member's lines come out bitwise as on its own.
+int ins_k_zsolve_members(double* data, int nz, long long nl, const double* ax, int kxn, const double* ay_rows, const double* az, const double* tw, double inv_n,
+                         hipStream_t s, int kxs) {
+  double2* d = reinterpret_cast<double2*>(data);
+  const double2* w = reinterpret_cast<const double2*>(tw);
+  const bool r4 = ins_opt(OPT_INS_ZSOLVE_RADIX4) != 0;
+  switch (nz) {
+    case 16: return launch_zsolve<4, 16, 256, true>(d, nl, ax, kxn, ay_rows, az, w, inv_n, true, s, kxs);
+    case 32: return launch_zsolve<5, 16, 256, true>(d, nl, ax, kxn, ay_rows, az, w, inv_n, true, s, kxs);
+    case 64: return launch_zsolve<6, 16, 256, true>(d, nl, ax, kxn, ay_rows, az, w, inv_n, true, s, kxs);
+    case 128: return launch_zsolve<7, 16, 256, true>(d, nl, ax, kxn, ay_rows, az, w, inv_n, true, s, kxs);
+    case 256:
+      if (r4) return launch_zsolve<8, 8, 256, true>(d, nl, ax, kxn, ay_rows, az, w, inv_n, true, s, kxs);
+      return launch_zsolve3<8, 8, 256, double2, true>(d, nl, ax, kxn, ay_rows, az, w, inv_n, true, s, kxs);
+    case 512:
+      if (r4) return launch_zsolve<9, 8, 256, true>(d, nl, ax, kxn, ay_rows, az, w, inv_n, true, s, kxs);
+      return launch_zsolve3<9, 16, 512, double2, true>(d, nl, ax, kxn, ay_rows, az, w, inv_n, true, s, kxs);
+    case 1024: return launch_zsolve<10, 4, 256, true>(d, nl, ax, kxn, ay_rows, az, w, inv_n, true, s, kxs);
+  }
+  ins_set_error("ins_k_zsolve_members: unsupported length %d", nz);
   return INS_ERR_UNSUPPORTED;
 }
 

@@ -194,6 +194,17 @@ def vectorfield(setup):
     return _alloc(setup, setup.grid.N + (setup.grid.dimension,))
 
 
+def vectorfields(setup, B):
+    """`B` empty vector fields of one setup in one allocation, shape (B,) + N + (D,): `U[b]` has the layout of `vectorfield(setup)`, so every operator,
+    observer and filter takes it unchanged, and `timesteps_ensemble_` advances all of them in one native loop."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("an ensemble has at least one member")
+    shape = setup.grid.N + (setup.grid.dimension,)
+    t = torch.zeros((B,) + tuple(reversed(shape)), dtype=torch.float64, device=setup.device)
+    return t.permute(0, *reversed(range(1, len(shape) + 1)))
+
+
 def from_numpy(setup, a):
     """Upload a host array of field shape into a fresh device field (keeps the reference layout)."""
     a = np.asarray(a, dtype=np.float64)

@@ -378,6 +378,117 @@ class ERKCache:
                 pass
 
 
+_PER_MEMBER = "advance each member with timesteps_ (one ERKCache, `timesteps_(method, stepper, Δt, nsteps, cache=cache)` per member)"
+
+
+def _ensemble_refusal(method, setup, psolver):
+    """Why the ensemble loop does not take this problem (None: it does).  Host-side facts only: nothing here touches the device."""
+    from .boundary_conditions import PeriodicBC
+
+    g = setup.grid
+    if g.dimension != 2:
+        return "a 3-D setup"
+    if not all(isinstance(bc, PeriodicBC) for side in setup.boundary_conditions for bc in side):
+        return "a side that is not periodic"
+    if setup.bodyforce is not None:
+        return "a body force"
+    if setup.closure_model is not None:
+        return "a closure model"
+    if setup.temperature is not None:
+        return "a temperature equation"
+    n = tuple(ni - 2 for ni in g.N)
+    if any(ni < 16 or ni > 1024 or ni & (ni - 1) for ni in n):
+        return f"a {n[0]} x {n[1]} grid (sides must be powers of two in 16 .. 1024: others solve through rocFFT)"
+    if len(method.b) < 2:
+        return "a one-stage method"
+    if type(psolver).__name__ != "psolver_spectral":
+        return f"the solver {type(psolver).__name__} (the ensemble loop runs on psolver_spectral)"
+    return None
+
+
+class EnsembleCache:
+    """Work arrays of `timesteps_ensemble_` for `B` members of one 2-D periodic setup (an `ins_rk_ensemble_t` handle): B-fold stage forces, stage
+    buffers, start field, pressure and spectrum.  The psolver lends its symbol and twiddle tables; its own single-field arrays are not touched, so it and
+    any `ERKCache` of the setup keep working beside the ensemble.  Refused (NotImplementedError) for everything outside the chained 2-D loop of
+    `timesteps_`: 3-D, a non-periodic side, a side that is no power of two in 16 .. 1024, a body force, a closure, a temperature equation, a one-stage method."""
+
+    def __init__(self, method, setup, psolver, B):
+        if isinstance(method, LMWray3):  # the scheme as the explicit RK method it is, as timesteps_ runs it
+            method = _lmwray3_as_erk(method)
+        B = int(B)
+        if B < 1:
+            raise ValueError("an ensemble has at least one member")
+        why = _ensemble_refusal(method, setup, psolver)
+        if why is not None:
+            raise NotImplementedError(f"EnsembleCache: {why} is outside the ensemble loop; {_PER_MEMBER}")
+        self.method, self.setup, self.psolver, self.B = method, setup, psolver, B
+        A = np.ascontiguousarray(method.A, dtype=np.float64)
+        c = np.ascontiguousarray(method.c, dtype=np.float64)
+        self._handle = C.c_void_p()
+        lib = _lib.load()
+        rc = lib.ins_rk_ensemble_create(setup.handle, psolver.handle, len(method.b), A.ctypes.data_as(_lib.c_double_p), c.ctypes.data_as(_lib.c_double_p), B,
+                                        C.byref(self._handle))
+        if rc == -4:  # INS_ERR_UNSUPPORTED: the library's own predicate (a run-time switch, a grid that is not exactly uniform)
+            raise NotImplementedError(f"EnsembleCache: {lib.ins_last_error().decode()}; {_PER_MEMBER}")
+        _lib.check(rc)
+
+    @property
+    def handle(self):
+        return self._handle
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            try:
+                _lib.load().ins_rk_ensemble_destroy(h)
+            except Exception:
+                pass
+
+
+def _ensemble_ustride(cache, U):
+    """Member stride of `U` in elements after the type, shape, stride and device checks of `timesteps_ensemble_` (host-side facts of `U` and `cache` only)."""
+    import torch
+
+    from .setup import _fortran_strides
+
+    if not isinstance(cache, EnsembleCache):
+        raise TypeError("timesteps_ensemble_ needs an EnsembleCache")
+    if not isinstance(U, torch.Tensor) or U.dtype != torch.float64:
+        raise TypeError("ensemble fields must be float64 torch tensors (vectorfields)")
+    g = cache.setup.grid
+    shape = g.N + (g.dimension,)
+    if U.dim() != len(shape) + 1 or tuple(U.shape[1:]) != shape:
+        raise ValueError(f"ensemble field must have shape (B,) + {shape} (use vectorfields), got {tuple(U.shape)}")
+    if U.shape[0] != cache.B:
+        raise ValueError(f"ensemble field has {U.shape[0]} members, the cache was created for B = {cache.B}")
+    if tuple(U.stride()[1:]) != _fortran_strides(shape):
+        raise ValueError("every member U[b] must have the column-major strides of vectorfield(setup) (use vectorfields)")
+    ncomp = int(np.prod(shape))
+    if U.shape[0] > 1 and U.stride(0) < ncomp:
+        raise ValueError(f"members overlap: stride {U.stride(0)} between members is shorter than a vector field ({ncomp})")
+    if U.device != cache.setup.device:
+        raise ValueError(f"ensemble field lives on {U.device}, setup on {cache.setup.device}")
+    return int(U.stride(0)) if U.shape[0] > 1 else ncomp
+
+
+def timesteps_ensemble_(cache, U, t, Δt, nsteps):
+    """`nsteps` explicit Runge-Kutta steps of size Δt of every member `U[b]`, in place, as ONE native loop (`ins_rk_ensemble_steps_f64`): the kernels and
+    the number of launches of `timesteps_` on a single field, each launch working on all B members.  Re, Δt and the tableau are the cache's and shared; no
+    member sees another, and `U[b]` comes out bitwise as `timesteps_` leaves that field on its own.  Ghost volumes of every member are valid on return.
+    Returns U."""
+    ustride = _ensemble_ustride(cache, U)
+    nsteps = int(nsteps)
+    if nsteps < 0:
+        raise ValueError("nsteps must be non-negative")
+    setup = cache.setup
+    lib = _lib.load()
+    rc = lib.ins_rk_ensemble_steps_f64(cache.handle, 1.0 / setup.Re, C.c_void_p(U.data_ptr()), ustride, float(t), float(Δt), nsteps, setup.stream)
+    if rc == -4:
+        raise NotImplementedError(f"timesteps_ensemble_: {lib.ins_last_error().decode()}; {_PER_MEMBER}")
+    _lib.check(rc)
+    return U
+
+
 def ode_method_cache(method, setup, psolver=None):
     """time_stepper_caches.jl:34-49.  (`psolver` is needed up front because the native cache owns the
     projection scratch; `solve_unsteady` passes it.)"""
