@@ -251,6 +251,12 @@ SIGNATURES = {
     "ins_comm_alltoall_f64": (C.c_int, [vp, vp, vp, C.c_int64, vp]),
 }
 
+# test hooks of csrc/ins_debug.h (not in include/ins_hip.h), bound where the library has them: INS_HIP_LIB may name a build from before a hook existed
+DEBUG_SIGNATURES = {
+    "ins_dbg_f32_choose": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ins_dbg_rk32_route": (C.c_int, [vp, C.POINTER(C.c_int32)]),
+}
+
 _lib = None
 
 
@@ -273,6 +279,9 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in DEBUG_SIGNATURES.items():
+        if hasattr(lib, name):
+            getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
     _lib = lib
     return lib
 

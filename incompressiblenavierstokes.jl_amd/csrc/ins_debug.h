@@ -28,6 +28,12 @@ int ins_dbg_spectral_choose(int D, int n0, int n1, int n2, int32_t* ky_order, in
 void ins_dbg_permute_ky(int ky_order, int n, const double* ay, double* out);
 int ins_dbg_line3_pos_of_freq(int n, int k);
 
+/* ins_f32.hip.  Test hooks, not part of the public ABI: the Float32 solver route (F32Route of csrc/ins_f32_internal.h) of an all-periodic uniform box of
+ * n0 x n1 (x n2) volumes under the current option values, without touching the device; a live Float32 integrator's solver route, and in *flags its step
+ * route as a bit set (1 general, 2 wide, 4 in-register correction, 8 float2 spectra, 16 stage-velocity basis, 32 chainable) */
+int ins_dbg_f32_choose(int D, int n0, int n1, int n2);
+int ins_dbg_rk32_route(const ins_rk32_t* rk, int32_t* flags);
+
 /* ins_zsolve.hip.  Experiment hook, not part of the public ABI: time `reps` launches of the fused z pass on `data` = nbox independent [nz][nl] blocks
  * (nl = nky * kxs lines, kxn live columns), average ms per sweep over all boxes */
 int ins_dbg_zsolve(double* data, int nz, long long nl, int kxn, int kxs, int nbox, int reps, float* ms);

@@ -15,11 +15,15 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "ins_debug.h"
 #include "ins_f32_internal.h"
 #include "ins_rk_terms.h"
 
 struct ins_poisson32 {
   const ins_grid* grid = nullptr;
+  // which launch sequence this solver runs: what its creation actually set up (ins_f32_choose; ins_poisson_wrap_f32).  The pointers below are resources
+  // of a route, never tests of it.
+  F32Route route = F32_HIPFFT;
   hipfftHandle fwd = 0, inv = 0;
   bool plans = false;
   float* pI = nullptr;
@@ -32,7 +36,6 @@ struct ins_poisson32 {
   ins_poisson* ps64 = nullptr;
   // sides the three-pass z kernel takes (192, 256, 384, 512 planes): the same five passes on FLOAT2 spectra — half the bytes of every pass; ps64
   // then only supplies the symbol vectors (INS_F32_FP64_SPECTRA=1 keeps the fp64 passes)
-  bool own32 = false;
   float* phat32 = nullptr;
   float* tw32[3] = {nullptr, nullptr, nullptr};
   int kxs32 = 0;
@@ -274,7 +277,56 @@ dim3 grid_over(const Box32& b, bool padded) {
   return dim3(cdiv(e0, 64), cdiv(e1, 4), e2);
 }
 
+// kern<2> on a 2-D box, kern<3> on a 3-D one, 64 x 4 work-items a block
+#define K32_LAUNCH_BY_DIM(D, kern, grid, s, ...)                                         \
+  do {                                                                                   \
+    if ((D) == 2) hipLaunchKernelGGL(kern<2>, grid, dim3(64, 4), 0, s, __VA_ARGS__);     \
+    else hipLaunchKernelGGL(kern<3>, grid, dim3(64, 4), 0, s, __VA_ARGS__);              \
+  } while (0)
+
+void pad32(const Box32& b, const float* pI, float* p, hipStream_t s) { K32_LAUNCH_BY_DIM(b.D, k32_pad, grid_over(b, true), s, b, pI, p); }
+void pad32(const Box32& b, const double* pI, float* p, hipStream_t s) {  // the fp64 passes exist in 3-D only
+  hipLaunchKernelGGL((k32_pad<3, double>), grid_over(b, true), dim3(64, 4), 0, s, b, pI, p);
+}
+
+// The tail of project!: pI (unpadded, float or double) -> p with ghosts, u -= ∇p with ghosts, as one kernel (3-D) or pad -> gradient-subtract -> periodic ghosts
+template <typename S>
+int project_tail(const ins_grid* G, const Box32& b, float* u, float* p, const S* pI, bool one_kernel, hipStream_t s) {
+  if (one_kernel) {
+    hipLaunchKernelGGL((k32_grad_ghost3<S>), grid_over(b, false), dim3(64, 4), 0, s, b, u, p, pI);
+    INS_LAUNCH_CHECK();
+    return INS_OK;
+  }
+  pad32(b, pI, p, s);
+  K32_LAUNCH_BY_DIM(b.D, k32_applypressure, grid_over(b, false), s, b, u, p);
+  INS_LAUNCH_CHECK();
+  return bc_periodic(G, u, b.D, s);
+}
+
+// maximum(abs, dev[0..n)) on the host (blocking)
+int host_max_abs(const float* dev, long long n, hipStream_t s, float* out) {
+  std::vector<float> h(n);
+  INS_HIP_TRY(hipMemcpyAsync(h.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost, s));
+  INS_HIP_TRY(hipStreamSynchronize(s));
+  *out = 0.f;
+  for (float v : h) *out = std::fmax(*out, std::fabs(v));
+  return INS_OK;
+}
+
 }  // namespace
+
+// out = base + Σ coef[q] k[q], terms in index order; serves this file's stage loops and the recomputation of the reverse loop (ins_rk_adjoint_loop.h)
+int ins_k32_combine(long long n, const float* base, float* out, int nterms, const float* coef, const float* const* k, hipStream_t s) {
+  Comb32 cb;
+  cb.n = nterms;
+  for (int q = 0; q < nterms; ++q) {
+    cb.coef[q] = coef[q];
+    cb.k[q] = k[q];
+  }
+  hipLaunchKernelGGL(k32_combine, dim3((unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 8192))), dim3(256), 0, s, n, base, out, cb);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
 
 extern "C" int ins_apply_bc_u_f32(const ins_grid_t* G, float* u, void* stream) {
   INS_REQUIRE(G && u, "null argument");
@@ -301,10 +353,7 @@ extern "C" int ins_momentum_f32(const ins_grid_t* G, float visc, const float* u,
   if (!periodic_uniform(G)) return ins_k32g_momentum(G, visc, u, F, s);
   if (ins_flux64_supported(G)) return ins_k_flux64_f32(G, (double)visc, u, F, nullptr, nullptr, 0, s);
   const Box32 b = box_of(G);
-  if (b.D == 2)
-    hipLaunchKernelGGL(k32_momentum<2>, grid_over(b, false), dim3(64, 4), 0, s, b, visc, u, F);
-  else
-    hipLaunchKernelGGL(k32_momentum<3>, grid_over(b, false), dim3(64, 4), 0, s, b, visc, u, F);
+  K32_LAUNCH_BY_DIM(b.D, k32_momentum, grid_over(b, false), s, b, visc, u, F);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
@@ -343,6 +392,7 @@ extern "C" int ins_poisson_wrap_f32(const ins_grid_t* G, ins_poisson_t* ps64, in
     }
   ins_poisson32* ps = new ins_poisson32();
   ps->grid = G;
+  ps->route = F32_WRAP;
   ps->wrap64 = ps64;
   for (int a = 0; a < g.D; ++a) ps->np[a] = g.ip_hi[a] - g.ip_lo[a];
   const bool ok = hipMalloc(&ps->p64, G->ncell * sizeof(double)) == hipSuccess && hipMemset(ps->p64, 0, G->ncell * sizeof(double)) == hipSuccess &&
@@ -354,6 +404,15 @@ extern "C" int ins_poisson_wrap_f32(const ins_grid_t* G, ins_poisson_t* ps64, in
   }
   *out = ps;
   return INS_OK;
+}
+
+// Which launch sequence an all-periodic uniform box of n0 x n1 (x n2) volumes gets: a function of the box and of the option values at the time of the call, with
+// no HIP call.  ins_poisson_spectral_create_f32 calls it once, so INS_F32_HIPFFT_PROJECT, INS_F32_FP64_SPECTRA and the switches behind the two predicates
+// (ins_spectral_choose's, INS_DISABLE_ZSOLVE) are frozen in a solver that exists; INS_F32_SPLIT_GRADIENT alone is read per call (ins_project_f32).
+F32Route ins_f32_choose(int D, int n0, int n1, int n2) {
+  if (D != 3 || ins_opt(OPT_INS_F32_HIPFFT_PROJECT)) return F32_HIPFFT;
+  if (ins_dbg_spectral_choose(D, n0, n1, n2, nullptr, nullptr) < ROUTE_OWN2D) return F32_HIPFFT;  // the fp64 solver of this box has no own passes
+  return ins_zsolve_f32_supported(n2) && !ins_opt(OPT_INS_F32_FP64_SPECTRA) ? F32_FLOAT2_SPECTRA : F32_FP64_SPECTRA;
 }
 
 // psolver_spectral(setup) with T = Float32                                               pressure.jl:289-351
@@ -406,21 +465,15 @@ extern "C" int ins_poisson_spectral_create_f32(const ins_grid_t* G, ins_poisson3
     ins_poisson_destroy_f32(ps);
     return INS_ERR_FFT;
   }
-  if (g.D == 3 && !ins_opt(OPT_INS_F32_HIPFFT_PROJECT)) {  // the fused fp64 passes for project! where they exist (power-of-two sides)
-    ins_poisson* p64 = nullptr;
-    if (ins_poisson_spectral_create(G, &p64) == INS_OK) {
-      if (ins_k_spectral_own3d(p64))
-        ps->ps64 = p64;
-      else
-        (void)ins_poisson_destroy(p64);
-    }
-    if (ps->ps64 && ins_k_spectral_own3d_f32(ps->ps64) && !ins_opt(OPT_INS_F32_FP64_SPECTRA)) {
-      ps->kxs32 = (ps->kmax[0] + 15) & ~15;  // rows of the float2 spectrum padded to whole 128-B lines
-      const size_t nb = (size_t)ps->kxs32 * ps->np[1] * ps->np[2] * 2 * sizeof(float);
-      bool ok32 = hipMalloc(&ps->phat32, nb) == hipSuccess && hipMemset(ps->phat32, 0, nb) == hipSuccess;
-      for (int a = 0; ok32 && a < 3; ++a) ok32 = ins_zsolve_twiddles_f32(ps->np[a], &ps->tw32[a]) == INS_OK;
-      ps->own32 = ok32;
-    }
+  // the plans above serve every route (ins_poisson_solve_f32); a route that cannot be set up leaves the solver one route down
+  const F32Route want = ins_f32_choose(g.D, ps->np[0], ps->np[1], ps->np[2]);
+  if (want != F32_HIPFFT && ins_poisson_spectral_create(G, &ps->ps64) == INS_OK) ps->route = F32_FP64_SPECTRA;  // the fused fp64 passes for project!
+  if (want == F32_FLOAT2_SPECTRA && ps->route == F32_FP64_SPECTRA) {
+    ps->kxs32 = (ps->kmax[0] + 15) & ~15;  // rows of the float2 spectrum padded to whole 128-B lines
+    const size_t nb = (size_t)ps->kxs32 * ps->np[1] * ps->np[2] * 2 * sizeof(float);
+    bool ok32 = hipMalloc(&ps->phat32, nb) == hipSuccess && hipMemset(ps->phat32, 0, nb) == hipSuccess;
+    for (int a = 0; ok32 && a < 3; ++a) ok32 = ins_zsolve_twiddles_f32(ps->np[a], &ps->tw32[a]) == INS_OK;
+    if (ok32) ps->route = F32_FLOAT2_SPECTRA;
   }
   *out = ps;
   return INS_OK;
@@ -433,10 +486,7 @@ static int solve32(ins_poisson32* ps, hipStream_t s) {  // pI -> pI
   INS_FFT_TRY(hipfftExecR2C(ps->fwd, ps->pI, ps->phat));
   const float inv_n = 1.0f / ((float)ps->np[0] * (float)ps->np[1] * (float)ps->np[2]);
   const dim3 grid(cdiv(ps->kmax[0], 64), cdiv(ps->kmax[1], 4), g.D == 3 ? ps->kmax[2] : 1);
-  if (g.D == 2)
-    hipLaunchKernelGGL(k32_symbol<2>, grid, dim3(64, 4), 0, s, ps->phat, ps->ahat[0], ps->ahat[1], nullptr, ps->kmax[0], ps->kmax[1], inv_n);
-  else
-    hipLaunchKernelGGL(k32_symbol<3>, grid, dim3(64, 4), 0, s, ps->phat, ps->ahat[0], ps->ahat[1], ps->ahat[2], ps->kmax[0], ps->kmax[1], inv_n);
+  K32_LAUNCH_BY_DIM(g.D, k32_symbol, grid, s, ps->phat, ps->ahat[0], ps->ahat[1], ps->ahat[2], ps->kmax[0], ps->kmax[1], inv_n);  // 2-D: ahat[2] is null
   INS_LAUNCH_CHECK();
   INS_FFT_TRY(hipfftExecC2R(ps->inv, ps->phat, ps->pI));
   return INS_OK;
@@ -448,49 +498,24 @@ extern "C" int ins_project_f32(const ins_grid_t* G, ins_poisson32_t* ps, float* 
   INS_REQUIRE(G && ps && u && p, "null argument");
   INS_REQUIRE(ps->grid == G, "psolver was created for a different grid");
   hipStream_t s = as_stream(stream);
-  if (ps->wrap64) return ins_k32g_project(G, ps->wrap64, ps->p64, u, p, s);
   const Box32 b = box_of(G);
+  const bool one_kernel = !ins_opt(OPT_INS_F32_SPLIT_GRADIENT);  // read per call; the own passes exist in 3-D only
   int rc;
-  if (ps->own32) {
-    if ((rc = ins_k_spectral_solve_f32(ps->ps64, u, ps->pI, ps->phat32, ps->kxs32, ps->tw32[0], ps->tw32[1], ps->tw32[2], s))) return rc;
-    if (!ins_opt(OPT_INS_F32_SPLIT_GRADIENT)) {
-      hipLaunchKernelGGL((k32_grad_ghost3<float>), grid_over(b, false), dim3(64, 4), 0, s, b, u, p, (const float*)ps->pI);
+  switch (ps->route) {
+    case F32_WRAP: return ins_k32g_project(G, ps->wrap64, ps->p64, u, p, s);
+    case F32_FLOAT2_SPECTRA:
+      if ((rc = ins_k_spectral_solve_f32(ps->ps64, u, ps->pI, ps->phat32, ps->kxs32, ps->tw32[0], ps->tw32[1], ps->tw32[2], s))) return rc;
+      return project_tail(G, b, u, p, (const float*)ps->pI, one_kernel, s);
+    case F32_FP64_SPECTRA:
+      if ((rc = ins_k_spectral_solve_from_u32(ps->ps64, u, s))) return rc;
+      return project_tail(G, b, u, p, ins_k_spectral_pI(ps->ps64), one_kernel, s);
+    case F32_HIPFFT:
+      K32_LAUNCH_BY_DIM(b.D, k32_div, grid_over(b, false), s, b, u, ps->pI);
       INS_LAUNCH_CHECK();
-      return INS_OK;
-    }
-    hipLaunchKernelGGL((k32_pad<3, float>), grid_over(b, true), dim3(64, 4), 0, s, b, (const float*)ps->pI, p);
-    hipLaunchKernelGGL(k32_applypressure<3>, grid_over(b, false), dim3(64, 4), 0, s, b, u, p);
-    INS_LAUNCH_CHECK();
-    return bc_periodic(G, u, b.D, s);
+      if ((rc = solve32(ps, s))) return rc;
+      return project_tail(G, b, u, p, (const float*)ps->pI, false, s);  // the three kernels, in 3-D too
   }
-  if (ps->ps64) {
-    if ((rc = ins_k_spectral_solve_from_u32(ps->ps64, u, s))) return rc;
-    if (!ins_opt(OPT_INS_F32_SPLIT_GRADIENT)) {
-      hipLaunchKernelGGL((k32_grad_ghost3<double>), grid_over(b, false), dim3(64, 4), 0, s, b, u, p, ins_k_spectral_pI(ps->ps64));
-      INS_LAUNCH_CHECK();
-      return INS_OK;
-    }
-    hipLaunchKernelGGL((k32_pad<3, double>), grid_over(b, true), dim3(64, 4), 0, s, b, ins_k_spectral_pI(ps->ps64), p);
-    hipLaunchKernelGGL(k32_applypressure<3>, grid_over(b, false), dim3(64, 4), 0, s, b, u, p);
-    INS_LAUNCH_CHECK();
-    return bc_periodic(G, u, b.D, s);
-  }
-  if (b.D == 2) {
-    hipLaunchKernelGGL(k32_div<2>, grid_over(b, false), dim3(64, 4), 0, s, b, u, ps->pI);
-  } else {
-    hipLaunchKernelGGL(k32_div<3>, grid_over(b, false), dim3(64, 4), 0, s, b, u, ps->pI);
-  }
-  INS_LAUNCH_CHECK();
-  if ((rc = solve32(ps, s))) return rc;
-  if (b.D == 2) {
-    hipLaunchKernelGGL(k32_pad<2>, grid_over(b, true), dim3(64, 4), 0, s, b, ps->pI, p);
-    hipLaunchKernelGGL(k32_applypressure<2>, grid_over(b, false), dim3(64, 4), 0, s, b, u, p);
-  } else {
-    hipLaunchKernelGGL(k32_pad<3>, grid_over(b, true), dim3(64, 4), 0, s, b, ps->pI, p);
-    hipLaunchKernelGGL(k32_applypressure<3>, grid_over(b, false), dim3(64, 4), 0, s, b, u, p);
-  }
-  INS_LAUNCH_CHECK();
-  return bc_periodic(G, u, b.D, s);
+  return INS_ERR_INVALID;
 }
 
 // psolver(p): solve L p = f on view(p, Ip) in place (pressure.jl:318-350); ghosts of p are refreshed
@@ -499,8 +524,8 @@ extern "C" int ins_poisson_solve_f32(ins_poisson32_t* ps, float* p, void* stream
   hipStream_t s = as_stream(stream);
   const ins_grid* G = ps->grid;
   const GridDev& g = G->g;
-  if (ps->wrap64) return ins_k32g_solve(G, ps->wrap64, ps->p64, p, s);
-  // strip the ghosts (2-D copies), solve, pad
+  if (ps->route == F32_WRAP) return ins_k32g_solve(G, ps->wrap64, ps->p64, p, s);
+  // every spectral route: strip the ghosts (2-D copies), solve on the hipFFT plans, pad
   const size_t w = (size_t)ps->np[0] * sizeof(float);
   hipMemcpy3DParms c = {};
   c.srcPtr = make_hipPitchedPtr(p, (size_t)g.N[0] * sizeof(float), g.N[0], g.N[1]);
@@ -511,11 +536,7 @@ extern "C" int ins_poisson_solve_f32(ins_poisson32_t* ps, float* p, void* stream
   INS_HIP_TRY(hipMemcpy3DAsync(&c, s));
   int rc = solve32(ps, s);
   if (rc) return rc;
-  const Box32 b = box_of(G);
-  if (b.D == 2)
-    hipLaunchKernelGGL(k32_pad<2>, grid_over(b, true), dim3(64, 4), 0, s, b, ps->pI, p);
-  else
-    hipLaunchKernelGGL(k32_pad<3>, grid_over(b, true), dim3(64, 4), 0, s, b, ps->pI, p);
+  pad32(box_of(G), (const float*)ps->pI, p, s);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
@@ -562,11 +583,29 @@ extern "C" int ins_rk_create_f32(const ins_grid_t* G, ins_poisson32_t* ps, int n
   return INS_OK;
 }
 
-// The in-register correction runs: boxes the 64-wide stage kernel takes, on the fp64 solver's spectral passes
-static bool rk32_incorr(const ins_rk32* rk) {
+// Which stage loop a step takes: the only place these conditions are written.  Evaluated per call, since INS_DISABLE_INKERNEL_CORR, INS_RK_KEEP_K and
+// INS_DISABLE_STEP_CHAIN are read per call; the solver's route is the one its creation stored.  (ins_dbg_rk32_route: the bools in this order, bit 0 up.)
+struct Rk32Route {
+  F32Route solver;
+  bool general;         // walls / stretched spacings: the operator kernels of ins_f32g.hip, the reference's sequence stage by stage
+  bool wide;            // the 64-wide stage kernel, the stage combination as its epilogue
+  bool incorr;          // stages >= 2 correct the previous stage's velocity in registers: wide boxes on the fp64 solver's own passes (either spectra)
+  bool float2_spectra;  // the solver's float pI is what the next stage's stencil kernel reads
+  bool vbasis;          // stage-velocity basis: no stage force is stored or read
+  bool chainable;       // ins_rk_steps_f32 folds a step's last correction into the next step's first stage
+};
+static Rk32Route rk32_route(const ins_rk32* rk) {
   const ins_grid* G = rk->grid;
-  return ins_flux64_supported(G) && rk->ps->ps64 && rk->nstage > 1 && G->uniform_exact && G->g.N[0] >= 8 && G->g.N[1] >= 8 && G->g.N[2] >= 8 &&
-         !ins_opt(OPT_INS_DISABLE_INKERNEL_CORR);
+  Rk32Route r;
+  r.solver = rk->ps->route;
+  r.general = !periodic_uniform(G);
+  r.wide = !r.general && ins_flux64_supported(G);
+  r.float2_spectra = r.solver == F32_FLOAT2_SPECTRA;
+  r.incorr = r.wide && (r.float2_spectra || r.solver == F32_FP64_SPECTRA) && rk->nstage > 1 && G->uniform_exact && G->g.N[0] >= 8 && G->g.N[1] >= 8 &&
+             G->g.N[2] >= 8 && !ins_opt(OPT_INS_DISABLE_INKERNEL_CORR);
+  r.vbasis = r.incorr && !ins_opt(OPT_INS_RK_KEEP_K) && ins_rk_vbasis_possible(rk->A.data(), rk->nstage);
+  r.chainable = r.float2_spectra && r.vbasis && !ins_opt(OPT_INS_DISABLE_STEP_CHAIN);  // the chain needs the solver's float pI and the stage-velocity basis
+  return r;
 }
 
 // timestep!(method, stepper, Δt; cache) for closure_model = temp = bodyforce = nothing, T = Float32       step_explicit_runge_kutta.jl:4-59
@@ -579,25 +618,23 @@ static int rk32_step(ins_rk32* rk, float visc, float* u, float dt, hipStream_t s
   const ins_grid* G = rk->grid;
   const int ns = rk->nstage, D = G->g.D;
   const long long nvec = G->ncell * D;
-  const bool general = !periodic_uniform(G);  // walls / stretched spacings: the operator kernels of ins_f32g.hip, the reference's sequence stage by stage
-  const bool wide = !general && ins_flux64_supported(G);
+  const Rk32Route r = rk32_route(rk);
+  const bool general = r.general, wide = r.wide, incorr = r.incorr, fl2 = r.float2_spectra, vbasis = r.vbasis;
   const bool raw_in = chain & 1, raw_out = chain & 2;
   int rc;
-  if (general && !rk->ps->wrap64) {
+  if (general && r.solver != F32_WRAP) {
     ins_set_error("ins_rk_step_f32: this grid needs a solver made by ins_poisson_wrap_f32");
     return INS_ERR_UNSUPPORTED;
   }
+  // F32_WRAP with !general (a wrapped solver on a periodic uniform box) takes the periodic loop without ghost fills: ADVICE.md, first finding, open
   if (!raw_in && (rc = general ? ins_k32g_apply_bc_u(G, u, s) : bc_periodic(G, u, D, s))) return rc;  // :19
   // Wide power-of-two boxes: the fp64 path's stage structure in float — stages >= 2 read the previous stage's UNCORRECTED u* and
   // its pressure and apply u = u* - ∇p in registers (CORR = 1), the solve forms Ω·div(u*) from the float field inside its x
   // pass; only the last stage materialises u (padded p, gradient-subtract, ghosts).
-  const bool incorr = wide && rk32_incorr(rk);  // wide: not on the general path (walls / stretched spacings)
   const long long ncell_in = (long long)(G->g.N[0] - 2) * (G->g.N[1] - 2) * (G->g.N[2] - 2);
-  const bool own32 = rk->ps->own32;  // float2 spectra: the solver's float pI is what the next stage's stencil kernel reads
-  if (incorr && !own32 && !rk->pu) INS_HIP_TRY(hipMalloc(&rk->pu, ncell_in * sizeof(float)));
-  const float* pcorr = own32 ? rk->ps->pI : rk->pu;
-  const bool vbasis = incorr && !ins_opt(OPT_INS_RK_KEEP_K) && ins_rk_vbasis_possible(rk->A.data(), ns);
-  if (chain && !(incorr && own32)) {
+  if (incorr && !fl2 && !rk->pu) INS_HIP_TRY(hipMalloc(&rk->pu, ncell_in * sizeof(float)));
+  const float* pcorr = fl2 ? rk->ps->pI : rk->pu;
+  if (chain && !(incorr && fl2)) {
     ins_set_error("ins_rk_steps_f32: chained steps need the in-register correction on float2 spectra");
     return INS_ERR_UNSUPPORTED;
   }
@@ -616,13 +653,13 @@ static int rk32_step(ins_rk32* rk, float visc, float* u, float dt, hipStream_t s
       if ((rc = ins_k_flux64_f32(G, (double)visc, cur, vbasis ? rk->ub[0] : rk->ku[i], &epi, corr ? pcorr : nullptr, corr ? 1 : 0, s))) return rc;   // :21, :35-38
     } else {
       if ((rc = ins_momentum_f32(G, visc, cur, rk->ku[i], s))) return rc;       // :21
-      Comb32 cb;
-      cb.n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), (const float*)nullptr, cb.coef, cb.k);  // Δt (float)A[i,j], in float
-      hipLaunchKernelGGL(k32_combine, dim3((unsigned)std::min<long long>((nvec + 255) / 256, 8192)), dim3(256), 0, s, nvec, u, outp, cb);  // :35-38
-      INS_LAUNCH_CHECK();
+      float coef[INS_MAX_STAGES + 1];
+      const float* k[INS_MAX_STAGES + 1];
+      const int nt = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), (const float*)nullptr, coef, k);  // Δt (float)A[i,j], in float
+      if ((rc = ins_k32_combine(nvec, u, outp, nt, coef, k, s))) return rc;      // :35-38
       if (general && (rc = ins_k32g_apply_bc_u(G, outp, s))) return rc;          // :47
     }
-    if (incorr && (i < ns - 1 || raw_out) && own32) {  // solve only, float2 spectra: p lands in the solver's float pI
+    if (incorr && (i < ns - 1 || raw_out) && fl2) {  // solve only, float2 spectra: p lands in the solver's float pI
       ins_poisson32* q = rk->ps;
       if ((rc = ins_k_spectral_solve_f32(q->ps64, outp, q->pI, q->phat32, q->kxs32, q->tw32[0], q->tw32[1], q->tw32[2], s))) return rc;
     } else if (incorr && i < ns - 1) {  // solve only: p (unpadded, float) for the next stage's in-register correction
@@ -651,10 +688,7 @@ extern "C" int ins_rk_steps_f32(ins_rk32_t* rk, float visc, float* u, float dt, 
   INS_REQUIRE(rk && u && nsteps >= 0, "bad argument");
   const ins_grid* G = rk->grid;
   hipStream_t s = as_stream(stream);
-  // the chain needs the solver's float pI (float2 spectra) and the stage-velocity basis
-  const bool ok = rk32_incorr(rk) && rk->ps->own32 && !ins_opt(OPT_INS_DISABLE_STEP_CHAIN) && !ins_opt(OPT_INS_RK_KEEP_K) &&
-                  ins_rk_vbasis_possible(rk->A.data(), rk->nstage);
-  if (!ok || nsteps < 2) {
+  if (!rk32_route(rk).chainable || nsteps < 2) {
     for (int n = 0; n < nsteps; ++n) {
       int rc = rk32_step(rk, visc, u, dt, s, 0);
       if (rc) return rc;
@@ -719,7 +753,8 @@ static int rk32_step_ext(ins_rk32* rk, float visc, float* u, float* temp, float 
   const int ns = rk->nstage, D = g.D;
   const long long nvec = G->ncell * D;
   const size_t sbytes = (size_t)G->ncell * sizeof(float);
-  const bool general = !periodic_uniform(G);
+  const Rk32Route r = rk32_route(rk);
+  const bool general = r.general;
   const ins_temperature_desc_t& td = rk->td;
   const bool closure = rk->closure == 1;
   int rc;
@@ -728,7 +763,7 @@ static int rk32_step_ext(ins_rk32* rk, float visc, float* u, float* temp, float 
       ins_set_error("ins_rk_step_ext_f32: slab (halo) grids run in fp64 only");
       return INS_ERR_UNSUPPORTED;
     }
-  if (general && !rk->ps->wrap64) {
+  if (general && r.solver != F32_WRAP) {
     ins_set_error("ins_rk_step_ext_f32: this grid needs a solver made by ins_poisson_wrap_f32");
     return INS_ERR_UNSUPPORTED;
   }
@@ -790,20 +825,13 @@ static int rk32_step_ext(ins_rk32* rk, float visc, float* u, float* temp, float 
         INS_HIP_TRY(hipMemsetAsync(rk->ktemp[i], 0, sbytes, s));
         if ((rc = ins_convection_diffusion_temp_f32(G, a4, cur, tin, rk->ktemp[i], s))) return rc;
         if (td.dodissipation && (rc = ins_dissipation_f32(G, visc, dcoef, cur, rk->diff, rk->ktemp[i], s))) return rc;
-        Comb32 cb;
-        cb.n = i + 1;
-        for (int j = 0; j <= i; ++j) {
-          cb.coef[j] = tcoef[j];
-          cb.k[j] = tk[j];
-        }
-        hipLaunchKernelGGL(k32_combine, dim3((unsigned)std::min<long long>((G->ncell + 255) / 256, 8192)), dim3(256), 0, s, G->ncell, rk->tempstart, tout, cb);
-        INS_LAUNCH_CHECK();
+        if ((rc = ins_k32_combine(G->ncell, rk->tempstart, tout, i + 1, tcoef, tk, s))) return rc;
       }
     }
-    Comb32 cb;
-    cb.n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, cb.coef, cb.k);                // the body force: one more term
-    hipLaunchKernelGGL(k32_combine, dim3((unsigned)std::min<long long>((nvec + 255) / 256, 8192)), dim3(256), 0, s, nvec, u, outp, cb);  // :35-38
-    INS_LAUNCH_CHECK();
+    float coef[INS_MAX_STAGES + 1];
+    const float* k[INS_MAX_STAGES + 1];
+    const int nt = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, coef, k);             // the body force: one more term
+    if ((rc = ins_k32_combine(nvec, u, outp, nt, coef, k, s))) return rc;                                  // :35-38
     if (general && (rc = bc_u(outp))) return rc;                                                           // :47
     if ((rc = ins_project_f32(G, rk->ps, outp, rk->p, s))) return rc;                                      // :48-49 (periodic boxes: fills the ghosts itself)
     if (general && (rc = bc_u(outp))) return rc;
@@ -834,30 +862,16 @@ extern "C" int ins_rk_step_ext_f32(ins_rk32_t* rk, float visc, float* u, float* 
 extern "C" int ins_max_abs_divergence_f32(const ins_grid_t* G, ins_poisson32_t* ps, const float* u, float* out, void* stream) {
   INS_REQUIRE(G && ps && u && out, "null argument");
   hipStream_t s = as_stream(stream);
-  if (ps->wrap64) {  // any grid: divergence! on Ip of a padded scratch (zero elsewhere), maximum on the host
-    int rc = ins_k32g_divergence(G, u, ps->div32, s);
-    if (rc) return rc;
-    std::vector<float> h(G->ncell);
-    INS_HIP_TRY(hipMemcpyAsync(h.data(), ps->div32, G->ncell * sizeof(float), hipMemcpyDeviceToHost, s));
-    INS_HIP_TRY(hipStreamSynchronize(s));
-    float m = 0.f;
-    for (float v : h) m = std::fmax(m, std::fabs(v));
-    *out = m;
-    return INS_OK;
+  int rc;
+  if (ps->route == F32_WRAP) {  // any grid: divergence! on Ip of a padded scratch (zero elsewhere), maximum on the host
+    if ((rc = ins_k32g_divergence(G, u, ps->div32, s))) return rc;
+    return host_max_abs(ps->div32, G->ncell, s, out);
   }
-  const Box32 b = box_of(G);
-  if (b.D == 2)
-    hipLaunchKernelGGL(k32_div<2>, grid_over(b, false), dim3(64, 4), 0, s, b, u, ps->pI);
-  else
-    hipLaunchKernelGGL(k32_div<3>, grid_over(b, false), dim3(64, 4), 0, s, b, u, ps->pI);
+  const Box32 b = box_of(G);  // every spectral route: Ω·div(u) in the solver's pI
+  K32_LAUNCH_BY_DIM(b.D, k32_div, grid_over(b, false), s, b, u, ps->pI);
   INS_LAUNCH_CHECK();
-  const long long n = (long long)ps->np[0] * ps->np[1] * ps->np[2];
-  std::vector<float> h(n);
-  INS_HIP_TRY(hipMemcpyAsync(h.data(), ps->pI, n * sizeof(float), hipMemcpyDeviceToHost, s));
-  INS_HIP_TRY(hipStreamSynchronize(s));
-  float m = 0.f;
-  for (float v : h) m = std::fmax(m, std::fabs(v));
-  *out = m / b.om;
+  if ((rc = host_max_abs(ps->pI, (long long)ps->np[0] * ps->np[1] * ps->np[2], s, out))) return rc;
+  *out /= b.om;
   return INS_OK;
 }
 
@@ -865,6 +879,15 @@ extern "C" int ins_max_abs_divergence_f32(const ins_grid_t* G, ins_poisson32_t* 
 // and the grid the handle was made for.
 ins_poisson* ins_k32_wrapped(const ins_poisson32* ps, double** p64) {
   *p64 = ps->p64;
-  return ps->wrap64;
+  return ps->route == F32_WRAP ? ps->wrap64 : nullptr;
 }
 const ins_grid* ins_k32_solver_grid(const ins_poisson32* ps) { return ps->grid; }
+
+// test hooks: the route a periodic uniform box would get under the current option values, without touching the device; a live integrator's solver route and
+// the bit set of its step route (Rk32Route)
+extern "C" int ins_dbg_f32_choose(int D, int n0, int n1, int n2) { return (int)ins_f32_choose(D, n0, n1, D == 3 ? n2 : 1); }
+extern "C" int ins_dbg_rk32_route(const ins_rk32_t* rk, int32_t* flags) {
+  const Rk32Route r = rk32_route(rk);
+  if (flags) *flags = r.general | r.wide << 1 | r.incorr << 2 | r.float2_spectra << 3 | r.vbasis << 4 | r.chainable << 5;
+  return (int)r.solver;
+}

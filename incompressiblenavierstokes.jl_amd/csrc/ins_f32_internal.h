@@ -3,9 +3,21 @@
 
 #include "ins_internal.h"
 
-// ins_f32.hip: the wrapped fp64 solver of a Float32 solver handle (nullptr: a spectral Float32 solver) with its padded fp64 scratch, and the handle's grid
+// Launch sequence of a Float32 solver: chosen once, when the solver is created (ins_f32_choose / ins_poisson_wrap_f32, ins_f32.hip), stored in the handle and
+// dispatched on by ins_project_f32, ins_poisson_solve_f32, ins_max_abs_divergence_f32 and the step's route (rk32_route).  A new route is a new value here.
+enum F32Route {
+  F32_HIPFFT = 0,      // Ω·div(u) -> hipFFT R2C -> symbol -> C2R in float, then pad -> gradient-subtract -> periodic ghosts
+  F32_FP64_SPECTRA,    // 3-D boxes whose fp64 solver runs on own passes: those passes, fed from the float field
+  F32_FLOAT2_SPECTRA,  // of those, the z sides of the three-pass z kernel (192, 256, 384, 512): the same passes on float2 spectra
+  F32_WRAP,            // a caller-owned fp64 solver of any kind (ins_poisson_wrap_f32): walls, stretched spacings
+};
+// ins_f32.hip: the route of an all-periodic uniform box under the option values at the time of the call (no device); never F32_WRAP
+F32Route ins_f32_choose(int D, int n0, int n1, int n2);
+// the wrapped fp64 solver of a Float32 solver handle (nullptr: not on F32_WRAP) with its padded fp64 scratch, and the handle's grid
 ins_poisson* ins_k32_wrapped(const ins_poisson32* ps, double** p64);
 const ins_grid* ins_k32_solver_grid(const ins_poisson32* ps);
+// out = base + Σ_q coef[q]·k[q] over n floats, terms in index order (k32_combine)
+int ins_k32_combine(long long n, const float* base, float* out, int nterms, const float* coef, const float* const* k, hipStream_t s);
 
 // ins_f32g.hip: the operators on any grid (walls, stretched spacings, 2-D or 3-D), boundary data constant
 int ins_k32g_apply_bc_u(const ins_grid* G, float* u, hipStream_t s, int dudt = 0);

@@ -21,6 +21,7 @@
 // every array is 16-byte aligned, terms in index order, zero coefficients skipped.  The combination is never fused into the pullback kernels
 // here (INS_ADJ_STAGE_FUSED is the fp64 isothermal loop's): the two-launch form is the measured-faster one.
 #pragma once
+#include "ins_f32_internal.h"
 #include "ins_internal.h"
 #include "ins_rk_terms.h"
 
@@ -155,21 +156,6 @@ inline int launch_sums(long long nv, long long nc, T* outv, T* outc, const Terms
   return INS_OK;
 }
 
-// out = base + Σ_q coef[q]·k[q], terms in index order (the stage combinations of the recomputation in float; fp64 has ins_combine_f64).  The
-// arithmetic of k32_combine (csrc/ins_f32.hip), which is local to that file; internal linkage, so that a second includer of this header defines nothing twice.
-struct Comb32 {
-  int n;
-  float coef[INS_MAX_STAGES + 1];
-  const float* k[INS_MAX_STAGES + 1];
-};
-static __global__ __launch_bounds__(256) void k_adj_combine32(long long n, const float* __restrict__ base, float* __restrict__ out, Comb32 cb) {
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
-    float v = base[t];
-    for (int q = 0; q < cb.n; ++q) v += cb.coef[q] * cb.k[q][t];
-    out[t] = v;
-  }
-}
-
 // ---- the operator-level entries of the two families under one spelling
 inline int bc_u(const ins_grid* G, double* u, hipStream_t s) { return ins_k_apply_bc_u(G, u, 0, nullptr, s); }
 inline int bc_u(const ins_grid* G, float* u, hipStream_t s) { return ins_apply_bc_u_f32(G, u, s); }
@@ -205,15 +191,7 @@ inline int combine(const ins_grid* G, long long n, const double* base, double* o
   return n == G->ncell ? ins_combine_scalar_f64(G, base, out, nt, coef, k, s) : ins_combine_f64(G, base, out, nt, coef, k, s);
 }
 inline int combine(const ins_grid*, long long n, const float* base, float* out, int nt, const float* coef, const float* const* k, hipStream_t s) {
-  Comb32 cb;
-  cb.n = nt;
-  for (int q = 0; q < nt; ++q) {
-    cb.coef[q] = coef[q];
-    cb.k[q] = k[q];
-  }
-  hipLaunchKernelGGL(k_adj_combine32, dim3((unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 8192))), dim3(256), 0, s, n, base, out, cb);
-  INS_LAUNCH_CHECK();
-  return INS_OK;
+  return ins_k32_combine(n, base, out, nt, coef, k, s);
 }
 inline int project(const ins_grid* G, ins_poisson* ps, double* u, double* p, hipStream_t s) { return ins_k_project(G, ps, u, p, s); }
 inline int project(const ins_grid* G, ins_poisson32* ps, float* u, float* p, hipStream_t s) { return ins_project_f32(G, ps, u, p, s); }

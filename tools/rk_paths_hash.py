@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """One SHA-256 per stage-loop path of the Runge-Kutta drivers (csrc/ins_rk.hip, ins_rk_ext.hip, ins_f32.hip): u (and temp, p where they exist) after a few
 steps from a fixed seeded field, with the route counters (stage kernels that wrote the Poisson right-hand side, graph replays, fused ext steps) beside it.
+The Float32 family adds one line per solver route (projection, solver call, divergence maximum), extended-loop case and `ad32.timesteps` gradient.
 For a change that must not move a bit: run it on both builds (INS_HIP_LIB selects the library) on the same machine and diff the two outputs.
 
     python tools/rk_paths_hash.py [--only REGEX] > hashes.txt
@@ -173,6 +174,102 @@ def run_f32(label, x, bc, method, nsteps, chained, opts):
     del cache, ps
 
 
+def setup32(geom, with_force=False, temp=False, smag=False, wrap=None):
+    """Setup, Float32 solver and projected float32 start field(s) of a Float32 case.  wrap: None (default_psolver32), or the constructor of the fp64
+    solver psolver_wrap32 goes around."""
+    f32 = ins.f32
+    x, bc, _ = geometry(geom)
+    D = len(x)
+    kw = {} if bc is None else {"boundary_conditions": bc}
+    if with_force:
+        kw.update(bodyforce=force, issteadybodyforce=True)
+    if temp:
+        tbcs = ((P(), P()),) * D if bc is None else ((ins.SymmetricBC(), ins.SymmetricBC()), (Dn(1.0), Dn(0.0)), (P(), P()))
+        kw["temperature"] = ins.temperature_equation(Pr=0.71, Ra=1e6, Ge=0.1, boundary_conditions=tbcs, gdir=1, dodissipation=True)
+    else:
+        kw["Re"] = 500.0
+    sp = ins.Setup(x=x, **kw)
+    if smag:
+        sp.closure_model = f32.smagorinsky_closure32(sp)
+    u0 = ins.apply_bc_u(ins.project(ins.apply_bc_u(ins.from_numpy(sp, 0.1 * randn(sp.grid.N + (D,), 5)), 0.0, sp), sp, ins.default_psolver(sp)), 0.0, sp)
+    dt = min(DT, 0.5 * ins.get_cfl_timestep_(None, u0, sp))
+    t0 = f32.apply_bc_temp32_(f32.to_f32(sp, 0.5 + 0.1 * randn(sp.grid.N, 4)), sp) if temp else None
+    return sp, (lambda: f32.default_psolver32(sp) if wrap is None else f32.psolver_wrap32(sp, wrap(sp))), f32.to_f32(sp, ins.to_numpy(u0)), t0, dt
+
+
+def run_f32_solver(label, geom, pre, post, wrap=None):
+    """project32_ (u and p), the solver call on a padded p and max_abs_divergence32, one hash each; `pre` is set before the solver is created, `post` after"""
+    f32 = ins.f32
+    sp, mkps, u0, _, _ = setup32(geom, wrap=wrap)
+    raw = f32.to_f32(sp, 0.1 * randn(sp.grid.N + (len(sp.grid.N),), 7))  # not divergence-free: the projection has work to do
+    with _lib.options(**pre):
+        ps = mkps()
+        with _lib.options(**post):
+            u, p = raw.clone(), f32.scalarfield32(sp)
+            f32.project32_(u, sp, ps, p)
+            hp = sha(label, u.cpu().numpy(), p.cpu().numpy())
+            q = f32.to_f32(sp, randn(sp.grid.N, 9))
+            ps(q)
+            hs = sha(label, q.cpu().numpy())
+            hd = sha(label, np.float32(f32.max_abs_divergence32(raw, sp, ps)))
+    print(f"{label:58s} project={hp} solve={hs} maxdiv={hd}", flush=True)
+    del ps
+
+
+def run_f32_ext(label, geom, method, opts, temp=False, smag=False, with_force=False, wrap=None, nsteps=3, chained=False):
+    f32 = ins.f32
+    sp, mkps, u, t, dt = setup32(geom, with_force, temp, smag, wrap)
+    with _lib.options(**opts):
+        ps = mkps()
+        cache = f32.ERKCache32(getattr(ins.RKMethods, method)(), sp, ps)
+        kw = dict(temp=t, θ=0.17 if smag else None)
+        if chained:
+            f32.timesteps32_(cache, u, dt, nsteps, **kw)
+        else:
+            for _ in range(nsteps):
+                f32.timestep32_(cache, u, dt, **kw)
+        print(f"{label:58s} {sha(label, u.cpu().numpy(), *([t.cpu().numpy()] if temp else []))}", flush=True)
+    del cache, ps
+
+
+def run_ad32(label, geom, temp):
+    """∂L/∂u0 (and ∂L/∂temp0) of L = Σu² (+ Σtemp²) after 3 RK44 steps of ad32.timesteps: the recomputation runs the shared Float32 combine"""
+    sp, mkps, u, t, dt = setup32(geom, temp=temp)
+    ps = mkps()
+    m = ins.RKMethods.RK44()
+    u.requires_grad_(True)
+    if temp:
+        t.requires_grad_(True)
+    st = ins.ad32.timesteps(m, ins.create_stepper(m, setup=sp, psolver=ps, u=u, temp=t), dt, 3)
+    ((st.u * st.u).sum() + ((st.temp * st.temp).sum() if temp else 0.0)).backward()
+    print(f"{label:58s} {sha(label, u.grad.cpu().numpy(), *([t.grad.cpu().numpy()] if temp else []))}", flush=True)
+    del st, ps
+
+
+def cases_f32():
+    """the Float32 solver routes, the extended loop, the adjoint's recomputation and the wrapped solver on periodic boxes (csrc/ins_f32.hip)"""
+    boxes = (("hipfft", "per32x32"), ("hipfft", "per66x12x10"), ("hipfft", "per24x18"), ("fp64spectra", "per128x16x16"), ("fp64spectra", "per32x16x16"),
+             ("float2", "per128x16x256"), ("float2", "per256x16x192"), ("wrapped", "walls24"))
+    for route, geom in boxes:
+        yield f"f32 solver {route} {geom}", run_f32_solver, dict(geom=geom, pre={}, post={})
+    for name, pre, post in (("fp64spectra=1", dict(INS_F32_FP64_SPECTRA=1), {}), ("hipfftproject=1", dict(INS_F32_HIPFFT_PROJECT=1), {}),
+                            ("splitgradient=1", {}, dict(INS_F32_SPLIT_GRADIENT=1))):
+        yield f"f32 solver per128x16x256 {name}", run_f32_solver, dict(geom="per128x16x256", pre=pre, post=post)
+    terms = (("temp", dict(temp=True)), ("smag", dict(smag=True)), ("force", dict(with_force=True)), ("all", dict(temp=True, smag=True, with_force=True)))
+    for geom in ("per32x16x16", "per72x10x8", "walls24"):
+        for method in ("RK44", "Wray3"):
+            for what, kw in terms:
+                yield f"f32 ext {what} {geom} {method}", run_f32_ext, dict(geom=geom, method=method, opts={}, **kw)
+            yield f"f32 ext all {geom} {method} tempsplit", run_f32_ext, dict(geom=geom, method=method, opts=dict(INS_DISABLE_TEMP32_STAGE=1), temp=True,
+                                                                              smag=True, with_force=True)
+    for geom in ("per32x16x16", "walls24"):
+        for temp in (False, True):
+            yield f"f32 ad32.timesteps gradient {geom}{' temp' if temp else ''}", run_ad32, dict(geom=geom, temp=temp)
+    for geom in ("per32x16x16", "per32x32"):  # ADVICE.md, first finding: pinned as it is, not as it should be
+        yield f"f32 wrap32(spectral) {geom} RK44 (ADVICE.md defect: no ghost fills)", run_f32_ext, dict(geom=geom, method="RK44", opts={},
+                                                                                                      wrap=ins.psolver_spectral)
+
+
 def cases():
     per3 = [f"per{n}" for n in ("32x32x32", "66x10x4", "128x16x12", "128x16x16")]
     for with_force in (False, True):
@@ -211,6 +308,7 @@ def cases():
         yield f"f32 per128x16x16 Wray3 chain3 {vn}", run_f32, dict(x=exact((128, 16, 16)), bc=None, method="Wray3", nsteps=3, chained=True, opts=vo)
     yield "f32 per32x16x16 RK44 single (narrow: plain kernels)", run_f32, dict(x=exact((32, 16, 16)), bc=None, method="RK44", nsteps=3, chained=False, opts={})
     yield "f32 walls24 RK44 single (wrapped fp64 solver)", run_f32, dict(x=wx, bc=wbc, method="RK44", nsteps=3, chained=False, opts={})
+    yield from cases_f32()
 
 
 def main():
