@@ -236,6 +236,15 @@ int ins_filter_face_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, 
 /* (Φ::VolumeAverage)(v, u, setup_les, comp) filter.jl:82-116: mean over the coarse volume centred on the coarse face (comp + 1 planes along α
  * for even comp, comp for odd), fine indices wrapped over the fine interior.  All-periodic grids, else INS_ERR_UNSUPPORTED.  Writes Iu[α] only. */
 int ins_filter_volume_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, const double* u, double* v, void* stream);
+/* The two filters for nbatch fields of one pair of 2-D grids in one launch (the member is one more launch dimension of the generic kernel, the window sum
+ * the same text): coarse member b, at v + b·vstride, is bitwise what the entry above gives for the fine field at u + b·ustride.  ustride >= 2·ncell of the
+ * fine grid, vstride >= 2·ncell of the coarse grid; only Iu[α] of every coarse member is written, what lies between members is neither read nor written.
+ * Fields that share a buffer and a stride (a state and its right-hand side) are filtered by one call with nbatch counting both.  3-D grids:
+ * INS_ERR_UNSUPPORTED with a message that names ins_filter_face_f64 / ins_filter_volume_f64 per member; the volume average needs all-periodic grids. */
+int ins_filter_face_members_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, int nbatch, const double* u, int64_t ustride, double* v,
+                                int64_t vstride, void* stream);
+int ins_filter_volume_members_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, int nbatch, const double* u, int64_t ustride, double* v,
+                                  int64_t vstride, void* stream);
 /* reconstruct!(u, v, setup_dns, setup_les, comp)  filter.jl:48-80: piecewise linear along α, piecewise constant across.  All-periodic grids,
  * else INS_ERR_UNSUPPORTED.  The left neighbour is wrapped over the coarse interior; writes the fine interior only. */
 int ins_reconstruct_f64(const ins_grid_t* dns, const ins_grid_t* les, int comp, const double* v, double* u, void* stream);
@@ -277,6 +286,17 @@ int ins_rk_steps_f64(ins_rk_t* rk, double visc, double* u, double t, double dt, 
 int ins_rk_ensemble_create(const ins_grid_t* grid, ins_poisson_t* poisson, int nstage, const double* A, const double* c, int nbatch, ins_rk_ensemble_t** out);
 int ins_rk_ensemble_destroy(ins_rk_ensemble_t* ens);
 int ins_rk_ensemble_steps_f64(ins_rk_ensemble_t* ens, double visc, double* U, int64_t ustride, double t, double dt, int nsteps, void* stream);
+/* The projected right-hand side of every member, F[b] = apply_bc_u(project(apply_bc_u(momentum(U[b]); dudt))): the `F` that filtersaver forms on the DNS grid
+ * and lesdatagen on the LES grid (data_generation.jl:37-120), for all members in the launches of one field — the force form of the stage kernel, the solve (one
+ * pass or three) and the gradient-subtract + ghost pass, on the handle's own pressure and spectrum arrays.  U is read only and has valid ghost volumes (as
+ * ins_rk_ensemble_steps_f64 leaves them); F != U, member b at F + b·fstride, fstride >= 2·ncell, ghost volumes of every F[b] valid on return, what lies between
+ * members not touched.  Agrees with the per-member chain ins_momentum_f64, ins_apply_bc_u_f64(dudt), ins_project_f64, ins_apply_bc_u_f64 to rounding (the
+ * fused kernels sum in another order), and member b is bitwise what a handle with nbatch = 1 gives for that field.  A handle whose box an INS_DISABLE_*
+ * switch has since turned away: INS_ERR_UNSUPPORTED with a message that names that per-member chain. */
+int ins_rk_ensemble_rhs_f64(ins_rk_ensemble_t* ens, double visc, const double* U, int64_t ustride, double* F, int64_t fstride, void* stream);
+/* apply_bc_u! of every member (periodic images, corners included) in two launches: for fields whose interior was written by something other than the
+ * stepper, e.g. the member filters below, before they go to ins_rk_ensemble_rhs_f64 or ins_rk_ensemble_steps_f64. */
+int ins_rk_ensemble_apply_bc_u_f64(ins_rk_ensemble_t* ens, double* U, int64_t ustride, void* stream);
 /* Device pointers into the cache (valid until ins_rk_destroy): the stage pressure `p` and `ku[i]`. */
 /* K6 alone: out = base + Σ_q coefs[q]·ks[q] over whole vector fields, summed in index order — the stage-combination
  * broadcasts `u .= ustart; u .+= Δt A[i,j] ku[j]` (step_explicit_runge_kutta.jl:35-38) and LMWray3's state_copyto! /

@@ -110,6 +110,8 @@ from .time_steppers import (
     LMWray3,
     RKMethods,
     create_stepper,
+    ensemble_apply_bc_u_,
+    ensemble_rhs_,
     ode_method_cache,
     runge_kutta_method,
     timestep,
@@ -122,7 +124,7 @@ from . import autodiff32 as ad32  # noqa: E402  (the same over float32 fields an
 
 from . import neuralclosure  # noqa: E402  (lib/NeuralClosure: filters, filtered-DNS data generation, closures, losses, training)
 from .neuralclosure import (FaceAverage, VolumeAverage, cnn, collocate, create_dataloader_post, create_dataloader_prior,  # noqa: E402
-                            create_io_arrays, create_les_data, create_loss_post, create_loss_prior, create_relerr_post, create_relerr_prior,
+                            create_io_arrays, create_les_data, create_les_data_ensemble, create_loss_post, create_loss_prior, create_relerr_post, create_relerr_prior,
                             decollocate, filtersaver, lesdatagen, reconstruct, reconstruct_, tensorclosure, train, wrappedclosure)
 
 _lib.load()  # fail loudly at import time if libinship.so is absent

@@ -10,6 +10,18 @@ extern "C" int ins_filter_volume_f64(const ins_grid_t* les, const ins_grid_t* dn
   return launch_filter<true, double, 1>(les, dns, comp, u, v, as_stream(stream));
 }
 
+// The two filters for the nbatch members of an ensemble of 2-D fields in one launch (member on blockIdx.z): the window sums are the text of k_filter<2, VOL, double>,
+// so member b is bitwise what the entries above give for that field alone.
+extern "C" int ins_filter_face_members_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, int nbatch, const double* u, int64_t ustride, double* v,
+                                           int64_t vstride, void* stream) {
+  return launch_filter_members<false, double>(les, dns, comp, nbatch, u, ustride, v, vstride, as_stream(stream));
+}
+
+extern "C" int ins_filter_volume_members_f64(const ins_grid_t* les, const ins_grid_t* dns, int comp, int nbatch, const double* u, int64_t ustride, double* v,
+                                             int64_t vstride, void* stream) {
+  return launch_filter_members<true, double>(les, dns, comp, nbatch, u, ustride, v, vstride, as_stream(stream));
+}
+
 extern "C" int ins_reconstruct_f64(const ins_grid_t* dns, const ins_grid_t* les, int comp, const double* v, double* u, void* stream) {
   return launch_reconstruct<double>(dns, les, comp, v, u, as_stream(stream));
 }

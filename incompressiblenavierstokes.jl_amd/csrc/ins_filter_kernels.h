@@ -44,9 +44,11 @@ struct FilterArgs {
 // --------------------------------------------------------------------------------------------
 // generic filters: one work-item per coarse volume, all components
 // --------------------------------------------------------------------------------------------
+// The window sums of coarse volume I (linear index c) for every component: the one text of the generic filters.  mu / mv: element offsets of the member of
+// an ensemble this work-item works on (k_filter_members); the single-field kernel passes the constant 0, which folds away.
 template <int D, bool VOL, typename T>
-__global__ __launch_bounds__(256) void k_filter(FilterArgs a, const T* __restrict__ ufield, T* __restrict__ vfield) {
-  INS_VOL_INDEX(a.sxc, 0, 0, 0, i >= a.Nc[0] || j >= a.Nc[1]);
+__device__ __forceinline__ void filter_faces(const FilterArgs& a, const int (&I)[3], const long long c, const T* __restrict__ ufield, T* __restrict__ vfield,
+                                             const long long mu, const long long mv) {
   const int C = a.comp;
   const int h = C / 2;
 #pragma unroll
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(256) void k_filter(FilterArgs a, const T* __restric
     }
     if (!in) continue;
     const double cnt = (double)(n[0] * n[1] * n[2]);
-    const T* __restrict__ u = ufield + al * a.scf;
+    const T* __restrict__ u = ufield + mu + al * a.scf;
     double sum = 0.0;
     for (int q2 = 0; q2 < n[2]; ++q2) {
       int f2 = s[2] + q2;
@@ -82,8 +84,25 @@ __global__ __launch_bounds__(256) void k_filter(FilterArgs a, const T* __restric
         }
       }
     }
-    vfield[al * a.scc + c] = (T)(sum / cnt);
+    vfield[mv + al * a.scc + c] = (T)(sum / cnt);
   }
+}
+
+template <int D, bool VOL, typename T>
+__global__ __launch_bounds__(256) void k_filter(FilterArgs a, const T* __restrict__ ufield, T* __restrict__ vfield) {
+  INS_VOL_INDEX(a.sxc, 0, 0, 0, i >= a.Nc[0] || j >= a.Nc[1]);
+  filter_faces<D, VOL, T>(a, I, c, ufield, vfield, 0LL, 0LL);
+}
+
+// The same sums for member blockIdx.z of an ensemble of 2-D fields (in 2-D INS_VOL_INDEX leaves blockIdx.z unused): member b of the fine fields lies
+// b·ustride elements behind ufield, of the coarse fields b·vstride behind vfield.  One launch for all members; the tiles are the single field's.
+template <bool VOL, typename T>
+__global__ __launch_bounds__(256) void k_filter_members(FilterArgs a, const T* __restrict__ ufield, long long ustride, T* __restrict__ vfield,
+                                                        long long vstride) {
+  constexpr int D = 2;
+  INS_VOL_INDEX(a.sxc, 0, 0, 0, i >= a.Nc[0] || j >= a.Nc[1]);
+  const long long b = blockIdx.z;
+  filter_faces<2, VOL, T>(a, I, c, ufield, vfield, b * ustride, b * vstride);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -341,6 +360,32 @@ int launch_filter(const ins_grid* les, const ins_grid* dns, int comp, const T* u
   } else {
     INS_LAUNCH_D((k_filter<D, VOL, T>), box_launch(g.D, a.Nc), s, a, u, v);
   }
+  return INS_OK;
+}
+
+// nbatch 2-D fields in one launch of the generic kernel's text (k_filter_members).  Member b of the fine fields lies at u + b·ustride (ustride >= 2·ncell of the
+// fine grid), of the coarse fields at v + b·vstride; what lies between members is neither read nor written.
+template <bool VOL, typename T>
+int launch_filter_members(const ins_grid* les, const ins_grid* dns, int comp, int nbatch, const T* u, long long ustride, T* v, long long vstride,
+                          hipStream_t s) {
+  INS_REQUIRE(les && dns, "null grid handle");
+  if (les->g.D != 2 || dns->g.D != 2) {
+    ins_set_error("ins_filter_%s_members_f64: a 3-D grid; the member form of the filters runs 2-D grids only: filter each member with ins_filter_%s_f64",
+                  VOL ? "volume" : "face", VOL ? "volume" : "face");
+    return INS_ERR_UNSUPPORTED;
+  }
+  FilterArgs a;
+  int rc = prepare(les, dns, comp, VOL, VOL ? "the volume average" : "the face average", a);
+  if (rc) return rc;
+  INS_REQUIRE(u && v, "null field");
+  INS_REQUIRE((const void*)u != (const void*)v, "the filter cannot run in place");
+  INS_REQUIRE(nbatch >= 1 && nbatch <= 65535, "an ensemble has 1 .. 65535 members");
+  INS_REQUIRE(ustride >= 2 * dns->ncell, "member stride of the fine fields shorter than a vector field (2 ncell)");
+  INS_REQUIRE(vstride >= 2 * les->ncell, "member stride of the coarse fields shorter than a vector field (2 ncell)");
+  Launch3 l = box_launch(2, a.Nc);
+  l.grid.z = (unsigned)nbatch;
+  hipLaunchKernelGGL((k_filter_members<VOL, T>), l.grid, l.block, 0, s, a, u, ustride, v, vstride);
+  INS_LAUNCH_CHECK();
   return INS_OK;
 }
 

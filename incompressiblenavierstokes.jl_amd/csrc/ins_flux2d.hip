@@ -136,6 +136,12 @@ __global__ __launch_bounds__(256) void k_flux2d_members(Flux2dArgs a, RkMemberSt
   flux2d_rows<true, CORR>(a, RkMemberStrides{b * st.u, b * st.p, b * st.F, b * st.ustart, b * st.k, b * st.ustar, b * st.ustart_out});
 }
 
+// The force form (k_flux2d<false>: plain momentum! into F, no stage combination) for member blockIdx.z: ustride / fstride elements between members
+__global__ __launch_bounds__(256) void k_flux2d_members_force(Flux2dArgs a, long long ustride, long long fstride) {
+  const long long b = blockIdx.z;
+  flux2d_rows<false, false>(a, RkMemberStrides{b * ustride, 0, b * fstride, 0, 0, 0, 0});
+}
+
 }  // namespace
 
 bool ins_flux2d_supported(const ins_grid* G) {
@@ -202,6 +208,20 @@ int ins_k_flux2d_members(const ins_grid* G, double visc, const double* u, double
     hipLaunchKernelGGL(k_flux2d_members<true>, grid, block, 0, s, a, st);
   else
     hipLaunchKernelGGL(k_flux2d_members<false>, grid, block, 0, s, a, st);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+
+// Its force form: F[b] = momentum!(u[b]) on the interior of every member (ghost ring of F untouched, as ins_k_flux2d without an epilogue); u has valid ghosts.
+int ins_k_flux2d_members_force(const ins_grid* G, double visc, const double* u, long long ustride, double* F, long long fstride, int nb, hipStream_t s) {
+  dim3 block(64, 4, 1), grid;
+  const Flux2dArgs a = flux2d_args(G, visc, u, F, nullptr, nullptr, &grid);
+  if (nb < 1 || nb > 65535) {
+    ins_set_error("ins_k_flux2d_members_force: %d members do not fit one launch", nb);
+    return INS_ERR_INVALID;
+  }
+  grid.z = (unsigned)nb;
+  hipLaunchKernelGGL(k_flux2d_members_force, grid, block, 0, s, a, ustride, fstride);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }

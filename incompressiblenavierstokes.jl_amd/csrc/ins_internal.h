@@ -492,6 +492,8 @@ struct RkMemberStrides {
 };
 int ins_k_flux2d_members(const ins_grid* G, double visc, const double* u, double* F, const RkEpi& epi, hipStream_t s, const double* pI, int nb,
                          const RkMemberStrides& st);
+// its force form: F[b] = momentum!(u[b]), interior only (the projected right-hand side of all members, ins_rk_ensemble_rhs_f64)
+int ins_k_flux2d_members_force(const ins_grid* G, double visc, const double* u, long long ustride, double* F, long long fstride, int nb, hipStream_t s);
 int ins_k_solve_members_2d(const ins_grid* G, const ins_poisson* ps, const double* u, long long ustride, int nb, double* pI, double* phat, const double* zrows,
                            hipStream_t s);
 int ins_k_grad_ghost_members_2d(const ins_grid* G, const ins_poisson* ps, double* u, long long ustride, int nb, const double* pI, hipStream_t s);

@@ -63,6 +63,13 @@ int refuse(const char* why) {
   return INS_ERR_UNSUPPORTED;
 }
 
+// the same for the entries that run one link of the data-generation chain, not the stepper: the per-member route is the operator-level calls
+int refuse_chain(const char* entry, const char* why) {
+  ins_set_error("%s: %s; the member forms run the boxes of the chained 2-D loop only (all-periodic, exactly uniform, power-of-two sides 16 .. 1024, spectral "
+                "solver on its own passes, more than one stage): run ins_momentum_f64, ins_apply_bc_u_f64 and ins_project_f64 on each member", entry, why);
+  return INS_ERR_UNSUPPORTED;
+}
+
 int fill_ghosts(const ins_rk_ensemble* e, double* U, long long ustride, hipStream_t s) {
   const GridDev& g = e->grid->g;
   for (int be = 0; be < 2; ++be) {
@@ -170,4 +177,31 @@ extern "C" int ins_rk_ensemble_steps_f64(ins_rk_ensemble_t* e, double visc, doub
   for (int n = 0; n < nsteps; ++n)
     if ((rc = step(e, visc, U, ustride, dt, s, chain ? ((n > 0 ? 1 : 0) | (n < nsteps - 1 ? 2 : 0)) : 0))) return rc;
   return INS_OK;
+}
+
+// The projected right-hand side of every member, F[b] = apply_bc_u!(project!(apply_bc_u!(momentum!(U[b]); dudt))): what filtersaver and lesdatagen form per saved
+// state (data_generation.jl:37-60, 62-120), on the member forms the step drives and on the handle's own pI / phat.  Launches: the force form of the stage
+// kernel, the solve (one pass or three) and the gradient-subtract + ghost pass, whatever nb is.  On a periodic box the solve reads the interior of F through
+// its periodic images and the last pass writes every ghost volume of F, so the ghost fill between momentum! and project! of the per-member chain has no reader
+// and is not launched.  U is read only (ghosts valid); F's padding between members is not touched.
+extern "C" int ins_rk_ensemble_rhs_f64(ins_rk_ensemble_t* e, double visc, const double* U, int64_t ustride, double* F, int64_t fstride, void* stream) {
+  INS_REQUIRE(e && U && F, "null argument");
+  INS_REQUIRE(U != F, "the right-hand side cannot be formed in place");
+  int rc = check_args(e->grid->ncell, e->nb, ustride, 0);
+  if (rc || (rc = check_args(e->grid->ncell, e->nb, fstride, 0))) return rc;
+  if (!supported(e->grid, e->ps, e->nstage)) return refuse_chain("ins_rk_ensemble_rhs_f64", "an option has switched the chained 2-D loop off since the handle was created");
+  hipStream_t s = as_stream(stream);
+  if ((rc = ins_k_flux2d_members_force(e->grid, visc, U, ustride, F, fstride, e->nb, s))) return rc;
+  if ((rc = ins_k_solve_members_2d(e->grid, e->ps, F, fstride, e->nb, e->pI, e->phat, e->zrows, s))) return rc;
+  return ins_k_grad_ghost_members_2d(e->grid, e->ps, F, fstride, e->nb, e->pI, s);
+}
+
+// apply_bc_u! of every member on the periodic box (boundary_conditions.jl:276-288): the first-stage ghost fill of the step as an entry of its own, for fields
+// that reach the ensemble from elsewhere with their interior only (filtered fields: the filters write Iu[α]).  Two launches whatever nb is.
+extern "C" int ins_rk_ensemble_apply_bc_u_f64(ins_rk_ensemble_t* e, double* U, int64_t ustride, void* stream) {
+  INS_REQUIRE(e && U, "null argument");
+  int rc = check_args(e->grid->ncell, e->nb, ustride, 0);
+  if (rc) return rc;
+  if (!supported(e->grid, e->ps, e->nstage)) return refuse_chain("ins_rk_ensemble_apply_bc_u_f64", "an option has switched the chained 2-D loop off since the handle was created");
+  return fill_ghosts(e, U, ustride, as_stream(stream));
 }

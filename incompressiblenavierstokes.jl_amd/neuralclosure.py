@@ -15,6 +15,7 @@ CNN) are `(n_1, …, n_D, D, nsample)`: interior volumes only, component, then s
 
 Out of scope: FNO and group-equivariant layers, the symmetry errors (`rot2stag`), `gaussian_force`, JLD2 files (`filenames` writes `.npz`).
 """
+import os
 import time
 
 import numpy as np
@@ -32,7 +33,7 @@ from .solver import solve_unsteady
 from .time_steppers import RKMethods, create_stepper, ode_method_cache, timestep_
 
 __all__ = ["AbstractFilter", "FaceAverage", "VolumeAverage", "reconstruct", "reconstruct_", "lesdatagen", "filtersaver", "create_les_data",
-           "create_io_arrays", "wrappedclosure", "collocate", "decollocate", "cnn", "tensorclosure", "create_dataloader_prior", "create_dataloader_post",
+           "create_les_data_ensemble", "create_io_arrays", "wrappedclosure", "collocate", "decollocate", "cnn", "tensorclosure", "create_dataloader_prior", "create_dataloader_post",
            "create_loss_prior", "create_relerr_prior", "create_loss_post", "create_relerr_post", "train"]
 
 
@@ -98,6 +99,27 @@ class AbstractFilter:
         sfx, pu, pv = _filter_ptrs(dns, u, setup_les, v, "Φ(v, u, …)")
         _lib.call(f"ins_filter_{self._entry}_{sfx}", setup_les.handle, dns.handle, int(comp), pu, pv, setup_les.stream)
         return v
+
+    def members(self, V, U, setup_les, comp, setup_dns=None):
+        """`Φ(V[b], U[b], setup_les, comp)` for every member of the ensemble fields `U` (fine) and `V` (coarse), both `(B,) + N + (D,)` as `vectorfields`
+        makes them, in ONE launch (`ins_filter_{face,volume}_members_f64`): member b is bitwise what the per-member call gives, only `Iu[α]` of every
+        `V[b]` is written.  A state and its right-hand side that share a buffer (`UF = vectorfields(dns, 2 * B)`) are filtered by one call.  float64, 2-D;
+        float32 tensors: TypeError, 3-D grids: NotImplementedError, both naming the per-member call.  Returns V."""
+        from .time_steppers import _member_stride
+
+        per_member = f"filter each member with {type(self).__name__}()(V[b], U[b], setup_les, comp)"
+        if _is32(U) or _is32(V):
+            raise TypeError(f"Φ.members(V, U, …): the member form of the filters runs float64 fields; {per_member} (float32 fields take the `_f32` kernels there)")
+        dns = setup_dns or dns_setup_of(setup_les, int(comp))
+        ustride = _member_stride(dns, U)
+        vstride = _member_stride(setup_les, V, U.shape[0])
+        lib = _lib.load()
+        rc = getattr(lib, f"ins_filter_{self._entry}_members_f64")(setup_les.handle, dns.handle, int(comp), int(U.shape[0]), U.data_ptr(), ustride,
+                                                                  V.data_ptr(), vstride, setup_les.stream)
+        if rc == -4:  # INS_ERR_UNSUPPORTED: a 3-D grid, a volume average on a non-periodic grid
+            raise NotImplementedError(f"Φ.members(V, U, …): {lib.ins_last_error().decode()}; {per_member}")
+        _lib.check(rc)
+        return V
 
     def pullback_(self, ubar, w, setup_les, comp, setup_dns=None):
         """ubar = Φᵀ w over the whole padded fine array."""
@@ -274,6 +296,133 @@ def create_les_data(*, D, Re, lims, nles, ndns, filters, tburn, tsim, savefreq, 
     _, outputs = solve_unsteady(setup=dns, ustart=u, docopy=False, tlims=(0.0, tsim), Δt=Δt, method=method, psolver=psolver, cache=cache,
                                 processors={**processors, "f": saver})
     return outputs["f"]
+
+
+_PER_SEED = "call create_les_data once per seed ([create_les_data(…, rng=rng) for _ in range(ntrajectory)])"
+
+
+def _les_ensemble_refusal(D, Δt, nles, ndns, extra):
+    """Why `create_les_data_ensemble` does not take this problem (None: it does).  Host-side facts only: no setup exists yet."""
+    if Δt is None:
+        return "Δt=None (an adaptive step differs from member to member; the ensemble loop shares one fixed Δt)"
+    if D != 2:
+        return f"D = {D} (the ensemble loop and the member filters are 2-D)"
+    for name, n in [("ndns", ndns)] + [("nles", n) for n in nles]:
+        if n != int(n) or n < 16 or n > 1024 or int(n) & (int(n) - 1):
+            return f"{name} = {n} (sides must be powers of two in 16 .. 1024: others solve through rocFFT)"
+    extra = dict(extra)
+    dtype = extra.pop("dtype", torch.float64)
+    if dtype != torch.float64:
+        return f"dtype = {dtype} (the ensemble loop is fp64)"
+    if extra.pop("processors", None):
+        return "extra processors (they observe one state; the ensemble has B)"
+    if extra.pop("create_psolver", None) is not None:
+        return "create_psolver (the ensemble loop runs on psolver_spectral)"
+    if extra:
+        return f"the Setup keyword(s) {', '.join(sorted(extra))} (the ensemble loop runs the plain all-periodic setup: no body force, closure or other sides)"
+    return None
+
+
+def create_les_data_ensemble(*, ntrajectory, D, Re, lims, nles, ndns, filters, tburn, tsim, savefreq, Δt, method=None, icfunc=None, rng=None, filenames=None,
+                             device=None, **kwargs):
+    """`[create_les_data(…, rng=rng) for _ in range(ntrajectory)]` with all trajectories advanced and filtered together (2-D periodic, fp64, fixed Δt): one
+    `EnsembleCache` on the DNS grid and one per LES grid, the call pattern of `solve_unsteady` with a fixed Δt (burn-in in one `timesteps_ensemble_` call,
+    then calls of `savefreq` steps; the initial state is saved first; `t` accumulates as `timesteps_` accumulates it), and at every save one
+    `ensemble_rhs_` on the DNS grid and, per (filter, LES grid) pair, LES grid fastest: ONE member-filter launch for `u` and `F` of all members, the member
+    ghost fill of ū, `ensemble_rhs_` on the LES cache, one subtraction and one device-to-host copy each of ū and c for the whole ensemble.  The launch count
+    per save does not depend on `ntrajectory`.
+    The initial fields are `icfunc(dns, psolver, rng)` in member order (default: that of `create_les_data`), so with an identically seeded `rng` member b
+    is the b-th of the consecutive `create_les_data` calls: `u` and `t` bitwise, `c` to the rounding of the fused right-hand side.
+    Returns a list over members of what `create_les_data` returns (a list of `dict(u, c, t, comptime)` per pair; `comptime` is the whole ensemble's);
+    `filenames`: one list per member.  Everything outside the ensemble loop — Δt=None, D=3, a side that is no power of two in 16 .. 1024,
+    dtype=torch.float32, processors, any `Setup` keyword — is refused (NotImplementedError) before any launch, naming `create_les_data` per seed."""
+    from .setup import vectorfields
+    from .time_steppers import LMWray3, EnsembleCache, ensemble_apply_bc_u_, ensemble_rhs_, timesteps_ensemble_
+
+    nles, filters = list(nles), list(filters)
+    why = _les_ensemble_refusal(D, Δt, nles, ndns, kwargs)
+    if why is not None:
+        raise NotImplementedError(f"create_les_data_ensemble: {why} is outside the ensemble route; {_PER_SEED}")
+    B = int(ntrajectory)
+    if B < 1:
+        raise ValueError("an ensemble has at least one member")
+    compression = [ndns // n for n in nles]
+    if any(c * n != ndns for c, n in zip(compression, nles)):
+        raise ValueError("every nles must divide ndns")
+    npair = len(nles) * len(filters)
+    if filenames is not None and (len(filenames) != B or any(len(f) != npair for f in filenames)):
+        raise ValueError("one list of file names per member, each with one name per (LES grid, filter) pair")
+    method = method or RKMethods.RK44()
+    c_last = 1.0 if isinstance(method, LMWray3) else method.c[-1]  # as timesteps_ advances t
+    rng = rng if rng is not None else np.random.default_rng()
+    dns = Setup(x=tuple(np.linspace(lims[0], lims[1], ndns + 1) for _ in range(D)), Re=Re, device=device)
+    les = [Setup(x=tuple(np.linspace(lims[0], lims[1], n + 1) for _ in range(D)), Re=Re, device=device) for n in nles]
+    psolver = default_psolver(dns)
+    psolver_les = [default_psolver(s) for s in les]
+    if icfunc is None:
+        def icfunc(setup, psolver, rng):
+            return random_field(setup, 0.0, psolver=psolver, seed=int(rng.integers(2**31 - 1)))
+    # the state and its right-hand side share one buffer and one stride, so one filter launch serves both: members 0 .. B-1 are u, B .. 2B-1 are F
+    UF = vectorfields(dns, 2 * B)
+    U, F = UF[:B], UF[B:]
+    for b in range(B):
+        U[b].copy_(icfunc(dns, psolver, rng))
+    if bool(torch.isnan(U).any()):
+        print("Warning: initial conditions contain NaNs")
+    try:
+        cache = EnsembleCache(method, dns, psolver, B)
+        cache_les = [EnsembleCache(method, s, ps, B) for s, ps in zip(les, psolver_les)]
+    except NotImplementedError as e:
+        raise NotImplementedError(f"create_les_data_ensemble: {e}; {_PER_SEED}") from None
+    if tburn > 0:  # solve_unsteady without processors: one native call
+        nstep = int(round(tburn / Δt))
+        timesteps_ensemble_(cache, U, 0.0, tburn / nstep, nstep)
+    VF = [vectorfields(s, 2 * B) for s in les]  # ū = VF[:B], ΦF = VF[B:]
+    FΦ = [vectorfields(s, B) for s in les]
+    cbuf = [vectorfields(s, B) for s in les]
+    pairs = [(Φ, i) for Φ in filters for i in range(len(les))]
+    saved = [dict(u=[], c=[]) for _ in pairs]
+    ts = []
+    comptime = time.time()
+
+    def save(t):
+        ensemble_rhs_(cache, F, U)
+        for q, (Φ, i) in enumerate(pairs):
+            Φ.members(VF[i], UF, les[i], compression[i], setup_dns=dns)
+            ū, ΦF = VF[i][:B], VF[i][B:]
+            ensemble_apply_bc_u_(cache_les[i], ū)
+            ensemble_rhs_(cache_les[i], FΦ[i], ū)
+            torch.sub(ΦF, FΦ[i], out=cbuf[i])
+            saved[q]["u"].append(ū.cpu().numpy())
+            saved[q]["c"].append(cbuf[i].cpu().numpy())
+        ts.append(t)
+
+    # solve_unsteady with the saver as its one processor: the steps between the multiples of savefreq run as one native call
+    nstep = int(round(tsim / Δt))
+    Δt = tsim / nstep
+    g = 1 if int(savefreq) <= 1 or os.environ.get("INS_NO_PROCESSOR_BATCH") else int(savefreq)
+    t, n, done = 0.0, 0, 0
+    save(t)
+    while done < nstep:
+        k = min(g - (n % g), nstep - done)
+        timesteps_ensemble_(cache, U, t, Δt, k)
+        t = t + k * c_last * Δt if k > 1 else t + c_last * Δt
+        n += k
+        done += k
+        if n % savefreq == 0:
+            save(t)
+    comptime = time.time() - comptime
+    out = []
+    for b in range(B):
+        member = []
+        for q in range(len(pairs)):
+            r = dict(u=np.stack([np.asfortranarray(a[b]) for a in saved[q]["u"]], axis=-1),
+                     c=np.stack([np.asfortranarray(a[b]) for a in saved[q]["c"]], axis=-1), t=np.array(ts), comptime=comptime)
+            if filenames is not None:
+                np.savez(filenames[b][q], **r)
+            member.append(r)
+        out.append(member)
+    return out
 
 
 def create_io_arrays(data, setup):

@@ -447,27 +447,33 @@ class EnsembleCache:
 
 def _ensemble_ustride(cache, U):
     """Member stride of `U` in elements after the type, shape, stride and device checks of `timesteps_ensemble_` (host-side facts of `U` and `cache` only)."""
+    if not isinstance(cache, EnsembleCache):
+        raise TypeError("timesteps_ensemble_ needs an EnsembleCache")
+    return _member_stride(cache.setup, U, cache.B)
+
+
+def _member_stride(setup, U, B=None):
+    """Member stride in elements of the ensemble field `U` of `setup` after the type, shape, stride and device checks (host-side facts only).  `B`: the
+    number of members the caller's cache was created for (None: any)."""
     import torch
 
     from .setup import _fortran_strides
 
-    if not isinstance(cache, EnsembleCache):
-        raise TypeError("timesteps_ensemble_ needs an EnsembleCache")
     if not isinstance(U, torch.Tensor) or U.dtype != torch.float64:
         raise TypeError("ensemble fields must be float64 torch tensors (vectorfields)")
-    g = cache.setup.grid
+    g = setup.grid
     shape = g.N + (g.dimension,)
     if U.dim() != len(shape) + 1 or tuple(U.shape[1:]) != shape:
         raise ValueError(f"ensemble field must have shape (B,) + {shape} (use vectorfields), got {tuple(U.shape)}")
-    if U.shape[0] != cache.B:
-        raise ValueError(f"ensemble field has {U.shape[0]} members, the cache was created for B = {cache.B}")
+    if B is not None and U.shape[0] != B:
+        raise ValueError(f"ensemble field has {U.shape[0]} members, the cache was created for B = {B}")
     if tuple(U.stride()[1:]) != _fortran_strides(shape):
         raise ValueError("every member U[b] must have the column-major strides of vectorfield(setup) (use vectorfields)")
     ncomp = int(np.prod(shape))
     if U.shape[0] > 1 and U.stride(0) < ncomp:
         raise ValueError(f"members overlap: stride {U.stride(0)} between members is shorter than a vector field ({ncomp})")
-    if U.device != cache.setup.device:
-        raise ValueError(f"ensemble field lives on {U.device}, setup on {cache.setup.device}")
+    if U.device != setup.device:
+        raise ValueError(f"ensemble field lives on {U.device}, setup on {setup.device}")
     return int(U.stride(0)) if U.shape[0] > 1 else ncomp
 
 
@@ -485,6 +491,42 @@ def timesteps_ensemble_(cache, U, t, Δt, nsteps):
     rc = lib.ins_rk_ensemble_steps_f64(cache.handle, 1.0 / setup.Re, C.c_void_p(U.data_ptr()), ustride, float(t), float(Δt), nsteps, setup.stream)
     if rc == -4:
         raise NotImplementedError(f"timesteps_ensemble_: {lib.ins_last_error().decode()}; {_PER_MEMBER}")
+    _lib.check(rc)
+    return U
+
+
+_PER_MEMBER_RHS = ("form it per member: apply_bc_u_(project_(apply_bc_u_(momentum_(F[b], U[b], None, t, setup), t, setup, dudt=True), setup, psolver, p), "
+                   "t, setup)")
+
+
+def ensemble_rhs_(cache, F, U):
+    """The projected right-hand side of every member, `F[b] = apply_bc_u_(project_(apply_bc_u_(momentum_(U[b]), dudt=True)))`, as ONE native call
+    (`ins_rk_ensemble_rhs_f64`): the `F` that `filtersaver` forms on the DNS grid and `lesdatagen` on the LES grid, in the launches of a single field
+    whatever B is.  `U` is read only and has valid ghost volumes (`timesteps_ensemble_` leaves them so; `ensemble_apply_bc_u_` fills them); `F` and `U`
+    pass the checks of `timesteps_ensemble_`.  Agrees with the per-member chain to rounding; member b is bitwise what a cache with B = 1 gives.
+    Returns F."""
+    ustride = _ensemble_ustride(cache, U)
+    fstride = _ensemble_ustride(cache, F)
+    if F.data_ptr() == U.data_ptr():
+        raise ValueError("ensemble_rhs_ cannot run in place: F and U are the same array")
+    setup = cache.setup
+    lib = _lib.load()
+    rc = lib.ins_rk_ensemble_rhs_f64(cache.handle, 1.0 / setup.Re, C.c_void_p(U.data_ptr()), ustride, C.c_void_p(F.data_ptr()), fstride, setup.stream)
+    if rc == -4:
+        raise NotImplementedError(f"ensemble_rhs_: {lib.ins_last_error().decode()}; {_PER_MEMBER_RHS}")
+    _lib.check(rc)
+    return F
+
+
+def ensemble_apply_bc_u_(cache, U):
+    """`apply_bc_u_` of every member of `U` on the periodic box of `cache`, in place, in two launches (`ins_rk_ensemble_apply_bc_u_f64`): for members whose
+    interior something other than the stepper wrote (the member filters write `Iu[α]` only).  Returns U."""
+    ustride = _ensemble_ustride(cache, U)
+    setup = cache.setup
+    lib = _lib.load()
+    rc = lib.ins_rk_ensemble_apply_bc_u_f64(cache.handle, C.c_void_p(U.data_ptr()), ustride, setup.stream)
+    if rc == -4:
+        raise NotImplementedError(f"ensemble_apply_bc_u_: {lib.ins_last_error().decode()}; call apply_bc_u_(U[b], t, setup) per member")
     _lib.check(rc)
     return U
 

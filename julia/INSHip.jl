@@ -418,6 +418,20 @@ function reconstruct!(u::RA, v::RA, setup_dns, setup_les, comp)           # filt
                 handle(setup_dns), handle(setup_les), Cint(comp), pointer(v), pointer(u), stream()))
     u
 end
+# The filters for an ensemble of 2-D fields in one launch: `U` is (N_dns..., 2, B), `V` (N_les..., 2, B), members along the last axis (column-major, so
+# member b lies stride(U, 4) elements behind member b - 1).  Member b of V is bitwise `Φ(V[:, :, :, b], U[:, :, :, b], …)`; only Iu[α] is written.
+function filter_members!(::FaceAverage, V::RA, U::RA, setup_les, comp; setup_dns)
+    check(ccall((:ins_filter_face_members_f64, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                handle(setup_les), handle(setup_dns), Cint(comp), Cint(size(U, 4)), pointer(U), Int64(stride(U, 4)), pointer(V), Int64(stride(V, 4)), stream()))
+    V
+end
+function filter_members!(::VolumeAverage, V::RA, U::RA, setup_les, comp; setup_dns)
+    check(ccall((:ins_filter_volume_members_f64, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                handle(setup_les), handle(setup_dns), Cint(comp), Cint(size(U, 4)), pointer(U), Int64(stride(U, 4)), pointer(V), Int64(stride(V, 4)), stream()))
+    V
+end
 # ubar = Φᵀ w over the whole padded fine array (the reference has no filter rrule)
 function filter_pullback!(::FaceAverage, ubar::RA, w::RA, setup_les, comp; setup_dns)
     check(ccall((:ins_filter_face_pullback_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
@@ -578,6 +592,39 @@ function native!(cache::HipRKCache, method, setup, psolver)
                 handle(setup), psolver.h, ns, A, c, h))
     cache.psolver = psolver
     cache.h = h[]
+end
+# Ensembles of 2-D periodic flows (csrc/ins_rk_ensemble.hip): B members of one setup, U = (N..., 2, B), in the launches of a single field.  The handle owns
+# the B-fold work arrays; `setup` and `psolver` must outlive it.  Anything outside the chained 2-D loop is refused by the library (`check` raises its message).
+mutable struct HipEnsembleCache
+    h::Ptr{Cvoid}
+    setup::Any
+    psolver::Any
+    B::Int
+end
+function ensemble_cache(method::ExplicitRungeKuttaMethod, setup::ROCSetup, psolver, B)
+    A = collect(transpose(Float64.(method.A)))
+    c = Float64.(method.c)
+    h = Ref{Ptr{Cvoid}}()
+    check(ccall((:ins_rk_ensemble_create, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+                handle(setup), psolver.h, Cint(length(method.b)), A, c, Cint(B), h))
+    cache = HipEnsembleCache(h[], setup, psolver, B)
+    finalizer(x -> ccall((:ins_rk_ensemble_destroy, lib), Cint, (Ptr{Cvoid},), x.h), cache)
+end
+function timesteps_ensemble!(cache::HipEnsembleCache, U::RA, t, Δt, nsteps)
+    check(ccall((:ins_rk_ensemble_steps_f64, lib), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Float64}, Int64, Cdouble, Cdouble, Cint, Ptr{Cvoid}),
+                cache.h, 1 / cache.setup.Re, pointer(U), Int64(stride(U, 4)), t, Δt, Cint(nsteps), stream()))
+    U
+end
+# F[:, :, :, b] = apply_bc_u!(project!(apply_bc_u!(momentum!(U[:, :, :, b]); dudt = true))) for every member: the F of filtersaver / lesdatagen
+function ensemble_rhs!(cache::HipEnsembleCache, F::RA, U::RA)
+    check(ccall((:ins_rk_ensemble_rhs_f64, lib), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                cache.h, 1 / cache.setup.Re, pointer(U), Int64(stride(U, 4)), pointer(F), Int64(stride(F, 4)), stream()))
+    F
+end
+function ensemble_apply_bc_u!(cache::HipEnsembleCache, U::RA)
+    check(ccall((:ins_rk_ensemble_apply_bc_u_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                cache.h, pointer(U), Int64(stride(U, 4)), stream()))
+    U
 end
 # ins_temperature_desc_t (include/ins_hip.h): the scalars of `temperature_equation` (setup.jl:48-87) the native stage loop needs
 struct TempDesc
