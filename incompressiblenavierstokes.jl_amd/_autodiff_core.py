@@ -14,6 +14,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from ._step_route import Closure, Force, classify, mark_ad_closure, mark_library_closure, smagorinsky_of
 from .setup import _fortran_strides
 from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
 
@@ -352,8 +353,7 @@ def smagorinsky_closure(ops, setup):
         τ = apply_bc_p_fields(lambda p, t, s: _ApplyBCP.apply(p, t, s, ops), _TensorClosureStress.apply(u, a, setup, ops), 0.0, setup)
         return _DivOfTensor.apply(τ, setup, ops)
 
-    closure._ad_smagorinsky = (ops.name, setup)  # `timesteps` takes it for the closure of its native loops (not `_ins_closure`: the step functions route on that)
-    return closure
+    return mark_ad_closure(closure, ops.name, setup)  # `timesteps` takes it for the closure of its native loops (the step functions do not route on it)
 
 
 class _SmagorinskyForce(torch.autograd.Function):
@@ -384,23 +384,13 @@ def smagorinsky_force(ops, u, θ, setup):
     return _SmagorinskyForce.apply(u, θ, setup, ops)
 
 
-def smagorinsky_of(setup, name, dtype):
-    """True when `setup.closure_model` is the library's Smagorinsky closure of this setup in the precision `dtype`: the fused one
-    (`smagorinsky_closure` / `smagorinsky_closure32`) or the differentiable one of the module `name` (`ad` / `ad32`)."""
-    m = setup.closure_model
-    if getattr(m, "_ins_closure", None) == "smagorinsky" and getattr(m, "_ins_setup", None) is setup and getattr(m, "_ins_dtype", None) == dtype:
-        return True
-    tag = getattr(m, "_ad_smagorinsky", None)
-    return tag is not None and tag[0] == name and tag[1] is setup
-
-
 class native_closure:
     """While a rollout's native forward runs: `setup.closure_model` carries the tags on which `timesteps_` / `timesteps32_` put the Smagorinsky
     closure into the native stage loop.  The fused closure has them; the differentiable one is replaced, for the duration, by a stand-in made by
     `make(setup)` on first use and kept on the setup."""
 
     def __init__(self, setup, θ, make):
-        self.setup, self.on, self.make = setup, θ is not None and getattr(setup.closure_model, "_ins_closure", None) != "smagorinsky", make
+        self.setup, self.on, self.make = setup, θ is not None and classify(setup).closure is not Closure.LIBRARY, make
 
     def __enter__(self):
         if self.on:
@@ -414,8 +404,7 @@ class native_closure:
                         real.append(self.make(s))
                     return real[0](u, θ)
 
-                closure._ins_closure, closure._ins_setup = "smagorinsky", s
-                s._ad_native_closure = closure
+                s._ad_native_closure = mark_library_closure(closure, s)
             s.closure_model = s._ad_native_closure
 
     def __exit__(self, *exc):
@@ -580,6 +569,49 @@ class _TimeSteps(torch.autograd.Function):
         if θbar is not None:
             θbar = θbar.to(dtype=ctx.θlike[0], device=ctx.θlike[1])
         return ubar, tempbar, θbar, None, None, None, None, None, None
+
+
+# module, dtype name and pressure solvers of the two precision tables, for the messages that send a caller to the other one
+_PRECISIONS = {torch.float64: ("ad", "float64", "default_psolver and its kin"), torch.float32: ("ad32", "float32", "f32.default_psolver32 / f32.psolver_wrap32")}
+
+
+def check_rollout(ops, stepper, θ):
+    """What `ad.timesteps` and `ad32.timesteps` refuse alike.  The first check that applies names the reason, in this order:
+      TypeError            `u` of another dtype; `temp` of another dtype than `u`; a pressure solver of the other precision
+      ValueError           a temperature field without a temperature equation
+      NotImplementedError  a closure model other than the library's Smagorinsky closure of this setup with its θ (or θ without one); a temperature
+                           equation without a field; a slab side; callable velocity data; callable temperature data; an unsteady body force
+    What one precision adds comes after this list, the shape ValueErrors of the fields last.  The setup is classified (`_step_route.classify`) once
+    the types are right: a stepper of the wrong precision is turned away whatever its setup is."""
+    from . import f32
+
+    setup, psolver, u, temp = stepper.setup, stepper.psolver, stepper.u, stepper.temp
+    (name, dt, solvers), (other, odt, osolvers) = _PRECISIONS[ops.dtype], _PRECISIONS[torch.float32 if ops.dtype == torch.float64 else torch.float64]
+    if u.dtype != ops.dtype:
+        raise TypeError(f"{name}.timesteps: fields must be {dt} torch tensors ({odt} fields: {other}.timesteps)")
+    if temp is not None and temp.dtype != ops.dtype:
+        raise TypeError(f"{name}.timesteps: a {dt} u with a {odt} temp: give both fields in one precision")
+    if isinstance(psolver, f32.psolver_spectral32) != (ops.dtype == torch.float32):
+        raise TypeError(f"{name}.timesteps: a {dt} u with a {odt} psolver ({dt} fields: {solvers}; {odt} fields: {other}.timesteps with {osolvers})")
+    if temp is not None and setup.temperature is None:
+        raise ValueError("a temperature field needs setup.temperature (temperature_equation)")
+    facts = classify(setup, temp, θ)
+    stepwise = f"use {name}.timestep step by step"
+    if (facts.closure is not Closure.NONE or θ is not None) and not (θ is not None and smagorinsky_of(facts, name, ops.dtype)):
+        raise NotImplementedError(f"{name}.timesteps: a closure model is not part of the native reverse loop; {stepwise}")
+    if temp is None and setup.temperature is not None:
+        raise NotImplementedError(f"{name}.timesteps: a setup with a temperature equation takes stepper.temp in the native reverse loop; without one "
+                                  f"{stepwise}")
+    # the rest the Float32 family does not run at all: its step-by-step route is the fp64 one
+    if facts.slab:
+        raise NotImplementedError(f"{name}.timesteps: slab (halo) setups are not supported; use ad.timestep step by step")
+    if facts.bc_u_callable:
+        raise NotImplementedError(f"{name}.timesteps: callable Dirichlet data needs the host between the stages; use ad.timestep step by step")
+    if temp is not None and facts.bc_temp_callable:
+        raise NotImplementedError(f"{name}.timesteps: callable Dirichlet data of the temperature needs the host between the stages; use ad.timestep step "
+                                  "by step")
+    if facts.force is Force.UNSTEADY:
+        raise NotImplementedError(f"{name}.timesteps: an unsteady body force is evaluated in fp64 on the host; use ad.timestep step by step")
 
 
 def checkpoint_interval(ops, nsteps, checkpoint_every):

@@ -22,7 +22,7 @@ import torch
 
 from . import _autodiff_core as core
 from . import operators as O
-from .boundary_conditions import DirichletBC
+from ._step_route import Closure, Force, classify, steady_force
 from .pressure import project_, project_pullback_
 from .setup import _alloc, scalarfield, vectorfield
 from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
@@ -92,7 +92,7 @@ def _rk_step_pullback_(adj, ubar, tempbar, ustart, tempstart, Δt):
     from .time_steppers import _temperature_desc
 
     setup = adj.setup
-    f = setup.bodyforce if (setup.bodyforce is not None and setup.issteadybodyforce) else None
+    f = steady_force(setup)
     fp = setup.ptr(f, True) if f is not None else None
     if tempbar is None:
         _lib.call("ins_rk_step_pullback_f64", adj._handle, 1.0 / setup.Re, setup.ptr(ustart, True), fp, float(Δt), setup.ptr(ubar, True), setup.stream)
@@ -432,9 +432,7 @@ def smagorinsky_force(u, θ, setup):
     """The Smagorinsky closure force `smagorinsky_closure(setup)(u, θ)` of a ghost-filled `u` (operators.jl:1284-1300) as ONE native call, with the
     fused pullback as backward (csrc/ins_smagpullback_kernels.h): ubar, and for a 0-dim tensor θ that requires grad θbar = 2θ <σ̄, σ̂>, which falls
     out of the same pass.  The same function of (u, θ) as `ad.smagorinsky_closure(setup)`, without its per-stage tensor-basis fields."""
-    from .boundary_conditions import HaloBC
-
-    if any(isinstance(bc, HaloBC) for side in setup.boundary_conditions for bc in side):
+    if classify(setup).slab:
         raise NotImplementedError("ad.smagorinsky_force: slab (halo) setups are not supported")
     return core.smagorinsky_force(_OPS, u, θ, setup)
 
@@ -447,11 +445,10 @@ def timestep(method, stepper, Δt, θ=None):
     setup, temp = stepper.setup, stepper.temp
     if temp is not None and setup.temperature is None:
         raise ValueError("a temperature field needs setup.temperature (temperature_equation)")
-    m = setup.closure_model
-    if m is not None and getattr(m, "_ins_closure", None) == "smagorinsky" and torch.is_grad_enabled():
+    facts = classify(setup, temp, θ)
+    if facts.closure is Closure.LIBRARY and torch.is_grad_enabled():
         raise NotImplementedError("ad.timestep: the Smagorinsky closure has no pullback; give the closure as a torch function m(u, θ)")
-    tempplanes = temp is not None and any(isinstance(bc, DirichletBC) and callable(bc.u) for side in setup.temperature.boundary_conditions for bc in side)
-    if isinstance(method, LMWray3) and (setup.needs_bc_planes or tempplanes or (setup.bodyforce is not None and not setup.issteadybodyforce)):
+    if isinstance(method, LMWray3) and (facts.bc_u_callable or (facts.has_temp and facts.bc_temp_callable) or facts.force is Force.UNSTEADY):
         # the native step runs the low-storage loop then (step_lmwray3.jl), whose ghost fills happen at other times than the ERK form's
         raise NotImplementedError("ad.timestep: LMWray3 with time-dependent boundary data or body force; use an ExplicitRungeKuttaMethod")
     return core.timestep(_OPS, method, stepper, Δt, θ)
@@ -479,33 +476,7 @@ def timesteps(method, stepper, Δt, nsteps, *, θ=None, checkpoint_every=None):
     callable boundary data, an unsteady body force and slab setups raise NotImplementedError: use `ad.timestep` step by step.  Float32 fields:
     `ad32.timesteps`."""
     nsteps, every = core.checkpoint_interval(_OPS, nsteps, checkpoint_every)
-    setup, psolver, u, temp = stepper.setup, stepper.psolver, stepper.u, stepper.temp
-    if u.dtype == torch.float32:
-        raise TypeError("ad.timesteps: fields must be float64 torch tensors (float32 fields: ad32.timesteps)")
-    if u.dtype != torch.float64:
-        raise TypeError("ad.timesteps: fields must be float64 torch tensors")
-    if temp is not None and temp.dtype != torch.float64:
-        raise TypeError("ad.timesteps: a float64 u with a float32 temp: give both fields in one precision")
-    from . import f32
-    from .boundary_conditions import HaloBC
-
-    if isinstance(psolver, f32.psolver_spectral32):
-        raise TypeError("ad.timesteps: a float64 u with a float32 psolver (float32 fields: ad32.timesteps with f32.default_psolver32 / f32.psolver_wrap32; "
-                        "float64 fields: default_psolver and its kin)")
-    if temp is not None and setup.temperature is None:
-        raise ValueError("a temperature field needs setup.temperature (temperature_equation)")
-    if (setup.closure_model is not None or θ is not None) and not (θ is not None and core.smagorinsky_of(setup, "ad", torch.float64)):
-        raise NotImplementedError("ad.timesteps: a closure model is not part of the native reverse loop; use ad.timestep step by step")
-    if temp is None and setup.temperature is not None:
-        raise NotImplementedError("ad.timesteps: a setup with a temperature equation takes stepper.temp in the native reverse loop; without one use "
-                                  "ad.timestep step by step")
-    if setup.needs_bc_planes:
-        raise NotImplementedError("ad.timesteps: callable Dirichlet data needs the host between the stages; use ad.timestep step by step")
-    if temp is not None and any(isinstance(bc, DirichletBC) and callable(bc.u) for side in setup.temperature.boundary_conditions for bc in side):
-        raise NotImplementedError("ad.timesteps: callable Dirichlet data of the temperature needs the host between the stages; use ad.timestep step by step")
-    if setup.bodyforce is not None and not setup.issteadybodyforce:
-        raise NotImplementedError("ad.timesteps: an unsteady body force is evaluated on the host; use ad.timestep step by step")
-    if any(isinstance(bc, HaloBC) for side in setup.boundary_conditions for bc in side):
-        raise NotImplementedError("ad.timesteps: slab (halo) setups are not supported; use ad.timestep step by step")
+    setup, u, temp = stepper.setup, stepper.u, stepper.temp
+    core.check_rollout(_OPS, stepper, θ)
     _check_f64(setup, u, *(() if temp is None else (temp,)))
     return core.timesteps(_OPS, method, stepper, Δt, nsteps, every, θ=θ)

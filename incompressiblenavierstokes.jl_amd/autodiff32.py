@@ -40,24 +40,26 @@ import torch
 
 from . import _autodiff_core as core
 from . import f32 as F32
-from .boundary_conditions import HaloBC, PeriodicBC
+from ._step_route import Closure, Force, classify
+from .boundary_conditions import PeriodicBC
 
 __all__ = ["apply_bc_u", "momentum", "project", "timestep"]  # `timesteps` and the operators below are module attributes (an existing test pins this list)
 
 
 def _check_slab(setup, what):
-    if any(isinstance(bc, HaloBC) for side in setup.boundary_conditions for bc in side):
+    facts = classify(setup)
+    if facts.slab:
         raise NotImplementedError(f"ad32.{what}: slab (halo) setups run in fp64 only")
+    return facts
 
 
 def _check_setup(setup, what):
-    _check_slab(setup, what)
-    if setup.needs_bc_planes:
+    facts = _check_slab(setup, what)
+    if facts.bc_u_callable:
         raise NotImplementedError(f"ad32.{what}: the _f32 family takes constant boundary data (callable DirichletBC values: use ins_amd.ad)")
-    if setup.bodyforce is not None and not setup.issteadybodyforce:
+    if facts.force is Force.UNSTEADY:
         raise NotImplementedError(f"ad32.{what}: an unsteady body force is evaluated in fp64 on the host (use ins_amd.ad)")
-    m = setup.closure_model
-    if m is not None and getattr(m, "_ins_closure", None) == "smagorinsky":
+    if facts.closure is Closure.LIBRARY:
         raise NotImplementedError(f"ad32.{what}: the fused Smagorinsky closure is fp64 and has no pullback; use ad32.smagorinsky_closure(setup), "
                                   "or give the closure as a torch function m(u, θ)")
 
@@ -358,28 +360,7 @@ def timesteps(method, stepper, Δt, nsteps, *, θ=None, checkpoint_every=None):
     step by step (or `ins_amd.ad`)."""
     nsteps, every = core.checkpoint_interval(_OPS, nsteps, checkpoint_every)
     setup, psolver, u, temp = stepper.setup, stepper.psolver, stepper.u, stepper.temp
-    if u.dtype != torch.float32:
-        raise TypeError("ad32.timesteps: fields must be float32 torch tensors (float64 fields: ad.timesteps)")
-    if temp is not None and temp.dtype != torch.float32:
-        raise TypeError("ad32.timesteps: a float32 u with a float64 temp: give both fields in one precision")
-    if not isinstance(psolver, F32.psolver_spectral32):
-        raise TypeError("ad32.timesteps: a float32 u with a float64 psolver (float32 fields: f32.default_psolver32 / f32.psolver_wrap32; "
-                        "float64 fields: ad.timesteps with default_psolver and its kin)")
-    if temp is not None and setup.temperature is None:
-        raise ValueError("a temperature field needs setup.temperature (temperature_equation)")
-    if (setup.closure_model is not None or θ is not None) and not (θ is not None and core.smagorinsky_of(setup, "ad32", torch.float32)):
-        raise NotImplementedError("ad32.timesteps: a closure model is not part of the native reverse loop; use ad32.timestep step by step")
-    if temp is None and setup.temperature is not None:
-        raise NotImplementedError("ad32.timesteps: a setup with a temperature equation takes stepper.temp in the native reverse loop; without one use "
-                                  "ad32.timestep step by step")
-    if any(isinstance(bc, HaloBC) for side in setup.boundary_conditions for bc in side):
-        raise NotImplementedError("ad32.timesteps: slab (halo) setups run in fp64 only; use ad.timestep step by step")
-    if setup.needs_bc_planes:
-        raise NotImplementedError("ad32.timesteps: the _f32 family takes constant boundary data; use ad.timestep step by step")
-    if temp is not None and any(callable(getattr(bc, "u", None)) for side in setup.temperature.boundary_conditions for bc in side):
-        raise NotImplementedError("ad32.timesteps: the _f32 family takes constant temperature boundary data; use ad.timestep step by step")
-    if setup.bodyforce is not None and not setup.issteadybodyforce:
-        raise NotImplementedError("ad32.timesteps: an unsteady body force is evaluated in fp64 on the host; use ad.timestep step by step")
+    core.check_rollout(_OPS, stepper, θ)
     _check_psolver(setup, psolver, "timesteps")
     if getattr(psolver, "psolver64", None) is not None and _periodic_uniform(setup):
         # measured on the 7 x 7 periodic box with a wrapped direct solver, 5 RK44 steps: timesteps32_ is 2.0e-3 from fp64, ad32.timestep 1.0e-7

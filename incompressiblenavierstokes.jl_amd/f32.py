@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._step_route import Closure, Force, classify, mark_library_closure
 from .setup import _fortran_strides
 
 
@@ -46,7 +47,7 @@ def _ptr(setup, f, ncomp):
 
 
 def _constant_bc_only(setup):
-    if setup.needs_bc_planes:
+    if classify(setup).bc_u_callable:
         raise NotImplementedError("the _f32 family takes constant boundary data (callable DirichletBC values: use the fp64 entry points)")
 
 
@@ -74,24 +75,15 @@ def momentum32_(F, u, setup, temp=None):
 
 # ---- temperature equation (csrc/ins_temp32.hip): the Float32 twins of operators.apply_bc_temp_ ... gravity_, constant boundary data
 def _temp_desc(setup):
-    """ins_temperature_desc_t of setup.temperature, built as time_steppers._native_ext builds it; callable Dirichlet data is refused."""
-    from .boundary_conditions import DirichletBC
-    from .time_steppers import _TempDesc
+    """ins_temperature_desc_t of setup.temperature (the one `time_steppers._temperature_desc` builds); callable Dirichlet data is refused."""
+    from .time_steppers import _temperature_desc
 
-    T = setup.temperature
-    if T is None:
+    if setup.temperature is None:
         raise ValueError("the setup has no temperature equation (Setup(temperature=temperature_equation(...)))")
-    desc = _TempDesc(a2=T.α2, a4=T.α4, diss_coef=setup.Re * T.α1 / T.γ, gdir=int(T.gdir), dodissipation=int(T.dodissipation))
-    for be in range(setup.grid.dimension):
-        for side in range(2):
-            bc = T.boundary_conditions[be][side]
-            desc.bc[2 * be + side] = bc.code
-            if isinstance(bc, DirichletBC) and bc.u is not None:
-                if callable(bc.u):
-                    raise NotImplementedError("the _f32 family takes constant boundary data (callable temperature DirichletBC values: use the fp64 "
-                                              "entry points)")
-                desc.val[2 * be + side] = float(bc.u)
-    return desc
+    if classify(setup).bc_temp_callable:
+        raise NotImplementedError("the _f32 family takes constant boundary data (callable temperature DirichletBC values: use the fp64 "
+                                  "entry points)")
+    return _temperature_desc(setup)
 
 
 def apply_bc_temp32_(temp, setup):
@@ -381,9 +373,7 @@ def smagorinsky_closure32(setup):
             σ = scratch["σ"]
         return smagorinsky_force32_(s, u, θ, setup, σ)
 
-    closure._ins_closure, closure._ins_setup = "smagorinsky", setup
-    closure._ins_dtype = torch.float32
-    return closure
+    return mark_library_closure(closure, setup, torch.float32)
 
 
 def max_abs_divergence32(u, setup, psolver):
@@ -468,24 +458,24 @@ def _set_force_closure32(cache, θ):
     """Hand the steady body force and the Smagorinsky closure of the cache's setup to its native handle; True if the extended loop is needed.
     What the Float32 stage loop does not run is refused: it would otherwise be dropped from the step without a word."""
     s = cache.setup
-    if s.bodyforce is not None and not s.issteadybodyforce:
+    facts = classify(s, None, θ)
+    if facts.force is Force.UNSTEADY:
         raise NotImplementedError("the _f32 family takes a steady body force (an unsteady one: the fp64 entry points, timestep_ / solve_unsteady)")
     f = s.bodyforce
     if getattr(cache, "_force_src", None) is not f:  # cast once per cache; the float32 field is kept alive here
         cache._force32 = to_f32(s, f) if f is not None else None
         _lib.call("ins_rk_set_bodyforce_f32", cache._handle, _ptr(s, cache._force32, s.grid.dimension) if f is not None else None)
         cache._force_src = f
-    m = s.closure_model
-    if m is None:
+    if facts.closure is Closure.NONE:
         kind, θ = 0, 0.0  # (a θ without a closure model has nothing to act on, as in timestep_)
     else:
-        if getattr(m, "_ins_closure", None) != "smagorinsky" or getattr(m, "_ins_setup", None) is not s:
+        if not facts.closure_mine:
             raise NotImplementedError("the _f32 stage loop runs the library's Smagorinsky closure of this setup (smagorinsky_closure / "
                                       "smagorinsky_closure32); another closure_model: the fp64 entry points, or ad32.timestep with a torch closure")
         if θ is None:
             raise NotImplementedError("the setup has a closure_model: give its parameter as θ= (a scalar); without one the closure would be dropped "
                                       "(fp64 entry points: timestep_(..., θ=θ))")
-        if not np.isscalar(θ):
+        if not facts.theta_scalar:
             raise NotImplementedError("the _f32 stage loop takes a scalar θ (a tensor θ: ad32.timestep with ad32.smagorinsky_closure)")
         kind, θ = 1, float(θ)
     if getattr(cache, "_closure", (0, 0.0)) != (kind, θ):
@@ -494,28 +484,27 @@ def _set_force_closure32(cache, θ):
     return f is not None or kind != 0
 
 
+def _steps32_(plain, ext, cache, u, Δt, nsteps, temp, θ):
+    """The body of both step functions: the entry `plain`, or with a temperature, a steady body force or the closure the entry `ext`; `nsteps`
+    (an argument of the multi-step entries only) as a tuple."""
+    s = cache.setup
+    ext_needed = _set_force_closure32(cache, θ)
+    if temp is None and not ext_needed:
+        _lib.call(plain, cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), float(Δt), *nsteps, s.stream)
+        return u
+    tp = _set_temperature32(cache, temp) if temp is not None else None
+    _lib.call(ext, cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), tp, float(Δt), *nsteps, s.stream)
+    return u if temp is None else (u, temp)
+
+
 def timestep32_(cache, u, Δt, temp=None, θ=None):
     """One explicit RK step of the float32 field `u` in place (step_explicit_runge_kutta.jl:4-59); with `temp` (a float32 scalar field; the setup has a
     temperature equation) the temperature is advanced with it and (u, temp) is returned.  A steady `setup.bodyforce` and the library's Smagorinsky
     `setup.closure_model` with the scalar parameter `θ` join every stage force (operators.jl:873-880, 1294-1305)."""
-    s = cache.setup
-    ext = _set_force_closure32(cache, θ)
-    if temp is None and not ext:
-        _lib.call("ins_rk_step_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), float(Δt), s.stream)
-        return u
-    tp = _set_temperature32(cache, temp) if temp is not None else None
-    _lib.call("ins_rk_step_ext_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), tp, float(Δt), s.stream)
-    return u if temp is None else (u, temp)
+    return _steps32_("ins_rk_step_f32", "ins_rk_step_ext_f32", cache, u, Δt, (), temp, θ)
 
 
 def timesteps32_(cache, u, Δt, nsteps, temp=None, θ=None):
     """`nsteps` explicit RK steps of size Δt of the float32 field `u` in place: the fixed-Δt loop of solve_unsteady (solver.jl:74-83) as one native call;
     with `temp` and `θ` as `timestep32_`."""
-    s = cache.setup
-    ext = _set_force_closure32(cache, θ)
-    if temp is None and not ext:
-        _lib.call("ins_rk_steps_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), float(Δt), int(nsteps), s.stream)
-        return u
-    tp = _set_temperature32(cache, temp) if temp is not None else None
-    _lib.call("ins_rk_steps_ext_f32", cache._handle, float(1.0 / s.Re), _ptr(s, u, s.grid.dimension), tp, float(Δt), int(nsteps), s.stream)
-    return u if temp is None else (u, temp)
+    return _steps32_("ins_rk_steps_f32", "ins_rk_steps_ext_f32", cache, u, Δt, (int(nsteps),), temp, θ)

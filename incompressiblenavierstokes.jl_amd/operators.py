@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._step_route import mark_library_closure
 from .boundary_conditions import DirichletBC
 from .setup import copyfield, scalarfield, vectorfield
 
@@ -494,9 +495,7 @@ def smagorinsky_closure(setup):
         _lib.call("ins_smagorinsky_force_f64", setup.handle, float(θ), setup.ptr(u, True), σp, setup.ptr(s, True), setup.stream)
         return s
 
-    closure._ins_closure, closure._ins_setup = "smagorinsky", setup  # lets timestep_ run it inside the native stage loop (ins_rk_set_closure)
-    closure._ins_dtype = torch.float64
-    return closure
+    return mark_library_closure(closure, setup, torch.float64)  # lets timestep_ run it inside the native stage loop (ins_rk_set_closure)
 
 
 def smagorinsky_force_(s, u, θ, setup, σ=None):

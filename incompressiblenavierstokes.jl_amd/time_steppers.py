@@ -1,7 +1,6 @@
 """Explicit Runge-Kutta time stepping (time_steppers/methods.jl, RKMethods.jl,
 step_explicit_runge_kutta.jl, time_stepper_caches.jl), host side."""
 import ctypes as C
-import os
 from dataclasses import dataclass
 from fractions import Fraction
 from types import SimpleNamespace
@@ -9,6 +8,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import _lib
+from ._step_route import Route, steady_force, step_route
 from .operators import apply_bc_temp_, apply_bc_u_, convection_diffusion_temp_, dissipation_, momentum_
 from .pressure import project_
 from .setup import copyfield, scalarfield, vectorfield
@@ -216,15 +216,10 @@ def combine_(out, base, coefs, ks, setup, vector=True):
 
 def _native_force(cache, setup):
     """Hand a steady body force to the native stage loop (ins_rk_set_bodyforce); the field lives in `setup`."""
-    f = setup.bodyforce if (setup.bodyforce is not None and setup.issteadybodyforce) else None
+    f = steady_force(setup)
     if getattr(cache, "_force", None) is not f:
         _lib.call("ins_rk_set_bodyforce", cache.handle, setup.ptr(f, True) if f is not None else None)
         cache._force = f
-
-
-def _host_driven(setup, temp):
-    """True when the stage loop must run on the host: a user callback or an extra equation sits between the kernels."""
-    return temp is not None or setup.closure_model is not None or (setup.bodyforce is not None and not setup.issteadybodyforce) or setup.needs_bc_planes
 
 
 class _TempDesc(C.Structure):
@@ -234,36 +229,19 @@ class _TempDesc(C.Structure):
                 ("bc", C.c_int32 * 6), ("val", C.c_double * 6)]
 
 
-def _native_ext(setup, temp, θ):
-    """The native extended stage loop (csrc/ins_rk_ext.hip) serves the temperature equation and the Smagorinsky closure when nothing
-    else needs the host between the kernels: returns (closure kind, θ, temperature descriptor or None), or None for the host loop."""
-    if setup.needs_bc_planes or (setup.bodyforce is not None and not setup.issteadybodyforce):
-        return None
-    m = setup.closure_model
-    kind = 0
-    if m is not None:
-        if getattr(m, "_ins_closure", None) != "smagorinsky" or getattr(m, "_ins_setup", None) is not setup or not np.isscalar(θ):
-            return None  # a user callable: only the host can evaluate it
-        kind = 1
-    desc = None
-    if temp is not None:
-        desc = _temperature_desc(setup)
-        if desc is None:
-            return None  # callable temperature boundary data
-    return kind, float(θ) if kind else 0.0, desc
-
-
 def _temperature_desc(setup):
-    """The descriptor of `setup.temperature` for the native loops (ins_temperature_desc_t), or None with callable temperature boundary data."""
-    from .operators import _temp_bc_args
+    """The descriptor of `setup.temperature` for the native loops of both precisions (ins_temperature_desc_t): the scalars, the boundary codes and
+    the constant Dirichlet values.  Callable Dirichlet data has no descriptor: the callers turn it away first (`Facts.bc_temp_callable`)."""
+    from .boundary_conditions import DirichletBC
 
     T = setup.temperature
-    codes, vals, planes, _ = _temp_bc_args(setup, 0.0)
-    if planes is not None:
-        return None
     desc = _TempDesc(a2=T.α2, a4=T.α4, diss_coef=setup.Re * T.α1 / T.γ, gdir=int(T.gdir), dodissipation=int(T.dodissipation))
-    for q in range(6):
-        desc.bc[q], desc.val[q] = codes[q], vals[q]
+    for be in range(setup.grid.dimension):
+        for side in range(2):
+            bc = T.boundary_conditions[be][side]
+            desc.bc[2 * be + side] = bc.code
+            if isinstance(bc, DirichletBC) and bc.u is not None:
+                desc.val[2 * be + side] = float(bc.u)
     return desc
 
 
@@ -548,76 +526,93 @@ def create_stepper(method, *, setup, psolver, u, temp=None, t=0.0, n=0):
     return SimpleNamespace(setup=setup, psolver=psolver, u=u, temp=temp, t=t, n=n)
 
 
+def _native_form(method, cache):
+    """(method, cache) as the native loops take them: the low-storage scheme as the explicit RK method it is, on the cache kept for that form."""
+    return cache.erk(method) if isinstance(method, LMWray3) else (method, cache)
+
+
 def timesteps_(method, stepper, Δt, nsteps, *, θ=None, cache):
     """`nsteps` time steps of size Δt, in place: the fixed-Δt loop of solve_unsteady (solver.jl:74-83) as one native call
-    (`ins_rk_steps_f64`) when the boundary data is time-independent; otherwise `nsteps` calls of `timestep_`.
+    (`ins_rk_steps_f64`) on the route NATIVE (_step_route.py); otherwise `nsteps` calls of `timestep_`.
     The stepper's `u` is valid on entry and on return (intermediate steps are not observable, as inside the reference's loop
     without processors)."""
     setup, psolver = stepper.setup, stepper.psolver
-    if nsteps >= 1 and isinstance(method, LMWray3) and not _host_driven(setup, stepper.temp) and not os.environ.get("INS_HOST_STAGE_LOOP"):
-        m_erk, c_erk = cache.erk(method)
-        st = timesteps_(m_erk, stepper, Δt, nsteps, θ=θ, cache=c_erk)
-        return create_stepper(method, setup=setup, psolver=psolver, u=st.u, temp=None, t=stepper.t + nsteps * Δt, n=stepper.n + nsteps)
-    if nsteps >= 1 and not isinstance(method, LMWray3) and not _host_driven(setup, stepper.temp):
+    lmwray3 = isinstance(method, LMWray3)
+    if nsteps >= 1 and step_route(lmwray3, setup, stepper.temp, θ) is Route.NATIVE:
+        erk, cache = _native_form(method, cache)
         if cache.psolver is not psolver:
             raise ValueError("cache was created for a different psolver")
         _native_force(cache, setup)
         _lib.call("ins_rk_steps_f64", cache.handle, 1.0 / setup.Re, setup.ptr(stepper.u, True), float(stepper.t), float(Δt), int(nsteps), setup.stream)
-        return create_stepper(method, setup=setup, psolver=psolver, u=stepper.u, temp=None, t=stepper.t + nsteps * method.c[-1] * Δt, n=stepper.n + nsteps)
+        return create_stepper(method, setup=setup, psolver=psolver, u=stepper.u, temp=None,
+                              t=stepper.t + (nsteps * Δt if lmwray3 else nsteps * erk.c[-1] * Δt), n=stepper.n + nsteps)
     for _ in range(nsteps):
         stepper = timestep_(method, stepper, Δt, θ=θ, cache=cache)
     return stepper
 
 
 def timestep_(method, stepper, Δt, *, θ=None, cache):
-    """Perform one time step, in place (step_explicit_runge_kutta.jl:4-59).
-
-    Fully native (`ins_rk_step_f64`) when boundary data is time-independent; with callable Dirichlet data
-    the stage loop runs here and calls the operator-level kernels so `bc.u(α, x..., t)` can be evaluated
-    between stages (SURVEY.md §8b closure-hook caveat)."""
-    setup, psolver, u, temp, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.temp, stepper.t, stepper.n
+    """Perform one time step, in place (step_explicit_runge_kutta.jl:4-59), on the route `_step_route.route` gives (DESIGN.md "Step routes"):
+    one native call when nothing needs the host between the kernels, else a stage loop here that calls the operator-level kernels so that
+    `bc.u(α, x..., t)`, an unsteady force or a user closure can be evaluated between stages (SURVEY.md §8b closure-hook caveat)."""
+    setup, temp = stepper.setup, stepper.temp
     if (temp is None) != (setup.temperature is None):
         raise ValueError("a temperature field needs setup.temperature (temperature_equation) and vice versa")
-    if isinstance(method, LMWray3):
-        # native when nothing has to run on the host between the kernels: the scheme as the explicit RK method it is, inside the native stage loop
-        if os.environ.get("INS_HOST_STAGE_LOOP") or (_host_driven(setup, temp) and _native_ext(setup, temp, θ) is None):
-            return _timestep_lmwray3_(method, stepper, Δt, cache, θ)
-        m_erk, c_erk = cache.erk(method)
-        st = timestep_(m_erk, stepper, Δt, θ=θ, cache=c_erk)
-        return create_stepper(method, setup=setup, psolver=psolver, u=st.u, temp=st.temp, t=t + Δt, n=n + 1)
-    if cache.psolver is not psolver:
+    r = step_route(isinstance(method, LMWray3), setup, temp, θ)
+    if r is Route.HOST_LMWRAY3:
+        return _timestep_lmwray3_(method, stepper, Δt, cache, θ)
+    erk, cache = _native_form(method, cache)
+    if cache.psolver is not stepper.psolver:
         raise ValueError("cache was created for a different psolver")
-    if not _host_driven(setup, temp):
-        _native_force(cache, setup)
-        _lib.call("ins_rk_step_f64", cache.handle, 1.0 / setup.Re, setup.ptr(u, True), float(t), float(Δt), None, setup.stream)
-        return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=None, t=stepper.t + method.c[-1] * Δt, n=n + 1)
-    if (setup.needs_bc_planes and temp is None and setup.closure_model is None and (setup.bodyforce is None or setup.issteadybodyforce)
-            and not os.environ.get("INS_HOST_STAGE_LOOP")):
-        # callable Dirichlet data is the only thing that needs the host: the ghost fills of the stage loop happen at times known before the step
-        # (tstart and tstart + c[i] Δt), so the closures are evaluated for those now and the whole stage loop runs natively (ins_rk_step_bc_f64)
-        from .operators import _bc_planes
+    st = _STEP[r](erk, stepper, Δt, θ, cache)
+    if erk is not method:
+        st.t = stepper.t + Δt
+    return st
 
-        ns = len(method.b)
-        sets = (C.c_void_p * (18 * (ns + 1)))()
-        keep = []
-        for q in range(ns + 1):
-            arr, k = _bc_planes(setup, t if q == 0 else t + method.c[q - 1] * Δt, False)
-            keep.append(k)
-            for j in range(18):
-                sets[18 * q + j] = arr[j]
-        _native_force(cache, setup)
-        _lib.call("ins_rk_step_bc_f64", cache.handle, 1.0 / setup.Re, setup.ptr(u, True), float(t), float(Δt), sets, setup.stream)
-        return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=None, t=stepper.t + method.c[-1] * Δt, n=n + 1)
-    ext = None if os.environ.get("INS_HOST_STAGE_LOOP") else _native_ext(setup, temp, θ)
-    if ext is not None:  # temperature equation / Smagorinsky closure inside the native loop
-        kind, th, desc = ext
-        _native_force(cache, setup)
-        _lib.call("ins_rk_set_closure", cache.handle, kind, th)
-        _lib.call("ins_rk_set_temperature", cache.handle, C.byref(desc) if desc is not None else None)
-        _lib.call("ins_rk_step_ext_f64", cache.handle, 1.0 / setup.Re, setup.ptr(u, True), setup.ptr(temp, False) if temp is not None else None,
-                  float(t), float(Δt), setup.stream)
-        return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=stepper.t + method.c[-1] * Δt, n=n + 1)
-    # host-driven stage loop (time-dependent boundary data, unsteady body force, user closure model)
+
+def _step_native_(method, stepper, Δt, θ, cache):
+    setup, psolver, u, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.t, stepper.n
+    _native_force(cache, setup)
+    _lib.call("ins_rk_step_f64", cache.handle, 1.0 / setup.Re, setup.ptr(u, True), float(t), float(Δt), None, setup.stream)
+    return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=None, t=stepper.t + method.c[-1] * Δt, n=n + 1)
+
+
+def _step_native_bc_(method, stepper, Δt, θ, cache):
+    """Callable Dirichlet data is the only thing that needs the host: the ghost fills of the stage loop happen at times known before the step
+    (tstart and tstart + c[i] Δt), so the closures are evaluated for those now and the whole stage loop runs natively (ins_rk_step_bc_f64)."""
+    from .operators import _bc_planes
+
+    setup, psolver, u, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.t, stepper.n
+    ns = len(method.b)
+    sets = (C.c_void_p * (18 * (ns + 1)))()
+    keep = []
+    for q in range(ns + 1):
+        arr, k = _bc_planes(setup, t if q == 0 else t + method.c[q - 1] * Δt, False)
+        keep.append(k)
+        for j in range(18):
+            sets[18 * q + j] = arr[j]
+    _native_force(cache, setup)
+    _lib.call("ins_rk_step_bc_f64", cache.handle, 1.0 / setup.Re, setup.ptr(u, True), float(t), float(Δt), sets, setup.stream)
+    return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=None, t=stepper.t + method.c[-1] * Δt, n=n + 1)
+
+
+def _step_native_ext_(method, stepper, Δt, θ, cache):
+    """Temperature equation / Smagorinsky closure inside the native loop (csrc/ins_rk_ext.hip); the route has seen to it that a closure model is the
+    library's of this setup with a scalar θ, and that the temperature's boundary data is constant."""
+    setup, psolver, u, temp, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.temp, stepper.t, stepper.n
+    kind = int(setup.closure_model is not None)
+    desc = _temperature_desc(setup) if temp is not None else None
+    _native_force(cache, setup)
+    _lib.call("ins_rk_set_closure", cache.handle, kind, float(θ) if kind else 0.0)
+    _lib.call("ins_rk_set_temperature", cache.handle, C.byref(desc) if desc is not None else None)
+    _lib.call("ins_rk_step_ext_f64", cache.handle, 1.0 / setup.Re, setup.ptr(u, True), setup.ptr(temp, False) if temp is not None else None,
+              float(t), float(Δt), setup.stream)
+    return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=stepper.t + method.c[-1] * Δt, n=n + 1)
+
+
+def _step_host_erk_(method, stepper, Δt, θ, cache):
+    """Host-driven stage loop (time-dependent boundary data, unsteady body force, user closure model)."""
+    setup, psolver, u, temp, t, n = stepper.setup, stepper.psolver, stepper.u, stepper.temp, stepper.t, stepper.n
     A, c = method.A, method.c
     ns = len(method.b)
     m = setup.closure_model
@@ -650,6 +645,9 @@ def timestep_(method, stepper, Δt, *, θ=None, cache):
     if temp is not None:
         apply_bc_temp_(temp, t, setup)
     return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=t, n=n + 1)
+
+
+_STEP = {Route.NATIVE: _step_native_, Route.NATIVE_BC: _step_native_bc_, Route.NATIVE_EXT: _step_native_ext_, Route.HOST_ERK: _step_host_erk_}
 
 
 def timestep(method, stepper, Δt, *, θ=None):

@@ -2,6 +2,7 @@
 `ad.timesteps` / `ad32.timesteps`: the symbols are exported and bound with the header's signatures, the refusals that need no device, and the checkpoint
 and chunk bookkeeping of `_autodiff_core._TimeSteps` for the pair state (u, temp) on the stand-in operators of tests/test_autodiff_core_cpu.py."""
 import ctypes as C
+import itertools
 import os
 import re
 from types import SimpleNamespace
@@ -110,16 +111,22 @@ def test_refusals_without_gpu(which):
         ad.timesteps(method, _stepper(_setup(), wrong_ps, mine), 1e-3, 2)
     # NotImplementedError, each naming the step-by-step route
     refused = [
-        (_setup(closure_model=lambda u, θ: u), None),
-        (_setup(temperature=T), None),  # a temperature equation without stepper.temp
-        (_setup(needs_bc_planes=True), None),
-        (_setup(temperature=Tfun), mine),
-        (_setup(bodyforce=torch.zeros(4, 4, 2), issteadybodyforce=False), None),
-        (_setup(boundary_conditions=((HaloBC(), HaloBC()),)), None),
+        (dict(closure_model=lambda u, θ: u), None),
+        (dict(temperature=T), None),  # a temperature equation without stepper.temp
+        (dict(needs_bc_planes=True), None),
+        (dict(temperature=Tfun), mine),
+        (dict(bodyforce=torch.zeros(4, 4, 2), issteadybodyforce=False), None),
+        (dict(boundary_conditions=((HaloBC(), HaloBC()),)), None),
     ]
-    for sp, tdtype in refused:
+    for kw, tdtype in refused:
         with pytest.raises(NotImplementedError, match=step):
-            ad.timesteps(method, _stepper(sp, ps, mine, tdtype), 1e-3, 2)
+            ad.timesteps(method, _stepper(_setup(**kw), ps, mine, tdtype), 1e-3, 2)
+    # two refused setups in one (the second's attributes over the first's; a temperature field where either has one).  Which reason is named is the
+    # business of the shared list (core.check_rollout); the type is NotImplementedError, and a wrongly shaped field does not get in front of it
+    for (a, ta), (b, tb) in itertools.combinations(refused, 2):
+        for N in ((4, 4), (4, 5)):
+            with pytest.raises(NotImplementedError):
+                ad.timesteps(method, _stepper(_setup(**{**a, **b}), ps, mine, ta or tb, N=N), 1e-3, 2)
 
 
 # ------------------------------------------------------------------------------------ checkpoint and chunk bookkeeping on the stand-in table

@@ -111,8 +111,8 @@ class Setups:
     def __init__(self):
         self.made = {}
 
-    def get(self, geom, with_force=False, temp=False, smag=False):
-        key = (geom, with_force, temp, smag)
+    def get(self, geom, with_force=False, temp=False, smag=False, user=False):
+        key = (geom, with_force, temp, smag, user)
         if key not in self.made:
             x, bc, mk = geometry(geom)
             kw = {}
@@ -128,6 +128,8 @@ class Setups:
             sp = ins.Setup(x=x, **kw)
             if smag:
                 sp.closure_model = ins.smagorinsky_closure(sp)
+            if user:  # a callable the library knows nothing about: only the host stage loop can evaluate it
+                sp.closure_model = lambda u, θ: θ * u
             ps = mk(sp)
             D = len(x)
             u0 = ins.apply_bc_u(ins.project(ins.apply_bc_u(ins.from_numpy(sp, 0.1 * randn(sp.grid.N + (D,), 11)), 0.0, sp), sp, ps), 0.0, sp)
@@ -136,21 +138,32 @@ class Setups:
         return self.made[key]
 
 
-def run_f64(S, label, geom, method, mode, opts, with_force=False, temp=False, smag=False):
-    sp, ps, u0, t0, dt = S.get(geom, with_force, temp, smag)
-    m = getattr(ins.RKMethods, method)()
-    theta = 0.17 if smag else None
+def run_f64(S, label, geom, method, mode, opts, with_force=False, temp=False, smag=False, user=False, host_loop=False):
+    sp, ps, u0, t0, dt = S.get(geom, with_force, temp, smag, user)
+    m = ins.LMWray3() if method == "LMWray3" else getattr(ins.RKMethods, method)()
+    theta = 0.17 if smag or user else None
     before = int(_lib.load().ins_dbg_ext_fused_steps())
-    with _lib.options(**opts):
-        cache = ins.ode_method_cache(m, sp, ps)
-        st = ins.create_stepper(m, setup=sp, psolver=ps, u=u0.clone(), temp=None if t0 is None else t0.clone())
-        if mode == "single":
-            for _ in range(3):
-                st = ins.timestep_(m, st, dt, θ=theta, cache=cache)
-        else:  # chainN / graphN: one native call of N steps
-            st = ins.timesteps_(m, st, dt, int(mode[5:]), θ=theta, cache=cache)
-        fields = [ins.to_numpy(st.u)] + ([ins.to_numpy(st.temp)] if st.temp is not None else []) + [pressure(cache, sp)]
-        rhs, replays, fused = counters(cache)
+    if host_loop:
+        os.environ["INS_HOST_STAGE_LOOP"] = "1"
+    try:
+        with _lib.options(**opts):
+            cache = ins.ode_method_cache(m, sp, ps)
+            st = ins.create_stepper(m, setup=sp, psolver=ps, u=u0.clone(), temp=None if t0 is None else t0.clone())
+            if mode == "single":
+                for _ in range(3):
+                    st = ins.timestep_(m, st, dt, θ=theta, cache=cache)
+            else:  # chainN / graphN: one native call of N steps
+                st = ins.timesteps_(m, st, dt, int(mode[5:]), θ=theta, cache=cache)
+            # the pressure of the loop that ran: the host loops keep theirs in a field of the cache, the native ones in the handle
+            if method == "LMWray3":
+                rk, hostp = (cache._erk[1] if cache._erk else None), (cache.p if cache._host else None)
+            else:
+                rk, hostp = cache, (cache._host["p"] if hasattr(cache, "_host") else None)
+            fields = [ins.to_numpy(st.u)] + ([ins.to_numpy(st.temp)] if st.temp is not None else [])
+            fields.append(ins.to_numpy(hostp) if hostp is not None else pressure(rk, sp))
+            rhs, replays, fused = counters(rk) if rk is not None else (0, 0, before)
+    finally:
+        os.environ.pop("INS_HOST_STAGE_LOOP", None)
     print(f"{label:58s} {sha(label, *fields)} rhs={rhs} replays={replays} extfused={fused - before}", flush=True)
 
 
@@ -301,6 +314,12 @@ def cases():
             for with_force in (False, True):
                 yield f"ext smag{'+force' if with_force else ''} walls24 RK44 (tiled)", run_f64, dict(geom="walls24", method="RK44", mode="single", opts={},
                                                                                                    with_force=with_force, smag=True)
+    # the host stage loops: a user closure (only the host can call it), and the low-storage scheme natively and behind INS_HOST_STAGE_LOOP=1
+    for geom in ("per32x32x32", "per64x32", "walls24"):
+        yield f"host user-closure {geom} RK44 single", run_f64, dict(geom=geom, method="RK44", mode="single", opts={}, user=True)
+        for mode in ("single", "chain3"):
+            yield f"lmwray3 {geom} {mode} native", run_f64, dict(geom=geom, method="LMWray3", mode=mode, opts={})
+            yield f"lmwray3 {geom} {mode} INS_HOST_STAGE_LOOP=1", run_f64, dict(geom=geom, method="LMWray3", mode=mode, opts={}, host_loop=True)
     wx, wbc, _ = geometry("walls24")
     for vn, vo in VARIANTS:
         yield f"f32 per128x16x256 RK44 single {vn}", run_f32, dict(x=exact((128, 16, 256)), bc=None, method="RK44", nsteps=3, chained=False, opts=vo)
