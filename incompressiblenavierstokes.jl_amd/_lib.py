@@ -259,6 +259,7 @@ SIGNATURES = {
 DEBUG_SIGNATURES = {
     "ins_dbg_f32_choose": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ins_dbg_rk32_route": (C.c_int, [vp, C.POINTER(C.c_int32)]),
+    "ins_dbg_dev_live": (None, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 _lib = None

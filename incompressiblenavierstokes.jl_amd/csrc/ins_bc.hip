@@ -99,18 +99,10 @@ extern "C" int ins_apply_bc_u_f64(const ins_grid_t* G, double* u, int dudt, cons
   INS_REQUIRE(G && u, "null argument");
   if (!planes) return ins_k_apply_bc_u(G, u, dudt, nullptr, as_stream(stream));
   // `planes` is a host array of 18 device pointers; stage it in device memory for the kernels.
-  const double** dplanes = nullptr;
-  INS_HIP_TRY(hipMalloc(&dplanes, 18 * sizeof(double*)));
-  hipError_t e = hipMemcpy(dplanes, planes, 18 * sizeof(double*), hipMemcpyHostToDevice);
-  int rc = INS_OK;
-  if (e != hipSuccess) {
-    ins_set_error("hipMemcpy(planes): %s", hipGetErrorString(e));
-    rc = INS_ERR_HIP;
-  } else {
-    rc = ins_k_apply_bc_u(G, u, dudt, dplanes, as_stream(stream));
-    if (rc == INS_OK && hipStreamSynchronize(as_stream(stream)) != hipSuccess) rc = INS_ERR_HIP;
-  }
-  (void)hipFree(dplanes);
+  DevBuf<const double*> dplanes;
+  int rc = dplanes.alloc_copy_host(18, planes);
+  if (rc == INS_OK) rc = ins_k_apply_bc_u(G, u, dudt, dplanes, as_stream(stream));
+  if (rc == INS_OK && hipStreamSynchronize(as_stream(stream)) != hipSuccess) rc = INS_ERR_HIP;  // dplanes is freed on return
   return rc;
 }
 

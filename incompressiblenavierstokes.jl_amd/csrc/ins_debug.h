@@ -57,6 +57,10 @@ int ins_dbg_rk_ensemble_args(int64_t ncell, int32_t nbatch, int64_t ustride, int
 long long ins_dbg_ext_tiled_steps(void);
 long long ins_dbg_ext_fused_steps(void);
 
+/* ins_devmem.hip.  Test hook, not part of the public ABI: device and pinned-host buffers the library holds at this moment, and their bytes (either
+ * pointer may be NULL).  A handle that has been destroyed holds none. */
+void ins_dbg_dev_live(int64_t* buffers, int64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

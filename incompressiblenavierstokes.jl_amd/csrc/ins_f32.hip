@@ -20,54 +20,54 @@
 #include "ins_rk_terms.h"
 
 struct ins_poisson32 {
-  const ins_grid* grid = nullptr;
+  const ins_grid* grid = nullptr;  // borrowed
   // which launch sequence this solver runs: what its creation actually set up (ins_f32_choose; ins_poisson_wrap_f32).  The pointers below are resources
   // of a route, never tests of it.
   F32Route route = F32_HIPFFT;
   hipfftHandle fwd = 0, inv = 0;
   bool plans = false;
-  float* pI = nullptr;
-  hipfftComplex* phat = nullptr;
-  float* ahat[3] = {nullptr, nullptr, nullptr};
+  DevBuf<float> pI;
+  DevBuf<hipfftComplex> phat;
+  DevBuf<float> ahat[3];
   int np[3] = {1, 1, 1}, kmax[3] = {1, 1, 1};
   // 3-D power-of-two boxes: project! solves its pressure equation with the library's fused fp64 passes (right-hand side formed from the
   // float field inside the x pass, five passes instead of hipFFT's 3-D plans + separate kernels; the pressure is MORE accurate than a float
   // solve would give).  512^3 RK44 step: 26.9 ms with hipFFT's float plans -> see DESIGN.md §5.
-  ins_poisson* ps64 = nullptr;
+  ins_poisson* ps64 = nullptr;  // owned: ins_poisson_destroy
   // sides the three-pass z kernel takes (192, 256, 384, 512 planes): the same five passes on FLOAT2 spectra — half the bytes of every pass; ps64
   // then only supplies the symbol vectors (INS_F32_FP64_SPECTRA=1 keeps the fp64 passes)
-  float* phat32 = nullptr;
-  float* tw32[3] = {nullptr, nullptr, nullptr};
+  DevBuf<float> phat32;
+  DevBuf<float> tw32[3];
   int kxs32 = 0;
   // ins_poisson_wrap_f32: a Float32 solver around a caller-owned fp64 solver of any kind (walls / stretched grids: psolver_direct, psolver_cg)
-  ins_poisson* wrap64 = nullptr;
-  double* p64 = nullptr;  // padded fp64 right-hand side / solution
-  float* div32 = nullptr; // padded scratch of the divergence diagnostic
+  ins_poisson* wrap64 = nullptr;  // borrowed
+  DevBuf<double> p64;   // padded fp64 right-hand side / solution
+  DevBuf<float> div32;  // padded scratch of the divergence diagnostic
 };
 
 struct ins_rk32 {
-  const ins_grid* grid = nullptr;
-  ins_poisson32* ps = nullptr;
+  const ins_grid* grid = nullptr;  // borrowed
+  ins_poisson32* ps = nullptr;     // borrowed
   int nstage = 0;
   std::vector<double> A, c;
-  std::vector<float*> ku;
-  float* ub[2] = {nullptr, nullptr};
-  float* p = nullptr;
-  float* pu = nullptr;  // unpadded float copy of the stage pressure (in-register correction of the next stage's stencil kernel)
-  float* ustart = nullptr;  // chained steps: the corrected start field of steps 2..K (the caller's array holds the uncorrected last stage velocity then)
+  std::vector<DevBuf<float>> ku;
+  DevBuf<float> ub[2];
+  DevBuf<float> p;
+  DevBuf<float> pu;  // unpadded float copy of the stage pressure (in-register correction of the next stage's stencil kernel)
+  DevBuf<float> ustart;  // chained steps: the corrected start field of steps 2..K (the caller's array holds the uncorrected last stage velocity then)
   // temperature equation (ins_rk_set_temperature_f32, ins_rk_step_ext_f32): scalar scratch allocated by the first step that carries a temperature
   bool temp_on = false;
   ins_temperature_desc_t td = {};
-  float* tempstart = nullptr;
-  float* tstage = nullptr;      // the one stage temperature buffer: stage temperatures alternate between it and the caller's array
-  float* diff = nullptr;        // scratch of dissipation! (vector field)
-  std::vector<float*> ktemp;    // nstage scalars
+  DevBuf<float> tempstart;
+  DevBuf<float> tstage;         // the one stage temperature buffer: stage temperatures alternate between it and the caller's array
+  DevBuf<float> diff;           // scratch of dissipation! (vector field)
+  std::vector<DevBuf<float>> ktemp;  // nstage scalars
   // Smagorinsky closure and steady body force (ins_rk_set_closure_f32, ins_rk_set_bodyforce_f32)
   int closure = 0;              // 0 none, 1 Smagorinsky
   float theta = 0.f;
-  const float* force = nullptr; // the caller's device field
-  float* E = nullptr;           // closure force (vector field; only its degrees of freedom are ever written)
-  float* sigma = nullptr;       // D(D+1)/2 scalar fields (three-kernel route)
+  const float* force = nullptr; // borrowed: the caller's device field
+  DevBuf<float> E;              // closure force (vector field; only its degrees of freedom are ever written)
+  DevBuf<float> sigma;          // D(D+1)/2 scalar fields (three-kernel route)
 };
 
 namespace {
@@ -364,16 +364,7 @@ extern "C" int ins_poisson_destroy_f32(ins_poisson32_t* ps) {
     (void)hipfftDestroy(ps->fwd);
     (void)hipfftDestroy(ps->inv);
   }
-  if (ps->pI) (void)hipFree(ps->pI);
-  if (ps->phat) (void)hipFree(ps->phat);
-  for (float* a : ps->ahat)
-    if (a) (void)hipFree(a);
   if (ps->ps64) (void)ins_poisson_destroy(ps->ps64);
-  if (ps->phat32) (void)hipFree(ps->phat32);
-  for (float* t : ps->tw32)
-    if (t) (void)hipFree(t);
-  if (ps->p64) (void)hipFree(ps->p64);
-  if (ps->div32) (void)hipFree(ps->div32);
   delete ps;  // wrap64 is the caller's
   return INS_OK;
 }
@@ -395,12 +386,10 @@ extern "C" int ins_poisson_wrap_f32(const ins_grid_t* G, ins_poisson_t* ps64, in
   ps->route = F32_WRAP;
   ps->wrap64 = ps64;
   for (int a = 0; a < g.D; ++a) ps->np[a] = g.ip_hi[a] - g.ip_lo[a];
-  const bool ok = hipMalloc(&ps->p64, G->ncell * sizeof(double)) == hipSuccess && hipMemset(ps->p64, 0, G->ncell * sizeof(double)) == hipSuccess &&
-                  hipMalloc(&ps->div32, G->ncell * sizeof(float)) == hipSuccess && hipMemset(ps->div32, 0, G->ncell * sizeof(float)) == hipSuccess;
-  if (!ok) {
-    ins_set_error("ins_poisson_wrap_f32: device allocation failed");
+  int rc;
+  if ((rc = ps->p64.alloc_zero(G->ncell)) || (rc = ps->div32.alloc_zero(G->ncell))) {
     ins_poisson_destroy_f32(ps);
-    return INS_ERR_HIP;
+    return rc;
   }
   *out = ps;
   return INS_OK;
@@ -437,15 +426,14 @@ extern "C" int ins_poisson_spectral_create_f32(const ins_grid_t* G, ins_poisson3
     ncplx *= ps->kmax[a];
     om *= G->h[a];
   }
-  bool ok = hipMalloc(&ps->pI, nreal * sizeof(float)) == hipSuccess && hipMalloc(&ps->phat, ncplx * sizeof(hipfftComplex)) == hipSuccess;
+  bool ok = ps->pI.alloc(nreal) == INS_OK && ps->phat.alloc(ncplx) == INS_OK;
   for (int a = 0; ok && a < g.D; ++a) {  // âα(k) = 4 Ω sin²(π k / Npα) / Δxα², evaluated in double, stored in float
     std::vector<float> h(ps->kmax[a]);
     for (int k = 0; k < ps->kmax[a]; ++k) {
       const double sn = std::sin(M_PI * (double)k / ps->np[a]);
       h[k] = (float)(4.0 * om * sn * sn / (G->h[a] * G->h[a]));
     }
-    ok = hipMalloc(&ps->ahat[a], h.size() * sizeof(float)) == hipSuccess &&
-         hipMemcpy(ps->ahat[a], h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ps->ahat[a].alloc_copy_host(h.size(), h.data()) == INS_OK;
   }
   if (ok) {
     hipfftResult r1, r2;
@@ -470,8 +458,7 @@ extern "C" int ins_poisson_spectral_create_f32(const ins_grid_t* G, ins_poisson3
   if (want != F32_HIPFFT && ins_poisson_spectral_create(G, &ps->ps64) == INS_OK) ps->route = F32_FP64_SPECTRA;  // the fused fp64 passes for project!
   if (want == F32_FLOAT2_SPECTRA && ps->route == F32_FP64_SPECTRA) {
     ps->kxs32 = (ps->kmax[0] + 15) & ~15;  // rows of the float2 spectrum padded to whole 128-B lines
-    const size_t nb = (size_t)ps->kxs32 * ps->np[1] * ps->np[2] * 2 * sizeof(float);
-    bool ok32 = hipMalloc(&ps->phat32, nb) == hipSuccess && hipMemset(ps->phat32, 0, nb) == hipSuccess;
+    bool ok32 = ps->phat32.alloc_zero((size_t)ps->kxs32 * ps->np[1] * ps->np[2] * 2) == INS_OK;
     for (int a = 0; ok32 && a < 3; ++a) ok32 = ins_zsolve_twiddles_f32(ps->np[a], &ps->tw32[a]) == INS_OK;
     if (ok32) ps->route = F32_FLOAT2_SPECTRA;
   }
@@ -543,18 +530,6 @@ extern "C" int ins_poisson_solve_f32(ins_poisson32_t* ps, float* p, void* stream
 
 // ---------------------------------------------------------------------------------------------- explicit Runge-Kutta, T = Float32
 extern "C" int ins_rk_destroy_f32(ins_rk32_t* rk) {
-  if (rk && rk->ustart) (void)hipFree(rk->ustart);
-  if (!rk) return INS_OK;
-  for (float* k : rk->ku)
-    if (k) (void)hipFree(k);
-  for (float* b : rk->ub)
-    if (b) (void)hipFree(b);
-  if (rk->p) (void)hipFree(rk->p);
-  if (rk->pu) (void)hipFree(rk->pu);
-  for (float* b : {rk->tempstart, rk->tstage, rk->diff, rk->E, rk->sigma})
-    if (b) (void)hipFree(b);
-  for (float* k : rk->ktemp)
-    if (k) (void)hipFree(k);
   delete rk;
   return INS_OK;
 }
@@ -569,15 +544,14 @@ extern "C" int ins_rk_create_f32(const ins_grid_t* G, ins_poisson32_t* ps, int n
   rk->nstage = nstage;
   rk->A.assign(A, A + nstage * nstage);
   rk->c.assign(c, c + nstage);
-  const size_t vbytes = (size_t)G->ncell * G->g.D * sizeof(float);
-  rk->ku.assign(nstage, nullptr);
-  bool ok = hipMalloc(&rk->p, G->ncell * sizeof(float)) == hipSuccess && hipMemset(rk->p, 0, G->ncell * sizeof(float)) == hipSuccess;
-  for (int i = 0; ok && i < nstage; ++i) ok = hipMalloc(&rk->ku[i], vbytes) == hipSuccess && hipMemset(rk->ku[i], 0, vbytes) == hipSuccess;
-  for (int b = 0; ok && b < 2; ++b) ok = hipMalloc(&rk->ub[b], vbytes) == hipSuccess && hipMemset(rk->ub[b], 0, vbytes) == hipSuccess;
-  if (!ok) {
-    ins_set_error("ins_rk_create_f32: device allocation failed");
+  const size_t nvec = (size_t)G->ncell * G->g.D;
+  rk->ku.resize(nstage);
+  int rc = rk->p.alloc_zero(G->ncell);
+  for (int i = 0; rc == INS_OK && i < nstage; ++i) rc = rk->ku[i].alloc_zero(nvec);
+  for (int b = 0; rc == INS_OK && b < 2; ++b) rc = rk->ub[b].alloc_zero(nvec);
+  if (rc != INS_OK) {
     ins_rk_destroy_f32(rk);
-    return INS_ERR_HIP;
+    return rc;
   }
   *out = rk;
   return INS_OK;
@@ -632,7 +606,7 @@ static int rk32_step(ins_rk32* rk, float visc, float* u, float dt, hipStream_t s
   // its pressure and apply u = u* - ∇p in registers (CORR = 1), the solve forms Ω·div(u*) from the float field inside its x
   // pass; only the last stage materialises u (padded p, gradient-subtract, ghosts).
   const long long ncell_in = (long long)(G->g.N[0] - 2) * (G->g.N[1] - 2) * (G->g.N[2] - 2);
-  if (incorr && !fl2 && !rk->pu) INS_HIP_TRY(hipMalloc(&rk->pu, ncell_in * sizeof(float)));
+  if (incorr && !fl2 && !rk->pu && (rc = rk->pu.alloc(ncell_in))) return rc;
   const float* pcorr = fl2 ? rk->ps->pI : rk->pu;
   if (chain && !(incorr && fl2)) {
     ins_set_error("ins_rk_steps_f32: chained steps need the in-register correction on float2 spectra");
@@ -644,18 +618,18 @@ static int rk32_step(ins_rk32* rk, float visc, float* u, float dt, hipStream_t s
     if (wide) {
       // the V_m live in the ku arrays (float arrays behind RkEpi's untyped pointers: the kernels cast back); V_{i-1} is this stage's stencil input and the
       // kernel always has its uncorrected value in registers
-      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, (double)dt, rk->ku.data(), (const float*)nullptr, vbasis ? RK_V_BASIS : RK_K_BASIS, true,
+      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, (double)dt, rk->ku, (const float*)nullptr, vbasis ? RK_V_BASIS : RK_K_BASIS, true,
                                      RK_FORCE_DIAG_FIRST);
       epi.ustart = i == 0 ? nullptr : reinterpret_cast<const double*>(raw_in ? rk->ustart : u);
       epi.ustar = reinterpret_cast<double*>(outp);
-      if (i == 0 && raw_in) epi.ustart_out = reinterpret_cast<double*>(rk->ustart);
+      if (i == 0 && raw_in) epi.ustart_out = reinterpret_cast<double*>(rk->ustart.get());
       const bool corr = incorr && (i > 0 || raw_in);
       if ((rc = ins_k_flux64_f32(G, (double)visc, cur, vbasis ? rk->ub[0] : rk->ku[i], &epi, corr ? pcorr : nullptr, corr ? 1 : 0, s))) return rc;   // :21, :35-38
     } else {
       if ((rc = ins_momentum_f32(G, visc, cur, rk->ku[i], s))) return rc;       // :21
       float coef[INS_MAX_STAGES + 1];
       const float* k[INS_MAX_STAGES + 1];
-      const int nt = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), (const float*)nullptr, coef, k);  // Δt (float)A[i,j], in float
+      const int nt = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku, (const float*)nullptr, coef, k);  // Δt (float)A[i,j], in float
       if ((rc = ins_k32_combine(nvec, u, outp, nt, coef, k, s))) return rc;      // :35-38
       if (general && (rc = ins_k32g_apply_bc_u(G, outp, s))) return rc;          // :47
     }
@@ -695,7 +669,8 @@ extern "C" int ins_rk_steps_f32(ins_rk32_t* rk, float visc, float* u, float dt, 
     }
     return INS_OK;
   }
-  if (!rk->ustart) INS_HIP_TRY(hipMalloc(&rk->ustart, (size_t)G->ncell * G->g.D * sizeof(float)));
+  if (!rk->ustart)
+    if (int rc = rk->ustart.alloc((size_t)G->ncell * G->g.D)) return rc;
   for (int n = 0; n < nsteps; ++n) {
     int rc = rk32_step(rk, visc, u, dt, s, (n > 0 ? 1 : 0) | (n < nsteps - 1 ? 2 : 0));
     if (rc) return rc;
@@ -714,12 +689,8 @@ extern "C" int ins_rk_set_temperature_f32(ins_rk32_t* rk, const ins_temperature_
   return INS_OK;
 }
 
-static int zalloc32(float** p, size_t bytes, hipStream_t s) {
-  if (*p) return INS_OK;
-  INS_HIP_TRY(hipMalloc(p, bytes));
-  INS_HIP_TRY(hipMemsetAsync(*p, 0, bytes, s));
-  return INS_OK;
-}
+// first use of a buffer: allocated and zeroed on the stream
+static int zalloc32(DevBuf<float>* b, size_t bytes, hipStream_t s) { return *b ? INS_OK : b->alloc_zero_async(bytes / sizeof(float), s); }
 
 // kind 0: no closure; 1: smagorinsky_closure(setup) with constant θ (operators.jl:1294-1305)
 extern "C" int ins_rk_set_closure_f32(ins_rk32_t* rk, int32_t kind, float theta) {
@@ -770,7 +741,7 @@ static int rk32_step_ext(ins_rk32* rk, float visc, float* u, float* temp, float 
   if (temp) {
     if ((rc = zalloc32(&rk->tempstart, sbytes, s)) || (rc = zalloc32(&rk->tstage, sbytes, s))) return rc;
     if (td.dodissipation && (rc = zalloc32(&rk->diff, sbytes * D, s))) return rc;
-    if ((int)rk->ktemp.size() < ns) rk->ktemp.resize(ns, nullptr);
+    if ((int)rk->ktemp.size() < ns) rk->ktemp.resize(ns);
     for (int i = 0; i < ns; ++i)
       if ((rc = zalloc32(&rk->ktemp[i], sbytes, s))) return rc;
   }
@@ -830,7 +801,7 @@ static int rk32_step_ext(ins_rk32* rk, float visc, float* u, float* temp, float 
     }
     float coef[INS_MAX_STAGES + 1];
     const float* k[INS_MAX_STAGES + 1];
-    const int nt = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, coef, k);             // the body force: one more term
+    const int nt = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku, rk->force, coef, k);             // the body force: one more term
     if ((rc = ins_k32_combine(nvec, u, outp, nt, coef, k, s))) return rc;                                  // :35-38
     if (general && (rc = bc_u(outp))) return rc;                                                           // :47
     if ((rc = ins_project_f32(G, rk->ps, outp, rk->p, s))) return rc;                                      // :48-49 (periodic boxes: fills the ghosts itself)

@@ -50,7 +50,7 @@ int ins_k_ownfft_xinv_f32(const float* phat, float* pI, int n0, int n1, int n2, 
 int ins_k_ownfft_y_f32(float* phat, int kxn, int n1, int n2, const float* tw, bool inverse, hipStream_t s, int kxs);
 int ins_k_line3_y_f32(float* phat, int kxn, int n1, int n2, const float* tw, bool inverse, hipStream_t s, int kxs);
 bool ins_zsolve_f32_supported(int nz);
-int ins_zsolve_twiddles_f32(int nz, float** out);
+int ins_zsolve_twiddles_f32(int nz, DevBuf<float>* out);
 int ins_k_zsolve_f32(float* data, int nz, long long nl, const double* ax, int kxn, const double* ay, const double* az, const float* tw, double inv_n,
                      bool zero_mean, hipStream_t s, int kxs);
 

@@ -472,11 +472,11 @@ int ins_flux3d_prepare(const ins_grid* G, double visc, hipStream_t s) {
   const GridDev& g = G->g;
   if (!M->rec_dev) {
     const size_t n = (size_t)g.N[0] + g.N[1] + g.N[2];
-    INS_HIP_TRY(hipMalloc(&M->rec_dev, n * sizeof(Rec)));
+    if (int rc = M->rec_dev.alloc(n * sizeof(Rec))) return rc;
     M->rec_visc = -1.0;
   }
   if (M->rec_visc != visc) {
-    Rec* r0 = reinterpret_cast<Rec*>(M->rec_dev);
+    Rec* r0 = reinterpret_cast<Rec*>(M->rec_dev.get());
     Rec* r1 = r0 + g.N[0];
     Rec* r2 = r1 + g.N[1];
     const int nmax = std::max(g.N[0], std::max(g.N[1], g.N[2]));
@@ -491,7 +491,7 @@ template <int R, int XW, bool FUSE>
 static int launch_flux(const ins_grid* G, const double* u, double* F, const RkEpi& epi, const double* pI, int corr_mode, hipStream_t s,
                        const void* recs = nullptr) {
   const GridDev& g = G->g;
-  const Rec* r0 = reinterpret_cast<const Rec*>(recs ? recs : G->rec_dev);
+  const Rec* r0 = reinterpret_cast<const Rec*>(recs ? recs : G->rec_dev.get());
   const Rec* r1 = r0 + g.N[0];
   const Rec* r2 = r1 + g.N[1];
   const int zc = g_zchunk ? g_zchunk : ((g.N[2] >= 384 || (pI && corr_mode == 3 && g.N[2] >= 128)) ? 8 : 4);
@@ -597,11 +597,11 @@ int ins_k_diffusion_flux3d(const ins_grid* G, double visc, const double* u, doub
   ins_grid* M = const_cast<ins_grid*>(G);
   if (!M->rec_diff_dev) {
     const size_t n = (size_t)g.N[0] + g.N[1] + g.N[2];
-    INS_HIP_TRY(hipMalloc(&M->rec_diff_dev, n * sizeof(Rec)));
+    if (int rc = M->rec_diff_dev.alloc(n * sizeof(Rec))) return rc;
     M->rec_diff_visc = -1.0;
   }
   if (M->rec_diff_visc != visc) {
-    Rec* r0 = reinterpret_cast<Rec*>(M->rec_diff_dev);
+    Rec* r0 = reinterpret_cast<Rec*>(M->rec_diff_dev.get());
     Rec* r1 = r0 + g.N[0];
     Rec* r2 = r1 + g.N[1];
     const int nmax = std::max(g.N[0], std::max(g.N[1], g.N[2]));
@@ -611,7 +611,7 @@ int ins_k_diffusion_flux3d(const ins_grid* G, double visc, const double* u, doub
   }
   RkEpi epi;
   memset(&epi, 0, sizeof(epi));
-  int rc = launch_flux_any<false>(G, u, F, epi, nullptr, 0, s, M->rec_diff_dev);
+  int rc = launch_flux_any<false>(G, u, F, epi, nullptr, 0, s, M->rec_diff_dev.get());
   if (rc || !zero_shell) return rc;
   const long long total = 2LL * ((long long)g.N[0] * g.N[1] + (long long)g.N[0] * g.N[2] + (long long)g.N[1] * g.N[2]);
   hipLaunchKernelGGL(k_zero_shell, dim3((unsigned)std::min<long long>((total + 255) / 256, 2048)), dim3(256), 0, s, g, F);

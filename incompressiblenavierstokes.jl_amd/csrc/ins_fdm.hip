@@ -20,11 +20,11 @@ struct ins_fdm {
   rocblas_handle h = nullptr;
   int D = 3;
   int n[3] = {1, 1, 1};
-  double* V[3] = {nullptr, nullptr, nullptr};    // n[a] x n[a], column-major, Dα-orthonormal eigenvectors
-  double* lam[3] = {nullptr, nullptr, nullptr};  // eigenvalues (<= 0)
-  double *a = nullptr, *b = nullptr;             // two n0*n1*n2 work arrays
-  double* sums = nullptr;                        // [0..4095] block partials of Σ p, [4096] mean(f), [4097] mean(p)
-  double* ones[3] = {nullptr, nullptr, nullptr};  // Vαᵀ 1: (Vx⊗Vy⊗Vz)ᵀ 1 = ones_x ⊗ ones_y ⊗ ones_z
+  DevBuf<double> V[3];                           // n[a] x n[a], column-major, Dα-orthonormal eigenvectors
+  DevBuf<double> lam[3];                         // eigenvalues (<= 0)
+  DevBuf<double> a, b;                           // two n0*n1*n2 work arrays
+  DevBuf<double> sums;                           // [0..4095] block partials of Σ p, [4096] mean(f), [4097] mean(p)
+  DevBuf<double> ones[3];                        // Vαᵀ 1: (Vx⊗Vy⊗Vz)ᵀ 1 = ones_x ⊗ ones_y ⊗ ones_z
   long long null_index = 0;                      // storage index of the null mode (λx = λy = λz = 0)
   double null_scale = 1.0;                       // V₀ = null_scale · 1  =>  Σ f = q[null] / null_scale
   bool singular = true;
@@ -34,29 +34,29 @@ struct ins_fdm {
   // periodic uniform z: Fourier modes instead of the dense Vz (ins_fdm_enable_zfft)
   bool zfft = false;
   bool zdct = false;        // uniform z between two walls: cosine modes (ins_fdm_enable_zdct), same fused pass in its DCT form
-  double* zwq = nullptr;    // e^{-iπk/2n2}, k = 0..n2/2
+  DevBuf<double> zwq;       // e^{-iπk/2n2}, k = 0..n2/2
   double hz = 0.0;
-  double* lzk = nullptr;    // λz(k), k = 0..n2/2
-  double* ztw = nullptr;    // twiddles
-  double* zpart = nullptr;  // block partials of the fused z kernel
+  DevBuf<double> lzk;       // λz(k), k = 0..n2/2
+  DevBuf<double> ztw;       // twiddles
+  DevBuf<double> zpart;     // block partials of the fused z kernel
   // periodic uniform x as well (channel flows): real-to-complex x passes (ins_fft.hip) instead of the dense Vx
   bool xfft = false;
   int kxs = 0;              // complex row stride of the half spectrum (n0/2+1 rounded up to 8)
   double hx = 0.0;
-  double* lxd = nullptr;    // λx per REAL slot of a spectrum row (re and im of a mode share it), 2 kxs
-  double* oxd = nullptr;    // Vxᵀ1 in that layout: sqrt(n0/hx) at the real part of kx = 0
-  double* xtw = nullptr;
+  DevBuf<double> lxd;       // λx per REAL slot of a spectrum row (re and im of a mode share it), 2 kxs
+  DevBuf<double> oxd;       // Vxᵀ1 in that layout: sqrt(n0/hx) at the real part of kx = 0
+  DevBuf<double> xtw;
   // periodic uniform x AND y with any z (walls in z: the orientation of TurbulentChannel.jl): x and y through the own FFT passes, z through Vz
   bool xyfft = false;
   double hy = 0.0;
-  double* lyp = nullptr;    // λy in the digit-reversed order the own y pass leaves behind
-  double* oyp = nullptr;    // Vyᵀ1 in that layout: sqrt(n1/hy) at position 0
-  double* ytw = nullptr;
+  DevBuf<double> lyp;       // λy in the digit-reversed order the own y pass leaves behind
+  DevBuf<double> oyp;       // Vyᵀ1 in that layout: sqrt(n1/hy) at position 0
+  DevBuf<double> ytw;
   // Symmetric directions (cosine / tanh / uniform walls: Tα and Dα commute with the reflection i -> n-1-i): every eigenvector is even or odd, so
   // with the modes ordered [even | odd] and the data folded into (f_i + f_{n-1-i} | f_i - f_{n-1-i}) a transform along that direction is two
   // GEMMs of half the size — half the flops of the dense transform.  Vh[a]: the top halves of the reordered eigenvectors, (n/2) x n, column-major.
   bool fold[3] = {false, false, false};
-  double* Vh[3] = {nullptr, nullptr, nullptr};
+  DevBuf<double> Vh[3];
 };
 
 namespace {
@@ -197,25 +197,6 @@ __global__ __launch_bounds__(256) void k_fdm_mean(double* __restrict__ sums, int
 int ins_fdm_destroy(ins_fdm* F) {
   if (!F) return INS_OK;
   if (F->h) (void)rocblas_destroy_handle(F->h);
-  for (int a = 0; a < 3; ++a) {
-    if (F->V[a]) (void)hipFree(F->V[a]);
-    if (F->lam[a]) (void)hipFree(F->lam[a]);
-    if (F->ones[a]) (void)hipFree(F->ones[a]);
-    if (F->Vh[a]) (void)hipFree(F->Vh[a]);
-  }
-  if (F->a) (void)hipFree(F->a);
-  if (F->b) (void)hipFree(F->b);
-  if (F->sums) (void)hipFree(F->sums);
-  if (F->lzk) (void)hipFree(F->lzk);
-  if (F->ztw) (void)hipFree(F->ztw);
-  if (F->zwq) (void)hipFree(F->zwq);
-  if (F->zpart) (void)hipFree(F->zpart);
-  if (F->lxd) (void)hipFree(F->lxd);
-  if (F->oxd) (void)hipFree(F->oxd);
-  if (F->xtw) (void)hipFree(F->xtw);
-  if (F->lyp) (void)hipFree(F->lyp);
-  if (F->oyp) (void)hipFree(F->oyp);
-  if (F->ytw) (void)hipFree(F->ytw);
   delete F;
   return INS_OK;
 }
@@ -283,27 +264,22 @@ int ins_fdm_create(int D, const int n[3], const double* const V[3], const double
     // 4/h_min²) and the lowest physical mode (~π²/L²), and on strongly stretched grids (cosine grid, N >= 1024) there is no such gap.
     std::vector<double> lam_up(la, la + n[a]);
     if (F->singular) lam_up[inull] = 0.0;
-    ok = hipMalloc(&F->V[a], (size_t)n[a] * n[a] * 8) == hipSuccess && hipMalloc(&F->lam[a], (size_t)n[a] * 8) == hipSuccess &&
-         hipMemcpy(F->V[a], Va, (size_t)n[a] * n[a] * 8, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(F->lam[a], lam_up.data(), (size_t)n[a] * 8, hipMemcpyHostToDevice) == hipSuccess;
+    ok = F->V[a].alloc_copy_host((size_t)n[a] * n[a], Va) == INS_OK && F->lam[a].alloc_copy_host(n[a], lam_up.data()) == INS_OK;
     if (ok && sym) {
       std::vector<double> top((size_t)hh * na);
       for (int j = 0; j < na; ++j)
         for (int i = 0; i < hh; ++i) top[i + (size_t)hh * j] = Va[i + (size_t)na * j];
-      ok = hipMalloc(&F->Vh[a], top.size() * 8) == hipSuccess && hipMemcpy(F->Vh[a], top.data(), top.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
+      ok = F->Vh[a].alloc_copy_host(top.size(), top.data()) == INS_OK;
     }
     for (int i = 0; i < n[a]; ++i) lmax = std::fmax(lmax, std::fabs(lam[a][i]));
     F->null_index += (long long)inull * (a == 0 ? 1 : (a == 1 ? n[0] : (long long)n[0] * n[1]));
     F->null_scale *= Va[(size_t)n[a] * inull];
     F->null_i[a] = inull;
     F->null_s[a] = Va[(size_t)n[a] * inull];
-    ok = ok && hipMalloc(&F->ones[a], (size_t)n[a] * 8) == hipSuccess &&
-         hipMemcpy(F->ones[a], o.data(), (size_t)n[a] * 8, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && F->ones[a].alloc_copy_host(n[a], o.data()) == INS_OK;
   }
-  ok = ok && hipMalloc(&F->a, total * 8) == hipSuccess && hipMalloc(&F->b, total * 8) == hipSuccess && hipMalloc(&F->sums, 4098 * 8) == hipSuccess &&
-       hipMemset(F->sums, 0, 4098 * 8) == hipSuccess;
-  if (!ok) {
-    ins_set_error("ins_fdm_create: allocation / upload failed");
+  ok = ok && F->a.alloc(total) == INS_OK && F->b.alloc(total) == INS_OK && F->sums.alloc_zero(4098) == INS_OK;
+  if (!ok) {  // the buffer that failed has recorded the message
     ins_fdm_destroy(F);
     return INS_ERR_HIP;
   }
@@ -332,13 +308,8 @@ int ins_fdm_enable_zfft(ins_fdm* F, double hz, const double* lam_z_host) {
   for (int k = 0; k < n2; ++k)
     if (std::fabs(want[k] - have[k]) > 1e-9 * scale) return INS_OK;
   const int nblk = (int)(((long long)(F->n[0] / 2) * F->n[1] + 7) / 8);
-  if (hipMalloc(&F->lzk, lzk.size() * 8) != hipSuccess || hipMemcpy(F->lzk, lzk.data(), lzk.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc(&F->zpart, (size_t)nblk * 8) != hipSuccess || hipMemset(F->zpart, 0, (size_t)nblk * 8) != hipSuccess) {
-    ins_set_error("ins_fdm_enable_zfft: allocation failed");
-    return INS_ERR_HIP;
-  }
-  int rc = ins_zsolve_twiddles(n2, &F->ztw);
-  if (rc) return rc;
+  int rc;
+  if ((rc = F->lzk.alloc_copy_host(lzk.size(), lzk.data())) || (rc = F->zpart.alloc_zero(nblk)) || (rc = ins_zsolve_twiddles(n2, &F->ztw))) return rc;
   F->hz = hz;
   F->zfft = true;
   F->fold[2] = false;
@@ -366,14 +337,10 @@ int ins_fdm_enable_zdct(ins_fdm* F, double hz, const double* lam_z_host) {
   for (int k = 0; k < n2; ++k)
     if (std::fabs(want[k] - have[k]) > 1e-9 * scale) return INS_OK;
   const int nblk = (int)(((long long)(F->n[0] / 2) * F->n[1] + 7) / 8);
-  if (hipMalloc(&F->lzk, lzk.size() * 8) != hipSuccess || hipMemcpy(F->lzk, lzk.data(), lzk.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc(&F->zwq, wq.size() * 8) != hipSuccess || hipMemcpy(F->zwq, wq.data(), wq.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc(&F->zpart, (size_t)nblk * 8) != hipSuccess || hipMemset(F->zpart, 0, (size_t)nblk * 8) != hipSuccess) {
-    ins_set_error("ins_fdm_enable_zdct: allocation failed");
-    return INS_ERR_HIP;
-  }
-  int rc = ins_zsolve_twiddles(n2, &F->ztw);
-  if (rc) return rc;
+  int rc;
+  if ((rc = F->lzk.alloc_copy_host(lzk.size(), lzk.data())) || (rc = F->zwq.alloc_copy_host(wq.size(), wq.data())) || (rc = F->zpart.alloc_zero(nblk)) ||
+      (rc = ins_zsolve_twiddles(n2, &F->ztw)))
+    return rc;
   F->hz = hz;
   F->zdct = true;
   F->fold[2] = false;
@@ -404,21 +371,13 @@ int ins_fdm_enable_xfft(ins_fdm* F, double hx, const double* lam_x_host) {
   oxd[0] = std::sqrt((double)n0 / hx);
   const size_t elems = std::max<size_t>((size_t)n0 * n1 * n2, (size_t)2 * kxs * n1 * n2);
   const int nblk = (int)(((long long)kxs * n1 + 7) / 8);
-  (void)hipFree(F->a);
-  (void)hipFree(F->b);
-  (void)hipFree(F->zpart);
-  F->a = F->b = F->zpart = nullptr;
-  bool ok = hipMalloc(&F->a, elems * 8) == hipSuccess && hipMalloc(&F->b, elems * 8) == hipSuccess && hipMemset(F->a, 0, elems * 8) == hipSuccess &&
-            hipMemset(F->b, 0, elems * 8) == hipSuccess && hipMalloc(&F->zpart, (size_t)nblk * 8) == hipSuccess &&
-            hipMemset(F->zpart, 0, (size_t)nblk * 8) == hipSuccess && hipMalloc(&F->lxd, lxd.size() * 8) == hipSuccess &&
-            hipMalloc(&F->oxd, oxd.size() * 8) == hipSuccess && hipMemcpy(F->lxd, lxd.data(), lxd.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(F->oxd, oxd.data(), oxd.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    ins_set_error("ins_fdm_enable_xfft: allocation failed");
-    return INS_ERR_HIP;
-  }
-  int rc = ins_zsolve_twiddles(n0, &F->xtw);
-  if (rc) return rc;
+  // the work arrays grow to hold the padded spectrum: all three go before the first comes back
+  F->a.reset(), F->b.reset(), F->zpart.reset();
+  int rc;
+  if ((rc = F->a.alloc_zero(elems)) || (rc = F->b.alloc_zero(elems)) || (rc = F->zpart.alloc_zero(nblk)) ||
+      (rc = F->lxd.alloc_copy_host(lxd.size(), lxd.data())) || (rc = F->oxd.alloc_copy_host(oxd.size(), oxd.data())) ||
+      (rc = ins_zsolve_twiddles(n0, &F->xtw)))
+    return rc;
   F->kxs = kxs;
   F->hx = hx;
   F->null_i[0] = 0;
@@ -463,23 +422,12 @@ int ins_fdm_enable_xyfft(ins_fdm* F, double hx, double hy, const double* lam_x_h
   oxd[0] = std::sqrt((double)n0 / hx);
   oyp[0] = std::sqrt((double)n1 / hy);  // frequency 0 sits at position 0
   const size_t elems = std::max<size_t>((size_t)n0 * n1 * n2, (size_t)2 * kxs * n1 * n2);
-  (void)hipFree(F->a);
-  (void)hipFree(F->b);
-  F->a = F->b = nullptr;
-  bool ok = hipMalloc(&F->a, elems * 8) == hipSuccess && hipMalloc(&F->b, elems * 8) == hipSuccess && hipMemset(F->a, 0, elems * 8) == hipSuccess &&
-            hipMemset(F->b, 0, elems * 8) == hipSuccess && hipMalloc(&F->lxd, lxd.size() * 8) == hipSuccess && hipMalloc(&F->oxd, oxd.size() * 8) == hipSuccess &&
-            hipMalloc(&F->lyp, lyp.size() * 8) == hipSuccess && hipMalloc(&F->oyp, oyp.size() * 8) == hipSuccess &&
-            hipMemcpy(F->lxd, lxd.data(), lxd.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(F->oxd, oxd.data(), oxd.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(F->lyp, lyp.data(), lyp.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(F->oyp, oyp.data(), oyp.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    ins_set_error("ins_fdm_enable_xyfft: allocation failed");
-    return INS_ERR_HIP;
-  }
-  int rc = ins_zsolve_twiddles(n0, &F->xtw);
-  if (rc) return rc;
-  if ((rc = ins_zsolve_twiddles(n1, &F->ytw))) return rc;
+  F->a.reset(), F->b.reset();
+  int rc;
+  if ((rc = F->a.alloc_zero(elems)) || (rc = F->b.alloc_zero(elems)) || (rc = F->lxd.alloc_copy_host(lxd.size(), lxd.data())) ||
+      (rc = F->oxd.alloc_copy_host(oxd.size(), oxd.data())) || (rc = F->lyp.alloc_copy_host(lyp.size(), lyp.data())) ||
+      (rc = F->oyp.alloc_copy_host(oyp.size(), oyp.data())) || (rc = ins_zsolve_twiddles(n0, &F->xtw)) || (rc = ins_zsolve_twiddles(n1, &F->ytw)))
+    return rc;
   F->kxs = kxs;
   F->hx = hx;
   F->hy = hy;

@@ -31,21 +31,11 @@ int ins_validate_real_plans(hipfftHandle fwd, hipfftHandle inv, int rank, const 
     s ^= s << 5;
     v = (double)(s >> 8) / (1 << 24) - 0.5;
   }
-  double *din = nullptr, *dback = nullptr;
-  hipfftDoubleComplex* dout = nullptr;
-  struct Guard {
-    double*& a;
-    double*& b;
-    hipfftDoubleComplex*& c;
-    ~Guard() {
-      if (a) (void)hipFree(a);
-      if (b) (void)hipFree(b);
-      if (c) (void)hipFree(c);
-    }
-  } guard{din, dback, dout};
-  INS_HIP_TRY(hipMalloc(&din, in.size() * sizeof(double)));
-  INS_HIP_TRY(hipMalloc(&dback, in.size() * sizeof(double)));
-  INS_HIP_TRY(hipMalloc(&dout, (size_t)ncplx * batch * sizeof(hipfftDoubleComplex)));
+  DevBuf<double> din, dback;
+  DevBuf<hipfftDoubleComplex> dout;
+  if (int rc = din.alloc(in.size())) return rc;
+  if (int rc = dback.alloc(in.size())) return rc;
+  if (int rc = dout.alloc((size_t)ncplx * batch)) return rc;
   INS_HIP_TRY(hipMemcpy(din, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice));
   INS_FFT_TRY(hipfftSetStream(fwd, nullptr));
   INS_FFT_TRY(hipfftSetStream(inv, nullptr));

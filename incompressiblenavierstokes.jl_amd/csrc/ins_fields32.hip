@@ -80,7 +80,7 @@ extern "C" int ins_cfl_timestep_f32(const ins_grid_t* G, float Re, const float* 
     dt_diff = fmin(dt_diff, (double)Re * damin * damin / 2);
   }
   // the grid's reduction scratch (4096 doubles on the device, pinned on the host) holds the workgroup partials and, behind them, the result
-  float* partial = reinterpret_cast<float*>(G->red_dev);
+  float* partial = reinterpret_cast<float*>(G->red_dev.get());
   const long long nrows = (long long)g.N[1] * (g.D == 3 ? g.N[2] : 1);
   const int nwg = (int)std::min<long long>((nrows + 3) / 4, CFL_MAX_WG);
   if (g.D == 2)
@@ -90,7 +90,7 @@ extern "C" int ins_cfl_timestep_f32(const ins_grid_t* G, float Re, const float* 
   INS_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_cfl32_finish, dim3(1), dim3(256), 0, s, (const float*)partial, nwg, partial + CFL_MAX_WG);
   INS_LAUNCH_CHECK();
-  float* host = reinterpret_cast<float*>(G->red_host);
+  float* host = reinterpret_cast<float*>(G->red_host.get());
   INS_HIP_TRY(hipMemcpyAsync(host, partial + CFL_MAX_WG, sizeof(float), hipMemcpyDeviceToHost, s));
   INS_HIP_TRY(hipStreamSynchronize(s));
   *out = (float)fmin(dt_diff, (double)host[0]);

@@ -464,7 +464,7 @@ int ins_k_flux64m(const ins_grid* G, double visc, const double* u, double* k_out
   a.N0 = g.N[0];
   a.N1 = g.N[1];
   a.N2 = g.N[2];
-  a.rx = reinterpret_cast<const Rec*>(G->rec_dev);
+  a.rx = reinterpret_cast<const Rec*>(G->rec_dev.get());
   a.ry = a.rx + g.N[0];
   a.rz = a.ry + g.N[1];
   for (int d = 0; d < 3; ++d) a.per[d] = g.bc[d][0] == INS_BC_PERIODIC;

@@ -75,19 +75,9 @@ extern "C" int ins_grid_create(const ins_grid_desc_t* d, ins_grid_t** out) {
         // A[a][b] is indexed along direction b and has N[b] entries (grid.jl:227-248)
         for (int i = 0; i < d->N[b]; ++i) h.push_back(src[i]);
       }
-  G->dev_count = h.size();
-  hipError_t e = hipMalloc(&G->dev, h.size() * sizeof(double));
-  if (e != hipSuccess) {
+  if (int rc = G->dev.alloc_copy_host(h.size(), h.data())) {
     delete G;
-    ins_set_error("hipMalloc(grid tables): %s", hipGetErrorString(e));
-    return INS_ERR_HIP;
-  }
-  e = hipMemcpy(G->dev, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(G->dev);
-    delete G;
-    ins_set_error("hipMemcpy(grid tables): %s", hipGetErrorString(e));
-    return INS_ERR_HIP;
+    return rc;
   }
 
   GridDev& g = G->g;
@@ -172,12 +162,11 @@ extern "C" int ins_grid_create(const ins_grid_desc_t* d, ins_grid_t** out) {
       if (!same) G->uniform_exact = false;
     }
   }
-  e = hipMalloc(&G->red_dev, 4096 * sizeof(double));
-  if (e == hipSuccess) e = hipHostMalloc(&G->red_host, 4096 * sizeof(double));
-  if (e != hipSuccess) {
-    ins_grid_destroy(G);
-    ins_set_error("grid scratch allocation: %s", hipGetErrorString(e));
-    return INS_ERR_HIP;
+  int rc = G->red_dev.alloc(4096);
+  if (rc == INS_OK) rc = G->red_host.alloc(4096);
+  if (rc != INS_OK) {
+    delete G;
+    return rc;
   }
   *out = G;
   return INS_OK;
@@ -187,13 +176,6 @@ extern "C" int ins_grid_is_uniform_exact(const ins_grid_t* G) { return G && G->u
 
 extern "C" int ins_grid_destroy(ins_grid_t* G) {
   if (!G) return INS_OK;
-  if (G->dev) (void)hipFree(G->dev);
-  if (G->red_dev) (void)hipFree(G->red_dev);
-  if (G->rec_dev) (void)hipFree(G->rec_dev);
-  if (G->rec_diff_dev) (void)hipFree(G->rec_diff_dev);
-  if (G->gradbar_dev) (void)hipFree(G->gradbar_dev);
-  if (G->smagpart_dev) (void)hipFree(G->smagpart_dev);
-  if (G->red_host) (void)hipHostFree(G->red_host);
   delete G;
   return INS_OK;
 }

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "ins_devbuf.h"
 #include "ins_hip.h"
 
 #define INS_EPS 2.220446049250313e-16
@@ -183,8 +184,7 @@ struct GridDev {
 struct ins_grid {
   ins_grid_desc_t desc;  // host copy (metric pointers below are re-pointed to `host`)
   std::vector<double> host;
-  double* dev = nullptr;  // one device slab holding every table
-  size_t dev_count = 0;
+  DevBuf<double> dev;  // one device slab holding every table
   GridDev g;
   bool all_periodic = false;
   bool uniform = false;
@@ -192,19 +192,17 @@ struct ins_grid {
   long long ncell = 0;      // prod(N)
   bool all_dof = false;        // every interior volume is a DOF of every component (all-periodic)
   bool uniform_exact = false;  // all metric records bitwise identical over the used index range
-  void* rec_dev = nullptr;     // flux-kernel metric records (ins_fast3d_flux.hip), built lazily
+  DevBuf<unsigned char> rec_dev;  // flux-kernel metric records (ins_fast3d_flux.hip), built lazily
   double rec_visc = -1.0;
-  void* rec_diff_dev = nullptr;  // the same records with zero interpolation weights: the flux kernels then evaluate diffusion!(F, u) alone
+  DevBuf<unsigned char> rec_diff_dev;  // the same records with zero interpolation weights: the flux kernels then evaluate diffusion!(F, u) alone
   double rec_diff_visc = -1.0;
   // scratch for blocking reductions
-  double* red_dev = nullptr;
-  double* red_host = nullptr;  // pinned
+  DevBuf<double> red_dev;
+  HostPinned<double> red_host;
   // ∇ubar of the tensor-basis pullbacks (ins_tensorclosure.hip): D·D scalar fields, allocated on first use
-  double* gradbar_dev = nullptr;
-  size_t gradbar_count = 0;
+  DevBuf<double> gradbar_dev;
   // workgroup partials of the Smagorinsky force pullback's θ cotangent (ins_smagpullback.hip), allocated on first use
-  double* smagpart_dev = nullptr;
-  size_t smagpart_count = 0;
+  DevBuf<double> smagpart_dev;
 };
 
 enum PoissonKind { POISSON_SPECTRAL = 0, POISSON_CG = 1, POISSON_FDM = 2 };
@@ -240,56 +238,55 @@ enum KyOrder { KY_NATURAL = 0, KY_DIGITREV, KY_LINE3 };  // rocFFT and the 2-D k
 
 struct ins_poisson {
   PoissonKind kind;
-  const ins_grid* grid;
+  const ins_grid* grid;  // borrowed
   // spectral
   hipfftHandle plan_fwd = 0, plan_inv = 0;
   SpectralRoute route = ROUTE_ROCFFT;
   KyOrder ky_order = KY_NATURAL;
-  double* pI = nullptr;            // real n^D
-  double* rhs = nullptr;           // real n^D, allocated on first use: Ω·div(u*) written by the stage kernel (ins_poisson_stage_rhs; pI is that kernel's pressure input)
-  hipfftDoubleComplex* phat = nullptr;  // (n/2+1) n [n]
-  double* ahat[3] = {nullptr, nullptr, nullptr};
+  DevBuf<double> pI;               // real n^D
+  DevBuf<double> rhs;              // real n^D, allocated on first use: Ω·div(u*) written by the stage kernel (ins_poisson_stage_rhs; pI is that kernel's pressure input)
+  DevBuf<hipfftDoubleComplex> phat;     // (n/2+1) n [n]
+  DevBuf<double> ahat[3];
   int np[3] = {1, 1, 1};
   int kmax[3] = {1, 1, 1};
-  void* work = nullptr;
-  size_t work_bytes = 0;
   hipStream_t plan_stream = nullptr;
   int kxs = 0;              // own routes: row stride of phat (kmax[0] rounded up to 8 complex = 128 B)
   bool spec_pending = false;  // a stage kernel has been handed phat for the x-spectrum of its right-hand side (ins_poisson_stage_spec) and no solve has consumed it yet
-  double* tw = nullptr;     // z twiddles
-  double* tw_x = nullptr;   // x / y twiddles (own routes)
-  double* tw_y = nullptr;
+  DevBuf<double> tw;        // z twiddles
+  DevBuf<double> tw_x;      // x / y twiddles (own routes)
+  DevBuf<double> tw_y;
   int yz_P = 0;             // ROUTE_OWN_YZ: partition count of the k_yz_* passes; 0 on every other route
-  double* yz_scratch = nullptr;
+  DevBuf<double> yz_scratch;
   // cg
   double abstol = 0, reltol = 0;
   long long maxiter = 0;
-  double *r = nullptr, *L = nullptr, *q = nullptr, *dinv = nullptr;
+  DevBuf<double> r, L, q, dinv;
   bool bordered = false;
   bool singular = true;  // no PressureBC side
   long long ndof = 0;
   long long last_iter = 0;
   double last_res = 0;
-  double* cg_scal = nullptr;  // device scalars + block partials of the device-resident iteration
-  double* cg_host = nullptr;  // pinned mirror of the scalars
-  struct ins_comm* comm = nullptr;  // z-slab CG: scalar all-reduces + ghost planes of q (ins_poisson_cg_set_comm)
+  DevBuf<double> cg_scal;     // device scalars + block partials of the device-resident iteration
+  HostPinned<double> cg_host;  // pinned mirror of the scalars
+  struct ins_comm* comm = nullptr;  // borrowed; z-slab CG: scalar all-reduces + ghost planes of q (ins_poisson_cg_set_comm)
   // fdm (psolver_direct)
-  ins_fdm* fdm = nullptr;
+  ins_fdm* fdm = nullptr;  // owned: ins_fdm_destroy
 };
 
 struct ins_rk_ext;  // temperature equation / closure state of the extended stage loop (ins_rk_ext.hip)
 void ins_rk_ext_free(ins_rk_ext* e);
 struct ins_rk {
-  const ins_grid* grid;
-  ins_poisson* ps;
+  const ins_grid* grid;  // borrowed
+  ins_poisson* ps;       // borrowed
   int nstage;
   std::vector<double> A, c;
-  double* ustart = nullptr;
-  std::vector<double*> ku;
-  double* p = nullptr;
-  double* ub[2] = {nullptr, nullptr};  // ping-pong stage velocities of the fused path
-  std::vector<double*> vb;        // all uncorrected stage velocities V_0..V_{s-2} (stage-velocity basis, ins_rk.hip)
-  const double* force = nullptr;  // steady body force field (caller-owned), ins_rk_set_bodyforce
+  DevBuf<double> ustart;
+  std::vector<DevBuf<double>> ku;
+  DevBuf<double> p;
+  DevBuf<double> ub[2];  // ping-pong stage velocities of the fused path
+  std::vector<double*> vb;  // borrowed: all uncorrected stage velocities V_0..V_{s-2} (stage-velocity basis, ins_rk.hip); ub[0], ub[1], then vb_extra
+  std::vector<DevBuf<double>> vb_extra;  // the arrays of vb beyond ub[0..1]
+  const double* force = nullptr;  // borrowed: steady body force field, ins_rk_set_bodyforce
   ins_rk_ext* ext = nullptr;
   long long stage_carry_launches = 0;  // stage kernels enqueued that stored a carried combination (ins_dbg_stage_carry_used)
   long long stage_rhs_launches = 0;  // stage kernels enqueued that wrote the Poisson right-hand side themselves (ins_dbg_stage_rhs_used)
@@ -556,7 +553,7 @@ int ins_k_ownfft_yz_solve(double* phat, int kxn, int n1, int n2, int kxs, int P,
                           double* scratch, hipStream_t s);
 int ins_k_ownfft_y_packed(double* phat, double* packed, int kxn, int n1, int nzl, int nyl, int cw, const double* tw, bool inverse,
                           hipStream_t s);
-int ins_zsolve_twiddles(int nz, double** out);
+int ins_zsolve_twiddles(int nz, DevBuf<double>* out);
 int ins_k_fdm_z(double* data, int n0, int n1, int nz, const double* lx, const double* ly, const double* lz, const double* ox, const double* oy,
                 double h, double tol, int singular, const double* meanf, double* partial, const double* tw, int* nblk, hipStream_t s, const double* dct_w = nullptr);
 int ins_k_zsolve(double* data, int nz, long long nl, const double* ax, int kxn, const double* ay, const double* az, const double* tw,

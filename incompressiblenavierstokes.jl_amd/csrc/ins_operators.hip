@@ -318,32 +318,26 @@ extern "C" int ins_kinetic_energy_f64(const ins_grid_t* G, const double* u, doub
   return INS_OK;
 }
 
-// Scratch scalar field for the blocking diagnostics (allocated per call: these are not on the step path).
-struct ScratchField {
-  double* p = nullptr;
-  ~ScratchField() {
-    if (p) (void)hipFree(p);
-  }
-};
+// The blocking diagnostics take their scratch scalar field per call (a local DevBuf): they are not on the step path.
 
 extern "C" int ins_total_kinetic_energy_f64(const ins_grid_t* G, const double* u, int interpolate_first, double* out, void* stream) {
   INS_ARGS2(G, u, out);
-  ScratchField ke;
-  INS_HIP_TRY(hipMalloc(&ke.p, G->ncell * sizeof(double)));
+  DevBuf<double> ke;
   hipStream_t s = as_stream(stream);
-  INS_HIP_TRY(hipMemsetAsync(ke.p, 0, G->ncell * sizeof(double), s));
-  int rc = ins_kinetic_energy_f64(G, u, ke.p, interpolate_first, stream);
+  int rc = ke.alloc_zero_async(G->ncell, s);
   if (rc) return rc;
-  rc = ins_k_scalewithvolume(G, ke.p, s);
+  rc = ins_kinetic_energy_f64(G, u, ke.get(), interpolate_first, stream);
   if (rc) return rc;
-  return ins_k_reduce(G, 3, ke.p, nullptr, G->g.ip_lo, G->g.ip_hi, out, s);
+  rc = ins_k_scalewithvolume(G, ke.get(), s);
+  if (rc) return rc;
+  return ins_k_reduce(G, 3, ke.get(), nullptr, G->g.ip_lo, G->g.ip_hi, out, s);
 }
 
 extern "C" int ins_cfl_timestep_f64(const ins_grid_t* G, double Re, const double* u, double* out, void* stream) {
   INS_ARGS2(G, u, out);
   const GridDev& g = G->g;
-  ScratchField buf;
-  INS_HIP_TRY(hipMalloc(&buf.p, G->ncell * sizeof(double)));
+  DevBuf<double> buf;
+  if (int rc = buf.alloc(G->ncell)) return rc;
   hipStream_t s = as_stream(stream);
   double dt = INFINITY;
   for (int a = 0; a < g.D; ++a) {
@@ -351,9 +345,9 @@ extern "C" int ins_cfl_timestep_f64(const ins_grid_t* G, double Re, const double
     for (int i = g.iu_lo[a][a]; i < g.iu_hi[a][a]; ++i) damin = fmin(damin, G->desc.dxu[a][i]);
     const double dt_diff = Re * damin * damin / 2;
     Launch3 l = box_launch(g.D, g.N);
-    INS_LAUNCH_D((k_cfl<D>), l, s, g, u, a, buf.p);
+    INS_LAUNCH_D((k_cfl<D>), l, s, g, u, a, buf.get());
     double dt_conv;
-    int rc = ins_k_reduce(G, 2, buf.p, nullptr, g.iu_lo[a], g.iu_hi[a], &dt_conv, s);
+    int rc = ins_k_reduce(G, 2, buf.get(), nullptr, g.iu_lo[a], g.iu_hi[a], &dt_conv, s);
     if (rc) return rc;
     dt = fmin(dt, fmin(dt_diff, dt_conv));
   }
@@ -363,10 +357,11 @@ extern "C" int ins_cfl_timestep_f64(const ins_grid_t* G, double Re, const double
 
 extern "C" int ins_max_abs_divergence_f64(const ins_grid_t* G, const double* u, double* out, void* stream) {
   INS_ARGS2(G, u, out);
-  ScratchField d;
-  INS_HIP_TRY(hipMalloc(&d.p, G->ncell * sizeof(double)));
+  DevBuf<double> d;
   hipStream_t s = as_stream(stream);
-  int rc = ins_k_divergence(G, u, d.p, s);
+  int rc = d.alloc(G->ncell);
   if (rc) return rc;
-  return ins_k_reduce(G, 1, d.p, nullptr, G->g.ip_lo, G->g.ip_hi, out, s);
+  rc = ins_k_divergence(G, u, d.get(), s);
+  if (rc) return rc;
+  return ins_k_reduce(G, 1, d.get(), nullptr, G->g.ip_lo, G->g.ip_hi, out, s);
 }

@@ -865,11 +865,7 @@ extern "C" int ins_poisson_spectral_create(const ins_grid_t* G, ins_poisson_t** 
     ps->kxs = ins_opt(OPT_INS_PHAT_DENSE) ? ps->kmax[0] : ((ps->kmax[0] + 7) & ~7);
     ncplx = (long long)ps->kxs * ps->kmax[1] * ps->kmax[2];
   }
-  if (hipMalloc(&ps->pI, nreal * sizeof(double)) != hipSuccess || hipMalloc(&ps->phat, ncplx * sizeof(hipfftDoubleComplex)) != hipSuccess ||
-      hipMemset(ps->phat, 0, ncplx * sizeof(hipfftDoubleComplex)) != hipSuccess) {
-    ins_set_error("hipMalloc(pI/phat) failed for %lld cells", nreal);
-    return fail(INS_ERR_HIP);
-  }
+  if ((rc = ps->pI.alloc(nreal)) || (rc = ps->phat.alloc_zero(ncplx))) return fail(rc);
   // ahat[α][k] = 4 Ω sinpi(k/Np[α])² / Δx[α]²                                      pressure.jl:305-311
   for (int a = 0; a < D; ++a) {
     std::vector<double> ah(ps->kmax[a]);
@@ -882,28 +878,21 @@ extern "C" int ins_poisson_spectral_create(const ins_grid_t* G, ins_poisson_t** 
       permute_ky(ps->ky_order, ps->np[1], ah.data(), perm.data());
       ah.swap(perm);
     }
-    if (hipMalloc(&ps->ahat[a], ah.size() * sizeof(double)) != hipSuccess ||
-        hipMemcpy(ps->ahat[a], ah.data(), ah.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-      ins_set_error("ahat upload failed");
-      return fail(INS_ERR_HIP);
-    }
+    if ((rc = ps->ahat[a].alloc_copy_host(ah.size(), ah.data()))) return fail(rc);
   }
   if (own2d) {  // own x passes around the fused solve kernel run along y (FFT · symbol · inverse FFT in one pass): three kernels instead of rocFFT's
                 // eight plus its three staging copies per solve
     if ((rc = ins_zsolve_twiddles(ps->np[0], &ps->tw_x))) return fail(rc);
     if ((rc = ins_zsolve_twiddles(ps->np[1], &ps->tw))) return fail(rc);
     // the solve kernel adds ay[line / kxs] to the symbol: one "row" of lines here, contributing nothing
-    if (hipMalloc(&ps->ahat[2], sizeof(double)) != hipSuccess || hipMemset(ps->ahat[2], 0, sizeof(double)) != hipSuccess) return fail(INS_ERR_HIP);
+    if ((rc = ps->ahat[2].alloc_zero(1))) return fail(rc);
   } else if (own) {  // no rocFFT plans at all
     if ((rc = ins_zsolve_twiddles(ps->np[0], &ps->tw_x))) return fail(rc);
     if ((rc = ins_zsolve_twiddles(ps->np[1], &ps->tw_y))) return fail(rc);
     if ((rc = ins_zsolve_twiddles(ps->np[2], &ps->tw))) return fail(rc);
     if (ps->route == ROUTE_OWN_YZ) {  // four passes instead of five: the z direction as tridiagonal systems carried by the two y passes (ins_fft.hip, k_yz_*)
       const long long nc = ins_ownfft_yz_scratch(ps->kmax[0], ps->np[1], ps->np[2], ps->yz_P);
-      if (hipMalloc(&ps->yz_scratch, nc * 2 * sizeof(double)) != hipSuccess) {
-        ins_set_error("hipMalloc(yz scratch) failed");
-        return fail(INS_ERR_HIP);
-      }
+      if ((rc = ps->yz_scratch.alloc(nc * 2))) return fail(rc);
     }
   } else {
     // plan_rfft(pI): all D dims, real -> half-complex along x (pressure.jl:316); hipFFT takes lengths slowest first.
@@ -937,7 +926,7 @@ static bool route_starts_with_xfwd(SpectralRoute r) { return r == ROUTE_OWN_LDS 
 static int spectral_transform(ins_poisson* ps, hipStream_t s, const double* u = nullptr, int src = XSRC_DIV, const double* rhs = nullptr) {
   const GridDev& g = ps->grid->g;
   const int n0 = ps->np[0], n1 = ps->np[1], n2 = ps->np[2], kxn = ps->kmax[0], kxs = ps->kxs;
-  double* ph = reinterpret_cast<double*>(ps->phat);
+  double* ph = reinterpret_cast<double*>(ps->phat.get());
   if (rhs) u = nullptr;
   const double* f = u ? u : (rhs ? rhs : ps->pI);
   const bool from_spec = src == XSRC_SPEC;
@@ -1040,12 +1029,10 @@ extern "C" int ins_poisson_cg_create(const ins_grid_t* G, double abstol, double 
   ps->ndof = ndof;
   for (int a = 0; a < g.D; ++a)
     if (g.bc[a][0] == INS_BC_PRESSURE || g.bc[a][1] == INS_BC_PRESSURE) ps->singular = false;
-  const size_t bytes = G->ncell * sizeof(double);
-  if (hipMalloc(&ps->r, bytes) != hipSuccess || hipMalloc(&ps->L, bytes) != hipSuccess || hipMalloc(&ps->q, bytes) != hipSuccess ||
-      hipMalloc(&ps->dinv, bytes) != hipSuccess) {
-    ins_set_error("hipMalloc(cg scratch) failed");
+  int rca;
+  if ((rca = ps->r.alloc(G->ncell)) || (rca = ps->L.alloc(G->ncell)) || (rca = ps->q.alloc(G->ncell)) || (rca = ps->dinv.alloc(G->ncell))) {
     ins_poisson_destroy(ps);
-    return INS_ERR_HIP;
+    return rca;
   }
   BoxLaunch l = full_box(g);
   if (g.D == 2)
@@ -1091,8 +1078,8 @@ static int cg_solve_device(ins_poisson* ps, double* p, hipStream_t s) {
   const GridDev& g = G->g;
   const long long n = G->ncell;
   if (!ps->cg_scal) {
-    INS_HIP_TRY(hipMalloc(&ps->cg_scal, (CG_NSCAL + CG_NPART) * sizeof(double)));
-    INS_HIP_TRY(hipHostMalloc(&ps->cg_host, CG_NSCAL * sizeof(double)));
+    if (int rc = ps->cg_scal.alloc(CG_NSCAL + CG_NPART)) return rc;
+    if (int rc = ps->cg_host.alloc(CG_NSCAL)) return rc;
   }
   double* sc = ps->cg_scal;
   double* partial = sc + CG_NSCAL;
@@ -1147,13 +1134,9 @@ static int cg_solve(ins_poisson* ps, double* p, hipStream_t s) {
   const ins_grid* G = ps->grid;
   const GridDev& g = G->g;
   BoxLaunch l = full_box(g);
-  double* partial = nullptr;
-  INS_HIP_TRY(hipMalloc(&partial, l.nblk * sizeof(double)));
-  struct Guard {
-    double* p;
-    ~Guard() { (void)hipFree(p); }
-  } guard{partial};
+  DevBuf<double> partial;
   int rc;
+  if ((rc = partial.alloc(l.nblk))) return rc;
   double ss;
   const bool bordered = ps->bordered && ps->singular;
   if (bordered && (rc = cg_remove_mean(ps, p, s))) return rc;
@@ -1230,21 +1213,6 @@ extern "C" int ins_poisson_destroy(ins_poisson_t* ps) {
     (void)hipfftDestroy(ps->plan_inv);
     ins_fft_solver_released();
   }
-  if (ps->tw) (void)hipFree(ps->tw);
-  if (ps->tw_x) (void)hipFree(ps->tw_x);
-  if (ps->tw_y) (void)hipFree(ps->tw_y);
-  if (ps->yz_scratch) (void)hipFree(ps->yz_scratch);
-  if (ps->pI) (void)hipFree(ps->pI);
-  if (ps->rhs) (void)hipFree(ps->rhs);
-  if (ps->phat) (void)hipFree(ps->phat);
-  for (int a = 0; a < 3; ++a)
-    if (ps->ahat[a]) (void)hipFree(ps->ahat[a]);
-  if (ps->r) (void)hipFree(ps->r);
-  if (ps->cg_scal) (void)hipFree(ps->cg_scal);
-  if (ps->cg_host) (void)hipHostFree(ps->cg_host);
-  if (ps->L) (void)hipFree(ps->L);
-  if (ps->q) (void)hipFree(ps->q);
-  if (ps->dinv) (void)hipFree(ps->dinv);
   if (ps->fdm) (void)ins_fdm_destroy(ps->fdm);
   delete ps;
   return INS_OK;
@@ -1543,10 +1511,7 @@ int ins_k_grad_ghost_members_2d(const ins_grid* G, const ins_poisson* ps, double
 bool ins_k_spectral_own3d(const ins_poisson* ps) { return ps->kind == POISSON_SPECTRAL && own_route(ps->route) && ps->grid->g.D == 3; }
 double* ins_poisson_stage_rhs(ins_poisson* ps) {
   if (!ins_k_spectral_own3d(ps)) return nullptr;
-  if (!ps->rhs && hipMalloc(&ps->rhs, (size_t)ps->np[0] * ps->np[1] * ps->np[2] * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    ps->rhs = nullptr;
-  }
+  if (!ps->rhs) (void)ps->rhs.alloc((size_t)ps->np[0] * ps->np[1] * ps->np[2]);  // failure: nullptr, the caller keeps the route without it
   return ps->rhs;
 }
 // phat as the output of a stage kernel whose pressure input is pI_in (ins_internal.h).  Stream order is the only thing between that launch and the y pass: the
@@ -1559,7 +1524,7 @@ double* ins_poisson_stage_spec(ins_poisson* ps, const void* pI_in, const double*
   ps->spec_pending = true;
   *tw = ps->tw_x;
   *kxs = ps->kxs;
-  return reinterpret_cast<double*>(ps->phat);
+  return reinterpret_cast<double*>(ps->phat.get());
 }
 int ins_k_spectral_solve_from_u32(ins_poisson* ps, const float* u32, hipStream_t s) {
   return spectral_transform(ps, s, reinterpret_cast<const double*>(u32), XSRC_DIV_U32);

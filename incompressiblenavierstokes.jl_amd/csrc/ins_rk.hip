@@ -87,16 +87,14 @@ extern "C" int ins_rk_create(const ins_grid_t* G, ins_poisson_t* ps, int nstage,
   rk->nstage = nstage;
   rk->A.assign(A, A + nstage * nstage);
   rk->c.assign(c, c + nstage);
-  const size_t vbytes = (size_t)G->ncell * G->g.D * sizeof(double);
-  bool ok = hipMalloc(&rk->ustart, vbytes) == hipSuccess && hipMalloc(&rk->p, G->ncell * sizeof(double)) == hipSuccess;
-  rk->ku.assign(nstage, nullptr);
-  for (int i = 0; ok && i < nstage; ++i) ok = hipMalloc(&rk->ku[i], vbytes) == hipSuccess;
-  if (ok) ok = hipMemset(rk->p, 0, G->ncell * sizeof(double)) == hipSuccess && hipMemset(rk->ustart, 0, vbytes) == hipSuccess;
-  for (int i = 0; ok && i < nstage; ++i) ok = hipMemset(rk->ku[i], 0, vbytes) == hipSuccess;
-  if (!ok) {
-    ins_set_error("ins_rk_create: device allocation of %d vector fields failed", nstage + 1);
+  const size_t nvec = (size_t)G->ncell * G->g.D;
+  rk->ku.resize(nstage);
+  int rc = rk->ustart.alloc_zero(nvec);
+  if (rc == INS_OK) rc = rk->p.alloc_zero(G->ncell);
+  for (int i = 0; rc == INS_OK && i < nstage; ++i) rc = rk->ku[i].alloc_zero(nvec);
+  if (rc != INS_OK) {
     ins_rk_destroy(rk);
-    return INS_ERR_HIP;
+    return rc;
   }
   *out = rk;
   return INS_OK;
@@ -104,14 +102,6 @@ extern "C" int ins_rk_create(const ins_grid_t* G, ins_poisson_t* ps, int nstage,
 
 extern "C" int ins_rk_destroy(ins_rk_t* rk) {
   if (!rk) return INS_OK;
-  if (rk->ustart) (void)hipFree(rk->ustart);
-  if (rk->p) (void)hipFree(rk->p);
-  for (double* k : rk->ku)
-    if (k) (void)hipFree(k);
-  for (double* v : rk->vb)
-    if (v && v != rk->ub[0] && v != rk->ub[1]) (void)hipFree(v);
-  for (double* b : rk->ub)
-    if (b) (void)hipFree(b);
   for (hipEvent_t e : rk->prof_events) (void)hipEventDestroy(e);
   ins_rk_ext_free(rk->ext);
   step_graph_free(rk);
@@ -318,11 +308,8 @@ static int timed_stage(ins_rk* rk, hipStream_t s, F&& launch) {
 int ins_rk_ensure_ub(ins_rk* rk, size_t bytes, hipStream_t s, const double* init_from) {
   for (int b = 0; b < 2; ++b)
     if (!rk->ub[b]) {
-      INS_HIP_TRY(hipMalloc(&rk->ub[b], bytes));
-      if (init_from)
-        INS_HIP_TRY(hipMemcpyAsync(rk->ub[b], init_from, bytes, hipMemcpyDeviceToDevice, s));
-      else
-        INS_HIP_TRY(hipMemsetAsync(rk->ub[b], 0, bytes, s));
+      const size_t n = bytes / sizeof(double);
+      if (int rc = init_from ? rk->ub[b].alloc_copy_device(n, init_from, s) : rk->ub[b].alloc_zero_async(n, s)) return rc;
     }
   return INS_OK;
 }
@@ -358,8 +345,9 @@ static int rk_step_fused_periodic(ins_rk* rk, double visc, double* u, double dt,
           rk->vb[m] = rk->ub[m];
           continue;
         }
-        INS_HIP_TRY(hipMalloc(&rk->vb[m], vbytes));
-        INS_HIP_TRY(hipMemsetAsync(rk->vb[m], 0, vbytes, s));
+        rk->vb_extra.emplace_back();
+        if (int rc2 = rk->vb_extra.back().alloc_zero_async(vbytes / sizeof(double), s)) return rc2;
+        rk->vb[m] = rk->vb_extra.back();
       }
   }
   // Carry plan (ins_rk_terms.h; INS_DISABLE_STAGE_CARRY=1 switches it off): stage pl.j also stores S, the part of the last stage's combination it has in
@@ -371,10 +359,12 @@ static int rk_step_fused_periodic(ins_rk* rk, double visc, double* u, double dt,
   if (vbasis && ins_flux64_stage_carry_supported(G)) pl = ins_rk_carry_plan(rk->A.data(), ns);
   const bool carry = pl.j >= 0;
   const double* in = u;
+  double* tab[INS_MAX_STAGES];  // the arrays of the earlier stages in this basis: V_m or k_m
+  for (int m = 0; m < ns - 1; ++m) tab[m] = vbasis ? rk->vb[m] : rk->ku[m].get();
   for (int i = 0; i < ns; ++i) {
     double* out = (i == ns - 1 && ns > 1) ? u : (vbasis ? rk->vb[(carry && i == pl.j + 1) ? pl.j - 1 : i] : rk->ub[i & 1]);
     // the V_m live in rk->vb; V_{i-1}, the stencil input, comes from registers on the 64-wide kernel only (the 62-wide one keeps no uncorrected copy)
-    RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, vbasis ? rk->vb.data() : rk->ku.data(), rk->force, vbasis ? RK_V_BASIS : RK_K_BASIS,
+    RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, tab, rk->force, vbasis ? RK_V_BASIS : RK_K_BASIS,
                                    vbasis && ins_flux64_supported(G), RK_FORCE_DIAG_FIRST);
     epi.ustart = (i == 0) ? nullptr : (raw_in ? rk->ustart : u);  // raw_in: the corrected start field lives in the cache array
     epi.ustar = out;
@@ -444,7 +434,7 @@ static int rk_step_fused_periodic_2d(ins_rk* rk, double visc, double* u, double 
   const double* in = u;
   for (int i = 0; i < ns; ++i) {
     double* out = (i == ns - 1 && ns > 1) ? u : rk->ub[i & 1];
-    RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, RK_K_BASIS, false, RK_FORCE_INDEX_ORDER);  // k-basis only
+    RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku, rk->force, RK_K_BASIS, false, RK_FORCE_INDEX_ORDER);  // k-basis only
     epi.ustart = (i == 0) ? nullptr : (raw_in ? rk->ustart : u);  // raw_in: the corrected start field lives in the cache array
     epi.ustar = out;
     if (i == 0 && raw_in) epi.ustart_out = rk->ustart;
@@ -611,18 +601,9 @@ static int rk_step_any(ins_rk_t* rk, double visc, double* u, double dt, const do
   if (!planes && ins_rk_fused3d(rk)) return rk_step_fused_periodic(rk, visc, u, dt, s);
   if (!planes && ins_rk_fused2d(rk)) return rk_step_fused_periodic_2d(rk, visc, u, dt, s);
   const long long nvec = G->ncell * G->g.D;
-  const double** dplanes = nullptr;
-  struct Guard {
-    const double** p;
-    ~Guard() {
-      if (p) (void)hipFree(p);
-    }
-  } guard{nullptr};
-  if (planes) {
-    INS_HIP_TRY(hipMalloc(&dplanes, (size_t)nsets * 18 * sizeof(double*)));
-    guard.p = dplanes;
-    INS_HIP_TRY(hipMemcpy(dplanes, planes, (size_t)nsets * 18 * sizeof(double*), hipMemcpyHostToDevice));
-  }
+  DevBuf<const double*> dplanes;
+  if (planes)
+    if (int rc0 = dplanes.alloc_copy_host((size_t)nsets * 18, planes)) return rc0;
   auto pset = [&](int q) -> const double** { return dplanes ? dplanes + 18 * (nsets > 1 ? q : 0) : nullptr; };
   int rc;
   const int ns = rk->nstage;
@@ -649,7 +630,7 @@ static int rk_step_any(ins_rk_t* rk, double visc, double* u, double dt, const do
       if (!corr_in && (rc = ins_k_apply_bc_u(G, cur, 0, nullptr, s))) return rc;  // :19 (corr_in: `cur` got its boundary data at :48 already)
       double* out = (i == ns - 1 && ns > 1) ? u : (vbasis ? rk->ku[i] : rk->ub[i & 1]);
       // the V_m live in the ku arrays; the tiled kernels read V_{i-1} from memory like every other term (no self_in)
-      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, vbasis ? RK_V_BASIS : RK_K_BASIS, false, RK_FORCE_DIAG_FIRST);
+      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku, rk->force, vbasis ? RK_V_BASIS : RK_K_BASIS, false, RK_FORCE_DIAG_FIRST);
       epi.ustart = (i == 0) ? nullptr : u;
       epi.ustar = out;
       rc = timed_stage(rk, s, [&] {  // :21, :35-38
@@ -679,7 +660,7 @@ static int rk_step_any(ins_rk_t* rk, double visc, double* u, double dt, const do
     });
     if (rc) return rc;
     Combine cb;                                                               // :35-38
-    cb.n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, cb.coef, cb.k);
+    cb.n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku, rk->force, cb.coef, cb.k);
     const unsigned nblk = (unsigned)std::min<long long>((nvec / 2 + 255) / 256, 8192);
     hipLaunchKernelGGL(k_combine, dim3(nblk), dim3(256), 0, s, nvec, rk->ustart, u, cb);
     INS_LAUNCH_CHECK();

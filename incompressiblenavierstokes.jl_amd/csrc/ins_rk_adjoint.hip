@@ -43,14 +43,6 @@ __global__ __launch_bounds__(256) void k_weighted_sum(long long n, double* __res
 template <typename ADJ>
 int adjoint_destroy(ADJ* adj) {
   if (!adj) return INS_OK;
-  for (auto* arrays : {&adj->v, &adj->y, &adj->tau, &adj->z})
-    for (auto* p : *arrays)
-      if (p) (void)hipFree(p);
-  if (adj->kbar) (void)hipFree(adj->kbar);
-  if (adj->pwork) (void)hipFree(adj->pwork);
-  if (adj->cbar) (void)hipFree(adj->cbar);
-  if (adj->mforce) (void)hipFree(adj->mforce);
-  if (adj->sigma) (void)hipFree(adj->sigma);
   delete adj;
   return INS_OK;
 }
@@ -72,18 +64,16 @@ int adjoint_create(const ins_grid* G, PS* ps, int nstage, const double* A, const
   adj->nstage = nstage;
   adj->A.assign(A, A + nstage * nstage);
   adj->c.assign(c, c + nstage);
-  adj->v.assign(nstage, nullptr);
-  adj->y.assign(nstage, nullptr);
-  const size_t vbytes = (size_t)G->ncell * G->g.D * sizeof(T), sbytes = (size_t)G->ncell * sizeof(T);
-  bool ok = hipMalloc(&adj->kbar, vbytes) == hipSuccess && hipMalloc(&adj->pwork, sbytes) == hipSuccess;
-  for (int i = 0; ok && i < nstage; ++i) ok = hipMalloc(&adj->v[i], vbytes) == hipSuccess && hipMalloc(&adj->y[i], vbytes) == hipSuccess;
-  if (ok) ok = hipMemset(adj->pwork, 0, sbytes) == hipSuccess && hipMemset(adj->kbar, 0, vbytes) == hipSuccess;
-  for (int i = 0; ok && i < nstage; ++i) ok = hipMemset(adj->v[i], 0, vbytes) == hipSuccess && hipMemset(adj->y[i], 0, vbytes) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    ins_set_error("%s: device allocation of %d vector fields failed", name, 2 * nstage + 1);
+  adj->v.resize(nstage);
+  adj->y.resize(nstage);
+  const size_t nvec = (size_t)G->ncell * G->g.D;
+  int rc = adj->kbar.alloc_zero(nvec);
+  if (rc == INS_OK) rc = adj->pwork.alloc_zero(G->ncell);
+  for (int i = 0; rc == INS_OK && i < nstage; ++i)
+    if ((rc = adj->v[i].alloc_zero(nvec)) == INS_OK) rc = adj->y[i].alloc_zero(nvec);
+  if (rc != INS_OK) {
     adjoint_destroy(adj);
-    return INS_ERR_HIP;
+    return rc;
   }
   *out = adj;
   return INS_OK;
@@ -101,22 +91,16 @@ int adjoint_set_temperature(RkAdjointT<T, PS>* adj, const ins_temperature_desc_t
   for (int q = 0; q < 2 * D; ++q)
     INS_REQUIRE(desc->bc[q] == INS_BC_PERIODIC || desc->bc[q] == INS_BC_DIRICHLET || desc->bc[q] == INS_BC_SYMMETRIC || desc->bc[q] == INS_BC_PRESSURE,
                 "unsupported temperature boundary condition");
-  const size_t sbytes = (size_t)adj->grid->ncell * sizeof(T);
+  const size_t ncell = (size_t)adj->grid->ncell;
   if (!adj->cbar) {
-    adj->tau.assign(ns, nullptr);
-    adj->z.assign(ns, nullptr);
-    bool ok = hipMalloc(&adj->cbar, sbytes) == hipSuccess && hipMemset(adj->cbar, 0, sbytes) == hipSuccess;
-    for (int i = 0; ok && i < ns; ++i)
-      ok = hipMalloc(&adj->tau[i], sbytes) == hipSuccess && hipMalloc(&adj->z[i], sbytes) == hipSuccess && hipMemset(adj->tau[i], 0, sbytes) == hipSuccess &&
-           hipMemset(adj->z[i], 0, sbytes) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      for (auto* arrays : {&adj->tau, &adj->z})
-        for (auto*& p : *arrays)
-          if (p) (void)hipFree(p), p = nullptr;
-      if (adj->cbar) (void)hipFree(adj->cbar), adj->cbar = nullptr;
-      ins_set_error("ins_rk_adjoint_set_temperature: device allocation of %d scalar fields failed", 2 * ns + 1);
-      return INS_ERR_HIP;
+    adj->tau.clear(), adj->z.clear();
+    adj->tau.resize(ns), adj->z.resize(ns);
+    int rc = adj->cbar.alloc_zero(ncell);
+    for (int i = 0; rc == INS_OK && i < ns; ++i)
+      if ((rc = adj->tau[i].alloc_zero(ncell)) == INS_OK) rc = adj->z[i].alloc_zero(ncell);
+    if (rc != INS_OK) {
+      adj->tau.clear(), adj->z.clear(), adj->cbar.reset();
+      return rc;
     }
   }
   adj->td = *desc;
@@ -134,14 +118,11 @@ int adjoint_set_closure(RkAdjointT<T, PS>* adj, int32_t kind, double theta, doub
     const int D = G->g.D;
     const size_t vbytes = (size_t)G->ncell * D * sizeof(T), tbytes = (size_t)G->ncell * (D * (D + 1) / 2) * sizeof(T);
     const bool need_sigma = ins_smagorinsky_force_needs_sigma(G) != 0;
-    bool ok = hipMalloc(&adj->mforce, vbytes) == hipSuccess && hipMemset(adj->mforce, 0, vbytes) == hipSuccess;
-    if (ok && need_sigma) ok = hipMalloc(&adj->sigma, tbytes) == hipSuccess && hipMemset(adj->sigma, 0, tbytes) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      if (adj->mforce) (void)hipFree(adj->mforce), adj->mforce = nullptr;
-      if (adj->sigma) (void)hipFree(adj->sigma), adj->sigma = nullptr;
-      ins_set_error("ins_rk_adjoint_set_closure: device allocation of the closure scratch failed");
-      return INS_ERR_HIP;
+    int rc = adj->mforce.alloc_zero(vbytes / sizeof(T));
+    if (rc == INS_OK && need_sigma) rc = adj->sigma.alloc_zero(tbytes / sizeof(T));
+    if (rc != INS_OK) {
+      adj->mforce.reset(), adj->sigma.reset();
+      return rc;
     }
   }
   adj->closure_kind = kind;
@@ -246,7 +227,7 @@ extern "C" int ins_rk_step_pullback_f64(ins_rk_adjoint_t* adj, double visc, cons
     if ((rc = ins_k_momentum(G, visc, adj->v[i], adj->y[i], s))) return rc;  // :21
     double coef[INS_MAX_STAGES + 1];
     const double* k[INS_MAX_STAGES + 1];
-    const int n = ins_rk_sum_terms(A, ns, i, dt, adj->y.data(), bodyforce, coef, k);  // :35-38
+    const int n = ins_rk_sum_terms(A, ns, i, dt, adj->y, bodyforce, coef, k);  // :35-38
     if ((rc = ins_combine_f64(G, ustart, adj->v[i + 1], n, coef, k, stream))) return rc;
     if ((rc = ins_k_apply_bc_u(G, adj->v[i + 1], 0, nullptr, s))) return rc;          // :48
     if ((rc = ins_k_project(G, adj->ps, adj->v[i + 1], adj->pwork, s))) return rc;    // :49
@@ -284,6 +265,7 @@ extern "C" int ins_rk_step_pullback_f64(ins_rk_adjoint_t* adj, double visc, cons
   }
   if ((rc = ins_k_apply_bc_u_pullback(G, ubar, s))) return rc;  // :19 of stage 0
   double one[INS_MAX_STAGES];
-  for (int i = 0; i < ns; ++i) one[i] = 1.0;
-  return ins_combine_f64(G, ubar, ubar, ns, one, adj->y.data(), stream);
+  const double* ybar[INS_MAX_STAGES];
+  for (int i = 0; i < ns; ++i) one[i] = 1.0, ybar[i] = adj->y[i];
+  return ins_combine_f64(G, ubar, ubar, ns, one, ybar, stream);
 }

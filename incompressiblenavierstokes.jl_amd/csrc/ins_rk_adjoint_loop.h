@@ -31,26 +31,26 @@
 // and cbar, allocated by set_temperature.
 template <typename T, typename PS>
 struct RkAdjointT {
-  const ins_grid* grid = nullptr;
-  PS* ps = nullptr;
+  const ins_grid* grid = nullptr;  // borrowed
+  PS* ps = nullptr;                // borrowed
   int nstage = 0;
   std::vector<double> A, c;
-  std::vector<T*> v;  // stage inputs v_i (ghosts filled)
-  std::vector<T*> y;  // k_i during the recomputation, then the stage cotangents ȳ_i
-  T* kbar = nullptr;  // k̄_i; the `diff` scratch of dissipation! during the recomputation
-  T* pwork = nullptr;
+  std::vector<DevBuf<T>> v;  // stage inputs v_i (ghosts filled)
+  std::vector<DevBuf<T>> y;  // k_i during the recomputation, then the stage cotangents ȳ_i
+  DevBuf<T> kbar;     // k̄_i; the `diff` scratch of dissipation! during the recomputation
+  DevBuf<T> pwork;
   bool temp_on = false;
   ins_temperature_desc_t td{};
-  std::vector<T*> tau;  // stage temperatures τ_i (ghosts filled)
-  std::vector<T*> z;    // c_i during the recomputation, then the stage cotangents z̄_i
-  T* cbar = nullptr;
+  std::vector<DevBuf<T>> tau;  // stage temperatures τ_i (ghosts filled)
+  std::vector<DevBuf<T>> z;    // c_i during the recomputation, then the stage cotangents z̄_i
+  DevBuf<T> cbar;
   // Smagorinsky closure (set_closure): θ, the device double that collects ∂L/∂θ (nullable), the closure force of the stage being recomputed and the
   // `sigma` scratch of the three-kernel force (where ins_smagorinsky_force_needs_sigma answers 1)
   int closure_kind = 0;
   double theta = 0.0;
-  double* thetabar = nullptr;
-  T* mforce = nullptr;
-  T* sigma = nullptr;
+  double* thetabar = nullptr;  // borrowed
+  DevBuf<T> mforce;
+  DevBuf<T> sigma;
 };
 
 namespace rkadj {
@@ -260,7 +260,7 @@ int step_pullback(RkAdjointT<T, PS>* adj, bool with_temp, T visc, const T* ustar
       INS_HIP_TRY(hipMemsetAsync(adj->z[i], 0, sbytes, s));                                   // :23-27
       if ((rc = convdiff_temp(G, td, adj->v[i], adj->tau[i], adj->z[i], s))) return rc;
       if (td.dodissipation && (rc = dissipation(G, td, visc, adj->v[i], adj->kbar, adj->z[i], s))) return rc;
-      const int n = ins_rk_sum_terms(A, ns, i, dt, adj->z.data(), (const T*)nullptr, coef, k);  // :39-44
+      const int n = ins_rk_sum_terms(A, ns, i, dt, adj->z, (const T*)nullptr, coef, k);  // :39-44
       if ((rc = combine(G, G->ncell, tempstart, adj->tau[i + 1], n, coef, k, s))) return rc;
     }
     if (closure) {                                                                            // :31-34, the last term of k_i: k_i += m(v_i, θ)
@@ -269,7 +269,7 @@ int step_pullback(RkAdjointT<T, PS>* adj, bool with_temp, T visc, const T* ustar
       const T* both[1] = {adj->mforce};
       if ((rc = combine(G, nvec, adj->y[i], adj->y[i], 1, &one, both, s))) return rc;
     }
-    const int n = ins_rk_sum_terms(A, ns, i, dt, adj->y.data(), bodyforce, coef, k);          // :35-38
+    const int n = ins_rk_sum_terms(A, ns, i, dt, adj->y, bodyforce, coef, k);          // :35-38
     if ((rc = combine(G, nvec, ustart, adj->v[i + 1], n, coef, k, s))) return rc;
     if ((rc = bc_u(G, adj->v[i + 1], s))) return rc;                                          // :48
     if ((rc = project(G, adj->ps, adj->v[i + 1], adj->pwork, s))) return rc;                  // :49

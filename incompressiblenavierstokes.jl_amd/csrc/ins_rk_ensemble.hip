@@ -12,17 +12,17 @@
 #include "ins_rk_terms.h"
 
 struct ins_rk_ensemble {
-  const ins_grid* grid = nullptr;
-  ins_poisson* ps = nullptr;
+  const ins_grid* grid = nullptr;  // borrowed
+  ins_poisson* ps = nullptr;       // borrowed
   int nstage = 0, nb = 0;
   std::vector<double> A, c;
   long long ms = 0;  // member stride of the work arrays: 2·ncell
-  double* ustart = nullptr;
-  std::vector<double*> ku;
-  double* ub[2] = {nullptr, nullptr};
-  double* pI = nullptr;    // nb · n0 · n1
-  double* phat = nullptr;  // ROUTE_OWN2D: n1 · nb · kxs complex, [ky][member][kxs]
-  double* zrows = nullptr;  // nb zeros: the per-row part of the symbol in the fused y solve
+  DevBuf<double> ustart;
+  std::vector<DevBuf<double>> ku;
+  DevBuf<double> ub[2];
+  DevBuf<double> pI;     // nb · n0 · n1
+  DevBuf<double> phat;   // ROUTE_OWN2D: n1 · nb · kxs complex, [ky][member][kxs]
+  DevBuf<double> zrows;  // nb zeros: the per-row part of the symbol in the fused y solve
 };
 
 namespace {
@@ -95,7 +95,7 @@ int step(ins_rk_ensemble* e, double visc, double* U, long long ustride, double d
     const bool last = i == ns - 1;
     double* out = last ? U : e->ub[i & 1];
     const long long out_stride = last ? ustride : e->ms;
-    RkEpi epi = ins_rk_stage_terms(e->A.data(), ns, i, dt, e->ku.data(), (const double*)nullptr, RK_K_BASIS, false, RK_FORCE_INDEX_ORDER);
+    RkEpi epi = ins_rk_stage_terms(e->A.data(), ns, i, dt, e->ku, (const double*)nullptr, RK_K_BASIS, false, RK_FORCE_INDEX_ORDER);
     epi.ustart = (i == 0) ? nullptr : (raw_in ? e->ustart : U);
     epi.ustar = out;
     if (i == 0 && raw_in) epi.ustart_out = e->ustart;
@@ -133,21 +133,18 @@ extern "C" int ins_rk_ensemble_create(const ins_grid_t* G, ins_poisson_t* ps, in
   e->A.assign(A, A + nstage * nstage);
   e->c.assign(c, c + nstage);
   e->ms = 2 * G->ncell;
-  const size_t vbytes = (size_t)e->ms * nbatch * sizeof(double);
-  const size_t pbytes = (size_t)ps->np[0] * ps->np[1] * nbatch * sizeof(double);
-  const size_t hbytes = (size_t)ps->kxs * ps->np[1] * nbatch * 2 * sizeof(double);
+  const size_t nvec = (size_t)e->ms * nbatch;
+  const size_t npre = (size_t)ps->np[0] * ps->np[1] * nbatch;
+  const size_t nhat = (size_t)ps->kxs * ps->np[1] * nbatch * 2;
   // every array zeroed once: ghost rings and padding columns that no kernel writes are read by none either, but hold defined values
-  auto alloc0 = [](double** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess; };
-  bool ok = alloc0(&e->ustart, vbytes) && alloc0(&e->ub[0], vbytes) && alloc0(&e->ub[1], vbytes) && alloc0(&e->pI, pbytes) &&
-            alloc0(&e->zrows, (size_t)nbatch * sizeof(double));
-  if (ok && ps->route == ROUTE_OWN2D) ok = alloc0(&e->phat, hbytes);
-  e->ku.assign(nstage, nullptr);
-  for (int i = 0; ok && i < nstage; ++i) ok = alloc0(&e->ku[i], vbytes);
-  if (!ok) {
-    (void)hipGetLastError();
-    ins_set_error("ins_rk_ensemble_create: device allocation of %d x %d vector fields failed", nstage + 3, nbatch);
+  (rc = e->ustart.alloc_zero(nvec)) || (rc = e->ub[0].alloc_zero(nvec)) || (rc = e->ub[1].alloc_zero(nvec)) || (rc = e->pI.alloc_zero(npre)) ||
+      (rc = e->zrows.alloc_zero(nbatch));
+  if (rc == INS_OK && ps->route == ROUTE_OWN2D) rc = e->phat.alloc_zero(nhat);
+  e->ku.resize(nstage);
+  for (int i = 0; rc == INS_OK && i < nstage; ++i) rc = e->ku[i].alloc_zero(nvec);
+  if (rc != INS_OK) {
     ins_rk_ensemble_destroy(e);
-    return INS_ERR_HIP;
+    return rc;
   }
   *out = e;
   return INS_OK;
@@ -155,10 +152,6 @@ extern "C" int ins_rk_ensemble_create(const ins_grid_t* G, ins_poisson_t* ps, in
 
 extern "C" int ins_rk_ensemble_destroy(ins_rk_ensemble_t* e) {
   if (!e) return INS_OK;
-  for (double* p : {e->ustart, e->ub[0], e->ub[1], e->pI, e->phat, e->zrows})
-    if (p) (void)hipFree(p);
-  for (double* k : e->ku)
-    if (k) (void)hipFree(k);
   delete e;
   return INS_OK;
 }

@@ -25,23 +25,16 @@ struct ins_rk_ext {
   double theta = 0.0;
   bool temp_on = false;
   ins_temperature_desc_t td;
-  double* sigma = nullptr;      // D(D+1)/2 scalar fields
-  double* E = nullptr;          // closure term + gravity (vector field)
-  double* diff = nullptr;       // scratch of dissipation! (vector field)
-  double* tempstart = nullptr;  // scalar
-  double* w = nullptr;          // u · diffusion(u) (vector field, written by the stage kernel; fused path)
-  double* tb[2] = {nullptr, nullptr};  // stage temperatures (fused path)
-  std::vector<double*> ktemp;   // nstage scalars
+  DevBuf<double> sigma;      // D(D+1)/2 scalar fields
+  DevBuf<double> E;          // closure term + gravity (vector field)
+  DevBuf<double> diff;       // scratch of dissipation! (vector field)
+  DevBuf<double> tempstart;  // scalar
+  DevBuf<double> w;          // u · diffusion(u) (vector field, written by the stage kernel; fused path)
+  DevBuf<double> tb[2];      // stage temperatures (fused path)
+  std::vector<DevBuf<double>> ktemp;  // nstage scalars
 };
 
-void ins_rk_ext_free(ins_rk_ext* e) {
-  if (!e) return;
-  for (double* p : {e->sigma, e->E, e->diff, e->tempstart, e->w, e->tb[0], e->tb[1]})
-    if (p) (void)hipFree(p);
-  for (double* p : e->ktemp)
-    if (p) (void)hipFree(p);
-  delete e;
-}
+void ins_rk_ext_free(ins_rk_ext* e) { delete e; }
 
 static ins_rk_ext* ext_of(ins_rk* rk) {
   if (!rk->ext) rk->ext = new ins_rk_ext();
@@ -73,12 +66,8 @@ extern "C" long long ins_dbg_ext_tiled_steps(void) { return g_tiled_steps; }
 // test hook: how many steps took the fused path (periodic uniform 3-D boxes, spectral solver)
 extern "C" long long ins_dbg_ext_fused_steps(void) { return g_fused_steps; }
 
-static int zalloc(double** p, size_t bytes, hipStream_t s) {
-  if (*p) return INS_OK;
-  INS_HIP_TRY(hipMalloc(p, bytes));
-  INS_HIP_TRY(hipMemsetAsync(*p, 0, bytes, s));
-  return INS_OK;
-}
+// first use of a buffer: allocated and zeroed on the stream
+static int zalloc(DevBuf<double>* b, size_t bytes, hipStream_t s) { return *b ? INS_OK : b->alloc_zero_async(bytes / sizeof(double), s); }
 
 extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double* temp, double t, double dt, void* stream) {
   INS_REQUIRE(rk && u, "null argument");
@@ -98,7 +87,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
   if (with_temp) {
     if ((rc = zalloc(&e->tempstart, sbytes, s))) return rc;
     if (e->td.dodissipation && (rc = zalloc(&e->diff, vbytes, s))) return rc;
-    if ((int)e->ktemp.size() < ns) e->ktemp.resize(ns, nullptr);
+    if ((int)e->ktemp.size() < ns) e->ktemp.resize(ns);
     for (int i = 0; i < ns; ++i)
       if ((rc = zalloc(&e->ktemp[i], sbytes, s))) return rc;
     INS_HIP_TRY(hipMemcpyAsync(e->tempstart, temp, sbytes, hipMemcpyDeviceToDevice, s));  // state_copyto!(xstart, x)   :14
@@ -166,7 +155,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
       double* tout = with_temp ? (last ? temp : e->tb[i & 1]) : nullptr;
       const bool corr_in = incorr && i > 0;  // `in` is the uncorrected V_{i-1}, ps->pI its pressure
       if (smag1) {
-        if ((rc = ins_k_smagforce(G, e->theta, in, corr_in ? rk->ps->pI : nullptr, e->E, s))) return rc;
+        if ((rc = ins_k_smagforce(G, e->theta, in, corr_in ? rk->ps->pI.get() : nullptr, e->E, s))) return rc;
       } else if (closure) {
         if ((rc = need_sigma())) return rc;
         rc = corr_in ? ins_k_smagtensor_corr(G, e->theta, in, rk->ps->pI, e->sigma, s) : ins_smagtensor_f64(G, e->theta, in, e->sigma, stream);
@@ -176,7 +165,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
       }
       // the V_m live in the ku arrays; V_{i-1} comes from registers where it is this stage's uncorrected stencil input (corr_in), else the stencil reads
       // the projection's corrected copy and V_{i-1} is a term like the others.  The steady force is not part of what is stored.
-      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, vbasis ? RK_V_BASIS : RK_K_BASIS, corr_in, RK_FORCE_DIAG_FIRST);
+      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku, rk->force, vbasis ? RK_V_BASIS : RK_K_BASIS, corr_in, RK_FORCE_DIAG_FIRST);
       epi.ustart = (i == 0) ? nullptr : u;
       epi.ustar = out;
       epi.extra = closure ? e->E : nullptr;
@@ -190,7 +179,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
           te.temp = tin;
           te.tempstart = e->tempstart;
           te.temp_out = tout;
-          te.ktemp_out = ins_rk_needed_later(rk->A.data(), ns, i) ? e->ktemp[i] : nullptr;
+          te.ktemp_out = ins_rk_needed_later(rk->A.data(), ns, i) ? e->ktemp[i].get() : nullptr;
           for (int j = 0; j < i; ++j) {
             const double c = dt * rk->A[i * ns + j];
             if (c == 0.0) continue;
@@ -219,7 +208,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
         }
         const bool later = ins_rk_needed_later(rk->A.data(), ns, i);
         if ((rc = ins_k_temp_stage(G, td.a4, td.diss_coef, in, tin, td.dodissipation ? e->w : nullptr, e->tempstart, n, coefs, ks, dt * rk->A[i * ns + i],
-                                   later ? e->ktemp[i] : nullptr, tout, s, corr_in ? rk->ps->pI : nullptr)))
+                                   later ? e->ktemp[i].get() : nullptr, tout, s, corr_in ? rk->ps->pI.get() : nullptr)))
           return rc;
       }
       if (incorr && i < ns - 1)
@@ -246,8 +235,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
     if (with_temp) {
       for (int b = 0; b < 2; ++b)
         if (!e->tb[b]) {
-          INS_HIP_TRY(hipMalloc(&e->tb[b], sbytes));
-          INS_HIP_TRY(hipMemcpyAsync(e->tb[b], temp, sbytes, hipMemcpyDeviceToDevice, s));
+          if ((rc = e->tb[b].alloc_copy_device(sbytes / sizeof(double), temp, s))) return rc;
         }
     }
     // The 64-wide masked stage kernel also leaves w = u·diffusion(u) (the dissipation term of the temperature equation) from
@@ -273,7 +261,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
       }
       if (with_temp && td.dodissipation && !w_from_stage && (rc = ins_k_diffusion_flux3d(G, visc, cur, e->diff, false, s)))
         return rc;  // e->diff: shell zero since its allocation
-      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, RK_K_BASIS, false, RK_FORCE_INDEX_ORDER);  // k-basis only
+      RkEpi epi = ins_rk_stage_terms(rk->A.data(), ns, i, dt, rk->ku, rk->force, RK_K_BASIS, false, RK_FORCE_INDEX_ORDER);  // k-basis only
       epi.ustart = (i == 0) ? nullptr : u;
       epi.ustar = out;
       epi.extra = closure ? e->E : nullptr;
@@ -295,7 +283,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
         }
         const bool later = ins_rk_needed_later(rk->A.data(), ns, i);
         if ((rc = ins_k_temp_stage(G, td.a4, td.diss_coef, cur, tin, w_from_stage ? e->w : nullptr, e->tempstart, n, coefs, ks, dt * rk->A[i * ns + i],
-                                   later ? e->ktemp[i] : nullptr, tout, s, nullptr, td.dodissipation && !w_from_stage ? e->diff : nullptr)))
+                                   later ? e->ktemp[i].get() : nullptr, tout, s, nullptr, td.dodissipation && !w_from_stage ? e->diff.get() : nullptr)))
           return rc;
       }
       if ((rc = ins_k_apply_bc_u(G, out, 0, nullptr, s))) return rc;                                          // :48
@@ -331,7 +319,7 @@ extern "C" int ins_rk_step_ext_f64(ins_rk_t* rk, double visc, double* u, double*
     }
     double coefs[INS_MAX_STAGES + 1];
     const double* ks[INS_MAX_STAGES + 1];
-    const int n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku.data(), rk->force, coefs, ks);
+    const int n = ins_rk_sum_terms(rk->A.data(), ns, i, dt, rk->ku, rk->force, coefs, ks);
     if ((rc = ins_combine_f64(G, rk->ustart, u, n, coefs, ks, stream))) return rc;
     if ((rc = temp_combine(i))) return rc;
     if ((rc = ins_k_apply_bc_u(G, u, 0, nullptr, s))) return rc;

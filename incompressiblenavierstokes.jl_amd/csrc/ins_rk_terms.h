@@ -47,12 +47,12 @@ enum RkBasis { RK_K_BASIS, RK_V_BASIS };
 //                                                                    second branch) and the reference-order lists (ins_rk_sum_terms)
 enum RkForceOrder { RK_FORCE_DIAG_FIRST, RK_FORCE_INDEX_ORDER };
 
-// A zeroed RkEpi with n, coef[], k[], c0m1, self_in, coef_self and write_k of stage i filled.  prev[m]: the array of earlier stage m (k_m or V_m; P =
+// A zeroed RkEpi with n, coef[], k[], c0m1, self_in, coef_self and write_k of stage i filled.  prev[m]: the array of earlier stage m (k_m or V_m; any table of pointers or of buffers; P =
 // float on the Float32 path, whose kernels cast RkEpi's untyped pointers back); force: nullptr or the steady body force, always the last term.
 // input_in_regs (stage-velocity basis): V_{i-1} is the stencil input and the kernel keeps its uncorrected value in registers, so β_{i,i-1} goes to
 // self_in instead of a term that would be loaded.  Terms with a zero coefficient are skipped.
-template <typename P>
-static inline RkEpi ins_rk_stage_terms(const double* A, int ns, int i, double dt, P* const* prev, const P* force, RkBasis basis, bool input_in_regs,
+template <typename P, typename Prev>
+static inline RkEpi ins_rk_stage_terms(const double* A, int ns, int i, double dt, const Prev& prev, const P* force, RkBasis basis, bool input_in_regs,
                                        RkForceOrder order) {
   RkEpi epi;
   memset(&epi, 0, sizeof(epi));
@@ -155,8 +155,8 @@ static inline RkEpi ins_rk_carry_consumer_terms(const double* A, int ns, const R
 // non-zero coefficients and their arrays to coef[] / k[] (room for INS_MAX_STAGES + 1), then the body force with Σ_{j<=i} Δt A[i,j] in index order
 // (zeros included: they add nothing), and returns the number of terms.  The products are formed in S, the caller's precision: the Float32 loop
 // multiplies Δt (float)A[i,j] in float.
-template <typename S, typename P>
-static inline int ins_rk_sum_terms(const double* A, int ns, int i, S dt, P* const* prev, const P* force, S* coef, const P** k) {
+template <typename S, typename P, typename Prev>
+static inline int ins_rk_sum_terms(const double* A, int ns, int i, S dt, const Prev& prev, const P* force, S* coef, const P** k) {
   int n = 0;
   S cf = 0;
   for (int j = 0; j <= i; ++j) {

@@ -20,19 +20,18 @@ struct ins_slab_fft {
   int nzl, nyl, kxn; // local planes, local rows (transposed layout), nx/2+1
   hipfftHandle xy_fwd = 0, xy_inv = 0, z_fwd = 0;
   bool plans = false, has_z_plan = false;
-  double *ax = nullptr, *ay = nullptr, *az = nullptr;  // symbol vectors (ay: this rank's ky range)
-  double* tw = nullptr;                                 // twiddles of the fused z kernel (power-of-two nz)
+  DevBuf<double> ax, ay, az;                            // symbol vectors (ay: this rank's ky range)
+  DevBuf<double> tw;                                    // twiddles of the fused z kernel (power-of-two nz)
   bool ownfft = false;                                  // power-of-two box: own x / y passes too (ins_fft.hip), no rocFFT
-  double *tw_x = nullptr, *tw_y = nullptr;
-  const ins_grid* dummy_grid = nullptr;
+  DevBuf<double> tw_x, tw_y;
   // transpose-free z solve (ins_ztri.hip): every ky in storage order, Ω/Δz², interface values (L_{r-1}, F_{r+1}) per line
-  double* ay_full = nullptr;
+  DevBuf<double> ay_full;
   // tridiagonal route: its y passes run on the register passes (k_line3, ins_zsolve.hip) where they exist; ay3 = the full symbol vector in THEIR storage order
   // (the transposes route keeps the LDS passes: its packed y kernels and the ky ownership of the ranks are tied to the digit-reversed order)
   bool y3 = false;
-  double* ay3 = nullptr;
+  DevBuf<double> ay3;
   double cz = 0.0;
-  double* ztri_bc = nullptr;
+  DevBuf<double> ztri_bc;
   int kxs = 0;  // row stride of `work` on the transpose-free route: kxn rounded up to whole 128-B lines with the own passes
 };
 
@@ -171,19 +170,14 @@ extern "C" int ins_slab_fft_create(const int32_t np[3], const double h[3], int r
     std::vector<double> full(np[1]), p3(np[1]);
     for (int k = 0; k < np[1]; ++k) full[k] = symbol(1, k);
     ins_line3_permute_symbol(np[1], full.data(), p3.data());
-    if (hipMalloc(&S->ay3, p3.size() * 8) != hipSuccess || hipMemcpy(S->ay3, p3.data(), p3.size() * 8, hipMemcpyHostToDevice) != hipSuccess) S->y3 = false;
+    if (S->ay3.alloc_copy_host(p3.size(), p3.data()) != INS_OK) S->y3 = false;
   }
-  bool ok = hipMalloc(&S->ax, ax.size() * 8) == hipSuccess && hipMalloc(&S->ay, ay.size() * 8) == hipSuccess &&
-            hipMalloc(&S->az, az.size() * 8) == hipSuccess && hipMalloc(&S->ay_full, ayf.size() * 8) == hipSuccess &&
-            hipMalloc(&S->ztri_bc, (size_t)4 * S->kxn * np[1] * 8) == hipSuccess;
-  ok = ok && hipMemcpy(S->ay_full, ayf.data(), ayf.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(S->ax, ax.data(), ax.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(S->ay, ay.data(), ay.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(S->az, az.data(), az.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    ins_set_error("ins_slab_fft_create: symbol upload failed");
+  int rcs;
+  if ((rcs = S->ax.alloc_copy_host(ax.size(), ax.data())) || (rcs = S->ay.alloc_copy_host(ay.size(), ay.data())) ||
+      (rcs = S->az.alloc_copy_host(az.size(), az.data())) || (rcs = S->ay_full.alloc_copy_host(ayf.size(), ayf.data())) ||
+      (rcs = S->ztri_bc.alloc((size_t)4 * S->kxn * np[1]))) {
     ins_slab_fft_destroy(S);
-    return INS_ERR_HIP;
+    return rcs;
   }
   // batched 2-D transforms over (y, x) for nzl planes; 1-D transforms along z (stride nyl*kxn) for nyl*kxn lines
   int n2[2] = {np[1], np[0]};
@@ -233,15 +227,6 @@ extern "C" int ins_slab_fft_destroy(ins_slab_fft_t* S) {
     if (S->has_z_plan) (void)hipfftDestroy(S->z_fwd);
     ins_fft_solver_released();
   }
-  if (S->tw) (void)hipFree(S->tw);
-  if (S->tw_x) (void)hipFree(S->tw_x);
-  if (S->tw_y) (void)hipFree(S->tw_y);
-  if (S->ax) (void)hipFree(S->ax);
-  if (S->ay) (void)hipFree(S->ay);
-  if (S->az) (void)hipFree(S->az);
-  if (S->ay_full) (void)hipFree(S->ay_full);
-  if (S->ay3) (void)hipFree(S->ay3);
-  if (S->ztri_bc) (void)hipFree(S->ztri_bc);
   delete S;
   return INS_OK;
 }

@@ -7,13 +7,7 @@
 int ins_k_smag_partials(const ins_grid* G, double** out) {
   ins_grid* M = const_cast<ins_grid*>(G);
   const size_t need = (size_t)smag_partials(box_launch(G->g.D, G->g.ip_lo, G->g.ip_hi));
-  if (M->smagpart_count < need) {
-    if (M->smagpart_dev) INS_HIP_TRY(hipFree(M->smagpart_dev));
-    M->smagpart_dev = nullptr;
-    M->smagpart_count = 0;
-    INS_HIP_TRY(hipMalloc(&M->smagpart_dev, need * sizeof(double)));
-    M->smagpart_count = need;
-  }
+  if (int rc = M->smagpart_dev.ensure(need)) return rc;
   *out = M->smagpart_dev;
   return INS_OK;
 }

@@ -10,27 +10,27 @@
 #include "ins_stencil.h"
 
 struct ins_spectrum {
-  const ins_grid* grid;
+  const ins_grid* grid;  // borrowed
   hipfftHandle plan = 0;
   bool has_plan = false;
-  double* real = nullptr;                // Np
-  hipfftDoubleComplex* hat = nullptr;    // (Np0/2+1) Np1 [Np2]
-  long long* offsets = nullptr;          // nbin + 1
-  long long* inds = nullptr;             // positions inside `hat`
-  double* weights = nullptr;             // optional weight per index (get_scale_numbers: 1/|k|)
+  DevBuf<double> real;                   // Np
+  DevBuf<hipfftDoubleComplex> hat;       // (Np0/2+1) Np1 [Np2]
+  DevBuf<long long> offsets;             // nbin + 1
+  DevBuf<long long> inds;                // positions inside `hat`
+  DevBuf<double> weights;                // optional weight per index (get_scale_numbers: 1/|k|)
   int nbin = 0;
   int np[3] = {1, 1, 1};
   double scale = 0.0;
   // own passes (3-D)
   bool own = false;
   int kxs = 0;
-  double* tw[3] = {nullptr, nullptr, nullptr};
+  DevBuf<double> tw[3];
   // chunked shell sums
   int nchunk = 0;
-  long long* chunk_lo = nullptr;   // nchunk + 1 starts inside the index list (chunk c = [chunk_lo[c], chunk_hi[c]))
-  long long* chunk_hi = nullptr;
-  int* bin_chunk0 = nullptr;       // nbin + 1: first chunk of every shell
-  double* partial = nullptr;       // nchunk
+  DevBuf<long long> chunk_lo;      // nchunk + 1 starts inside the index list (chunk c = [chunk_lo[c], chunk_hi[c]))
+  DevBuf<long long> chunk_hi;
+  DevBuf<int> bin_chunk0;          // nbin + 1: first chunk of every shell
+  DevBuf<double> partial;          // nchunk
 };
 
 namespace {
@@ -76,17 +76,6 @@ __global__ __launch_bounds__(64) void k_shell_finish(const int* __restrict__ bin
 extern "C" int ins_spectrum_destroy(ins_spectrum_t* S) {
   if (!S) return INS_OK;
   if (S->has_plan) (void)hipfftDestroy(S->plan);
-  (void)hipFree(S->real);
-  (void)hipFree(S->hat);
-  (void)hipFree(S->offsets);
-  (void)hipFree(S->inds);
-  (void)hipFree(S->weights);
-  for (double* t : S->tw)
-    if (t) (void)hipFree(t);
-  (void)hipFree(S->chunk_lo);
-  (void)hipFree(S->chunk_hi);
-  (void)hipFree(S->bin_chunk0);
-  (void)hipFree(S->partial);
   delete S;
   return INS_OK;
 }
@@ -144,30 +133,25 @@ extern "C" int ins_spectrum_create_weighted(const ins_grid_t* G, int nbin, const
   bc0[nbin] = (int)clo.size();
   S->nchunk = (int)clo.size();
   std::vector<long long> off(offsets, offsets + nbin + 1);
-  bool ok = hipMalloc(&S->real, ntot * sizeof(double)) == hipSuccess && hipMalloc(&S->hat, nhat * sizeof(hipfftDoubleComplex)) == hipSuccess &&
-            hipMalloc(&S->offsets, (nbin + 1) * sizeof(long long)) == hipSuccess &&
-            hipMalloc(&S->inds, std::max<long long>(nind, 1) * sizeof(long long)) == hipSuccess;
-  if (ok) ok = hipMemcpy(S->offsets, off.data(), (nbin + 1) * sizeof(long long), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && nind) ok = hipMemcpy(S->inds, pos.data(), nind * sizeof(long long), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && weights && nind)
-    ok = hipMalloc(&S->weights, nind * sizeof(double)) == hipSuccess && hipMemcpy(S->weights, weights, nind * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok) {
+  // inds, chunk_lo, chunk_hi and partial hold at least one element; what the host lists have goes in
+  int rc;
+  (rc = S->real.alloc(ntot)) || (rc = S->hat.alloc(nhat)) || (rc = S->offsets.alloc_copy_host(nbin + 1, off.data())) ||
+      (rc = S->inds.alloc(std::max<long long>(nind, 1))) || (rc = nind ? ins_devmem_copy_from_host(S->inds, pos.data(), nind * sizeof(long long)) : INS_OK);
+  if (rc == INS_OK && weights && nind) rc = S->weights.alloc_copy_host(nind, weights);
+  if (rc == INS_OK) {
     const size_t nc = std::max<size_t>(clo.size(), 1);
-    ok = hipMalloc(&S->chunk_lo, nc * sizeof(long long)) == hipSuccess && hipMalloc(&S->chunk_hi, nc * sizeof(long long)) == hipSuccess &&
-         hipMalloc(&S->bin_chunk0, (nbin + 1) * sizeof(int)) == hipSuccess && hipMalloc(&S->partial, nc * sizeof(double)) == hipSuccess &&
-         hipMemcpy(S->bin_chunk0, bc0.data(), (nbin + 1) * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && !clo.empty())
-      ok = hipMemcpy(S->chunk_lo, clo.data(), clo.size() * sizeof(long long), hipMemcpyHostToDevice) == hipSuccess &&
-           hipMemcpy(S->chunk_hi, chi.data(), chi.size() * sizeof(long long), hipMemcpyHostToDevice) == hipSuccess;
+    (rc = S->chunk_lo.alloc(nc)) || (rc = S->chunk_hi.alloc(nc)) || (rc = S->bin_chunk0.alloc_copy_host(nbin + 1, bc0.data())) || (rc = S->partial.alloc(nc));
+    if (rc == INS_OK && !clo.empty())
+      (rc = ins_devmem_copy_from_host(S->chunk_lo, clo.data(), clo.size() * sizeof(long long))) ||
+          (rc = ins_devmem_copy_from_host(S->chunk_hi, chi.data(), chi.size() * sizeof(long long)));
   }
-  if (ok && S->own) {
-    ok = hipMemset(S->hat, 0, nhat * sizeof(hipfftDoubleComplex)) == hipSuccess;
-    for (int a = 0; ok && a < 3; ++a) ok = ins_zsolve_twiddles(S->np[a], &S->tw[a]) == INS_OK;
+  if (rc == INS_OK && S->own) {
+    rc = ins_devmem_zero(S->hat, nhat * sizeof(hipfftDoubleComplex));
+    for (int a = 0; rc == INS_OK && a < 3; ++a) rc = ins_zsolve_twiddles(S->np[a], &S->tw[a]);
   }
-  if (!ok) {
+  if (rc != INS_OK) {
     ins_spectrum_destroy(S);
-    ins_set_error("spectrum: device allocation failed");
-    return INS_ERR_HIP;
+    return rc;
   }
   if (S->own) {
     *out = S;
@@ -202,7 +186,7 @@ static int spectrum_run(ins_spectrum_t* S, const T* u, double* ehat, hipStream_t
       INS_LAUNCH_D((k_strip<D, T>), (Launch3{grid, block}), s, g, u + a * g.sc, S->real, S->np[0], S->np[1]);
     }
     if (S->own) {
-      double* ph = reinterpret_cast<double*>(S->hat);
+      double* ph = reinterpret_cast<double*>(S->hat.get());
       const int kxn = S->np[0] / 2 + 1;
       const double* src = F32 ? S->real : reinterpret_cast<const double*>(u + a * g.sc);  // T = double: ghosts stripped inside the x pass
       int rc;
@@ -212,7 +196,7 @@ static int spectrum_run(ins_spectrum_t* S, const T* u, double* ehat, hipStream_t
     } else {
       INS_FFT_TRY(hipfftExecD2Z(S->plan, S->real, S->hat));
     }
-    if (S->nchunk) hipLaunchKernelGGL(k_shell_chunks, dim3(S->nchunk), dim3(256), 0, s, reinterpret_cast<const double2*>(S->hat), S->chunk_lo, S->chunk_hi, S->inds, S->weights, S->partial);
+    if (S->nchunk) hipLaunchKernelGGL(k_shell_chunks, dim3(S->nchunk), dim3(256), 0, s, reinterpret_cast<const double2*>(S->hat.get()), S->chunk_lo, S->chunk_hi, S->inds, S->weights, S->partial);
     hipLaunchKernelGGL(k_shell_finish, dim3(cdiv(S->nbin, 64)), dim3(64), 0, s, S->bin_chunk0, S->partial, S->nbin, S->scale, ehat);
     INS_LAUNCH_CHECK();
   }

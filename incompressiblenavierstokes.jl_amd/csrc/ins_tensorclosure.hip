@@ -104,13 +104,7 @@ __global__ __launch_bounds__(256) void k_divoftensor_adjoint(GridDev g, const do
 int gradbar_scratch(const ins_grid* G, double** out) {
   ins_grid* M = const_cast<ins_grid*>(G);
   const size_t need = (size_t)G->g.D * G->g.D * (size_t)G->ncell;
-  if (M->gradbar_count < need) {
-    if (M->gradbar_dev) INS_HIP_TRY(hipFree(M->gradbar_dev));
-    M->gradbar_dev = nullptr;
-    M->gradbar_count = 0;
-    INS_HIP_TRY(hipMalloc(&M->gradbar_dev, need * sizeof(double)));
-    M->gradbar_count = need;
-  }
+  if (int rc = M->gradbar_dev.ensure(need)) return rc;
   *out = M->gradbar_dev;
   return INS_OK;
 }

@@ -783,8 +783,8 @@ int ins_k_line3_y_f32(float* phat, int kxn, int n1, int n2, const float* tw, boo
   return line3_y<float2>(reinterpret_cast<float2*>(phat), kxn, kxs, n1, n2, reinterpret_cast<const float2*>(tw), inverse, s);
 }
 
-// Twiddles W_nz^m = exp(-2πi m / nz), m = 0..nz-1, on the device (caller frees).
-int ins_zsolve_twiddles(int nz, double** out) {
+// Twiddles W_nz^m = exp(-2πi m / nz), m = 0..nz-1, on the device, in a buffer of the caller's handle
+int ins_zsolve_twiddles(int nz, DevBuf<double>* out) {
   std::vector<double> h(2 * (size_t)nz);
   for (int m = 0; m < nz; ++m) {
     // octant symmetry keeps the table accurate to the last bit where it matters
@@ -800,21 +800,12 @@ int ins_zsolve_twiddles(int nz, double** out) {
       h[2 * m + 1] = sn[q];
     }
   }
-  double* d = nullptr;
-  INS_HIP_TRY(hipMalloc(&d, h.size() * sizeof(double)));
-  hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d);
-    ins_set_error("twiddle upload: %s", hipGetErrorString(e));
-    return INS_ERR_HIP;
-  }
-  *out = d;
-  return INS_OK;
+  return out->alloc_copy_host(h.size(), h.data());
 }
 
 // float2 spectra (`_f32` family): the three-pass kernel with twice the lines per tile (same bytes per row segment); symbols stay double
 bool ins_zsolve_f32_supported(int nz) { return !ins_opt(OPT_INS_DISABLE_ZSOLVE) && (nz == 192 || nz == 256 || nz == 384 || nz == 512); }
-int ins_zsolve_twiddles_f32(int nz, float** out) {
+int ins_zsolve_twiddles_f32(int nz, DevBuf<float>* out) {
   std::vector<float> h(2 * (size_t)nz);
   for (int m = 0; m < nz; ++m) {
     const double a = -2.0 * M_PI * (double)m / (double)nz;
@@ -827,15 +818,7 @@ int ins_zsolve_twiddles_f32(int nz, float** out) {
       h[2 * m + 1] = sn[q];
     }
   }
-  float* d = nullptr;
-  INS_HIP_TRY(hipMalloc(&d, h.size() * sizeof(float)));
-  if (hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    ins_set_error("twiddle upload failed");
-    return INS_ERR_HIP;
-  }
-  *out = d;
-  return INS_OK;
+  return out->alloc_copy_host(h.size(), h.data());
 }
 int ins_k_zsolve_f32(float* data, int nz, long long nl, const double* ax, int kxn, const double* ay, const double* az, const float* tw, double inv_n,
                      bool zero_mean, hipStream_t s, int kxs) {
@@ -931,17 +914,12 @@ int ins_k_zsolve(double* data, int nz, long long nl, const double* ax, int kxn, 
 // [nz][nl] blocks (nl = nky * kxs lines, kxn live columns), average ms per sweep over all boxes.  tools/zpass_lab.py varies the plane
 // stride (nl * 16 B) at a fixed byte count with it.
 extern "C" int ins_dbg_zsolve(double* data, int nz, long long nl, int kxn, int kxs, int nbox, int reps, float* ms) {
-  double *ax = nullptr, *ay = nullptr, *az = nullptr, *tw = nullptr;
+  DevBuf<double> ax, ay, az, tw;
   const int nky = (int)(nl / kxs);
   std::vector<double> h(std::max(std::max(kxs, nky), nz), 1.0);
-  INS_HIP_TRY(hipMalloc(&ax, kxs * 8));
-  INS_HIP_TRY(hipMalloc(&ay, nky * 8));
-  INS_HIP_TRY(hipMalloc(&az, nz * 8));
-  INS_HIP_TRY(hipMemcpy(ax, h.data(), kxs * 8, hipMemcpyHostToDevice));
-  INS_HIP_TRY(hipMemcpy(ay, h.data(), nky * 8, hipMemcpyHostToDevice));
-  INS_HIP_TRY(hipMemcpy(az, h.data(), nz * 8, hipMemcpyHostToDevice));
-  int rc = ins_zsolve_twiddles(nz, &tw);
-  if (rc) return rc;
+  int rc;
+  if ((rc = ax.alloc_copy_host(kxs, h.data())) || (rc = ay.alloc_copy_host(nky, h.data())) || (rc = az.alloc_copy_host(nz, h.data()))) return rc;
+  if ((rc = ins_zsolve_twiddles(nz, &tw))) return rc;
   hipEvent_t e0, e1;
   INS_HIP_TRY(hipEventCreate(&e0));
   INS_HIP_TRY(hipEventCreate(&e1));
@@ -954,10 +932,6 @@ extern "C" int ins_dbg_zsolve(double* data, int nz, long long nl, int kxn, int k
   INS_HIP_TRY(hipEventSynchronize(e1));
   INS_HIP_TRY(hipEventElapsedTime(ms, e0, e1));
   *ms /= (float)std::max(reps, 1);
-  (void)hipFree(ax);
-  (void)hipFree(ay);
-  (void)hipFree(az);
-  (void)hipFree(tw);
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   return INS_OK;
