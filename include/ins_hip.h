@@ -297,6 +297,22 @@ int ins_rk_ensemble_rhs_f64(ins_rk_ensemble_t* ens, double visc, const double* U
 /* apply_bc_u! of every member (periodic images, corners included) in two launches: for fields whose interior was written by something other than the
  * stepper, e.g. the member filters below, before they go to ins_rk_ensemble_rhs_f64 or ins_rk_ensemble_steps_f64. */
 int ins_rk_ensemble_apply_bc_u_f64(ins_rk_ensemble_t* ens, double* U, int64_t ustride, void* stream);
+/* The operators of one differentiable step of all members and their pullbacks (ad.timestep_ensemble: a-posteriori training on B trajectories in one autograd
+ * graph).  Member b of every field at ptr + b·stride, every stride >= 2·ncell, what lies between members is never touched; each entry costs the launches of one
+ * field whatever nbatch is, member b is bitwise what a handle with nbatch = 1 gives, and a handle whose box an INS_DISABLE_* switch has since turned away gets
+ * INS_ERR_UNSUPPORTED with a message that names the per-trajectory route (ad.timestep, create_loss_post).
+ * momentum: F[b] = momentum!(U[b]) on the interior (U read only, ghosts valid; the ghost ring of F untouched; no member of F may overlap a member of U).
+ * project, in place: U[b] <- apply_bc_u(project(apply_bc_u(U[b]))): the interior is read through its periodic images, every ghost volume is written.
+ * apply_bc_u_pullback, in place: the transpose of ins_rk_ensemble_apply_bc_u_f64 (the arithmetic of ins_apply_bc_u_pullback_f64 on a periodic box), two launches.
+ * momentum_pullback: Ubar[b] (+)= J_F(U[b])^T Phibar[b] over the whole padded array, the contract of ins_momentum_pullback_f64 (no member of Ubar may overlap a member of U or Phibar: INS_ERR_INVALID), one launch.
+ * project_pullback, in place: the exact transpose of ins_rk_ensemble_project_f64 on the padded arrays: ghost cotangents folded into the interior, the same member
+ *   solve and gradient-subtract, every ghost volume zero on return (the launches of the forward plus the fold's two). */
+int ins_rk_ensemble_momentum_f64(ins_rk_ensemble_t* ens, double visc, const double* U, int64_t ustride, double* F, int64_t fstride, void* stream);
+int ins_rk_ensemble_project_f64(ins_rk_ensemble_t* ens, double* U, int64_t ustride, void* stream);
+int ins_rk_ensemble_apply_bc_u_pullback_f64(ins_rk_ensemble_t* ens, double* G, int64_t gstride, void* stream);
+int ins_rk_ensemble_momentum_pullback_f64(ins_rk_ensemble_t* ens, double visc, const double* U, int64_t ustride, const double* Phibar, int64_t pstride, double* Ubar,
+                                          int64_t bstride, int accumulate, void* stream);
+int ins_rk_ensemble_project_pullback_f64(ins_rk_ensemble_t* ens, double* G, int64_t gstride, void* stream);
 /* Device pointers into the cache (valid until ins_rk_destroy): the stage pressure `p` and `ku[i]`. */
 /* K6 alone: out = base + Σ_q coefs[q]·ks[q] over whole vector fields, summed in index order — the stage-combination
  * broadcasts `u .= ustart; u .+= Δt A[i,j] ku[j]` (step_explicit_runge_kutta.jl:35-38) and LMWray3's state_copyto! /

@@ -111,6 +111,11 @@ from .time_steppers import (
     RKMethods,
     create_stepper,
     ensemble_apply_bc_u_,
+    ensemble_apply_bc_u_pullback_,
+    ensemble_momentum_,
+    ensemble_momentum_pullback_,
+    ensemble_project_,
+    ensemble_project_pullback_,
     ensemble_rhs_,
     ode_method_cache,
     runge_kutta_method,
@@ -124,7 +129,7 @@ from . import autodiff32 as ad32  # noqa: E402  (the same over float32 fields an
 
 from . import neuralclosure  # noqa: E402  (lib/NeuralClosure: filters, filtered-DNS data generation, closures, losses, training)
 from .neuralclosure import (FaceAverage, VolumeAverage, cnn, collocate, create_dataloader_post, create_dataloader_prior,  # noqa: E402
-                            create_io_arrays, create_les_data, create_les_data_ensemble, create_loss_post, create_loss_prior, create_relerr_post, create_relerr_prior,
-                            decollocate, filtersaver, lesdatagen, reconstruct, reconstruct_, tensorclosure, train, wrappedclosure)
+                            create_io_arrays, create_les_data, create_les_data_ensemble, create_loss_post, create_loss_post_ensemble, create_loss_prior, create_relerr_post, create_relerr_prior,
+                            decollocate, filtersaver, lesdatagen, reconstruct, reconstruct_, tensorclosure, train, wrappedclosure, wrappedclosure_ensemble)
 
 _lib.load()  # fail loudly at import time if libinship.so is absent

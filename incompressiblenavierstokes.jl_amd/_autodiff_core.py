@@ -455,6 +455,121 @@ def timestep(ops, method, stepper, Δt, θ):
     return create_stepper(method, setup=setup, psolver=psolver, u=u, temp=temp, t=t, n=n + 1)
 
 
+# ------------------------------------------------------------------------------------ member forms: B trajectories in one graph
+# fp64 only (the ensemble handle is): the Functions take the `EnsembleCache` where the single-field ones take (setup, ops), and act on (B,) + N + (2,)
+# tensors in the layout of `vectorfields`.  Copy and save-for-backward rules are those of `_copy`, `_field` and `_save_inputs` above.
+def _ens_copy(cache, x):
+    """A fresh ensemble field (the layout of `vectorfields`) holding `x`: the in-place member forwards and pullbacks work on it."""
+    from .setup import vectorfields
+
+    f = vectorfields(cache.setup, cache.B)
+    if tuple(x.shape) != tuple(f.shape):
+        raise ValueError(f"ensemble field must have shape {tuple(f.shape)} (use vectorfields), got {tuple(x.shape)}")
+    f.copy_(x.detach())
+    return f
+
+
+def _ens_field(cache, x):
+    """`x` itself when it already is an ensemble field of the cache (float64, on its device, every member in the library's layout, members not
+    overlapping), else a copy in the layout of `vectorfields` (a cotangent with foreign strides, an expanded view)."""
+    from .time_steppers import _ensemble_ustride
+
+    try:
+        _ensemble_ustride(cache, x)
+        return x
+    except (TypeError, ValueError):
+        return _ens_copy(cache, x)
+
+
+def _ens_save(ctx, cache, x):
+    """The ensemble field a backward reads: an input that already is one goes through save_for_backward (an in-place edit before backward() raises), a
+    layout copy is private to the Function."""
+    f = _ens_field(cache, x)
+    ctx.save_for_backward(*((x,) if f is x else ()))
+    ctx.copy = None if f is x else f
+    return f
+
+
+def _ens_saved(ctx):
+    return ctx.saved_tensors[0] if ctx.copy is None else ctx.copy
+
+
+class _EnsembleApplyBCU(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, U, cache):
+        from .time_steppers import ensemble_apply_bc_u_
+
+        ctx.cache = cache
+        return ensemble_apply_bc_u_(cache, _ens_copy(cache, U))
+
+    @staticmethod
+    def backward(ctx, g):
+        from .time_steppers import ensemble_apply_bc_u_pullback_
+
+        return ensemble_apply_bc_u_pullback_(ctx.cache, _ens_copy(ctx.cache, g)), None
+
+
+class _EnsembleMomentum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, U, cache):
+        from .setup import vectorfields
+        from .time_steppers import ensemble_momentum_
+
+        ctx.cache = cache
+        return ensemble_momentum_(cache, vectorfields(cache.setup, cache.B), _ens_save(ctx, cache, U))
+
+    @staticmethod
+    def backward(ctx, g):
+        from .setup import vectorfields
+        from .time_steppers import ensemble_momentum_pullback_
+
+        c = ctx.cache
+        return ensemble_momentum_pullback_(c, vectorfields(c.setup, c.B), _ens_field(c, g), _ens_saved(ctx)), None
+
+
+class _EnsembleProject(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, U, cache):
+        from .time_steppers import ensemble_project_
+
+        ctx.cache = cache
+        return ensemble_project_(cache, _ens_copy(cache, U))
+
+    @staticmethod
+    def backward(ctx, g):
+        from .time_steppers import ensemble_project_pullback_
+
+        return ensemble_project_pullback_(ctx.cache, _ens_copy(ctx.cache, g)), None
+
+
+def timestep_ensemble(method, cache, U, Δt, θ, closure):
+    """The stage loop of `timestep` on the member Functions (the refusals are the caller's): one explicit Runge-Kutta step of all B members of `U`
+    without mutation.  Stage combinations are torch arithmetic on the whole (B, …) tensor, `closure(u, θ)` is called once per stage on all members, F
+    is summed in the order momentum, closure.
+
+    Ghost fills of `timestep` that are dropped here because they are the identity, in value and in the backward:
+      * the fill before every projection: `_EnsembleProject` is E·P·R, it reads the interior only (through its periodic images), and its pullback
+        returns zero ghost cotangents, on which the fill's transpose is the identity;
+      * the fill after every projection, the one at the top of stages 2 … s and the one that ends the step: `_EnsembleProject` ends with the periodic
+        extension E, fill = E·R and R·E = I, so fill·E = E and Eᵀ·fillᵀ = Eᵀ.
+    Only the fill at the top of the first stage stays: the caller's `U` may come with any ghost volumes."""
+    erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
+    A = erk.A
+    ustart, ku = U, []
+    u = _EnsembleApplyBCU.apply(U, cache)
+    for i in range(len(erk.b)):
+        F = _EnsembleMomentum.apply(u, cache)
+        if closure is not None:
+            F = F + closure(u, θ)
+        ku.append(F)
+        u = ustart
+        for j in range(i + 1):
+            if A[i, j] != 0:
+                u = u + (Δt * A[i, j]) * ku[j]
+        u = _EnsembleProject.apply(u, cache)
+    return u
+
+
 # ------------------------------------------------------------------------------------ checkpointed rollouts
 # The table's part of a rollout (the only native calls of this section):
 #   rk_cache(erk, setup, psolver)                           the forward's native cache (`ERKCache` / `ERKCache32`)

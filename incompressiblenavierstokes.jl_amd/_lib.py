@@ -141,6 +141,11 @@ SIGNATURES = {
     "ins_rk_ensemble_steps_f64": (C.c_int, [vp, C.c_double, vp, C.c_int64, C.c_double, C.c_double, C.c_int, vp]),
     "ins_rk_ensemble_rhs_f64": (C.c_int, [vp, C.c_double, vp, C.c_int64, vp, C.c_int64, vp]),
     "ins_rk_ensemble_apply_bc_u_f64": (C.c_int, [vp, vp, C.c_int64, vp]),
+    "ins_rk_ensemble_momentum_f64": (C.c_int, [vp, C.c_double, vp, C.c_int64, vp, C.c_int64, vp]),
+    "ins_rk_ensemble_project_f64": (C.c_int, [vp, vp, C.c_int64, vp]),
+    "ins_rk_ensemble_apply_bc_u_pullback_f64": (C.c_int, [vp, vp, C.c_int64, vp]),
+    "ins_rk_ensemble_momentum_pullback_f64": (C.c_int, [vp, C.c_double, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, vp]),
+    "ins_rk_ensemble_project_pullback_f64": (C.c_int, [vp, vp, C.c_int64, vp]),
     "ins_filter_face_members_f64": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, vp]),
     "ins_filter_volume_members_f64": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, vp]),
     "ins_combine_f64": (C.c_int, [vp, vp, vp, C.c_int, c_double_p, C.POINTER(vp), vp]),

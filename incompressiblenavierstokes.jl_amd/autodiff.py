@@ -25,11 +25,12 @@ from . import operators as O
 from ._step_route import Closure, Force, classify, steady_force
 from .pressure import project_, project_pullback_
 from .setup import _alloc, scalarfield, vectorfield
-from .time_steppers import LMWray3, _lmwray3_as_erk, create_stepper
+from .time_steppers import _PER_TRAJECTORY, LMWray3, _lmwray3_as_erk, create_stepper
 
 __all__ = ["apply_bc_u", "apply_bc_p", "apply_bc_temp", "gravity", "convection_diffusion_temp", "dissipation", "scalewithvolume", "divergence", "pressuregradient", "applypressure", "poisson", "convection", "diffusion",
            "momentum", "project", "right_hand_side", "create_right_hand_side", "timestep", "timesteps", "FaceAverage", "VolumeAverage", "tensorbasis", "divoftensor",
-           "lastdimcontract", "tensorinvariants", "tensorclosure_stress", "apply_bc_p_fields", "smagorinsky_closure", "smagorinsky_force"]
+           "lastdimcontract", "tensorinvariants", "tensorclosure_stress", "apply_bc_p_fields", "smagorinsky_closure", "smagorinsky_force",
+           "ensemble_apply_bc_u", "ensemble_momentum", "ensemble_project", "timestep_ensemble"]
 
 
 def _check_f64(setup, *xs):
@@ -452,6 +453,57 @@ def timestep(method, stepper, Δt, θ=None):
         # the native step runs the low-storage loop then (step_lmwray3.jl), whose ghost fills happen at other times than the ERK form's
         raise NotImplementedError("ad.timestep: LMWray3 with time-dependent boundary data or body force; use an ExplicitRungeKuttaMethod")
     return core.timestep(_OPS, method, stepper, Δt, θ)
+
+
+# ------------------------------------------------------------------------------------ B trajectories in one graph
+def _ensemble_cache(cache, U, what):
+    """The checks the member Functions share: an `EnsembleCache` (whose constructor has refused everything outside fp64 / 2-D / all-periodic / uniform /
+    power-of-two sides / psolver_spectral / no body force, closure or temperature on the setup) and a float64 tensor of its shape."""
+    from .time_steppers import EnsembleCache
+
+    if not isinstance(cache, EnsembleCache):
+        raise TypeError(f"ad.{what} needs an EnsembleCache (EnsembleCache(method, setup, psolver, B)); without one, {_PER_TRAJECTORY}")
+    if not isinstance(U, torch.Tensor):
+        raise TypeError(f"ad.{what}: ensemble fields are torch tensors (vectorfields)")
+    if U.dtype == torch.float32:
+        raise NotImplementedError(f"ad.{what}: Float32 ensembles are outside the member operators (fp64 only); {_PER_TRAJECTORY.replace('ad.', 'ad32.')}")
+    shape = (cache.B,) + tuple(cache.setup.grid.N) + (2,)
+    if tuple(U.shape) != shape:
+        raise ValueError(f"ad.{what}: ensemble field must have shape {shape} (use vectorfields), got {tuple(U.shape)}")
+    return cache
+
+
+def ensemble_apply_bc_u(cache, U):
+    """`ad.apply_bc_u` of every member of `U`, `(B,) + N + (2,)` as `vectorfields` makes it, in two launches forward and two backward."""
+    return core._EnsembleApplyBCU.apply(U, _ensemble_cache(cache, U, "ensemble_apply_bc_u"))
+
+
+def ensemble_momentum(cache, U):
+    """`ad.momentum(U[b], None, t, setup)` of every member in one launch; the backward is the member form of the tiled momentum pullback
+    (csrc/ins_adjoint.hip, k_momentum_pullback_members_2d), one launch.  `U` has valid ghost volumes."""
+    return core._EnsembleMomentum.apply(U, _ensemble_cache(cache, U, "ensemble_momentum"))
+
+
+def ensemble_project(cache, U):
+    """`ad.apply_bc_u(ad.project(ad.apply_bc_u(U[b])))` of every member: the member solve and the gradient-subtract + ghost pass forward, and backward
+    the ghost fold, the same solve and the gradient-subtract that leaves zero ghosts (the forward is E·P·R with P symmetric)."""
+    return core._EnsembleProject.apply(U, _ensemble_cache(cache, U, "ensemble_project"))
+
+
+def timestep_ensemble(method, cache, U, t, Δt, θ=None, closure=None):
+    """One explicit Runge-Kutta step of all B members of `U` without mutation: `ad.timestep` of every trajectory as ONE autograd graph.  The launch count
+    of the step's own operators and of their pullbacks does not depend on B; what `closure` launches is the closure's own (torch convolves float64
+    tensors sample by sample: `neuralclosure.cnn(..., batched=True)` does not).  Returns the new `(B,) + N + (2,)` field (ghost volumes valid), differentiable in `U` and, through the torch member closure
+    `closure(U, θ)` (`neuralclosure.wrappedclosure_ensemble`), in θ.  `t` is accepted for symmetry with `ad.timestep`: nothing in the scope depends on
+    time.  `method`: an ExplicitRungeKuttaMethod with more than one stage, or LMWray3 (run as the explicit method it is).
+
+    Scope: that of `EnsembleCache` — fp64, 2-D, all-periodic, exactly uniform, power-of-two sides 16 … 1024, `psolver_spectral`, no body force, no
+    temperature, one Δt and Re for all members.  Everything else raises NotImplementedError naming `ad.timestep` per trajectory."""
+    _ensemble_cache(cache, U, "timestep_ensemble")
+    erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
+    if len(erk.b) < 2:
+        raise NotImplementedError(f"ad.timestep_ensemble: a one-stage method is outside the ensemble loop; {_PER_TRAJECTORY}")
+    return core.timestep_ensemble(erk, cache, U, float(Δt), θ, closure)
 
 
 # ------------------------------------------------------------------------------------ checkpointed rollouts

@@ -189,7 +189,148 @@ int launch_momentum_pullback_tiled(const ins_grid* G, double visc, const double*
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
+
+// --------------------------------------------------------------------------------------------
+// Member momentum pullback: the 2-D sibling of the tiled kernel above for the members of an ensemble (ins_rk_ensemble.hip), in the idiom of k_flux2d
+//   lanes along x, 62 output columns per wavefront (lanes 0 and 63 carry the x halos; x neighbours by DPP shifts), a wavefront marches through the rows
+//   of a y-chunk with rows j-1, j, j+1 of both components of u and φ in registers (a 2 x 3 window each, rolled per row: two loads of u and two of φ per
+//   output row).  blockIdx.z is the member; its fields lie b·(its stride) elements behind the pointers.  φ is masked to the interior and everything
+//   outside the padded array reads as 0, so the terms are the branch-free ones of the 3-D kernel with the z direction dropped: the same sums as
+//   k_convdiff_adjoint<2, double, 3, ·> with the metric tables taken as constants.  The whole padded array of ubar is written (ghost volumes too).
+//   Chunking and tile walk depend on the grid only, so member b is bitwise what one member alone gives.
+// --------------------------------------------------------------------------------------------
+struct Adj2dArgs {
+  int N0, N1;
+  int yc;  // rows per chunk
+  long long sc;
+  double r[2][2];              // r[α][β]: 1/Δuβ (α == β) or 1/Δβ
+  double dco[2][2];            // ν · r[γ][β] · (mdx | mdxu)β: diffusion coefficient
+  double a1[2][2], a2[2][2];   // [β][α]: A₁βα, A₂βα
+  const double* u;
+  const double* phi;
+  double* ubar;
+};
+
+// Component q at this lane's volume + (dx, dy), |d| <= 1: y from the register window, x by a DPP shift (all lanes active); constant indices after unrolling.
+__device__ __forceinline__ double at2(const double (&W)[2][3], int q, int dx, int dy) {
+  const double v = W[q][dy + 1];
+  return dx == 1 ? next_h(v, 0.0) : dx == -1 ? prev_h(v, 0.0) : v;
+}
+
+template <bool ACC>
+__global__ __launch_bounds__(256) void k_momentum_pullback_members_2d(Adj2dArgs a, long long ustride, long long pstride, long long bstride) {
+  const long long b = blockIdx.z;
+  const int lane = threadIdx.x;
+  const int j0 = ((int)blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.y)) * a.yc;  // first output row (padded index)
+  if (j0 >= a.N1) return;  // whole wavefront
+  const int j1 = min(j0 + a.yc, a.N1);
+  const int P = (int)blockIdx.x * 62 + lane - 1;  // padded column of this lane
+  const bool colin = P >= 0 && P < a.N0;
+  const bool colint = P >= 1 && P <= a.N0 - 2;
+  const double* __restrict__ u = a.u + b * ustride;
+  const double* __restrict__ phi = a.phi + b * pstride;
+  double* __restrict__ ubar = a.ubar + b * bstride;
+
+  double U[2][3], F[2][3];  // [component][dy + 1] at this lane's column
+  auto load_row = [&](int slot, int yy) {
+    const bool ok = colin && yy >= 0 && yy < a.N1;
+    const bool okp = colint && yy >= 1 && yy <= a.N1 - 2;
+    const long long c = P + (long long)yy * a.N0;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      U[q][slot] = ok ? u[q * a.sc + c] : 0.0;
+      F[q][slot] = okp ? phi[q * a.sc + c] : 0.0;
+    }
+  };
+  load_row(0, j0 - 1);
+  load_row(1, j0);
+  for (int j = j0; j < j1; ++j) {
+    load_row(2, j + 1);
+    double out[2];
+#pragma unroll
+    for (int ga = 0; ga < 2; ++ga) {
+      const int g0 = ga == 0, g1 = ga == 1;  // e_γ
+      double v = 0.0;
+#pragma unroll
+      for (int be = 0; be < 2; ++be) {
+        const int b0 = be == 0, b1 = be == 1;  // e_β
+        const double f0 = at2(F, ga, 0, 0);
+        // diffusion
+        v += a.dco[ga][be] * (at2(F, ga, b0, b1) + at2(F, ga, -b0, -b1) - 2.0 * f0);
+        // (a) α = γ, direction β
+        const double rg = a.r[ga][be];
+        const double p0 = rg * (at2(F, ga, b0, b1) - f0);
+        const double p1 = rg * (f0 - at2(F, ga, -b0, -b1));
+        v += 0.5 * (p0 * (a.a2[be][ga] * at2(U, be, 0, 0) + a.a1[be][ga] * at2(U, be, g0, g1)) +
+                    p1 * (a.a2[be][ga] * at2(U, be, -b0, -b1) + a.a1[be][ga] * at2(U, be, g0 - b0, g1 - b1)));
+        // (b) β = γ, component α = be
+        const int al = be;
+        const double fa = at2(F, al, 0, 0);
+        const double ra = a.r[al][ga];
+        const double q0 = ra * (at2(F, al, g0, g1) - fa);
+        const double q1 = ra * (at2(F, al, g0 - b0, g1 - b1) - at2(F, al, -b0, -b1));
+        v += 0.5 * (q0 * (at2(U, al, 0, 0) + at2(U, al, g0, g1)) * a.a2[ga][al] +
+                    q1 * (at2(U, al, -b0, -b1) + at2(U, al, g0 - b0, g1 - b1)) * a.a1[ga][al]);
+      }
+      out[ga] = v;
+    }
+    if (lane >= 1 && lane <= 62 && colin) {
+      const long long c = P + (long long)j * a.N0;
+#pragma unroll
+      for (int ga = 0; ga < 2; ++ga) {
+        double* o = ubar + ga * a.sc + c;
+        *o = ACC ? *o + out[ga] : out[ga];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      U[q][0] = U[q][1];
+      U[q][1] = U[q][2];
+      F[q][0] = F[q][1];
+      F[q][1] = F[q][2];
+    }
+  }
+}
 }  // namespace
+
+// ubar[b] (+)= J_F(u[b])ᵀ phi[b] for the nb members of an ensemble in one launch (blockIdx.z = member); the grid is one of the chained 2-D loop (all-periodic,
+// every volume a DOF, exactly uniform: the caller's predicate).  Coefficients from the host copy of the grid tables, as launch_momentum_pullback_tiled.
+int ins_k_momentum_pullback_members_2d(const ins_grid* G, double visc, const double* u, long long ustride, const double* phi, long long pstride, double* ubar,
+                                       long long bstride, bool acc, int nb, hipStream_t s) {
+  const GridDev& g = G->g;
+  const ins_grid_desc_t& d = G->desc;
+  if (g.D != 2 || nb < 1 || nb > 65535) {
+    ins_set_error("ins_k_momentum_pullback_members_2d: a 2-D grid and 1 .. 65535 members");
+    return INS_ERR_INVALID;
+  }
+  Adj2dArgs a;
+  a.N0 = g.N[0];
+  a.N1 = g.N[1];
+  a.sc = g.sc;
+  for (int al = 0; al < 2; ++al)
+    for (int be = 0; be < 2; ++be) {
+      const double dxb = d.dx[be][1], dxub = d.dxu[be][1];
+      a.r[al][be] = al == be ? 1.0 / dxub : 1.0 / dxb;
+      const double m = al == be ? (dxb > 2 * INS_EPS ? 1.0 / dxb : 0.0) : (dxub > 2 * INS_EPS ? 1.0 / dxub : 0.0);
+      a.dco[al][be] = visc * a.r[al][be] * m;
+      a.a1[be][al] = d.A1[be][al][2];
+      a.a2[be][al] = d.A2[be][al][1];
+    }
+  a.u = u;
+  a.phi = phi;
+  a.ubar = ubar;
+  // rows per chunk as the forward stage kernel chooses them (ins_flux2d.hip): a function of the grid only
+  const int ntx = (int)cdiv(a.N0, 62);
+  const int want_chunks = std::max(1, 2048 / ntx);
+  a.yc = std::min(64, std::max(4, a.N1 / want_chunks));
+  const dim3 grid(ntx, cdiv(cdiv(a.N1, a.yc), 4), (unsigned)nb), block(64, 4, 1);
+  if (acc)
+    hipLaunchKernelGGL(k_momentum_pullback_members_2d<true>, grid, block, 0, s, a, ustride, pstride, bstride);
+  else
+    hipLaunchKernelGGL(k_momentum_pullback_members_2d<false>, grid, block, 0, s, a, ustride, pstride, bstride);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // internal launchers

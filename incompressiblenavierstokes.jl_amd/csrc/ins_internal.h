@@ -494,6 +494,11 @@ int ins_k_flux2d_members_force(const ins_grid* G, double visc, const double* u, 
 int ins_k_solve_members_2d(const ins_grid* G, const ins_poisson* ps, const double* u, long long ustride, int nb, double* pI, double* phat, const double* zrows,
                            hipStream_t s);
 int ins_k_grad_ghost_members_2d(const ins_grid* G, const ins_poisson* ps, double* u, long long ustride, int nb, const double* pI, hipStream_t s);
+// the same pass with every ghost volume written as 0 instead of its periodic image: the last pass of the members' projection pullback (Rᵀ of E·P·R)
+int ins_k_grad_zero_ghost_members_2d(const ins_grid* G, const ins_poisson* ps, double* u, long long ustride, int nb, const double* pI, hipStream_t s);
+// ubar[b] (+)= J_F(u[b])ᵀ phi[b] on the whole padded array of every member, one launch (ins_adjoint.hip, k_momentum_pullback_members_2d)
+int ins_k_momentum_pullback_members_2d(const ins_grid* G, double visc, const double* u, long long ustride, const double* phi, long long pstride, double* ubar,
+                                       long long bstride, bool acc, int nb, hipStream_t s);
 int ins_k_ownfft_xfwd_members(const ins_grid* G, const double* u, long long mstride, double* phat, int n0, int n1, int nb, const double* tw, hipStream_t s, int kxs);
 int ins_k_ownfft_xinv_members(const double* phat, double* pI, int n0, int n1, int nb, const double* tw, hipStream_t s, int kxs);
 int ins_k_ownfft_xysolve2d_members(const ins_grid* G, const double* u, long long mstride, double* pI, int n0, int n1, int nb, const double* twx, const double* twy,

@@ -416,10 +416,12 @@ __global__ __launch_bounds__(256) void k_grad_from_pI(GridDev g, double* __restr
 // images of the updated velocity (boundary_conditions.jl:276-288) — up to 7 images for a corner volume — so no
 // separate apply_bc_u! pass is needed before the next stage.  KEEP_P: also store the padded, ghost-filled p.
 // MEMBERS (D == 2, ensembles: ins_rk_ensemble.hip): blockIdx.z is the member; its field lies mstride elements further on, its pressure n0·n1.
-template <int D, bool KEEP_P, bool MEMBERS = false>
+// ZERO_GHOSTS (members only): the ghost images are written as 0, not as copies — the restriction's transpose at the end of the members' projection pullback.
+template <int D, bool KEEP_P, bool MEMBERS = false, bool ZERO_GHOSTS = false>
 __global__ __launch_bounds__(256) void k_grad_ghost(GridDev g, double* __restrict__ u, double* __restrict__ p, const double* __restrict__ pI, int n0,
                                                     int n1, int n2, long long mstride) {
   static_assert(!MEMBERS || (D == 2 && !KEEP_P), "members: 2-D, no padded pressure");
+  static_assert(!ZERO_GHOSTS || MEMBERS, "zeroed ghosts: the member form only");
   if (MEMBERS) {
     u += (long long)blockIdx.z * mstride;
     pI += (long long)blockIdx.z * n0 * n1;
@@ -456,7 +458,7 @@ __global__ __launch_bounds__(256) void k_grad_ghost(GridDev g, double* __restric
     }
     if (ok) {
 #pragma unroll
-      for (int a = 0; a < D; ++a) u[cc + a * g.sc] = un[a];
+      for (int a = 0; a < D; ++a) u[cc + a * g.sc] = (ZERO_GHOSTS && m != 0) ? 0.0 : un[a];
       if (KEEP_P) p[cc] = pc;
     }
   }
@@ -1502,6 +1504,13 @@ int ins_k_grad_ghost_members_2d(const ins_grid* G, const ins_poisson* ps, double
   const int n0 = ps->np[0], n1 = ps->np[1];
   dim3 block(64, 4, 1), grid(cdiv(n0, 64), cdiv(n1, 4), (unsigned)nb);
   hipLaunchKernelGGL((k_grad_ghost<2, false, true>), grid, block, 0, s, G->g, u, (double*)nullptr, pI, n0, n1, 1, ustride);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+int ins_k_grad_zero_ghost_members_2d(const ins_grid* G, const ins_poisson* ps, double* u, long long ustride, int nb, const double* pI, hipStream_t s) {
+  const int n0 = ps->np[0], n1 = ps->np[1];
+  dim3 block(64, 4, 1), grid(cdiv(n0, 64), cdiv(n1, 4), (unsigned)nb);
+  hipLaunchKernelGGL((k_grad_ghost<2, false, true, true>), grid, block, 0, s, G->g, u, (double*)nullptr, pI, n0, n1, 1, ustride);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }

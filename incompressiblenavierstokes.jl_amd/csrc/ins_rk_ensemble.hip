@@ -70,6 +70,65 @@ int refuse_chain(const char* entry, const char* why) {
   return INS_ERR_UNSUPPORTED;
 }
 
+// the same for the operator-level entries of the differentiable member step (ad.timestep_ensemble): the per-trajectory route is ad.timestep / create_loss_post
+int refuse_ad(const char* entry, const char* why) {
+  ins_set_error("%s: %s; the member operators run the boxes of the chained 2-D loop only (all-periodic, exactly uniform, power-of-two sides 16 .. 1024, spectral "
+                "solver on its own passes, more than one stage): differentiate each trajectory on its own (ad.timestep, create_loss_post: ins_momentum_f64, "
+                "ins_project_f64 and their pullbacks ins_momentum_pullback_f64, ins_apply_bc_u_pullback_f64, ins_project_pullback_f64 on each member)", entry, why);
+  return INS_ERR_UNSUPPORTED;
+}
+
+// Does a member of `out` (nb members of len elements, so apart) share an element with a member of `in` (si apart)?  The kernels read neighbours of what other
+// work-items write, so an output may not overlap an input anywhere, not only at the base pointers.  Both strides are >= len (check_args), so member i of `out`,
+// which starts a elements behind `in`, can only meet members floor(a / si) and floor(a / si) + 1 of `in`.
+bool members_overlap(const double* out, long long so, const double* in, long long si, int nb, long long len) {
+  const long long d = (long long)(((intptr_t)out - (intptr_t)in) / (intptr_t)sizeof(double));
+  for (int i = 0; i < nb; ++i) {
+    const long long a = d + (long long)i * so;
+    const long long j0 = a >= 0 ? a / si : -((-a + si - 1) / si);
+    for (long long j = j0; j <= j0 + 1; ++j)
+      if (j >= 0 && j < nb && a < j * si + len && j * si < a + len) return true;
+  }
+  return false;
+}
+
+// the checks every operator-level entry makes of one ensemble field and of the handle's box
+int check_entry(const ins_rk_ensemble* e, const char* entry, std::initializer_list<long long> strides) {
+  for (const long long st : strides) {
+    const int rc = check_args(e->grid->ncell, e->nb, st, 0);
+    if (rc) return rc;
+  }
+  if (!supported(e->grid, e->ps, e->nstage)) return refuse_ad(entry, "an option has switched the chained 2-D loop off since the handle was created");
+  return INS_OK;
+}
+
+// Transpose of k_bc_u_periodic2d_members in direction be: the copies x[0] = x[last-1]; x[last] = x[1] become, in reverse order, x̄[1] += x̄[last], x̄[last] = 0,
+// then x̄[last-1] += x̄[0], x̄[0] = 0 — the arithmetic of k_bc_u_pullback<2, double> on a periodic line.  Same launch shape as the forward.
+__global__ __launch_bounds__(256) void k_bc_u_periodic2d_members_pullback(double* __restrict__ G, long long gstride, long long sc, int N0, int N1, int be) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= (be == 0 ? N1 : N0)) return;
+  double* ga = G + (long long)blockIdx.y * gstride + (long long)blockIdx.z * sc;
+  const long long base = be == 0 ? (long long)q * N0 : q, sb = be == 0 ? 1 : N0;
+  const int last = (be == 0 ? N0 : N1) - 1;
+  const double r = ga[base + last * sb];
+  ga[base + last * sb] = 0.0;
+  ga[base + sb] += r;
+  const double l = ga[base];
+  ga[base] = 0.0;
+  ga[base + (last - 1) * sb] += l;
+}
+
+// the ghost fill's transpose for all members: direction 1, then direction 0 (the reverse of fill_ghosts), two launches whatever nb is
+int fold_ghosts(const ins_rk_ensemble* e, double* G, long long gstride, hipStream_t s) {
+  const GridDev& g = e->grid->g;
+  for (int be = 1; be >= 0; --be) {
+    const dim3 grid(cdiv(g.N[be == 0 ? 1 : 0], 256), (unsigned)e->nb, 2);
+    hipLaunchKernelGGL(k_bc_u_periodic2d_members_pullback, grid, dim3(256), 0, s, G, gstride, g.sc, g.N[0], g.N[1], be);
+    INS_LAUNCH_CHECK();
+  }
+  return INS_OK;
+}
+
 int fill_ghosts(const ins_rk_ensemble* e, double* U, long long ustride, hipStream_t s) {
   const GridDev& g = e->grid->g;
   for (int be = 0; be < 2; ++be) {
@@ -197,4 +256,63 @@ extern "C" int ins_rk_ensemble_apply_bc_u_f64(ins_rk_ensemble_t* e, double* U, i
   if (rc) return rc;
   if (!supported(e->grid, e->ps, e->nstage)) return refuse_chain("ins_rk_ensemble_apply_bc_u_f64", "an option has switched the chained 2-D loop off since the handle was created");
   return fill_ghosts(e, U, ustride, as_stream(stream));
+}
+
+// ------------------------------------------------------------------------------------------------
+// The operators of one differentiable step of all members (ad.timestep_ensemble) and their pullbacks.  Each entry costs the launches of one field whatever nb is.
+// ------------------------------------------------------------------------------------------------
+// F[b] = momentum!(U[b]) on the interior of every member (the force form of the stage kernel): U has valid ghosts and is read only, the ghost ring of F is untouched.
+extern "C" int ins_rk_ensemble_momentum_f64(ins_rk_ensemble_t* e, double visc, const double* U, int64_t ustride, double* F, int64_t fstride, void* stream) {
+  INS_REQUIRE(e && U && F, "null argument");
+  const int rc = check_entry(e, "ins_rk_ensemble_momentum_f64", {ustride, fstride});
+  if (rc) return rc;
+  INS_REQUIRE(!members_overlap(F, fstride, U, ustride, e->nb, 2 * e->grid->ncell), "momentum of the members cannot be formed in place: a member of F overlaps a member of U");
+  return ins_k_flux2d_members_force(e->grid, visc, U, ustride, F, fstride, e->nb, as_stream(stream));
+}
+
+// U[b] <- apply_bc_u(project(apply_bc_u(U[b]))) in place: the member solve, which reads the interior of U through its periodic images, then the
+// gradient-subtract + ghost pass, on the handle's pI / phat (the last two calls of ins_rk_ensemble_rhs_f64).
+extern "C" int ins_rk_ensemble_project_f64(ins_rk_ensemble_t* e, double* U, int64_t ustride, void* stream) {
+  INS_REQUIRE(e && U, "null argument");
+  int rc = check_entry(e, "ins_rk_ensemble_project_f64", {ustride});
+  if (rc) return rc;
+  hipStream_t s = as_stream(stream);
+  if ((rc = ins_k_solve_members_2d(e->grid, e->ps, U, ustride, e->nb, e->pI, e->phat, e->zrows, s))) return rc;
+  return ins_k_grad_ghost_members_2d(e->grid, e->ps, U, ustride, e->nb, e->pI, s);
+}
+
+// The transpose of ins_rk_ensemble_apply_bc_u_f64 on the padded arrays, in place: ghost cotangents are added to the interior volumes they were copied from and
+// zeroed, direction 1 before direction 0.
+extern "C" int ins_rk_ensemble_apply_bc_u_pullback_f64(ins_rk_ensemble_t* e, double* G, int64_t gstride, void* stream) {
+  INS_REQUIRE(e && G, "null argument");
+  const int rc = check_entry(e, "ins_rk_ensemble_apply_bc_u_pullback_f64", {gstride});
+  if (rc) return rc;
+  return fold_ghosts(e, G, gstride, as_stream(stream));
+}
+
+// Ubar[b] (+)= J_F(U[b])ᵀ Phibar[b] over the whole padded array of every member, the contract of ins_momentum_pullback_f64, in one launch.
+extern "C" int ins_rk_ensemble_momentum_pullback_f64(ins_rk_ensemble_t* e, double visc, const double* U, int64_t ustride, const double* Phibar, int64_t pstride,
+                                                     double* Ubar, int64_t bstride, int accumulate, void* stream) {
+  INS_REQUIRE(e && U && Phibar && Ubar, "null argument");
+  const int rc = check_entry(e, "ins_rk_ensemble_momentum_pullback_f64", {ustride, pstride, bstride});
+  if (rc) return rc;
+  const long long len = 2 * e->grid->ncell;
+  INS_REQUIRE(!members_overlap(Ubar, bstride, U, ustride, e->nb, len) && !members_overlap(Ubar, bstride, Phibar, pstride, e->nb, len),
+              "momentum pullback cannot run in place: a member of Ubar overlaps a member of U or Phibar");
+  return ins_k_momentum_pullback_members_2d(e->grid, visc, U, ustride, Phibar, pstride, Ubar, bstride, accumulate != 0, e->nb, as_stream(stream));
+}
+
+// The exact transpose of ins_rk_ensemble_project_f64 on the padded arrays, in place.  The forward is E·P·R: R restricts to the interior (the solve forms the
+// divergence through the periodic wrap and reads no ghost volume: k_xfwd / k_xysolve2d with XSRC_DIV_2D), P = I − G L⁻¹ Ω D is the periodic projection, which
+// is symmetric on an exactly uniform grid (Ω constant, G = −Dᵀ), and E is the periodic extension written by the last pass.  So the transpose is Rᵀ·P·Eᵀ: fold
+// the ghost cotangents into the interior, the SAME member solve and gradient-subtract on the folded cotangent, every ghost volume zero.
+// Launches: the forward's plus the two of the fold.
+extern "C" int ins_rk_ensemble_project_pullback_f64(ins_rk_ensemble_t* e, double* G, int64_t gstride, void* stream) {
+  INS_REQUIRE(e && G, "null argument");
+  int rc = check_entry(e, "ins_rk_ensemble_project_pullback_f64", {gstride});
+  if (rc) return rc;
+  hipStream_t s = as_stream(stream);
+  if ((rc = fold_ghosts(e, G, gstride, s))) return rc;
+  if ((rc = ins_k_solve_members_2d(e->grid, e->ps, G, gstride, e->nb, e->pI, e->phat, e->zrows, s))) return rc;
+  return ins_k_grad_zero_ghost_members_2d(e->grid, e->ps, G, gstride, e->nb, e->pI, s);
 }

@@ -30,11 +30,11 @@ from .pressure import default_psolver, project_
 from .processors import Observable, processor
 from .setup import Setup, scalarfield, to_numpy, vectorfield
 from .solver import solve_unsteady
-from .time_steppers import RKMethods, create_stepper, ode_method_cache, timestep_
+from .time_steppers import _PER_TRAJECTORY, RKMethods, create_stepper, ode_method_cache, timestep_
 
 __all__ = ["AbstractFilter", "FaceAverage", "VolumeAverage", "reconstruct", "reconstruct_", "lesdatagen", "filtersaver", "create_les_data",
-           "create_les_data_ensemble", "create_io_arrays", "wrappedclosure", "collocate", "decollocate", "cnn", "tensorclosure", "create_dataloader_prior", "create_dataloader_post",
-           "create_loss_prior", "create_relerr_prior", "create_loss_post", "create_relerr_post", "train"]
+           "create_les_data_ensemble", "create_io_arrays", "wrappedclosure", "wrappedclosure_ensemble", "collocate", "decollocate", "cnn", "tensorclosure", "create_dataloader_prior", "create_dataloader_post",
+           "create_loss_prior", "create_relerr_prior", "create_loss_post", "create_loss_post_ensemble", "create_relerr_post", "train"]
 
 
 # ------------------------------------------------------------------------------------------------ filters (filter.jl)
@@ -469,6 +469,25 @@ def wrappedclosure(m, setup):
     return neuralclosure
 
 
+def wrappedclosure_ensemble(m, setup):
+    """`wrappedclosure` for the B members of an ensemble field `(B,) + N + (2,)` (`vectorfields`): the interiors of all members go into `m` as B samples,
+    `(n0, n1, 2, B)`, in ONE call, the result is padded periodically and comes back in the layout of `vectorfields`.  Differentiable; no loop over B.
+    A member closure for `ad.timestep_ensemble` and `create_loss_post_ensemble`."""
+    inside = _inside(setup)
+    if setup.grid.dimension != 2:
+        raise NotImplementedError("wrappedclosure_ensemble: a 3-D setup is outside the member operators (2-D); wrap the model with wrappedclosure and use "
+                                  "ad.timestep / create_loss_post per trajectory")
+
+    def neuralclosure_ensemble(U, θ):
+        x = U[(slice(None),) + inside].permute(1, 2, 3, 0)  # (n0, n1, 2, B)
+        mu = m(x, θ).permute(3, 2, 1, 0)  # (B, 2, n1, n0): the memory order of `vectorfields`
+        for d in (2, 3):
+            mu = torch.cat([mu.narrow(d, mu.shape[d] - 1, 1), mu, mu.narrow(d, 0, 1)], dim=d)
+        return mu.permute(0, 3, 2, 1)
+
+    return neuralclosure_ensemble
+
+
 def collocate(u):
     """Interpolate velocity components to volume centers (closure.jl:37-72): `(n…, D, nsample)`, out[i] = (u_α[i] + u_α[i − e_α]) / 2,
     periodic."""
@@ -482,12 +501,54 @@ def decollocate(u):
     return torch.stack([(u[..., a, :] + torch.roll(u[..., a, :], -1, dims=a)) / 2 for a in range(D)], dim=-2)
 
 
+class _ConvFoldedSamples(torch.autograd.Function):
+    """`conv2d(x, w, b)` of the ONE sample that `CNN(batched=True)` folds all samples into, with the weight gradient summed in chunks.  torch's own float64
+    weight gradient is one GEMM with an 8 x 50-sized result and the whole folded plane as its inner dimension; the library kernel chosen for it runs that
+    reduction in a single workgroup and was measured at 3.5 ms per call for 18 000 columns (88 % of a loss evaluation at 32², B = 16).  Here the columns are
+    cut into chunks of `CHUNK`, one batched GEMM forms the partial sums side by side and one sum adds them: two launches whatever the plane's size."""
+
+    CHUNK = 2048
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        return torch.nn.functional.conv2d(x, w, b)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        gx = torch.nn.grad.conv2d_input(x.shape, w, g) if ctx.needs_input_grad[0] else None
+        gw = gb = None
+        G = g.reshape(g.shape[1], -1)  # (Cout, N): one sample
+        if ctx.needs_input_grad[1]:
+            cols = torch.nn.functional.unfold(x, w.shape[2:])[0]  # (Cin·k², N)
+            n = _ConvFoldedSamples.CHUNK
+            S = -(-G.shape[1] // n)
+            pad = S * n - G.shape[1]
+            Gp, cp = torch.nn.functional.pad(G, (0, pad)), torch.nn.functional.pad(cols, (0, pad))
+            parts = torch.bmm(Gp.reshape(G.shape[0], S, n).transpose(0, 1), cp.reshape(cols.shape[0], S, n).permute(1, 2, 0))  # (S, Cout, Cin·k²)
+            gw = parts.sum(0).reshape(w.shape)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = G.sum(1)
+        return gx, gw, gb
+
+
 class CNN(torch.nn.Module):
     """collocate → circular padding by Σ radii → convolutions (kernel 2r+1, no further padding) → decollocate (cnn.jl); float64 parameters, or
-    float32 with `dtype=torch.float32`."""
+    float32 with `dtype=torch.float32`.
 
-    def __init__(self, D, radii, channels, activations, use_bias, generator=None, dtype=torch.float64):
+    `batched=True` (off by default): the convolutions see all samples as ONE sample.  torch convolves float64 tensors sample by sample (im2col, GEMM,
+    col2im per sample), so the launch count of a forward and backward grows with the number of samples.  The convolutions take no padding of their own,
+    so the circularly padded samples can be laid side by side along the first spatial axis: an output row of sample b reads rows of sample b's own padded
+    block only, the rows that straddle two samples are computed and dropped (2·Σradii of every n + 2·Σradii rows).  Same sums per output value in another
+    GEMM blocking: the result agrees with `batched=False` to rounding, and the launch count does not depend on the number of samples.  In 2-D the weight
+    gradient of the folded sample is summed in chunks (`_ConvFoldedSamples`)."""
+
+    def __init__(self, D, radii, channels, activations, use_bias, generator=None, dtype=torch.float64, batched=False):
         super().__init__()
+        self.batched = bool(batched)
         if dtype not in (torch.float64, torch.float32):
             raise TypeError("cnn: dtype is torch.float64 or torch.float32")
         if channels[-1] != D:
@@ -508,22 +569,29 @@ class CNN(torch.nn.Module):
         x = collocate(u)
         x = x.permute(D + 1, D, *range(D))  # (nsample, D, n…)
         x = torch.nn.functional.pad(x, (self.pad,) * (2 * D), mode="circular")
+        nsample, n0, rows = x.shape[0], x.shape[2] - 2 * self.pad, x.shape[2]
+        if self.batched:  # (nsample, C, Hp, …) -> (1, C, nsample·Hp, …)
+            x = x.transpose(0, 1).reshape(1, x.shape[1], nsample * rows, *x.shape[3:])
         for conv, σ in zip(self.convs, self.activations):
-            x = conv(x)
+            x = _ConvFoldedSamples.apply(x, conv.weight, conv.bias) if self.batched and D == 2 else conv(x)
             if σ is not None:
                 x = σ(x)
+        if self.batched:  # rows b·Hp … b·Hp + n0 − 1 are sample b's; the 2·pad rows the convolutions consumed are put back so that the blocks line up
+            x = torch.nn.functional.pad(x, (0, 0) * (D - 1) + (0, 2 * self.pad))
+            x = x.reshape(x.shape[1], nsample, rows, *x.shape[3:]).narrow(2, 0, n0).transpose(0, 1)
         x = x.permute(*range(2, D + 2), 1, 0)
         return decollocate(x)
 
 
-def cnn(*, setup, radii, channels, activations, use_bias, rng=None, dtype=torch.float64):
+def cnn(*, setup, radii, channels, activations, use_bias, rng=None, dtype=torch.float64, batched=False):
     """Create CNN closure model (cnn.jl): a `torch.nn.Module` on the device of `setup`, callable as `m(x, θ)`.  `activations[i]` is a
     callable or None (identity); `rng`: a `torch.Generator` (CPU) or an integer seed for the weights; `dtype`: the precision of the
-    parameters, and so of the arrays the model takes (torch.float64 or torch.float32)."""
+    parameters, and so of the arrays the model takes (torch.float64 or torch.float32).  `batched=True`: all samples of a call go through the
+    convolutions as one (see `CNN`), for member closures (`wrappedclosure_ensemble`); same parameters and, to rounding, the same result."""
     gen = rng
     if rng is not None and not isinstance(rng, torch.Generator):
         gen = torch.Generator().manual_seed(int(rng))
-    return CNN(setup.grid.dimension, list(radii), list(channels), activations, use_bias, gen, dtype).to(setup.device)
+    return CNN(setup.grid.dimension, list(radii), list(channels), activations, use_bias, gen, dtype, batched).to(setup.device)
 
 
 class TensorClosure(torch.nn.Module):
@@ -708,6 +776,73 @@ def create_loss_post(*, setup, method, psolver, closure_model, nsubstep=1):
         return total / len(data)
 
     return loss_post
+
+
+def _post_ensemble_steps(data):
+    """The shared step sizes `t[it] − t[it−1]` of a batch of trajectories (start times may differ: nothing depends on t).  ValueError for trajectories of
+    different lengths or step sizes.  Two saved times carry a rounding error of eps·|t| each, so their difference is known to 2·eps·max|t|, and two such
+    differences compare to 4·eps·max|t| (absolute): sizes that agree within that are the same step, and the first trajectory's are used."""
+    ts = [np.asarray(traj["t"], dtype=np.float64) for traj in data]
+    if not ts:
+        raise ValueError("create_loss_post_ensemble: an empty batch")
+    dts = np.diff(ts[0])
+    for t in ts[1:]:
+        if len(t) != len(ts[0]):
+            raise ValueError(f"create_loss_post_ensemble: trajectories of {len(ts[0])} and {len(t)} states in one batch; the ensemble step advances all "
+                             f"members together; {_PER_TRAJECTORY}")
+        tol = 4 * np.finfo(np.float64).eps * max(np.abs(t).max(), np.abs(ts[0]).max())
+        if not np.all(np.abs(np.diff(t) - dts) <= tol):
+            raise ValueError(f"create_loss_post_ensemble: the trajectories of the batch have different step sizes (the ensemble step shares one Δt); "
+                             f"{_PER_TRAJECTORY}")
+    return dts
+
+
+def create_loss_post_ensemble(*, setup, method, psolver, closure_model, nsubstep=1):
+    """`create_loss_post` with all trajectories of the batch in ONE unrolled graph (`ad.timestep_ensemble`): the B first states go into one ensemble
+    field, every step advances all members, and the same per-trajectory normalised error sums Σ|u − u_ref|² / Σ|u_ref|² (on `Iu`) are averaged over
+    trajectories and states.  The launch count of the step's operators and of their backward does not depend on B; the closure's is its own (torch convolves
+    float64 tensors sample by sample: a `cnn(..., batched=True)` keeps the whole evaluation independent of B).  `data`: the batch format of
+    `create_dataloader_post`; all trajectories share `len(t)` and the step sizes (ValueError otherwise, naming `create_loss_post`).  `closure_model`: a
+    member closure (`wrappedclosure_ensemble(m, setup)`) or None.  One `EnsembleCache` per B is built on first use and kept.
+
+    Scope: that of `EnsembleCache` (fp64, 2-D, all-periodic, uniform, power-of-two sides 16 … 1024, `psolver_spectral`, a method with more than one stage, no
+    body force / temperature / closure on the setup itself); everything else raises NotImplementedError naming `create_loss_post`."""
+    from .time_steppers import EnsembleCache, LMWray3, _ensemble_refusal, _lmwray3_as_erk
+    from .setup import vectorfields
+
+    erk = _lmwray3_as_erk(method) if isinstance(method, LMWray3) else method
+    why = "a Float32 pressure solver (the member operators are fp64)" if isinstance(psolver, f32.psolver_spectral32) else _ensemble_refusal(erk, setup, psolver)
+    if why is not None:
+        raise NotImplementedError(f"create_loss_post_ensemble: {why} is outside the ensemble route; {_PER_TRAJECTORY}")
+    nsubstep = int(nsubstep)
+    if nsubstep < 1:
+        raise ValueError("nsubstep must be at least 1")
+    inside = (slice(None),) + _inside(setup)
+    caches = {}
+
+    def loss_post_ensemble(data, θ):
+        dts = _post_ensemble_steps(data)
+        B = len(data)
+        if B not in caches:
+            try:
+                caches[B] = EnsembleCache(erk, setup, psolver, B)
+            except NotImplementedError as e:  # the library's own predicate: a grid that is not exactly uniform, a run-time switch
+                raise NotImplementedError(f"create_loss_post_ensemble: {e}; {_PER_TRAJECTORY}") from None
+        cache = caches[B]
+        ref = torch.stack([traj["u"] for traj in data]).to(dtype=torch.float64, device=setup.device)  # (B,) + N + (2, nt)
+        U = vectorfields(setup, B)
+        U.copy_(ref[..., 0])
+        loss = 0.0
+        for it in range(1, len(dts) + 1):
+            Δt = float(dts[it - 1]) / nsubstep
+            for _ in range(nsubstep):
+                U = ad.timestep_ensemble(erk, cache, U, 0.0, Δt, θ, closure_model)
+            uref = ref[..., it][inside]
+            d = U[inside] - uref
+            loss = loss + ((d * d).sum(dim=(1, 2, 3)) / (uref * uref).sum(dim=(1, 2, 3))).sum()
+        return loss / (len(dts) * B)
+
+    return loss_post_ensemble
 
 
 def create_relerr_post(*, data, setup, method, psolver, closure_model, nsubstep=1):

@@ -455,6 +455,16 @@ def _member_stride(setup, U, B=None):
     return int(U.stride(0)) if U.shape[0] > 1 else ncomp
 
 
+def _ensemble_call(name, entry, cache, route, *args):
+    """One native call of an ensemble wrapper: `entry(handle, *args, stream)`; the library's own refusal (INS_ERR_UNSUPPORTED: a run-time switch) becomes a
+    NotImplementedError that names `route`, the way without the ensemble."""
+    lib = _lib.load()
+    rc = getattr(lib, entry)(cache.handle, *args, cache.setup.stream)
+    if rc == -4:
+        raise NotImplementedError(f"{name}: {lib.ins_last_error().decode()}; {route}")
+    _lib.check(rc)
+
+
 def timesteps_ensemble_(cache, U, t, Δt, nsteps):
     """`nsteps` explicit Runge-Kutta steps of size Δt of every member `U[b]`, in place, as ONE native loop (`ins_rk_ensemble_steps_f64`): the kernels and
     the number of launches of `timesteps_` on a single field, each launch working on all B members.  Re, Δt and the tableau are the cache's and shared; no
@@ -464,12 +474,8 @@ def timesteps_ensemble_(cache, U, t, Δt, nsteps):
     nsteps = int(nsteps)
     if nsteps < 0:
         raise ValueError("nsteps must be non-negative")
-    setup = cache.setup
-    lib = _lib.load()
-    rc = lib.ins_rk_ensemble_steps_f64(cache.handle, 1.0 / setup.Re, C.c_void_p(U.data_ptr()), ustride, float(t), float(Δt), nsteps, setup.stream)
-    if rc == -4:
-        raise NotImplementedError(f"timesteps_ensemble_: {lib.ins_last_error().decode()}; {_PER_MEMBER}")
-    _lib.check(rc)
+    _ensemble_call("timesteps_ensemble_", "ins_rk_ensemble_steps_f64", cache, _PER_MEMBER, 1.0 / cache.setup.Re, C.c_void_p(U.data_ptr()), ustride, float(t),
+                   float(Δt), nsteps)
     return U
 
 
@@ -487,12 +493,8 @@ def ensemble_rhs_(cache, F, U):
     fstride = _ensemble_ustride(cache, F)
     if F.data_ptr() == U.data_ptr():
         raise ValueError("ensemble_rhs_ cannot run in place: F and U are the same array")
-    setup = cache.setup
-    lib = _lib.load()
-    rc = lib.ins_rk_ensemble_rhs_f64(cache.handle, 1.0 / setup.Re, C.c_void_p(U.data_ptr()), ustride, C.c_void_p(F.data_ptr()), fstride, setup.stream)
-    if rc == -4:
-        raise NotImplementedError(f"ensemble_rhs_: {lib.ins_last_error().decode()}; {_PER_MEMBER_RHS}")
-    _lib.check(rc)
+    _ensemble_call("ensemble_rhs_", "ins_rk_ensemble_rhs_f64", cache, _PER_MEMBER_RHS, 1.0 / cache.setup.Re, C.c_void_p(U.data_ptr()), ustride,
+                   C.c_void_p(F.data_ptr()), fstride)
     return F
 
 
@@ -500,13 +502,66 @@ def ensemble_apply_bc_u_(cache, U):
     """`apply_bc_u_` of every member of `U` on the periodic box of `cache`, in place, in two launches (`ins_rk_ensemble_apply_bc_u_f64`): for members whose
     interior something other than the stepper wrote (the member filters write `Iu[α]` only).  Returns U."""
     ustride = _ensemble_ustride(cache, U)
-    setup = cache.setup
-    lib = _lib.load()
-    rc = lib.ins_rk_ensemble_apply_bc_u_f64(cache.handle, C.c_void_p(U.data_ptr()), ustride, setup.stream)
-    if rc == -4:
-        raise NotImplementedError(f"ensemble_apply_bc_u_: {lib.ins_last_error().decode()}; call apply_bc_u_(U[b], t, setup) per member")
-    _lib.check(rc)
+    _ensemble_call("ensemble_apply_bc_u_", "ins_rk_ensemble_apply_bc_u_f64", cache, "call apply_bc_u_(U[b], t, setup) per member", C.c_void_p(U.data_ptr()), ustride)
     return U
+
+
+_PER_TRAJECTORY = "differentiate each trajectory on its own: ad.timestep per member, create_loss_post for the a-posteriori loss"
+
+
+def _members_overlap(out, so, inp, si, nb, n):
+    """Does a member of the ensemble field `out` (member stride `so` elements) share an element with a member of `inp` (stride `si`)?  `n`: elements of
+    a member.  The host-side twin of the library's own check (csrc/ins_rk_ensemble.hip, members_overlap)."""
+    d = (out.data_ptr() - inp.data_ptr()) // out.element_size()
+    for i in range(nb):
+        a = d + i * so
+        j0 = a // si
+        if any(0 <= j < nb and a < j * si + n and j * si < a + n for j in (j0, j0 + 1)):
+            return True
+    return False
+
+
+def ensemble_momentum_(cache, F, U):
+    """`F[b] = momentum_(U[b])` of every member on the interior, one launch whatever B is (`ins_rk_ensemble_momentum_f64`, the force form of the stage
+    kernel).  `U` is read only and has valid ghost volumes; the ghost ring of `F` is untouched.  Returns F."""
+    ustride, fstride = _ensemble_ustride(cache, U), _ensemble_ustride(cache, F)
+    if _members_overlap(F, fstride, U, ustride, cache.B, int(np.prod(U.shape[1:]))):
+        raise ValueError("ensemble_momentum_ cannot run in place: a member of F overlaps a member of U")
+    _ensemble_call("ensemble_momentum_", "ins_rk_ensemble_momentum_f64", cache, _PER_TRAJECTORY, 1.0 / cache.setup.Re, C.c_void_p(U.data_ptr()), ustride, C.c_void_p(F.data_ptr()), fstride)
+    return F
+
+
+def ensemble_project_(cache, U):
+    """`U[b] ← apply_bc_u_(project_(apply_bc_u_(U[b])))` of every member, in place (`ins_rk_ensemble_project_f64`): the member solve reads the interior
+    through its periodic images, the last pass writes every ghost volume.  Returns U."""
+    _ensemble_call("ensemble_project_", "ins_rk_ensemble_project_f64", cache, _PER_TRAJECTORY, C.c_void_p(U.data_ptr()), _ensemble_ustride(cache, U))
+    return U
+
+
+def ensemble_apply_bc_u_pullback_(cache, G):
+    """The transpose of `ensemble_apply_bc_u_` on the padded arrays of every member, in place, two launches (`ins_rk_ensemble_apply_bc_u_pullback_f64`).
+    Returns G."""
+    _ensemble_call("ensemble_apply_bc_u_pullback_", "ins_rk_ensemble_apply_bc_u_pullback_f64", cache, _PER_TRAJECTORY, C.c_void_p(G.data_ptr()), _ensemble_ustride(cache, G))
+    return G
+
+
+def ensemble_momentum_pullback_(cache, Ubar, Φbar, U, accumulate=False):
+    """`Ubar[b] (+)= J_F(U[b])ᵀ Φbar[b]` over the whole padded array of every member in one launch (`ins_rk_ensemble_momentum_pullback_f64`, the
+    member form of the tiled pullback): the contract of `momentum_pullback_`.  `U` and `Φbar` are read only.  Returns Ubar."""
+    ustride, pstride, bstride = _ensemble_ustride(cache, U), _ensemble_ustride(cache, Φbar), _ensemble_ustride(cache, Ubar)
+    n = int(np.prod(U.shape[1:]))
+    if _members_overlap(Ubar, bstride, U, ustride, cache.B, n) or _members_overlap(Ubar, bstride, Φbar, pstride, cache.B, n):
+        raise ValueError("ensemble_momentum_pullback_ cannot run in place: a member of Ubar overlaps a member of U or Φbar")
+    _ensemble_call("ensemble_momentum_pullback_", "ins_rk_ensemble_momentum_pullback_f64", cache, _PER_TRAJECTORY, 1.0 / cache.setup.Re, C.c_void_p(U.data_ptr()), ustride, C.c_void_p(Φbar.data_ptr()), pstride,
+                   C.c_void_p(Ubar.data_ptr()), bstride, int(bool(accumulate)))
+    return Ubar
+
+
+def ensemble_project_pullback_(cache, G):
+    """The exact transpose of `ensemble_project_` on the padded arrays of every member, in place (`ins_rk_ensemble_project_pullback_f64`): ghost cotangents
+    folded into the interior, the same member solve, ghost volumes zero on return.  Returns G."""
+    _ensemble_call("ensemble_project_pullback_", "ins_rk_ensemble_project_pullback_f64", cache, _PER_TRAJECTORY, C.c_void_p(G.data_ptr()), _ensemble_ustride(cache, G))
+    return G
 
 
 def ode_method_cache(method, setup, psolver=None):

@@ -626,6 +626,38 @@ function ensemble_apply_bc_u!(cache::HipEnsembleCache, U::RA)
                 cache.h, pointer(U), Int64(stride(U, 4)), stream()))
     U
 end
+# The operators of one differentiable step of all members and their pullbacks (a-posteriori training on B trajectories): each a launch chain of one field.
+# F[:, :, :, b] = momentum!(U[:, :, :, b]) on the interior; U has valid ghosts
+function ensemble_momentum!(cache::HipEnsembleCache, F::RA, U::RA)
+    check(ccall((:ins_rk_ensemble_momentum_f64, lib), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                cache.h, 1 / cache.setup.Re, pointer(U), Int64(stride(U, 4)), pointer(F), Int64(stride(F, 4)), stream()))
+    F
+end
+# U[:, :, :, b] = apply_bc_u!(project!(apply_bc_u!(U[:, :, :, b]))), in place
+function ensemble_project!(cache::HipEnsembleCache, U::RA)
+    check(ccall((:ins_rk_ensemble_project_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                cache.h, pointer(U), Int64(stride(U, 4)), stream()))
+    U
+end
+function ensemble_apply_bc_u_pullback!(cache::HipEnsembleCache, G::RA)
+    check(ccall((:ins_rk_ensemble_apply_bc_u_pullback_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                cache.h, pointer(G), Int64(stride(G, 4)), stream()))
+    G
+end
+# Ubar[:, :, :, b] (+)= J_F(U[:, :, :, b])ᵀ Φbar[:, :, :, b] over the whole padded array
+function ensemble_momentum_pullback!(cache::HipEnsembleCache, Ubar::RA, Φbar::RA, U::RA; accumulate = false)
+    check(ccall((:ins_rk_ensemble_momentum_pullback_f64, lib), Cint,
+                (Ptr{Cvoid}, Cdouble, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Cint, Ptr{Cvoid}),
+                cache.h, 1 / cache.setup.Re, pointer(U), Int64(stride(U, 4)), pointer(Φbar), Int64(stride(Φbar, 4)), pointer(Ubar), Int64(stride(Ubar, 4)),
+                Cint(accumulate), stream()))
+    Ubar
+end
+# the exact transpose of ensemble_project!, in place; ghost volumes zero on return
+function ensemble_project_pullback!(cache::HipEnsembleCache, G::RA)
+    check(ccall((:ins_rk_ensemble_project_pullback_f64, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                cache.h, pointer(G), Int64(stride(G, 4)), stream()))
+    G
+end
 # ins_temperature_desc_t (include/ins_hip.h): the scalars of `temperature_equation` (setup.jl:48-87) the native stage loop needs
 struct TempDesc
     a2::Float64
