@@ -313,6 +313,21 @@ int ins_rk_ensemble_apply_bc_u_pullback_f64(ins_rk_ensemble_t* ens, double* G, i
 int ins_rk_ensemble_momentum_pullback_f64(ins_rk_ensemble_t* ens, double visc, const double* U, int64_t ustride, const double* Phibar, int64_t pstride, double* Ubar,
                                           int64_t bstride, int accumulate, void* stream);
 int ins_rk_ensemble_project_pullback_f64(ins_rk_ensemble_t* ens, double* G, int64_t gstride, void* stream);
+/* Observing the ensemble (csrc/ins_rk_ensemble_observe.hip): the single-field diagnostics for all members in a launch count that does not depend on nbatch,
+ * with no allocation per call and no host synchronisation.  U as above, read only, ghost volumes valid; what lies between members is not read.
+ * stats: out (DEVICE, nbatch x 3): out[3b] = ins_total_kinetic_energy_f64(interpolate_first = 0) of member b (the same terms summed in another order: agrees
+ *   to a relative 2 n0 n1 2^-53), out[3b+1] = ins_max_abs_divergence_f64 and out[3b+2] = ins_cfl_timestep_f64(grid, Re) of member b, both bitwise.  Two
+ *   launches: one pass over U that writes workgroup partials to an array of the handle (allocated on the first call), one workgroup per member that combines
+ *   them in a fixed order.  No floating-point atomics; a member's values do not depend on nbatch.
+ * spectrum: `offsets` / `inds` are the shells of spectral_stuff, as ins_spectrum_create takes them; row b of ehat (DEVICE, nbatch x nbin) is ins_spectrum_f64 of
+ *   member b.  Four launches and no FFT-library call: the solver's paired-row x pass fed from the velocity components, a forward y pass over the lines of all
+ *   members, chunked shell sums.  The handle borrows `ens`, which must outlive it and keep its nbatch.
+ * A handle whose box an INS_DISABLE_* switch has since turned away: INS_ERR_UNSUPPORTED with a message that names the per-member diagnostics. */
+typedef struct ins_ensemble_spectrum ins_ensemble_spectrum_t;
+int ins_rk_ensemble_stats_f64(ins_rk_ensemble_t* ens, double Re, const double* U, int64_t ustride, double* out, void* stream);
+int ins_rk_ensemble_spectrum_create(ins_rk_ensemble_t* ens, int nbin, const int64_t* offsets, const int64_t* inds, ins_ensemble_spectrum_t** out);
+int ins_rk_ensemble_spectrum_f64(ins_ensemble_spectrum_t* spectrum, const double* U, int64_t ustride, double* ehat, void* stream);
+int ins_rk_ensemble_spectrum_destroy(ins_ensemble_spectrum_t* spectrum);
 /* Device pointers into the cache (valid until ins_rk_destroy): the stage pressure `p` and `ku[i]`. */
 /* K6 alone: out = base + Σ_q coefs[q]·ks[q] over whole vector fields, summed in index order — the stage-combination
  * broadcasts `u .= ustart; u .+= Δt A[i,j] ku[j]` (step_explicit_runge_kutta.jl:35-38) and LMWray3's state_copyto! /

@@ -99,11 +99,11 @@ from .pressure import (
     psolver_direct,
     psolver_spectral,
 )
-from .processors import (Observable, fieldsaver, get_scale_numbers, observefield, observespectrum, processor, save_vtk, spectral_stuff, timelogger,
+from .processors import (Observable, fieldsaver, get_scale_numbers, observefield, observespectrum, observespectrum_ensemble, processor, save_vtk, spectral_stuff, timelogger,
                          vtk_writer)
 from .setup import Setup, copyfield, from_numpy, scalarfield, temperature_equation, to_numpy, vectorfield, vectorfields
 from .sciml import create_right_hand_side, right_hand_side_
-from .solver import get_cfl_timestep_, get_state, solve_unsteady
+from .solver import get_cfl_timestep_, get_state, solve_unsteady, solve_unsteady_ensemble
 from .time_steppers import (
     EnsembleCache,
     ExplicitRungeKuttaMethod,
@@ -117,6 +117,8 @@ from .time_steppers import (
     ensemble_project_,
     ensemble_project_pullback_,
     ensemble_rhs_,
+    ensemble_stats,
+    get_cfl_timestep_ensemble,
     ode_method_cache,
     runge_kutta_method,
     timestep,

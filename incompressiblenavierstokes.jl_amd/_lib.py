@@ -146,6 +146,10 @@ SIGNATURES = {
     "ins_rk_ensemble_apply_bc_u_pullback_f64": (C.c_int, [vp, vp, C.c_int64, vp]),
     "ins_rk_ensemble_momentum_pullback_f64": (C.c_int, [vp, C.c_double, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, vp]),
     "ins_rk_ensemble_project_pullback_f64": (C.c_int, [vp, vp, C.c_int64, vp]),
+    "ins_rk_ensemble_stats_f64": (C.c_int, [vp, C.c_double, vp, C.c_int64, vp, vp]),
+    "ins_rk_ensemble_spectrum_create": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(vp)]),
+    "ins_rk_ensemble_spectrum_f64": (C.c_int, [vp, vp, C.c_int64, vp, vp]),
+    "ins_rk_ensemble_spectrum_destroy": (C.c_int, [vp]),
     "ins_filter_face_members_f64": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, vp]),
     "ins_filter_volume_members_f64": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, vp]),
     "ins_combine_f64": (C.c_int, [vp, vp, vp, C.c_int, c_double_p, C.POINTER(vp), vp]),

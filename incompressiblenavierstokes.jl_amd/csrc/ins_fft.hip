@@ -359,8 +359,12 @@ template <int LOGN, int NP, int SRC, typename C = double2, bool MEMBERS = false>
 __global__ __launch_bounds__(256) void k_xfwd(GridDev g, const double* __restrict__ src, C* __restrict__ out, int n1,
                                               const C* __restrict__ tw_g, int kxs, int kz0, int skel, long long mstride) {
   using T = real_t<C>;  // (C = float2: `src` points to float data — SRC 0: the float pI; SRC 5: the float velocity field)
-  static_assert(!MEMBERS || SRC == XSRC_DIV_2D, "members: the 2-D divergence source only");
-  if (MEMBERS) src += (long long)blockIdx.y * mstride;
+  static_assert(!MEMBERS || SRC == XSRC_DIV_2D || SRC == XSRC_FIELD, "members: the 2-D divergence or a 2-D velocity component");
+  // MEMBERS with XSRC_FIELD (observespectrum of an ensemble, ins_rk_ensemble_observe.hip): blockIdx.y = 2·member + component, one scalar array each
+  if (MEMBERS && SRC == XSRC_FIELD)
+    src += (long long)(blockIdx.y >> 1) * mstride + (long long)(blockIdx.y & 1) * g.sc;
+  else if (MEMBERS)
+    src += (long long)blockIdx.y * mstride;
   constexpr int N = fft_len(LOGN);
   constexpr int KXN = N / 2 + 1;
   extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -387,7 +391,7 @@ __global__ __launch_bounds__(256) void k_xfwd(GridDev g, const double* __restric
         v[q] = reinterpret_cast<const T*>(src)[i + (long long)N * (j + (long long)n1 * kz)];
       } else if (SRC == XSRC_FIELD) {
         // one padded scalar array (a velocity component): its interior volumes, ghosts stripped on the fly (observespectrum, ins_spectrum.hip)
-        v[q] = (T)src[(g.ip_lo[0] + i) + (g.ip_lo[1] + j) * g.sx[1] + (g.ip_lo[2] + kz) * g.sx[2]];
+        v[q] = (T)src[(g.ip_lo[0] + i) + (g.ip_lo[1] + j) * g.sx[1] + (MEMBERS ? 0 : (g.ip_lo[2] + kz) * g.sx[2])];
       } else if (SRC == XSRC_DIV_U32) {
         // as SRC 1, from a FLOAT velocity field (the `_f32` family solves its pressure equation with these fp64 passes, ins_f32.hip):
         // differences and metrics in double from the float values
@@ -748,6 +752,18 @@ int launch_xfwd_members(const GridDev& g, const double* src, double2* out, int n
   constexpr size_t lds = ((size_t)NP * N + N) * sizeof(double2);
   dim3 grid((n1 + 2 * NP - 1) / (2 * NP), nb);
   hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_DIV_2D, double2, true>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, 0, (int)ins_opt(OPT_INS_X_SKEL), mstride);
+  INS_LAUNCH_CHECK();
+  return INS_OK;
+}
+// the same rows from the two velocity components of every member, ghosts stripped in the load: line 2·b + a of every ky row is component a of member b
+template <int LOGN>
+int launch_xfwd_field_members(const GridDev& g, const double* src, double2* out, int n1, int nb, const double2* tw, int kxs, hipStream_t s, long long mstride) {
+  constexpr int N = fft_len(LOGN);
+  constexpr int NP = N >= 1024 ? 2 : (1024 / N > 16 ? 16 : 1024 / N);
+  static_assert(fft_r3(LOGN) == 1, "ensembles: power-of-two sides");
+  constexpr size_t lds = ((size_t)NP * N + N) * sizeof(double2);
+  dim3 grid((n1 + 2 * NP - 1) / (2 * NP), 2 * nb);
+  hipLaunchKernelGGL((k_xfwd<LOGN, NP, XSRC_FIELD, double2, true>), grid, dim3(256), lds, s, g, src, out, n1, tw, kxs, 0, 0, mstride);
   INS_LAUNCH_CHECK();
   return INS_OK;
 }
@@ -1597,6 +1613,15 @@ int ins_k_ownfft_xfwd_members(const ins_grid* G, const double* u, long long mstr
   double2* out = reinterpret_cast<double2*>(phat);
   const double2* w = reinterpret_cast<const double2*>(tw);
 #define CALL(LG) launch_xfwd_members<LG>(G->g, u, out, n1, nb, w, kxs, s, mstride)
+  INS_POW2_ONLY_SWITCH(n0, CALL)
+#undef CALL
+}
+
+// phat holds [ky][2·member + component][kxs]: the x-spectra of the velocity components of all members (ins_rk_ensemble_observe.hip)
+int ins_k_ownfft_xfwd_field_members(const ins_grid* G, const double* u, long long mstride, double* phat, int n0, int n1, int nb, const double* tw, hipStream_t s, int kxs) {
+  double2* out = reinterpret_cast<double2*>(phat);
+  const double2* w = reinterpret_cast<const double2*>(tw);
+#define CALL(LG) launch_xfwd_field_members<LG>(G->g, u, out, n1, nb, w, kxs, s, mstride)
   INS_POW2_ONLY_SWITCH(n0, CALL)
 #undef CALL
 }

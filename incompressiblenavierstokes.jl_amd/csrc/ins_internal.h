@@ -501,6 +501,26 @@ int ins_k_momentum_pullback_members_2d(const ins_grid* G, double visc, const dou
                                        long long bstride, bool acc, int nb, hipStream_t s);
 int ins_k_ownfft_xfwd_members(const ins_grid* G, const double* u, long long mstride, double* phat, int n0, int n1, int nb, const double* tw, hipStream_t s, int kxs);
 int ins_k_ownfft_xinv_members(const double* phat, double* pI, int n0, int n1, int nb, const double* tw, hipStream_t s, int kxs);
+// the x pass fed from the velocity components of all members (ghosts stripped in the load): phat holds [ky][2·member + component][kxs]
+int ins_k_ownfft_xfwd_field_members(const ins_grid* G, const double* u, long long mstride, double* phat, int n0, int n1, int nb, const double* tw, hipStream_t s,
+                                    int kxs);
+// The ensemble handle (ins_rk_ensemble.hip); the observers of ins_rk_ensemble_observe.hip keep their workgroup partials on it.
+struct ins_rk_ensemble {
+  const ins_grid* grid = nullptr;  // borrowed
+  ins_poisson* ps = nullptr;       // borrowed
+  int nstage = 0, nb = 0;
+  std::vector<double> A, c;
+  long long ms = 0;  // member stride of the work arrays: 2·ncell
+  DevBuf<double> ustart;
+  std::vector<DevBuf<double>> ku;
+  DevBuf<double> ub[2];
+  DevBuf<double> pI;     // nb · n0 · n1
+  DevBuf<double> phat;   // ROUTE_OWN2D: n1 · nb · kxs complex, [ky][member][kxs]
+  DevBuf<double> zrows;  // nb zeros: the per-row part of the symbol in the fused y solve
+  DevBuf<double> stats_part;  // ins_rk_ensemble_stats_f64: [member][chunk][3] workgroup partials, allocated on first use
+};
+// the checks an observer entry makes of one ensemble field and of the handle's box: INS_OK, an argument error, or the refusal that names the per-member calls
+int ins_rk_ensemble_check_observer(const ins_rk_ensemble* e, const char* entry, long long ustride);
 int ins_k_ownfft_xysolve2d_members(const ins_grid* G, const double* u, long long mstride, double* pI, int n0, int n1, int nb, const double* twx, const double* twy,
                                    const double* ax, const double* ay, hipStream_t s);
 int ins_k_zsolve_members(double* data, int nz, long long nl, const double* ax, int kxn, const double* ay_rows, const double* az, const double* tw, double inv_n,

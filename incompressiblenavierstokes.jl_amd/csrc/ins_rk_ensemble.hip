@@ -11,19 +11,7 @@
 #include "ins_internal.h"
 #include "ins_rk_terms.h"
 
-struct ins_rk_ensemble {
-  const ins_grid* grid = nullptr;  // borrowed
-  ins_poisson* ps = nullptr;       // borrowed
-  int nstage = 0, nb = 0;
-  std::vector<double> A, c;
-  long long ms = 0;  // member stride of the work arrays: 2·ncell
-  DevBuf<double> ustart;
-  std::vector<DevBuf<double>> ku;
-  DevBuf<double> ub[2];
-  DevBuf<double> pI;     // nb · n0 · n1
-  DevBuf<double> phat;   // ROUTE_OWN2D: n1 · nb · kxs complex, [ky][member][kxs]
-  DevBuf<double> zrows;  // nb zeros: the per-row part of the symbol in the fused y solve
-};
+// struct ins_rk_ensemble: ins_internal.h (the observers of ins_rk_ensemble_observe.hip share it)
 
 namespace {
 
@@ -75,6 +63,14 @@ int refuse_ad(const char* entry, const char* why) {
   ins_set_error("%s: %s; the member operators run the boxes of the chained 2-D loop only (all-periodic, exactly uniform, power-of-two sides 16 .. 1024, spectral "
                 "solver on its own passes, more than one stage): differentiate each trajectory on its own (ad.timestep, create_loss_post: ins_momentum_f64, "
                 "ins_project_f64 and their pullbacks ins_momentum_pullback_f64, ins_apply_bc_u_pullback_f64, ins_project_pullback_f64 on each member)", entry, why);
+  return INS_ERR_UNSUPPORTED;
+}
+
+// the same for the observers (ensemble_stats, observespectrum_ensemble): the per-member route is the single-field diagnostics
+int refuse_observe(const char* entry, const char* why) {
+  ins_set_error("%s: %s; the member observers run the boxes of the chained 2-D loop only (all-periodic, exactly uniform, power-of-two sides 16 .. 1024, spectral "
+                "solver on its own passes, more than one stage): observe each member on its own (ins_total_kinetic_energy_f64, ins_max_abs_divergence_f64, "
+                "ins_cfl_timestep_f64 and ins_spectrum_f64 on each member)", entry, why);
   return INS_ERR_UNSUPPORTED;
 }
 
@@ -170,6 +166,13 @@ int step(ins_rk_ensemble* e, double visc, double* U, long long ustride, double d
 }
 
 }  // namespace
+
+int ins_rk_ensemble_check_observer(const ins_rk_ensemble* e, const char* entry, long long ustride) {
+  const int rc = check_args(e->grid->ncell, e->nb, ustride, 0);
+  if (rc) return rc;
+  if (!supported(e->grid, e->ps, e->nstage)) return refuse_observe(entry, "an option has switched the chained 2-D loop off since the handle was created");
+  return INS_OK;
+}
 
 extern "C" int ins_dbg_rk_ensemble_args(int64_t ncell, int32_t nbatch, int64_t ustride, int32_t nsteps) { return check_args(ncell, nbatch, ustride, nsteps); }
 

@@ -289,6 +289,88 @@ def observespectrum(state, *, setup, npoint=100, a=(1 + math.sqrt(5)) / 2):
     return dict(ehat=state.map(lambda s: spec(s["u"]).cpu().numpy().copy()), κ=st["κ"])
 
 
+def _member_spectrum_positions(n, inds, row_stride, pos_of_ky):
+    """Where the library's member spectrum reads mode `m` of the K = n .÷ 2 array (0-based, column-major) inside one line set of its spectral buffer:
+    `kx + row_stride · pos_of_ky[ky]` — the x pass leaves kx in natural order, the y pass leaves ky at storage position `pos_of_ky[ky]`.  The host-side
+    restatement of the re-addressing `ins_rk_ensemble_spectrum_create` does once (csrc/ins_rk_ensemble_observe.hip)."""
+    K0 = n[0] // 2
+    inds = np.asarray(inds, dtype=np.int64)
+    return inds % K0 + row_stride * np.asarray(pos_of_ky, dtype=np.int64)[inds // K0]
+
+
+def _yfft_storage_position(n):
+    """Storage position of frequency k = 0 .. n-1 after the library's forward y pass on a power-of-two length (decimation in frequency: a radix-2 stage first
+    when log2 n is odd, then radix-4 stages; csrc/ins_fft.hip pos_of_freq)."""
+    logn = n.bit_length() - 1
+    pos = np.zeros(n, dtype=np.int64)
+    for k in range(n):
+        p, kk, L = 0, k, n
+        if logn & 1:
+            p += (kk & 1) * (L // 2)
+            kk >>= 1
+            L //= 2
+        for _ in range(logn // 2):
+            p += (kk & 3) * (L // 4)
+            kk >>= 2
+            L //= 4
+        pos[k] = p
+    return pos
+
+
+class _EnsembleSpectrum:
+    """`ins_ensemble_spectrum_t` of an `EnsembleCache` for one set of shells, with its `(B, nbin)` device result."""
+
+    def __init__(self, cache, inds):
+        from .time_steppers import _PER_MEMBER_OBSERVE
+
+        self.setup, self.nbin = cache.setup, len(inds)  # not the cache itself: it keeps this object, and a cycle would put off both destructors
+        off = np.zeros(self.nbin + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(i) for i in inds])
+        flat = np.ascontiguousarray(np.concatenate(inds) if off[-1] else np.zeros(1), dtype=np.int64)
+        self._handle = C.c_void_p()
+        lib = _lib.load()
+        rc = lib.ins_rk_ensemble_spectrum_create(cache.handle, self.nbin, off.ctypes.data_as(C.POINTER(C.c_int64)), flat.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 C.byref(self._handle))
+        if rc == -4:
+            raise NotImplementedError(f"observespectrum_ensemble: {lib.ins_last_error().decode()}; {_PER_MEMBER_OBSERVE}")
+        _lib.check(rc)
+        self.ehat = torch.zeros((cache.B, self.nbin), dtype=torch.float64, device=cache.setup.device)
+
+    def __call__(self, U, ustride):
+        from .time_steppers import _PER_MEMBER_OBSERVE
+
+        lib = _lib.load()
+        rc = lib.ins_rk_ensemble_spectrum_f64(self._handle, C.c_void_p(U.data_ptr()), ustride, C.c_void_p(self.ehat.data_ptr()), self.setup.stream)
+        if rc == -4:
+            raise NotImplementedError(f"observespectrum_ensemble: {lib.ins_last_error().decode()}; {_PER_MEMBER_OBSERVE}")
+        _lib.check(rc)
+        return self.ehat
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            try:
+                _lib.load().ins_rk_ensemble_spectrum_destroy(h)
+            except Exception:
+                pass
+
+
+def observespectrum_ensemble(cache, U, *, npoint=100, a=(1 + math.sqrt(5)) / 2):
+    """Energy spectrum of every member of `U` (`observespectrum` per member) in four launches whatever B is and without an FFT-library call
+    (`ins_rk_ensemble_spectrum_f64`): returns `dict(ehat=(B, nbin) host array, κ)`.  The spectrum handle is kept on the `EnsembleCache` per `(npoint, a)`.
+    `U` passes the checks of `timesteps_ensemble_`; its ghost volumes are not read."""
+    from .time_steppers import _ensemble_ustride
+
+    ustride = _ensemble_ustride(cache, U)
+    specs = cache.__dict__.setdefault("_spectra", {})
+    key = (int(npoint), float(a))
+    if key not in specs:
+        st = spectral_stuff(cache.setup, npoint=npoint, a=a)
+        specs[key] = (_EnsembleSpectrum(cache, st["inds"]), st["κ"])
+    spec, κ = specs[key]
+    return dict(ehat=spec(U, ustride).cpu().numpy().copy(), κ=κ)
+
+
 def get_scale_numbers(u, setup):
     """Dimensional scale numbers (operators.jl:1558-1617): uavg, ϵ, η, λ, Reλ, L, τ, Re_int.  Follows the reference's formulas as written —
     including its `uavg`, which sums ALL components' u² under each component's volume weights (D ⟨u_i u_i⟩ on a uniform grid)."""

@@ -7,8 +7,9 @@ import torch
 
 from . import _lib
 from .pressure import default_psolver
-from .setup import copyfield
-from .time_steppers import LMWray3, RKMethods, create_stepper, ode_method_cache, timestep_, timesteps_
+from .setup import copyfield, vectorfields
+from .time_steppers import (LMWray3, RKMethods, _ensemble_ustride, create_stepper, get_cfl_timestep_ensemble, ode_method_cache, timestep_, timesteps_,
+                            timesteps_ensemble_)
 
 
 def get_state(stepper):
@@ -166,3 +167,60 @@ def solve_unsteady(*, setup, tlims, ustart, tempstart=None, method=None, psolver
                 fire()
     outputs = {k: processors[k].finalize(initialized[k], lambda: state["value"]) for k in processors}
     return (stepper.u, stepper.temp, stepper.t), outputs
+
+
+def solve_unsteady_ensemble(*, cache, U, tlims, Δt=None, Δt_min=None, cfl=0.9, n_adapt_Δt=1, docopy=True, observe=None, nupdate=1):
+    """The loop of `solve_unsteady` for all members of the ensemble field `U` of an `EnsembleCache`, with ONE Δt shared by the members.
+
+    Fixed Δt: `nstep = round((tend - tstart) / Δt)` steps; the steps between the multiples of `nupdate` run as one `timesteps_ensemble_` call.
+    `Δt=None`: every `n_adapt_Δt` steps `Δt = cfl · get_cfl_timestep_ensemble(cache, U)` (the smallest CFL step of any member; one host read), raised
+    to `Δt_min` when given; the last step is clipped to `tend`.  The `n_adapt_Δt` steps of one Δt run as one native call when all of them fit before
+    `tend` (and no multiple of `nupdate` lies inside them), otherwise step by step.
+    `observe(U, t, n)` is called at n = 0 and at every multiple of `nupdate`.  `t` accumulates as `solve_unsteady` accumulates it for the same calls.
+    Returns `((U, t), Δts)` with the list of the Δt of every step.  `U` passes the checks of `timesteps_ensemble_`."""
+    _ensemble_ustride(cache, U)  # the checks of timesteps_ensemble_, before anything is copied or launched
+    n_adapt_Δt, nupdate = int(n_adapt_Δt), int(nupdate)
+    if n_adapt_Δt < 1 or nupdate < 1:
+        raise ValueError("n_adapt_Δt and nupdate are positive")
+    if docopy:
+        V = vectorfields(cache.setup, cache.B)
+        V.copy_(U)
+        U = V
+    tstart, tend = tlims
+    c_end = cache.method.c[-1]
+    t, n, Δts = tstart, 0, []
+
+    def advance(k, Δt):
+        nonlocal t, n
+        timesteps_ensemble_(cache, U, t, Δt, k)
+        t = t + (c_end * Δt if k == 1 else k * c_end * Δt)  # timestep_ / timesteps_
+        n += k
+        Δts.extend([Δt] * k)
+        if observe is not None and n % nupdate == 0:
+            observe(U, t, n)
+
+    if observe is not None:
+        observe(U, t, n)
+    if Δt is None:
+        while t < tend:
+            if n % n_adapt_Δt == 0:
+                Δt = cfl * get_cfl_timestep_ensemble(cache, U)
+                Δt = Δt if Δt_min is None else max(Δt, Δt_min)
+            Δt = min(Δt, tend - t)
+            k = n_adapt_Δt - n % n_adapt_Δt  # steps this Δt still holds for
+            if observe is not None:
+                k = min(k, nupdate - n % nupdate)
+            if k > 1 and t + k * c_end * Δt < tend:
+                advance(k, Δt)
+            else:
+                advance(1, Δt)
+    else:
+        nstep = int(round((tend - tstart) / Δt))
+        Δt = (tend - tstart) / nstep
+        g = nupdate if observe is not None else nstep
+        done = 0
+        while done < nstep:
+            k = min(g - n % g, nstep - done)
+            advance(k, Δt)
+            done += k
+    return (U, t), Δts

@@ -711,3 +711,30 @@ def timestep(method, stepper, Δt, *, θ=None):
     s2 = create_stepper(method, setup=stepper.setup, psolver=stepper.psolver, u=copyfield(stepper.u),
                         temp=None if stepper.temp is None else copyfield(stepper.temp), t=stepper.t, n=stepper.n)
     return timestep_(method, s2, Δt, θ=θ, cache=cache)
+
+
+_PER_MEMBER_OBSERVE = ("observe each member on its own: total_kinetic_energy(U[b], setup), max_abs_divergence(U[b], setup), "
+                       "get_cfl_timestep_(None, U[b], setup), observespectrum(dict(u=U[b]), setup=setup)")
+
+
+def ensemble_stats(cache, U):
+    """Kinetic energy, max |div u| and CFL step of every member in two launches whatever B is (`ins_rk_ensemble_stats_f64`): `dict(E=, maxdiv=, Δt_cfl=)` of
+    `(B,)` float64 device tensors — `total_kinetic_energy(U[b], setup)` (the same terms summed in another order), `max_abs_divergence(U[b], setup)` and
+    `get_cfl_timestep_(None, U[b], setup)` (both bitwise).  The three are views of one `(B, 3)` buffer kept on the cache, overwritten by the next call.
+    `U` is read only and has valid ghost volumes (`timesteps_ensemble_` leaves them so); it passes the checks of `timesteps_ensemble_`.  Does not
+    synchronise: reading a value on the host does."""
+    import torch
+
+    ustride = _ensemble_ustride(cache, U)
+    out = getattr(cache, "_stats", None)
+    if out is None:
+        out = cache._stats = torch.zeros((cache.B, 3), dtype=torch.float64, device=cache.setup.device)
+    _ensemble_call("ensemble_stats", "ins_rk_ensemble_stats_f64", cache, _PER_MEMBER_OBSERVE, float(cache.setup.Re), C.c_void_p(U.data_ptr()), ustride,
+                   C.c_void_p(out.data_ptr()))
+    return dict(E=out[:, 0], maxdiv=out[:, 1], Δt_cfl=out[:, 2])
+
+
+def get_cfl_timestep_ensemble(cache, U):
+    """The CFL step all members can take: the minimum over members of `get_cfl_timestep_(None, U[b], setup)`, as a Python float.  Two launches and a
+    device-side minimum, then ONE host read, whatever B is."""
+    return float(ensemble_stats(cache, U)["Δt_cfl"].min())
